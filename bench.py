@@ -5,15 +5,17 @@ One step = one discriminator sub-step (B labeled + B unlabeled + B generated row
 sub-step (B generated + B unlabeled rows), Adam included (mr_gan.py:204-213).  Workload = BASELINE
 config 2: synthetic N=65536 x D=512, K=6, batch 4096, bf16 MFMA with fp32 accumulate/master weights.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch G]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch G] [--dump-outputs DIR] [--full]
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU, RCCL).  Default: per-GPU batch stays
 4096 (weak scaling) and `value` counts batch-4096 steps summed over ranks.  --global-batch G: every rank takes G / N rows
 of each stream (strong scaling at a fixed global batch) and `value` counts global-batch steps.
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live: per-launch hipEvent pairs recorded by the
-library on the launch stream over a separate profiled pass (never the timed region's numbers re-used),
-`cpu_baseline` times the CPU oracle (a port: the reference's Theano/Keras path cannot run)
-on a bounded sample of the same workload.
+Prints ONE JSON line on rank 0.  A plain run sets up, runs W warm-up steps, times ONE block of exactly K steps
+(`value`, `ms_per_step`) and, with --dump-outputs, writes what the last timed step left behind.  --full adds the
+measurements beyond the headline, all after the headline block: the block repeated (>= 5 times, >= --min-seconds
+timed) for its spread, `roofline` measured live (per-launch hipEvent pairs recorded by the library on the launch
+stream over a separate profiled pass, never the timed region's numbers re-used), and `cpu_baseline`, which times the
+CPU oracle (a port: the reference's Theano/Keras path cannot run) on a bounded sample of the same workload.
 """
 import argparse
 import json
@@ -76,6 +78,31 @@ def build_problem(args, rank):
     X = ((X - mu) / sd).astype(np.float32)                           # StandardScaler (mr_gan.py:96-98)
     xl, yl, _ = select_labeled(X, y, args.labeled_per_class)
     return X, y, xl, yl
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, eng, E):
+    """--dump-outputs: what the last timed step leaves a caller of train_pair, as float32 DIR/<name>.npy.
+    losses.npy: loss_lab, loss_unl, train_err, loss_gen of that step (mrgan_read_metrics); gen_NN.npy / disc_NN.npy: the
+    generator's and the discriminator's fp32 master weights in Keras order.  If the weights exceed DUMP_MAX_BYTES (the wide
+    --hidden stacks), every tensor keeps the same share of its elements, at sorted flat indices drawn from a generator
+    seeded by the tensor's name, so that the sample depends only on the geometry."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"losses": np.asarray(eng.read_metrics(reset=False)[4:8], np.float32)}
+    for net, tag in ((E.NET_G, "gen"), (E.NET_D, "disc")):
+        for i, w in enumerate(eng.get_weights(net)):
+            arrays["%s_%02d" % (tag, i)] = np.asarray(w, np.float32)
+    cap = (DUMP_MAX_BYTES - 256 * len(arrays)) // 4                  # elements, less room for the .npy headers
+    total = sum(a.size for a in arrays.values())
+    for name, a in arrays.items():
+        if total > cap and a.size > 4:
+            k = max(1, a.size * cap // total)
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(args, X, xl, yl, budget_s=12.0):
@@ -198,15 +225,21 @@ def main():
                          "--hidden 4096 --batch 8192); generator / loss head stay bf16")
     ap.add_argument("--global-batch", type=int, default=0,
                     help="strong scaling: every rank takes GLOBAL / N rows of each stream (default 0: --batch rows per rank, weak scaling)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline block: repeated blocks (spread), the live per-kernel roofline pass, the CPU baseline "
+                         "and the training metrics of the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (last losses, generator and discriminator weights) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--local-stats", action="store_true",
                     help="N > 1: keep the BatchNorm / feature-matching statistics per shard (a different, labelled algorithm: 3 "
                          "fewer small collectives per step). Default: they are all-reduced, so that W ranks at B/W reproduce the "
                          "one-GPU batch-B step")
-    ap.add_argument("--profile-steps", type=int, default=10)
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="the timed block of --steps steps is repeated until this much time was timed (>= 5 repeats)")
-    ap.add_argument("--max-repeats", type=int, default=2000)
+    ap.add_argument("--profile-steps", type=int, default=10, help="with --full: steps of the profiled pass behind `roofline`")
+    ap.add_argument("--min-seconds", type=float, default=0.5,
+                    help="with --full: the timed block of --steps steps is repeated until this much time was timed (>= 5 repeats)")
+    ap.add_argument("--max-repeats", type=int, default=2000, help="with --full: at most this many blocks")
     ap.add_argument("--ablate", type=int, default=0, help="timing experiments only (see mrgan_debug_ablate)")
     ap.add_argument("--tune", action="append", default=[], metavar="KNOB=VALUE",
                     help="mrgan_set_tuning experiments, e.g. --tune 1=3 (MRGAN_TUNE_KC_CFG = 3); results stay within rounding")
@@ -331,20 +364,22 @@ def main():
 
         run(args.warmup)
         torch.cuda.synchronize(dev)
-        eng.read_metrics(reset=True)          # train_metrics below cover the timed steps only
-        # median of >= 5 repeats of the timed block, and >= 0.5 s of timed work in total whatever --steps is
-        blocks = over_ranks([timed_block()])
-        repeats = max(5, int(np.ceil(args.min_seconds / max(blocks[0], 1e-6))))
-        repeats = min(repeats, args.max_repeats)
-        blocks += over_ranks([timed_block() for _ in range(repeats - 1)])
-        elapsed = float(np.median(blocks))
-        timed_steps = repeats * args.steps
-        metrics = eng.read_metrics(reset=True)
-        rewind()
+        if args.full:
+            eng.read_metrics(reset=True)      # train_metrics below cover the timed steps only
+        # the headline: ONE block of exactly --steps steps
+        elapsed = over_ranks([timed_block()])[0]
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, eng, E)
+        if args.full:
+            # the spread of >= 5 repeats of the timed block, and >= --min-seconds of timed work in total
+            repeats = max(5, int(np.ceil(args.min_seconds / max(elapsed, 1e-6))))
+            repeats = min(repeats, args.max_repeats)
+            blocks = [elapsed] + over_ranks([timed_block() for _ in range(repeats - 1)])
+            timed_steps = repeats * args.steps
+            metrics = eng.read_metrics(reset=True)
+            rewind()
 
-        # ---- live per-kernel timing (separate pass, eager launches with hipEvent pairs) ----
-        prof = None
-        if rank == 0 or world > 1:
+            # ---- live per-kernel timing (separate pass, eager launches with hipEvent pairs) ----
             eng.profile_begin()
             for _ in range(args.profile_steps):
                 step()
@@ -358,6 +393,29 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     strong = args.global_batch > 0
     value = (1 if strong else world) * args.steps / elapsed
+    out = {
+        "metric": "GAN train steps/sec (labeled+unlabeled+G) at batch 4096", "value": round(value, 2), "unit": "steps/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
+        "dtype": args.dtype, "data": "synthetic",
+        "timing": "one block of exactly %d steps after %d warm-up steps, between barrier + synchronize brackets (max over ranks)"
+                  % (args.steps, args.warmup),
+        "config": {"workload": "%s: synthetic N=%d x D=%d, K=6, batch %d per GPU, labeled %d/class; one step = "
+                               "D sub-step (3B rows) + G sub-step (2B rows) + both Adam updates"
+                               % ("BASELINE configs[4] geometry (hidden %d x 5, generator %d x 2) on one GPU" % (args.hidden, args.g_hidden or args.hidden)
+                                  if args.hidden else "BASELINE configs[1]", args.rows, D, B, args.labeled_per_class),
+                   "global_batch": B * world, "rows_per_gpu": B, "parallelism": "dp%d" % world if world > 1 else "single",
+                   "batch_statistics": ("local_stats (per shard)" if args.local_stats else "synced over ranks") if world > 1 else "n/a",
+                   "launch": ("%s phases + RCCL all-reduce (%s gradients)" % ("hipGraph-replayed" if args.dp_graph else "eager", args.grad_dtype)) if use_dp
+                             else ("eager" if args.no_graph else "hipGraph replay")},
+    }
+    if not args.full:
+        print(json.dumps(out))
+        sys.stdout.flush()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     fl = algorithmic_flops(B, D, g_hidden, d_hidden)
     peak = PEAK_TFLOPS[args.dtype]
     ridge = peak * 1e12 / (PEAK_HBM_GBS * 1e9)                       # FLOP per byte at which the two roofs meet (312 for bf16)
@@ -440,7 +498,8 @@ def main():
     # traffic: HBM (fabric) bytes per launch of the dominant kernel / per step for the headline, numbers or null; where they come from
     # goes into traffic_source
     dom_line.update({"kernel": dom, "traffic": traffic, "traffic_unit": "bytes per launch", "avg_launch_us": round(1e3 * prof[dom][0] / max(prof[dom][1], 1), 2)})
-    step_tf = fl["total"] / (elapsed / args.steps) / 1e12
+    med = float(np.median(blocks))                                   # the median block of the repeats
+    step_tf = fl["total"] / (med / args.steps) / 1e12
     alg_bytes = sum(v[3] for v in prof.values()) / P
     # headline: the WHOLE step against the MFMA roof (650 FLOP per algorithmic byte, MFMA side), with the dominant
     # kernel's own line beside it
@@ -462,27 +521,15 @@ def main():
                  "kernel_launches": {k: v[1] / P for k, v in prof.items()},
                  "all_kernels_ms": round(all_ms, 4)},
     }
-    out = {
-        "metric": "GAN train steps/sec (labeled+unlabeled+G) at batch 4096", "value": round(value, 2), "unit": "steps/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
-        "dtype": args.dtype, "data": "synthetic",
+    out.update({
         "repeats": repeats, "timed_steps_total": timed_steps,
-        "timing": "median over %d repeats of a block of exactly %d steps, each block between barrier + synchronize brackets "
-                  "(max over ranks per block); ms per step of the blocks: min %.4f / median %.4f / max %.4f"
-                  % (repeats, args.steps, 1e3 * min(blocks) / args.steps, ms_per_step, 1e3 * max(blocks) / args.steps),
-        "config": {"workload": "%s: synthetic N=%d x D=%d, K=6, batch %d per GPU, labeled %d/class; one step = "
-                               "D sub-step (3B rows) + G sub-step (2B rows) + both Adam updates"
-                               % ("BASELINE configs[4] geometry (hidden %d x 5, generator %d x 2) on one GPU" % (args.hidden, args.g_hidden or args.hidden)
-                                  if args.hidden else "BASELINE configs[1]", args.rows, D, B, args.labeled_per_class),
-                   "global_batch": B * world, "rows_per_gpu": B, "parallelism": "dp%d" % world if world > 1 else "single",
-                   "batch_statistics": ("local_stats (per shard)" if args.local_stats else "synced over ranks") if world > 1 else "n/a",
-                   "launch": ("%s phases + RCCL all-reduce (%s gradients)" % ("hipGraph-replayed" if args.dp_graph else "eager", args.grad_dtype)) if use_dp
-                             else ("eager" if args.no_graph else "hipGraph replay")},
+        "repeated_blocks": "%d blocks of exactly %d steps (the headline block first), each between barrier + synchronize brackets "
+                           "(max over ranks per block); ms per step of the blocks: min %.4f / median %.4f / max %.4f"
+                           % (repeats, args.steps, 1e3 * min(blocks) / args.steps, 1e3 * med / args.steps, 1e3 * max(blocks) / args.steps),
         "roofline": roofline,
         "train_metrics": {"mean_loss_lab": metrics[0] / timed_steps, "mean_loss_unl": metrics[1] / timed_steps,
                           "mean_train_err": metrics[2] / timed_steps, "mean_loss_gen": metrics[3] / timed_steps},
-    }
+    })
     if world == 1 and not args.no_cpu_baseline and not args.hidden:
         out["cpu_baseline"] = cpu_baseline(args, X, xl, yl)
     print(json.dumps(out))

@@ -2,11 +2,12 @@
 # usage: bash scripts/pmc.sh <tag> "<counters>" -- <program args...>   (counters in their own pass; no trace domains)
 tag=$1; ctrs=$2; shift 3
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-rm -rf gpurun_out/pmc_$tag
-rocprofv3 --pmc $ctrs --output-format csv -d gpurun_out/pmc_$tag -- "$@" > gpurun_out/pmc_$tag.log 2>&1
+OUT=${OUT:-out}; export OUT; mkdir -p "$OUT"      # results go under $OUT (default: out/ in the repository root)
+rm -rf $OUT/pmc_$tag
+rocprofv3 --pmc $ctrs --output-format csv -d $OUT/pmc_$tag -- "$@" > $OUT/pmc_$tag.log 2>&1
 python3 - <<PY
 import csv, glob, collections
-f = glob.glob('gpurun_out/pmc_$tag/*/*counter_collection.csv')
+f = glob.glob('$OUT/pmc_$tag/*/*counter_collection.csv')
 rows = list(csv.DictReader(open(f[0])))
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); cnt = collections.Counter()
 for r in rows:

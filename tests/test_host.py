@@ -186,3 +186,47 @@ def test_bench_algorithmic_flops_match_survey():
     assert abs(fl["total"] - (d_step + g_step)) < 1e-6 * fl["total"]
     assert abs(fl["total"] / 1e9 - 129.40) < 0.01
     assert abs(d_step / 1e9 - 85.13) < 0.01 and abs(g_step / 1e9 - 44.27) < 0.01
+
+
+def test_bench_dump_outputs_stay_under_the_cap_with_a_fixed_sample(tmp_path):
+    """--dump-outputs writes every tensor in full while they fit in DUMP_MAX_BYTES; above it, each tensor becomes a sample whose
+    indices depend only on the geometry, so two runs of a wide stack stay comparable element for element."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class FakeEngine(object):
+        def __init__(self, shapes):
+            self.shapes = shapes
+
+        def read_metrics(self, reset=True):
+            return [10.0, 20.0, 30.0, 40.0, 0.5, 0.25, 0.125, 2.0]
+
+        def get_weights(self, net):
+            return [np.arange(int(np.prod(s)), dtype=np.float32).reshape(s) + net for s in self.shapes[net]]
+
+    E = type("E", (), {"NET_G": 0, "NET_D": 1})
+    small = FakeEngine({0: [(100, 50), (50,)], 1: [(16, 30), (30,), (30, 6), (6,)]})
+    bench.dump_outputs(str(tmp_path / "small"), small, E)
+    assert sorted(os.listdir(str(tmp_path / "small"))) == ["disc_00.npy", "disc_01.npy", "disc_02.npy", "disc_03.npy",
+                                                            "gen_00.npy", "gen_01.npy", "losses.npy"]
+    assert np.load(str(tmp_path / "small" / "losses.npy")).tolist() == [0.5, 0.25, 0.125, 2.0]
+    np.testing.assert_array_equal(np.load(str(tmp_path / "small" / "disc_02.npy")), small.get_weights(1)[2])
+
+    old = bench.DUMP_MAX_BYTES
+    bench.DUMP_MAX_BYTES = 40000
+    try:
+        wide = FakeEngine({0: [(100, 64), (64,)], 1: [(64, 64), (64,)]})
+        for d in ("a", "b"):
+            bench.dump_outputs(str(tmp_path / d), wide, E)
+    finally:
+        bench.DUMP_MAX_BYTES = old
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= 40000
+    for f in files:
+        a, b = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert a.dtype == np.float32
+        np.testing.assert_array_equal(a, b)
+    g0 = np.load(str(tmp_path / "a" / "gen_00.npy"))
+    assert 0 < g0.size < 6400 and np.all(np.diff(g0) > 0)       # a sorted sample of the distinct elements 0 .. 6399
