@@ -162,15 +162,15 @@ int mrgan_train_pair(mrgan_handle* h, const mrgan_disc_args* d, const mrgan_gen_
 int mrgan_pair_hint(mrgan_handle* h, int on);
 
 /* Launch-structure knobs of one handle (results stay within rounding; defaults are the measured best).  Call between
- * steps, never inside a captured pair. */
+ * steps, never inside a captured pair.  Knobs 2 and 3 are retired: mrgan_set_tuning refuses them, and their numbers are
+ * not reused. */
 enum {
     MRGAN_TUNE_CHAIN = 0,        /* 1 (default where the layer widths allow): the 256-wide tail D3..D5 + loss head of the
                                   * discriminator runs as row-block chain launches; 0: one launch per layer            */
-    MRGAN_TUNE_KC_CFG = 1,       /* forward / input-gradient tile: -1 (default) measured table; 0 64x128/3 stages,
-                                  * 1 128x128, 2 256x128, 3 256x256, 4 64x128 pipelined fragments, 5 64x128/2 stages  */
-    MRGAN_TUNE_KC_PIPE = 2,      /* 1: pipelined-fragment variant for launches with <= 1 tile per CU (default 0)       */
-    MRGAN_TUNE_KS_W8 = 3,        /* grouped weight-gradient launch: 0 (default) 8 waves, two blocks per CU; 1: 8 waves with a
-                                  * 3-stage ring, one block per CU; 2: 4 waves, two blocks per CU                           */
+    MRGAN_TUNE_KC_CFG = 1,       /* forward / input-gradient tile: -1 (default) measured table; 0 64x128 / 3 stages,
+                                  * 1 128x128 / 4 waves, 3 256x256, 5 64x128 / 2 stages, 7 128x128 / 8 waves, 9 64x64; any
+                                  * other value is an error.  Shapes a tile cannot serve fall back to 0 or 1; the fp8
+                                  * products read 1 and 3 only (128x128 / 256x256)                                         */
     MRGAN_TUNE_KS_GROUP = 4,     /* 0: one launch per weight gradient instead of one grouped launch (default 1)        */
     MRGAN_TUNE_PAIR_GEN = 5,     /* 0: mrgan_train_pair runs the two generator forwards separately (default 1: as one) */
     MRGAN_TUNE_HEAD_MFMA = 6     /* feature layers wider than 256 columns (bf16 / fp8): 1 (default) the loss head of the D

@@ -1679,9 +1679,9 @@ int mrgan_set_tuning(mrgan_handle* h, int knob, int value) {
     phase_graphs_clear(h);
     switch (knob) {
         case MRGAN_TUNE_CHAIN: h->use_chain = value != 0 && h->chain_ok; break;
-        case MRGAN_TUNE_KC_CFG: h->tune_kc_cfg = value; break;
-        case MRGAN_TUNE_KC_PIPE: h->tune_bits = (h->tune_bits & ~TUNE_BIT_KC_PIPE) | (value ? TUNE_BIT_KC_PIPE : 0); break;
-        case MRGAN_TUNE_KS_W8: h->tune_bits = (h->tune_bits & ~(TUNE_BIT_KS_W8 | TUNE_BIT_KS_W4)) | (value == 1 ? TUNE_BIT_KS_W8 : value == 2 ? TUNE_BIT_KS_W4 : 0); break;
+        case MRGAN_TUNE_KC_CFG:
+            if (!kc_cfg_supported(value)) return fail(-1, "unsupported forward / dX tile config %d", value);
+            h->tune_kc_cfg = value; break;
         case MRGAN_TUNE_KS_GROUP: h->tune_bits = (h->tune_bits & ~TUNE_BIT_NO_KS_GROUP) | (value ? 0 : TUNE_BIT_NO_KS_GROUP); break;
         case MRGAN_TUNE_PAIR_GEN: h->tune_pair_gen = value ? 1 : 0; break;
         case MRGAN_TUNE_HEAD_MFMA: h->head_wide = value != 0 && h->head_wide_ok; break;
@@ -1816,6 +1816,7 @@ int mrgan_debug_gemm_time(int op, int m, int n, int k, int nbatch, int splits, i
     const bool is_dx = op == 1 || op >= 5;
     const int a_cols = is_dx ? n : k, o_cols = is_dx ? k : n;
     if (op < 0 || op > 8) return fail(-1, "debug_gemm_time: bad op");
+    if (!kc_cfg_supported(kc_cfg)) return fail(-1, "debug_gemm_time: unsupported forward / dX tile config %d", kc_cfg);
     __bf16 *ta = nullptr, *tb = nullptr, *to = nullptr;
     uint16_t* mask = nullptr; float* slabs = nullptr; float* bias = nullptr; DevState* st = nullptr;
     HIPCHK(hipMalloc((void**)&ta, rows * std::max(a_cols, n) * 2));

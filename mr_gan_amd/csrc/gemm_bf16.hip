@@ -22,8 +22,8 @@
 // Tile order is XCD-aware: consecutive block ids round-robin over the 8 XCDs, so each XCD is handed a
 // contiguous run of tiles that share the same A row panel in its private L2.
 //
-// Block = 4 waves as 2x2.  KC: BM x 128 x 64 with BM = 128 (wave 64x64) or 64 (wave 32x64, used when the
-// 128-row grid would not fill the chip).  KS: 128 x 128 x 64.
+// KC: the block tiles and the measured table that picks one are listed in one place, above launch_kc_tile.
+// KS: 128 x 128 x 64 blocks of 8 waves (64x32 each).
 // The weight-gradient product over ragged segments (batch not a multiple of 128) keeps a register-staged
 // kernel that can zero-fill arbitrary reduction rows.
 #include <algorithm>
@@ -71,10 +71,7 @@ __device__ __forceinline__ void wait_groups(int n) {
 // Block tile BM x BNT, WM x WN waves (each (BM/WM) x (BNT/WN), as MR x NR accumulators of 32x32), NS-stage ring.
 // LDS-DMA issue is the scarce resource of this loop (~60-100 issue cycles per 1 KiB wave-instruction), so the
 // achievable MFMA share grows with the tile's arithmetic intensity BM*BNT/(BM+BNT): 64x128 -> 43, 128x128 -> 64,
-// 256x128 -> 85, 256x256 -> 128 flop per staged byte.
-// PIPE: the fragments of k-tile kt+1 are read from LDS into a second register set while the MFMAs of k-tile kt run
-// (needs k-tile kt+1 landed one iteration early, so NS >= 4 to keep two k-tiles of LDS-DMA in flight).  Meant for
-// launches with <= 1 block per CU, where no second block hides the barrier -> ds_read -> MFMA latency chain.
+// 256x256 -> 128 flop per staged byte.
 #ifdef MRGAN_STAMPS
 struct KcStamps { unsigned long long acc[6], prev, epi[5]; };      // make STAMPS=1: cycles per phase, summed over the block's tiles
 #define KC_STAMPS_PARAM , KcStamps& stamps_
@@ -85,13 +82,13 @@ struct KcStamps { unsigned long long acc[6], prev, epi[5]; };      // make STAMP
 #endif
 // one output tile (batch, tile_m, tile_n) of the product described by g: prologue, main loop, epilogue, ending with
 // the barrier after which the LDS ring may be refilled
-template <int EPI, int BM, int BNT, int WM, int WN, int NS, int VAR, bool PIPE = false>
+template <int EPI, int BM, int BNT, int WM, int WN, int NS, int VAR>
 __device__ __forceinline__ void kc_tile(const GemmArgs& g, const int batch, const int tile_m, const int tile_n, char* lds KC_STAMPS_PARAM) {
     constexpr int NW = WM * WN;
     constexpr int MR = BM / WM / 32, NR = BNT / WN / 32;   // 32x32 accumulators per wave
     constexpr int A_BYTES = BM * 128, B_BYTES = BNT * 128, STAGE = A_BYTES + B_BYTES;
     constexpr int A_INSTR = BM / 8 / NW, B_INSTR = BNT / 8 / NW;   // wave-instructions per wave per k-tile (8 rows each)
-    static_assert(NS >= 2 && NS <= 4 && (!PIPE || NS >= 3), "ring depth");
+    static_assert(NS >= 2 && NS <= 4, "ring depth");
     static_assert(MR >= 1 && NR >= 1 && A_INSTR >= 1 && B_INSTR >= 1 && BM % (8 * NW) == 0 && BNT % (8 * NW) == 0, "tile/wave layout");
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -174,95 +171,44 @@ __device__ __forceinline__ void kc_tile(const GemmArgs& g, const int batch, cons
         EpiPrefetch<MR, NR> pf;
         epilogue_prefetch<__bf16, EPI, MR, NR, VAR>(pf, g, batch, row_blk, col_blk, wm, wn, lane);
 
-        if constexpr (!PIPE) {
-            int buf = 0;
-            for (int kt = 0; kt < nk; ++kt) {
-                // vmcnt counts in issue order (stores of the previous tile and the prefetch loads are older than or as old
-                // as the group being waited for, so waiting for the group also retires them)
-                if (kt == 0) STAMP(0);                                        // tile setup + issue
-                wait_groups<A_INSTR + B_INSTR>(min(NS - 2, nk - 1 - kt));   // this wave's loads of k-tile kt have landed
-                __builtin_amdgcn_s_barrier();                                 // ... everyone's; everyone finished k-tile kt-1
-                asm volatile("" ::: "memory");
-                if (kt == 0) STAMP(1);                                        // first k-tile landed (pipeline fill)
-                if (kt + NS - 1 < nk) {                                       // refill the stage read during k-tile kt-1
-                    int nb = buf + NS - 1; if (nb >= NS) nb -= NS;
-                    issue((kt + NS - 1) * BK, nb);
-                }
-                const char* As = lds + buf * STAGE;
-                const char* Bs = As + A_BYTES;
-                buf = (buf + 1 == NS) ? 0 : buf + 1;
-                // fragments of KG k-steps are fetched as one batch ahead of their MFMAs: the LDS latency is paid once per
-                // batch (counted lgkmcnt waits) instead of once per MFMA
-                constexpr int KG = (MR + NR <= 4) ? 4 : 2;
-    #pragma unroll
-                for (int kg = 0; kg < BK / 16; kg += KG) {
-                    bf16x8 a[KG][MR], b[KG][NR];
-    #pragma unroll
-                    for (int kk = 0; kk < KG; ++kk) {
-    #pragma unroll
-                        for (int mi = 0; mi < MR; ++mi) a[kk][mi] = *(const bf16x8*)(As + kc_off((wm * MR + mi) * 32 + lr, (kg + kk) * 2 + lh));
-    #pragma unroll
-                        for (int ni = 0; ni < NR; ++ni) b[kk][ni] = *(const bf16x8*)(Bs + kc_off((wn * NR + ni) * 32 + lr, (kg + kk) * 2 + lh));
-                    }
-                    __builtin_amdgcn_sched_barrier(0);       // keep the scheduler from re-serialising read -> wait -> MFMA
-    #pragma unroll
-                    for (int kk = 0; kk < KG; ++kk)
-    #pragma unroll
-                        for (int mi = 0; mi < MR; ++mi)
-    #pragma unroll
-                            for (int ni = 0; ni < NR; ++ni)
-                                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kk][mi], b[kk][ni], acc[mi][ni], 0, 0, 0);
-                }
+        int buf = 0;
+        for (int kt = 0; kt < nk; ++kt) {
+            // vmcnt counts in issue order (stores of the previous tile and the prefetch loads are older than or as old
+            // as the group being waited for, so waiting for the group also retires them)
+            if (kt == 0) STAMP(0);                                        // tile setup + issue
+            wait_groups<A_INSTR + B_INSTR>(min(NS - 2, nk - 1 - kt));   // this wave's loads of k-tile kt have landed
+            __builtin_amdgcn_s_barrier();                                 // ... everyone's; everyone finished k-tile kt-1
+            asm volatile("" ::: "memory");
+            if (kt == 0) STAMP(1);                                        // first k-tile landed (pipeline fill)
+            if (kt + NS - 1 < nk) {                                       // refill the stage read during k-tile kt-1
+                int nb = buf + NS - 1; if (nb >= NS) nb -= NS;
+                issue((kt + NS - 1) * BK, nb);
             }
-        } else {
-            constexpr int KS = BK / 16;
-            auto read_frags = [&](bf16x8 (&fa)[KS][MR], bf16x8 (&fb)[KS][NR], int stage) {
-                const char* As = lds + stage * STAGE;
-                const char* Bs = As + A_BYTES;
+            const char* As = lds + buf * STAGE;
+            const char* Bs = As + A_BYTES;
+            buf = (buf + 1 == NS) ? 0 : buf + 1;
+            // fragments of KG k-steps are fetched as one batch ahead of their MFMAs: the LDS latency is paid once per
+            // batch (counted lgkmcnt waits) instead of once per MFMA
+            constexpr int KG = (MR + NR <= 4) ? 4 : 2;
 #pragma unroll
-                for (int kk = 0; kk < KS; ++kk) {
+            for (int kg = 0; kg < BK / 16; kg += KG) {
+                bf16x8 a[KG][MR], b[KG][NR];
 #pragma unroll
-                    for (int mi = 0; mi < MR; ++mi) fa[kk][mi] = *(const bf16x8*)(As + kc_off((wm * MR + mi) * 32 + lr, kk * 2 + lh));
+                for (int kk = 0; kk < KG; ++kk) {
 #pragma unroll
-                    for (int ni = 0; ni < NR; ++ni) fb[kk][ni] = *(const bf16x8*)(Bs + kc_off((wn * NR + ni) * 32 + lr, kk * 2 + lh));
+                    for (int mi = 0; mi < MR; ++mi) a[kk][mi] = *(const bf16x8*)(As + kc_off((wm * MR + mi) * 32 + lr, (kg + kk) * 2 + lh));
+#pragma unroll
+                    for (int ni = 0; ni < NR; ++ni) b[kk][ni] = *(const bf16x8*)(Bs + kc_off((wn * NR + ni) * 32 + lr, (kg + kk) * 2 + lh));
                 }
-            };
-            bf16x8 fa0[KS][MR], fb0[KS][NR], fa1[KS][MR], fb1[KS][NR];
-            int stg = 0;                                                    // stage of k-tile kt
-            // one pipeline step: on entry the reads of k-tile kt's fragments into (ca, cb) have been issued
-            auto step = [&](bf16x8 (&ca)[KS][MR], bf16x8 (&cb)[KS][NR], bf16x8 (&na)[KS][MR], bf16x8 (&nb)[KS][NR], int kt) {
-                int s1 = stg + 1; if (s1 >= NS) s1 -= NS;                   // stage of k-tile kt+1
-                if (kt + 1 < nk) wait_groups<A_INSTR + B_INSTR>(min(NS - 3, nk - 2 - kt));   // k-tile kt+1 has landed (this wave)
-                __builtin_amdgcn_s_barrier();     // ... everyone's; and every wave has its k-tile kt-1 fragments in registers
-                asm volatile("" ::: "memory");
-                if (kt + NS - 1 < nk) {                                     // refill the stage of k-tile kt-1
-                    int nb = stg - 1; if (nb < 0) nb += NS;
-                    issue((kt + NS - 1) * BK, nb);
-                }
-                __builtin_amdgcn_s_waitcnt(0xC07F);    // lgkmcnt(0), as a builtin so that the compiler's own wait insertion
-                                                       // knows (ca, cb) are complete (issued a whole k-tile ago)
-                __builtin_amdgcn_sched_barrier(0);
-                if (kt + 1 < nk) read_frags(na, nb, s1);
-                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);       // keep the scheduler from re-serialising read -> wait -> MFMA
 #pragma unroll
-                for (int kk = 0; kk < KS; ++kk)
+                for (int kk = 0; kk < KG; ++kk)
 #pragma unroll
                     for (int mi = 0; mi < MR; ++mi)
 #pragma unroll
                         for (int ni = 0; ni < NR; ++ni)
-                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ca[kk][mi], cb[kk][ni], acc[mi][ni], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                stg = s1;
-            };
-            if (nk > 0) {
-                wait_groups<A_INSTR + B_INSTR>(min(NS - 2, nk - 1));
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                read_frags(fa0, fb0, 0);
+                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kk][mi], b[kk][ni], acc[mi][ni], 0, 0, 0);
             }
-            int kt = 0;
-            for (; kt + 1 < nk; kt += 2) { step(fa0, fb0, fa1, fb1, kt); step(fa1, fb1, fa0, fb0, kt + 1); }
-            if (kt < nk) step(fa0, fb0, fa1, fb1, kt);
         }
         STAMP(2);               // main loop
         __syncthreads();
@@ -283,7 +229,7 @@ __device__ __forceinline__ void kc_tile(const GemmArgs& g, const int batch, cons
 
 // Persistent block: walks the tiles bid, bid + grid, ...  One tile's output stores drain while the next tile's
 // loads and MFMAs run, and co-resident blocks drift out of phase instead of all hitting HBM at once.
-template <int EPI, int BM, int BNT, int WM, int WN, int NS, int VAR, bool PIPE = false>
+template <int EPI, int BM, int BNT, int WM, int WN, int NS, int VAR>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kc_kernel(const GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char lds[];        // max(NS * STAGE, BM * BNT * 2 + scratch) bytes
     const int ntn = (g.N + BNT - 1) / BNT, ntm = (g.M + BM - 1) / BM;
@@ -301,7 +247,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kc_kernel(const GemmAr
             const int grp = rem / (4 * ntn), in = rem - grp * (4 * ntn);
             tile_m = grp * 4 + (in & 3); tile_n = in >> 2;
         } else { tile_m = rem / ntn; tile_n = rem - tile_m * ntn; }
-        kc_tile<EPI, BM, BNT, WM, WN, NS, VAR, PIPE>(g, batch, tile_m, tile_n, lds KC_STAMPS_ARG);
+        kc_tile<EPI, BM, BNT, WM, WN, NS, VAR>(g, batch, tile_m, tile_n, lds KC_STAMPS_ARG);
     }
 #ifdef MRGAN_STAMPS
     if (g.e.slab && threadIdx.x == 0)
@@ -314,11 +260,11 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kc_kernel(const GemmAr
 
 thread_local const char* g_last_kernel = "";
 
-template <int EPI, int BM, int BNT, int WM, int WN, int NS, int VAR, bool PIPE = false>
+template <int EPI, int BM, int BNT, int WM, int WN, int NS, int VAR>
 int launch_kc(const GemmArgs& g, hipStream_t s) {
     static const std::string name = "gemm_bf16_kc_kernel<" + std::to_string(EPI) + ", " + std::to_string(BM) + ", " +
                                     std::to_string(BNT) + ", " + std::to_string(WM) + ", " + std::to_string(WN) + ", " +
-                                    std::to_string(NS) + ", " + std::to_string(VAR) + (PIPE ? ", true>" : ", false>");
+                                    std::to_string(NS) + ", " + std::to_string(VAR) + ">";
     g_last_kernel = name.c_str();
     constexpr int STAGE = BM * 128 + BNT * 128;
     // staged output tile + column-sum scratch (+ the tile of e.h for the DX epilogues that read it)
@@ -326,7 +272,7 @@ int launch_kc(const GemmArgs& g, hipStream_t s) {
     constexpr int LDS = (NS * STAGE > OUT ? NS * STAGE : OUT) + ((EPI == EPI_DX && (VAR & VAR_ACT_MASK) != ACT_RELU) ? BM * BNT * 2 : 0);
     static_assert(LDS <= 160 * 1024, "LDS budget");
     static DeviceOnce attr;
-    auto kern = gemm_bf16_kc_kernel<EPI, BM, BNT, WM, WN, NS, VAR, PIPE>;
+    auto kern = gemm_bf16_kc_kernel<EPI, BM, BNT, WM, WN, NS, VAR>;
     if (attr.first()) {
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return -2;
         attr.mark();
@@ -610,15 +556,15 @@ __global__ void tr_probe_kernel(unsigned short* out) {
 }  // namespace
 
 // epilogue variants compiled for the bf16 path (anything else is a host-side error)
-// tile configs: 0 = 64x128 / 4 waves / 3 stages ; 1 = 128x128 / 4 waves / 2 stages ; 2 = 256x128 / 8 waves / 2 stages ;
-//               3 = 256x256 / 8 waves / 2 stages ; 4 = cfg 0 with pipelined fragments ; 5 = 64x128 / 4 waves / 2 stages
-//               (three blocks per CU) ; 6 = 128x256 / 8 waves ; 7 = 128x128 / EIGHT waves of 64x32 / 2 stages ; 9 = 64x64 / 4 waves /
-//               3 stages.
-//               mrgan_set_tuning(MRGAN_TUNE_KC_CFG) forces one; default picks by grid size.
+// Block tiles (BM x BN, waves, LDS ring stages), by config number:
+//   0 = 64x128, 4 waves of 32x64, 3 stages      1 = 128x128, 4 waves of 64x64, 2 stages   3 = 256x256, 8 waves of 128x64, 2 stages
+//   5 = 64x128, 4 waves, 2 stages (three blocks per CU)   7 = 128x128, 8 waves of 64x32, 2 stages   9 = 64x64, 4 waves of 32x32, 3 stages
+// The default (-1) picks one by the measured table below; mrgan_set_tuning(MRGAN_TUNE_KC_CFG) forces one (kc_cfg_supported).
+// Shape fallbacks apply to both: 3 / 5 / 7 need N % 128 == 0 (else 0), 3 needs N % 256 == 0 (else 1), and the DX epilogues
+// that stage a tile of e.h in LDS only exist for 0, 1 and 9 (3 / 5 / 7 become 1).
 template <int EPI, int VAR>
 static int launch_kc_tile(const GemmArgs& g, hipStream_t s) {
-    const int forced = g.e.tune_kc_cfg;
-    int cfg = forced;
+    int cfg = g.e.tune_kc_cfg;
     if (cfg < 0) {
         // measured on MI355X (scripts/gemm_bench.py): bigger tiles win once they still give >= ~1.5 blocks per CU
         const int t128 = ceil_div(g.M, 128) * ceil_div(g.N, 128) * g.nbatch;
@@ -642,24 +588,16 @@ static int launch_kc_tile(const GemmArgs& g, hipStream_t s) {
         if (cfg == 0 && ceil_div(g.M, 64) * ceil_div(g.N, 128) * g.nbatch <= 256) cfg = 9;
     }
     if (cfg >= 2 && cfg != 9 && (g.N % 128) != 0) cfg = 0;
-    if (cfg == 6 && (g.N % 256) != 0) cfg = 1;
-    // DX epilogues that may stage a tile of e.h in LDS (softplus derivative, xhat sums) only exist for the small tiles
+    if (cfg == 3 && (g.N % 256) != 0) cfg = 1;
     constexpr bool H_TILE = EPI == EPI_DX && (VAR & VAR_ACT_MASK) != ACT_RELU;
     if (H_TILE && cfg >= 2 && cfg != 9) cfg = 1;
     if constexpr (!H_TILE) {
         if (cfg == 7) return launch_kc<EPI, 128, 128, 2, 4, 2, VAR>(g, s);
-        if (cfg == 6 && (g.N % 256) == 0) return launch_kc<EPI, 128, 256, 2, 4, 2, VAR>(g, s);      // 8 waves of 64x64
-        if (cfg == 2) return launch_kc<EPI, 256, 128, 4, 2, 2, VAR>(g, s);
-        if (cfg == 3) return (g.N % 256) == 0 ? launch_kc<EPI, 256, 256, 2, 4, 2, VAR>(g, s) : launch_kc<EPI, 256, 128, 4, 2, 2, VAR>(g, s);
+        if (cfg == 3) return launch_kc<EPI, 256, 256, 2, 4, 2, VAR>(g, s);
     }
     if (cfg == 9) return launch_kc<EPI, 64, 64, 2, 2, 3, VAR>(g, s);       // 48 KiB ring: three blocks per CU
     if (cfg == 1) return launch_kc<EPI, 128, 128, 2, 2, 2, VAR>(g, s);
     if (cfg == 5) return launch_kc<EPI, 64, 128, 2, 2, 2, VAR>(g, s);      // 48 KiB ring: three blocks per CU
-    // cfg 4 / TUNE_BIT_KC_PIPE (launches with at most one 64x128 tile per CU): pipelined fragments, 4-stage ring.
-    // Measured no faster than cfg 0 on MI355X -- these launches are bound by the L2 -> LDS fill, not by the LDS -> MFMA chain.
-    const int pipe = g.e.tune_bits & TUNE_BIT_KC_PIPE;
-    const int t64 = ceil_div(g.M, 64) * ceil_div(g.N, 128) * g.nbatch;
-    if (cfg == 4 || (forced < 0 && pipe && t64 <= 256)) return launch_kc<EPI, 64, 128, 2, 2, 4, VAR, true>(g, s);
     return launch_kc<EPI, 64, 128, 2, 2, 3, VAR>(g, s);
 }
 
@@ -710,34 +648,15 @@ int launch_gemm_bf16_dw_group(const GemmArgs* gs, int n, hipStream_t s, const ch
     // blocks = 16 waves per CU: 58.7 us; 4 waves of 64x64, two blocks per CU (round 2's default, 1.0 instead of 1.5 transposing
     // reads per MFMA): 64.7 us; 8 waves with a 3-stage ring, one block per CU: 89 us.  More resident waves hide the
     // barrier -> LDS read -> MFMA chain; the LDS read rate is not the limit at two blocks per CU.
-    // MRGAN_TUNE_KS_W8: 0 (default) the first, 1 the third, 2 the second.
-    constexpr int STAGE = 2 * 64 * 256;
-    static DeviceOnce attr8, attr4, attr16;
-    if (gs[0].e.tune_bits & TUNE_BIT_KS_W8) {
-        auto kern = gemm_bf16_ks_group_kernel<3, 2, 4>;
-        if (attr8.first()) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * STAGE) != hipSuccess) return -2;
-            attr8.mark();
-        }
-        MRGAN_LAUNCH(kern, dim3(total), dim3(512), 3 * STAGE, s, grp);
-        if (kname) *kname = "gemm_bf16_ks_group_kernel<3, 2, 4>";
-    } else if (gs[0].e.tune_bits & TUNE_BIT_KS_W4) {
-        auto kern = gemm_bf16_ks_group_kernel<2, 2, 2>;
-        if (attr4.first()) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE) != hipSuccess) return -2;
-            attr4.mark();
-        }
-        MRGAN_LAUNCH(kern, dim3(total), dim3(256), 2 * STAGE, s, grp);
-        if (kname) *kname = "gemm_bf16_ks_group_kernel<2, 2, 2>";
-    } else {
-        auto kern = gemm_bf16_ks_group_kernel<2, 2, 4>;
-        if (attr16.first()) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE) != hipSuccess) return -2;
-            attr16.mark();
-        }
-        MRGAN_LAUNCH(kern, dim3(total), dim3(512), 2 * STAGE, s, grp);
-        if (kname) *kname = "gemm_bf16_ks_group_kernel<2, 2, 4>";
+    constexpr int STAGE = 2 * 64 * 256, LDS = 2 * STAGE;
+    static DeviceOnce attr;
+    auto kern = gemm_bf16_ks_group_kernel<2, 2, 4>;
+    if (attr.first()) {
+        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return -2;
+        attr.mark();
     }
+    MRGAN_LAUNCH(kern, dim3(total), dim3(512), LDS, s, grp);
+    if (kname) *kname = "gemm_bf16_ks_group_kernel<2, 2, 4>";
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -745,10 +664,7 @@ int launch_gemm_bf16(int epi, const GemmArgs& g, hipStream_t s, const char** kna
     int r = 0;
     if (epi == EPI_SLAB) {
         if (g.a_si != 1 || g.b_sj != 1) return -3;
-        const bool dense_k = g.nbatch == 1 && (g.K % BK) == 0 && (g.kchunk % BK) == 0 &&
-                             (g.seg_rows >= g.seg_stride || g.K <= g.seg_rows) &&
-                             (long)g.K * g.a_sk * 2 < (1L << 31) && (long)g.K * g.b_sk * 2 < (1L << 31);
-        if (dense_k) {
+        if (ks_dense_k(g)) {
             r = launch_ks_fast<3, 2, 4>(g, s);      // single product: 8 waves (64x32 each), 3-stage ring
         } else {
             dim3 grid(ceil_div(g.N, BN), ceil_div(g.M, 128), g.nbatch * g.splits);

@@ -672,6 +672,59 @@ def test_fp8_large_tiles_equal_small_tiles():
         assert rel_err(a, b) < 1e-3, ("dG", i, rel_err(a, b))       # (the bf16 generator kernels change their tile with the knob too)
 
 
+def test_forced_kc_tiles_equal_the_measured_table():
+    """every forward / dX tile MRGAN_TUNE_KC_CFG accepts, forced on one bf16 D and one G sub-step, against the measured table's
+    choice.  Each output element accumulates its k-steps in the same order on every tile, but the BatchNorm statistics of the
+    generator are per-64-row column sums that a 128- or 256-row tile adds in another order: with 1 / 3 / 7 forced the generated
+    rows differ from the default's by bf16 roundings (measured: losses 6e-6, D gradients 2.2e-3, G gradients 1e-2; 0 / 5 / 9
+    are bit-identical in the D sub-step at this shape).  The G sub-step starts from the default run's discriminator weights (Adam turns rounding-level gradient
+    differences into +-lr steps); its softplus / BatchNorm dX launches take the H_TILE fallback (forced 3 / 5 / 7 run 128x128).
+    Forced 3 runs 256x256 where N allows it (D1: 1024 columns).  Unsupported values and the retired knobs 2 and 3 are refused."""
+    from mr_gan_amd import engine as E
+    case = Case(D=512, B=1024, steps=1, device_z=True)
+    res, wd = [], None
+    for cfg in (-1, 0, 1, 3, 5, 7, 9):
+        eng = _engine(512, 1024, 1, flags=E.FLAG_FLAT_GRADS)
+        eng.set_tuning(E.TUNE_KC_CFG, cfg)
+        _load(eng, case)
+        da = E.Engine.disc_args(_t(case.x_lab[0]), _t(case.labels[0], torch.int32), _t(case.x_unl[0]))
+        eng.disc_step(da, E.D_GEN, E.D_MAIN, want_outputs=False)
+        gd = eng.get_slot(E.NET_D, 2)
+        out = eng.disc_step(da, E.D_ADAM, E.D_ADAM)
+        if wd is None:
+            wd = eng.get_weights(E.NET_D)
+        eng.set_weights(E.NET_D, wd)
+        ga = E.Engine.gen_args(_t(case.x_unl2[0]))
+        eng.gen_step(ga, E.G_GEN, E.G_TAIL, want_outputs=False)
+        gg = eng.get_slot(E.NET_G, 2)
+        res.append((cfg, gd, out, gg, eng.gen_step(ga, E.G_ADAM, E.G_ADAM)))
+        if cfg == -1:
+            for bad in (-2, 2, 4, 6, 8, 10):
+                with pytest.raises(E.MrganError):
+                    eng.set_tuning(E.TUNE_KC_CFG, bad)
+            for knob in (2, 3):
+                with pytest.raises(E.MrganError):
+                    eng.set_tuning(knob, 0)
+        eng.close()
+    with pytest.raises(E.MrganError):
+        E.debug_gemm_time(0, 256, 128, 128, reps=1, kc_cfg=2)
+    _, gd0, out0, gg0, lg0 = res[0]
+    for cfg, gd, out, gg, lg in res[1:]:
+        print("cfg %d: losses %.1e, dD %.1e, dG %s, loss_gen %.1e" % (
+            cfg, np.max(np.abs(np.array(out) - np.array(out0))), max(rel_err(a, b) for a, b in zip(gd, gd0)),
+            ["%.1e" % rel_err(a, b) for a, b in zip(gg, gg0)], abs(lg - lg0) / abs(lg0)))
+    for cfg, gd, out, gg, lg in res[1:]:
+        np.testing.assert_allclose(out, out0, rtol=1e-5, atol=1e-6, err_msg="cfg %d" % cfg)
+        for i, (a, b) in enumerate(zip(gd, gd0)):
+            assert rel_err(a, b) < 5e-3, ("dD", cfg, i, rel_err(a, b))
+        for i, (a, b) in enumerate(zip(gg, gg0)):
+            # (b1 sits in front of the BatchNorm: its true gradient is 0 and what is stored is rounding noise, so it is held to
+            #  the scale of dW1 instead of its own)
+            scale = np.abs(gg0[0]).max() if i == 1 else np.abs(b).max()
+            assert np.abs(a - b).max() < 3e-2 * scale, ("dG", cfg, i, np.abs(a - b).max() / scale)
+        assert abs(lg - lg0) < 1e-3 * abs(lg0), (cfg, lg, lg0)
+
+
 def test_wide_stack_fp32_matches_oracle():
     """the same wide geometry through the fp32 MFMA path at a small batch, against the fp64 restatement"""
     _grad_parity(64, 64, 0, None, tol=5e-5, tol_loss=1e-5, d_hidden=(1024, 512, 512, 320, 320), g_hidden=(320, 576), eval_first=False)

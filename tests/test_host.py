@@ -134,6 +134,16 @@ int main(void) {
                     ctypes.sizeof(E.DiscArgs), ctypes.sizeof(E.GenArgs)]
 
 
+def test_tuning_knobs_match_header():
+    """engine.TUNE_* carry the values of the MRGAN_TUNE_* enumerators, and nothing else (retired knob numbers stay retired)"""
+    from mr_gan_amd import engine as E
+    src = open(os.path.join(ROOT, "include", "mrgan_abi.h")).read()
+    header = {m.group(1): int(m.group(2)) for m in re.finditer(r"\bMRGAN_(TUNE_[A-Z0-9_]+)\s*=\s*(\d+)", src)}
+    python = {n: getattr(E, n) for n in dir(E) if n.startswith("TUNE_")}
+    assert len(header) >= 5
+    assert python == header
+
+
 def test_default_config_and_workspace_size_without_gpu():
     from mr_gan_amd import engine as E
     cfg = E.default_config(512, 4096)
