@@ -145,10 +145,6 @@ struct mrgan_handle {
 
     // graph replay of (D step, G step)
     hipGraphExec_t graph_exec; bool graph_ready; int graph_cur; mrgan_disc_args graph_d; mrgan_gen_args graph_g;
-    // graph replay of phase ranges (data-parallel hosts: the kernels between two collectives), see phase_graph_run
-    struct PhaseState { int cur, pair_gen, gen_ready, real_staged, xbase, gen_seg, fp8_kind; };
-    struct PhaseGraph { int kind, p0, p1; PhaseState pre, post; mrgan_disc_args d; mrgan_gen_args g; hipGraphExec_t exec; };
-    std::vector<PhaseGraph> phase_graphs;
 };
 
 namespace {
@@ -1293,56 +1289,23 @@ int eval_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, cons
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Phase-range graphs.  A data-parallel host calls the sub-steps phase by phase, with its collectives in between
-// (mr_gan_amd/dist.py); launched eagerly those 22 kernels cost 7 % more than the whole-pair graph of mrgan_train_pair (launch
-// gaps).  With MRGAN_FLAG_GRAPH every phase range [p0, p1] of a stream-mode sub-step is captured once and replayed: kernel
-// arguments never change between steps (DevState slots, device-side batch counter), and the host-side state a phase reads and
-// leaves behind (slot parity, the pairing flags, the generator view) is part of the cache key / restored from the snapshot
-// taken when the range was captured.
+// fp8 calibration of a sub-step kind (0 = D, 1 = G): dry passes (forward + backward phases, no update) between begin and
+// done, each followed by end_pass, settle the delayed scales, one layer of the gradient chain per pass.  Whole sub-steps run
+// them by themselves, phase-wise hosts through mrgan_fp8_calibration.  The G sub-step's feature-matching kernel adds its loss
+// to the epoch accumulator, which the dry passes must leave alone.
 // ---------------------------------------------------------------------------------------------------
-mrgan_handle::PhaseState phase_snap(const mrgan_handle* h) {
-    return mrgan_handle::PhaseState{h->cur, h->pair_gen, h->gen_ready, h->real_staged, h->xbase, h->gen_seg, h->fp8_kind};
+int fp8_cal_begin(mrgan_handle* h, int kind, hipStream_t s) {
+    h->fp8_cal[kind] = 2;                         // in progress: the phases run as they are
+    if (kind == 1) HIPCHK(hipMemcpyAsync(h->accum_save, h->accum, 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
 }
-void phase_restore(mrgan_handle* h, const mrgan_handle::PhaseState& st) {
-    set_gen_view(h, st.gen_seg);
-    h->cur = st.cur; h->pair_gen = st.pair_gen; h->gen_ready = st.gen_ready; h->real_staged = st.real_staged;
-    h->xbase = st.xbase; h->fp8_kind = st.fp8_kind;
+int fp8_cal_end_pass(mrgan_handle* h, int /*kind*/, hipStream_t s) {
+    CHK(fp8_update_scales(h, s));
+    return 0;
 }
-void phase_graphs_clear(mrgan_handle* h) {
-    for (auto& g : h->phase_graphs) hipGraphExecDestroy(g.exec);
-    h->phase_graphs.clear();
-}
-// kind 0: disc phases of `d`; kind 1: gen phases of `g`.  Returns 1 when the range was not graphed (caller runs it eagerly).
-template <typename Run>
-int phase_graph_run(mrgan_handle* h, int kind, int p0, int p1, const mrgan_disc_args* d, const mrgan_gen_args* g, hipStream_t s, Run run) {
-    const bool want = (h->cfg.flags & MRGAN_FLAG_GRAPH) && h->flat_grads && !h->prof && !h->pair_g &&
-                      (kind == 0 ? d->stream_mode : g->stream_mode) && (!h->fp8 || (h->fp8_cal[0] == 1 && h->fp8_cal[1] == 1));
-    if (!want) return 1;
-    const mrgan_handle::PhaseState pre = phase_snap(h);
-    for (auto& pg : h->phase_graphs) {
-        if (pg.kind != kind || pg.p0 != p0 || pg.p1 != p1 || memcmp(&pg.pre, &pre, sizeof pre) != 0) continue;
-        if (kind == 0 ? memcmp(&pg.d, d, sizeof *d) != 0 : memcmp(&pg.g, g, sizeof *g) != 0) continue;
-        phase_restore(h, pg.post);
-        HIPCHK(hipGraphLaunch(pg.exec, s));
-        return 0;
-    }
-    if (h->phase_graphs.size() >= 64) phase_graphs_clear(h);           // (argument pointers keep changing: start over)
-    mrgan_handle::PhaseGraph pg;
-    memset(&pg, 0, sizeof pg);
-    pg.kind = kind; pg.p0 = p0; pg.p1 = p1; pg.pre = pre;
-    if (kind == 0) pg.d = *d; else pg.g = *g;
-    hipGraph_t graph = nullptr;
-    HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int r = run();
-    const hipError_t e = hipStreamEndCapture(s, &graph);
-    if (r) { if (graph) hipGraphDestroy(graph); return r; }
-    if (e != hipSuccess) return fail(-10, "hipStreamEndCapture (phase range): %s", hipGetErrorString(e));
-    const hipError_t e2 = hipGraphInstantiate(&pg.exec, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    if (e2 != hipSuccess) return fail(-10, "hipGraphInstantiate (phase range): %s", hipGetErrorString(e2));
-    pg.post = phase_snap(h);
-    h->phase_graphs.push_back(pg);
-    HIPCHK(hipGraphLaunch(pg.exec, s));
+int fp8_cal_done(mrgan_handle* h, int kind, hipStream_t s) {
+    if (kind == 1) HIPCHK(hipMemcpyAsync(h->accum, h->accum_save, 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    h->fp8_cal[kind] = 1;
     return 0;
 }
 
@@ -1447,7 +1410,6 @@ int mrgan_create(const mrgan_config* cfg, void* workspace, size_t bytes, mrgan_s
 int mrgan_destroy(mrgan_handle* h) {
     if (!h) return 0;
     if (h->graph_exec) hipGraphExecDestroy(h->graph_exec);
-    phase_graphs_clear(h);
     if (h->own_ws && h->ws) hipFree(h->ws);
     delete h;
     return 0;
@@ -1532,17 +1494,15 @@ int mrgan_disc_step(mrgan_handle* h, const mrgan_disc_args* a, int p0, int p1, f
     if (h->fp8 && p0 == 0 && !h->fp8_cal[0] && p1 < MRGAN_D_NPHASES - 1 && h->sync_stats)
         return fail(-3, "fp8 with synchronised statistics: a phase-wise host runs the calibration passes itself (mrgan_fp8_calibration)");
     if (h->fp8 && p0 == 0 && !h->fp8_cal[0]) {
-        // first D sub-step of an fp8 handle: dry passes (forward + backward, no update) settle the delayed scales, one
-        // layer of the gradient chain per pass
+        // first D sub-step of an fp8 handle: calibrate with dry passes
+        CHK(fp8_cal_begin(h, 0, s));
         for (int i = 0; i < FP8_DRY_PASSES; ++i) {
             for (int p = MRGAN_D_GEN; p <= MRGAN_D_MAIN; ++p) { r = disc_phase(h, a, p, s); if (r) return r; }
-            CHK(fp8_update_scales(h, s));
+            CHK(fp8_cal_end_pass(h, 0, s));
         }
-        h->fp8_cal[0] = 1;
+        CHK(fp8_cal_done(h, 0, s));
     }
-    r = phase_graph_run(h, 0, p0, p1, a, nullptr, s, [&]() { int rr = 0; for (int p = p0; p <= p1 && !rr; ++p) rr = disc_phase(h, a, p, s); return rr; });
-    if (r < 0) return r;
-    if (r == 1) for (int p = p0; p <= p1; ++p) { r = disc_phase(h, a, p, s); if (r) return r; }
+    for (int p = p0; p <= p1; ++p) { r = disc_phase(h, a, p, s); if (r) return r; }
     if (out3) {
         HIPCHK(hipMemcpyAsync(out3, h->step_out, 3 * sizeof(float), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
@@ -1559,19 +1519,15 @@ int mrgan_gen_step(mrgan_handle* h, const mrgan_gen_args* a, int p0, int p1, flo
     if (h->fp8 && p0 == 0 && !h->fp8_cal[1] && p1 < MRGAN_G_NPHASES - 1 && h->sync_stats)
         return fail(-3, "fp8 with synchronised statistics: a phase-wise host runs the calibration passes itself (mrgan_fp8_calibration)");
     if (h->fp8 && p0 == 0 && !h->fp8_cal[1]) {
-        // same for the G sub-step's tensors (its own slots: the feature-matching gradient has another scale than the D loss's);
-        // the feature-matching kernel adds its loss to the epoch accumulator, which the dry passes must leave alone
-        HIPCHK(hipMemcpyAsync(h->accum_save, h->accum, 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        // same for the G sub-step's tensors (its own slots: the feature-matching gradient has another scale than the D loss's)
+        CHK(fp8_cal_begin(h, 1, s));
         for (int i = 0; i < FP8_DRY_PASSES; ++i) {
             for (int p = MRGAN_G_GEN; p <= MRGAN_G_BWD; ++p) { r = gen_phase(h, a, p, s); if (r) return r; }
-            CHK(fp8_update_scales(h, s));
+            CHK(fp8_cal_end_pass(h, 1, s));
         }
-        HIPCHK(hipMemcpyAsync(h->accum, h->accum_save, 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        h->fp8_cal[1] = 1;
+        CHK(fp8_cal_done(h, 1, s));
     }
-    r = phase_graph_run(h, 1, p0, p1, nullptr, a, s, [&]() { int rr = 0; for (int p = p0; p <= p1 && !rr; ++p) rr = gen_phase(h, a, p, s); return rr; });
-    if (r < 0) return r;
-    if (r == 1) for (int p = p0; p <= p1; ++p) { r = gen_phase(h, a, p, s); if (r) return r; }
+    for (int p = p0; p <= p1; ++p) { r = gen_phase(h, a, p, s); if (r) return r; }
     if (out1) {
         HIPCHK(hipMemcpyAsync(out1, h->step_out + 3, sizeof(float), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
@@ -1585,15 +1541,9 @@ int mrgan_fp8_calibration(mrgan_handle* h, int kind, int action, mrgan_stream st
     if (action == MRGAN_FP8_CAL_QUERY) return (!h->fp8 || h->fp8_cal[kind] == 1) ? 1 : 0;
     if (!h->fp8) return 0;
     switch (action) {
-        case MRGAN_FP8_CAL_BEGIN:
-            h->fp8_cal[kind] = 2;                     // in progress: the phases run as they are
-            if (kind == 1) HIPCHK(hipMemcpyAsync(h->accum_save, h->accum, 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
-            return 0;
-        case MRGAN_FP8_CAL_END_PASS: CHK(fp8_update_scales(h, s)); return 0;
-        case MRGAN_FP8_CAL_DONE:
-            if (kind == 1) HIPCHK(hipMemcpyAsync(h->accum, h->accum_save, 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
-            h->fp8_cal[kind] = 1;
-            return 0;
+        case MRGAN_FP8_CAL_BEGIN: return fp8_cal_begin(h, kind, s);
+        case MRGAN_FP8_CAL_END_PASS: return fp8_cal_end_pass(h, kind, s);
+        case MRGAN_FP8_CAL_DONE: return fp8_cal_done(h, kind, s);
         default: return fail(-1, "fp8_calibration: unknown action %d", action);
     }
 }
@@ -1676,7 +1626,6 @@ int mrgan_train_pair(mrgan_handle* h, const mrgan_disc_args* d, const mrgan_gen_
 int mrgan_set_tuning(mrgan_handle* h, int knob, int value) {
     if (!h) return fail(-1, "null handle");
     if (h->graph_exec) { hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; h->graph_ready = false; }   // launches change
-    phase_graphs_clear(h);
     switch (knob) {
         case MRGAN_TUNE_CHAIN: h->use_chain = value != 0 && h->chain_ok; break;
         case MRGAN_TUNE_KC_CFG:
@@ -1703,8 +1652,15 @@ int mrgan_region(mrgan_handle* h, int region, void** ptr, size_t* bytes) {
         case MRGAN_REGION_BN_STATS: *ptr = h->r_bn_stats; *bytes = 4 * n1 * 4; break;
         case MRGAN_REGION_FM_MOMENTS: *ptr = h->r_fm; *bytes = 2 * (size_t)h->Fp * 4; break;
         case MRGAN_REGION_BN_BWD: *ptr = h->r_bn_bwd; *bytes = 2 * n1 * 4; break;
-        case MRGAN_REGION_GRAD_D: *ptr = h->flat_d; *bytes = (h->flat_d_n + 4) * 4; break;
-        case MRGAN_REGION_GRAD_G: *ptr = h->flat_g; *bytes = (h->flat_g_n + 4) * 4; break;
+        case MRGAN_REGION_GRAD_D: case MRGAN_REGION_GRAD_G: {
+            // the reduce / Adam phases of a bfloat16-payload handle never touch the fp32 bodies: exchanging them would leave
+            // the replicas' gradients unreduced
+            if (h->flat16_d) return fail(-3, "region %d: the gradients of this handle travel as bfloat16 (MRGAN_FLAG_GRAD_BF16): "
+                                             "all-reduce MRGAN_REGION_GRAD_*_BF16 and MRGAN_REGION_TAIL_*", region);
+            const bool d = region == MRGAN_REGION_GRAD_D;
+            *ptr = d ? h->flat_d : h->flat_g; *bytes = ((d ? h->flat_d_n : h->flat_g_n) + 4) * 4;
+            break;
+        }
         case MRGAN_REGION_WORKSPACE: *ptr = h->ws; *bytes = h->ws_bytes; break;
         case MRGAN_REGION_GRAD_D_BF16: case MRGAN_REGION_GRAD_G_BF16: {
             if (!h->flat16_d) return fail(-3, "the bfloat16 gradient regions exist with MRGAN_FLAG_GRAD_BF16 only");
@@ -1787,7 +1743,6 @@ int mrgan_debug_noise(mrgan_handle* h, uint32_t site, uint32_t seg, uint32_t ste
 int mrgan_debug_ablate(mrgan_handle* h, int bits) {
     if (!h) return fail(-1, "null handle");
     if (h->graph_exec) { hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; h->graph_ready = false; }
-    phase_graphs_clear(h);
     h->ablate = bits;
     return 0;
 }

@@ -20,8 +20,11 @@ from mr_gan_amd import engine as E
 
 
 class PhaseBackend(object):
-    """What DataParallel needs from an engine: run phases, expose the exchange regions as tensors.
+    """What DataParallel needs from an engine: run phases, name the tensors to all-reduce (sum, in place) at each exchange
+    point, and the payload of the gradient exchanges (grad_dtype: 'bf16' or None = fp32), which the backend alone decides.
     Engine satisfies it; the CPU tests supply an oracle-backed stand-in to exercise the protocol."""
+
+    grad_dtype = None
 
     def disc_phase(self, args, phase):
         raise NotImplementedError
@@ -32,10 +35,14 @@ class PhaseBackend(object):
     def region(self, which):
         raise NotImplementedError
 
+    def exchange_regions(self, which):
+        return E.exchange_regions(self.region, self.grad_dtype, which)
+
 
 class EngineBackend(PhaseBackend):
     def __init__(self, engine):
         self.engine = engine
+        self.grad_dtype = engine.grad_dtype
 
     def disc_phase(self, args, phase):
         return self.engine.disc_step(args, phase, phase, want_outputs=False)
@@ -46,6 +53,9 @@ class EngineBackend(PhaseBackend):
     def region(self, which):
         return self.engine.region(which)
 
+    def exchange_regions(self, which):
+        return self.engine.exchange_regions(which)
+
     def pair_hint(self, on=True):
         self.engine.pair_hint(on)
 
@@ -54,30 +64,29 @@ class EngineBackend(PhaseBackend):
 
 
 class DataParallel(object):
-    """grad_dtype: None (default) all-reduces the flat gradient buffers in fp32 -- replicas then reproduce the one-GPU step up
-    to summation order; 'bf16' sends them as bfloat16 (half the bytes on the xGMI links: 2.5 MB instead of 5.1 MB for the
-    discriminator at D = 512; the four scalars at the tail stay fp32) at the price of an 8-bit mantissa per addend -- a
-    different, labelled numerical path.  It needs a backend built with dp_flags(grad_dtype='bf16'): the engine then writes and
-    reads the bfloat16 regions itself.  The small statistic regions always travel in fp32."""
+    """The gradient payload is the backend's (dp_flags(grad_dtype=...) made its handle; grad_dtype=None here follows it, any
+    other value must agree).  fp32 replicas reproduce the one-GPU step up to summation order; 'bf16' halves the bytes on the
+    xGMI links (2.5 MB instead of 5.1 MB for the discriminator at D = 512; the four scalars at the tail and the statistic
+    regions stay fp32) at the price of an 8-bit mantissa per addend -- a different, labelled numerical path.  A backend that
+    states neither grad_dtype nor exchange_regions (phases and region() only) takes the payload named here."""
 
     def __init__(self, backend, exact=True, group=None, grad_dtype=None):
+        own = getattr(backend, "grad_dtype", grad_dtype)
+        if grad_dtype is not None and grad_dtype != own:
+            raise ValueError("DataParallel(grad_dtype=%r) disagrees with the backend's gradient payload %r, which its handle "
+                             "fixed at creation (dp_flags(grad_dtype=...))" % (grad_dtype, own))
         self.backend = backend
         self.exact = exact
         self.group = group
-        self.grad_dtype = grad_dtype
+        self.grad_dtype = own
+        self._exchange = getattr(backend, "exchange_regions", None) or (lambda which: E.exchange_regions(backend.region, own, which))
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
 
     def _allreduce(self, which):
         if self.world <= 1:
             return
-        if self.grad_dtype == 'bf16' and which in (E.REGION_GRAD_D, E.REGION_GRAD_G):
-            # the library wrote the gradients as bfloat16 (FLAG_GRAD_BF16) and reads them back from the same region: reduced in
-            # place, no cast, no allocation; the four loss scalars travel on in fp32
-            d = which == E.REGION_GRAD_D
-            dist.all_reduce(self.backend.region(E.REGION_GRAD_D_BF16 if d else E.REGION_GRAD_G_BF16), op=dist.ReduceOp.SUM, group=self.group)
-            dist.all_reduce(self.backend.region(E.REGION_TAIL_D if d else E.REGION_TAIL_G), op=dist.ReduceOp.SUM, group=self.group)
-        else:
-            dist.all_reduce(self.backend.region(which), op=dist.ReduceOp.SUM, group=self.group)
+        for t in self._exchange(which):
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
 
     def _calibrate(self, kind, run_pass):
         """fp8 engines: the first sub-step of a kind is preceded by dry passes (forward + backward phases WITH the statistic
@@ -109,14 +118,10 @@ class DataParallel(object):
         b.gen_phase(args, E.G_BWD)
 
     def disc_step(self, args):
-        b = self.backend
         self._calibrate(0, lambda: self._disc_fwd_bwd(args))
-        b.disc_phase(args, E.D_GEN)
-        if self.exact:
-            self._allreduce(E.REGION_BN_STATS)
-        b.disc_phase(args, E.D_MAIN)
+        self._disc_fwd_bwd(args)
         self._allreduce(E.REGION_GRAD_D)
-        b.disc_phase(args, E.D_ADAM)
+        self.backend.disc_phase(args, E.D_ADAM)
 
     def gen_step(self, args, stats_done=False):
         b = self.backend
@@ -131,13 +136,7 @@ class DataParallel(object):
         if cal is not None and not cal(1, E.Engine.FP8_CAL_QUERY):
             self._calibrate(1, dry)
             stats_done = False
-        b.gen_phase(args, E.G_GEN)
-        if self.exact and not stats_done:
-            self._allreduce(E.REGION_BN_STATS)
-        b.gen_phase(args, E.G_FEAT)
-        if self.exact:
-            self._allreduce(E.REGION_FM_MOMENTS)
-        b.gen_phase(args, E.G_BWD)
+        self._gen_fwd_bwd(args, stats_done)
         if self.exact:
             self._allreduce(E.REGION_BN_BWD)
         b.gen_phase(args, E.G_TAIL)
@@ -162,8 +161,8 @@ class DataParallel(object):
 
 
 def dp_flags(exact=True, graph=False, grad_dtype=None):
-    """handle flags of a data-parallel rank.  graph=True: the kernels of every phase range are replayed as captured hipGraphs
-    (stream-mode arguments; the collectives stay between the ranges; measured SLOWER than eager launches on one GPU, see
-    DESIGN.md section 6).  grad_dtype='bf16': the gradients travel as bfloat16 (DataParallel(grad_dtype='bf16'))."""
-    return (E.FLAG_FLAT_GRADS | (E.FLAG_SYNC_STATS if exact else 0) | (E.FLAG_GRAPH if graph else 0) |
-            (E.FLAG_GRAD_BF16 if grad_dtype == 'bf16' else 0))
+    """handle flags of a data-parallel rank.  grad_dtype='bf16': the gradients travel as bfloat16 (DataParallel follows)."""
+    if graph:
+        raise ValueError("dp_flags(graph=True): phase-range hipGraphs were removed, they measured slower than eager phases "
+                         "(DESIGN.md section 6)")
+    return E.FLAG_FLAT_GRADS | (E.FLAG_SYNC_STATS if exact else 0) | (E.FLAG_GRAD_BF16 if grad_dtype == 'bf16' else 0)

@@ -123,6 +123,16 @@ def _f32(t, dev):
     return t.to(device=dev, dtype=torch.float32).contiguous()
 
 
+def exchange_regions(region, grad_dtype, which):
+    """the regions a data-parallel host all-reduces at exchange point `which` (a REGION_* of the phase protocol), given
+    region(REGION_*) -> tensor and the gradient payload: a gradient exchange with grad_dtype 'bf16' is the bfloat16 body plus
+    the four fp32 loss scalars"""
+    if grad_dtype == 'bf16' and which in (REGION_GRAD_D, REGION_GRAD_G):
+        d = which == REGION_GRAD_D
+        return (region(REGION_GRAD_D_BF16 if d else REGION_GRAD_G_BF16), region(REGION_TAIL_D if d else REGION_TAIL_G))
+    return (region(which),)
+
+
 class Engine(object):
     """One handle = the Keras shared state of one mr_gan() call (weights, Adam slots, iteration counter)
     plus the three compiled functions of mr_gan.py:169-171."""
@@ -326,6 +336,14 @@ class Engine(object):
         _check(self.lib.mrgan_region(self.handle, which, C.byref(p), C.byref(n)))
         off = p.value - self.workspace.data_ptr()
         return self.workspace[off:off + n.value].view(torch.bfloat16 if which in (REGION_GRAD_D_BF16, REGION_GRAD_G_BF16) else torch.float32)
+
+    @property
+    def grad_dtype(self):
+        """payload of the gradient exchanges, decided by the handle: 'bf16' (FLAG_GRAD_BF16) or None (fp32)"""
+        return 'bf16' if self.cfg.flags & FLAG_GRAD_BF16 else None
+
+    def exchange_regions(self, which):
+        return exchange_regions(self.region, self.grad_dtype, which)
 
     def debug_ablate(self, bits):
         _check(self.lib.mrgan_debug_ablate(self.handle, int(bits)))

@@ -37,7 +37,7 @@ def _unflat(v, like):
 class OraclePhases(object):
     """The oracle's D / G sub-steps cut into the phases of the C ABI, for one rank's row shard."""
 
-    def __init__(self, g, d, world, exact=True):
+    def __init__(self, g, d, world, exact=True, grad_dtype=None):
         from mr_gan_amd import engine as E
         self.E = E
         self.orc = O.MRGANOracle(g, d)
@@ -52,16 +52,19 @@ class OraclePhases(object):
             E.REGION_GRAD_D: torch.zeros(sum(p.size for p in d) + 4, dtype=torch.float64),
             E.REGION_GRAD_G: torch.zeros(sum(p.size for p in g) + 4, dtype=torch.float64),
         }
-        self.bf16 = False           # FLAG_GRAD_BF16: the reduce phases write bfloat16 regions (+ fp32 tails), the Adam phases read them
+        self.grad_dtype = grad_dtype    # 'bf16' (FLAG_GRAD_BF16): the reduce phases write bfloat16 regions (+ fp32 tails), the Adam phases read them
         self.last = None
 
     def region(self, which):
         return self.regions[which]
 
+    def exchange_regions(self, which):
+        return self.E.exchange_regions(self.region, self.grad_dtype, which)      # the engine's own mapping, over these regions
+
     def _publish(self, which):
         """what the engine's reduce phase does with MRGAN_FLAG_GRAD_BF16: gradients rounded once to bfloat16, the four scalars fp32"""
         E = self.E
-        if not self.bf16:
+        if self.grad_dtype != 'bf16':
             return
         d = which == E.REGION_GRAD_D
         v = self.regions[which]
@@ -69,12 +72,7 @@ class OraclePhases(object):
         self.regions[E.REGION_TAIL_D if d else E.REGION_TAIL_G] = v[-4:].float()
 
     def _collect(self, which):
-        E = self.E
-        if not self.bf16:
-            return self.regions[which].numpy()
-        d = which == E.REGION_GRAD_D
-        body = self.regions[E.REGION_GRAD_D_BF16 if d else E.REGION_GRAD_G_BF16].double().numpy()
-        return np.concatenate([body, self.regions[E.REGION_TAIL_D if d else E.REGION_TAIL_G].double().numpy()])
+        return np.concatenate([t.double().numpy() for t in self.exchange_regions(which)])
 
     # ---- generator pieces with externally supplied (global) batch statistics ----
     def _gen_head(self, z):
@@ -178,7 +176,14 @@ def _case(sorted_labels=False):
     return case
 
 
-def _worker(rank, world, port, exact, q, sorted_labels=False, grad_dtype=None):
+class _RegionOnly(object):
+    """a backend that states neither its payload nor its exchange regions: phases and region() only"""
+
+    def __init__(self, inner):
+        self.disc_phase, self.gen_phase, self.region = inner.disc_phase, inner.gen_phase, inner.region
+
+
+def _worker(rank, world, port, exact, q, sorted_labels=False, grad_dtype=None, dp_grad_dtype=None, region_only=False):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -186,9 +191,8 @@ def _worker(rank, world, port, exact, q, sorted_labels=False, grad_dtype=None):
     B, D, steps = 16, 12, 2
     case = _case(sorted_labels)
     h = B // world
-    backend = OraclePhases(case.g0, case.d0, world, exact)
-    backend.bf16 = grad_dtype == 'bf16'
-    dp = DataParallel(backend, exact=exact, grad_dtype=grad_dtype)
+    backend = OraclePhases(case.g0, case.d0, world, exact, grad_dtype)
+    dp = DataParallel(_RegionOnly(backend) if region_only else backend, exact=exact, grad_dtype=dp_grad_dtype)
     res = []
     it = 0
     for t in range(steps):
@@ -212,11 +216,12 @@ def _free_port():
     return p
 
 
-def _run(exact, world=2, sorted_labels=False, grad_dtype=None):
+def _run(exact, world=2, sorted_labels=False, grad_dtype=None, dp_grad_dtype=None, region_only=False):
+    """grad_dtype: the backend's gradient payload; dp_grad_dtype: what the host passes to DataParallel"""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, exact, q, sorted_labels, grad_dtype)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, exact, q, sorted_labels, grad_dtype, dp_grad_dtype, region_only)) for r in range(world)]
     for p in procs:
         p.start()
     out = sorted([q.get(timeout=120) for _ in procs], key=lambda x: x[0])
@@ -263,7 +268,7 @@ def test_bf16_gradient_payload_keeps_replicas_identical():
     """grad_dtype='bf16': half the bytes per gradient all-reduce; replicas still agree bit for bit (they all receive the same
     reduced bf16 values) and the losses stay those of the full-batch step; the weights differ from the fp32 exchange at the
     bf16 level (a labelled, different numerical path)"""
-    out = _run(exact=True, world=2, grad_dtype='bf16')
+    out = _run(exact=True, world=2, grad_dtype='bf16', dp_grad_dtype='bf16')
     ref = _case().run_oracle()
     (_, res0, d0, g0), (_, res1, d1, g1) = out
     np.testing.assert_allclose(res0[0], ref['disc'][0], rtol=1e-5, atol=1e-7)        # first sub-step: weights still identical
@@ -273,6 +278,39 @@ def test_bf16_gradient_payload_keeps_replicas_identical():
     case = _case()
     errs = [update_rel_err(a, r, w0) for a, r, w0 in zip(d0, ref['d'], case.d0)]
     assert max(errs) < 0.5 and max(errs) > 1e-6
+
+
+def test_host_follows_the_backends_gradient_payload():
+    """DataParallel(grad_dtype=None) over a bf16-payload backend exchanges the bfloat16 regions: exactly the result of
+    grad_dtype='bf16'.  (It used to all-reduce the fp32 buffers, which such a handle never reads: no error, unreduced
+    gradients, replicas drifting apart.)"""
+    follow = _run(exact=True, world=2, grad_dtype='bf16', dp_grad_dtype=None)
+    named = _run(exact=True, world=2, grad_dtype='bf16', dp_grad_dtype='bf16')
+    for (_, res_f, d_f, g_f), (_, res_n, d_n, g_n) in zip(follow, named):
+        assert res_f == res_n
+        for a, b in zip(d_f + g_f, d_n + g_n):
+            np.testing.assert_array_equal(a, b)
+
+
+def test_region_only_backend_takes_the_hosts_payload():
+    """a backend without grad_dtype / exchange_regions: DataParallel(grad_dtype=...) names the payload and maps the gradient
+    exchanges through region() itself -- exactly the result of a backend that states them"""
+    for host in (None, 'bf16'):
+        plain = _run(exact=True, world=2, grad_dtype=host, dp_grad_dtype=host, region_only=True)
+        stated = _run(exact=True, world=2, grad_dtype=host, dp_grad_dtype=host)
+        for (_, res_p, d_p, g_p), (_, res_s, d_s, g_s) in zip(plain, stated):
+            assert res_p == res_s
+            for a, b in zip(d_p + g_p, d_s + g_s):
+                np.testing.assert_array_equal(a, b)
+
+
+def test_grad_dtype_that_disagrees_with_the_backend_is_refused():
+    from mr_gan_amd.dist import DataParallel
+    case = _case()
+    with pytest.raises(ValueError, match="disagrees"):
+        DataParallel(OraclePhases(case.g0, case.d0, 2), grad_dtype='bf16')
+    bf16 = OraclePhases(case.g0, case.d0, 2, grad_dtype='bf16')
+    assert DataParallel(bf16).grad_dtype == DataParallel(bf16, grad_dtype='bf16').grad_dtype == 'bf16'
 
 
 def test_local_statistics_mode_is_a_different_algorithm():
@@ -292,6 +330,12 @@ def test_dp_flags():
     from mr_gan_amd.dist import dp_flags
     assert dp_flags(True) == E.FLAG_FLAT_GRADS | E.FLAG_SYNC_STATS
     assert dp_flags(False) == E.FLAG_FLAT_GRADS
+
+
+def test_dp_flags_refuse_phase_graphs():
+    from mr_gan_amd.dist import dp_flags
+    with pytest.raises(ValueError, match="removed"):
+        dp_flags(True, graph=True)
 
 
 class _PairingStub(object):
