@@ -23,6 +23,44 @@ int mrgan_debug_gemm_time(int op, int m, int n, int k, int nbatch, int splits, i
 int mrgan_debug_gemm(int dtype, int op, int m, int n, int k, const float* a_dev, const float* b_dev, const float* bias_dev,
                      int act, int splits, float* out_dev, mrgan_stream stream);
 
+/* One GEMM launch described field by field, for kernel-level tests of every tile and epilogue variant.  Nothing is allocated,
+ * converted or cleared except the DevState that carries `iter`: every buffer is the caller's device memory in the kernel's own
+ * element type (dtype MRGAN_BF16: bf16 operands / h / out; MRGAN_F32: float), so a caller that pre-fills the buffers sees
+ * every element the kernel did not write.
+ *   op 0 (forward) / 1 (input gradient): out[b][i][j] = epilogue(sum_k A(b,i,k) B(b,k,j)), i < m, j < n, reduction length k
+ *   op 2 (weight gradient): slab[split][i][j] = sum of A(i,v) B(v,j) over the reduction rows v of that split, v < k
+ *   A(b,i,k) at a + b*a_bs + i*a_si + k*a_sk ; B(b,k,j) at b + b*b_bs + k*b_sk + j*b_sj  (strides in elements).
+ * The remaining fields are those of the library's GEMM argument block (csrc/gemm.h), which documents them. */
+typedef struct mrgan_debug_gemm_desc {
+    int32_t dtype, op, m, n, k, nbatch, splits;
+    int32_t kchunk;                      /* reduction elements per split; 0 = k */
+    int32_t kc_cfg;                      /* bf16 forward / dX block tile, as MRGAN_TUNE_KC_CFG: -1 = the measured table */
+    int32_t tune_bits;
+    int32_t seg_stride, seg_rows;        /* op 2: reduction row v is valid when v % seg_stride < seg_rows; 0 = no holes */
+    const void* a; int64_t a_bs, a_si, a_sk;
+    const void* b; int64_t b_bs, b_sk, b_sj;
+    int32_t act, n_valid;
+    const float* bias;
+    void* out; int64_t out_bs; int32_t ldo;
+    float sigma; uint32_t site, seg0; int32_t seg_step; uint32_t iter_step, row0;
+    uint32_t iter;                       /* DevState::iter of the launch */
+    uint64_t seed;
+    uint16_t* mask; int64_t mask_bs; int32_t ldm;
+    const void* h; int64_t h_bs; int32_t ldh;
+    int32_t cs_mode; float* cs1; float* cs2; int32_t ldcs;
+    const float* bn_mu; const float* bn_rstd;
+    float* slab; int64_t slab_stride;
+} mrgan_debug_gemm_desc;
+/* per-block partial rows folded by the tail blocks of a grouped weight-gradient launch:
+ * dst[g][i] = sum of src[p][i] over p = g, g + ngroups, ... < nsrc  (i < n, rows `stride` floats apart) */
+typedef struct mrgan_debug_fold { const float* src; float* dst; int64_t stride; int32_t nsrc, n, ngroups; } mrgan_debug_fold;
+/* grouped = 0: launches d[0] (count must be 1) through the dtype's launcher.  grouped = 1: `count` bf16 weight-gradient
+ * products (+ the optional fold) as one grouped launch; returns 1 when the grouped kernel does not apply (nothing launched).
+ * Returns -1 for arguments the entry refuses (kc_cfg among them), the launcher's code (-3) for products it refuses.
+ * kname (optional, kname_len bytes) receives the name of the kernel that ran.  Synchronises the stream. */
+int mrgan_debug_gemm_launch(const mrgan_debug_gemm_desc* d, int count, int grouped, const mrgan_debug_fold* fold,
+                            char* kname, int kname_len, mrgan_stream stream);
+
 /* fp8 (OCP e4m3) forward product on the matrix cores, operands quantised from the fp32 inputs with per-tensor scales:
  * out[m,n] = act((q(a * scale_a) q(b * scale_b)) / (scale_a scale_b) + bias).  reps > 0 also times `reps` launches.
  * kc_cfg: -1 = the launcher's choice, 1 = 128x128 blocks, 3 = 256x256 blocks. */

@@ -1979,4 +1979,97 @@ int mrgan_debug_gemm(int dtype, int op, int m, int n, int k, const float* a, con
     return 0;
 }
 
+// one descriptor -> the launchers' argument block; the checks are the preconditions the kernels state for themselves
+static int debug_gemm_args(const mrgan_debug_gemm_desc& d, const DevState* st, GemmArgs& g, int& epi) {
+    const bool bf = d.dtype == MRGAN_BF16;
+    if (d.dtype != MRGAN_BF16 && d.dtype != MRGAN_F32) return fail(-1, "debug_gemm_launch: dtype must be fp32 or bf16");
+    if (d.op < 0 || d.op > 2) return fail(-1, "debug_gemm_launch: op must be 0, 1 or 2");
+    if (!kc_cfg_supported(d.kc_cfg)) return fail(-1, "debug_gemm_launch: kc_cfg %d is not a block tile", d.kc_cfg);
+    if (d.m < 1 || d.n < 1 || d.k < 1 || d.nbatch < 1 || d.splits < 1 || !d.a || !d.b) return fail(-1, "debug_gemm_launch: empty problem");
+    if (d.n % 64) return fail(-1, "debug_gemm_launch: n must be a multiple of 64");
+    memset(&g, 0, sizeof g);
+    epi = d.op == 0 ? EPI_FWD : d.op == 1 ? EPI_DX : EPI_SLAB;
+    g.M = d.m; g.N = d.n; g.K = d.k; g.nbatch = d.nbatch; g.splits = d.splits;
+    g.kchunk = d.kchunk > 0 ? d.kchunk : d.k;
+    g.tiles_m = ceil_div(d.m, 64);
+    g.seg_stride = d.seg_stride > 0 ? d.seg_stride : 1 << 30; g.seg_rows = d.seg_stride > 0 ? d.seg_rows : 1 << 30;
+    g.A = d.a; g.a_bs = d.a_bs; g.a_si = d.a_si; g.a_sk = d.a_sk;
+    g.B = d.b; g.b_bs = d.b_bs; g.b_sk = d.b_sk; g.b_sj = d.b_sj;
+    Epi& e = g.e;
+    e.act = d.act; e.n_valid = d.n_valid; e.bias = d.bias;
+    e.out = d.out; e.out_bs = d.out_bs; e.ldo = d.ldo;
+    e.sigma = d.sigma; e.site = d.site; e.seg0 = d.seg0; e.seg_step = d.seg_step; e.iter_step = d.iter_step; e.row0 = d.row0; e.seed = d.seed;
+    e.mask = d.mask; e.mask_bs = d.mask_bs; e.ldm = d.ldm;
+    e.h = d.h; e.h_bs = d.h_bs; e.ldh = d.ldh;
+    e.cs_mode = d.cs_mode; e.cs1 = d.cs1; e.cs2 = d.cs2; e.ldcs = d.ldcs; e.bn_mu = d.bn_mu; e.bn_rstd = d.bn_rstd;
+    e.slab = d.slab; e.slab_stride = d.slab_stride;
+    e.st = st; e.acc_scale = 1.f; e.tune_kc_cfg = d.kc_cfg; e.tune_bits = d.tune_bits;
+    if (epi == EPI_SLAB) {
+        const int bk = bf ? 64 : 16;
+        if (!d.slab || d.ldo < d.n) return fail(-1, "debug_gemm_launch: weight gradient needs slab and ldo >= n");
+        if ((g.kchunk % bk) || (g.seg_stride % bk)) return fail(-1, "debug_gemm_launch: kchunk and seg_stride must be multiples of %d", bk);
+        // 16-byte operand loads of the bf16 kernels: 8 elements per predicate
+        if (bf && ((d.a_sk % 8) || (d.b_sk % 8) || d.a_sk < round_up(d.m, 8))) return fail(-1, "debug_gemm_launch: bf16 row pitches must be multiples of 8");
+    } else {
+        if (!d.out || d.ldo < d.n || d.n_valid < 0 || d.n_valid > d.n) return fail(-1, "debug_gemm_launch: needs out, ldo >= n and n_valid <= n");
+        if (bf && ((d.ldo % 8) || (d.a_si % 8) || (d.b_sj % 8))) return fail(-1, "debug_gemm_launch: bf16 row pitches must be multiples of 8");
+        if (d.cs_mode != CS_NONE && (!d.cs1 || d.ldcs < d.n || (d.cs_mode != CS_SUM && !d.cs2))) return fail(-1, "debug_gemm_launch: column sums need cs1 / cs2 and ldcs >= n");
+        if (d.cs_mode == CS_SUM_XHAT && (epi != EPI_DX || !d.bn_mu || !d.bn_rstd || !d.h)) return fail(-1, "debug_gemm_launch: xhat sums need bn_mu, bn_rstd and h on a dX product");
+        if (epi == EPI_DX && d.act == ACT_SOFTPLUS && !d.h) return fail(-1, "debug_gemm_launch: the softplus derivative needs h");
+        if (epi == EPI_DX && d.act == ACT_RELU && !d.mask) return fail(-1, "debug_gemm_launch: the relu derivative needs mask");
+        if (d.h && (d.ldh < d.n || (bf && (d.ldh % 8)))) return fail(-1, "debug_gemm_launch: ldh");
+        if (d.mask && d.ldm < d.n) return fail(-1, "debug_gemm_launch: ldm >= n");
+    }
+    return 0;
+}
+
+int mrgan_debug_gemm_launch(const mrgan_debug_gemm_desc* d, int count, int grouped, const mrgan_debug_fold* fold,
+                            char* kname, int kname_len, mrgan_stream stream) {
+    if (!d || count < 1) return fail(-1, "null argument");
+    if (kname && kname_len > 0) kname[0] = 0;
+    hipStream_t s = (hipStream_t)stream;
+    DevState* st = nullptr;
+    DevState hst[2];
+    memset(hst, 0, sizeof hst);
+    hst[0].iter = hst[1].iter = d[0].iter;
+    HIPCHK(hipMalloc((void**)&st, sizeof hst));
+    hipError_t he = hipMemcpy(st, hst, sizeof hst, hipMemcpyHostToDevice);
+    const char* name = "";
+    int r = he == hipSuccess ? 0 : fail(-10, "hipMemcpy failed: %s", hipGetErrorString(he));
+    if (!r && !grouped) {
+        GemmArgs g;
+        int epi = 0;
+        if (count != 1) r = fail(-1, "debug_gemm_launch: one product per plain launch");
+        if (!r) r = debug_gemm_args(d[0], st, g, epi);
+        if (!r) {
+            r = d[0].dtype == MRGAN_BF16 ? launch_gemm_bf16(epi, g, s, &name) : launch_gemm_f32(epi, g, s, &name);
+            if (r) fail(r, "debug_gemm_launch: launch refused (%d)", r);
+        }
+    } else if (!r) {
+        // (a count beyond KS_GROUP_MAX is the launcher's refusal to make: it looks at no descriptor then)
+        GemmArgs gs[KS_GROUP_MAX];
+        for (int i = 0; i < count && i < KS_GROUP_MAX && !r; ++i) {
+            int epi = 0;
+            r = debug_gemm_args(d[i], st, gs[i], epi);
+            if (!r && (epi != EPI_SLAB || d[i].dtype != MRGAN_BF16)) r = fail(-1, "debug_gemm_launch: grouped launches are bf16 weight gradients");
+        }
+        FoldJob fj;
+        memset(&fj, 0, sizeof fj);
+        if (!r && fold) {
+            if (!fold->src || !fold->dst || fold->nsrc < 1 || fold->n < 1 || fold->ngroups < 1 || fold->stride < fold->n)
+                r = fail(-1, "debug_gemm_launch: fold");
+            fj.src = fold->src; fj.dst = fold->dst; fj.stride = fold->stride; fj.nsrc = fold->nsrc; fj.n = fold->n; fj.ngroups = fold->ngroups;
+        }
+        if (!r) {
+            r = launch_gemm_bf16_dw_group(gs, count, s, &name, fold ? &fj : nullptr);
+            if (r < 0) fail(r, "debug_gemm_launch: grouped launch failed (%d)", r);
+        }
+    }
+    he = hipStreamSynchronize(s);
+    hipFree(st);
+    if (!r && he != hipSuccess) return fail(-10, "debug_gemm_launch: %s", hipGetErrorString(he));
+    if (!r && kname && kname_len > 0) snprintf(kname, (size_t)kname_len, "%s", name);
+    return r;
+}
+
 }  // extern "C"

@@ -331,7 +331,7 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
                         s1 += __shfl_xor(s1, 32, 64);                     // lanes l and l ^ 32 hold the same column
                         const int col = col_blk + (wn * NR + ni) * 32 + lc;
                         const long pr = prow0 + wm * (MR / 2) + hh;
-                        if (lh == 0 && col < e.ldcs && row_blk + (wm * (MR / 2) + hh) * 64 < M) e.cs1[pr * e.ldcs + col] = s1;
+                        if (lh == 0 && col < g.N && col < e.ldcs && row_blk + (wm * (MR / 2) + hh) * 64 < M) e.cs1[pr * e.ldcs + col] = s1;
                     }
             }
         } else if (e.cs_mode != CS_NONE) {
@@ -384,7 +384,8 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
                         for (int ni = 0; ni < NR; ++ni) {
                             const int col = col_blk + (wn * NR + ni) * 32 + lc;
                             const long pr = prow0 + wm * NH + hh;
-                            if (col < e.ldcs && row_blk + (wm * NH + hh) * 64 < M) {
+                            // (col < N: a block tile wider than the last columns of N must not touch a row's pad up to ldcs)
+                            if (col < g.N && col < e.ldcs && row_blk + (wm * NH + hh) * 64 < M) {
                                 e.cs1[pr * e.ldcs + col] = cs1[hh][ni];
                                 if (e.cs_mode != CS_SUM) e.cs2[pr * e.ldcs + col] = cs2[hh][ni];
                             }
@@ -408,7 +409,7 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
                     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
                     for (int w = 0; w < WM; ++w) { s1 += lds[(w * 2 + 0) * bn + t]; s2 += lds[(w * 2 + 1) * bn + t]; }
-                    if (col_blk + t < e.ldcs) {
+                    if (col_blk + t < g.N && col_blk + t < e.ldcs) {
                         e.cs1[prow0 * e.ldcs + col_blk + t] = s1;
                         if (e.cs_mode != CS_SUM) e.cs2[prow0 * e.ldcs + col_blk + t] = s2;
                     }

@@ -27,7 +27,7 @@ EXPORTS = [
     "mrgan_num_tensors", "mrgan_tensor_shape", "mrgan_set_weights", "mrgan_get_weights", "mrgan_get_slot",
     "mrgan_set_slot", "mrgan_get_iterations", "mrgan_set_iterations", "mrgan_disc_step", "mrgan_gen_step",
     "mrgan_train_pair", "mrgan_sup_step", "mrgan_fp8_calibration", "mrgan_logmel", "mrgan_logmel_frames", "mrgan_region", "mrgan_eval_error", "mrgan_predict_logits", "mrgan_read_metrics",
-    "mrgan_pair_hint", "mrgan_set_tuning", "mrgan_debug_noise", "mrgan_debug_tr_probe", "mrgan_debug_gemm", "mrgan_profile_begin", "mrgan_profile_end", "mrgan_debug_ablate", "mrgan_debug_gemm_time", "mrgan_debug_buffer", "mrgan_debug_gemm_fp8",
+    "mrgan_pair_hint", "mrgan_set_tuning", "mrgan_debug_noise", "mrgan_debug_tr_probe", "mrgan_debug_gemm", "mrgan_debug_gemm_launch", "mrgan_profile_begin", "mrgan_profile_end", "mrgan_debug_ablate", "mrgan_debug_gemm_time", "mrgan_debug_buffer", "mrgan_debug_gemm_fp8",
 ]
 PROF_NAME_LEN = 96
 
@@ -379,6 +379,62 @@ def debug_gemm(dtype, op, a, b, bias=None, act=0, splits=1):
         out = torch.empty((k, n), dtype=torch.float32, device=a.device)
     _check(lib.mrgan_debug_gemm(dtype, op, m, n, k, _ptr(a), _ptr(b), _ptr(bias), act, splits, _ptr(out), _stream()))
     return out
+
+
+class DebugGemmDesc(C.Structure):
+    """mrgan_debug_gemm_desc (include/mrgan_debug.h)"""
+    _fields_ = [
+        ("dtype", C.c_int32), ("op", C.c_int32), ("m", C.c_int32), ("n", C.c_int32), ("k", C.c_int32),
+        ("nbatch", C.c_int32), ("splits", C.c_int32), ("kchunk", C.c_int32), ("kc_cfg", C.c_int32), ("tune_bits", C.c_int32),
+        ("seg_stride", C.c_int32), ("seg_rows", C.c_int32),
+        ("a", C.c_void_p), ("a_bs", C.c_int64), ("a_si", C.c_int64), ("a_sk", C.c_int64),
+        ("b", C.c_void_p), ("b_bs", C.c_int64), ("b_sk", C.c_int64), ("b_sj", C.c_int64),
+        ("act", C.c_int32), ("n_valid", C.c_int32), ("bias", C.c_void_p),
+        ("out", C.c_void_p), ("out_bs", C.c_int64), ("ldo", C.c_int32),
+        ("sigma", C.c_float), ("site", C.c_uint32), ("seg0", C.c_uint32), ("seg_step", C.c_int32),
+        ("iter_step", C.c_uint32), ("row0", C.c_uint32), ("iter", C.c_uint32), ("seed", C.c_uint64),
+        ("mask", C.c_void_p), ("mask_bs", C.c_int64), ("ldm", C.c_int32),
+        ("h", C.c_void_p), ("h_bs", C.c_int64), ("ldh", C.c_int32),
+        ("cs_mode", C.c_int32), ("cs1", C.c_void_p), ("cs2", C.c_void_p), ("ldcs", C.c_int32),
+        ("bn_mu", C.c_void_p), ("bn_rstd", C.c_void_p),
+        ("slab", C.c_void_p), ("slab_stride", C.c_int64),
+    ]
+
+
+class DebugFold(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("stride", C.c_int64), ("nsrc", C.c_int32), ("n", C.c_int32),
+                ("ngroups", C.c_int32)]
+
+
+def debug_gemm_desc(**kw):
+    """a DebugGemmDesc from keywords; tensors become device pointers (and are kept alive by the descriptor)"""
+    d = DebugGemmDesc()
+    d.kc_cfg, d.nbatch, d.splits = -1, 1, 1
+    d._refs = []
+    for name, v in kw.items():
+        if isinstance(v, torch.Tensor):
+            d._refs.append(v)
+            v = v.data_ptr()
+        setattr(d, name, v)
+    return d
+
+
+def debug_gemm_launch(descs, grouped=False, fold=None):
+    """One launch through mrgan_debug_gemm_launch -> (return code, kernel name).  Codes the launchers use to refuse a product
+    (-3, and 1 for the grouped launch) and the entry's own -1 are returned, anything else raises."""
+    if isinstance(descs, DebugGemmDesc):
+        descs = [descs]
+    arr = (DebugGemmDesc * len(descs))(*descs)
+    name = C.create_string_buffer(PROF_NAME_LEN)
+    f = None
+    if fold is not None:
+        src, dst, stride, nsrc, n, ngroups = fold
+        f = DebugFold(src.data_ptr(), dst.data_ptr(), stride, nsrc, n, ngroups)
+    rc = load_library().mrgan_debug_gemm_launch(arr, len(descs), 1 if grouped else 0, C.byref(f) if f is not None else None,
+                                                name, PROF_NAME_LEN, _stream())
+    if rc not in (0, 1, -1, -3):
+        _check(rc)
+    return rc, name.value.decode()
 
 
 def debug_tr_probe(device="cuda:0"):

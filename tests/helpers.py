@@ -105,6 +105,52 @@ def cosine(a, ref):
     return float(a @ ref / (np.linalg.norm(a) * np.linalg.norm(ref) + 1e-300))
 
 
+# ---------------------------------------------------------------------------------------------------------
+# layouts the GEMM epilogues write (csrc/gemm.h), restated for the kernel-level tests
+# ---------------------------------------------------------------------------------------------------------
+def _mask_pos(rows):
+    """row -> (32-row block, lane half, bit) of the lane-native relu mask: a 32x32 accumulator holds row
+    (r & 3) + 8 (r >> 2) + 4 half in register r, and bit r of the word of (block, column, half) is that element"""
+    rows = np.asarray(rows)
+    rr = rows & 31
+    return rows >> 5, (rr >> 2) & 1, (rr & 3) | ((rr >> 3) << 2)
+
+
+def mask_decode(words, m, n):
+    """uint16 words [ceil(m / 32) or more][ldm][2] -> bool [m][n]"""
+    words = np.asarray(words)
+    blk, half, bit = _mask_pos(np.arange(m))
+    w = words[blk[:, None], np.arange(n)[None, :], half[:, None]].astype(np.uint32)
+    return ((w >> bit[:, None].astype(np.uint32)) & 1).astype(bool)
+
+
+def mask_encode(bits, ldm):
+    """bool [m][n] -> uint16 words [ceil(m / 32)][ldm][2], zero where no element of `bits` lives"""
+    bits = np.asarray(bits, dtype=bool)
+    m, n = bits.shape
+    blk, half, bit = _mask_pos(np.arange(m))
+    words = np.zeros(((m + 31) // 32, ldm, 2), dtype=np.uint32)
+    np.bitwise_or.at(words, (blk[:, None], np.arange(n)[None, :], half[:, None]), bits.astype(np.uint32) << bit[:, None].astype(np.uint32))
+    return words.astype(np.uint16)
+
+
+def colsum_rows(m, nbatch):
+    """partial-sum row of every (batch, row): the sums have a fixed granularity of 64 rows, [batch * tiles_m + row / 64][ldcs]
+    with tiles_m = ceil(m / 64) -> (tiles_m, int array [nbatch][m])"""
+    tiles_m = (m + 63) // 64
+    return tiles_m, np.arange(nbatch)[:, None] * tiles_m + (np.arange(m) // 64)[None, :]
+
+
+def colsum_groups(v):
+    """[nbatch][m][n] -> the column sums over 64-row groups in the layout above, [nbatch * tiles_m][n] (same dtype)"""
+    v = np.asarray(v)
+    nbatch, m, n = v.shape
+    tiles_m, prow = colsum_rows(m, nbatch)
+    out = np.zeros((nbatch * tiles_m, n), dtype=v.dtype)
+    np.add.at(out, prow.ravel(), v.reshape(nbatch * m, n))
+    return out
+
+
 def stub_training(job, datasets, device):
     """CPU stand-in for scheduler.train_job: a deterministic 'test error' from the job's rows (and the worker's pid, so
     tests can see that several processes took part)."""
