@@ -18,10 +18,6 @@ int mrgan_debug_buffer(mrgan_handle* h, int kind, int l, void** ptr_dev, int* ro
 /* average device time (us) of `reps` back-to-back launches of one bf16 product on scratch buffers:
  * op 0 forward (relu+noise+mask), 1 input-gradient (relu mask), 2 weight-gradient with `splits` slabs */
 int mrgan_debug_gemm_time(int op, int m, int n, int k, int nbatch, int splits, int reps, int ablate, int kc_cfg, float* avg_us);
-/* raw GEMM entry for kernel-level parity tests: op 0 = Y = act(X W + b), 1 = dX = dY W^T, 2 = dW = X^T dY.
- * fp32 device buffers in and out (converted internally when dtype = bf16). */
-int mrgan_debug_gemm(int dtype, int op, int m, int n, int k, const float* a_dev, const float* b_dev, const float* bias_dev,
-                     int act, int splits, float* out_dev, mrgan_stream stream);
 
 /* One GEMM launch described field by field, for kernel-level tests of every tile and epilogue variant.  Nothing is allocated,
  * converted or cleared except the DevState that carries `iter`: every buffer is the caller's device memory in the kernel's own

@@ -1,0 +1,138 @@
+// What the engine's translation units share: the handle, its parts, error reporting.
+//   engine_state.hip  workspace layout, create / destroy, weights and Adam slots in and out, regions, tuning
+//   engine.hip        the launch call sites, the phases of the sub-steps, the public step entries
+//   engine_debug.hip  the diagnostic entries of include/mrgan_debug.h
+#pragma once
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/mrgan_abi.h"
+#include "../../include/mrgan_debug.h"
+#include "aux_kernels.h"
+#include "chain.h"
+#include "logmel.h"
+#include "gemm.h"
+
+namespace mrgan {
+
+int fail(int code, const char* fmt, ...);      // records the message behind mrgan_last_error (per thread), returns code
+#define HIPCHK(x)                                                                               \
+    do {                                                                                        \
+        hipError_t e_ = (x);                                                                    \
+        if (e_ != hipSuccess) return fail(-10, "%s failed: %s", #x, hipGetErrorString(e_));     \
+    } while (0)
+#define CHK(x)                                                          \
+    do {                                                                \
+        int r_ = (x);                                                   \
+        if (r_ != 0) return r_ < -9 ? r_ : fail(r_, "launch failed (%d) at %s:%d", r_, __FILE__, __LINE__); \
+    } while (0)
+
+constexpr int SEG_ALIGN = 128; // segment row stride is a multiple of the GEMM block tile
+
+struct Tensor {                // one trainable tensor (padded fp32 master + Adam slots)
+    int rows, cols;            // logical (1-D: rows = 1)
+    int prow, pcol;            // padded
+    float *p, *m, *v;
+    __bf16 *w16, *wt16;
+    float* flat;               // position inside the flat gradient buffer
+    __bf16* flat16;            // ... inside the bfloat16 one (MRGAN_FLAG_GRAD_BF16)
+    const float* g; int nslab; long slab_stride;      // fused-mode gradient source
+};
+
+struct Dense {
+    int K, N, Kp, Np, act;
+    Tensor *W, *b;
+    float* slabs; int splits;   // weight-gradient slabs [nseg*splits][Kp][Np]
+};
+
+struct ProfRec { int cat; hipEvent_t start, stop; double flops, bytes; };      // device-side begin / end of one kernel (MRGAN_LAUNCH)
+
+// fp8 scaling slots: kind 0 = D sub-step, 1 = G sub-step; X = activations (e4m3), G = gradients (e5m2), W = weights (e4m3)
+constexpr int FP8_NSLOT = 28, FP8_DRY_PASSES = MRGAN_FP8_DRY_PASSES;
+inline int slot_x(int kind, int l) { return kind * 10 + l; }
+inline int slot_g(int kind, int l) { return kind * 10 + 5 + l; }
+inline int slot_w(int l) { return 20 + l; }
+// the generator's 4096 x 4096-class layer G2 (hbn -> h2): input, output gradient, weight
+constexpr int SLOT_GX = 25, SLOT_GG = 26, SLOT_GW = 27;
+constexpr float FP8_TARGET_E4M3 = 224.0f, FP8_TARGET_E5M2 = 28672.0f;      // half the largest finite value: 2x headroom
+
+
+}  // namespace mrgan
+
+using namespace mrgan;      // (the handle is a global type of the C ABI)
+
+struct mrgan_handle {
+    mrgan_config cfg;
+    bool bf16, sync_stats, flat_grads, own_ws;
+    int es;                               // activation element size
+    int B, S, tiles_m, Bg;                // local batch, segment stride, row tiles per segment, global batch
+    float stat_count, fm_scale;           // rows behind a batch statistic; 1/world when statistics stay per-shard
+    int Dp, nzp, Fp, F;                   // padded input / z / feature widths
+    char* ws; size_t ws_bytes;
+
+    std::vector<Tensor> gt, dt;           // Keras order
+    Dense g[3], d[6];
+
+    DevState* state;                      // [2]
+    int cur;                              // host mirror of the live slot
+    float* step_out;                      // [4]
+    float* accum;                         // [4]
+    int* err_count;
+    float *flat_d, *flat_g; size_t flat_d_n, flat_g_n;
+    __bf16 *flat16_d, *flat16_g;          // MRGAN_FLAG_GRAD_BF16
+    float *r_bn_stats, *r_fm, *r_bn_bwd;
+
+    // activations (T = float | __bf16)
+    void *zbuf, *h1, *hbn, *h2;          // the generator activations the current sub-step works on (views into *_all)
+    void *zbuf_all, *h1_all, *hbn_all, *h2_all;   // [2][S] rows: segment 1 = the G sub-step's batch when a pair runs its two
+                                                  // generator forwards as one (pair_gen)
+    int pair_gen, gen_ready;             // train_pair: D_GEN also ran the G sub-step's generator forward
+    const mrgan_gen_args* pair_g; int real_staged;   // train_pair: ... and staged the G sub-step's real rows
+    int xbase;                           // first xin[0] slot of the current G sub-step (0, or 3 after a paired forward)
+    void* xin[5]; void* feat; uint16_t* mask[5]; int ldm[5];
+    void* dpre[5];
+    void *dxfake, *dpre2g, *dhbn, *dpre1g;
+    float* logits;
+    float *bn_mu, *bn_rstd, *bn_mu_all, *bn_rstd_all;
+    // partial sums
+    float *cs_bn1, *cs_bn2, *cs_db[4], *cs_f, *cs_db3g, *cs_db2g, *cs_dbeta, *cs_dgamma, *db1g_part;
+    float *head_part, *head_red, *loss_part; int head_stride, head_groups;
+    int head_nblk;                        // partial rows of head_part / loss_part behind the last loss head (set where it is launched)
+    int bnb_blocks;
+    // fp8 mode (gemm_fp8.hip): fp8 copies of the discriminator's activations x8 / gradients g8 (row-major and transposed),
+    // of its weights, and the scaling slots (index fp8_slot())
+    bool fp8; int fp8_cal[2];
+    unsigned char *x8[5], *x8t[5], *g8[5], *g8t[5], *w8[5], *w8t[5];
+    unsigned char *hbn8, *hbn8t, *dp2g8, *dp2g8t, *gw8, *gw8t;      // generator layer G2: BN(h1) [2][S][N1], dpre2 [S][N2], W2
+    int gen_seg;                                                  // segment the generator views point at (set_gen_view)
+    Fp8Slot* slots; float* slot_targets; float* accum_save;
+    float* fm_scratch; unsigned int* fm_count;       // feature-matching loss partials of a wide feature layer (aux_kernels.hip)
+    bool chain_ok, use_chain;            // the 256-wide tail of the discriminator runs as row-block chain launches (gemm_chain.hip)
+    bool head_wide_ok, head_wide; __bf16 *w6c, *w6r;   // feature layers wider than the chain holds: the stand-alone MFMA loss head (chain.h: HeadWideArgs)
+    int tune_kc_cfg, tune_bits, tune_pair_gen;      // mrgan_set_tuning
+    int ablate;                                      // mrgan_debug_ablate (timing experiments)
+    AdamTile *tiles_g_dev, *tiles_d_dev; int ntiles_g, ntiles_d;
+
+    // per-launch hipEvent profiling (bench.py's live roofline measurement)
+    bool prof; std::vector<ProfRec> prof_recs; std::vector<std::string> prof_names;
+
+    // graph replay of (D step, G step)
+    hipGraphExec_t graph_exec; bool graph_ready; int graph_cur; mrgan_disc_args graph_d; mrgan_gen_args graph_g;
+};
+
+namespace mrgan {
+
+inline void* rowptr(mrgan_handle* h, void* base, long row, int ld) { return (char*)base + (size_t)row * ld * h->es; }
+inline dim3 grid2d(int prow, int pcol) { return dim3(ceil_div(pcol, 64), ceil_div(prow, 4)); }
+// which of the two generator-activation segments the following kernels work on
+void set_gen_view(mrgan_handle* h, int seg);
+// fp8 copies of a network's weights / the delayed scales of every slot (launches; mrgan_set_weights needs them too)
+int fp8_refresh_weights(mrgan_handle* h, int net, hipStream_t s);
+int fp8_update_scales(mrgan_handle* h, hipStream_t s);
+
+}  // namespace mrgan

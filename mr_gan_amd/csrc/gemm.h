@@ -14,6 +14,8 @@
 // epilogue of the matching DX product loads it back the same way.  relu_mask_bit() decodes it for
 // kernels that walk rows and columns.
 #pragma once
+#include <string.h>
+
 #include "common.h"
 
 namespace mrgan {
@@ -459,5 +461,56 @@ int launch_fp8_update_scales(Fp8Slot* slots, int n, hipStream_t s);
 int launch_fp8_init_slots(Fp8Slot* slots, int n, const float* targets_dev, hipStream_t s);
 int launch_gemm_bf16_dw_group(const GemmArgs* gs, int n, hipStream_t s, const char** kname = nullptr,
                               const FoldJob* fold = nullptr);   // 1 = not applicable
+
+// ---- host side: one builder per product kind ------------------------------------------------------------------------
+// Every launch description is built here, so these conventions exist once: the block is zero-initialised; a forward / dX
+// product is one slab over the whole reduction (kchunk = K) with one column-sum partial row per 64 output rows; a weight
+// gradient has one per 128 (the kernels' output tile); a reduction range without holes carries the sentinel below.
+// The caller adds what is its own: the epilogue (outputs, noise site, masks, column sums, scaling slots).
+constexpr int GEMM_NO_HOLES = 1 << 30;
+inline GemmArgs gemm_args(int M, int N, int K, int nbatch, int tile_rows) {
+    GemmArgs g;
+    memset(&g, 0, sizeof g);
+    g.M = M; g.N = N; g.K = K; g.nbatch = nbatch; g.splits = 1; g.kchunk = K; g.tiles_m = ceil_div(M, tile_rows);
+    g.seg_stride = g.seg_rows = GEMM_NO_HOLES;
+    return g;
+}
+// Y[b] = X[b] W: X [nb][rows][lda], batches a_bs elements apart.  The bf16 and fp8 kernels read the transposed weight copy
+// Wt [N][ldw] (reduction index contiguous, w_transposed), the fp32 kernel W [K][ldw] itself.
+inline GemmArgs gemm_fwd_args(int rows, int K, int N, int nb, const void* x, long a_bs, long lda, const void* w, long ldw,
+                              bool w_transposed) {
+    GemmArgs g = gemm_args(rows, N, K, nb, 64);
+    g.A = x; g.a_bs = a_bs; g.a_si = lda; g.a_sk = 1;
+    g.B = w;
+    if (w_transposed) { g.b_sj = ldw; g.b_sk = 1; }
+    else { g.b_sk = ldw; g.b_sj = 1; }
+    return g;
+}
+// dX[b] = dY[b] W^T: dY [nb][rows][ldy] -> K output columns; W [K][ldw] as stored, its rows being the reduction-contiguous
+// operand already (every dtype)
+inline GemmArgs gemm_dx_args(int rows, int K, int N, int nb, const void* dy, long a_bs, long ldy, const void* w, long ldw) {
+    GemmArgs g = gemm_args(rows, K, N, nb, 64);
+    g.A = dy; g.a_bs = a_bs; g.a_si = ldy; g.a_sk = 1;
+    g.B = w; g.b_sk = 1; g.b_sj = ldw;
+    return g;
+}
+// reduction rows per slab of a weight gradient over vrows rows
+inline int gemm_dw_kchunk(int vrows, int splits) { return (int)round_up(ceil_div(vrows, splits), 64); }
+// dW[K][N] = X^T dY over vrows reduction rows in `splits` fp32 slabs [split][K][N] of kchunk rows each.  Row v counts when
+// v % seg_stride < seg_rows (seg_stride <= 0: every row).  X [vrows][ldx] and dY [vrows][ldy] as stored (bf16, fp32), or
+// their transposed copies Xt [K][ldx], dYt [N][ldy] (fp8: transposed).
+inline GemmArgs gemm_dw_args(int K, int N, int vrows, int splits, int kchunk, int seg_stride, int seg_rows, const void* x, long ldx,
+                             const void* dy, long ldy, bool transposed, float* slab) {
+    GemmArgs g = gemm_args(K, N, vrows, 1, 128);
+    g.splits = splits; g.kchunk = kchunk;
+    if (seg_stride > 0) { g.seg_stride = seg_stride; g.seg_rows = seg_rows; }
+    g.A = x; g.B = dy;
+    if (transposed) { g.a_si = ldx; g.a_sk = 1; g.b_sj = ldy; g.b_sk = 1; }
+    else { g.a_si = 1; g.a_sk = ldx; g.b_sk = ldy; g.b_sj = 1; }
+    g.e.slab = slab; g.e.slab_stride = (long)K * N; g.e.ldo = N;
+    return g;
+}
+// words between two segments of seg_rows rows in a lane-native relu mask of pitch ldm (2 x u16 per (32 rows, column))
+inline long mask_pitch(int seg_rows, int ldm) { return (long)(seg_rows / 32) * ldm * 2; }
 
 }  // namespace mrgan

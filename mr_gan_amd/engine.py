@@ -27,7 +27,7 @@ EXPORTS = [
     "mrgan_num_tensors", "mrgan_tensor_shape", "mrgan_set_weights", "mrgan_get_weights", "mrgan_get_slot",
     "mrgan_set_slot", "mrgan_get_iterations", "mrgan_set_iterations", "mrgan_disc_step", "mrgan_gen_step",
     "mrgan_train_pair", "mrgan_sup_step", "mrgan_fp8_calibration", "mrgan_logmel", "mrgan_logmel_frames", "mrgan_region", "mrgan_eval_error", "mrgan_predict_logits", "mrgan_read_metrics",
-    "mrgan_pair_hint", "mrgan_set_tuning", "mrgan_debug_noise", "mrgan_debug_tr_probe", "mrgan_debug_gemm", "mrgan_debug_gemm_launch", "mrgan_profile_begin", "mrgan_profile_end", "mrgan_debug_ablate", "mrgan_debug_gemm_time", "mrgan_debug_buffer", "mrgan_debug_gemm_fp8",
+    "mrgan_pair_hint", "mrgan_set_tuning", "mrgan_debug_noise", "mrgan_debug_tr_probe", "mrgan_debug_gemm_launch", "mrgan_profile_begin", "mrgan_profile_end", "mrgan_debug_ablate", "mrgan_debug_gemm_time", "mrgan_debug_buffer", "mrgan_debug_gemm_fp8",
 ]
 PROF_NAME_LEN = 96
 
@@ -364,23 +364,6 @@ class Engine(object):
         return out
 
 
-def debug_gemm(dtype, op, a, b, bias=None, act=0, splits=1):
-    """Raw kernel-level product for parity tests. op 0: act(a b + bias); 1: a b^T; 2: a^T b."""
-    lib = load_library()
-    m = a.shape[0]
-    if op == 0:
-        k, n = b.shape
-        out = torch.empty((m, n), dtype=torch.float32, device=a.device)
-    elif op == 1:
-        k, n = b.shape
-        out = torch.empty((m, k), dtype=torch.float32, device=a.device)
-    else:
-        k, n = a.shape[1], b.shape[1]
-        out = torch.empty((k, n), dtype=torch.float32, device=a.device)
-    _check(lib.mrgan_debug_gemm(dtype, op, m, n, k, _ptr(a), _ptr(b), _ptr(bias), act, splits, _ptr(out), _stream()))
-    return out
-
-
 class DebugGemmDesc(C.Structure):
     """mrgan_debug_gemm_desc (include/mrgan_debug.h)"""
     _fields_ = [
@@ -435,6 +418,35 @@ def debug_gemm_launch(descs, grouped=False, fold=None):
     if rc not in (0, 1, -1, -3):
         _check(rc)
     return rc, name.value.decode()
+
+
+def debug_gemm(dtype, op, a, b, bias=None, act=0, splits=1):
+    """Raw kernel-level product for parity tests. op 0: act(a b + bias); 1: a b^T; 2: a^T b.  fp32 tensors in and out: the
+    operands are rounded to the dtype here (to nearest even), the bf16 forward gets the transposed weight copy it reads,
+    and the weight gradient's slabs are added in index order."""
+    td = torch.bfloat16 if dtype == BF16 else torch.float32
+    m = a.shape[0]
+    k, n = (a.shape[1], b.shape[1]) if op == 2 else b.shape
+    if n % 64 or k % 64:
+        raise ValueError("debug_gemm: n and k must be multiples of 64")
+    a, b = a.to(td).contiguous(), b.to(td).contiguous()
+    if op == 0:
+        wt = dtype == BF16
+        out = torch.zeros((m, n), dtype=td, device=a.device)
+        d = debug_gemm_desc(dtype=dtype, op=0, m=m, n=n, k=k, a=a, a_si=k, a_sk=1, b=b.t().contiguous() if wt else b,
+                            b_sk=1 if wt else n, b_sj=k if wt else 1, act=act, n_valid=n, bias=bias, out=out, ldo=n)
+    elif op == 1:
+        out = torch.zeros((m, k), dtype=td, device=a.device)
+        d = debug_gemm_desc(dtype=dtype, op=1, m=m, n=k, k=n, a=a, a_si=n, a_sk=1, b=b, b_sk=1, b_sj=n, n_valid=k, out=out, ldo=k)
+    else:
+        splits = max(1, splits)
+        out = torch.zeros((splits, k, n), dtype=torch.float32, device=a.device)
+        d = debug_gemm_desc(dtype=dtype, op=2, m=k, n=n, k=m, splits=splits, kchunk=-(-(-(-m // splits)) // 64) * 64,
+                            a=a, a_si=1, a_sk=k, b=b, b_sk=n, b_sj=1, slab=out, slab_stride=k * n, ldo=n)
+    _check(debug_gemm_launch(d)[0])
+    for s in range(1, splits if op == 2 else 0):
+        out[0] += out[s]
+    return out[0] if op == 2 else out.float()
 
 
 def debug_tr_probe(device="cuda:0"):
