@@ -40,13 +40,21 @@ enum {
     MRGAN_FLAG_FLAT_GRADS = 2,   /* gradients are reduced into the flat buffers; Adam runs as its own phase        */
     MRGAN_FLAG_GRAPH      = 4,   /* stream-mode arguments only: mrgan_train_pair replays a captured hipGraph of the whole
                                   * pair.  No effect with MRGAN_FLAG_FLAT_GRADS: the phases always launch eagerly          */
-    MRGAN_FLAG_GRAD_BF16  = 8    /* with MRGAN_FLAG_FLAT_GRADS: the gradients travel as bfloat16.  The reduce phase writes
+    MRGAN_FLAG_GRAD_BF16  = 8,   /* with MRGAN_FLAG_FLAT_GRADS: the gradients travel as bfloat16.  The reduce phase writes
                                   * MRGAN_REGION_GRAD_*_BF16 (rounded once from the fp32 sums) instead of the fp32 flat
                                   * buffers and the Adam phase reads them back: the host all-reduces those regions in place,
                                   * nothing is cast or allocated per step.  The four fp32 scalars behind the fp32 buffers
                                   * (MRGAN_REGION_TAIL_*) still travel in fp32, and mrgan_region refuses
                                   * MRGAN_REGION_GRAD_D / _G, whose fp32 bodies no phase reads.  A labelled, different
                                   * numerical path.                                                                       */
+    MRGAN_FLAG_GAUSS_NOISE = 16  /* the five GaussianNoise sites and the device-drawn z are true N(0, 1) variates (Box-Muller
+                                  * on the same counter keys, support +-5.77 sigma) instead of the default Irwin-Hall(32)
+                                  * sums: what the reference's K.random_normal draws, for comparisons against it.  A
+                                  * DIFFERENT random stream (results are not comparable draw by draw with a default handle)
+                                  * and a slower epilogue in every noisy forward product and in the staging kernel.  Every
+                                  * entry honours it: mrgan_disc_step / mrgan_gen_step and their phases, mrgan_train_pair
+                                  * with and without graph replay, data-parallel shards (rows stay global: the shards of a
+                                  * batch draw what the full batch would), mrgan_sup_step.  Host-supplied z is untouched.  */
 };
 
 /* Hyper-parameters are literals inside mr_gan() in the reference (mr_gan.py:77-79, :111-128, :165);

@@ -9,6 +9,9 @@
 extern "C" {
 #endif
 
+/* out[rows][cols] = the standard normals the handle's generator draws at (site, seg, step), first global row row0: the
+ * Irwin-Hall variates by default, the true-Gaussian ones on a MRGAN_FLAG_GAUSS_NOISE handle (which draws whole row pairs:
+ * row0 must be even there) */
 int mrgan_debug_noise(mrgan_handle* h, uint32_t site, uint32_t seg, uint32_t step, uint32_t row0, int rows, int cols,
                       float* out_dev, mrgan_stream stream);
 int mrgan_debug_tr_probe(uint16_t* out1024_dev, mrgan_stream stream);

@@ -22,6 +22,7 @@ struct StageArgs {
     StageSeg s[5]; int nseg;
     uint64_t seed; uint32_t row0;
     const DevState* cur;
+    int gauss;                                      // 0 = Irwin-Hall noise / z, 1 = true Gaussian (MRGAN_FLAG_GAUSS_NOISE)
 };
 int launch_stage(int bf16, const StageArgs& a, hipStream_t s);
 
@@ -120,7 +121,7 @@ struct AdamArgs {
 };
 int launch_adam(const AdamArgs& a, hipStream_t s);
 
-int launch_noise_debug(uint64_t seed, uint32_t site, uint32_t seg, uint32_t step, uint32_t row0, int rows, int cols,
+int launch_noise_debug(int gauss, uint64_t seed, uint32_t site, uint32_t seg, uint32_t step, uint32_t row0, int rows, int cols,
                        float* out, hipStream_t s);
 
 }  // namespace mrgan

@@ -39,9 +39,14 @@ template <> __device__ __forceinline__ void store8<__bf16>(__bf16* p, const floa
 // layout (lane = column, 16 rows in registers); the integer sums (|s| <= 4064) go through a per-wave int16 LDS image so
 // that global loads and stores move 8 consecutive columns per lane (2 x 16 B in, 16 B out).
 // =========================================================================================
-template <typename T>
+// GAUSS (StageArgs::gauss): the true-Gaussian generator's floats go through a per-wave fp32 image of one 32 x 32 block at a
+// time; the lanes whose 8 columns lie in that block add it.
+template <typename T, bool GAUSS = false>
 __global__ __launch_bounds__(256) void stage_kernel(const StageArgs a) {
-    __shared__ __attribute__((aligned(16))) short nlds[4][32][128 + 8];          // +8: rows 272 B apart (bank spread for the 2-byte writes)
+    // int16 sums [4][32][128 + 8] (+8: rows 272 B apart, bank spread for the 2-byte writes), or (GAUSS) floats [4][32][32 + 4]
+    __shared__ __attribute__((aligned(16))) char nraw[GAUSS ? 4 * 32 * (32 + 4) * 4 : 4 * 32 * (128 + 8) * 2];
+    short (*nlds)[32][128 + 8] = (short (*)[32][128 + 8])nraw;
+    float (*glds)[32][32 + 4] = (float (*)[32][32 + 4])nraw;
     const DevState st = *a.cur;
     const StageSeg& sg = a.s[blockIdx.z];
     const int lane = threadIdx.x & 63, lc = lane & 31, lh = lane >> 5;
@@ -51,7 +56,7 @@ __global__ __launch_bounds__(256) void stage_kernel(const StageArgs a) {
     const long o = sg.stream ? (long)st.batch * sg.rows : 0;
     T* out = (T*)sg.out;
     const bool noisy = sg.gen || sg.sigma > 0.f;
-    const float sigs = (sg.gen ? 1.0f : sg.sigma) * NOISE_SCALE;
+    const float sigs = (sg.gen ? 1.0f : sg.sigma) * (GAUSS ? 1.0f : NOISE_SCALE);
     const int cg = (lane & 15) * 8, rl = lane >> 4;                // lane <-> (8 columns, every 4th row)
     const int col = cbase + cg;
     const bool vec_ok = !sg.gen && (sg.ld & 3) == 0 && ((uintptr_t)sg.src & 15) == 0 && col + 7 < sg.cols;
@@ -80,7 +85,34 @@ __global__ __launch_bounds__(256) void stage_kernel(const StageArgs a) {
     }
     // the noise of the wave's 32 x 128 block is generated while the row loads above are in flight (it was generated first in
     // round 2, with nothing in flight)
-    if (noisy) {
+    if constexpr (GAUSS) {
+        if (noisy) {
+            const uint32_t ph = gauss_pairhash(noise_key(a.seed, sg.site * 256u + sg.seg, st.iter + sg.iter_off), a.row0 + (uint32_t)rbase, lane);
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) {
+                const int c0 = cbase + cb * 32;
+                if (c0 >= sg.cols) break;                          // wave-uniform
+                const f32x16 nz = gauss_block(ph, (uint32_t)(c0 + lc), lane);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) glds[wave][(r & 3) + 8 * (r >> 2) + 4 * lh][lc] = nz[r];
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if ((cg >> 5) == cb) {
+#pragma unroll
+                    for (int it = 0; it < 8; ++it) {
+                        const f32x4 n0 = *(const f32x4*)&glds[wave][it * 4 + rl][cg & 31], n1 = *(const f32x4*)&glds[wave][it * 4 + rl][(cg & 31) + 4];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+                            if (col + c < sg.cols) v[it][c] = fmaf(sigs, n0[c], v[it][c]);
+                            if (col + 4 + c < sg.cols) v[it][4 + c] = fmaf(sigs, n1[c], v[it][4 + c]);
+                        }
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();                   // the next block overwrites the image
+            }
+        }
+    } else if (noisy) {
         const uint32_t rowhash = noise_rowhash(noise_key(a.seed, sg.site * 256u + sg.seg, st.iter + sg.iter_off), a.row0 + (uint32_t)(rbase + lc));
         const i32x4 hfrag = hadamard_frag(lane);
 #pragma unroll
@@ -99,7 +131,7 @@ __global__ __launch_bounds__(256) void stage_kernel(const StageArgs a) {
     for (int it = 0; it < 8; ++it) {
         const int rr = it * 4 + rl, row = rbase + rr;
         if (row >= sg.rows) break;
-        if (noisy && col < sg.cols) {
+        if (!GAUSS && noisy && col < sg.cols) {
             const s16x8 nz = *(const s16x8*)&nlds[wave][rr][cg];
 #pragma unroll
             for (int c = 0; c < 8; ++c) if (col + c < sg.cols) v[it][c] = fmaf(sigs, (float)nz[c], v[it][c]);
@@ -751,10 +783,20 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
     }
 }
 
-__global__ __launch_bounds__(64) void noise_debug_kernel(uint64_t seed, uint32_t site, uint32_t seg, uint32_t step, uint32_t row0,
+// what a handle's generator draws: NOISE_SCALE * noise_block, or (gauss) gauss_block as it is
+__global__ __launch_bounds__(64) void noise_debug_kernel(int gauss, uint64_t seed, uint32_t site, uint32_t seg, uint32_t step, uint32_t row0,
                                                          int rows, int cols, float* out) {
     const int lane = threadIdx.x, lc = lane & 31, lh = lane >> 5;
     const int rbase = blockIdx.y * 32, c0 = blockIdx.x * 32;
+    if (gauss) {                                                   // (kernel argument: wave-uniform)
+        const f32x16 ng = gauss_block(gauss_pairhash(noise_key(seed, site * 256u + seg, step), row0 + (uint32_t)rbase, lane), (uint32_t)(c0 + lc), lane);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = rbase + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            if (row < rows && c0 + lc < cols) out[(long)row * cols + c0 + lc] = ng[r];
+        }
+        return;
+    }
     const uint32_t rh = noise_rowhash(noise_key(seed, site * 256u + seg, step), row0 + (uint32_t)(rbase + lc));
     const i32x16 nz = noise_block(rh, (uint32_t)c0 >> 5, lane, hadamard_frag(lane));
 #pragma unroll
@@ -777,7 +819,10 @@ int launch_stage(int bf16, const StageArgs& a, hipStream_t s) {
     int maxc = 0, maxr = 0;
     for (int i = 0; i < a.nseg; ++i) { maxc = max(maxc, a.s[i].cols_pad); maxr = max(maxr, a.s[i].rows); }
     dim3 grid(ceil_div(maxc, 128), ceil_div(maxr, 128), a.nseg);
-    LAUNCH_T(stage_kernel, grid, dim3(256), 0, s, a);
+    if (a.gauss) {
+        if (bf16) MRGAN_LAUNCH((stage_kernel<__bf16, true>), grid, dim3(256), 0, s, a);
+        else MRGAN_LAUNCH((stage_kernel<float, true>), grid, dim3(256), 0, s, a);
+    } else LAUNCH_T(stage_kernel, grid, dim3(256), 0, s, a);
     RET_LAUNCH;
 }
 
@@ -853,9 +898,9 @@ int launch_adam(const AdamArgs& a, hipStream_t s) {
     RET_LAUNCH;
 }
 
-int launch_noise_debug(uint64_t seed, uint32_t site, uint32_t seg, uint32_t step, uint32_t row0, int rows, int cols,
+int launch_noise_debug(int gauss, uint64_t seed, uint32_t site, uint32_t seg, uint32_t step, uint32_t row0, int rows, int cols,
                        float* out, hipStream_t s) {
-    MRGAN_LAUNCH(noise_debug_kernel, dim3(ceil_div(cols, 32), ceil_div(rows, 32)), dim3(64), 0, s, seed, site, seg,
+    MRGAN_LAUNCH(noise_debug_kernel, dim3(ceil_div(cols, 32), ceil_div(rows, 32)), dim3(64), 0, s, gauss, seed, site, seg,
                        step, row0, rows, cols, out);
     RET_LAUNCH;
 }

@@ -69,6 +69,7 @@ struct ChainArgs {
     int head_f_off, head_scratch_off, head_o_off;         // LDS offsets: features in, scratch, dpre out
     int seg0;                          // noise segment id of segment 0
     uint64_t seed; uint32_t row0; const DevState* st;
+    int gauss;                         // layer noise of the forward products: 0 = Irwin-Hall, 1 = true Gaussian (MRGAN_FLAG_GAUSS_NOISE)
     unsigned long long* stamps;        // diagnostic build only (make STAMPS=1): [block][8] cycles per phase
     int ablate;                        // timing experiments only (mrgan_debug_ablate): CH_ABL_* bits
 

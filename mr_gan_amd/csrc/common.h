@@ -138,6 +138,50 @@ __device__ __forceinline__ i32x16 noise_block(uint32_t rowhash, uint32_t cblk, i
 }
 
 // ---------------------------------------------------------------------------------------
+// True-Gaussian generator (MRGAN_FLAG_GAUSS_NOISE): the same keys, Box-Muller instead of the Hadamard mix.  A different
+// random stream and ~an order of magnitude more VALU work per normal than noise_block: the parity / evidence mode.
+// Restated in tests/gaussian_noise.py; the integer part agrees exactly, the float part to a few fp32 ulp.
+//
+// The normal at (global row R, column C):
+//     key = mix(seed, site*256+seg, sub-step)                                 (noise_key, as above)
+//     ph  = mix32((key ^ 0x47415553) + (R >> 1) * 0x9E3779B1)                 one hash per row PAIR
+//     w0  = mix32(ph ^ (2C) * 0x85EBCA77),  w1 = mix32(ph ^ (2C + 1) * 0x85EBCA77)
+//     u1  = (2 (w0 >> 9) + 1) * 2^-24  in (0, 1);   u2 = (w1 >> 8) * 2^-24  in [0, 1)        (both exact in fp32)
+//     n   = sqrt(-2 ln u1) * (R even ? cos : sin)(2 pi u2)                    support +-sqrt(48 ln 2) = +-5.77 sigma
+// Registers 2p and 2p+1 of a lane in the accumulator layout are rows (even, odd) of one pair in one column, so one
+// Box-Muller evaluation fills both.  The float part uses the precise library functions (logf, sqrtf, sincospif on the
+// exact argument 2 u2): the fp32 parity mode's step-level bounds (1e-5) leave no room for the hardware transcendentals.
+// Rows are global, and pairs must not straddle ranks: callers pass an even first row.
+// ---------------------------------------------------------------------------------------
+// lane l carries the hash of row pair (l & 15) of the 32-row block whose first global row is `row_first` (even)
+__device__ __forceinline__ uint32_t gauss_pairhash(uint32_t key, uint32_t row_first, int lane) {
+    return mix32((key ^ 0x47415553u) + ((row_first >> 1) + ((uint32_t)lane & 15u)) * 0x9E3779B1u);
+}
+// the 32 x 32 block (rows of `pairhash`, column `col` = this lane's global column) in the MFMA accumulator layout.
+// Needs the whole wave active (readlane).
+__device__ __forceinline__ f32x16 gauss_block(uint32_t pairhash, uint32_t col, int lane) {
+    const uint32_t c0 = (2u * col) * 0x85EBCA77u, c1 = (2u * col + 1u) * 0x85EBCA77u;
+    const bool hi = lane >= 32;
+    f32x16 n;
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        // registers 2p, 2p+1 <-> rows 2 (p&1) + 8 (p>>1) + 4 (lane>>5) + {0, 1}: pair (p&1) + 4 (p>>1) + 2 (lane>>5)
+        const int pr = (p & 1) + 4 * (p >> 1);
+        const uint32_t lo_h = (uint32_t)__builtin_amdgcn_readlane((int)pairhash, pr);
+        const uint32_t hi_h = (uint32_t)__builtin_amdgcn_readlane((int)pairhash, pr + 2);
+        const uint32_t ph = hi ? hi_h : lo_h;
+        const uint32_t w0 = mix32(ph ^ c0), w1 = mix32(ph ^ c1);
+        const float u1 = (float)(2u * (w0 >> 9) + 1u) * 5.9604644775390625e-08f;      // * 2^-24
+        const float u2x2 = (float)(w1 >> 8) * 1.1920928955078125e-07f;                // 2 u2 = (w1 >> 8) * 2^-23
+        const float r = sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincospif(u2x2, &sn, &cs);
+        n[2 * p] = r * cs; n[2 * p + 1] = r * sn;
+    }
+    return n;
+}
+
+// ---------------------------------------------------------------------------------------
 // numerics helpers (fp32)
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ float softplus_f(float x) {

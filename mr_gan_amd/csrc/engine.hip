@@ -80,6 +80,7 @@ double dw_bytes(const mrgan_handle* h, double rows, const Dense& L) { return row
 GemmArgs with_handle(mrgan_handle* h, GemmArgs g) {
     Epi& e = g.e;
     e.seed = h->cfg.seed;
+    e.gauss = h->gauss;
     e.row0 = (uint32_t)(h->cfg.rank * h->B);
     e.st = h->state + h->cur;
     e.ablate = h->ablate; e.tune_kc_cfg = h->tune_kc_cfg; e.tune_bits = h->tune_bits;
@@ -465,7 +466,7 @@ int stage_common(StageArgs& st, mrgan_handle* h, const float* z, int stream_mode
             st.nseg = slot + 2;
         }
     }
-    st.seed = h->cfg.seed; st.row0 = (uint32_t)(h->cfg.rank * h->B);
+    st.seed = h->cfg.seed; st.row0 = (uint32_t)(h->cfg.rank * h->B); st.gauss = h->gauss;
     st.cur = h->state + h->cur;
     return 0;
 }
@@ -505,7 +506,7 @@ ChainArgs chain_args(mrgan_handle* h, int variant, int nseg, int block_rows) {
     memset(&c, 0, sizeof c);
     c.variant = variant; c.block_rows = block_rows;
     c.rows = h->B; c.nseg = nseg; c.S = h->S; c.seg0 = 0;
-    c.seed = h->cfg.seed; c.row0 = (uint32_t)(h->cfg.rank * h->B); c.st = h->state + h->cur;
+    c.seed = h->cfg.seed; c.row0 = (uint32_t)(h->cfg.rank * h->B); c.st = h->state + h->cur; c.gauss = h->gauss;
     c.ablate = h->ablate;
     if (variant != CH_V_GBWD) { c.a_kind = CH_A_GLOBAL; c.a = (const __bf16*)h->xin[2]; c.a_bs = (long)h->S * h->d[2].Kp; c.lda = h->d[2].Kp; c.a_cols = h->d[2].Kp; }
     return c;

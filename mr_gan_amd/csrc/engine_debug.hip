@@ -22,7 +22,8 @@ extern "C" {
 int mrgan_debug_noise(mrgan_handle* h, uint32_t site, uint32_t seg, uint32_t step, uint32_t row0, int rows, int cols, float* out,
                       mrgan_stream stream) {
     if (!h || !out) return fail(-1, "null argument");
-    CHK(launch_noise_debug(h->cfg.seed, site, seg, step, row0, rows, cols, out, (hipStream_t)stream));
+    if (h->gauss && (row0 & 1u)) return fail(-1, "debug_noise: a true-Gaussian handle draws row pairs, row0 must be even");
+    CHK(launch_noise_debug(h->gauss, h->cfg.seed, site, seg, step, row0, rows, cols, out, (hipStream_t)stream));
     return 0;
 }
 

@@ -69,6 +69,7 @@ using namespace mrgan;      // (the handle is a global type of the C ABI)
 struct mrgan_handle {
     mrgan_config cfg;
     bool bf16, sync_stats, flat_grads, own_ws;
+    int gauss;               // MRGAN_FLAG_GAUSS_NOISE: layer noise and device-drawn z come from the true-Gaussian generator
     int es;                               // activation element size
     int B, S, tiles_m, Bg;                // local batch, segment stride, row tiles per segment, global batch
     float stat_count, fm_scale;           // rows behind a batch statistic; 1/world when statistics stay per-shard

@@ -117,6 +117,7 @@ int layout(mrgan_handle* h, char* base, size_t* bytes_out) {
     const int padw = h->fp8 ? 128 : 64;      // every feature dimension is padded (zero-filled) to a multiple of this
     auto padded = [padw](int x) { return (int)round_up(x, padw); };
     h->sync_stats = (c.flags & MRGAN_FLAG_SYNC_STATS) != 0;
+    h->gauss = (c.flags & MRGAN_FLAG_GAUSS_NOISE) ? 1 : 0;
     h->flat_grads = (c.flags & MRGAN_FLAG_FLAT_GRADS) != 0;
     h->B = c.batch; h->S = (int)round_up(c.batch, SEG_ALIGN); h->tiles_m = ceil_div(c.batch, 64);   // 64-row column-sum partials
     h->Bg = c.batch * c.world;

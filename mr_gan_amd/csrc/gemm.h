@@ -23,7 +23,9 @@ namespace mrgan {
 enum { EPI_FWD = 0, EPI_DX = 1, EPI_SLAB = 2 };
 // compile-time epilogue variant: activation in bits 0-1, then flags.  VAR_DYN keeps every decision at run time
 // (the fp32 parity kernels, where epilogue speed is irrelevant).
-enum { VAR_ACT_MASK = 3, VAR_NOISE = 4, VAR_MASK = 8, VAR_DYN = 64 };
+// VAR_GAUSS (only ever beside VAR_NOISE or VAR_DYN): the noise is the true-Gaussian generator's (common.h: gauss_block); the
+// launchers add it when Epi::gauss is set, so no default instantiation changes.
+enum { VAR_ACT_MASK = 3, VAR_NOISE = 4, VAR_MASK = 8, VAR_GAUSS = 16, VAR_DYN = 64 };
 
 
 struct Epi {
@@ -35,6 +37,7 @@ struct Epi {
     int seg_step; uint32_t iter_step;           // (1, 0) for the segments of one sub-step
     uint32_t row0;                              // global row offset of this rank inside a segment
     uint64_t seed;
+    int gauss;                                  // FWD: the noise generator: 0 = noise_block (Irwin-Hall), 1 = gauss_block (MRGAN_FLAG_GAUSS_NOISE)
     uint16_t* mask; long mask_bs; int ldm;      // FWD relu: written; DX relu: read. word ((row>>5)*ldm + col)*2 + half
     const void* h; long h_bs; int ldh;          // DX softplus: previous-layer output h (T); CS_SUM_XHAT: BN input h1
     int cs_mode; float* cs1; float* cs2; int ldcs;   // column partial sums per 64 rows: [batch*tiles_m + row/64][ldcs]
@@ -179,19 +182,22 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
         else if (DYN && e.mask) mask = e.mask + (long)batch * e.mask_bs;
         const T* hprev = e.h ? (const T*)e.h + (long)batch * e.h_bs : nullptr;
         const bool noisy = EPI == EPI_FWD && (DYN ? e.sigma > 0.f : (VAR & VAR_NOISE) != 0);
+        constexpr bool GAUSS = (VAR & VAR_GAUSS) != 0;     // rowhash[] then holds the row-pair hashes, sixteen per 32-row block
         // GaussianNoise of the NEXT layer's input (mr_gan.py:120-126), drawn per 32x32 accumulator tile by one integer
         // MFMA (common.h): the lane l&31 carries the hash of row rsub + (l&31), the result arrives in accumulator layout
         uint32_t rowhash[MR];
         i32x4 hfrag = {0, 0, 0, 0};
-        const float sigs = e.sigma * NOISE_SCALE;
+        const float sigs = GAUSS ? e.sigma : e.sigma * NOISE_SCALE;
         if constexpr (EPI == EPI_FWD) {
             if (noisy) {
                 const uint32_t nkey = noise_key(e.seed, e.site * 256u + e.seg0 + (uint32_t)(batch * e.seg_step),
                                                 (pf ? pf->iter : (e.st ? e.st->iter : 0u)) + (uint32_t)batch * e.iter_step);
-                hfrag = hadamard_frag(lane);
+                if constexpr (!GAUSS) hfrag = hadamard_frag(lane);
 #pragma unroll
-                for (int mi = 0; mi < MR; ++mi)
-                    rowhash[mi] = noise_rowhash(nkey, e.row0 + (uint32_t)(row_blk + (wm * MR + mi) * 32 + lc));
+                for (int mi = 0; mi < MR; ++mi) {
+                    if constexpr (GAUSS) rowhash[mi] = gauss_pairhash(nkey, e.row0 + (uint32_t)(row_blk + (wm * MR + mi) * 32), lane);
+                    else rowhash[mi] = noise_rowhash(nkey, e.row0 + (uint32_t)(row_blk + (wm * MR + mi) * 32 + lc));
+                }
             }
         }
 
@@ -228,8 +234,10 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
                     else if (act == ACT_RELU && colin && rsub < M) mbits = mask[mword];
                 }
                 i32x16 nzs = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                f32x16 nzg = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                 if constexpr (EPI == EPI_FWD) {
-                    if (noisy) nzs = noise_block(rowhash[mi], (uint32_t)col >> 5, lane, hfrag);
+                    if constexpr (GAUSS) { if (noisy) nzg = gauss_block(rowhash[mi], (uint32_t)col, lane); }
+                    else if (noisy) nzs = noise_block(rowhash[mi], (uint32_t)col >> 5, lane, hfrag);
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -249,7 +257,8 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
                             } else if (act == ACT_SOFTPLUS) {
                                 v = colvalid ? (fast_math ? softplus_fast(v) : softplus_f(v)) : 0.f;
                             }
-                            o = noisy ? fmaf(sig, (float)nzs[r], v) : v;
+                            if constexpr (GAUSS) o = noisy ? fmaf(sig, nzg[r], v) : v;
+                            else o = noisy ? fmaf(sig, (float)nzs[r], v) : v;
                         } else {
                             // rows >= M and padding columns arrive as exact zeros (zero-filled operands / zero weights)
                             if (act == ACT_RELU)        // all-ones / zero from the mask bit, applied to the float's bits

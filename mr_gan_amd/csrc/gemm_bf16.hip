@@ -605,6 +605,12 @@ static int launch_kc_any(int epi, const GemmArgs& g, hipStream_t s) {
     const Epi& e = g.e;
     if (epi == EPI_FWD) {
         const bool noise = e.sigma > 0.f, mask = e.mask != nullptr;
+        // (the true-Gaussian variants exist beside the noisy ones only: every other instantiation is the default build's)
+        if (e.gauss && noise) {
+            if (e.act == ACT_RELU && mask) return launch_kc_tile<EPI_FWD, ACT_RELU | VAR_NOISE | VAR_MASK | VAR_GAUSS>(g, s);
+            if (e.act == ACT_LINEAR && !mask) return launch_kc_tile<EPI_FWD, ACT_LINEAR | VAR_NOISE | VAR_GAUSS>(g, s);
+            return -3;
+        }
         if (e.act == ACT_RELU && noise && mask) return launch_kc_tile<EPI_FWD, ACT_RELU | VAR_NOISE | VAR_MASK>(g, s);
         if (e.act == ACT_RELU && !noise && mask) return launch_kc_tile<EPI_FWD, ACT_RELU | VAR_MASK>(g, s);
         if (e.act == ACT_RELU && !noise && !mask) return launch_kc_tile<EPI_FWD, ACT_RELU>(g, s);

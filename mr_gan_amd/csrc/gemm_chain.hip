@@ -472,7 +472,8 @@ __device__ __forceinline__ void chain_fmgrad(const ChainArgs& a, char* lds, int 
 
 // one dense product of the chain on the block's rows.  MODE is compile-time; `bias` (forward) and `mw` (the relu-mask words
 // of the output tile: read by dX, returned by forward) live in registers, loaded or produced before this call.
-template <int MODE, int MI>
+// GAUSS: forward noise from the true-Gaussian generator (common.h: gauss_block; rowhash[] then holds row-pair hashes)
+template <int MODE, int MI, bool GAUSS>
 __device__ __forceinline__ void chain_gemm(const ChainArgs& a, const ChainOp& op, const __bf16* nextW, const int nextK, const int nextN,
                                            char* lds, Stream& sm, const float bias,
                                            uint32_t (&mw)[2][MI], const int seg, const int nrb, const int rb, const int row_blk,
@@ -494,7 +495,10 @@ __device__ __forceinline__ void chain_gemm(const ChainArgs& a, const ChainOp& op
     if (noisy) {
         const uint32_t nkey = noise_key(a.seed, op.site * 256u + (uint32_t)(a.seg0 + seg), iter);
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) rowhash[mi] = noise_rowhash(nkey, a.row0 + (uint32_t)(row_blk + mi * 32 + lc));
+        for (int mi = 0; mi < MI; ++mi) {
+            if constexpr (GAUSS) rowhash[mi] = gauss_pairhash(nkey, a.row0 + (uint32_t)(row_blk + mi * 32), lane);
+            else rowhash[mi] = noise_rowhash(nkey, a.row0 + (uint32_t)(row_blk + mi * 32 + lc));
+        }
     }
     uint16_t* mask = op.mask ? op.mask + (long)seg * op.mask_bs : nullptr;
     BTile bt;
@@ -604,7 +608,7 @@ __device__ __forceinline__ void chain_gemm(const ChainArgs& a, const ChainOp& op
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             obase[i] = (cip >> 6) * (ROWS * 128) + lh * 512 + (((((cip & 63) >> 3) ^ (lh << 1)) ^ ((i & 1) | ((i >> 1) << 2))) << 4) + (cip & 7) * 2;
-        const float sig = (noisy && colvalid) ? op.sigma * NOISE_SCALE : 0.f;
+        const float sig = (noisy && colvalid) ? (GAUSS ? op.sigma : op.sigma * NOISE_SCALE) : 0.f;
         float s1 = 0.f;
         auto ostore = [&](int mi, int r, float o) {
 #ifdef MRGAN_CH_NO_OSTORE       // timing experiment (compile-time: a run-time test per element perturbs the epilogue it measures)
@@ -619,7 +623,9 @@ __device__ __forceinline__ void chain_gemm(const ChainArgs& a, const ChainOp& op
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
                 i32x16 nzs = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-                if (noisy) nzs = noise_block(rowhash[mi], (uint32_t)col >> 5, lane, hfrag);
+                f32x16 nzg = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                if constexpr (GAUSS) { if (noisy) nzg = gauss_block(rowhash[mi], (uint32_t)col, lane); }
+                else if (noisy) nzs = noise_block(rowhash[mi], (uint32_t)col >> 5, lane, hfrag);
                 uint32_t mbits = 0u;
                 // Rows >= rows_valid of a ragged block carry relu(bias) + noise instead of zeros.  That is harmless: every
                 // product is row-local, copy_out never stores those rows, the head gives them zero dlogits -- only a
@@ -631,7 +637,8 @@ __device__ __forceinline__ void chain_gemm(const ChainArgs& a, const ChainOp& op
                     mbits |= min(__builtin_bit_cast(uint32_t, v), 1u) << r;
                     s1 += v;
                     acc[mi][r] = v;
-                    ostore(mi, r, fmaf(sig, (float)nzs[r], v));       // sig = 0 without noise
+                    if constexpr (GAUSS) ostore(mi, r, fmaf(sig, nzg[r], v));
+                    else ostore(mi, r, fmaf(sig, (float)nzs[r], v));       // sig = 0 without noise
                 }
                 mw[pass][mi] = mbits;
                 if (mask && colin && row_blk + mi * 32 < a.rows)
@@ -700,7 +707,8 @@ __device__ __forceinline__ void load_mask_words(const ChainArgs& a, const ChainO
 // pipeline), relu masks of products whose forward ran in this launch never leave registers, and no per-op descriptor
 // reload sits between two products.
 // MI: 32-row groups per block (2: 64 rows, the D sub-step's launch; 1: 32 rows, for launches that would leave most CUs idle)
-template <int VARIANT, int MI>
+// GAUSS: the forward products draw their layer noise from the true-Gaussian generator (ChainArgs::gauss; never with CH_V_GBWD)
+template <int VARIANT, int MI, bool GAUSS = false>
 __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
     constexpr int ROWS = 32 * MI;
     static_assert(VARIANT != CH_V_DTAIL || MI == 2, "the loss head works on 64-row blocks");
@@ -783,7 +791,7 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
     // NEXT: index of the product that follows (-1: none) -- its first weight tile is issued during this product's last k-tile
 #define CH_GEMM(MODE, I, NEXT, BIAS, MW) do { const ChainOp op_ = a.op[opq(I)];                                                          \
         const int nx_ = opq(NEXT < 0 ? 0 : NEXT);                                                                                      \
-        chain_gemm<MODE, MI>(a, op_, NEXT < 0 ? nullptr : a.op[nx_].W, a.op[nx_].K, a.op[nx_].N, lds, sm, BIAS, MW, seg, nrb, rb, row_blk,  \
+        chain_gemm<MODE, MI, GAUSS>(a, op_, NEXT < 0 ? nullptr : a.op[nx_].W, a.op[nx_].K, a.op[nx_].N, lds, sm, BIAS, MW, seg, nrb, rb, row_blk,  \
                          rows_valid, iter, hfrag, t CH_ST_ARGS); } while (0)
     if constexpr (VARIANT == CH_V_DTAIL) {
         // D3 D4 D5 forward: the masks of D3 / D4 stay in registers for the way back
@@ -1201,6 +1209,9 @@ int chain_init_attributes() {
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_GBWD, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(64));
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_GFWD, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(32));
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_GBWD, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(32));
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_DTAIL, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(64));
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_GFWD, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(64));
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_GFWD, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(32));
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, HW_LDS);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_wide_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, HW_LDS);
     return e == hipSuccess ? 0 : -2;
@@ -1230,7 +1241,10 @@ int launch_chain(const ChainArgs& a, hipStream_t s) {
     const int nrb = (a.rows + a.block_rows - 1) / a.block_rows;
     const dim3 grid(nrb * a.nseg), block(CH_THREADS);
     const int lds = chain_lds_bytes(a.block_rows);
-    if (a.variant == CH_V_DTAIL) MRGAN_LAUNCH((chain_kernel<CH_V_DTAIL, 2>), grid, block, lds, s, a);
+    if (a.gauss && a.variant == CH_V_DTAIL) MRGAN_LAUNCH((chain_kernel<CH_V_DTAIL, 2, true>), grid, block, lds, s, a);
+    else if (a.gauss && a.variant == CH_V_GFWD && a.block_rows == 64) MRGAN_LAUNCH((chain_kernel<CH_V_GFWD, 2, true>), grid, block, lds, s, a);
+    else if (a.gauss && a.variant == CH_V_GFWD) MRGAN_LAUNCH((chain_kernel<CH_V_GFWD, 1, true>), grid, block, lds, s, a);
+    else if (a.variant == CH_V_DTAIL) MRGAN_LAUNCH((chain_kernel<CH_V_DTAIL, 2>), grid, block, lds, s, a);
     else if (a.variant == CH_V_GFWD && a.block_rows == 64) MRGAN_LAUNCH((chain_kernel<CH_V_GFWD, 2>), grid, block, lds, s, a);
     else if (a.variant == CH_V_GFWD) MRGAN_LAUNCH((chain_kernel<CH_V_GFWD, 1>), grid, block, lds, s, a);
     else if (a.block_rows == 64) MRGAN_LAUNCH((chain_kernel<CH_V_GBWD, 2>), grid, block, lds, s, a);

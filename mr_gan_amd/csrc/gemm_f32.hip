@@ -16,7 +16,7 @@ namespace mrgan {
 namespace {
 constexpr int BK = 16;
 
-template <int EPI, int TS>
+template <int EPI, int TS, int VAR = VAR_DYN>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmArgs g) {
     constexpr int BM = TS, BN = TS, LDT = TS, MR = TS / 64, KPT = TS / 16;       // KPT: k values staged per thread
     __shared__ __attribute__((aligned(16))) float lds[2 * BK * 128];              // (the epilogue's scratch needs the 128 form)
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmArgs g) {
         }
     }
     __syncthreads();
-    epilogue<float, EPI, MR, MR, 2>(acc, g, batch, split, tile_m, row_blk, col_blk, wm, wn, lane, lds, BN);
+    epilogue<float, EPI, MR, MR, 2, false, VAR>(acc, g, batch, split, tile_m, row_blk, col_blk, wm, wn, lane, lds, BN);
 }
 }  // namespace
 
@@ -101,7 +101,11 @@ static int launch_f32_ts(int epi, const GemmArgs& g, hipStream_t s) {
     dim3 grid(ceil_div(g.N, TS), ceil_div(g.M, TS), g.nbatch * g.splits);
     dim3 block(256);
     switch (epi) {
-        case EPI_FWD:  MRGAN_LAUNCH((gemm_f32_kernel<EPI_FWD, TS>), grid, block, 0, s, g); break;
+        case EPI_FWD:
+            // (a noisy forward product of a true-Gaussian handle: the same kernel with the other generator compiled in)
+            if (g.e.gauss && g.e.sigma > 0.f) MRGAN_LAUNCH((gemm_f32_kernel<EPI_FWD, TS, VAR_DYN | VAR_GAUSS>), grid, block, 0, s, g);
+            else MRGAN_LAUNCH((gemm_f32_kernel<EPI_FWD, TS>), grid, block, 0, s, g);
+            break;
         case EPI_DX:   MRGAN_LAUNCH((gemm_f32_kernel<EPI_DX, TS>), grid, block, 0, s, g); break;
         case EPI_SLAB: MRGAN_LAUNCH((gemm_f32_kernel<EPI_SLAB, TS>), grid, block, 0, s, g); break;
         default: return -1;

@@ -400,7 +400,9 @@ int launch_gemm_fp8(int epi, const GemmArgs& g, hipStream_t s, const char** knam
         if (e.cs_mode != CS_NONE && e.cs_mode != CS_SUM) return -3;
         if (out8) {
             if (e.cs_mode != CS_NONE) return -3;            // (the fp8-output epilogue carries column sums for dX only)
-            if (e.act == ACT_RELU && noise && mask) r = launch_fp8_var<EPI_FWD, ACT_RELU | VAR_NOISE | VAR_MASK, true>(g, s, big);
+            if (e.act == ACT_RELU && noise && mask)
+                r = e.gauss ? launch_fp8_var<EPI_FWD, ACT_RELU | VAR_NOISE | VAR_MASK | VAR_GAUSS, true>(g, s, big)
+                            : launch_fp8_var<EPI_FWD, ACT_RELU | VAR_NOISE | VAR_MASK, true>(g, s, big);
         } else {
             if (e.act == ACT_RELU && !noise && mask) r = launch_fp8_var<EPI_FWD, ACT_RELU | VAR_MASK, false>(g, s, big);
             else if (e.act == ACT_RELU && !noise && !mask) r = launch_fp8_var<EPI_FWD, ACT_RELU, false>(g, s, big);

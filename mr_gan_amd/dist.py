@@ -160,9 +160,10 @@ class DataParallel(object):
         self.gen_step(gargs, stats_done=paired)
 
 
-def dp_flags(exact=True, graph=False, grad_dtype=None):
-    """handle flags of a data-parallel rank.  grad_dtype='bf16': the gradients travel as bfloat16 (DataParallel follows)."""
+def dp_flags(exact=True, graph=False, grad_dtype=None, noise='irwin-hall'):
+    """handle flags of a data-parallel rank.  grad_dtype='bf16': the gradients travel as bfloat16 (DataParallel follows).
+    noise='gaussian': true-normal layer noise and z (engine.noise_flags); rows are global, so the shards draw the full batch's."""
     if graph:
         raise ValueError("dp_flags(graph=True): phase-range hipGraphs were removed, they measured slower than eager phases "
                          "(DESIGN.md section 6)")
-    return E.FLAG_FLAT_GRADS | (E.FLAG_SYNC_STATS if exact else 0) | (E.FLAG_GRAD_BF16 if grad_dtype == 'bf16' else 0)
+    return E.FLAG_FLAT_GRADS | (E.FLAG_SYNC_STATS if exact else 0) | (E.FLAG_GRAD_BF16 if grad_dtype == 'bf16' else 0) | E.noise_flags(noise)

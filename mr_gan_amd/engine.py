@@ -15,7 +15,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libmrgan_hip.so")
 
 F32, BF16, FP8 = 0, 1, 2
 NET_G, NET_D = 0, 1
-FLAG_SYNC_STATS, FLAG_FLAT_GRADS, FLAG_GRAPH, FLAG_GRAD_BF16 = 1, 2, 4, 8
+FLAG_SYNC_STATS, FLAG_FLAT_GRADS, FLAG_GRAPH, FLAG_GRAD_BF16, FLAG_GAUSS_NOISE = 1, 2, 4, 8, 16
+NOISE_MODES = ('irwin-hall', 'gaussian')
 D_GEN, D_MAIN, D_ADAM = 0, 1, 2
 G_GEN, G_FEAT, G_BWD, G_TAIL, G_ADAM = 0, 1, 2, 3, 4
 TUNE_CHAIN, TUNE_KC_CFG, TUNE_KS_GROUP, TUNE_PAIR_GEN, TUNE_HEAD_MFMA = 0, 1, 4, 5, 6
@@ -107,6 +108,14 @@ def default_config(d_in, batch):
     cfg = Config()
     _check(load_library().mrgan_default_config(C.byref(cfg), int(d_in), int(batch)))
     return cfg
+
+
+def noise_flags(noise):
+    """handle flag of a layer-noise / device-z generator: 'irwin-hall' (the default: sums of 32 uniform bytes on the matrix
+    cores) or 'gaussian' (true N(0, 1) by Box-Muller, FLAG_GAUSS_NOISE: a different random stream, slower epilogues)"""
+    if noise not in NOISE_MODES:
+        raise ValueError("noise must be one of %s, got %r" % (NOISE_MODES, noise))
+    return FLAG_GAUSS_NOISE if noise == 'gaussian' else 0
 
 
 def _ptr(t):

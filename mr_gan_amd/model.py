@@ -24,11 +24,13 @@ class MRGAN(object):
 
     dtype: 'float32' (fp32 MFMA: logits within 1e-3 of the reference arithmetic) or 'bfloat16'
     (bf16 MFMA, fp32 accumulate and fp32 master weights: the throughput mode).
+    noise: 'irwin-hall' (default) or 'gaussian': the generator of the five GaussianNoise sites and of the device-drawn z
+    (engine.noise_flags); 'gaussian' draws true normals as the reference's K.random_normal does, at a slower step.
     """
 
     def __init__(self, input_dim, batch_size=50, dtype='float32', seed=None, device='cuda:0', num_classes=6,
                  noise_size=100, g_hidden=(500, 500), d_hidden=(1000, 500, 250, 250, 250), lr=0.0006, beta_1=0.5,
-                 unlabeled_weight=1.0, use_graph=True, rank=0, world=1, flags=0, init_weights=True):
+                 unlabeled_weight=1.0, use_graph=True, rank=0, world=1, flags=0, init_weights=True, noise='irwin-hall'):
         self.input_dim = int(input_dim)
         self.batch_size = int(batch_size)
         self.seed = int(np.random.randint(1 << 31)) if seed is None else int(seed)   # mr_gan.py:75 is unseeded
@@ -41,7 +43,7 @@ class MRGAN(object):
         cfg.lr, cfg.beta1, cfg.unlabeled_weight = lr, beta_1, unlabeled_weight
         cfg.seed = self.seed
         cfg.rank, cfg.world = rank, world
-        cfg.flags = flags | (E.FLAG_GRAPH if use_graph else 0)
+        cfg.flags = flags | (E.FLAG_GRAPH if use_graph else 0) | E.noise_flags(noise)
         self.cfg = cfg
         self.engine = E.Engine(cfg, device)
         self.device = self.engine.device

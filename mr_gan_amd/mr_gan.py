@@ -7,7 +7,8 @@
     python -m mr_gan_amd.mr_gan --tables 1 3 5 6 [-v]        (mr_gan.py:236-341)
     python -m mr_gan_amd.mr_gan --tables 1 3 5 6 --gpus 8 --jobs-per-gpu 2     run-level scheduling of the tables (scheduler.py)
 
-Extra keyword arguments (batch_size, dtype, seed, device) default to the reference's literals.
+Extra keyword arguments (batch_size, dtype, seed, device, noise) default to the reference's literals; noise='gaussian'
+(--noise gaussian) draws the layer noise and z as true normals instead of the engine's default Irwin-Hall variates.
 """
 import argparse
 import itertools
@@ -24,11 +25,13 @@ MODALITIES = ['Force', 'Temperature', 'Force and Temperature', 'Contact mic', 'T
 
 
 def mr_gan(X, y, percentlabeled=50, percentunlabeled=None, epochs=100, trainTestSets=None, verbose=False,
-           batch_size=50, dtype='float32', seed=None, device='cuda:0'):
+           batch_size=50, dtype='float32', seed=None, device='cuda:0', noise='irwin-hall'):
     from sklearn.model_selection import train_test_split
     from sklearn.utils import shuffle
 
+    from mr_gan_amd.engine import noise_flags
     from mr_gan_amd.model import MRGAN
+    noise_flags(noise)                                             # an unknown value fails before any data is touched
 
     rs = np.random.RandomState(seed if seed is not None else np.random.randint(1 << 31))   # mr_gan.py:75 (unseeded there)
     test_ratio = 200 * len(MATERIALS)                              # mr_gan.py:81
@@ -50,7 +53,7 @@ def mr_gan(X, y, percentlabeled=50, percentunlabeled=None, epochs=100, trainTest
     if verbose:
         print('x_labeled:', np.shape(x_labeled), 'y_labeled:', np.shape(y_labeled))
 
-    model = MRGAN(X_train.shape[1], batch_size=batch_size, dtype=dtype, seed=int(rs.randint(1 << 31)), device=device)
+    model = MRGAN(X_train.shape[1], batch_size=batch_size, dtype=dtype, seed=int(rs.randint(1 << 31)), device=device, noise=noise)
     if verbose:
         print('Epochs:', epochs)
         print('Batch size:', batch_size)
@@ -256,11 +259,15 @@ def main(argv=None, dataset_fn=dataset, mr_gan_fn=mr_gan, scheduler_factory=None
     parser.add_argument('-v', '--verbose', help='Verbose', action='store_true')
     parser.add_argument('--epochs', type=int, default=100)
     parser.add_argument('--dtype', default='float32')
+    parser.add_argument('--noise', default='irwin-hall', choices=['irwin-hall', 'gaussian'],
+                        help="generator of the layer noise and z: the engine's default, or true normals as the reference draws")
     parser.add_argument('--gpus', type=int, default=0,
                         help='run-level scheduling: dispatch the independent trainings of tables 1 / 3 / 5 / 6 over this many GPUs (0 = in-process, sequential)')
     parser.add_argument('--jobs-per-gpu', type=int, default=1, help='concurrent trainings per GPU with --gpus')
     args = parser.parse_args(argv)
     kw = dict(epochs=args.epochs, dtype=args.dtype)
+    if args.noise != 'irwin-hall':                                 # travels in every job dict (scheduler.train_job -> mr_gan())
+        kw['noise'] = args.noise
     if args.gpus > 0:                                              # the independent trainings dispatched over worker processes
         from mr_gan_amd.scheduler import RunScheduler
         runs = (scheduler_factory or RunScheduler)(gpus=args.gpus, jobs_per_gpu=args.jobs_per_gpu)

@@ -25,7 +25,7 @@ class MRNN(object):
     """model.compile(loss='mse', optimizer='adam') + fit / evaluate of mr_nn.py:101-118 on one MI355X."""
 
     def __init__(self, input_dim, batch_size=20, dtype='float32', seed=None, device='cuda:0', num_classes=6,
-                 d_hidden=(1000, 500, 250, 250, 250), lr=NN_LR, beta_1=NN_BETA_1, init_weights=True):
+                 d_hidden=(1000, 500, 250, 250, 250), lr=NN_LR, beta_1=NN_BETA_1, init_weights=True, noise='irwin-hall'):
         self.input_dim, self.batch_size = int(input_dim), int(batch_size)
         self.seed = int(np.random.randint(1 << 31)) if seed is None else int(seed)      # mr_nn.py:71 is unseeded
         cfg = E.default_config(self.input_dim, self.batch_size)
@@ -35,6 +35,7 @@ class MRNN(object):
             cfg.d_hidden[i] = w
         cfg.lr, cfg.beta1 = lr, beta_1
         cfg.seed = self.seed
+        cfg.flags |= E.noise_flags(noise)                          # the GaussianNoise layers' generator (engine.noise_flags)
         self.engine = E.Engine(cfg, device)
         self.device = self.engine.device
         self.stream = torch.cuda.Stream(self.device)
@@ -99,9 +100,10 @@ class MRNN(object):
 
 
 def mr_nn(X, y, percentlabeled=50, trainTestSets=None, verbose=False, epochs=100, batch_size=20, dtype='float32',
-          seed=None, device='cuda:0'):
+          seed=None, device='cuda:0', noise='irwin-hall'):
     from sklearn.model_selection import train_test_split
     from sklearn.utils import shuffle
+    E.noise_flags(noise)
     rs = np.random.RandomState(seed if seed is not None else np.random.randint(1 << 31))     # mr_nn.py:71 is unseeded
     test_ratio = 200 * len(MATERIALS)                              # mr_nn.py:74
     num_labeled_examples = int(10 * percentlabeled)                # mr_nn.py:75
@@ -117,7 +119,7 @@ def mr_nn(X, y, percentlabeled=50, trainTestSets=None, verbose=False, epochs=100
     x_labeled, y_labeled, _ = select_labeled(X_train, y_train, num_labeled_examples)
     if verbose:
         print('x_labeled:', np.shape(x_labeled), 'y_labeled:', np.shape(y_labeled))
-    model = MRNN(X_train.shape[1], batch_size=batch_size, dtype=dtype, seed=int(rs.randint(1 << 31)), device=device)
+    model = MRNN(X_train.shape[1], batch_size=batch_size, dtype=dtype, seed=int(rs.randint(1 << 31)), device=device, noise=noise)
     model.fit(x_labeled, y_labeled, epochs=epochs, rng=rs)         # mr_nn.py:117
     testerror = model.evaluate(X_test, y_test)                     # mr_nn.py:118
     model.engine.close()
@@ -129,10 +131,12 @@ def main(argv=None, dataset_fn=dataset, fn=None):
     parser.add_argument('-t', '--tables', nargs='+', help='[Required] Tables to recompute', required=True)
     parser.add_argument('-v', '--verbose', help='Verbose', action='store_true')
     parser.add_argument('--dtype', default='float32', choices=['float32', 'bfloat16'])
+    parser.add_argument('--noise', default='irwin-hall', choices=['irwin-hall', 'gaussian'],
+                        help="generator of the GaussianNoise layers: the engine's default, or true normals as the reference draws")
     args = parser.parse_args(argv)
     if fn is None:
         def fn(X, y, **kw):
-            return mr_nn(X, y, dtype=args.dtype, **kw)
+            return mr_nn(X, y, dtype=args.dtype, noise=args.noise, **kw)
     baseline_tables(args.tables, fn, dataset_fn, args.verbose)
 
 

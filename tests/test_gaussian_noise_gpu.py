@@ -1,0 +1,286 @@
+"""MRGAN_FLAG_GAUSS_NOISE on the device: the true-Gaussian generator against its restatement (tests/gaussian_noise.py), its
+distribution, every call site through the unchanged oracle / mirror, the untouched default path, and the accuracy evidence.
+
+The step-level tests run the BODIES of the existing parity tests (tests/test_gpu_parity.py) with three substitutions and the
+same bounds: the Case draws its layer noise and z from gaussian_normal, every handle carries the flag, and (fp32) z is drawn
+on the device so that site 16 is covered.  Without the feature the flag is ignored, the device keeps drawing Irwin-Hall
+variates, and each of these tests fails."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import mrgan_oracle as O
+from tests import gaussian_noise as G
+from tests import test_gpu_parity as P
+from tests.helpers import SEED, rel_err, update_rel_err
+
+pytestmark = pytest.mark.gpu
+
+DEV = P.DEV
+_t = P._t
+
+# Float error of the device's Box-Muller (logf, sqrtf, sincospif in fp32) against the fp64 restatement, measured on an MI355X
+# over 2 679 424 values (2048 x 512 at (1, 1, 3), 1024 x 1152 at (4, 2, 11), 1000 x 400 at (0, 0, 0), 512 x 100 at (16, 0, 5)):
+# max |dev - ref| = 6.72e-7 overall and 1.79e-7 among |ref| <= 1; max |dev - ref| / |ref| among |ref| > 1 = 2.26e-7 (two fp32
+# ulp).  The integer part is exact, so the error is a fixed function of (w0, w1); the bound is 4 x the measured maxima (keys
+# not sampled): |dev - ref| <= A + B |ref| with
+A_ABS, B_REL = 4 * 1.79e-7, 4 * 2.26e-7
+# Condition (not measurement): at most 1e-5 absolute for |n| <= 6, the tightest fp32 step-level bound on quantities linear in
+# the noise.
+assert A_ABS + 6.0 * B_REL <= 1e-5
+
+
+def _flagged(build):
+    def flagged(D, B, dtype, flags=0, **kw):
+        from mr_gan_amd import engine as E
+        return build(D, B, dtype, flags=flags | E.FLAG_GAUSS_NOISE, **kw)
+    return flagged
+
+
+_gauss_engine = _flagged(P._engine)
+
+
+@pytest.fixture
+def gaussian_bodies(monkeypatch):
+    """the existing parity tests' bodies on true-Gaussian handles: their Case, noise_set and engine builder swapped"""
+    from mr_gan_amd import engine as E
+    real_default = E.default_config
+
+    def default_config(d_in, batch):                    # (bodies that fill a Config themselves)
+        cfg = real_default(d_in, batch)
+        cfg.flags |= E.FLAG_GAUSS_NOISE
+        return cfg
+
+    monkeypatch.setattr(P, "Case", G.GaussCase)
+    monkeypatch.setattr(P, "noise_set", G.noise_set)
+    monkeypatch.setattr(P, "_engine", _flagged(P._engine))
+    monkeypatch.setattr(E, "default_config", default_config)
+    return P
+
+
+# ---------------------------------------------------------------------------------------------------------
+# 1. device == restatement
+# ---------------------------------------------------------------------------------------------------------
+def _float_error(got, ref):
+    err = np.abs(got.astype(np.float64) - ref)
+    small = np.abs(ref) <= 1.0
+    return float(err.max()), float(err[small].max()), float((err[~small] / np.abs(ref[~small])).max())
+
+
+def test_device_gaussian_matches_restatement():
+    eng = _gauss_engine(16, 52, 0)
+    # the tuples of test_device_noise_matches_restatement with even first rows (the device draws whole row pairs), plus an odd
+    # number of rows
+    for site, seg, step, rows, cols, row0 in [(0, 0, 0, 52, 16, 0), (3, 2, 7, 50, 250, 0), (16, 0, 5, 48, 100, 48), (2, 1, 9, 70, 96, 36),
+                                              (4, 0, 2, 33, 40, 2)]:
+        got = eng.debug_noise(site, seg, step, rows, cols, row0).cpu().numpy()
+        ref = G.gaussian_normal(SEED, site, seg, step, rows, cols, row0=row0)
+        assert np.all(np.abs(got - ref) <= A_ABS + B_REL * np.abs(ref)), (site, seg, step, _float_error(got, ref))
+    worst = [0.0, 0.0, 0.0]
+    for site, seg, step, rows, cols in [(1, 1, 3, 2048, 512), (4, 2, 11, 1024, 1152)]:          # 2.2e6 values
+        got = eng.debug_noise(site, seg, step, rows, cols).cpu().numpy()
+        ref = G.gaussian_normal(SEED, site, seg, step, rows, cols)
+        e = _float_error(got, ref)
+        worst = [max(a, b) for a, b in zip(worst, e)]
+        assert np.all(np.abs(got - ref) <= A_ABS + B_REL * np.abs(ref)), (site, seg, step, e)
+    print("\nfloat error of the device Box-Muller: max abs %.3g, max abs among |n| <= 1 %.3g, max rel among |n| > 1 %.3g" % tuple(worst))
+    with pytest.raises(Exception):
+        eng.debug_noise(2, 1, 9, 70, 96, 37)            # an odd first row would split a pair
+    eng.close()
+
+
+def test_default_handle_of_the_same_geometry_still_draws_the_integer_sums():
+    eng = P._engine(16, 52, 0)
+    for site, seg, step, rows, cols, row0 in [(0, 0, 0, 52, 16, 0), (3, 2, 7, 50, 250, 0), (16, 0, 5, 48, 100, 48), (2, 1, 9, 70, 96, 37)]:
+        got = eng.debug_noise(site, seg, step, rows, cols, row0).cpu().numpy()
+        sums = O.device_noise_sums(SEED, site, seg, step, rows, cols, row0=row0)
+        np.testing.assert_array_equal(np.rint(got.astype(np.float64) / O.NOISE_SCALE).astype(np.int64), sums)
+    eng.close()
+
+
+# ---------------------------------------------------------------------------------------------------------
+# 2. distribution of the device's draw
+# ---------------------------------------------------------------------------------------------------------
+def test_device_gaussian_distribution():
+    eng = _gauss_engine(16, 52, 0)
+    G.check_distribution(eng.debug_noise(1, 1, 3, 2048, 512).cpu().numpy())
+    eng.close()
+
+
+# ---------------------------------------------------------------------------------------------------------
+# 3. every call site, through the unchanged oracle
+# ---------------------------------------------------------------------------------------------------------
+def test_fp32_gradients_match_oracle_gaussian():
+    """test_fp32_gradients_match_oracle (D = 48, B = 50) with the flag and device-drawn z: stage_kernel (site 0, site 16) and
+    the fp32 forward epilogues (sites 1 .. 4), same bounds"""
+    from mr_gan_amd import engine as E
+    case = G.GaussCase(D=48, B=50, steps=1, device_z=True)
+    orc = O.MRGANOracle(case.g0, case.d0)
+    (ll, lu, err), gd, _ = orc.disc_grads(**case.disc_inputs(0, 0))
+    eng = _gauss_engine(48, 50, 0, flags=E.FLAG_FLAT_GRADS | E.FLAG_SYNC_STATS)
+    P._load(eng, case)
+    da = E.Engine.disc_args(_t(case.x_lab[0]), _t(case.labels[0], torch.int32), _t(case.x_unl[0]))
+    eng.disc_step(da, E.D_GEN, E.D_MAIN, want_outputs=False)
+    for i, (a, b) in enumerate(zip(eng.get_slot(E.NET_D, 2), gd)):
+        assert rel_err(a, b) < 2e-5, ("dD", i, rel_err(a, b))
+    out = eng.disc_step(da, E.D_ADAM, E.D_ADAM)
+    np.testing.assert_allclose(out, (ll, lu, err), rtol=2e-4, atol=2e-5)
+    orc.adam.apply(orc.d, gd, 'd')
+    loss, gg, _ = orc.gen_grads(**case.gen_inputs(0, 1))
+    ga = E.Engine.gen_args(_t(case.x_unl2[0]))
+    eng.gen_step(ga, E.G_GEN, E.G_TAIL, want_outputs=False)
+    for i, (a, b) in enumerate(zip(eng.get_slot(E.NET_G, 2), gg)):
+        assert rel_err(a, b) < 2e-4, ("dG", i, rel_err(a, b))
+    assert abs(eng.gen_step(ga, E.G_ADAM, E.G_ADAM) - loss) < 2e-3 * abs(loss) + 1e-9
+    eng.close()
+
+
+@pytest.mark.parametrize("D,B", [(400, 50), (72, 132)])
+def test_fp32_steps_match_oracle_gaussian(gaussian_bodies, monkeypatch, D, B):
+    """the body of test_fp32_steps_match_oracle, z drawn on the device"""
+    real_case, real_run = gaussian_bodies.Case, gaussian_bodies._run_engine
+    monkeypatch.setattr(P, "Case", lambda **kw: real_case(device_z=True, **kw))
+    monkeypatch.setattr(P, "_run_engine", lambda eng, case: real_run(eng, case, device_z=True))
+    P.test_fp32_steps_match_oracle(D, B)
+
+
+@pytest.mark.parametrize("D,B", [(512, 4096),      # the bench workload: chain kernel (64-row blocks), 8-wave 128x128 tiles
+                                 (400, 1024)])     # 64x128 / 64x64 tiles, the 32-row chain of the G sub-step
+def test_bf16_gradients_match_bf16_mirror_gaussian(gaussian_bodies, D, B):
+    """the body of test_bf16_gradients_match_bf16_mirror: err(engine, mirror) < max(3e-3, 0.6 err(mirror, fp64)).  The mirror is
+    fed the fp64 restatement, not the device's own values: the device's float error (1e-6) is far below what decides a bf16
+    rounding here (the fp32-vs-fp64 accumulation the rule already allows for)."""
+    P._grad_parity(D, B, 1, 'bf16', tol=3e-3, tol_loss=5e-4)
+
+
+def test_fp8_gradients_match_fp8_mirror_gaussian(gaussian_bodies):
+    """the hidden-2048 case of test_fp8_gradients_match_fp8_mirror: the fp8-output forward epilogue with noise (256x256 and
+    128x128 tiles by the launcher's table)"""
+    kw = dict(d_hidden=(2048,) * 5, g_hidden=(2048,) * 2)
+    P._grad_parity(512, 1024, 2, 'fp8', tol=5e-3, tol_loss=2e-3, eval_first=False, frac=0.85, loose=(0.9, 0.8, 0.6), **kw)
+
+
+@pytest.mark.parametrize("D,B", [(400, 256), (96, 50)])
+def test_chain_launches_equal_per_layer_launches_gaussian(gaussian_bodies, D, B):
+    P.test_chain_launches_equal_per_layer_launches(D, B)
+
+
+def test_graph_replay_equals_eager_gaussian():
+    from mr_gan_amd import MRGAN, select_labeled, synthetic_blobs
+    X, y = synthetic_blobs(n=1200, d=32, seed=4)
+    xl, yl, _ = select_labeled(X, y, 10)
+    ws = []
+    for use_graph, noise in ((False, 'gaussian'), (True, 'gaussian'), (True, 'irwin-hall')):
+        m = MRGAN(32, batch_size=64, dtype='float32', seed=21, use_graph=use_graph, noise=noise)
+        m.fit(xl, yl, X, epochs=2, rng=np.random.RandomState(9))
+        ws.append(m.get_weights('discriminator') + m.get_weights('generator'))
+        m.engine.close()
+    for a, b in zip(ws[0], ws[1]):
+        np.testing.assert_array_equal(a, b)
+    assert any(np.abs(a - c).max() > 0 for a, c in zip(ws[1], ws[2]))          # and the keyword does select another stream
+    with pytest.raises(ValueError):
+        MRGAN(32, batch_size=64, noise='normal')
+
+
+def test_supervised_steps_match_oracle_gaussian(gaussian_bodies):
+    """mrgan_sup_step (fp32, D = 48, B = 20) against MRGANOracle(lr = NN_ADAM_LR, b1 = NN_ADAM_B1): the body of
+    test_supervised_steps_match_oracle"""
+    P.test_supervised_steps_match_oracle(0, 48, 20, 0)
+
+
+def test_two_rank_emulation_equals_full_batch_gaussian(gaussian_bodies):
+    """rows are global: two shards of 32 rows draw rows 0 .. 31 and 32 .. 63 of the full batch's noise and z"""
+    P.test_two_rank_emulation_equals_full_batch()
+
+
+# ---------------------------------------------------------------------------------------------------------
+# 4. the default path is untouched
+# ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [0, 1])
+def test_default_path_is_untouched(dtype):
+    from mr_gan_amd import engine as E
+    D, B = 400, 128
+    case = G.GaussCase(D=D, B=B, steps=3, device_z=True)
+
+    def run(flags):
+        eng = P._engine(D, B, dtype, flags=flags)
+        P._load(eng, case)
+        nz = eng.debug_noise(3, 2, 7, 50, 250).cpu().numpy()
+        xl, yl, xu, xu2 = (_t(case.x_lab.reshape(-1, D)), _t(case.labels.reshape(-1), torch.int32), _t(case.x_unl.reshape(-1, D)),
+                           _t(case.x_unl2.reshape(-1, D)))
+        eng.set_iterations(0, 0)
+        da, ga = E.Engine.disc_args(xl, yl, xu, stream_mode=1), E.Engine.gen_args(xu2, stream_mode=1)
+        for _ in range(case.steps):
+            eng.train_pair(da, ga)
+        w = eng.get_weights(E.NET_D) + eng.get_weights(E.NET_G)
+        eng.close()
+        return nz, w
+
+    nz_a, w_a = run(0)
+    nz_b, w_b = run(0)
+    nz_g, w_g = run(E.FLAG_GAUSS_NOISE)
+    np.testing.assert_array_equal(nz_a, nz_b)
+    np.testing.assert_array_equal(np.rint(nz_a.astype(np.float64) / O.NOISE_SCALE).astype(np.int64), O.device_noise_sums(SEED, 3, 2, 7, 50, 250))
+    for a, b in zip(w_a, w_b):
+        np.testing.assert_array_equal(a, b)
+    assert np.abs(nz_g - nz_a).max() > 1.0
+    assert all(np.abs(a - g).max() > 0 for a, g in zip(w_a, w_g) if a.ndim == 2)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# 5. the evidence: does the generator's distribution move the accuracy?
+# ---------------------------------------------------------------------------------------------------------
+def test_six_fold_accuracy_gaussian_vs_default_generator():
+    """Surrogate and folds exactly as in test_six_fold_mean_accuracy_parity_on_mreo_surrogate (N 7200, D 1200, B 50, 500 labeled
+    rows per class, 20 epochs, the same initial weights and index streams), engine only.  For bf16 and fp32: three noise seeds x
+    six folds with the default Irwin-Hall generator and the same 18 trainings with noise='gaussian' (z on the device in both).
+    Asserted: every six-fold mean < 5 % (everybody learned) and |mean_18(gaussian) - mean_18(default)| <= 0.005 per dtype --
+    north_star's +-0.5 %, the bound of the existing host-z comparison; three seeds because that comparison showed one six-fold
+    mean moving by 0.34 % from the stream alone.
+
+    Measured on an MI355X (six-fold means of the final whole-test-set error per noise seed, then the 18-training mean):
+        bf16  default  0.43 / 0.43 / 0.49 %  -> 0.45 %      gaussian 0.47 / 0.56 / 0.42 %  -> 0.48 %      difference +0.03 %
+        fp32  default  0.62 / 0.75 / 0.60 %  -> 0.66 %      gaussian 0.60 / 0.40 / 0.62 %  -> 0.54 %      difference -0.12 %
+    Seed-to-seed spread of the six-fold mean: default 0.06 % (bf16) / 0.15 % (fp32), gaussian 0.14 % / 0.22 % -- the
+    generators differ by less than either one differs from itself under another noise seed.  72 trainings, 115 s."""
+    from sklearn.model_selection import StratifiedKFold
+    from mr_gan_amd import MRGAN, select_labeled, standard_scale, synthetic_mreo
+    epochs, seed, n_lab = 20, 4321, 500
+    X, y, _ = synthetic_mreo(sep=0.5)
+    folds = []
+    for k, (tr, te) in enumerate(StratifiedKFold(n_splits=6, shuffle=True, random_state=0).split(X, y)):
+        Xtr, Xte = standard_scale(X[tr], X[te])
+        ytr, yte = y[tr], y[te]
+        perm = np.random.RandomState(100 + k).permutation(len(ytr))          # mr_gan.py:101
+        Xtr, ytr = Xtr[perm], ytr[perm]
+        xl, yl, _ = select_labeled(Xtr, ytr, n_lab)
+        folds.append((Xtr, Xte, yte, xl, yl))
+    m0 = MRGAN(X.shape[1], batch_size=50, dtype='float32', seed=seed)
+    g0, d0 = m0.get_weights('generator'), m0.get_weights('discriminator')
+    m0.engine.close()
+    noise_seeds = (seed, seed + 1000, seed + 2000)
+    means = {}
+    for dt in ('bfloat16', 'float32'):
+        for noise in ('irwin-hall', 'gaussian'):
+            for s in noise_seeds:
+                errs = []
+                for k, (Xtr, Xte, yte, xl, yl) in enumerate(folds):
+                    m = MRGAN(X.shape[1], batch_size=50, dtype=dt, seed=s + k, init_weights=False, noise=noise)
+                    m.set_weights(g0, 'generator')
+                    m.set_weights(d0, 'discriminator')
+                    m.fit(xl, yl, Xtr, epochs=epochs, rng=np.random.RandomState(5 + k))
+                    errs.append(m.evaluate(Xte, yte))
+                    m.engine.close()
+                means[(dt, noise, s)] = float(np.mean(errs))
+                print("%-8s %-10s noise seed %d: folds %s  six-fold mean %.4f" % (dt, noise, s, " ".join("%.4f" % e for e in errs), means[(dt, noise, s)]),
+                      flush=True)
+    for dt in ('bfloat16', 'float32'):
+        per = {noise: [means[(dt, noise, s)] for s in noise_seeds] for noise in ('irwin-hall', 'gaussian')}
+        m18 = {noise: float(np.mean(v)) for noise, v in per.items()}
+        spread = {noise: max(v) - min(v) for noise, v in per.items()}
+        print("%-8s 18-training means %s  seed-to-seed spread of the six-fold mean %s  difference %.4f" % (
+            dt, {k: round(v, 4) for k, v in m18.items()}, {k: round(v, 4) for k, v in spread.items()}, m18['gaussian'] - m18['irwin-hall']), flush=True)
+    for dt in ('bfloat16', 'float32'):
+        per = {noise: [means[(dt, noise, s)] for s in noise_seeds] for noise in ('irwin-hall', 'gaussian')}
+        assert max(max(v) for v in per.values()) < 0.05, (dt, per)
+        assert abs(np.mean(per['gaussian']) - np.mean(per['irwin-hall'])) <= 0.005 + 1e-9, (dt, per)
