@@ -2,6 +2,7 @@
 // Access pattern everywhere: 16-byte loads/stores per lane along the contiguous (feature) dimension,
 // 256-thread blocks laid out as 32 column-groups x 8 row-lanes, >= 128 blocks per launch.
 #include "aux_kernels.h"
+#include "head.h"
 
 namespace mrgan {
 namespace {
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(256) void stage_kernel(const StageArgs a) {
                 if (c0 >= sg.cols) break;                          // wave-uniform
                 const f32x16 nz = gauss_block(ph, (uint32_t)(c0 + lc), lane);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) glds[wave][(r & 3) + 8 * (r >> 2) + 4 * lh][lc] = nz[r];
+                for (int r = 0; r < 16; ++r) glds[wave][acc_row(r, lh)][lc] = nz[r];
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 if ((cg >> 5) == cb) {
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(256) void stage_kernel(const StageArgs a) {
             if (c0 >= sg.cols) break;                              // wave-uniform; columns beyond are never read back
             const i32x16 nz = noise_block(rowhash, (uint32_t)c0 >> 5, lane, hfrag);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) nlds[wave][(r & 3) + 8 * (r >> 2) + 4 * lh][cb * 32 + lc] = (short)nz[r];
+            for (int r = 0; r < 16; ++r) nlds[wave][acc_row(r, lh)][cb * 32 + lc] = (short)nz[r];
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();                           // same wave, in-order LDS: the reads below see the writes
@@ -327,61 +328,16 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
     }
     const int row = row_blk + r;
     const bool rowvalid = row < a.rows;
-    float mx = -3.0e38f;
+    float b[KMAX];
 #pragma unroll
-    for (int c = 0; c < KMAX; ++c) {
-        if (c < a.classes) { l[c] += a.b[c]; mx = fmaxf(mx, l[c]); }
+    for (int c = 0; c < KMAX; ++c) b[c] = (c < a.classes) ? a.b[c] : 0.f;
+    int y = 0;
+    if (rowvalid && head_kind_has_label(kind)) {
+        const long lo = a.labels_stream ? (long)a.st->batch * a.rows : 0;
+        y = a.labels[lo + row];
     }
-    int am = 0;
-    float se = 0.f, p[KMAX];
-#pragma unroll
-    for (int c = KMAX - 1; c >= 0; --c) {
-        p[c] = (c < a.classes) ? expf(l[c] - mx) : 0.f;
-        se += p[c];
-        if (c < a.classes && l[c] == mx) am = c;          // ties -> first index (theano argmax)
-    }
-    const float lse = mx + logf(se);
-    const float inv_se = 1.0f / se;
-    float loss0 = 0.f, loss1 = 0.f, err = 0.f;
-    float dl[KMAX];
-#pragma unroll
-    for (int c = 0; c < KMAX; ++c) dl[c] = 0.f;
-    if (rowvalid) {
-        if (kind == HEAD_MSE) {
-            // Keras 'mse' on one-hot targets (mr_nn.py:99, :112): mean over the classes, then over the batch
-            const long lo = a.labels_stream ? (long)a.st->batch * a.rows : 0;
-            const int y = a.labels[lo + row];
-            err = (y >= 0 && am != y) ? 1.f : 0.f;
-            const float invc = 1.0f / (float)a.classes;
-#pragma unroll
-            for (int c = 0; c < KMAX; ++c) {
-                if (c < a.classes && y >= 0) {            // label -1: padding row of a short last batch, no contribution
-                    const float d = l[c] - (c == y ? 1.f : 0.f);
-                    loss0 = fmaf(d * d, invc, loss0);
-                    dl[c] = 2.0f * d * invc * a.inv_count;
-                }
-            }
-        } else if (kind == HEAD_LAB || kind == HEAD_EVAL) {
-            const long lo = a.labels_stream ? (long)a.st->batch * a.rows : 0;
-            const int y = a.labels[lo + row];
-            err = (am != y) ? 1.f : 0.f;
-            if (kind == HEAD_LAB) {
-                float ly = 0.f;
-#pragma unroll
-                for (int c = 0; c < KMAX; ++c) {
-                    if (c == y) ly = l[c];
-                    dl[c] = (p[c] * inv_se - (c == y ? 1.f : 0.f)) * a.inv_count;
-                }
-                loss0 = lse - ly;
-            }
-        } else if (kind != HEAD_LOGITS) {
-            const float sg = sigmoid_f(lse), sp = softplus_f(lse);
-            const float k = 0.5f * a.inv_count * a.unl_weight * (kind == HEAD_UNL ? (sg - 1.0f) : sg);
-            loss1 = (kind == HEAD_UNL) ? 0.5f * (sp - lse) : 0.5f * sp;
-#pragma unroll
-            for (int c = 0; c < KMAX; ++c) dl[c] = k * p[c] * inv_se;
-        }
-    }
+    float loss0, loss1, err, dl[KMAX];
+    head_row<true>(l, b, kind, y, a.classes, a.inv_count, a.unl_weight, rowvalid, loss0, loss1, err, dl);
     if (part == 0) {
         *(f32x4*)(dl_lds + r * KMAX) = (f32x4){dl[0], dl[1], dl[2], dl[3]};
         *(f32x4*)(dl_lds + r * KMAX + 4) = (f32x4){dl[4], dl[5], dl[6], dl[7]};
@@ -792,7 +748,7 @@ __global__ __launch_bounds__(64) void noise_debug_kernel(int gauss, uint64_t see
         const f32x16 ng = gauss_block(gauss_pairhash(noise_key(seed, site * 256u + seg, step), row0 + (uint32_t)rbase, lane), (uint32_t)(c0 + lc), lane);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = rbase + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int row = rbase + acc_row(r, lh);
             if (row < rows && c0 + lc < cols) out[(long)row * cols + c0 + lc] = ng[r];
         }
         return;
@@ -801,7 +757,7 @@ __global__ __launch_bounds__(64) void noise_debug_kernel(int gauss, uint64_t see
     const i32x16 nz = noise_block(rh, (uint32_t)c0 >> 5, lane, hadamard_frag(lane));
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int row = rbase + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int row = rbase + acc_row(r, lh);
         if (row < rows && c0 + lc < cols) out[(long)row * cols + c0 + lc] = NOISE_SCALE * (float)nz[r];
     }
 }

@@ -77,6 +77,26 @@ struct ChainArgs {
 
 int launch_chain(const ChainArgs& a, hipStream_t s);
 
+// ---- device side: the activation image [K/64 k-tiles][ROWS rows][64 k] bf16, 16-byte chunks XOR-swizzled per row ----
+__device__ __forceinline__ int kc_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
+// byte offset of element (row, col) inside an activation image
+template <int ROWS = CH_ROWS>
+__device__ __forceinline__ int act_off(int row, int col) {
+    return (col >> 6) * (ROWS * 128) + kc_off(row, (col & 63) >> 3) + (col & 7) * 2;
+}
+// The same for an epilogue that walks a lane's accumulator registers: element (row 32 mi + acc_row(r, lh), column cip) sits at
+// obase[sel(r)] + a compile-time offset.  The swizzle term (row>>1)&7 of that row is ((r>>1)&1) | lh<<1 | ((r>>2)&1)<<2, i.e. a
+// lane part and 4 register cases.
+template <int ROWS>
+__device__ __forceinline__ void img_col_bases(int (&obase)[4], int cip, int lh) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        obase[i] = (cip >> 6) * (ROWS * 128) + lh * 512 + (((((cip & 63) >> 3) ^ (lh << 1)) ^ ((i & 1) | ((i >> 1) << 2))) << 4) + (cip & 7) * 2;
+}
+__device__ __forceinline__ int img_elem_off(const int (&obase)[4], int mi, int r) {
+    return obase[((r >> 1) & 1) | (((r >> 2) & 1) << 1)] + (mi * 32 + acc_row(r, 0)) * 128;
+}
+
 // Stand-alone loss head on the matrix cores for feature layers the chain cannot hold (wider than 256 columns; BASELINE
 // configs[4]: 4096): the three products of chain_head over 64-row blocks, the feature dimension walked in 256-column chunks.
 // feat % 256 == 0; bf16 features; segment kinds LAB / UNL / FAKE (training); mask = the feature layer's lane-native relu mask.

@@ -47,6 +47,9 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
+// row inside a 32x32 MFMA accumulator tile that register r of a lane in half lh = lane >> 5 holds (its column is lane & 31)
+__host__ __device__ constexpr int acc_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
+
 // activation codes shared by host and device
 enum { ACT_LINEAR = 0, ACT_RELU = 1, ACT_SOFTPLUS = 2 };
 // column-sum modes of the GEMM epilogues

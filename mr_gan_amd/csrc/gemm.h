@@ -165,7 +165,7 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
                 const int col = col_blk + (wn * NR + ni) * 32 + lc;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = row_blk + (wm * MR + mi) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int row = row_blk + (wm * MR + mi) * 32 + acc_row(r, lh);
                     if (row < M && col < g.N) dst[(long)row * e.ldo + col] = acc[mi][ni][r];
                 }
             }

@@ -13,6 +13,7 @@
 
 #include "chain.h"
 #include "gemm.h"
+#include "head.h"
 
 namespace mrgan {
 namespace {
@@ -20,12 +21,6 @@ namespace {
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
-__device__ __forceinline__ int kc_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-// byte offset of element (row, col) inside an activation image
-template <int ROWS = CH_ROWS>
-__device__ __forceinline__ int act_off(int row, int col) {
-    return (col >> 6) * (ROWS * 128) + kc_off(row, (col & 63) >> 3) + (col & 7) * 2;
-}
 __device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rs, char* lds_dst, int voff, int soff) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)lds_dst, 16, voff, soff, 0, 0);
 }
@@ -118,15 +113,8 @@ __device__ __forceinline__ void flush_copy(Stream& sm, int rows_valid, int t) {
 //   4. dL/d(pre5) for the wave's 32 feature columns: one 16-deep k-step (8 classes + 8 zeros) x 6 addend pairs, masked with
 //      the relu bits the D5 forward epilogue left in registers, written as the next product's A image (+ bias-gradient sums)
 //   5. dW6^T [class][feature] = dlogits^T F for the wave's 32 features: F enters through the transposing LDS read
+// The products, the row arithmetic and the LDS hand-over between them are head.h's; what is here is this kernel's staging.
 // ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void split3(float v, __bf16& hi, __bf16& mid, __bf16& lo) {
-    hi = (__bf16)v;
-    float r = v - (float)hi;            // exact: the remainder of a round-to-nearest has at most 16 significant bits
-    mid = (__bf16)r;
-    r -= (float)mid;                    // exact: at most 8 significant bits remain
-    lo = (__bf16)r;
-}
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4_t;
 
 // what the head reads from global memory, fetched in the kernel's prologue: inside the head each of these would be an exposed
 // L2 / HBM round trip with the whole block waiting at the next barrier (the labels even two dependent ones)
@@ -161,7 +149,6 @@ __device__ __forceinline__ void chain_head(const ChainArgs& a, char* lds, Stream
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int kind = h.seg_kind[seg];
     const int blk = seg * nrb + rb;
-    const bf16x8 zero8 = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
 
     if (!(a.ablate & CH_ABL_COPY)) flush_copy(sm, rows_valid, t);      // the feature image -> HBM (no DMA wait follows inside the head)
     // ---- 1. W6: thread <-> feature ----
@@ -176,7 +163,7 @@ __device__ __forceinline__ void chain_head(const ChainArgs& a, char* lds, Stream
         }
     }
     // B operand of product 4 (k = class, column = feature 32 wave + lc): the eight class weights of this lane's feature
-    bf16x8 bw[3] = {zero8, zero8, zero8};
+    bf16x8 bw[3] = {zero8(), zero8(), zero8()};
     {
         const int j = wave * 32 + lc;
         const f32x4 w0 = hi.bw0, w1 = hi.bw1;
@@ -201,24 +188,16 @@ __device__ __forceinline__ void chain_head(const ChainArgs& a, char* lds, Stream
         for (int u = 0; u < 2; ++u) {
             const int kg = 2 * wave + u;                      // k-step: features 16 kg .. 16 kg + 15
             if (16 * kg < h.feat) {                           // (wave-uniform)
-                const char* As = fimg + (kg >> 2) * (CH_ROWS * 128);
-                const int ch = (kg & 3) * 2 + lh;
-                const bf16x8 fa0 = *(const bf16x8*)(As + kc_off(lc, ch)), fa1 = *(const bf16x8*)(As + kc_off(32 + lc, ch));
+                bf16x8 fb[3];
 #pragma unroll
                 for (int p = 0; p < 3; ++p) {
-                    bf16x8 fb = *(const bf16x8*)(w6t + (p * KMAX + (lc & (KMAX - 1))) * CH_PW + 16 * kg + 8 * lh);
-                    if (lc >= KMAX) fb = zero8;               // columns 8 .. 31 of the product are padding
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa0, fb, acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa1, fb, acc[1], 0, 0, 0);
+                    fb[p] = *(const bf16x8*)(w6t + (p * KMAX + (lc & (KMAX - 1))) * CH_PW + 16 * kg + 8 * lh);
+                    if (lc >= KMAX) fb[p] = zero8();          // columns 8 .. 31 of the product are padding
                 }
+                head_logits_step(acc, fimg, kg, fb, lc, lh);
             }
         }
-        if (lc < KMAX) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) lpart[(wave * CH_ROWS + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * KMAX + lc] = acc[mi][r];
-        }
+        head_logits_scatter(acc, lpart, wave, lc, lh);
     }
     lds_barrier();
 
@@ -227,111 +206,23 @@ __device__ __forceinline__ void chain_head(const ChainArgs& a, char* lds, Stream
     if (wave == 0) {
         const int r = lane;
         float l[KMAX];
+        head_logits_gather(lpart, r, l);
+        float b[KMAX], loss0, loss1, err, dl[KMAX];
 #pragma unroll
-        for (int c = 0; c < KMAX; ++c) l[c] = 0.f;
-#pragma unroll
-        for (int w = 0; w < CH_THREADS / 64; ++w) {
-            const f32x4 p0 = *(const f32x4*)(lpart + (w * CH_ROWS + r) * KMAX), p1 = *(const f32x4*)(lpart + (w * CH_ROWS + r) * KMAX + 4);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { l[c] += p0[c]; l[4 + c] += p1[c]; }
-        }
-        const bool rowvalid = r < rows_valid;
-        float mx = -3.0e38f;
-#pragma unroll
-        for (int c = 0; c < KMAX; ++c) {
-            if (c < h.classes) { l[c] += (c < 4 ? hi.b0[c & 3] : hi.b1[c & 3]); mx = fmaxf(mx, l[c]); }
-        }
-        int am = 0;
-        float se = 0.f, p[KMAX];
-#pragma unroll
-        for (int c = KMAX - 1; c >= 0; --c) {
-            p[c] = (c < h.classes) ? expf(l[c] - mx) : 0.f;
-            se += p[c];
-            if (c < h.classes && l[c] == mx) am = c;          // ties -> first index (theano argmax)
-        }
-        const float lse = mx + logf(se);
-        const float inv_se = 1.0f / se;
-        float loss0 = 0.f, loss1 = 0.f, err = 0.f;
-        float dl[KMAX];
-#pragma unroll
-        for (int c = 0; c < KMAX; ++c) dl[c] = 0.f;
-        if (rowvalid) {
-            if (kind == HEAD_LAB) {
-                const int y = hi.label;
-                err = (am != y) ? 1.f : 0.f;
-                float ly = 0.f;
-#pragma unroll
-                for (int c = 0; c < KMAX; ++c) {
-                    if (c == y) ly = l[c];
-                    dl[c] = (p[c] * inv_se - (c == y ? 1.f : 0.f)) * h.inv_count;
-                }
-                loss0 = lse - ly;
-            } else {
-                const float sg = sigmoid_f(lse), sp = softplus_f(lse);
-                const float k = 0.5f * h.inv_count * h.unl_weight * (kind == HEAD_UNL ? (sg - 1.0f) : sg);
-                loss1 = (kind == HEAD_UNL) ? 0.5f * (sp - lse) : 0.5f * sp;
-#pragma unroll
-                for (int c = 0; c < KMAX; ++c) dl[c] = k * p[c] * inv_se;
-            }
-        }
-        bf16x8 d3[3];
-#pragma unroll
-        for (int c = 0; c < KMAX; ++c) {
-            __bf16 p0, p1, p2;
-            split3(dl[c], p0, p1, p2);
-            d3[0][c] = p0; d3[1][c] = p1; d3[2][c] = p2;
-        }
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            *(bf16x8*)(dl_rc + (q * CH_ROWS + r) * KMAX) = d3[q];
-#pragma unroll
-            for (int c = 0; c < KMAX; ++c) dl_t[(q * KMAX + c) * CH_ROWS + r] = d3[q][c];
-        }
-        // the eleven per-row quantities whose sums over the 64 rows leave the block (three loss terms, db6 = column sums of
-        // dlogits): to LDS, row-contiguous; eleven lanes of the last wave add them up behind the barrier (as wave-wide shuffle
-        // reductions -- eleven six-step ds_bpermute chains on this one wave -- they cost ~3 us with the other seven waves waiting)
-        red[0 * CH_ROWS + r] = loss0; red[1 * CH_ROWS + r] = loss1; red[2 * CH_ROWS + r] = err;
-#pragma unroll
-        for (int c = 0; c < KMAX; ++c) red[(3 + c) * CH_ROWS + r] = dl[c];
+        for (int c = 0; c < KMAX; ++c) b[c] = c < 4 ? hi.b0[c & 3] : hi.b1[c & 3];
+        head_row<false>(l, b, kind, hi.label, h.classes, h.inv_count, h.unl_weight, r < rows_valid, loss0, loss1, err, dl);
+        head_rows_to_lds(dl, loss0, loss1, err, r, dl_rc, dl_t, red);
     }
     lds_barrier();
 
     // ---- 4. dL/d(pre5) = (dlogits W6^T) * relu'(pre5) for columns 32 wave .. + 31: the next product's A image ----
     {
         f32x16 acc[2];
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mi][r] = 0.f;
         bf16x8 da[2][3];
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                da[mi][q] = *(const bf16x8*)(dl_rc + (q * CH_ROWS + mi * 32 + lc) * KMAX);
-                if (lh) da[mi][q] = zero8;                    // k = 8 .. 15: padding
-            }
-        // addend pairs down to 2^-24 of the product: (hi, hi) (hi, mid) (mid, hi) (hi, lo) (lo, hi) (mid, mid)
-        constexpr int PA[6] = {0, 0, 1, 0, 2, 1}, PB[6] = {0, 1, 0, 2, 0, 1};
-#pragma unroll
-        for (int i = 5; i >= 0; --i)                          // smallest terms first
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da[mi][PA[i]], bw[PB[i]], acc[mi], 0, 0, 0);
+        head_load_dl_rows(dl_rc, lc, lh, da);
+        head_dpre_product(acc, da, bw);
         const int cip = wave * 32 + lc;
-        int obase[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            obase[i] = (cip >> 6) * (CH_ROWS * 128) + lh * 512 + (((((cip & 63) >> 3) ^ (lh << 1)) ^ ((i & 1) | ((i >> 1) << 2))) << 4) + (cip & 7) * 2;
-        float s1 = 0.f;
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float av = acc[mi][r];
-                const float v = ((mw[0][mi] >> r) & 1u) ? av : 0.f;         // (a select: see chain_gemm)
-                s1 += v;
-                *(__bf16*)(oimg + obase[((r >> 1) & 1) | (((r >> 2) & 1) << 1)] + (mi * 32 + (r & 3) + 8 * (r >> 2)) * 128) = (__bf16)v;
-            }
+        float s1 = head_dpre_to_image(acc, mw[0], oimg, cip, lh);
         s1 += __shfl_xor(s1, 32, 64);
         if (lh == 0 && cip < h.feat) part_row[h.off_dbf + cip] = s1;       // bias gradient of the feature layer
     }
@@ -340,37 +231,16 @@ __device__ __forceinline__ void chain_head(const ChainArgs& a, char* lds, Stream
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        const int g4 = lane >> 4, i16 = lane & 15, q = i16 >> 2, pp = i16 & 3;
-        const int f0 = wave * 32 + (g4 & 1) * 16 + 4 * pp;
 #pragma unroll
         for (int ks = 0; ks < CH_ROWS / 16; ++ks) {
-            // B fragment: eight consecutive rows (k) of this lane's feature column, by the transposing read
-            const int m0 = ks * 16 + (g4 >> 1) * 8 + q;
-            const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(fimg + act_off(m0, f0)));
-            const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(fimg + act_off(m0 + 4, f0)));
-            const bf16x8 fb = __builtin_bit_cast(bf16x8, __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7));
-#pragma unroll
-            for (int p = 2; p >= 0; --p) {
-                bf16x8 fa = *(const bf16x8*)(dl_t + (p * KMAX + (lc & (KMAX - 1))) * CH_ROWS + 16 * ks + 8 * lh);
-                if (lc >= KMAX) fa = zero8;
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc, 0, 0, 0);
-            }
+            bf16x8 fa[3];
+            head_load_dl_cols(dl_t, ks, lc, lh, fa);
+            head_dw6t_step(acc, fimg, ks, fa, wave, lane);
         }
         const int j = wave * 32 + lc;                         // registers 0 .. 3 = classes 4 lh .. 4 lh + 3 of feature j
         if (j < h.feat) *(f32x4*)(part_row + (long)j * KMAX + 4 * lh) = (f32x4){acc[0], acc[1], acc[2], acc[3]};
     }
-    if (wave == CH_THREADS / 64 - 1 && lane < 3 + KMAX) {
-        float s4[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < CH_ROWS / 4; ++i) {
-            const f32x4 v = *(const f32x4*)(red + lane * CH_ROWS + 4 * i);
-            s4[i & 3] += (v[0] + v[1]) + (v[2] + v[3]);
-        }
-        const float tot = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-        if (lane < 3) h.loss_part[blk * 4 + lane] = tot;
-        else part_row[h.off_db + lane - 3] = tot;
-        if (lane == 0) h.loss_part[blk * 4 + 3] = 0.f;
-    }
+    head_block_sums(red, h, blk, part_row, wave, lane);
     lds_barrier();
     // dL/d(pre5): the next product's A image is complete; its copy for the weight-gradient launch leaves at the end of that
     // product's k-loop
@@ -602,19 +472,15 @@ __device__ __forceinline__ void chain_gemm(const ChainArgs& a, const ChainOp& op
         // ---- epilogue: bias / relu / mask / noise, bf16 into the output image, column sums ----
         char* oimg = lds + o_off;
         const int cip = wave * 32 + lc;                    // column inside the pass = column of the output image
-        // element (row, cip) of the image sits at obase[sel(r)] + a compile-time offset: the swizzle term (row>>1)&7 of
-        // row = 32 mi + (r&3) + 8 (r>>2) + 4 lh is  ((r>>1)&1) | lh<<1 | ((r>>2)&1)<<2, i.e. a lane part and 4 register cases
         int obase[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            obase[i] = (cip >> 6) * (ROWS * 128) + lh * 512 + (((((cip & 63) >> 3) ^ (lh << 1)) ^ ((i & 1) | ((i >> 1) << 2))) << 4) + (cip & 7) * 2;
+        img_col_bases<ROWS>(obase, cip, lh);
         const float sig = (noisy && colvalid) ? (GAUSS ? op.sigma : op.sigma * NOISE_SCALE) : 0.f;
         float s1 = 0.f;
         auto ostore = [&](int mi, int r, float o) {
 #ifdef MRGAN_CH_NO_OSTORE       // timing experiment (compile-time: a run-time test per element perturbs the epilogue it measures)
             asm volatile("" :: "v"(o)); return;
 #endif
-            *(__bf16*)(oimg + obase[((r >> 1) & 1) | (((r >> 2) & 1) << 1)] + (mi * 32 + (r & 3) + 8 * (r >> 2)) * 128) = (__bf16)o;
+            *(__bf16*)(oimg + img_elem_off(obase, mi, r)) = (__bf16)o;
         };
         if (a.ablate & CH_ABL_EPI) {
             if (acc[0][0] == 12345.678f) ostore(0, 0, s1);
@@ -664,7 +530,7 @@ __device__ __forceinline__ void chain_gemm(const ChainArgs& a, const ChainOp& op
 #pragma unroll
                 for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) s1 += (mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh < rows_valid) ? acc[mi][r] : 0.f;
+                    for (int r = 0; r < 16; ++r) s1 += (mi * 32 + acc_row(r, lh) < rows_valid) ? acc[mi][r] : 0.f;
             }
             s1 += __shfl_xor(s1, 32, 64);
             if (lh == 0 && col < op.ldcs) op.cs[((long)seg * nrb + rb) * op.ldcs + col] = s1;
@@ -871,7 +737,6 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
     const int seg = blockIdx.y, rb = blockIdx.x, nrb = gridDim.x, kind = h.seg_kind[seg];
     const int row_blk = rb * CH_ROWS, rows_valid = min(CH_ROWS, h.rows - row_blk), blk = seg * nrb + rb;
     const int nch = h.feat / CH_PW;
-    const bf16x8 zero8 = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
 
     // ---- feature chunks by LDS-DMA: [4 k-tiles][64 rows][64 k] with the chain's swizzle; rows >= h.rows arrive as zeros ----
     const __bf16* fseg = (const __bf16*)h.f + (long)seg * h.f_bs;
@@ -898,7 +763,7 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
                 const bf16x8 v = *(const bf16x8*)(a.w6c + ((long)p * KMAX + (lc & (KMAX - 1))) * h.feat + c * CH_PW + 16 * (2 * wave + u) + 8 * lh);
-                fb[u][p] = lc < KMAX ? v : zero8;             // columns 8 .. 31 of the product are padding
+                fb[u][p] = lc < KMAX ? v : zero8();             // columns 8 .. 31 of the product are padding
             }
     };
 
@@ -923,25 +788,10 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
         if (c + 1 < nch) { issue_chunk(c + 1); load_w6c(c + 1, fbn); }
         const char* fimg = lds + (c & 1) * HW_FIMG;
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int kg = 2 * wave + u;
-            const char* As = fimg + (kg >> 2) * (CH_ROWS * 128);
-            const int ch = (kg & 3) * 2 + lh;
-            const bf16x8 fa0 = *(const bf16x8*)(As + kc_off(lc, ch)), fa1 = *(const bf16x8*)(As + kc_off(32 + lc, ch));
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                lacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa0, fb[u][p], lacc[0], 0, 0, 0);
-                lacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa1, fb[u][p], lacc[1], 0, 0, 0);
-            }
-        }
+        for (int u = 0; u < 2; ++u) head_logits_step(lacc, fimg, 2 * wave + u, fb[u], lc, lh);
     }
     float* lpart = (float*)xreg;                              // [8 waves][CH_ROWS][KMAX]
-    if (lc < KMAX) {
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) lpart[(wave * CH_ROWS + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * KMAX + lc] = lacc[mi][r];
-    }
+    head_logits_scatter(lacc, lpart, wave, lc, lh);
     lds_barrier();
     // the chunk before the last one is needed next (pass 2 walks downwards): its image is free now
     if (nch > 1) issue_chunk(nch - 2);
@@ -950,108 +800,35 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
     float* part_row = h.part + (long)blk * h.part_stride;
     if (wave == 0) {
         const int r = lane;
-        float l[KMAX];
-#pragma unroll
-        for (int c = 0; c < KMAX; ++c) l[c] = 0.f;
-#pragma unroll
-        for (int w = 0; w < CH_THREADS / 64; ++w) {
-            const f32x4 p0 = *(const f32x4*)(lpart + (w * CH_ROWS + r) * KMAX), p1 = *(const f32x4*)(lpart + (w * CH_ROWS + r) * KMAX + 4);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { l[c] += p0[c]; l[4 + c] += p1[c]; }
-        }
         const bool rowvalid = r < rows_valid;
-        float mx = -3.0e38f;
+        float l[KMAX];
+        head_logits_gather(lpart, r, l);
+        float b[KMAX];
 #pragma unroll
-        for (int c = 0; c < KMAX; ++c) {
-            if (c < h.classes) { l[c] += h.b[c]; mx = fmaxf(mx, l[c]); }
+        for (int c = 0; c < KMAX; ++c) b[c] = (c < h.classes) ? h.b[c] : 0.f;
+        int y = 0;
+        if (rowvalid && kind == HEAD_LAB) {
+            const long lo = h.labels_stream ? (long)h.st->batch * h.rows : 0;
+            y = h.labels[lo + row_blk + r];
         }
-        int am = 0;
-        float se = 0.f, p[KMAX];
+        float loss0, loss1, err, dl[KMAX];
+        head_row<false>(l, b, kind, y, h.classes, h.inv_count, h.unl_weight, rowvalid, loss0, loss1, err, dl);
+        if (rowvalid && h.logits) {
+            float* lp = h.logits + (long)seg * h.logits_bs + (long)(row_blk + r) * KMAX;
 #pragma unroll
-        for (int c = KMAX - 1; c >= 0; --c) {
-            p[c] = (c < h.classes) ? expf(l[c] - mx) : 0.f;
-            se += p[c];
-            if (c < h.classes && l[c] == mx) am = c;          // ties -> first index (theano argmax)
+            for (int c = 0; c < KMAX; ++c) lp[c] = (c < h.classes) ? l[c] : 0.f;
         }
-        const float lse = mx + logf(se);
-        const float inv_se = 1.0f / se;
-        float loss0 = 0.f, loss1 = 0.f, err = 0.f;
-        float dl[KMAX];
-#pragma unroll
-        for (int c = 0; c < KMAX; ++c) dl[c] = 0.f;
-        if (rowvalid) {
-            if (kind == HEAD_LAB) {
-                const long lo = h.labels_stream ? (long)h.st->batch * h.rows : 0;
-                const int y = h.labels[lo + row_blk + r];
-                err = (am != y) ? 1.f : 0.f;
-                float ly = 0.f;
-#pragma unroll
-                for (int c = 0; c < KMAX; ++c) {
-                    if (c == y) ly = l[c];
-                    dl[c] = (p[c] * inv_se - (c == y ? 1.f : 0.f)) * h.inv_count;
-                }
-                loss0 = lse - ly;
-            } else {
-                const float sg = sigmoid_f(lse), sp = softplus_f(lse);
-                const float k = 0.5f * h.inv_count * h.unl_weight * (kind == HEAD_UNL ? (sg - 1.0f) : sg);
-                loss1 = (kind == HEAD_UNL) ? 0.5f * (sp - lse) : 0.5f * sp;
-#pragma unroll
-                for (int c = 0; c < KMAX; ++c) dl[c] = k * p[c] * inv_se;
-            }
-            if (h.logits) {
-                float* lp = h.logits + (long)seg * h.logits_bs + (long)(row_blk + r) * KMAX;
-#pragma unroll
-                for (int c = 0; c < KMAX; ++c) lp[c] = (c < h.classes) ? l[c] : 0.f;
-            }
-        }
-        bf16x8 d3[3];
-#pragma unroll
-        for (int c = 0; c < KMAX; ++c) {
-            __bf16 p0, p1, p2;
-            split3(dl[c], p0, p1, p2);
-            d3[0][c] = p0; d3[1][c] = p1; d3[2][c] = p2;
-        }
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            *(bf16x8*)(dl_rc + (q * CH_ROWS + r) * KMAX) = d3[q];
-#pragma unroll
-            for (int c = 0; c < KMAX; ++c) dl_t[(q * KMAX + c) * CH_ROWS + r] = d3[q][c];
-        }
-        red[0 * CH_ROWS + r] = loss0; red[1 * CH_ROWS + r] = loss1; red[2 * CH_ROWS + r] = err;
-#pragma unroll
-        for (int c = 0; c < KMAX; ++c) red[(3 + c) * CH_ROWS + r] = dl[c];
+        head_rows_to_lds(dl, loss0, loss1, err, r, dl_rc, dl_t, red);
     }
     lds_barrier();
-    if (wave == CH_THREADS / 64 - 1 && lane < 3 + KMAX) {     // the eleven sums over the block's rows that leave it
-        float s4[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < CH_ROWS / 4; ++i) {
-            const f32x4 v = *(const f32x4*)(red + lane * CH_ROWS + 4 * i);
-            s4[i & 3] += (v[0] + v[1]) + (v[2] + v[3]);
-        }
-        const float tot = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-        if (lane < 3) h.loss_part[blk * 4 + lane] = tot;
-        else part_row[h.off_db + lane - 3] = tot;
-        if (lane == 0) h.loss_part[blk * 4 + 3] = 0.f;
-    }
+    head_block_sums(red, h, blk, part_row, wave, lane);
 
     // =========================== pass 2: dL/d(pre5) and dW6^T, chunk by chunk ===========================
     // A operands that do not depend on the chunk, in registers for the whole pass
     bf16x8 da[2][3], dt[4][3];
+    head_load_dl_rows(dl_rc, lc, lh, da);
 #pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            da[mi][q] = *(const bf16x8*)(dl_rc + (q * CH_ROWS + mi * 32 + lc) * KMAX);
-            if (lh) da[mi][q] = zero8;                        // k = 8 .. 15: padding
-        }
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            dt[ks][q] = *(const bf16x8*)(dl_t + (q * KMAX + (lc & (KMAX - 1))) * CH_ROWS + 16 * ks + 8 * lh);
-            if (lc >= KMAX) dt[ks][q] = zero8;
-        }
+    for (int ks = 0; ks < 4; ++ks) head_load_dl_cols(dl_t, ks, lc, lh, dt[ks]);
     const uint16_t* mseg = a.mask + (long)seg * a.mask_bs;
     // per chunk: the W6 rows of this lane's feature as bf16 addends (B operand, k = class) and the relu-mask words of its column
     auto load_chunk_inputs = [&](int c, bf16x8 (&bw)[3], uint32_t (&mw)[2]) {
@@ -1059,7 +836,7 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             const bf16x8 v = *(const bf16x8*)(a.w6r + ((long)q * h.feat + col) * KMAX);
-            bw[q] = lh ? zero8 : v;                           // lh = 1: k = 8 .. 15, zeros
+            bw[q] = lh ? zero8() : v;                           // lh = 1: k = 8 .. 15, zeros
         }
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
@@ -1089,15 +866,7 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
         // ---- dL/d(pre5) = (dlogits W6^T) * relu'(pre5): one 16-deep k-step x 6 addend pairs ----
         {
             f32x16 acc[2];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mi][r] = 0.f;
-            constexpr int PA[6] = {0, 0, 1, 0, 2, 1}, PB[6] = {0, 1, 0, 2, 0, 1};
-#pragma unroll
-            for (int i = 5; i >= 0; --i)                      // smallest terms first
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi) acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da[mi][PA[i]], bw[PB[i]], acc[mi], 0, 0, 0);
+            head_dpre_product(acc, da, bw);
             float s1 = 0.f;
             if constexpr (Q8) {
                 unsigned char* timg = (unsigned char*)xreg;
@@ -1122,20 +891,7 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
                         *(uint32_t*)(rimg + (rl + kq) * HW_RPITCH + (cip - kq)) = quad_byte_transpose(w);
                     }
             } else {
-                char* oimg = xreg;
-                int obase[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    obase[i] = (cip >> 6) * (CH_ROWS * 128) + lh * 512 + (((((cip & 63) >> 3) ^ (lh << 1)) ^ ((i & 1) | ((i >> 1) << 2))) << 4) + (cip & 7) * 2;
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float av = acc[mi][r];
-                        const float v = ((mw[mi] >> r) & 1u) ? av : 0.f;
-                        s1 += v;
-                        *(__bf16*)(oimg + obase[((r >> 1) & 1) | (((r >> 2) & 1) << 1)] + (mi * 32 + (r & 3) + 8 * (r >> 2)) * 128) = (__bf16)v;
-                    }
+                s1 = head_dpre_to_image(acc, mw, xreg, cip, lh);
             }
             s1 += __shfl_xor(s1, 32, 64);
             if (lh == 0) part_row[h.off_dbf + c0 + cip] = s1;                   // bias gradient of the feature layer
@@ -1145,17 +901,8 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            const int g4 = lane >> 4, i16 = lane & 15, q = i16 >> 2, pp = i16 & 3;
-            const int f0 = wave * 32 + (g4 & 1) * 16 + 4 * pp;
 #pragma unroll
-            for (int ks = 0; ks < CH_ROWS / 16; ++ks) {
-                const int m0 = ks * 16 + (g4 >> 1) * 8 + q;
-                const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(fimg + act_off(m0, f0)));
-                const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(fimg + act_off(m0 + 4, f0)));
-                const bf16x8 fb = __builtin_bit_cast(bf16x8, __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7));
-#pragma unroll
-                for (int p = 2; p >= 0; --p) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dt[ks][p], fb, acc, 0, 0, 0);
-            }
+            for (int ks = 0; ks < CH_ROWS / 16; ++ks) head_dw6t_step(acc, fimg, ks, dt[ks], wave, lane);
             *(f32x4*)(part_row + (long)(c0 + cip) * KMAX + 4 * lh) = (f32x4){acc[0], acc[1], acc[2], acc[3]};
         }
         lds_barrier();                                        // the output image(s) of the chunk are complete
