@@ -12,6 +12,7 @@
 #pragma once
 #include "aux_kernels.h"
 #include "common.h"
+#include "lds_ring.h"
 
 namespace mrgan {
 
@@ -77,8 +78,7 @@ struct ChainArgs {
 
 int launch_chain(const ChainArgs& a, hipStream_t s);
 
-// ---- device side: the activation image [K/64 k-tiles][ROWS rows][64 k] bf16, 16-byte chunks XOR-swizzled per row ----
-__device__ __forceinline__ int kc_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
+// ---- device side: the activation image [K/64 k-tiles][ROWS rows][64 k] bf16, 16-byte chunks XOR-swizzled per row (kc_off) ----
 // byte offset of element (row, col) inside an activation image
 template <int ROWS = CH_ROWS>
 __device__ __forceinline__ int act_off(int row, int col) {

@@ -16,6 +16,8 @@
 #pragma once
 #include <string.h>
 
+#include <algorithm>
+
 #include "common.h"
 
 namespace mrgan {
@@ -521,5 +523,32 @@ inline GemmArgs gemm_dw_args(int K, int N, int vrows, int splits, int kchunk, in
 }
 // words between two segments of seg_rows rows in a lane-native relu mask of pitch ldm (2 x u16 per (32 rows, column))
 inline long mask_pitch(int seg_rows, int ldm) { return (long)(seg_rows / 32) * ldm * 2; }
+
+// ---- host side: launching ---------------------------------------------------------------------------------------------
+// The compile-time epilogue variant (VAR_* bits) a launch description asks for, or -1 where no kernel family builds one:
+// a dX product is specialised by its derivative alone (relu reads the mask), a forward product by activation, noise, mask
+// and noise generator -- masks are relu's, noisy relu layers always keep one, softplus (the feature-less output) has neither.
+// Each launcher switches over the values it instantiates and refuses the rest.
+inline int epi_variant(int epi, const Epi& e) {
+    if (e.act != ACT_LINEAR && e.act != ACT_RELU && e.act != ACT_SOFTPLUS) return -1;
+    if (epi != EPI_FWD) return e.act;
+    const bool noise = e.sigma > 0.f, mask = e.mask != nullptr;
+    if (e.act == ACT_RELU ? (noise && !mask) : (mask || (noise && e.act == ACT_SOFTPLUS))) return -1;
+    return e.act | (noise ? VAR_NOISE : 0) | (mask ? VAR_MASK : 0) | (noise && e.gauss ? VAR_GAUSS : 0);
+}
+// persistent blocks: at most as many as can be co-resident (LDS-limited) on the 256 CUs
+inline int persistent_grid(int tiles, int lds_bytes) { return std::min(tiles, 256 * std::max(1, (160 * 1024) / lds_bytes)); }
+// Launch KERN with LDS bytes of dynamic LDS, raising the kernel's limit first (once per device, DeviceOnce); -2 on failure.
+template <auto KERN, int LDS, typename... Args>
+int launch_with_dyn_lds(dim3 grid, dim3 block, hipStream_t s, const Args&... args) {
+    static_assert(LDS <= 160 * 1024, "LDS budget of a CU");
+    static DeviceOnce attr;
+    if (attr.first()) {
+        if (hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return -2;
+        attr.mark();
+    }
+    MRGAN_LAUNCH(KERN, grid, block, LDS, s, args...);
+    return 0;
+}
 
 }  // namespace mrgan

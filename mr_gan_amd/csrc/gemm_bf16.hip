@@ -10,17 +10,8 @@
 //        MFMA fragments (8 consecutive k for one row/col) are gathered with the hardware transposing
 //        LDS read ds_read_b64_tr_b16 from a [k][free] image.
 //
-// Staging is LDS-DMA: `buffer_load_dwordx4 ... offen lds` (16 B per lane, 1 KiB per wave-instruction)
-// straight from HBM/L2 into a double-buffered LDS image -- no VGPR round trip, no ds_write pass.
-//   * the LDS destination of a wave-instruction is lane-linear, so the bank-conflict swizzle is applied
-//     to the per-lane SOURCE address and undone by the same XOR on the fragment read;
-//   * the k-offset of a tile is the instruction's SGPR offset: advancing a tile costs no VALU;
-//   * rows past the end of an operand fall outside the buffer descriptor's range and arrive as zeros,
-//     which is what makes ragged M / N safe without per-lane predicates;
-//   * one raw s_barrier per k-tile: wait own loads (vmcnt(0)) -> barrier -> issue tile t+1 -> MFMA on
-//     tile t, so the next tile's loads are in flight under this tile's MFMAs.
-// Tile order is XCD-aware: consecutive block ids round-robin over the 8 XCDs, so each XCD is handed a
-// contiguous run of tiles that share the same A row panel in its private L2.
+// Staging is LDS-DMA into an XOR-swizzled LDS ring, one raw s_barrier per k-tile, persistent blocks in XCD-aware tile
+// order: the scheme, its helpers, the tile order and the ring main loop of both LDS-DMA kernels are lds_ring.h's.
 //
 // KC: the block tiles and the measured table that picks one are listed in one place, above launch_kc_tile.
 // KS: 128 x 128 x 64 blocks of 8 waves (64x32 each).
@@ -31,43 +22,18 @@
 #include <string>
 
 #include "gemm.h"
+#include "lds_ring.h"
 
 namespace mrgan {
 
 namespace {
-constexpr int BN = 128, BK = 64;
+constexpr int BN = 128, BK = RING_BK;
 constexpr int KS_PITCH = 320;                   // register-staged KS image: 256 data + 64 pad bytes per k-row
 constexpr int KS_TILE_BYTES = 64 * KS_PITCH;
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ int kc_off(int row, int chunk) {
-    // 16-B chunk `chunk` (0..7) of row `row`; (row>>1)&7 spreads the 16 rows of a ds_read_b128
-    // lane group over all sixteen 16-B slots of the 256-B bank row
-    return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-}
-
-// XCD-aware tile index: blocks b and b+8 share an XCD, so give XCD x the tiles [x*nt/8, (x+1)*nt/8)
-__device__ __forceinline__ int xcd_tile(int bid, int nt) {
-    return (nt & 7) == 0 ? (bid & 7) * (nt >> 3) + (bid >> 3) : bid;
-}
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rs, char* lds_dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)lds_dst, 16, voff, soff, 0, 0);
-}
 
 // =====================================================================================================
 // KC: forward and input-gradient products
 // =====================================================================================================
-// counted wait: all but the newest `n` LDS-DMA groups of LPT instructions each have landed
-template <int LPT>
-__device__ __forceinline__ void wait_groups(int n) {
-    if (n >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPT) : "memory");
-    else if (n == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPT) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
 // Block tile BM x BNT, WM x WN waves (each (BM/WM) x (BNT/WN), as MR x NR accumulators of 32x32), NS-stage ring.
 // LDS-DMA issue is the scarce resource of this loop (~60-100 issue cycles per 1 KiB wave-instruction), so the
 // achievable MFMA share grows with the tile's arithmetic intensity BM*BNT/(BM+BNT): 64x128 -> 43, 128x128 -> 64,
@@ -88,12 +54,11 @@ __device__ __forceinline__ void kc_tile(const GemmArgs& g, const int batch, cons
     constexpr int MR = BM / WM / 32, NR = BNT / WN / 32;   // 32x32 accumulators per wave
     constexpr int A_BYTES = BM * 128, B_BYTES = BNT * 128, STAGE = A_BYTES + B_BYTES;
     constexpr int A_INSTR = BM / 8 / NW, B_INSTR = BNT / 8 / NW;   // wave-instructions per wave per k-tile (8 rows each)
-    static_assert(NS >= 2 && NS <= 4, "ring depth");
     static_assert(MR >= 1 && NR >= 1 && A_INSTR >= 1 && B_INSTR >= 1 && BM % (8 * NW) == 0 && BNT % (8 * NW) == 0, "tile/wave layout");
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    const int lrow = lane >> 3, lp = lane & 7;       // lane -> (row within an instruction's 8 rows, 16-B chunk)
+    const int lrow = lane >> 3, lp = lane & 7;
     const int lr = lane & 31, lh = lane >> 5;
     const int nk = (g.e.ablate & 4) ? 0 : g.K / BK;
 #ifdef MRGAN_STAMPS
@@ -129,11 +94,10 @@ __device__ __forceinline__ void kc_tile(const GemmArgs& g, const int batch, cons
             for (int i = 0; i < B_INSTR; ++i) glds16(rsB, b_dst + i * 1024, voffB[i], k0 * 2);
         };
 
-        // ring of NS stages, tiles are issued NS-1 ahead of their use (the previous tile's epilogue ended with a
-        // barrier, so the ring is free)
 #pragma unroll
         for (int p = 0; p < NS - 1; ++p)
             if (p < nk) issue(p * BK, p);
+
 
         // DX epilogues that read e.h element-wise (softplus derivative, xhat sums: one column per lane, rows strided)
         // get the block's tile of h copied into LDS behind the ring with 16-byte LDS-DMA loads; it lands under the main
@@ -171,45 +135,11 @@ __device__ __forceinline__ void kc_tile(const GemmArgs& g, const int batch, cons
         EpiPrefetch<MR, NR> pf;
         epilogue_prefetch<__bf16, EPI, MR, NR, VAR>(pf, g, batch, row_blk, col_blk, wm, wn, lane);
 
-        int buf = 0;
-        for (int kt = 0; kt < nk; ++kt) {
-            // vmcnt counts in issue order (stores of the previous tile and the prefetch loads are older than or as old
-            // as the group being waited for, so waiting for the group also retires them)
-            if (kt == 0) STAMP(0);                                        // tile setup + issue
-            wait_groups<A_INSTR + B_INSTR>(min(NS - 2, nk - 1 - kt));   // this wave's loads of k-tile kt have landed
-            __builtin_amdgcn_s_barrier();                                 // ... everyone's; everyone finished k-tile kt-1
-            asm volatile("" ::: "memory");
-            if (kt == 0) STAMP(1);                                        // first k-tile landed (pipeline fill)
-            if (kt + NS - 1 < nk) {                                       // refill the stage read during k-tile kt-1
-                int nb = buf + NS - 1; if (nb >= NS) nb -= NS;
-                issue((kt + NS - 1) * BK, nb);
-            }
-            const char* As = lds + buf * STAGE;
-            const char* Bs = As + A_BYTES;
-            buf = (buf + 1 == NS) ? 0 : buf + 1;
-            // fragments of KG k-steps are fetched as one batch ahead of their MFMAs: the LDS latency is paid once per
-            // batch (counted lgkmcnt waits) instead of once per MFMA
-            constexpr int KG = (MR + NR <= 4) ? 4 : 2;
-#pragma unroll
-            for (int kg = 0; kg < BK / 16; kg += KG) {
-                bf16x8 a[KG][MR], b[KG][NR];
-#pragma unroll
-                for (int kk = 0; kk < KG; ++kk) {
-#pragma unroll
-                    for (int mi = 0; mi < MR; ++mi) a[kk][mi] = *(const bf16x8*)(As + kc_off((wm * MR + mi) * 32 + lr, (kg + kk) * 2 + lh));
-#pragma unroll
-                    for (int ni = 0; ni < NR; ++ni) b[kk][ni] = *(const bf16x8*)(Bs + kc_off((wn * NR + ni) * 32 + lr, (kg + kk) * 2 + lh));
-                }
-                __builtin_amdgcn_sched_barrier(0);       // keep the scheduler from re-serialising read -> wait -> MFMA
-#pragma unroll
-                for (int kk = 0; kk < KG; ++kk)
-#pragma unroll
-                    for (int mi = 0; mi < MR; ++mi)
-#pragma unroll
-                        for (int ni = 0; ni < NR; ++ni)
-                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kk][mi], b[kk][ni], acc[mi][ni], 0, 0, 0);
-            }
-        }
+#define KC_FRAG_A(As, mi, ks) *(const bf16x8*)(As + kc_off((wm * MR + mi) * 32 + lr, (ks) * 2 + lh))
+#define KC_FRAG_B(Bs, ni, ks) *(const bf16x8*)(Bs + kc_off((wn * NR + ni) * 32 + lr, (ks) * 2 + lh))
+        RING_MAINLOOP(NS, A_INSTR + B_INSTR, MR, NR, nk, acc, issue, 0, KC_FRAG_A, KC_FRAG_B, lds, STAGE, A_BYTES, STAMP)
+#undef KC_FRAG_A
+#undef KC_FRAG_B
         STAMP(2);               // main loop
         __syncthreads();
         STAMP(3);               // barrier after the main loop
@@ -240,8 +170,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kc_kernel(const GemmAr
     for (int tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
         const int tidx = xcd_tile(tl, ntiles);
         const int batch = tidx / (ntn * ntm), rem = tidx - batch * (ntn * ntm);
-        // large problems (operands beyond an XCD's L2): consecutive tiles form patches of 4 tile rows x 8 tile columns, so the
-        // CUs of one XCD fetch a third less distinct operand data per k-step than with plain row-major order (gemm_fp8.hip)
+        // large problems only (operands beyond an XCD's L2): patches of 4 tile rows (lds_ring.h, tile order)
         int tile_m, tile_n;
         if ((ntm & 3) == 0 && ntn >= 8 && g.K >= 2048) {
             const int grp = rem / (4 * ntn), in = rem - grp * (4 * ntn);
@@ -270,19 +199,8 @@ int launch_kc(const GemmArgs& g, hipStream_t s) {
     // staged output tile + column-sum scratch (+ the tile of e.h for the DX epilogues that read it)
     constexpr int OUT = BM * BNT * 2 + 4 * WM * BNT * 4;
     constexpr int LDS = (NS * STAGE > OUT ? NS * STAGE : OUT) + ((EPI == EPI_DX && (VAR & VAR_ACT_MASK) != ACT_RELU) ? BM * BNT * 2 : 0);
-    static_assert(LDS <= 160 * 1024, "LDS budget");
-    static DeviceOnce attr;
-    auto kern = gemm_bf16_kc_kernel<EPI, BM, BNT, WM, WN, NS, VAR>;
-    if (attr.first()) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return -2;
-        attr.mark();
-    }
-    // persistent blocks: at most as many as can be co-resident (LDS-limited) on the 256 CUs
     const int tiles = ceil_div(g.M, BM) * ceil_div(g.N, BNT) * g.nbatch;
-    const int per_cu = std::max(1, (160 * 1024) / LDS);
-    dim3 grid(std::min(tiles, 256 * per_cu));
-    MRGAN_LAUNCH(kern, grid, dim3(64 * WM * WN), LDS, s, g);
-    return 0;
+    return launch_with_dyn_lds<gemm_bf16_kc_kernel<EPI, BM, BNT, WM, WN, NS, VAR>, LDS>(dim3(persistent_grid(tiles, LDS)), dim3(64 * WM * WN), s, g);
 }
 
 // =====================================================================================================
@@ -317,8 +235,7 @@ __device__ __forceinline__ void ks_fast_body(const GemmArgs& g, const int bid) {
     const int ntn = (g.N + 127) / 128, ntm = (g.M + 127) / 128;
     const int tidx = xcd_tile(bid, ntn * ntm * g.splits);
     const int split = tidx / (ntn * ntm), rem = tidx - split * (ntn * ntm);
-    // wide layers: consecutive tiles (the 64 resident blocks of one XCD) form 8 x 8 patches instead of 2 x 32 strips, half
-    // the distinct operand columns per k-step into that XCD's L2 (as in the KC kernels)
+    // wide layers only: patches of 8 tile rows for the 64 resident blocks of an XCD (lds_ring.h, tile order)
     int tile_m, tile_n;
     if ((ntm & 7) == 0 && ntn >= 16) {
         const int grp = rem / (8 * ntn), in = rem - grp * (8 * ntn);
@@ -361,39 +278,13 @@ __device__ __forceinline__ void ks_fast_body(const GemmArgs& g, const int bid) {
 #pragma unroll
     for (int p = 0; p < NS - 1; ++p)
         if (p < nk) issue(k_begin + p * BK, p);
-    int buf = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        wait_groups<2 * T_INSTR>(min(NS - 2, nk - 1 - kt));
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (kt + NS - 1 < nk) {
-            int nb = buf + NS - 1; if (nb >= NS) nb -= NS;
-            issue(k_begin + (kt + NS - 1) * BK, nb);
-        }
-        const char* As = lds + buf * STAGE;
-        const char* Bs = As + T_BYTES;
-        buf = (buf + 1 == NS) ? 0 : buf + 1;
-        constexpr int KG = (MR + NR <= 4) ? 4 : 2;       // fragment batches, as in the KC kernel
-#pragma unroll
-        for (int kg = 0; kg < BK / 16; kg += KG) {
-            bf16x8 a[KG][MR], b[KG][NR];
-#pragma unroll
-            for (int kk = 0; kk < KG; ++kk) {
-#pragma unroll
-                for (int mi = 0; mi < MR; ++mi) a[kk][mi] = ks_frag_swz(As, (wm * MR + mi) * 32, kg + kk, lane);
-#pragma unroll
-                for (int ni = 0; ni < NR; ++ni) b[kk][ni] = ks_frag_swz(Bs, (wn * NR + ni) * 32, kg + kk, lane);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int kk = 0; kk < KG; ++kk)
-#pragma unroll
-                for (int mi = 0; mi < MR; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < NR; ++ni)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kk][mi], b[kk][ni], acc[mi][ni], 0, 0, 0);
-        }
-    }
+#define KS_FRAG_A(As, mi, ks) ks_frag_swz(As, (wm * MR + mi) * 32, ks, lane)
+#define KS_FRAG_B(Bs, ni, ks) ks_frag_swz(Bs, (wn * NR + ni) * 32, ks, lane)
+#define KS_NO_STAMP(i)
+    RING_MAINLOOP(NS, 2 * T_INSTR, MR, NR, nk, acc, issue, k_begin, KS_FRAG_A, KS_FRAG_B, lds, STAGE, T_BYTES, KS_NO_STAMP)
+#undef KS_FRAG_A
+#undef KS_FRAG_B
+#undef KS_NO_STAMP
     __syncthreads();
     epilogue<__bf16, EPI_SLAB, MR, NR, WM>(acc, g, 0, split, tile_m, row_blk, col_blk, wm, wn, lane, (float*)lds, BN);
 }
@@ -438,15 +329,8 @@ int launch_ks_fast(const GemmArgs& g, hipStream_t s) {
     static const std::string name = "gemm_bf16_ks_fast_kernel<" + std::to_string(NS) + ", " + std::to_string(WM) + ", " + std::to_string(WN) + ">";
     g_last_kernel = name.c_str();
     constexpr int STAGE = 2 * 64 * 256;
-    static DeviceOnce attr;
-    auto kern = gemm_bf16_ks_fast_kernel<NS, WM, WN>;
-    if (attr.first()) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, NS * STAGE) != hipSuccess) return -2;
-        attr.mark();
-    }
     dim3 grid(ceil_div(g.N, 128) * ceil_div(g.M, 128) * g.splits);
-    MRGAN_LAUNCH(kern, grid, dim3(64 * WM * WN), NS * STAGE, s, g);
-    return 0;
+    return launch_with_dyn_lds<gemm_bf16_ks_fast_kernel<NS, WM, WN>, NS * STAGE>(grid, dim3(64 * WM * WN), s, g);
 }
 
 // =====================================================================================================
@@ -602,26 +486,26 @@ static int launch_kc_tile(const GemmArgs& g, hipStream_t s) {
 }
 
 static int launch_kc_any(int epi, const GemmArgs& g, hipStream_t s) {
-    const Epi& e = g.e;
+    const int var = epi_variant(epi, g.e);
     if (epi == EPI_FWD) {
-        const bool noise = e.sigma > 0.f, mask = e.mask != nullptr;
-        // (the true-Gaussian variants exist beside the noisy ones only: every other instantiation is the default build's)
-        if (e.gauss && noise) {
-            if (e.act == ACT_RELU && mask) return launch_kc_tile<EPI_FWD, ACT_RELU | VAR_NOISE | VAR_MASK | VAR_GAUSS>(g, s);
-            if (e.act == ACT_LINEAR && !mask) return launch_kc_tile<EPI_FWD, ACT_LINEAR | VAR_NOISE | VAR_GAUSS>(g, s);
-            return -3;
+        switch (var) {
+            // (the true-Gaussian variants exist beside the noisy ones only: every other instantiation is the default build's)
+            case ACT_RELU | VAR_NOISE | VAR_MASK | VAR_GAUSS: return launch_kc_tile<EPI_FWD, ACT_RELU | VAR_NOISE | VAR_MASK | VAR_GAUSS>(g, s);
+            case ACT_LINEAR | VAR_NOISE | VAR_GAUSS: return launch_kc_tile<EPI_FWD, ACT_LINEAR | VAR_NOISE | VAR_GAUSS>(g, s);
+            case ACT_RELU | VAR_NOISE | VAR_MASK: return launch_kc_tile<EPI_FWD, ACT_RELU | VAR_NOISE | VAR_MASK>(g, s);
+            case ACT_RELU | VAR_MASK: return launch_kc_tile<EPI_FWD, ACT_RELU | VAR_MASK>(g, s);
+            case ACT_RELU: return launch_kc_tile<EPI_FWD, ACT_RELU>(g, s);
+            case ACT_LINEAR | VAR_NOISE: return launch_kc_tile<EPI_FWD, ACT_LINEAR | VAR_NOISE>(g, s);
+            case ACT_LINEAR: return launch_kc_tile<EPI_FWD, ACT_LINEAR>(g, s);
+            case ACT_SOFTPLUS: return launch_kc_tile<EPI_FWD, ACT_SOFTPLUS>(g, s);
+            default: return -3;
         }
-        if (e.act == ACT_RELU && noise && mask) return launch_kc_tile<EPI_FWD, ACT_RELU | VAR_NOISE | VAR_MASK>(g, s);
-        if (e.act == ACT_RELU && !noise && mask) return launch_kc_tile<EPI_FWD, ACT_RELU | VAR_MASK>(g, s);
-        if (e.act == ACT_RELU && !noise && !mask) return launch_kc_tile<EPI_FWD, ACT_RELU>(g, s);
-        if (e.act == ACT_LINEAR && !mask) return noise ? launch_kc_tile<EPI_FWD, ACT_LINEAR | VAR_NOISE>(g, s)
-                                                       : launch_kc_tile<EPI_FWD, ACT_LINEAR>(g, s);
-        if (e.act == ACT_SOFTPLUS && !noise && !mask) return launch_kc_tile<EPI_FWD, ACT_SOFTPLUS>(g, s);
-        return -3;
     }
-    if (e.act == ACT_RELU) return launch_kc_tile<EPI_DX, ACT_RELU>(g, s);
-    if (e.act == ACT_SOFTPLUS) return launch_kc_tile<EPI_DX, ACT_SOFTPLUS>(g, s);
-    return launch_kc_tile<EPI_DX, ACT_LINEAR>(g, s);
+    switch (var) {
+        case ACT_RELU: return launch_kc_tile<EPI_DX, ACT_RELU>(g, s);
+        case ACT_SOFTPLUS: return launch_kc_tile<EPI_DX, ACT_SOFTPLUS>(g, s);
+        default: return launch_kc_tile<EPI_DX, ACT_LINEAR>(g, s);
+    }
 }
 
 static bool ks_dense_k(const GemmArgs& g) {
@@ -655,13 +539,7 @@ int launch_gemm_bf16_dw_group(const GemmArgs* gs, int n, hipStream_t s, const ch
     // reads per MFMA): 64.7 us; 8 waves with a 3-stage ring, one block per CU: 89 us.  More resident waves hide the
     // barrier -> LDS read -> MFMA chain; the LDS read rate is not the limit at two blocks per CU.
     constexpr int STAGE = 2 * 64 * 256, LDS = 2 * STAGE;
-    static DeviceOnce attr;
-    auto kern = gemm_bf16_ks_group_kernel<2, 2, 4>;
-    if (attr.first()) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return -2;
-        attr.mark();
-    }
-    MRGAN_LAUNCH(kern, dim3(total), dim3(512), LDS, s, grp);
+    if (const int r = launch_with_dyn_lds<gemm_bf16_ks_group_kernel<2, 2, 4>, LDS>(dim3(total), dim3(512), s, grp)) return r;
     if (kname) *kname = "gemm_bf16_ks_group_kernel<2, 2, 4>";
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

@@ -1,12 +1,13 @@
 // Row-block chain kernel (see chain.h): consecutive dense products of one 64-row block inside one launch.
 //
 // One workgroup = 8 waves = one block of 64 rows of one segment.  The block's current activation is an LDS image
-// [K/64 k-tiles][64 rows][64 k] bf16 with the same XOR swizzle as the stand-alone forward kernel (gemm_bf16.hip), so the
+// [K/64 k-tiles][64 rows][64 k] bf16 with the XOR swizzle of the stand-alone forward kernels (lds_ring.h: kc_off), so the
 // MFMA A fragments are conflict-free ds_read_b128; the weights stream through a 2-stage ring of [256 columns][64 k] tiles
-// filled by LDS-DMA (buffer_load ... lds) from the XCD's L2.  Wave w owns output columns [32 w, 32 w + 32) of a 256-column
-// pass over all 64 rows (two 32x32 accumulators): its column sums need no cross-wave step, and the epilogue writes the
-// bf16 result straight into the LDS image that is the next product's A operand; a copy of it leaves for HBM in 16-byte
-// stores because the weight-gradient launch needs every layer's input and output gradient.
+// filled by LDS-DMA (lds_ring.h: glds16) from the XCD's L2 -- a per-wave, barrier-free ring of its own (BTile, wait_vm).
+// Wave w owns output columns [32 w, 32 w + 32) of a 256-column pass over all 64 rows (two 32x32 accumulators): its column
+// sums need no cross-wave step, and the epilogue writes the bf16 result straight into the LDS image that is the next
+// product's A operand; a copy of it leaves for HBM in 16-byte stores because the weight-gradient launch needs every
+// layer's input and output gradient.
 // The ring never drains between products: the weight tile stream is one flat sequence over (product, pass, k-tile), and
 // the first tile of the next product is already in flight while the current epilogue runs.
 #include <algorithm>
@@ -18,12 +19,6 @@
 namespace mrgan {
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rs, char* lds_dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)lds_dst, 16, voff, soff, 0, 0);
-}
 __device__ __forceinline__ void lds_barrier() {          // LDS writes of every wave visible to every wave; VMEM left in flight
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();

@@ -11,8 +11,9 @@
 // gfx950 (MI355X_MICROARCH.md, Matrix cores; the non-scaled 32x32x16_fp8_fp8 form issues at the bf16 rate).  Per-tensor
 // power-of-two scales (Fp8Slot, delayed scaling) are undone on the accumulator.  Lane l holds k = 32 (l >> 5) .. + 31 of row
 // l & 31: two ds_read_b128 per fragment from the same XOR-swizzled [rows][128 B] LDS image as the bf16 kernels, filled by
-// LDS-DMA (buffer_load ... lds) into a 2-stage ring, one s_barrier per k-tile (128 reduction elements), persistent blocks in
-// XCD-aware tile order, 128x128 (4 waves) or 256x256 (8 waves of 128x64) blocks.
+// LDS-DMA (lds_ring.h) into a 2-stage ring, one s_barrier per k-tile (128 reduction elements), persistent blocks in
+// lds_ring.h's XCD-aware tile order, 128x128 (4 waves) or 256x256 (8 waves of 128x64) blocks.  The
+// main loop is this file's own: it spreads a tile's DMA pieces over the MFMA steps of the previous one.
 //
 // Epilogue: the shared one of gemm.h (bias / relu / mask / GaussianNoise / column sums).  With OUT8 it packs the fp8 output
 // straight from the fp32 accumulators (one rounding; the oracle's fp8 mirror does the same) into a transposed and a
@@ -23,26 +24,14 @@
 #include <string>
 
 #include "gemm.h"
+#include "lds_ring.h"
 
 namespace mrgan {
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 constexpr int BKB = 128;                        // reduction BYTES (= fp8 elements) per k-tile
 
-__device__ __forceinline__ int kc_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int xcd_tile(int bid, int nt) { return (nt & 7) == 0 ? (bid & 7) * (nt >> 3) + (bid >> 3) : bid; }
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rs, char* lds_dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)lds_dst, 16, voff, soff, 0, 0);
-}
-
-template <int FMT>
-__device__ __forceinline__ u32x4 pack16(const float (&v)[16], float qs) {
-    return (u32x4){fp8_pack4<FMT>(v[0], v[1], v[2], v[3], qs), fp8_pack4<FMT>(v[4], v[5], v[6], v[7], qs),
-                   fp8_pack4<FMT>(v[8], v[9], v[10], v[11], qs), fp8_pack4<FMT>(v[12], v[13], v[14], v[15], qs)};
-}
 // the two fp8 images the shared epilogue (Q8 mode) left in LDS -> global memory, 16 bytes per lane
 template <int BM, int BNT, int NT>
 __device__ __forceinline__ void copy_tile(const unsigned char* tr, const Epi& e, int batch, int row_blk, int col_blk, int M, int N) {
@@ -98,8 +87,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_fp8_kc_kernel(const GemmArg
         const int bs = tidx / (ntn * ntm), rem = tidx - bs * (ntn * ntm);
         const int batch = EPI == EPI_SLAB ? 0 : bs, split = EPI == EPI_SLAB ? bs : 0;
         const int k0 = split * (EPI == EPI_SLAB ? g.kchunk : 0);
-        // consecutive tiles (= the CUs of one XCD at any moment) form patches of 4 tile rows x 8 tile columns instead of
-        // 2 x 16: a third less distinct operand data per k-step has to enter that XCD's L2
+        // patches of 4 tile rows (lds_ring.h, tile order)
         int tile_m, tile_n;
         if ((ntm & 3) == 0) {
             const int grp = rem / (4 * ntn), in = rem - grp * (4 * ntn);
@@ -324,17 +312,8 @@ int launch_fp8_cfg(const GemmArgs& g, hipStream_t s) {
     constexpr int STAGE = BM * 128 + BNT * 128, SCRATCH = 4 * WM * BNT * 4;
     constexpr int OUT = (OUT8 ? BM * (BNT + 16) + BNT * (BM + 16) : BM * BNT * 2) + SCRATCH;
     constexpr int LDS = 2 * STAGE > OUT ? 2 * STAGE : OUT;
-    static_assert(LDS <= 160 * 1024, "the ring exceeds the LDS of a CU");
     const int tiles = ceil_div(g.M, BM) * ceil_div(g.N, BNT) * g.nbatch * (EPI == EPI_SLAB ? g.splits : 1);
-    dim3 grid(std::min(tiles, 256 * std::max(1, (160 * 1024) / LDS)));
-    auto kern = gemm_fp8_kc_kernel<EPI, BM, BNT, WM, WN, VAR, OUT8>;
-    static DeviceOnce attr;
-    if (attr.first()) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return -2;
-        attr.mark();
-    }
-    MRGAN_LAUNCH(kern, grid, dim3(64 * WM * WN), LDS, s, g);
-    return 0;
+    return launch_with_dyn_lds<gemm_fp8_kc_kernel<EPI, BM, BNT, WM, WN, VAR, OUT8>, LDS>(dim3(persistent_grid(tiles, LDS)), dim3(64 * WM * WN), s, g);
 }
 
 template <int EPI, int VAR, bool OUT8>
@@ -390,7 +369,7 @@ int launch_gemm_fp8(int epi, const GemmArgs& g, hipStream_t s, const char** knam
     bool big = g.K >= 512 && t256 >= 192 && (g.N % 256) == 0;
     if (e.tune_kc_cfg == 1) big = false;
     if (e.tune_kc_cfg == 3 && (g.N % 256) == 0) big = true;
-    const bool noise = e.sigma > 0.f, mask = e.mask != nullptr;
+    const int var = epi_variant(epi, e);
     int r = -3;
     const char* nm = "?";
     const bool out8 = e.q8 || e.q8t;
@@ -400,25 +379,32 @@ int launch_gemm_fp8(int epi, const GemmArgs& g, hipStream_t s, const char** knam
         if (e.cs_mode != CS_NONE && e.cs_mode != CS_SUM) return -3;
         if (out8) {
             if (e.cs_mode != CS_NONE) return -3;            // (the fp8-output epilogue carries column sums for dX only)
-            if (e.act == ACT_RELU && noise && mask)
-                r = e.gauss ? launch_fp8_var<EPI_FWD, ACT_RELU | VAR_NOISE | VAR_MASK | VAR_GAUSS, true>(g, s, big)
-                            : launch_fp8_var<EPI_FWD, ACT_RELU | VAR_NOISE | VAR_MASK, true>(g, s, big);
+            switch (var) {
+                case ACT_RELU | VAR_NOISE | VAR_MASK | VAR_GAUSS: r = launch_fp8_var<EPI_FWD, ACT_RELU | VAR_NOISE | VAR_MASK | VAR_GAUSS, true>(g, s, big); break;
+                case ACT_RELU | VAR_NOISE | VAR_MASK: r = launch_fp8_var<EPI_FWD, ACT_RELU | VAR_NOISE | VAR_MASK, true>(g, s, big); break;
+            }
         } else {
-            if (e.act == ACT_RELU && !noise && mask) r = launch_fp8_var<EPI_FWD, ACT_RELU | VAR_MASK, false>(g, s, big);
-            else if (e.act == ACT_RELU && !noise && !mask) r = launch_fp8_var<EPI_FWD, ACT_RELU, false>(g, s, big);
-            else if (e.act == ACT_LINEAR && !noise && !mask) r = launch_fp8_var<EPI_FWD, ACT_LINEAR, false>(g, s, big);
-            else if (e.act == ACT_SOFTPLUS && !noise && !mask) r = launch_fp8_var<EPI_FWD, ACT_SOFTPLUS, false>(g, s, big);
+            switch (var) {      // (no noisy form with a bf16 output)
+                case ACT_RELU | VAR_MASK: r = launch_fp8_var<EPI_FWD, ACT_RELU | VAR_MASK, false>(g, s, big); break;
+                case ACT_RELU: r = launch_fp8_var<EPI_FWD, ACT_RELU, false>(g, s, big); break;
+                case ACT_LINEAR: r = launch_fp8_var<EPI_FWD, ACT_LINEAR, false>(g, s, big); break;
+                case ACT_SOFTPLUS: r = launch_fp8_var<EPI_FWD, ACT_SOFTPLUS, false>(g, s, big); break;
+            }
         }
     } else if (epi == EPI_DX) {
         nm = big ? "gemm_fp8_kc_kernel<1, 256, 256>" : "gemm_fp8_kc_kernel<1, 128, 128>";
-        if (out8) {
-            if (e.cs_mode != CS_NONE && e.cs_mode != CS_SUM) return -3;
-            if (e.act == ACT_RELU && mask) r = launch_fp8_var<EPI_DX, ACT_RELU, true>(g, s, big);
-        } else if (e.act == ACT_LINEAR) {
-            // CS_SUM_XHAT (BatchNorm backward sums of the generator): the epilogue reads e.h from global memory
-            if (e.cs_mode == CS_SUM_XHAT && !(e.h && e.bn_mu && e.bn_rstd && e.cs2)) return -3;
-            if (e.cs_mode == CS_SUM_SQ) return -3;
-            r = launch_fp8_var<EPI_DX, ACT_LINEAR, false>(g, s, big);
+        if (out8 && e.cs_mode != CS_NONE && e.cs_mode != CS_SUM) return -3;
+        switch (var) {      // relu leaves as fp8 (and needs its mask), linear as bf16
+            case ACT_RELU:
+                if (out8 && e.mask) r = launch_fp8_var<EPI_DX, ACT_RELU, true>(g, s, big);
+                break;
+            case ACT_LINEAR:
+                if (out8) break;
+                // CS_SUM_XHAT (BatchNorm backward sums of the generator): the epilogue reads e.h from global memory
+                if (e.cs_mode == CS_SUM_XHAT && !(e.h && e.bn_mu && e.bn_rstd && e.cs2)) return -3;
+                if (e.cs_mode == CS_SUM_SQ) return -3;
+                r = launch_fp8_var<EPI_DX, ACT_LINEAR, false>(g, s, big);
+                break;
         }
     } else if (epi == EPI_SLAB) {
         nm = big ? "gemm_fp8_kc_kernel<2, 256, 256>" : "gemm_fp8_kc_kernel<2, 128, 128>";
