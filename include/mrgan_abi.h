@@ -57,6 +57,8 @@ enum {
                                   * batch draw what the full batch would), mrgan_sup_step.  Host-supplied z is untouched.  */
 };
 
+#define MRGAN_MAX_CLASSES 32   /* largest mrgan_config.num_classes */
+
 /* Hyper-parameters are literals inside mr_gan() in the reference (mr_gan.py:77-79, :111-128, :165);
  * mrgan_default_config() fills exactly those values. */
 typedef struct mrgan_config {
@@ -65,7 +67,9 @@ typedef struct mrgan_config {
     int32_t noise_size;       /* 100                                                            (mr_gan.py:77) */
     int32_t g_hidden[2];      /* 500, 500                                                  (mr_gan.py:111-113) */
     int32_t d_hidden[5];      /* 1000, 500, 250, 250, 250                                  (mr_gan.py:119-127) */
-    int32_t num_classes;      /* 6 materials; the fake class is the implicit zero logit        (mr_gan.py:128) */
+    int32_t num_classes;      /* 6 materials; the fake class is the implicit zero logit        (mr_gan.py:128).
+                               * 2 .. MRGAN_MAX_CLASSES for MRGAN_F32 / MRGAN_BF16 (the last dense is stored at a class pitch of
+                               * 8 up to 8 classes and of 32 above, padding columns exact zeros); 2 .. 8 for MRGAN_FP8          */
     int32_t dtype;            /* MRGAN_F32 | MRGAN_BF16 | MRGAN_FP8 */
     float sigma[5];           /* GaussianNoise std before discriminator dense 1..5: .3 .5 .5 .5 .5 (:118-126)  */
     float lr, beta1, beta2, adam_eps;      /* Adam(lr=0.0006, beta_1=0.5), Keras defaults         (mr_gan.py:165) */

@@ -4,7 +4,9 @@
 
 namespace mrgan {
 
-constexpr int KMAX = 8;            // classes are padded to 8 logits (reference: 6 materials, mr_gan.py:80)
+constexpr int KMAX = 8;            // class pitch KP of a handle with <= 8 classes (reference: 6 materials, mr_gan.py:80)
+constexpr int KWIDE = 32;          // class pitch of a handle with 9 .. 32 classes; columns >= classes of W6 / b6 / logits are zeros
+constexpr int class_pitch(int classes) { return classes <= KMAX ? KMAX : KWIDE; }
 constexpr int HEAD_ROWS = 32;      // rows per loss-head block
 constexpr int HEAD_CHUNK = 256;    // feature columns of the loss head held in LDS at a time (wider layers are walked in chunks)
 
@@ -56,14 +58,14 @@ struct HeadArgs {
     const void* f; long f_bs; int ldf;         // features [seg][rows][ldf]
     int rows, nseg, seg_kind[3];
     int feat, feat_valid, classes;             // padded / logical feature width, number of classes
-    const float* w; int ldw; const float* b;   // last dense: w[feat][ldw], b[classes]
+    const float* w; int ldw; const float* b;   // last dense: w[feat][ldw], b[classes]; ldw = the class pitch KP (8 or 32)
     const int32_t* labels;                     // [rows] (stream mode: offset by batch*rows)
     const DevState* st; int labels_stream;
     float inv_count, unl_weight;               // 1/(global batch), mr_gan.py:79
-    float* logits; long logits_bs;             // optional [seg][rows][KMAX]
+    float* logits; long logits_bs;             // optional [seg][rows][KP]
     void* dpre; long dpre_bs; int ldd;         // dL/d(pre-activation of the feature layer), T
-    float* part; long part_stride;             // per-block partial gradients: part[blk][0 .. feat*KMAX) = dW6,
-    int off_db, off_dbf;                       //   [off_db .. +KMAX) = db6, [off_dbf .. +feat) = bias grad of the feature layer
+    float* part; long part_stride;             // per-block partial gradients: part[blk][0 .. feat*KP) = dW6,
+    int off_db, off_dbf;                       //   [off_db .. +KP) = db6, [off_dbf .. +feat) = bias grad of the feature layer
     float* loss_part;                          // [blk][4] : sum loss_lab, sum loss_unl terms, sum err, 0
     int* err_count;                            // HEAD_EVAL: integer count of argmax != label
     // fp8 mode: dpre leaves as e5m2 copies scaled by q8_slot->scale (row-major [seg][rows][ldq8] and transposed [feat][ldq8t] with

@@ -262,22 +262,39 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(const BnBwdArgs a) {
 // =========================================================================================
 // loss head: logits = f W6 + b6 ; labeled / unlabeled / fake losses of mr_gan.py:146-149 ; train error
 // :161 ; closed-form dlogits ; dW6, db6 ; and dL/d(pre5) = (dlogits W6^T) * [f > 0].
-// One block = HEAD_ROWS rows of one segment.  LDS: f tile as fp32 [HR][feat+8], W6 [feat][8], dlogits [HR][8].
+// One block = HEAD_ROWS rows of one segment.  LDS: f tile as fp32 [HR][feat+8], W6 [feat][KP], dlogits [HR][KP].
+// KP: the class pitch (8, or 32 for more than 8 classes): classes move as KP / 4 f32x4 groups.
 // Per-block partial gradients go to part[blk][...]; reduce_partials_kernel folds them to <= 8 slabs.
 // =========================================================================================
 constexpr int HR = HEAD_ROWS;
+// Accumulator of the two row products (logits, dlogits W6^T).  The bf16 head at the 32-class pitch sums them in fp64.  In the
+// bf16 engine's D sub-step this kernel stands in for head_wide_kernel<false, 32> (feature width no multiple of 256,
+// MRGAN_TUNE_HEAD_MFMA = 0) and has to give what that kernel gives: there every sum rounds a handful of times (exact bf16
+// addend products, fp32 MFMA accumulators), here a logit is a chain of 64 fp32 roundings per 256 features and an element of
+// dL/d(pre5) one of 32.  With up to 32 terms of mixed sign an element of dL/d(pre5) is worse conditioned than at 8 classes,
+// and with fp32 chains its bf16 rounding differs from the matrix-core head's on more rows than the two heads are allowed
+// (DESIGN.md section 4 has the figures and the cost).  make HEAD_ACC_F32=1 builds the fp32-chain variant they were taken
+// against.  The fp32 engine keeps fp32 chains: it has one head and is held against the fp64 oracle with fp32 bounds.
+template <bool WIDE> struct HeadAcc { typedef float type; };
+#ifndef MRGAN_HEAD_ACC_F32
+template <> struct HeadAcc<true> { typedef double type; };
+#endif
+__device__ __forceinline__ float head_fma(float a, float b, float c) { return fmaf(a, b, c); }
+__device__ __forceinline__ double head_fma(float a, float b, double c) { return fma((double)a, (double)b, c); }
 // Q8 (fp8 mode): dpre leaves as e5m2 copies (row-major + transposed) packed from the fp32 values; a separate instantiation,
 // so the bf16 / fp32 kernels keep their rolled row loop and register count
-template <typename T, bool Q8 = false>
+template <typename T, bool Q8 = false, int KP = KMAX>
 __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
+    constexpr int KG = KP / 4;                 // f32x4 groups of classes
+    typedef typename HeadAcc<(KP > KMAX && sizeof(T) == 2)>::type acc_t;
     extern __shared__ __attribute__((aligned(16))) float hl[];
     // the feature dimension is walked in chunks of CH <= 256 columns (one chunk for the reference's 250-wide layer)
     const int CH = min(a.feat, HEAD_CHUNK), nch = (a.feat + CH - 1) / CH;     // a ragged last chunk is zero-filled
     const int LDF = CH + 8;
     float* f_lds = hl;                         // [HR][LDF]   current chunk of f
-    float* w_lds = f_lds + HR * LDF;           // [CH][KMAX]  matching rows of W6
-    float* dl_lds = w_lds + CH * KMAX;         // [HR][KMAX]
-    float* red = dl_lds + HR * KMAX;           // [4 waves][4]
+    float* w_lds = f_lds + HR * LDF;           // [CH][KP]  matching rows of W6
+    float* dl_lds = w_lds + CH * KP;           // [HR][KP]
+    float* red = dl_lds + HR * KP;             // [4 waves][4]
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int seg = blockIdx.y, kind = a.seg_kind[seg];
@@ -295,20 +312,28 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
             *(f32x4*)(f_lds + r * LDF + c + 4) = (f32x4){v[4], v[5], v[6], v[7]};
         }
         for (int k = t; k < CH; k += 256) {
-            f32x4 w0 = {0.f, 0.f, 0.f, 0.f}, w1 = w0;
-            if (c0 + k < a.feat_valid) { w0 = *(const f32x4*)(a.w + (long)(c0 + k) * a.ldw); w1 = *(const f32x4*)(a.w + (long)(c0 + k) * a.ldw + 4); }
+            f32x4 w[KG];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { if (c >= a.classes) w0[c] = 0.f; if (c + 4 >= a.classes) w1[c] = 0.f; }
-            *(f32x4*)(w_lds + k * KMAX) = w0; *(f32x4*)(w_lds + k * KMAX + 4) = w1;
+            for (int g = 0; g < KG; ++g) w[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (c0 + k < a.feat_valid) {
+#pragma unroll
+                for (int g = 0; g < KG; ++g) w[g] = *(const f32x4*)(a.w + (long)(c0 + k) * a.ldw + 4 * g);
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int g = 0; g < KG; ++g) if (c + 4 * g >= a.classes) w[g][c] = 0.f;
+#pragma unroll
+            for (int g = 0; g < KG; ++g) *(f32x4*)(w_lds + k * KP + 4 * g) = w[g];
         }
     };
 
     // ---- logits: LPR lanes per row, each over an interleaved slice of the features ----
     constexpr int LPR = 256 / HR;
     const int r = t / LPR, part = t % LPR;
-    float l[KMAX];
+    acc_t la[KP];
 #pragma unroll
-    for (int c = 0; c < KMAX; ++c) l[c] = 0.f;
+    for (int c = 0; c < KP; ++c) la[c] = 0.f;
     for (int ch = 0; ch < nch; ++ch) {
         if (ch) __syncthreads();                   // every thread is done with the previous chunk
         load_chunk(ch * CH);
@@ -316,35 +341,42 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
         for (int kk = 0; kk < CH / LPR; ++kk) {
             const int k = kk * LPR + part;
             const float fv = f_lds[r * LDF + k];
-            const f32x4 w0 = *(const f32x4*)(w_lds + k * KMAX), w1 = *(const f32x4*)(w_lds + k * KMAX + 4);
+            f32x4 w[KG];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { l[c] = fmaf(fv, w0[c], l[c]); l[4 + c] = fmaf(fv, w1[c], l[4 + c]); }
+            for (int g = 0; g < KG; ++g) w[g] = *(const f32x4*)(w_lds + k * KP + 4 * g);
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int g = 0; g < KG; ++g) la[4 * g + c] = head_fma(fv, w[g][c], la[4 * g + c]);
         }
     }
 #pragma unroll
-    for (int c = 0; c < KMAX; ++c) {
+    for (int c = 0; c < KP; ++c) {
 #pragma unroll
-        for (int m = 1; m < LPR; m <<= 1) l[c] += __shfl_xor(l[c], m, 64);
+        for (int m = 1; m < LPR; m <<= 1) la[c] += __shfl_xor(la[c], m, 64);
     }
+    float l[KP];
+#pragma unroll
+    for (int c = 0; c < KP; ++c) l[c] = (float)la[c];
     const int row = row_blk + r;
     const bool rowvalid = row < a.rows;
-    float b[KMAX];
+    float b[KP];
 #pragma unroll
-    for (int c = 0; c < KMAX; ++c) b[c] = (c < a.classes) ? a.b[c] : 0.f;
+    for (int c = 0; c < KP; ++c) b[c] = (c < a.classes) ? a.b[c] : 0.f;
     int y = 0;
     if (rowvalid && head_kind_has_label(kind)) {
         const long lo = a.labels_stream ? (long)a.st->batch * a.rows : 0;
         y = a.labels[lo + row];
     }
-    float loss0, loss1, err, dl[KMAX];
+    float loss0, loss1, err, dl[KP];
     head_row<true>(l, b, kind, y, a.classes, a.inv_count, a.unl_weight, rowvalid, loss0, loss1, err, dl);
     if (part == 0) {
-        *(f32x4*)(dl_lds + r * KMAX) = (f32x4){dl[0], dl[1], dl[2], dl[3]};
-        *(f32x4*)(dl_lds + r * KMAX + 4) = (f32x4){dl[4], dl[5], dl[6], dl[7]};
-        if (a.logits && rowvalid) {
-            float* lp = a.logits + (long)seg * a.logits_bs + (long)row * KMAX;
 #pragma unroll
-            for (int c = 0; c < KMAX; ++c) lp[c] = (c < a.classes) ? l[c] : 0.f;
+        for (int g = 0; g < KG; ++g) *(f32x4*)(dl_lds + r * KP + 4 * g) = (f32x4){dl[4 * g], dl[4 * g + 1], dl[4 * g + 2], dl[4 * g + 3]};
+        if (a.logits && rowvalid) {
+            float* lp = a.logits + (long)seg * a.logits_bs + (long)row * KP;
+#pragma unroll
+            for (int c = 0; c < KP; ++c) lp[c] = (c < a.classes) ? l[c] : 0.f;
         }
     } else { loss0 = 0.f; loss1 = 0.f; err = 0.f; }
     loss0 = wave_sum(loss0); loss1 = wave_sum(loss1); err = wave_sum(err);
@@ -363,9 +395,9 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
 
     // ---- backward of the last dense: thread <-> feature column j ----
     float* part_row = a.part + (long)blk * a.part_stride;
-    if (t < KMAX) {
+    if (t < KP) {
         float s = 0.f;
-        for (int rr = 0; rr < HR; ++rr) s += dl_lds[rr * KMAX + t];
+        for (int rr = 0; rr < HR; ++rr) s += dl_lds[rr * KP + t];
         part_row[a.off_db + t] = s;
     }
     T* dpre = a.dpre ? (T*)a.dpre + (long)seg * a.dpre_bs : nullptr;
@@ -380,20 +412,24 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
         const int c0 = ch * CH;
         if (ch != nch - 1) { __syncthreads(); load_chunk(c0); __syncthreads(); }
         for (int j = t; j < CH && c0 + j < a.feat; j += 256) {
-            float wj[KMAX], dw[KMAX];
+            float wj[KP], dw[KP];
 #pragma unroll
-            for (int c = 0; c < KMAX; ++c) { wj[c] = w_lds[j * KMAX + c]; dw[c] = 0.f; }
+            for (int c = 0; c < KP; ++c) { wj[c] = w_lds[j * KP + c]; dw[c] = 0.f; }
             float dbf = 0.f;
             auto row_step = [&](int rr) -> float {
                 const float fv = f_lds[rr * LDF + j];
-                const f32x4 d0 = *(const f32x4*)(dl_lds + rr * KMAX), d1 = *(const f32x4*)(dl_lds + rr * KMAX + 4);
-                float dfe = 0.f;
+                f32x4 d[KG];
+#pragma unroll
+                for (int g = 0; g < KG; ++g) d[g] = *(const f32x4*)(dl_lds + rr * KP + 4 * g);
+                acc_t dfe = 0.f;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    dfe = fmaf(d0[c], wj[c], dfe); dfe = fmaf(d1[c], wj[4 + c], dfe);
-                    dw[c] = fmaf(fv, d0[c], dw[c]); dw[4 + c] = fmaf(fv, d1[c], dw[4 + c]);
+#pragma unroll
+                    for (int g = 0; g < KG; ++g) dfe = head_fma(d[g][c], wj[4 * g + c], dfe);
+#pragma unroll
+                    for (int g = 0; g < KG; ++g) dw[4 * g + c] = fmaf(fv, d[g][c], dw[4 * g + c]);
                 }
-                const float dp = (fv > 0.f) ? dfe : 0.f;
+                const float dp = (fv > 0.f) ? (float)dfe : 0.f;
                 if (dpre && row_blk + rr < a.rows) dpre[(long)(row_blk + rr) * a.ldd + c0 + j] = Elem<T>::from_f32(dp);
                 dbf += dp;
                 return dp;
@@ -428,8 +464,9 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
             } else {
                 for (int rr = 0; rr < HR; ++rr) row_step(rr);
             }
-            *(f32x4*)(part_row + (long)(c0 + j) * KMAX) = (f32x4){dw[0], dw[1], dw[2], dw[3]};
-            *(f32x4*)(part_row + (long)(c0 + j) * KMAX + 4) = (f32x4){dw[4], dw[5], dw[6], dw[7]};
+#pragma unroll
+            for (int g = 0; g < KG; ++g)
+                *(f32x4*)(part_row + (long)(c0 + j) * KP + 4 * g) = (f32x4){dw[4 * g], dw[4 * g + 1], dw[4 * g + 2], dw[4 * g + 3]};
             part_row[a.off_dbf + c0 + j] = dbf;
         }
     }
@@ -801,15 +838,24 @@ int init_kernel_attributes() {
     hipError_t e = hipFuncSetAttribute((const void*)head_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)head_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)head_kernel<float, false, KWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)head_kernel<__bf16, false, KWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     return e == hipSuccess ? 0 : -2;
 }
 
 int launch_head(int bf16, const HeadArgs& a, hipStream_t s) {
     const int ch = std::min(a.feat, HEAD_CHUNK);
-    if ((a.feat % 64) != 0 || a.classes > KMAX) return -3;
-    const size_t smem = sizeof(float) * ((size_t)HR * (ch + 8) + (size_t)ch * KMAX + HR * KMAX + 16);
+    const int kp = a.ldw;                      // the class pitch of W6, the logits and the partial-gradient rows
+    if ((a.feat % 64) != 0 || (kp != KMAX && kp != KWIDE) || a.classes > kp) return -3;
+    const size_t smem = sizeof(float) * ((size_t)HR * (ch + 8) + (size_t)ch * kp + HR * kp + 16);
     dim3 grid(ceil_div(a.rows, HR), a.nseg);
-    if (a.q8_slot) {
+    if (kp == KWIDE) {
+        if (a.q8_slot) return -3;              // the e5m2 packing epilogue exists at the 8-class pitch only
+        if (bf16) MRGAN_LAUNCH((head_kernel<__bf16, false, KWIDE>), grid, dim3(256), smem, s, a);
+        else MRGAN_LAUNCH((head_kernel<float, false, KWIDE>), grid, dim3(256), smem, s, a);
+    } else if (a.q8_slot) {
         if (!bf16 || !(a.q8 || a.q8t)) return -3;
         static DeviceOnce attr;
         if (attr.first()) {

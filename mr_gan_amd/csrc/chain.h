@@ -97,13 +97,14 @@ __device__ __forceinline__ int img_elem_off(const int (&obase)[4], int mi, int r
     return obase[((r >> 1) & 1) | (((r >> 2) & 1) << 1)] + (mi * 32 + acc_row(r, 0)) * 128;
 }
 
-// Stand-alone loss head on the matrix cores for feature layers the chain cannot hold (wider than 256 columns; BASELINE
-// configs[4]: 4096): the three products of chain_head over 64-row blocks, the feature dimension walked in 256-column chunks.
+// Stand-alone loss head on the matrix cores for what the chain cannot hold: feature layers wider than 256 columns (BASELINE
+// configs[4]: 4096), and more than 8 classes (class pitch 32) at any multiple of 256 columns: the three products of chain_head
+// over 64-row blocks, the feature dimension walked in 256-column chunks.
 // feat % 256 == 0; bf16 features; segment kinds LAB / UNL / FAKE (training); mask = the feature layer's lane-native relu mask.
 struct HeadWideArgs {
     HeadArgs h;
     const uint16_t* mask; long mask_bs; int ldm;
-    __bf16* w6c; __bf16* w6r;          // scratch: the bf16 addends of W6, class-major [3][KMAX][feat] and row-major [3][feat][KMAX]
+    __bf16* w6c; __bf16* w6r;          // scratch: the bf16 addends of W6, class-major [3][KP][feat] and row-major [3][feat][KP] (KP = h.ldw)
 };
 constexpr int HEAD_WIDE_ROWS = CH_ROWS;
 int launch_w6_split(const HeadWideArgs& a, hipStream_t s);       // first: the addends of the current W6

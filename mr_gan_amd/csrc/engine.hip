@@ -489,13 +489,13 @@ HeadArgs head_args(mrgan_handle* h, std::initializer_list<int> kinds, int rows, 
     hd.f = h->feat; hd.ldf = h->Fp; hd.rows = rows;
     for (int k : kinds) hd.seg_kind[hd.nseg++] = k;
     hd.feat = h->Fp; hd.feat_valid = h->F; hd.classes = h->cfg.num_classes;
-    hd.w = h->dt[10].p; hd.ldw = KMAX; hd.b = h->dt[11].p;
+    hd.w = h->dt[10].p; hd.ldw = h->KP; hd.b = h->dt[11].p;
     hd.st = h->state + h->cur;
     hd.logits = h->logits;
     if (!train) return hd;
-    hd.f_bs = (long)h->S * h->Fp; hd.logits_bs = (long)h->S * KMAX;
+    hd.f_bs = (long)h->S * h->Fp; hd.logits_bs = (long)h->S * h->KP;
     hd.dpre = h->dpre[4]; hd.dpre_bs = (long)h->S * h->Fp; hd.ldd = h->Fp;
-    hd.part = h->head_part; hd.part_stride = h->head_stride; hd.off_db = h->Fp * KMAX; hd.off_dbf = h->Fp * KMAX + KMAX;
+    hd.part = h->head_part; hd.part_stride = h->head_stride; hd.off_db = h->Fp * h->KP; hd.off_dbf = h->Fp * h->KP + h->KP;
     hd.loss_part = h->loss_part;
     return hd;
 }
@@ -516,7 +516,7 @@ ChainArgs chain_args(mrgan_handle* h, int variant, int nseg, int block_rows) {
 // discriminator sub-step
 // ---------------------------------------------------------------------------------------------------
 // D sub-step: the loss head over (labelled, unlabelled, generated) rows.  With the chain this launch also runs D3 .. D5 forward
-// before the head and their dX after it.  Records how many partial rows of head_part / loss_part it wrote.
+// before the head and their dX after it (8-class pitch only: at the 32-class pitch D3 .. D5 run per layer and the head alone).  Records how many partial rows of head_part / loss_part it wrote.
 int disc_head(mrgan_handle* h, const mrgan_disc_args* a, hipStream_t s) {
     HeadArgs hd = head_args(h, {HEAD_LAB, HEAD_UNL, HEAD_FAKE}, h->B, true);
     hd.labels = a->labels_dev; hd.labels_stream = a->stream_mode;
@@ -527,7 +527,7 @@ int disc_head(mrgan_handle* h, const mrgan_disc_args* a, hipStream_t s) {
         hd.q8t = h->g8t[4]; hd.q8t_bs = h->S; hd.ldq8t = 3 * h->S;
         hd.q8_slot = h->slots + slot_g(0, 4);
     }
-    if (h->use_chain) {
+    if (h->dtail_chain()) {
         // D3 D4 D5 forward -> loss head -> dX through D5 D4 D3, one launch: the rows of a block never leave its CU
         ChainArgs c = chain_args(h, CH_V_DTAIL, 3, CH_ROWS);
         c.op[0] = chain_fwd_op(h, 2, CH_BUF0, CH_BUF1, false);
@@ -605,10 +605,10 @@ int disc_phase(mrgan_handle* h, const mrgan_disc_args* a, int phase, hipStream_t
         CHK(gen_fwd_tail(h, h->pair_gen ? 2 : 1, 2, 2, s));               // fake rows -> slot 2 (+ the G sub-step's -> slot 3)
         h->gen_ready = h->pair_gen;
         h->pair_gen = 0;                                                  // one D sub-step per hint
-        CHK(disc_fwd_train(h, 0, 3, false, 0, s, h->use_chain ? 2 : 5));
+        CHK(disc_fwd_train(h, 0, 3, false, 0, s, h->dtail_chain() ? 2 : 5));
         CHK(disc_head(h, a, s));
         if (h->fp8) CHK(fp8_disc_bwd(h, s));
-        else CHK(disc_bwd(h, 3, h->use_chain ? 1 : 4, h->head_nblk, s));
+        else CHK(disc_bwd(h, 3, h->dtail_chain() ? 1 : 4, h->head_nblk, s));
         if (h->flat_grads) CHK(run_adam(h, MRGAN_NET_D, ADAM_REDUCE_ONLY, true, s));
     } else if (phase == MRGAN_D_ADAM) {
         CHK(run_adam(h, MRGAN_NET_D, h->flat_grads ? ADAM_FROM_FLAT : ADAM_FUSED, true, s));
@@ -799,7 +799,7 @@ int eval_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, cons
         PROF("head_kernel", launch_head(h->bf16, hd, s));
         if (logits_out)
             HIPCHK(hipMemcpy2DAsync(logits_out + r0 * h->cfg.num_classes, sizeof(float) * h->cfg.num_classes, h->logits,
-                                    sizeof(float) * KMAX, sizeof(float) * h->cfg.num_classes, rows, hipMemcpyDeviceToDevice, s));
+                                    sizeof(float) * h->KP, sizeof(float) * h->cfg.num_classes, rows, hipMemcpyDeviceToDevice, s));
     }
     // The evaluation used the training activations as scratch and filled rows [0, 3S) of every layer input, i.e. also the
     // padding rows B..S of each training segment.  The bf16 weight gradients reduce over all S rows of a segment (zero dY

@@ -82,8 +82,10 @@ int fp8_dw_splits(int tiles, int rows) {
 
 int validate(const mrgan_config& c) {
     if (c.d_in < 1 || c.batch < 1) return fail(-1, "d_in and batch must be positive");
-    if (c.num_classes < 2 || c.num_classes > KMAX) return fail(-1, "num_classes must be in [2,%d]", KMAX);
+    if (c.num_classes < 2 || c.num_classes > MRGAN_MAX_CLASSES) return fail(-1, "num_classes must be in [2,%d]", MRGAN_MAX_CLASSES);
     if (c.dtype != MRGAN_F32 && c.dtype != MRGAN_BF16 && c.dtype != MRGAN_FP8) return fail(-1, "unknown dtype");
+    if (c.dtype == MRGAN_FP8 && c.num_classes > KMAX)
+        return fail(-1, "the fp8 engine supports at most %d classes (num_classes = %d): its loss head packs e5m2 at the 8-class pitch only", KMAX, c.num_classes);
     if (c.world < 1 || c.rank < 0 || c.rank >= c.world) return fail(-1, "bad rank/world");
     if (c.world > 1 && (c.batch % 4) != 0) return fail(-1, "data-parallel shards need batch %% 4 == 0 (noise row groups)");
     if (c.world > 1 && (c.flags & (MRGAN_FLAG_FLAT_GRADS)) == 0) return fail(-1, "world > 1 requires MRGAN_FLAG_FLAT_GRADS");
@@ -125,6 +127,8 @@ int layout(mrgan_handle* h, char* base, size_t* bytes_out) {
     h->fm_scale = h->sync_stats ? 1.0f : 1.0f / (float)c.world;
     h->Dp = padded(c.d_in); h->nzp = padded(c.noise_size);
     h->F = c.d_hidden[4]; h->Fp = padded(h->F);
+    h->KP = class_pitch(c.num_classes);
+    const int KP = h->KP;
     const int B = h->B, S = h->S, tm = h->tiles_m;
     Arena a; a.base = base;
 
@@ -157,7 +161,7 @@ int layout(mrgan_handle* h, char* base, size_t* bytes_out) {
     mk(h->gt[2], 1, gdim[1], 1, padded(gdim[1]), false);
     mk(h->gt[3], 1, gdim[1], 1, padded(gdim[1]), false);
     for (int l = 0; l < 6; ++l) {
-        const int K = ddim[l], N = ddim[l + 1], Kp = padded(K), Np = (l == 5) ? KMAX : padded(N);
+        const int K = ddim[l], N = ddim[l + 1], Kp = padded(K), Np = (l == 5) ? KP : padded(N);
         mk(h->dt[2 * l], K, N, Kp, Np, l < 5);
         mk(h->dt[2 * l + 1], 1, N, 1, Np, false);
         h->d[l] = Dense{K, N, Kp, Np, l < 5 ? ACT_RELU : ACT_LINEAR, &h->dt[2 * l], &h->dt[2 * l + 1], nullptr, 1};
@@ -210,7 +214,7 @@ int layout(mrgan_handle* h, char* base, size_t* bytes_out) {
         h->slots = a.take<Fp8Slot>(FP8_NSLOT); h->slot_targets = a.take<float>(FP8_NSLOT); h->accum_save = a.take<float>(4);
     }
     h->dxfake = act(S, h->Dp); h->dpre2g = act(S, h->g[1].Np); h->dhbn = act(S, N1p); h->dpre1g = act(S, N1p);
-    h->logits = a.take<float>(3 * (size_t)S * KMAX);
+    h->logits = a.take<float>(3 * (size_t)S * KP);
     h->fm_scratch = a.take<float>(ceil_div(h->Fp, 64)); h->fm_count = a.take<unsigned int>(4);
 
     // ---- partial sums ----------------------------------------------------------------------------
@@ -228,12 +232,13 @@ int layout(mrgan_handle* h, char* base, size_t* bytes_out) {
                   std::min(std::min(h->d[2].Kp, h->d[2].Np), std::min(h->d[3].Np, h->d[4].Np)) >= 128;
     h->use_chain = h->chain_ok;
     // bf16 / fp8 engines whose feature layer is wider than the chain's 256 columns (the wide stack) run the loss head of the D
-    // sub-step on the matrix cores too (64-row blocks, as the chain's)
-    h->head_wide_ok = h->head_wide = h->bf16 && h->Fp > CH_PW && (h->Fp % CH_PW) == 0;
+    // sub-step on the matrix cores too (64-row blocks, as the chain's); at the 32-class pitch, where the D-tail chain does not
+    // run, so does a 256-wide feature layer (one chunk)
+    h->head_wide_ok = h->head_wide = h->bf16 && (h->Fp > CH_PW || (KP > KMAX && h->Fp == CH_PW)) && (h->Fp % CH_PW) == 0;
     h->w6c = h->w6r = nullptr;
-    if (h->head_wide) { h->w6c = a.take<__bf16>((size_t)3 * KMAX * h->Fp); h->w6r = a.take<__bf16>((size_t)3 * KMAX * h->Fp); }
+    if (h->head_wide) { h->w6c = a.take<__bf16>((size_t)3 * KP * h->Fp); h->w6r = a.take<__bf16>((size_t)3 * KP * h->Fp); }
     const int head_cap = 3 * ceil_div(B, HEAD_ROWS);                      // partial rows of the per-layer head; the 64-row heads fill fewer
-    h->head_stride = (int)round_up(h->Fp * KMAX + KMAX + h->Fp, 64);      // dW6 | db6 | bias grad of the feature layer
+    h->head_stride = (int)round_up(h->Fp * KP + KP + h->Fp, 64);      // dW6 | db6 | bias grad of the feature layer
     h->head_groups = std::min(8, 3 * ceil_div(B, CH_ROWS));
     h->head_part = a.take<float>((size_t)head_cap * h->head_stride);
     h->head_red = a.take<float>((size_t)h->head_groups * h->head_stride);
@@ -262,9 +267,9 @@ int layout(mrgan_handle* h, char* base, size_t* bytes_out) {
     auto src = [&](Tensor& t, const float* g, int nslab, long stride) { t.g = g; t.nslab = nslab; t.slab_stride = stride; };
     for (int l = 0; l < 5; ++l) src(*h->d[l].W, h->d[l].slabs, h->d[l].splits, (long)h->d[l].Kp * h->d[l].Np);
     for (int l = 0; l < 4; ++l) src(*h->d[l].b, h->cs_db[l], 3 * tm, h->d[l].Np);
-    src(*h->d[4].b, h->head_red + h->Fp * KMAX + KMAX, h->head_groups, h->head_stride);
+    src(*h->d[4].b, h->head_red + h->Fp * KP + KP, h->head_groups, h->head_stride);
     src(*h->d[5].W, h->head_red, h->head_groups, h->head_stride);
-    src(*h->d[5].b, h->head_red + h->Fp * KMAX, h->head_groups, h->head_stride);
+    src(*h->d[5].b, h->head_red + h->Fp * KP, h->head_groups, h->head_stride);
     for (int l = 0; l < 3; ++l) src(*h->g[l].W, h->g[l].slabs, h->g[l].splits, (long)h->g[l].Kp * h->g[l].Np);
     src(*h->g[0].b, h->db1g_part, h->bnb_blocks, N1p);
     src(h->gt[2], h->cs_dgamma, tm, N1p);

@@ -158,7 +158,7 @@ __device__ __forceinline__ void chain_head(const ChainArgs& a, char* lds, Stream
         }
     }
     // B operand of product 4 (k = class, column = feature 32 wave + lc): the eight class weights of this lane's feature
-    bf16x8 bw[3] = {zero8(), zero8(), zero8()};
+    bf16x8 bw[1][3] = {{zero8(), zero8(), zero8()}};               // (one k-step: head_dpre_product<1>)
     {
         const int j = wave * 32 + lc;
         const f32x4 w0 = hi.bw0, w1 = hi.bw1;
@@ -167,7 +167,7 @@ __device__ __forceinline__ void chain_head(const ChainArgs& a, char* lds, Stream
             const float wv = (lh == 0 && j < h.feat_valid && c < h.classes) ? (c < 4 ? w0[c & 3] : w1[c & 3]) : 0.f;      // lh = 1: k = 8 .. 15, zeros
             __bf16 p0, p1, p2;
             split3(wv, p0, p1, p2);
-            bw[0][c] = p0; bw[1][c] = p1; bw[2][c] = p2;
+            bw[0][0][c] = p0; bw[0][1][c] = p1; bw[0][2][c] = p2;
         }
     }
     lds_barrier();
@@ -213,9 +213,9 @@ __device__ __forceinline__ void chain_head(const ChainArgs& a, char* lds, Stream
     // ---- 4. dL/d(pre5) = (dlogits W6^T) * relu'(pre5) for columns 32 wave .. + 31: the next product's A image ----
     {
         f32x16 acc[2];
-        bf16x8 da[2][3];
-        head_load_dl_rows(dl_rc, lc, lh, da);
-        head_dpre_product(acc, da, bw);
+        bf16x8 da[1][2][3];
+        head_load_dl_rows(dl_rc, lc, lh, da[0]);
+        head_dpre_product<1>(acc, da, bw);
         const int cip = wave * 32 + lc;
         float s1 = head_dpre_to_image(acc, mw[0], oimg, cip, lh);
         s1 += __shfl_xor(s1, 32, 64);
@@ -698,35 +698,43 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
 // a lane's four consecutive rows of one column are one dword of the transposed image, the row-major dword comes from a 4 x 4
 // byte transpose inside the lane quad (gemm.h does the same in the fp8 epilogues); both images are assembled in LDS and leave
 // as 16-byte stores.  Otherwise dL/d(pre5) leaves as bf16 through the chain's image + copy_out.
+// KP: the class pitch.  KP = 32 (9 .. 32 classes, bf16 only) keeps all 32 columns of the logits product, folds the eight partial
+// logits tiles into four LDS slots in two rounds (head.h: head_logits_fold), runs dL/d(pre5) as two k-steps and stores all
+// sixteen registers of dW6^T; it also serves a 256-wide feature layer as a single chunk (the D-tail chain is an 8-class kernel).
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int HW_FIMG = CH_ROWS * CH_PW * 2;                  // 32 KiB per feature image
 constexpr int HW_TPITCH = CH_ROWS + 16, HW_RPITCH = CH_PW + 16;
 constexpr int HW_X = 2 * HW_FIMG, HW_X_BYTES = 40 * 1024;     // pass 1: logits partials; pass 2: output image(s)
 constexpr int HW_SMALL = HW_X + HW_X_BYTES;
-constexpr int HW_LDS = HW_SMALL + 2 * 3 * CH_ROWS * KMAX * 2 + (3 + KMAX) * CH_ROWS * 4;
+constexpr int hw_lds(int KP) { return HW_SMALL + 2 * 3 * CH_ROWS * KP * 2 + (3 + KP) * CH_ROWS * 4; }
+constexpr int HW_LDS = hw_lds(KMAX);
 static_assert(CH_PW * HW_TPITCH + CH_ROWS * HW_RPITCH <= HW_X_BYTES && 8 * CH_ROWS * KMAX * 4 <= HW_X_BYTES, "head_wide LDS map");
+static_assert(head_lslots(KWIDE) * CH_ROWS * head_lpitch(KWIDE) * 4 <= HW_X_BYTES && hw_lds(KWIDE) <= 160 * 1024, "head_wide LDS map, 32 classes");
 
+template <int KP>
 __global__ __launch_bounds__(256) void w6_split_kernel(const float* w, int ldw, int feat, int feat_valid, int classes, __bf16* w6c, __bf16* w6r) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= feat) return;
 #pragma unroll
-    for (int c = 0; c < KMAX; ++c) {
+    for (int c = 0; c < KP; ++c) {
         const float v = (j < feat_valid && c < classes) ? w[(long)j * ldw + c] : 0.f;
         __bf16 p0, p1, p2;
         split3(v, p0, p1, p2);
-        w6c[(0L * KMAX + c) * feat + j] = p0; w6c[(1L * KMAX + c) * feat + j] = p1; w6c[(2L * KMAX + c) * feat + j] = p2;
-        w6r[(0L * feat + j) * KMAX + c] = p0; w6r[(1L * feat + j) * KMAX + c] = p1; w6r[(2L * feat + j) * KMAX + c] = p2;
+        w6c[(0L * KP + c) * feat + j] = p0; w6c[(1L * KP + c) * feat + j] = p1; w6c[(2L * KP + c) * feat + j] = p2;
+        w6r[(0L * feat + j) * KP + c] = p0; w6r[(1L * feat + j) * KP + c] = p1; w6r[(2L * feat + j) * KP + c] = p2;
     }
 }
 
-template <bool Q8>
+template <bool Q8, int KP = KMAX>
 __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArgs a) {
+    static_assert(KP == KMAX || !Q8, "the e5m2 epilogue exists at the 8-class pitch only");
+    constexpr int NKS = KP == KMAX ? 1 : KP / 16;             // k-steps of the dL/d(pre5) product
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const HeadArgs& h = a.h;
     char* xreg = lds + HW_X;
-    __bf16* dl_rc = (__bf16*)(lds + HW_SMALL);                // [3][CH_ROWS][KMAX]   dlogits addends, row-major
-    __bf16* dl_t = dl_rc + 3 * CH_ROWS * KMAX;                // [3][KMAX][CH_ROWS]   ... class-major
-    float* red = (float*)(dl_t + 3 * KMAX * CH_ROWS);         // [3 + KMAX][CH_ROWS]
+    __bf16* dl_rc = (__bf16*)(lds + HW_SMALL);                // [3][CH_ROWS][KP]   dlogits addends, row-major
+    __bf16* dl_t = dl_rc + 3 * CH_ROWS * KP;                  // [3][KP][CH_ROWS]   ... class-major
+    float* red = (float*)(dl_t + 3 * KP * CH_ROWS);           // [3 + KP][CH_ROWS]
     const int t = threadIdx.x, lane = t & 63, lc = lane & 31, lh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int seg = blockIdx.y, rb = blockIdx.x, nrb = gridDim.x, kind = h.seg_kind[seg];
@@ -757,8 +765,9 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
         for (int u = 0; u < 2; ++u)
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
-                const bf16x8 v = *(const bf16x8*)(a.w6c + ((long)p * KMAX + (lc & (KMAX - 1))) * h.feat + c * CH_PW + 16 * (2 * wave + u) + 8 * lh);
-                fb[u][p] = lc < KMAX ? v : zero8();             // columns 8 .. 31 of the product are padding
+                const bf16x8 v = *(const bf16x8*)(a.w6c + ((long)p * KP + (lc & (KP - 1))) * h.feat + c * CH_PW + 16 * (2 * wave + u) + 8 * lh);
+                fb[u][p] = (KP == 32 || lc < KP) ? v : zero8();   // KP = 8: columns 8 .. 31 of the product are padding; KP = 32:
+                                                                // w6_split_kernel left zeros in the columns >= classes
             }
     };
 
@@ -785,8 +794,15 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
 #pragma unroll
         for (int u = 0; u < 2; ++u) head_logits_step(lacc, fimg, 2 * wave + u, fb[u], lc, lh);
     }
-    float* lpart = (float*)xreg;                              // [8 waves][CH_ROWS][KMAX]
-    head_logits_scatter(lacc, lpart, wave, lc, lh);
+    float* lpart = (float*)xreg;                              // [head_lslots(KP)][CH_ROWS][head_lpitch(KP)]
+    if constexpr (KP == KMAX) {
+        head_logits_scatter(lacc, lpart, wave, lc, lh);
+    } else {
+        // eight [64][32] tiles into four slots: waves 0 .. 3 store, then wave 4 + i adds to slot i (a fixed order of the sum)
+        if (wave < head_lslots(KP)) head_logits_scatter<KP>(lacc, lpart, wave, lc, lh);
+        lds_barrier();
+        if (wave >= head_lslots(KP)) head_logits_fold<KP>(lacc, lpart, wave - head_lslots(KP), lc, lh);
+    }
     lds_barrier();
     // the chunk before the last one is needed next (pass 2 walks downwards): its image is free now
     if (nch > 1) issue_chunk(nch - 2);
@@ -796,42 +812,49 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
     if (wave == 0) {
         const int r = lane;
         const bool rowvalid = r < rows_valid;
-        float l[KMAX];
+        float l[KP];
         head_logits_gather(lpart, r, l);
-        float b[KMAX];
+        float b[KP];
 #pragma unroll
-        for (int c = 0; c < KMAX; ++c) b[c] = (c < h.classes) ? h.b[c] : 0.f;
+        for (int c = 0; c < KP; ++c) b[c] = (c < h.classes) ? h.b[c] : 0.f;
         int y = 0;
         if (rowvalid && kind == HEAD_LAB) {
             const long lo = h.labels_stream ? (long)h.st->batch * h.rows : 0;
             y = h.labels[lo + row_blk + r];
         }
-        float loss0, loss1, err, dl[KMAX];
+        float loss0, loss1, err, dl[KP];
         head_row<false>(l, b, kind, y, h.classes, h.inv_count, h.unl_weight, rowvalid, loss0, loss1, err, dl);
         if (rowvalid && h.logits) {
-            float* lp = h.logits + (long)seg * h.logits_bs + (long)(row_blk + r) * KMAX;
+            float* lp = h.logits + (long)seg * h.logits_bs + (long)(row_blk + r) * KP;
 #pragma unroll
-            for (int c = 0; c < KMAX; ++c) lp[c] = (c < h.classes) ? l[c] : 0.f;
+            for (int c = 0; c < KP; ++c) lp[c] = (c < h.classes) ? l[c] : 0.f;
         }
         head_rows_to_lds(dl, loss0, loss1, err, r, dl_rc, dl_t, red);
     }
     lds_barrier();
-    head_block_sums(red, h, blk, part_row, wave, lane);
+    head_block_sums<KP>(red, h, blk, part_row, wave, lane);
 
     // =========================== pass 2: dL/d(pre5) and dW6^T, chunk by chunk ===========================
     // A operands that do not depend on the chunk, in registers for the whole pass
-    bf16x8 da[2][3], dt[4][3];
-    head_load_dl_rows(dl_rc, lc, lh, da);
+    bf16x8 da[NKS][2][3], dt[4][3];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) head_load_dl_cols(dl_t, ks, lc, lh, dt[ks]);
+    for (int ks = 0; ks < NKS; ++ks) head_load_dl_rows<KP>(dl_rc, lc, lh, da[ks], ks);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) head_load_dl_cols<KP>(dl_t, ks, lc, lh, dt[ks]);
     const uint16_t* mseg = a.mask + (long)seg * a.mask_bs;
     // per chunk: the W6 rows of this lane's feature as bf16 addends (B operand, k = class) and the relu-mask words of its column
-    auto load_chunk_inputs = [&](int c, bf16x8 (&bw)[3], uint32_t (&mw)[2]) {
+    // (KP = 32: k-step ks holds classes 16 ks + 8 lh .. + 7)
+    auto load_chunk_inputs = [&](int c, bf16x8 (&bw)[NKS][3], uint32_t (&mw)[2]) {
         const int col = c * CH_PW + wave * 32 + lc;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            const bf16x8 v = *(const bf16x8*)(a.w6r + ((long)q * h.feat + col) * KMAX);
-            bw[q] = lh ? zero8() : v;                           // lh = 1: k = 8 .. 15, zeros
+            if constexpr (KP == KMAX) {
+                const bf16x8 v = *(const bf16x8*)(a.w6r + ((long)q * h.feat + col) * KMAX);
+                bw[0][q] = lh ? zero8() : v;                    // lh = 1: k = 8 .. 15, zeros
+            } else {
+#pragma unroll
+                for (int ks = 0; ks < NKS; ++ks) bw[ks][q] = *(const bf16x8*)(a.w6r + ((long)q * h.feat + col) * KP + 16 * ks + 8 * lh);
+            }
         }
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
@@ -842,26 +865,28 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
     };
     const float q8s = Q8 ? h.q8_slot->scale : 1.f;
     float q8_amax = 0.f;
-    bf16x8 bwn[3];
+    bf16x8 bwn[NKS][3];
     uint32_t mwn[2];
     load_chunk_inputs(nch - 1, bwn, mwn);
     for (int c = nch - 1; c >= 0; --c) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // chunk c (this wave's pieces), its inputs; the previous copy-out
         __builtin_amdgcn_s_barrier();                         // ... everyone's: the output region and chunk c + 1's image are free
         asm volatile("" ::: "memory");
-        bf16x8 bw[3];
+        bf16x8 bw[NKS][3];
         uint32_t mw[2];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) bw[q] = bwn[q];
+        for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) bw[ks][q] = bwn[ks][q];
         mw[0] = mwn[0]; mw[1] = mwn[1];
         if (c >= 1) load_chunk_inputs(c - 1, bwn, mwn);
         if (c >= 1 && c != nch - 1) issue_chunk(c - 1);       // (chunk nch - 2 was issued before the row phase)
         const char* fimg = lds + (c & 1) * HW_FIMG;
         const int c0 = c * CH_PW, cip = wave * 32 + lc;
-        // ---- dL/d(pre5) = (dlogits W6^T) * relu'(pre5): one 16-deep k-step x 6 addend pairs ----
+        // ---- dL/d(pre5) = (dlogits W6^T) * relu'(pre5): NKS 16-deep k-steps x 6 addend pairs ----
         {
             f32x16 acc[2];
-            head_dpre_product(acc, da, bw);
+            head_dpre_product<NKS>(acc, da, bw);
             float s1 = 0.f;
             if constexpr (Q8) {
                 unsigned char* timg = (unsigned char*)xreg;
@@ -898,7 +923,9 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
             for (int ks = 0; ks < CH_ROWS / 16; ++ks) head_dw6t_step(acc, fimg, ks, dt[ks], wave, lane);
-            *(f32x4*)(part_row + (long)(c0 + cip) * KMAX + 4 * lh) = (f32x4){acc[0], acc[1], acc[2], acc[3]};
+#pragma unroll
+            for (int g = 0; g < KP / 8; ++g)                  // registers 4 g .. 4 g + 3 = classes 8 g + 4 lh .. + 3
+                *(f32x4*)(part_row + (long)(c0 + cip) * KP + 8 * g + 4 * lh) = (f32x4){acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
         }
         lds_barrier();                                        // the output image(s) of the chunk are complete
         if constexpr (Q8) {
@@ -926,13 +953,15 @@ __global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArg
 int launch_w6_split(const HeadWideArgs& a, hipStream_t s) {
     const HeadArgs& h = a.h;
     if (!a.w6c || !a.w6r || !h.w) return -3;
-    MRGAN_LAUNCH(w6_split_kernel, dim3((h.feat + 255) / 256), dim3(256), 0, s, h.w, h.ldw, h.feat, h.feat_valid, h.classes, a.w6c, a.w6r);
+    if (h.ldw == KWIDE) MRGAN_LAUNCH(w6_split_kernel<KWIDE>, dim3((h.feat + 255) / 256), dim3(256), 0, s, h.w, h.ldw, h.feat, h.feat_valid, h.classes, a.w6c, a.w6r);
+    else MRGAN_LAUNCH(w6_split_kernel<KMAX>, dim3((h.feat + 255) / 256), dim3(256), 0, s, h.w, h.ldw, h.feat, h.feat_valid, h.classes, a.w6c, a.w6r);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int launch_head_wide(const HeadWideArgs& a, hipStream_t s) {
     const HeadArgs& h = a.h;
-    if ((h.feat % CH_PW) != 0 || h.classes > KMAX || !a.mask || !a.w6c || !a.w6r || !h.part || !h.loss_part) return -3;
+    const int kp = h.ldw;                                     // the class pitch of W6, its addends, the logits and the partial rows
+    if ((h.feat % CH_PW) != 0 || (kp != KMAX && kp != KWIDE) || h.classes > kp || !a.mask || !a.w6c || !a.w6r || !h.part || !h.loss_part) return -3;
     for (int i = 0; i < h.nseg; ++i)
         if (h.seg_kind[i] != HEAD_LAB && h.seg_kind[i] != HEAD_UNL && h.seg_kind[i] != HEAD_FAKE) return -3;
     if ((long)h.rows * h.ldf * 2 >= (1L << 31)) return -3;
@@ -940,7 +969,10 @@ int launch_head_wide(const HeadWideArgs& a, hipStream_t s) {
     if (q8 ? !(h.q8 || h.q8t) : !h.dpre) return -3;
     // (the dynamic-LDS limit of both instantiations is raised by chain_init_attributes, outside any stream capture)
     const dim3 grid((h.rows + CH_ROWS - 1) / CH_ROWS, h.nseg), block(CH_THREADS);
-    if (q8) MRGAN_LAUNCH((head_wide_kernel<true>), grid, block, HW_LDS, s, a);
+    if (kp == KWIDE) {
+        if (q8) return -3;
+        MRGAN_LAUNCH((head_wide_kernel<false, KWIDE>), grid, block, hw_lds(KWIDE), s, a);
+    } else if (q8) MRGAN_LAUNCH((head_wide_kernel<true>), grid, block, HW_LDS, s, a);
     else MRGAN_LAUNCH((head_wide_kernel<false>), grid, block, HW_LDS, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -956,6 +988,7 @@ int chain_init_attributes() {
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_GFWD, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(32));
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, HW_LDS);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_wide_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, HW_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_wide_kernel<false, KWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, hw_lds(KWIDE));
     return e == hipSuccess ? 0 : -2;
 }
 
@@ -967,6 +1000,8 @@ int launch_chain(const ChainArgs& a, hipStream_t s) {
     static const int nops[3] = {7, 3, 3};
     if (a.variant < 0 || a.variant > 2 || a.nops != nops[a.variant]) return -3;
     if (a.block_rows != 64 && !(a.block_rows == 32 && a.variant != CH_V_DTAIL)) return -3;
+    // the head inside the D-tail chain is an 8-class kernel (its scratch is half of image 0)
+    if (a.variant == CH_V_DTAIL && (a.head.classes > KMAX || a.head.ldw != KMAX)) return -3;
     for (int i = 0; i < a.nops; ++i) {
         const ChainOp& op = a.op[i];
         if (op.kind != want[a.variant][i]) return -3;

@@ -5,6 +5,9 @@
 //                                 feature layers wider than 256 columns): the three small products as MFMAs at fp32 accuracy
 //                                 (see chain_head) over a block of CH_ROWS rows and the 256 feature columns of one LDS image.
 // Each kernel keeps its own operand staging (where W6, the label and the relu-mask words come from) and its own barriers.
+// KP: the class pitch (aux_kernels.h).  KP = 8 is the layout of chain_head and of every 8-class head; at KP = 32 (head_kernel and
+// head_wide_kernel) all 32 columns of the logits product are kept, dL/d(pre5) takes two 16-deep k-steps and dW6^T stores all
+// sixteen accumulator registers.
 #pragma once
 #include "chain.h"
 
@@ -27,18 +30,18 @@ __device__ __forceinline__ void split3(float v, __bf16& hi, __bf16& mid, __bf16&
 // segment gives zeros.
 // ALL_KINDS: head_kernel also serves HEAD_MSE, HEAD_EVAL and HEAD_LOGITS; the matrix-core heads are launched with the three
 // training kinds only (their launchers check it) and compile those branches out.
-template <bool ALL_KINDS>
-__device__ __forceinline__ void head_row(float (&l)[KMAX], const float (&b)[KMAX], int kind, int y, int classes, float inv_count, float unl_weight,
-                                         bool rowvalid, float& loss0, float& loss1, float& err, float (&dl)[KMAX]) {
+template <bool ALL_KINDS, int KP = KMAX>
+__device__ __forceinline__ void head_row(float (&l)[KP], const float (&b)[KP], int kind, int y, int classes, float inv_count, float unl_weight,
+                                         bool rowvalid, float& loss0, float& loss1, float& err, float (&dl)[KP]) {
     float mx = -3.0e38f;
 #pragma unroll
-    for (int c = 0; c < KMAX; ++c) {
+    for (int c = 0; c < KP; ++c) {
         if (c < classes) { l[c] += b[c]; mx = fmaxf(mx, l[c]); }
     }
     int am = 0;
-    float se = 0.f, p[KMAX];
+    float se = 0.f, p[KP];
 #pragma unroll
-    for (int c = KMAX - 1; c >= 0; --c) {
+    for (int c = KP - 1; c >= 0; --c) {
         p[c] = (c < classes) ? expf(l[c] - mx) : 0.f;
         se += p[c];
         if (c < classes && l[c] == mx) am = c;            // ties -> first index (theano argmax)
@@ -47,14 +50,14 @@ __device__ __forceinline__ void head_row(float (&l)[KMAX], const float (&b)[KMAX
     const float inv_se = 1.0f / se;
     loss0 = 0.f; loss1 = 0.f; err = 0.f;
 #pragma unroll
-    for (int c = 0; c < KMAX; ++c) dl[c] = 0.f;
+    for (int c = 0; c < KP; ++c) dl[c] = 0.f;
     if (!rowvalid) return;
     if (ALL_KINDS && kind == HEAD_MSE) {
         // Keras 'mse' on one-hot targets (mr_nn.py:99, :112): mean over the classes, then over the batch
         err = (y >= 0 && am != y) ? 1.f : 0.f;
         const float invc = 1.0f / (float)classes;
 #pragma unroll
-        for (int c = 0; c < KMAX; ++c) {
+        for (int c = 0; c < KP; ++c) {
             if (c < classes && y >= 0) {                  // label -1: padding row of a short last batch, no contribution
                 const float d = l[c] - (c == y ? 1.f : 0.f);
                 loss0 = fmaf(d * d, invc, loss0);
@@ -66,7 +69,7 @@ __device__ __forceinline__ void head_row(float (&l)[KMAX], const float (&b)[KMAX
         if (kind == HEAD_LAB) {
             float ly = 0.f;
 #pragma unroll
-            for (int c = 0; c < KMAX; ++c) {
+            for (int c = 0; c < KP; ++c) {
                 if (c == y) ly = l[c];
                 dl[c] = (p[c] * inv_se - (c == y ? 1.f : 0.f)) * inv_count;
             }
@@ -77,7 +80,7 @@ __device__ __forceinline__ void head_row(float (&l)[KMAX], const float (&b)[KMAX
         const float k = 0.5f * inv_count * unl_weight * (kind == HEAD_UNL ? (sg - 1.0f) : sg);
         loss1 = (kind == HEAD_UNL) ? 0.5f * (sp - lse) : 0.5f * sp;
 #pragma unroll
-        for (int c = 0; c < KMAX; ++c) dl[c] = k * p[c] * inv_se;
+        for (int c = 0; c < KP; ++c) dl[c] = k * p[c] * inv_se;
     }
 }
 // whether head_row reads the label of a row of this kind
@@ -96,54 +99,77 @@ __device__ __forceinline__ void head_logits_step(f32x16 (&acc)[2], const char* f
         acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa1, fb[p], acc[1], 0, 0, 0);
     }
 }
-// the wave's partial [64][8] tile -> lpart [8 waves][CH_ROWS][KMAX] (columns 8 .. 31 of the product are padding)
-__device__ __forceinline__ void head_logits_scatter(const f32x16 (&acc)[2], float* lpart, int wave, int lc, int lh) {
-    if (lc < KMAX) {
+// the wave's partial [64][KP] tile -> slot `slot` of lpart [slots][CH_ROWS][head_lpitch(KP)].  KP = 8: one slot per wave, columns
+// 8 .. 31 of the product are padding.  KP = 32: eight [64][32] fp32 tiles are 64 KB, more than the kernel has beside its feature
+// images, so the tiles meet in FOUR slots in two rounds: waves 0 .. 3 store (head_logits_scatter), and behind a barrier wave
+// 4 + i adds its tile to slot i (head_logits_fold; every element belongs to one lane, so the order of the sum is fixed).  The
+// row pitch of 36 floats spreads the 64 rows of the gather's 16-byte reads over all banks.
+constexpr int head_lpitch(int KP) { return KP == KMAX ? KMAX : KP + 4; }
+constexpr int head_lslots(int KP) { return KP == KMAX ? CH_THREADS / 64 : CH_THREADS / 128; }
+template <int KP = KMAX>
+__device__ __forceinline__ void head_logits_scatter(const f32x16 (&acc)[2], float* lpart, int slot, int lc, int lh) {
+    if (lc < KP) {
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) lpart[(wave * CH_ROWS + mi * 32 + acc_row(r, lh)) * KMAX + lc] = acc[mi][r];
+            for (int r = 0; r < 16; ++r) lpart[(slot * CH_ROWS + mi * 32 + acc_row(r, lh)) * head_lpitch(KP) + lc] = acc[mi][r];
     }
 }
-// row r's logits: the sum of the eight partial tiles, wave 0 first
-__device__ __forceinline__ void head_logits_gather(const float* lpart, int r, float (&l)[KMAX]) {
+template <int KP>
+__device__ __forceinline__ void head_logits_fold(const f32x16 (&acc)[2], float* lpart, int slot, int lc, int lh) {
 #pragma unroll
-    for (int c = 0; c < KMAX; ++c) l[c] = 0.f;
+    for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-    for (int w = 0; w < CH_THREADS / 64; ++w) {
-        const f32x4 p0 = *(const f32x4*)(lpart + (w * CH_ROWS + r) * KMAX), p1 = *(const f32x4*)(lpart + (w * CH_ROWS + r) * KMAX + 4);
+        for (int r = 0; r < 16; ++r) lpart[(slot * CH_ROWS + mi * 32 + acc_row(r, lh)) * head_lpitch(KP) + lc] += acc[mi][r];
+}
+// row r's logits: the sum of the slots, slot 0 first
+template <int KP = KMAX>
+__device__ __forceinline__ void head_logits_gather(const float* lpart, int r, float (&l)[KP]) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) { l[c] += p0[c]; l[4 + c] += p1[c]; }
+    for (int c = 0; c < KP; ++c) l[c] = 0.f;
+#pragma unroll
+    for (int w = 0; w < head_lslots(KP); ++w) {
+        f32x4 p[KP / 4];
+#pragma unroll
+        for (int g = 0; g < KP / 4; ++g) p[g] = *(const f32x4*)(lpart + (w * CH_ROWS + r) * head_lpitch(KP) + 4 * g);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int g = 0; g < KP / 4; ++g) l[4 * g + c] += p[g][c];
     }
 }
 
-// ---- row r's results -> LDS: dlogits as bf16 addends dl_rc [3][CH_ROWS][KMAX] (row-major, A operand of dL/d(pre5)) and
-// dl_t [3][KMAX][CH_ROWS] (class-major, A operand of dW6^T), and red [3 + KMAX][CH_ROWS] ----
-__device__ __forceinline__ void head_rows_to_lds(const float (&dl)[KMAX], float loss0, float loss1, float err, int r, __bf16* dl_rc, __bf16* dl_t,
+// ---- row r's results -> LDS: dlogits as bf16 addends dl_rc [3][CH_ROWS][KP] (row-major, A operand of dL/d(pre5)) and
+// dl_t [3][KP][CH_ROWS] (class-major, A operand of dW6^T), and red [3 + KP][CH_ROWS] ----
+template <int KP = KMAX>
+__device__ __forceinline__ void head_rows_to_lds(const float (&dl)[KP], float loss0, float loss1, float err, int r, __bf16* dl_rc, __bf16* dl_t,
                                                  float* red) {
-    bf16x8 d3[3];
+    bf16x8 d3[3][KP / 8];
 #pragma unroll
-    for (int c = 0; c < KMAX; ++c) {
+    for (int c = 0; c < KP; ++c) {
         __bf16 p0, p1, p2;
         split3(dl[c], p0, p1, p2);
-        d3[0][c] = p0; d3[1][c] = p1; d3[2][c] = p2;
+        d3[0][c >> 3][c & 7] = p0; d3[1][c >> 3][c & 7] = p1; d3[2][c >> 3][c & 7] = p2;
     }
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-        *(bf16x8*)(dl_rc + (q * CH_ROWS + r) * KMAX) = d3[q];
 #pragma unroll
-        for (int c = 0; c < KMAX; ++c) dl_t[(q * KMAX + c) * CH_ROWS + r] = d3[q][c];
+        for (int g = 0; g < KP / 8; ++g) *(bf16x8*)(dl_rc + (q * CH_ROWS + r) * KP + 8 * g) = d3[q][g];
+#pragma unroll
+        for (int c = 0; c < KP; ++c) dl_t[(q * KP + c) * CH_ROWS + r] = d3[q][c >> 3][c & 7];
     }
-    // the eleven per-row quantities whose sums over the 64 rows leave the block (three loss terms, db6 = column sums of
-    // dlogits): to LDS, row-contiguous; eleven lanes of the last wave add them up behind the barrier (as wave-wide shuffle
-    // reductions -- eleven six-step ds_bpermute chains on this one wave -- they cost ~3 us with the other seven waves waiting)
+    // the 3 + KP per-row quantities whose sums over the 64 rows leave the block (three loss terms, db6 = column sums of
+    // dlogits): to LDS, row-contiguous; 3 + KP lanes of the last wave add them up behind the barrier (as wave-wide shuffle
+    // reductions -- eleven six-step ds_bpermute chains on this one wave at KP = 8 -- they cost ~3 us with the other seven waves
+    // waiting)
     red[0 * CH_ROWS + r] = loss0; red[1 * CH_ROWS + r] = loss1; red[2 * CH_ROWS + r] = err;
 #pragma unroll
-    for (int c = 0; c < KMAX; ++c) red[(3 + c) * CH_ROWS + r] = dl[c];
+    for (int c = 0; c < KP; ++c) red[(3 + c) * CH_ROWS + r] = dl[c];
 }
-// ... and the eleven sums (behind a barrier): loss terms -> loss_part[blk], db6 -> the block's partial-gradient row
+// ... and the 3 + KP sums (behind a barrier): loss terms -> loss_part[blk], db6 -> the block's partial-gradient row
+template <int KP = KMAX>
 __device__ __forceinline__ void head_block_sums(const float* red, const HeadArgs& h, int blk, float* part_row, int wave, int lane) {
-    if (wave == CH_THREADS / 64 - 1 && lane < 3 + KMAX) {
+    if (wave == CH_THREADS / 64 - 1 && lane < 3 + KP) {
         float s4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < CH_ROWS / 4; ++i) {
@@ -157,19 +183,30 @@ __device__ __forceinline__ void head_block_sums(const float* red, const HeadArgs
     }
 }
 
-// ---- dL/d(pre5) = (dlogits W6^T) * relu'(pre5) for the wave's 32 feature columns: one 16-deep k-step (8 classes + 8 zeros) ----
-// A fragments: the dlogits addends of rows 32 mi + lc (lh = 1: k = 8 .. 15, padding)
-__device__ __forceinline__ void head_load_dl_rows(const __bf16* dl_rc, int lc, int lh, bf16x8 (&da)[2][3]) {
+// ---- dL/d(pre5) = (dlogits W6^T) * relu'(pre5) for the wave's 32 feature columns.  KP = 8: one 16-deep k-step (8 classes +
+// 8 zeros).  KP = 32: two k-steps, classes 0 .. 15 and 16 .. 31 ----
+// A fragments of k-step ks: the dlogits addends of rows 32 mi + lc.  KP = 8: lh = 1 is k = 8 .. 15, padding.  KP = 32: lane <->
+// classes 16 ks + 8 lh .. + 7
+template <int KP = KMAX>
+__device__ __forceinline__ void head_load_dl_rows(const __bf16* dl_rc, int lc, int lh, bf16x8 (&da)[2][3], int ks = 0) {
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            da[mi][q] = *(const bf16x8*)(dl_rc + (q * CH_ROWS + mi * 32 + lc) * KMAX);
-            if (lh) da[mi][q] = zero8();
+            if constexpr (KP == KMAX) {
+                da[mi][q] = *(const bf16x8*)(dl_rc + (q * CH_ROWS + mi * 32 + lc) * KMAX);
+                if (lh) da[mi][q] = zero8();
+            } else {
+                da[mi][q] = *(const bf16x8*)(dl_rc + (q * CH_ROWS + mi * 32 + lc) * KP + 16 * ks + 8 * lh);
+            }
         }
 }
-// bw: the W6 addends of this lane's feature (k = class; zeros for lh = 1)
-__device__ __forceinline__ void head_dpre_product(f32x16 (&acc)[2], const bf16x8 (&da)[2][3], const bf16x8 (&bw)[3]) {
+// NKS k-steps; bw: the W6 addends of this lane's feature (k = class; KP = 8: zeros for lh = 1).  The smallest terms of ALL
+// k-steps come first: every MFMA rounds its sum at the size of the accumulator, so only the NKS (hi, hi) products at the end
+// round at the size of the result.  (k-step by k-step, the five small pairs of the second step would each round a full-size
+// accumulator: seven such roundings instead of two, and visibly more bf16 results that differ from head_kernel's.)
+template <int NKS>
+__device__ __forceinline__ void head_dpre_product(f32x16 (&acc)[2], const bf16x8 (&da)[NKS][2][3], const bf16x8 (&bw)[NKS][3]) {
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
@@ -179,7 +216,10 @@ __device__ __forceinline__ void head_dpre_product(f32x16 (&acc)[2], const bf16x8
 #pragma unroll
     for (int i = 5; i >= 0; --i)                              // smallest terms first
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi) acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da[mi][PA[i]], bw[PB[i]], acc[mi], 0, 0, 0);
+        for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+                acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da[ks][mi][PA[i]], bw[ks][PB[i]], acc[mi], 0, 0, 0);
 }
 // the masked product as bf16 into column cip of an activation image (the next product's A operand); returns this lane's
 // share of the column sum (the feature layer's bias gradient)
@@ -199,14 +239,15 @@ __device__ __forceinline__ float head_dpre_to_image(const f32x16 (&acc)[2], cons
     return s1;
 }
 
-// ---- dW6^T [class][feature] = dlogits^T F for the wave's 32 features: registers 0 .. 3 of the result are classes
-// 4 lh .. 4 lh + 3 of feature 32 wave + lc ----
-// A fragments of k-step ks (rows 16 ks .. + 15): lane <-> (class lc, rows 16 ks + 8 lh .. + 7), zeros for lc >= KMAX
+// ---- dW6^T [class][feature] = dlogits^T F for the wave's 32 features: registers 4 g .. 4 g + 3 of the result are classes
+// 8 g + 4 lh .. + 3 of feature 32 wave + lc (KP = 8: only g = 0 is stored) ----
+// A fragments of k-step ks (rows 16 ks .. + 15): lane <-> (class lc, rows 16 ks + 8 lh .. + 7), zeros for lc >= KP
+template <int KP = KMAX>
 __device__ __forceinline__ void head_load_dl_cols(const __bf16* dl_t, int ks, int lc, int lh, bf16x8 (&fa)[3]) {
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-        fa[q] = *(const bf16x8*)(dl_t + (q * KMAX + (lc & (KMAX - 1))) * CH_ROWS + 16 * ks + 8 * lh);
-        if (lc >= KMAX) fa[q] = zero8();
+        fa[q] = *(const bf16x8*)(dl_t + (q * KP + (lc & (KP - 1))) * CH_ROWS + 16 * ks + 8 * lh);
+        if (KP < 32 && lc >= KP) fa[q] = zero8();
     }
 }
 __device__ __forceinline__ void head_dw6t_step(f32x16& acc, const char* fimg, int ks, const bf16x8 (&fa)[3], int wave, int lane) {

@@ -14,6 +14,11 @@ def standard_scale(X_train, X_test):
     return X_train, X_test
 
 
+def resolve_num_classes(num_classes=None):
+    """The class count of a run: `None` means the reference's six materials; the engine takes 2 .. 32 (fp8: 2 .. 8)."""
+    return len(MATERIALS) if num_classes is None else int(num_classes)
+
+
 def select_labeled(X_train, y_train, num_labeled, num_unlabeled=None, num_classes=len(MATERIALS)):
     """mr_gan.py:102-107 -- the first num_labeled rows of every class (class-sorted block matrix);
     with num_unlabeled also the table-6 unlabeled pool (labeled rows included)."""

@@ -18,14 +18,14 @@ import sys
 
 import numpy as np
 
-from mr_gan_amd.data import MATERIALS, select_labeled, standard_scale
+from mr_gan_amd.data import MATERIALS, resolve_num_classes, select_labeled, standard_scale
 
 MODALITIES = ['Force', 'Temperature', 'Force and Temperature', 'Contact mic', 'Temperature and Contact Mic',
               'Force, Temperature, and Contact Mic', 'Force and Contact Mic']          # mr_gan.py:237
 
 
 def mr_gan(X, y, percentlabeled=50, percentunlabeled=None, epochs=100, trainTestSets=None, verbose=False,
-           batch_size=50, dtype='float32', seed=None, device='cuda:0', noise='irwin-hall'):
+           batch_size=50, dtype='float32', seed=None, device='cuda:0', noise='irwin-hall', num_classes=None):
     from sklearn.model_selection import train_test_split
     from sklearn.utils import shuffle
 
@@ -34,7 +34,8 @@ def mr_gan(X, y, percentlabeled=50, percentunlabeled=None, epochs=100, trainTest
     noise_flags(noise)                                             # an unknown value fails before any data is touched
 
     rs = np.random.RandomState(seed if seed is not None else np.random.randint(1 << 31))   # mr_gan.py:75 (unseeded there)
-    test_ratio = 200 * len(MATERIALS)                              # mr_gan.py:81
+    num_classes = resolve_num_classes(num_classes)                 # None: the reference's six materials
+    test_ratio = 200 * num_classes                                 # mr_gan.py:81
     num_labeled_examples = int(10 * percentlabeled)                # mr_gan.py:82
     num_unlabeled_examples = int(10 * percentunlabeled) if percentunlabeled is not None else None
 
@@ -43,17 +44,18 @@ def mr_gan(X, y, percentlabeled=50, percentunlabeled=None, epochs=100, trainTest
     else:
         X_train, X_test, y_train, y_test = trainTestSets
     if verbose:
-        print('Num of class examples in test set:', [int(np.sum(y_test == i)) for i in range(len(MATERIALS))])
+        print('Num of class examples in test set:', [int(np.sum(y_test == i)) for i in range(num_classes)])
         print('X_train:', np.shape(X_train), 'y_train:', np.shape(y_train), 'X_test:', np.shape(X_test), 'y_test:',
               np.shape(y_test))
 
     X_train, X_test = standard_scale(X_train, X_test)              # mr_gan.py:96-98
     X_train, y_train = shuffle(X_train, y_train, random_state=rs)  # mr_gan.py:101
-    x_labeled, y_labeled, x_unlabeled = select_labeled(X_train, y_train, num_labeled_examples, num_unlabeled_examples)
+    x_labeled, y_labeled, x_unlabeled = select_labeled(X_train, y_train, num_labeled_examples, num_unlabeled_examples, num_classes=num_classes)
     if verbose:
         print('x_labeled:', np.shape(x_labeled), 'y_labeled:', np.shape(y_labeled))
 
-    model = MRGAN(X_train.shape[1], batch_size=batch_size, dtype=dtype, seed=int(rs.randint(1 << 31)), device=device, noise=noise)
+    model = MRGAN(X_train.shape[1], batch_size=batch_size, dtype=dtype, seed=int(rs.randint(1 << 31)), device=device, noise=noise,
+                  num_classes=num_classes)
     if verbose:
         print('Epochs:', epochs)
         print('Batch size:', batch_size)

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from mr_gan_amd import engine as E
-from mr_gan_amd.data import MATERIALS, select_labeled, standard_scale
+from mr_gan_amd.data import resolve_num_classes, select_labeled, standard_scale
 from mr_gan_amd.model import glorot_uniform
 from mr_gan_amd.mr_gan import dataset
 from mr_gan_amd.mr_svm import baseline_tables
@@ -100,26 +100,28 @@ class MRNN(object):
 
 
 def mr_nn(X, y, percentlabeled=50, trainTestSets=None, verbose=False, epochs=100, batch_size=20, dtype='float32',
-          seed=None, device='cuda:0', noise='irwin-hall'):
+          seed=None, device='cuda:0', noise='irwin-hall', num_classes=None):
     from sklearn.model_selection import train_test_split
     from sklearn.utils import shuffle
     E.noise_flags(noise)
     rs = np.random.RandomState(seed if seed is not None else np.random.randint(1 << 31))     # mr_nn.py:71 is unseeded
-    test_ratio = 200 * len(MATERIALS)                              # mr_nn.py:74
+    num_classes = resolve_num_classes(num_classes)                 # None: the reference's six materials
+    test_ratio = 200 * num_classes                                 # mr_nn.py:74
     num_labeled_examples = int(10 * percentlabeled)                # mr_nn.py:75
     if trainTestSets is None:                                      # mr_nn.py:78-81
         X_train, X_test, y_train, y_test = train_test_split(X, y, test_size=test_ratio, stratify=y, random_state=rs)
     else:
         X_train, X_test, y_train, y_test = trainTestSets
     if verbose:
-        print('Num of class examples in test set:', [int(np.sum(y_test == i)) for i in range(len(MATERIALS))])
+        print('Num of class examples in test set:', [int(np.sum(y_test == i)) for i in range(num_classes)])
         print('X_train:', np.shape(X_train), 'y_train:', np.shape(y_train), 'X_test:', np.shape(X_test), 'y_test:', np.shape(y_test))
     X_train, X_test = standard_scale(X_train, X_test)              # mr_nn.py:86-88
     X_train, y_train = shuffle(X_train, y_train, random_state=rs)  # mr_nn.py:91
-    x_labeled, y_labeled, _ = select_labeled(X_train, y_train, num_labeled_examples)
+    x_labeled, y_labeled, _ = select_labeled(X_train, y_train, num_labeled_examples, num_classes=num_classes)
     if verbose:
         print('x_labeled:', np.shape(x_labeled), 'y_labeled:', np.shape(y_labeled))
-    model = MRNN(X_train.shape[1], batch_size=batch_size, dtype=dtype, seed=int(rs.randint(1 << 31)), device=device, noise=noise)
+    model = MRNN(X_train.shape[1], batch_size=batch_size, dtype=dtype, seed=int(rs.randint(1 << 31)), device=device, noise=noise,
+                 num_classes=num_classes)
     model.fit(x_labeled, y_labeled, epochs=epochs, rng=rs)         # mr_nn.py:117
     testerror = model.evaluate(X_test, y_test)                     # mr_nn.py:118
     model.engine.close()
