@@ -3,7 +3,7 @@ import numpy as np, torch
 from mr_gan_amd import engine as E
 from oracle import mrgan_oracle as O
 from tests.helpers import Case, SEED
-from tests.test_gpu_parity import _engine, _load, _t
+from tests.parity import engine as _engine, load as _load, to_dev as _t
 B, D = 64, 32
 case = Case(D=D, B=B, steps=1, device_z=True)
 orc = O.MRGANOracle(case.g0, case.d0)

@@ -1,5 +1,5 @@
 """numpy restatement of the engine's true-Gaussian generator (csrc/common.h: gauss_pairhash / gauss_block, selected by
-MRGAN_FLAG_GAUSS_NOISE) and the twins of tests.helpers' noise_set / draw_z / Case that draw from it.
+MRGAN_FLAG_GAUSS_NOISE), and tests.helpers' noise_set / draw_z / Case drawing from it.
 
 The normal at global row R, column C of (seed, site, seg, step):
     key = noise_key(seed, site*256 + seg, step)
@@ -10,9 +10,8 @@ The normal at global row R, column C of (seed, site, seg, step):
 The integer part is exact on both sides; the transcendentals here are float64, on the device precise float32."""
 import numpy as np
 
-from oracle import mrgan_oracle as O
 from oracle.mrgan_oracle import mix32, noise_key
-from tests.helpers import SEED, Case, layer_dims
+from tests import helpers as H
 
 GAUSS_DOMAIN = 0x47415553
 SUPPORT = float(np.sqrt(48.0 * np.log(2.0)))            # u1 >= 2^-24: |n| <= sqrt(-2 ln 2^-24) = 5.768
@@ -40,33 +39,20 @@ def gaussian_normal(seed, site, seg, step, rows, cols, row0=0, dtype=np.float64)
     return np.where(odd, r * np.sin(2.0 * np.pi * u2), r * np.cos(2.0 * np.pi * u2)).astype(dtype)
 
 
-def noise_set(seed, seg, step, B, D, row0=0, dtype=np.float64, d_hidden=O.D_HIDDEN):
-    dims = layer_dims(D, d_hidden)
-    return [gaussian_normal(seed, l, seg, step, B, dims[l], row0=row0, dtype=dtype) for l in range(5)]
+def noise_set(*args, **kw):
+    return H.noise_set(*args, normal=gaussian_normal, **kw)
 
 
-def draw_z(seed, step, B, row0=0, dtype=np.float64, nz=O.NOISE_SIZE):
-    return gaussian_normal(seed, O.SITE_Z, 0, step, B, nz, row0=row0, dtype=dtype)
+def draw_z(*args, **kw):
+    return H.draw_z(*args, normal=gaussian_normal, **kw)
 
 
-class GaussCase(Case):
+class GaussCase(H.Case):
     """tests.helpers.Case with layer noise and device z from the true-Gaussian generator.  The oracle and the mirror take z
     and the layer noise as inputs, so nothing else changes."""
 
-    def disc_inputs(self, t, it, rows=None, row0=0):
-        nB = rows or self.B
-        sl = slice(row0, row0 + nB)
-        z = self.z1[t][sl] if self.z1 is not None else draw_z(self.noise_seed, it, nB, row0)
-        ns = lambda seg: noise_set(self.noise_seed, seg, it, nB, self.D, row0, self.dtype, self.d_hidden)
-        return dict(x_lab=self.x_lab[t][sl].astype(self.dtype), labels=self.labels[t][sl], x_unl=self.x_unl[t][sl].astype(self.dtype),
-                    z=np.asarray(z, self.dtype), n_lab=ns(0), n_unl=ns(1), n_fake=ns(2))
-
-    def gen_inputs(self, t, it, rows=None, row0=0):
-        nB = rows or self.B
-        sl = slice(row0, row0 + nB)
-        z = self.z2[t][sl] if self.z2 is not None else draw_z(self.noise_seed, it, nB, row0)
-        ns = lambda seg: noise_set(self.noise_seed, seg, it, nB, self.D, row0, self.dtype, self.d_hidden)
-        return dict(x_unl=self.x_unl2[t][sl].astype(self.dtype), z=np.asarray(z, self.dtype), n_fake=ns(0), n_real=ns(1))
+    def __init__(self, *args, **kw):
+        H.Case.__init__(self, *args, normal=gaussian_normal, **kw)
 
 
 def moments(x):

@@ -16,22 +16,28 @@ def layer_dims(D, d_hidden=O.D_HIDDEN):
     return (D,) + tuple(d_hidden)
 
 
-def noise_set(seed, seg, step, B, D, row0=0, dtype=np.float64, d_hidden=O.D_HIDDEN):
+def noise_set(seed, seg, step, B, D, row0=0, dtype=np.float64, d_hidden=O.D_HIDDEN, normal=O.device_normal):
+    """the five GaussianNoise draws of one segment; `normal` = the restated generator (tests.gaussian_noise has the other one)"""
     dims = layer_dims(D, d_hidden)
-    return [O.device_normal(seed, l, seg, step, B, dims[l], row0=row0, dtype=dtype) for l in range(5)]
+    return [normal(seed, l, seg, step, B, dims[l], row0=row0, dtype=dtype) for l in range(5)]
 
 
-def draw_z(seed, step, B, row0=0, dtype=np.float64, nz=O.NOISE_SIZE):
-    return O.device_normal(seed, O.SITE_Z, 0, step, B, nz, row0=row0, dtype=dtype)
+def draw_z(seed, step, B, row0=0, dtype=np.float64, nz=O.NOISE_SIZE, normal=O.device_normal):
+    return normal(seed, O.SITE_Z, 0, step, B, nz, row0=row0, dtype=dtype)
 
 
 class Case(object):
-    """A reproducible training problem + its oracle trajectory."""
+    """A reproducible training problem + its oracle trajectory.
+
+    normal: the generator that layer noise and device-drawn z come from (the oracle and the mirror take both as inputs).
+    K: a problem with K classes.  The six-class draws stay what they are (golden files and measured bounds rest on them), so
+    the weights (last dense from O.init_params(K=K)) and the labels are drawn again from a stream of their own, with class 8
+    and class K-1 present in every batch."""
 
     def __init__(self, D=16, B=50, steps=3, seed=7, noise_seed=SEED, dtype=np.float64, device_z=False,
-                 d_hidden=O.D_HIDDEN, g_hidden=O.G_HIDDEN):
+                 d_hidden=O.D_HIDDEN, g_hidden=O.G_HIDDEN, normal=O.device_normal, K=None):
         rng = np.random.default_rng(seed)
-        self.D, self.B, self.steps, self.noise_seed = D, B, steps, noise_seed
+        self.D, self.B, self.steps, self.noise_seed, self.normal = D, B, steps, noise_seed, normal
         self.d_hidden, self.g_hidden = tuple(d_hidden), tuple(g_hidden)
         g, d = O.init_params(D, seed=seed, dtype=dtype, g_hidden=self.g_hidden, d_hidden=self.d_hidden)
         # non-trivial biases / BN affine so every path carries signal
@@ -46,27 +52,33 @@ class Case(object):
         self.z2 = None if device_z else rng.standard_normal((steps, B, O.NOISE_SIZE)).astype(np.float32)
         self.probe = rng.standard_normal((64, D)).astype(np.float32)
         self.dtype = dtype
+        self.K = O.NUM_CLASSES if K is None else K
+        if K is not None:
+            rng = np.random.default_rng(seed + 1000 * K)
+            g, d = O.init_params(D, seed=seed, dtype=dtype, g_hidden=self.g_hidden, d_hidden=self.d_hidden, K=K)
+            self.g0 = [p + 0.05 * rng.standard_normal(p.shape).astype(dtype) for p in g]
+            self.d0 = [p + 0.05 * rng.standard_normal(p.shape).astype(dtype) for p in d]
+            self.labels = rng.integers(0, K, (steps, B)).astype(np.int32)
+            self.labels[:, 0], self.labels[:, B - 1] = 8, K - 1
+            assert self.d0[-2].shape[1] == K and (self.labels >= 8).any() and (self.labels == K - 1).any()
+
+    def _draws(self, z, it, rows, row0, segs):
+        """(row slice, z, one noise_set per segment) of a sub-step at Keras iteration `it`, optionally of a row shard"""
+        nB = rows or self.B
+        sl = slice(row0, row0 + nB)
+        z = z[sl] if z is not None else draw_z(self.noise_seed, it, nB, row0, normal=self.normal)
+        return sl, np.asarray(z, self.dtype), [noise_set(self.noise_seed, seg, it, nB, self.D, row0, self.dtype, self.d_hidden, self.normal)
+                                               for seg in range(segs)]
 
     def disc_inputs(self, t, it, rows=None, row0=0):
         """numpy inputs of D sub-step t executed at Keras iteration `it` (optionally a row shard)."""
-        B = self.B
-        sl = slice(row0, row0 + (rows or B))
-        nB = rows or B
-        z = self.z1[t][sl] if self.z1 is not None else draw_z(self.noise_seed, it, nB, row0)
+        sl, z, (n_lab, n_unl, n_fake) = self._draws(None if self.z1 is None else self.z1[t], it, rows, row0, 3)
         return dict(x_lab=self.x_lab[t][sl].astype(self.dtype), labels=self.labels[t][sl],
-                    x_unl=self.x_unl[t][sl].astype(self.dtype), z=np.asarray(z, self.dtype),
-                    n_lab=noise_set(self.noise_seed, 0, it, nB, self.D, row0, self.dtype, self.d_hidden),
-                    n_unl=noise_set(self.noise_seed, 1, it, nB, self.D, row0, self.dtype, self.d_hidden),
-                    n_fake=noise_set(self.noise_seed, 2, it, nB, self.D, row0, self.dtype, self.d_hidden))
+                    x_unl=self.x_unl[t][sl].astype(self.dtype), z=z, n_lab=n_lab, n_unl=n_unl, n_fake=n_fake)
 
     def gen_inputs(self, t, it, rows=None, row0=0):
-        B = self.B
-        sl = slice(row0, row0 + (rows or B))
-        nB = rows or B
-        z = self.z2[t][sl] if self.z2 is not None else draw_z(self.noise_seed, it, nB, row0)
-        return dict(x_unl=self.x_unl2[t][sl].astype(self.dtype), z=np.asarray(z, self.dtype),
-                    n_fake=noise_set(self.noise_seed, 0, it, nB, self.D, row0, self.dtype, self.d_hidden),
-                    n_real=noise_set(self.noise_seed, 1, it, nB, self.D, row0, self.dtype, self.d_hidden))
+        sl, z, (n_fake, n_real) = self._draws(None if self.z2 is None else self.z2[t], it, rows, row0, 2)
+        return dict(x_unl=self.x_unl2[t][sl].astype(self.dtype), z=z, n_fake=n_fake, n_real=n_real)
 
     def run_oracle(self, mirror=False, quantize=None):
         """trajectory through the fp64 restatement, or (mirror=True) through the engine-dataflow mirror with the engine's
@@ -149,6 +161,35 @@ def colsum_groups(v):
     out = np.zeros((nbatch * tiles_m, n), dtype=v.dtype)
     np.add.at(out, prow.ravel(), v.reshape(nbatch * m, n))
     return out
+
+
+def oracle_logmel(contacts, sr=48000, n_mels=128):
+    """CPU stand-in for the GPU front end of dataset() (the suite runs without a GPU; tests/test_gpu_parity.py holds the HIP
+    kernel to it)"""
+    from oracle.melspec_oracle import log_melspectrogram
+    return [log_melspectrogram(np.asarray(c, dtype=np.float64), sr=sr, n_mels=n_mels).astype(np.float32).flatten() for c in contacts]
+
+
+def write_fake_mreo(tmp, ft=4, cm=0.2, objects=2, trials=3):
+    """a synthetic MREO-format pickle per material under `tmp` (processdata.py:23-34)"""
+    import os
+    import pickle
+    from mr_gan_amd.data import MATERIALS
+    rng = np.random.default_rng(0)
+    for m, material in enumerate(MATERIALS):
+        allData = {}
+        for o in range(objects):
+            d = {k: [] for k in ('forceTime', 'force0', 'force1', 'pressureTime', 'pressure0', 'pressure1',
+                                 'temperatureTime', 'temperature', 'contactTime', 'contact')}
+            for t in range(trials):
+                n = int(100 * ft)
+                d['force0'].append((rng.standard_normal(n) + 10 * m).tolist())
+                d['force1'].append((rng.standard_normal(n) + 20 * m).tolist())
+                d['temperature'].append((rng.standard_normal(n) + 30 * m).tolist())
+                d['contact'].append(rng.standard_normal(int(48000 * cm)).tolist())
+            allData['%s_obj%d' % (material, o)] = d
+        with open(os.path.join(tmp, 'processed_0.1sbefore_%s_times_%.2f_%.2f.pkl' % (material, ft, cm)), 'wb') as f:
+            pickle.dump(allData, f, 2)          # protocol 2 = what Python-2 cPickle.HIGHEST_PROTOCOL wrote
 
 
 def stub_training(job, datasets, device):

@@ -7,39 +7,16 @@ import pickle
 import numpy as np
 
 from mr_gan_amd import dataset
-from mr_gan_amd.data import MATERIALS
 from oracle.melspec_oracle import log_melspectrogram, mel_filterbank
-
-
-def _oracle_logmel(contacts, sr=48000, n_mels=128):
-    """CPU stand-in for the GPU front end (this suite runs without a GPU; tests/test_gpu_parity.py holds the HIP kernel to it)"""
-    return [log_melspectrogram(np.asarray(c, dtype=np.float64), sr=sr, n_mels=n_mels).astype(np.float32).flatten() for c in contacts]
-
-
-def _write_fake_mreo(tmp, ft=4, cm=0.2, objects=2, trials=3):
-    rng = np.random.default_rng(0)
-    for m, material in enumerate(MATERIALS):
-        allData = {}
-        for o in range(objects):
-            d = {k: [] for k in ('forceTime', 'force0', 'force1', 'pressureTime', 'pressure0', 'pressure1',
-                                 'temperatureTime', 'temperature', 'contactTime', 'contact')}
-            for t in range(trials):
-                n = int(100 * ft)
-                d['force0'].append((rng.standard_normal(n) + 10 * m).tolist())
-                d['force1'].append((rng.standard_normal(n) + 20 * m).tolist())
-                d['temperature'].append((rng.standard_normal(n) + 30 * m).tolist())
-                d['contact'].append(rng.standard_normal(int(48000 * cm)).tolist())
-            allData['%s_obj%d' % (material, o)] = d
-        with open(os.path.join(tmp, 'processed_0.1sbefore_%s_times_%.2f_%.2f.pkl' % (material, ft, cm)), 'wb') as f:
-            pickle.dump(allData, f, 2)          # protocol 2 = what Python-2 cPickle.HIGHEST_PROTOCOL wrote
+from tests.helpers import oracle_logmel, write_fake_mreo
 
 
 def test_dataset_modalities_and_order(tmp_path):
-    _write_fake_mreo(str(tmp_path))
+    write_fake_mreo(str(tmp_path))
     mel = 128 * 19
     want = {0: 800, 1: 400, 2: 1200, 3: mel, 4: 400 + mel, 5: 1200 + mel, 6: 800 + mel}
     for mod, d in want.items():
-        X, y = dataset(modalities=mod, data_dir=str(tmp_path), logmel_fn=_oracle_logmel)
+        X, y = dataset(modalities=mod, data_dir=str(tmp_path), logmel_fn=oracle_logmel)
         assert X.shape == (6 * 2 * 3, d) and y.shape == (36,)
         assert list(np.unique(y)) == list(range(6))
     X, y = dataset(modalities=2, data_dir=str(tmp_path))      # temperature | force0 | force1 (mr_gan.py:54)
@@ -48,10 +25,10 @@ def test_dataset_modalities_and_order(tmp_path):
     objs = dataset(modalities=0, leaveObjectOut=True, data_dir=str(tmp_path))
     assert len(objs) == 12 and np.array(objs['glass_obj1']['x']).shape == (3, 800)
     # the contact-microphone block is the flattened [128 mels][19 frames] matrix of that trial (mr_gan.py:47, :57-62)
-    X, y = dataset(modalities=5, data_dir=str(tmp_path), logmel_fn=_oracle_logmel)
+    X, y = dataset(modalities=5, data_dir=str(tmp_path), logmel_fn=oracle_logmel)
     with open(os.path.join(str(tmp_path), 'processed_0.1sbefore_plastic_times_4.00_0.20.pkl'), 'rb') as f:
         first = pickle.load(f)['plastic_obj0']
-    np.testing.assert_allclose(X[0][1200:], _oracle_logmel([first['contact'][0]])[0], rtol=0, atol=0)
+    np.testing.assert_allclose(X[0][1200:], oracle_logmel([first['contact'][0]])[0], rtol=0, atol=0)
     np.testing.assert_allclose(X[0][:400], first['temperature'][0])
 
 
@@ -60,7 +37,7 @@ def test_dataset_without_a_gpu_fails_loudly(tmp_path):
     import torch
     if torch.cuda.is_available():
         pytest.skip("needs a box without a GPU")
-    _write_fake_mreo(str(tmp_path), objects=1, trials=1)
+    write_fake_mreo(str(tmp_path), objects=1, trials=1)
     with pytest.raises(RuntimeError, match="GPU only"):
         dataset(modalities=3, data_dir=str(tmp_path))
 

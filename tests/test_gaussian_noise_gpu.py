@@ -1,9 +1,9 @@
 """MRGAN_FLAG_GAUSS_NOISE on the device: the true-Gaussian generator against its restatement (tests/gaussian_noise.py), its
 distribution, every call site through the unchanged oracle / mirror, the untouched default path, and the accuracy evidence.
 
-The step-level tests run the BODIES of the existing parity tests (tests/test_gpu_parity.py) with three substitutions and the
-same bounds: the Case draws its layer noise and z from gaussian_normal, every handle carries the flag, and (fp32) z is drawn
-on the device so that site 16 is covered.  Without the feature the flag is ignored, the device keeps drawing Irwin-Hall
+The step-level tests are the bodies of tests/parity.py, with the same bounds as for the default engine, on the variant
+P.GAUSSIAN: the problems draw their layer noise and z from gaussian_normal, every handle carries the flag, and (fp32) z is
+drawn on the device so that site 16 is covered.  Without the feature the flag is ignored, the device keeps drawing Irwin-Hall
 variates, and each of these tests fails."""
 import numpy as np
 import pytest
@@ -11,13 +11,12 @@ import torch
 
 from oracle import mrgan_oracle as O
 from tests import gaussian_noise as G
-from tests import test_gpu_parity as P
-from tests.helpers import SEED, rel_err, update_rel_err
+from tests import parity as P
+from tests.helpers import SEED
 
 pytestmark = pytest.mark.gpu
 
-DEV = P.DEV
-_t = P._t
+_t = P.to_dev
 
 # Float error of the device's Box-Muller (logf, sqrtf, sincospif in fp32) against the fp64 restatement, measured on an MI355X
 # over 2 679 424 values (2048 x 512 at (1, 1, 3), 1024 x 1152 at (4, 2, 11), 1000 x 400 at (0, 0, 0), 512 x 100 at (16, 0, 5)):
@@ -30,34 +29,6 @@ A_ABS, B_REL = 4 * 1.79e-7, 4 * 2.26e-7
 assert A_ABS + 6.0 * B_REL <= 1e-5
 
 
-def _flagged(build):
-    def flagged(D, B, dtype, flags=0, **kw):
-        from mr_gan_amd import engine as E
-        return build(D, B, dtype, flags=flags | E.FLAG_GAUSS_NOISE, **kw)
-    return flagged
-
-
-_gauss_engine = _flagged(P._engine)
-
-
-@pytest.fixture
-def gaussian_bodies(monkeypatch):
-    """the existing parity tests' bodies on true-Gaussian handles: their Case, noise_set and engine builder swapped"""
-    from mr_gan_amd import engine as E
-    real_default = E.default_config
-
-    def default_config(d_in, batch):                    # (bodies that fill a Config themselves)
-        cfg = real_default(d_in, batch)
-        cfg.flags |= E.FLAG_GAUSS_NOISE
-        return cfg
-
-    monkeypatch.setattr(P, "Case", G.GaussCase)
-    monkeypatch.setattr(P, "noise_set", G.noise_set)
-    monkeypatch.setattr(P, "_engine", _flagged(P._engine))
-    monkeypatch.setattr(E, "default_config", default_config)
-    return P
-
-
 # ---------------------------------------------------------------------------------------------------------
 # 1. device == restatement
 # ---------------------------------------------------------------------------------------------------------
@@ -68,7 +39,7 @@ def _float_error(got, ref):
 
 
 def test_device_gaussian_matches_restatement():
-    eng = _gauss_engine(16, 52, 0)
+    eng = P.GAUSSIAN.engine(16, 52, 0)
     # the tuples of test_device_noise_matches_restatement with even first rows (the device draws whole row pairs), plus an odd
     # number of rows
     for site, seg, step, rows, cols, row0 in [(0, 0, 0, 52, 16, 0), (3, 2, 7, 50, 250, 0), (16, 0, 5, 48, 100, 48), (2, 1, 9, 70, 96, 36),
@@ -90,7 +61,7 @@ def test_device_gaussian_matches_restatement():
 
 
 def test_default_handle_of_the_same_geometry_still_draws_the_integer_sums():
-    eng = P._engine(16, 52, 0)
+    eng = P.engine(16, 52, 0)
     for site, seg, step, rows, cols, row0 in [(0, 0, 0, 52, 16, 0), (3, 2, 7, 50, 250, 0), (16, 0, 5, 48, 100, 48), (2, 1, 9, 70, 96, 37)]:
         got = eng.debug_noise(site, seg, step, rows, cols, row0).cpu().numpy()
         sums = O.device_noise_sums(SEED, site, seg, step, rows, cols, row0=row0)
@@ -102,7 +73,7 @@ def test_default_handle_of_the_same_geometry_still_draws_the_integer_sums():
 # 2. distribution of the device's draw
 # ---------------------------------------------------------------------------------------------------------
 def test_device_gaussian_distribution():
-    eng = _gauss_engine(16, 52, 0)
+    eng = P.GAUSSIAN.engine(16, 52, 0)
     G.check_distribution(eng.debug_noise(1, 1, 3, 2048, 512).cpu().numpy())
     eng.close()
 
@@ -111,58 +82,33 @@ def test_device_gaussian_distribution():
 # 3. every call site, through the unchanged oracle
 # ---------------------------------------------------------------------------------------------------------
 def test_fp32_gradients_match_oracle_gaussian():
-    """test_fp32_gradients_match_oracle (D = 48, B = 50) with the flag and device-drawn z: stage_kernel (site 0, site 16) and
-    the fp32 forward epilogues (sites 1 .. 4), same bounds"""
-    from mr_gan_amd import engine as E
-    case = G.GaussCase(D=48, B=50, steps=1, device_z=True)
-    orc = O.MRGANOracle(case.g0, case.d0)
-    (ll, lu, err), gd, _ = orc.disc_grads(**case.disc_inputs(0, 0))
-    eng = _gauss_engine(48, 50, 0, flags=E.FLAG_FLAT_GRADS | E.FLAG_SYNC_STATS)
-    P._load(eng, case)
-    da = E.Engine.disc_args(_t(case.x_lab[0]), _t(case.labels[0], torch.int32), _t(case.x_unl[0]))
-    eng.disc_step(da, E.D_GEN, E.D_MAIN, want_outputs=False)
-    for i, (a, b) in enumerate(zip(eng.get_slot(E.NET_D, 2), gd)):
-        assert rel_err(a, b) < 2e-5, ("dD", i, rel_err(a, b))
-    out = eng.disc_step(da, E.D_ADAM, E.D_ADAM)
-    np.testing.assert_allclose(out, (ll, lu, err), rtol=2e-4, atol=2e-5)
-    orc.adam.apply(orc.d, gd, 'd')
-    loss, gg, _ = orc.gen_grads(**case.gen_inputs(0, 1))
-    ga = E.Engine.gen_args(_t(case.x_unl2[0]))
-    eng.gen_step(ga, E.G_GEN, E.G_TAIL, want_outputs=False)
-    for i, (a, b) in enumerate(zip(eng.get_slot(E.NET_G, 2), gg)):
-        assert rel_err(a, b) < 2e-4, ("dG", i, rel_err(a, b))
-    assert abs(eng.gen_step(ga, E.G_ADAM, E.G_ADAM) - loss) < 2e-3 * abs(loss) + 1e-9
-    eng.close()
+    """(D = 48, B = 50) with device-drawn z: stage_kernel (site 0, site 16) and the fp32 forward epilogues (sites 1 .. 4)"""
+    P.fp32_gradients_match_oracle(P.GAUSSIAN, 48, 50, device_z=True)
 
 
 @pytest.mark.parametrize("D,B", [(400, 50), (72, 132)])
-def test_fp32_steps_match_oracle_gaussian(gaussian_bodies, monkeypatch, D, B):
-    """the body of test_fp32_steps_match_oracle, z drawn on the device"""
-    real_case, real_run = gaussian_bodies.Case, gaussian_bodies._run_engine
-    monkeypatch.setattr(P, "Case", lambda **kw: real_case(device_z=True, **kw))
-    monkeypatch.setattr(P, "_run_engine", lambda eng, case: real_run(eng, case, device_z=True))
-    P.test_fp32_steps_match_oracle(D, B)
+def test_fp32_steps_match_oracle_gaussian(D, B):
+    P.fp32_steps_match_oracle(P.GAUSSIAN, D, B, device_z=True)
 
 
 @pytest.mark.parametrize("D,B", [(512, 4096),      # the bench workload: chain kernel (64-row blocks), 8-wave 128x128 tiles
                                  (400, 1024)])     # 64x128 / 64x64 tiles, the 32-row chain of the G sub-step
-def test_bf16_gradients_match_bf16_mirror_gaussian(gaussian_bodies, D, B):
-    """the body of test_bf16_gradients_match_bf16_mirror: err(engine, mirror) < max(3e-3, 0.6 err(mirror, fp64)).  The mirror is
-    fed the fp64 restatement, not the device's own values: the device's float error (1e-6) is far below what decides a bf16
-    rounding here (the fp32-vs-fp64 accumulation the rule already allows for)."""
-    P._grad_parity(D, B, 1, 'bf16', tol=3e-3, tol_loss=5e-4)
+def test_bf16_gradients_match_bf16_mirror_gaussian(D, B):
+    """The mirror is fed the fp64 restatement, not the device's own values: the device's float error (1e-6) is far below what
+    decides a bf16 rounding here (the fp32-vs-fp64 accumulation the rule already allows for)."""
+    P.grad_parity(P.GAUSSIAN, D, B, 1, 'bf16', tol=3e-3, tol_loss=5e-4)
 
 
-def test_fp8_gradients_match_fp8_mirror_gaussian(gaussian_bodies):
+def test_fp8_gradients_match_fp8_mirror_gaussian():
     """the hidden-2048 case of test_fp8_gradients_match_fp8_mirror: the fp8-output forward epilogue with noise (256x256 and
     128x128 tiles by the launcher's table)"""
     kw = dict(d_hidden=(2048,) * 5, g_hidden=(2048,) * 2)
-    P._grad_parity(512, 1024, 2, 'fp8', tol=5e-3, tol_loss=2e-3, eval_first=False, frac=0.85, loose=(0.9, 0.8, 0.6), **kw)
+    P.grad_parity(P.GAUSSIAN, 512, 1024, 2, 'fp8', tol=5e-3, tol_loss=2e-3, eval_first=False, frac=0.85, loose=(0.9, 0.8, 0.6), **kw)
 
 
 @pytest.mark.parametrize("D,B", [(400, 256), (96, 50)])
-def test_chain_launches_equal_per_layer_launches_gaussian(gaussian_bodies, D, B):
-    P.test_chain_launches_equal_per_layer_launches(D, B)
+def test_chain_launches_equal_per_layer_launches_gaussian(D, B):
+    P.chain_launches_equal_per_layer_launches(P.GAUSSIAN, D, B)
 
 
 def test_graph_replay_equals_eager_gaussian():
@@ -182,15 +128,13 @@ def test_graph_replay_equals_eager_gaussian():
         MRGAN(32, batch_size=64, noise='normal')
 
 
-def test_supervised_steps_match_oracle_gaussian(gaussian_bodies):
-    """mrgan_sup_step (fp32, D = 48, B = 20) against MRGANOracle(lr = NN_ADAM_LR, b1 = NN_ADAM_B1): the body of
-    test_supervised_steps_match_oracle"""
-    P.test_supervised_steps_match_oracle(0, 48, 20, 0)
+def test_supervised_steps_match_oracle_gaussian():
+    """mrgan_sup_step (fp32, D = 48, B = 20) against MRGANOracle(lr = NN_ADAM_LR, b1 = NN_ADAM_B1)"""
+    P.supervised_steps_match_oracle(P.GAUSSIAN, 0, 48, 20, 0)
 
 
-def test_two_rank_emulation_equals_full_batch_gaussian(gaussian_bodies):
-    """rows are global: two shards of 32 rows draw rows 0 .. 31 and 32 .. 63 of the full batch's noise and z"""
-    P.test_two_rank_emulation_equals_full_batch()
+def test_two_rank_emulation_equals_full_batch_gaussian():
+    P.two_rank_emulation_equals_full_batch(P.GAUSSIAN)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -203,8 +147,8 @@ def test_default_path_is_untouched(dtype):
     case = G.GaussCase(D=D, B=B, steps=3, device_z=True)
 
     def run(flags):
-        eng = P._engine(D, B, dtype, flags=flags)
-        P._load(eng, case)
+        eng = P.engine(D, B, dtype, flags=flags)
+        P.load(eng, case)
         nz = eng.debug_noise(3, 2, 7, 50, 250).cpu().numpy()
         xl, yl, xu, xu2 = (_t(case.x_lab.reshape(-1, D)), _t(case.labels.reshape(-1), torch.int32), _t(case.x_unl.reshape(-1, D)),
                            _t(case.x_unl2.reshape(-1, D)))

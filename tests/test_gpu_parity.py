@@ -1,45 +1,18 @@
-"""GPU parity tests: the HIP path, called through the C ABI, against the CPU oracle on identical inputs.
-
-Tolerances.  north_star: logits within 1e-3 rel of the reference arithmetic for the fp32 mode.  "rel" is
-scale-relative (max |err| / max |ref|).  Weights after Adam steps are compared relative to the size of the
-update: early Adam moves every weight by ~lr * sign(g), so an element whose true gradient is at rounding level
-may legitimately move the other way (documented in DESIGN.md).  bf16 mode is held to 3e-2 on logits and is pinned
-for accuracy, not logits, by north_star (+-0.5 % accuracy).
-"""
+"""GPU parity tests of the default engine (six classes, the Irwin-Hall generator): the HIP path, called through the C ABI,
+against the CPU oracle on identical inputs.  The step-level bodies, their bounds and the reasoning behind the tolerances are
+in tests/parity.py, shared with the other engine variants (test_gaussian_noise_gpu.py, test_many_classes_gpu.py)."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import mrgan_oracle as O
-from tests.helpers import SEED, Case, cosine, frob_rel_err, noise_set, rel_err, update_rel_err
+from tests import parity as P
+from tests.helpers import SEED, Case, rel_err, update_rel_err
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-
-
-def _engine(D, B, dtype, flags=0, rank=0, world=1, seed=SEED, d_hidden=None, g_hidden=None):
-    from mr_gan_amd import engine as E
-    cfg = E.default_config(D, B)
-    cfg.dtype = dtype
-    cfg.seed = seed
-    cfg.flags = flags
-    cfg.rank, cfg.world = rank, world
-    for i, w in enumerate(d_hidden or ()):
-        cfg.d_hidden[i] = w
-    for i, w in enumerate(g_hidden or ()):
-        cfg.g_hidden[i] = w
-    return E.Engine(cfg, DEV)
-
-
-def _load(eng, case):
-    from mr_gan_amd import engine as E
-    eng.set_weights(E.NET_G, [p.astype(np.float32) for p in case.g0])
-    eng.set_weights(E.NET_D, [p.astype(np.float32) for p in case.d0])
-
-
-def _t(a, dtype=torch.float32):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV, dtype)
+DEV = P.DEV
+_engine, _load, _t, _run_engine = P.engine, P.load, P.to_dev, P.run_engine
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -114,117 +87,18 @@ def test_device_noise_matches_restatement():
 # ---------------------------------------------------------------------------------------------------------
 # the compiled functions of mr_gan.py:169-171
 # ---------------------------------------------------------------------------------------------------------
-def _run_engine(eng, case, device_z=False):
-    from mr_gan_amd import engine as E
-    out = dict(disc=[], gen=[])
-    out['logits0'] = eng.predict_logits(_t(case.probe)).cpu().numpy()
-    for t in range(case.steps):
-        da = E.Engine.disc_args(_t(case.x_lab[t]), _t(case.labels[t], torch.int32), _t(case.x_unl[t]),
-                                None if device_z else _t(case.z1[t]))
-        out['disc'].append(eng.disc_step(da))
-        ga = E.Engine.gen_args(_t(case.x_unl2[t]), None if device_z else _t(case.z2[t]))
-        out['gen'].append(eng.gen_step(ga))
-    out['logits'] = eng.predict_logits(_t(case.probe)).cpu().numpy()
-    out['g'] = eng.get_weights(E.NET_G)
-    out['d'] = eng.get_weights(E.NET_D)
-    return out
-
-
 @pytest.mark.parametrize("D,B", [(16, 50), (400, 50), (72, 132), (800, 256)])     # (800, .) = force-only modality (config 4)
 def test_fp32_steps_match_oracle(D, B):
-    case = Case(D=D, B=B, steps=3)
-    ref = case.run_oracle()
-    eng = _engine(D, B, 0)
-    _load(eng, case)
-    got = _run_engine(eng, case)
-    assert rel_err(got['logits0'], ref['logits0']) < 1e-5
-    # Everything after the first Adam update is bounded by what plain float32 arithmetic allows: the restatement evaluated
-    # in float32 on the same inputs deviates from its own fp64 run (rounding differences of near-zero gradients pass
-    # through Adam's m / (sqrt(v) + eps) as +-lr steps; tests/test_oracle.py shows > 1e-3 on logits at (800, 256)), so the
-    # engine gets max(the tight tolerance, 3 x that float32-vs-float64 deviation).  The first sub-step has no such slack.
-    r32 = Case(D=D, B=B, steps=3, dtype=np.float32).run_oracle()
-    for t in range(case.steps):
-        dev = max(abs(a - b) / max(abs(b), 1e-12) for a, b in zip(r32['disc'][t][:2], ref['disc'][t][:2]))
-        np.testing.assert_allclose(got['disc'][t][:2], ref['disc'][t][:2], rtol=2e-4 if t == 0 else max(2e-4, 3 * dev), atol=2e-5)
-        assert abs(got['disc'][t][2] - ref['disc'][t][2]) <= (1e-6 if t == 0 else 1.01 / B)
-        dev = abs(r32['gen'][t] - ref['gen'][t]) / abs(ref['gen'][t])
-        np.testing.assert_allclose(got['gen'][t], ref['gen'][t], rtol=max(2e-3, 3 * dev), atol=1e-9)
-    # weights after three (D, G) pairs: pins the shared Adam counter (t = 2n-1 / 2n)
-    for i, (w, wr, w0, w32) in enumerate(zip(got['d'], ref['d'], case.d0, r32['d'])):
-        assert update_rel_err(w, wr, w0) < max(0.02, 3 * update_rel_err(w32, wr, w0)), ("D", i, update_rel_err(w, wr, w0), update_rel_err(w32, wr, w0))
-    for i, (w, wr, w0, w32) in enumerate(zip(got['g'], ref['g'], case.g0, r32['g'])):
-        assert update_rel_err(w, wr, w0) < max(0.02, 3 * update_rel_err(w32, wr, w0)), ("G", i, update_rel_err(w, wr, w0), update_rel_err(w32, wr, w0))
-    # logits of fresh rows after the three updates.  north_star's 1e-3 holds wherever plain float32 arithmetic allows it:
-    # the restatement evaluated in float32 on the same inputs deviates from its fp64 run by e32 (rounding differences of
-    # near-zero gradients pass through Adam's m / (sqrt(v) + eps); tests/test_oracle.py shows e32 > 1e-3 at (800, 256)),
-    # so the engine is bounded by max(1e-3, 2 * e32)
-    e32 = rel_err(r32['logits'], ref['logits'])
-    assert rel_err(got['logits'], ref['logits']) < max(1e-3, 2.0 * e32), (rel_err(got['logits'], ref['logits']), e32)
-    assert eng.get_iterations() == 2 * case.steps
-    eng.close()
+    P.fp32_steps_match_oracle(P.DEFAULT, D, B)
 
 
 def test_fp32_gradients_match_oracle():
-    """Flat-gradient mode exposes the raw gradients of one D step and one G step."""
-    from mr_gan_amd import engine as E
-    case = Case(D=48, B=50, steps=1)
-    orc = O.MRGANOracle(case.g0, case.d0)
-    (ll, lu, err), gd, _ = orc.disc_grads(**case.disc_inputs(0, 0))
-    eng = _engine(48, 50, 0, flags=E.FLAG_FLAT_GRADS | E.FLAG_SYNC_STATS)
-    _load(eng, case)
-    da = E.Engine.disc_args(_t(case.x_lab[0]), _t(case.labels[0], torch.int32), _t(case.x_unl[0]), _t(case.z1[0]))
-    eng.disc_step(da, E.D_GEN, E.D_MAIN, want_outputs=False)
-    got = eng.get_slot(E.NET_D, 2)
-    for i, (a, b) in enumerate(zip(got, gd)):
-        assert rel_err(a, b) < 2e-5, ("dD", i)          # measured ~5e-7 (scripts/parity_probe.py)
-    out = eng.disc_step(da, E.D_ADAM, E.D_ADAM)
-    np.testing.assert_allclose(out, (ll, lu, err), rtol=2e-4, atol=2e-5)
-    orc.adam.apply(orc.d, gd, 'd')
-    loss, gg, _ = orc.gen_grads(**case.gen_inputs(0, 1))
-    ga = E.Engine.gen_args(_t(case.x_unl2[0]), _t(case.z2[0]))
-    eng.gen_step(ga, E.G_GEN, E.G_TAIL, want_outputs=False)
-    got = eng.get_slot(E.NET_G, 2)
-    for i, (a, b) in enumerate(zip(got, gg)):
-        assert rel_err(a, b) < 2e-4, ("dG", i)          # measured ~1e-5 on db1 (cancellation), ~1e-6 elsewhere
-    assert abs(eng.gen_step(ga, E.G_ADAM, E.G_ADAM) - loss) < 2e-3 * abs(loss) + 1e-9
-    eng.close()
+    P.fp32_gradients_match_oracle(P.DEFAULT, 48, 50)
 
 
 @pytest.mark.parametrize("dtype,D,B,short", [(0, 48, 20, 0), (0, 400, 20, 7), (1, 400, 20, 0), (1, 72, 50, 33)])
 def test_supervised_steps_match_oracle(dtype, D, B, short):
-    """mrgan_sup_step = one train_on_batch of the NN baseline (mr_nn.py:101-118).  fp32 against the fp64 restatement, bf16
-    against the bf16 mirror (tolerance rule of test_bf16_steps_match_bf16_mirror); `short` = Keras' short last batch."""
-    from mr_gan_amd import engine as E
-    case = Case(D=D, B=B, steps=3)
-    kw = dict(lr=O.NN_ADAM_LR, b1=O.NN_ADAM_B1)
-    ref = O.MRGANOracle(case.g0, case.d0, **kw)
-    mir = O.MRGANMirror(case.g0, case.d0, quantize='bf16' if dtype else None, **kw)
-    cfg = E.default_config(D, B)
-    cfg.dtype, cfg.seed, cfg.lr, cfg.beta1 = dtype, SEED, O.NN_ADAM_LR, O.NN_ADAM_B1
-    eng = E.Engine(cfg, DEV)
-    _load(eng, case)
-    for t in range(case.steps):
-        n = short if (short and t == 1) else B
-        x, y = case.x_lab[t].astype(np.float64), case.labels[t]
-        noise = [m[:n] for m in noise_set(SEED, 0, t, B, D)]
-        yb = y.copy()
-        yb[n:] = -1
-        got = eng.sup_step(E.Engine.sup_args(_t(case.x_lab[t]), _t(yb, torch.int32), rows_valid=0 if n == B else n))
-        want, wm = ref.sup_step(x[:n], y[:n], noise), mir.sup_step(x[:n], y[:n], noise)
-        slack = 0.0 if t == 0 else 0.25
-        if dtype == 0:
-            assert abs(got[0] - want[0]) < (2e-4 + slack * 0.02) * want[0], (t, got, want)
-        else:
-            assert abs(got[0] - wm[0]) < max(3e-3, 0.6 * abs(wm[0] - want[0]) / want[0] + slack * 0.2) * want[0], (t, got, wm, want)
-        assert abs(got[1] - (want[1] if dtype == 0 else wm[1])) <= (1e-6 if t == 0 else 2.01 / n)
-    w = eng.get_weights(E.NET_D)
-    for i, (a, b, m, w0) in enumerate(zip(w, ref.d, mir.d, case.d0)):
-        if dtype == 0:
-            assert update_rel_err(a, b, w0) < 0.03, ("D", i, update_rel_err(a, b, w0))
-        else:
-            assert update_rel_err(a, m, w0) < max(0.05, 0.85 * update_rel_err(m, b, w0)), ("D", i, update_rel_err(a, m, w0), update_rel_err(m, b, w0))
-    assert eng.get_iterations() == case.steps
-    eng.close()
+    P.supervised_steps_match_oracle(P.DEFAULT, dtype, D, B, short)
 
 
 def test_nn_baseline_fit_learns_planted_structure():
@@ -281,11 +155,11 @@ def test_dataset_contact_mic_modalities_on_the_gpu(tmp_path):
     """dataset() (mr_gan.py:23-71) with its default front end: the log-mel blocks of modalities 3 .. 6 come from ONE mrgan_logmel
     launch over all trials and match the rows built with the numpy restatement (tests/test_dataset.py) within 0.02 dB"""
     from mr_gan_amd import dataset
-    from tests.test_dataset import _oracle_logmel, _write_fake_mreo
-    _write_fake_mreo(str(tmp_path))
+    from tests.helpers import oracle_logmel, write_fake_mreo
+    write_fake_mreo(str(tmp_path))
     for mod, off in ((3, 0), (5, 1200)):
         X, y = dataset(modalities=mod, data_dir=str(tmp_path))
-        Xo, yo = dataset(modalities=mod, data_dir=str(tmp_path), logmel_fn=_oracle_logmel)
+        Xo, yo = dataset(modalities=mod, data_dir=str(tmp_path), logmel_fn=oracle_logmel)
         assert X.shape == Xo.shape and np.array_equal(y, yo)
         np.testing.assert_array_equal(X[:, :off], Xo[:, :off])
         assert np.abs(X[:, off:] - Xo[:, off:]).max() < 0.02
@@ -379,73 +253,6 @@ def test_bf16_steps_match_bf16_mirror():
     eng.close()
 
 
-def _grad_parity(D, B, dtype, quantize, tol, tol_loss, d_hidden=None, g_hidden=None, eval_first=True, frac=0.6, loose=(0.995, 0.98, 0.25)):
-    """One D sub-step and one G sub-step in flat-gradient mode: all 20 gradient tensors and the four losses.
-
-    fp32 engine (quantize None): against the fp64 restatement at `tol`.
-    bf16 engine: against the oracle MIRROR, which rounds to bf16 exactly where the engine stores bf16.  What is left
-    between engine and mirror is fp32-vs-fp64 accumulation: a pre-activation is a sum of K signed terms, so its fp32 error
-    relative to its own size is ~sqrt(K) * 1e-7 ~ 1e-5 .. 1e-4, which flips the bf16 rounding of a few per cent of the stored
-    activations by one ulp (2^-8); ten chained layers and the cancellation in the bias gradients bring that to 1e-3 .. 2e-2
-    on the gradients (measured: scripts/parity_probe.py).  A wrong kernel shows up as an error against the mirror as
-    large as the error against the fp64 oracle, so the bound is: err(engine, mirror) < max(tol, frac * err(mirror, fp64)), frac = 0.6
-    -- the mirror must explain most of what bf16 does -- and, labelled loose, the direction against fp64."""
-    from mr_gan_amd import engine as E
-    kw = {}
-    if d_hidden:
-        kw = dict(d_hidden=d_hidden, g_hidden=g_hidden)
-    case = Case(D=D, B=B, steps=1, **kw)
-    mir = O.MRGANMirror(case.g0, case.d0, quantize=quantize)
-    orc = O.MRGANOracle(case.g0, case.d0)
-    (ll, lu, err), gd_m, _ = mir.disc_grads(**case.disc_inputs(0, 0))
-    (ll_o, lu_o, _), gd_o, _ = orc.disc_grads(**case.disc_inputs(0, 0))
-    eng = _engine(D, B, dtype, flags=E.FLAG_FLAT_GRADS, **kw)
-    _load(eng, case)
-    if eval_first:
-        # an evaluation first: it fills ALL rows of the activation buffers (also the padding rows of a ragged batch),
-        # which the training step afterwards must tolerate
-        rs = np.random.RandomState(5)
-        eng.eval_error(_t(rs.randn(3 * 128 + 7, D).astype(np.float32)), _t(rs.randint(0, 6, size=3 * 128 + 7), torch.int32))
-    da = E.Engine.disc_args(_t(case.x_lab[0]), _t(case.labels[0], torch.int32), _t(case.x_unl[0]), _t(case.z1[0]))
-    eng.disc_step(da, E.D_GEN, E.D_MAIN, want_outputs=False)
-    report = []
-
-    def check(name, got, want_m, want_o, cos_min):
-        for i, (a, m, o) in enumerate(zip(got, want_m, want_o)):
-            em, eo, emo = frob_rel_err(a, m), frob_rel_err(a, o), frob_rel_err(m, o)
-            report.append("%s%-2d %.1e %.1e %.1e" % (name, i, em, eo, emo))
-            assert em < max(tol, frac * emo), (name + " vs mirror", i, em, emo)
-            if quantize:      # loose, vs fp64: ten chained contractions on bf16 operands keep the gradient's direction
-                assert cosine(a, o) > cos_min and eo < loose[2], (name + " vs fp64", i, cosine(a, o), eo)
-
-    check("dD", eng.get_slot(E.NET_D, 2), gd_m, gd_o, loose[0])
-    out = eng.disc_step(da, E.D_ADAM, E.D_ADAM)
-    # losses: the same rule as the gradients -- within tol_loss of the mirror, or within `frac` of what the storage format itself
-    # does to the loss (mirror vs fp64), whichever is larger (reductions of length 4096 in fp8: 2.0e-3 against a mirror that is
-    # itself 1 % from fp64)
-    for got_l, m_l, o_l in zip(out[:2], (ll, lu), (ll_o, lu_o)):
-        np.testing.assert_allclose(got_l, m_l, rtol=max(tol_loss, frac * abs(m_l - o_l) / max(abs(o_l), 1e-12)), atol=tol_loss * 0.1)
-    assert abs(out[2] - err) <= ((4.01 if quantize == 'fp8' else 1.01) / B if quantize else 1e-6)      # an argmax or two may flip
-    # the G sub-step sees the D network AFTER its update: give engine, mirror and oracle the same updated weights
-    mir.adam.apply(mir.d, gd_m, 'd')
-    if quantize == 'fp8':           # mrgan_set_weights below re-measures the fp8 weight copies in two passes; so does the mirror
-        for _ in range(2):
-            mir._refresh_w8()
-            mir.slots.update()
-    orc.d = [p.copy() for p in mir.d]
-    orc.adam.iterations = 1
-    eng.set_weights(E.NET_D, [p.astype(np.float32) for p in mir.d])
-    loss, gg_m, _ = mir.gen_grads(**case.gen_inputs(0, 1))
-    _, gg_o, _ = orc.gen_grads(**case.gen_inputs(0, 1))
-    ga = E.Engine.gen_args(_t(case.x_unl2[0]), _t(case.z2[0]))
-    eng.gen_step(ga, E.G_GEN, E.G_TAIL, want_outputs=False)
-    check("dG", eng.get_slot(E.NET_G, 2), gg_m, gg_o, loose[1])
-    lg = eng.gen_step(ga, E.G_ADAM, E.G_ADAM)
-    assert abs(lg - loss) < 5 * tol_loss * abs(loss) + 1e-12, (lg, loss)
-    eng.close()
-    print("\n(D=%d, B=%d) tensor: err vs mirror | vs fp64 | mirror vs fp64\n  " % (D, B) + "\n  ".join(report))
-
-
 @pytest.mark.parametrize("D,B", [(400, 50),       # the reference's ragged batch: the weight gradients reduce over the padding rows too
                                  (400, 256),      # reference-sized input, several row tiles
                                  (3632, 512),     # SURVEY 8d config 3: all three modalities fused, one rank's shard of batch 4096
@@ -454,91 +261,17 @@ def _grad_parity(D, B, dtype, quantize, tol, tol_loss, d_hidden=None, g_hidden=N
                                  (400, 1024),     # config 4: temperature only
                                  (512, 4096)])    # config 2: the bench workload at full size
 def test_bf16_gradients_match_bf16_mirror(D, B):
-    _grad_parity(D, B, 1, 'bf16', tol=3e-3, tol_loss=5e-4)
+    P.grad_parity(P.DEFAULT, D, B, 1, 'bf16', tol=3e-3, tol_loss=5e-4)
 
 
 @pytest.mark.parametrize("D,B", [(400, 256), (96, 50), (512, 1024)])
 def test_chain_launches_equal_per_layer_launches(D, B):
-    """The 256-wide tail D3..D5 + loss head (+ its dX chain) as row-block chain launches (gemm_chain.hip) against the same
-    products launched layer by layer (B = 50: a ragged, partly empty row block).
-    * Every dense product has the identical MFMA accumulation order and epilogue arithmetic in both forms: the stored layer
-      inputs xin[l] and the features are BIT-IDENTICAL, and so is the whole G sub-step (no loss head in it) when both engines
-      start it from the same discriminator weights.
-    * The loss head inside the chain runs on the matrix cores (three-addend bf16 splits of the fp32 factors: exact products,
-      fp32 accumulation), head_kernel of the per-layer path is an fmaf chain: the same fp32 arithmetic in another summation
-      order.  The losses agree to 1e-6; dlogits differ by ~1e-7 relative, which flips the bf16 rounding of a few stored
-      dL/d(pre) values by one ulp (measured at (400, 256): 19 of 768 rows hold such an element) -- the gradients therefore agree
-      to ~1e-4 of their largest element instead of bit for bit."""
-    from mr_gan_amd import engine as E
-    case = Case(D=D, B=B, steps=1, device_z=True)
-    res, engines = [], []
-    for chain in (1, 0):
-        eng = _engine(D, B, 1, flags=E.FLAG_FLAT_GRADS)
-        eng.set_tuning(E.TUNE_CHAIN, chain)
-        _load(eng, case)
-        da = E.Engine.disc_args(_t(case.x_lab[0]), _t(case.labels[0], torch.int32), _t(case.x_unl[0]))
-        eng.disc_step(da, E.D_GEN, E.D_MAIN, want_outputs=False)
-        gd = eng.get_slot(E.NET_D, 2)
-        acts = [eng.debug_buffer(0, l).cpu().numpy()[:, :B] for l in range(5)] + [eng.debug_buffer(2, 0).cpu().numpy()[:, :B]]
-        dpre = [eng.debug_buffer(1, l).cpu().numpy()[:, :B] for l in range(5)]
-        out = eng.disc_step(da, E.D_ADAM, E.D_ADAM)
-        res.append((gd, out, acts, dpre))
-        engines.append(eng)
-    (gd1, out1, acts1, dpre1), (gd0, out0, acts0, dpre0) = res
-    np.testing.assert_allclose(out1, out0, rtol=1e-6, atol=1e-7)
-    for l, (a, b) in enumerate(zip(acts1, acts0)):
-        np.testing.assert_array_equal(a, b, err_msg="layer input / features %d" % l)
-    for l, (a, b) in enumerate(zip(dpre1, dpre0)):
-        d = np.abs(a - b)
-        assert d.max() <= 2.0 ** -7 * np.abs(b).max() and (d.max(axis=2) > 0).mean() < 0.05, ("dpre", l, d.max(), (d.max(axis=2) > 0).mean())
-    for i, (a, b) in enumerate(zip(gd1, gd0)):
-        assert rel_err(a, b) < 5e-4, ("dD", i, rel_err(a, b))
-    # the G sub-step from identical discriminator weights (Adam turns rounding-level gradient differences into +-lr steps)
-    wd = engines[0].get_weights(E.NET_D)
-    gres = []
-    for eng in engines:
-        eng.set_weights(E.NET_D, wd)
-        ga = E.Engine.gen_args(_t(case.x_unl2[0]))
-        eng.gen_step(ga, E.G_GEN, E.G_TAIL, want_outputs=False)
-        gg = eng.get_slot(E.NET_G, 2)
-        gres.append((gg, eng.gen_step(ga, E.G_ADAM, E.G_ADAM)))
-        eng.close()
-    (gg1, lg1), (gg0, lg0) = gres
-    assert abs(lg1 - lg0) <= 1e-6 * abs(lg0)
-    for i, (a, b) in enumerate(zip(gg1, gg0)):
-        assert rel_err(a, b) < 2e-5, ("dG", i, rel_err(a, b))
+    P.chain_launches_equal_per_layer_launches(P.DEFAULT, D, B)
 
 
 @pytest.mark.parametrize("dtype,B", [(1, 200), (2, 256)])
 def test_matrix_core_loss_head_equals_scalar_head(dtype, B):
-    """Feature layers wider than the chain holds (here 512 columns = two chunks; BASELINE configs[4]: 4096) run the loss head of
-    the D sub-step as the stand-alone MFMA kernel over 64-row blocks (gemm_chain.hip: head_wide_kernel; TUNE_HEAD_MFMA = 1, the
-    default) instead of head_kernel's fmaf loops over 32-row blocks.  Same rule as the chain test above: three-addend bf16 splits
-    make every product exact, only the fp32 summation order differs -- losses to 1e-6, the bf16 dL/d(pre5) within one ulp on a few
-    rows (fp8 mode: the e5m2 copies are what leaves the kernel; compared through the weight gradients), D gradients to 5e-4.
-    B = 200: a ragged last row block (8 valid rows); dtype 2: the fp8 engine (e5m2 row-major + transposed copies, amax slot)."""
-    from mr_gan_amd import engine as E
-    D, hid = 96, (256, 256, 256, 512, 512)
-    case = Case(D=D, B=B, steps=1, device_z=True, d_hidden=hid)
-    res = []
-    for mfma in (1, 0):
-        eng = _engine(D, B, dtype, flags=E.FLAG_FLAT_GRADS, d_hidden=hid)
-        eng.set_tuning(E.TUNE_HEAD_MFMA, mfma)
-        _load(eng, case)
-        da = E.Engine.disc_args(_t(case.x_lab[0]), _t(case.labels[0], torch.int32), _t(case.x_unl[0]))
-        eng.disc_step(da, E.D_GEN, E.D_MAIN, want_outputs=False)
-        gd = eng.get_slot(E.NET_D, 2)
-        dpre = eng.debug_buffer(1, 4).cpu().numpy()[:, :B] if dtype == 1 else None
-        out = eng.disc_step(da, E.D_ADAM, E.D_ADAM)
-        res.append((gd, out, dpre))
-        eng.close()
-    (gd1, out1, dp1), (gd0, out0, dp0) = res
-    np.testing.assert_allclose(out1, out0, rtol=1e-6, atol=1e-7)
-    if dtype == 1:
-        d = np.abs(dp1 - dp0)
-        assert d.max() <= 2.0 ** -7 * np.abs(dp0).max() and (d.max(axis=2) > 0).mean() < 0.05, (d.max(), (d.max(axis=2) > 0).mean())
-    for i, (a, b) in enumerate(zip(gd1, gd0)):
-        assert rel_err(a, b) < (5e-4 if dtype == 1 else 5e-3), ("dD", i, rel_err(a, b))
+    P.matrix_core_loss_head_equals_scalar_head(P.DEFAULT, dtype, B)
 
 
 @pytest.mark.parametrize("D,B", [(2432, 1024), (400, 50)])
@@ -553,11 +286,11 @@ def test_substeps_are_bit_reproducible(D, B):
     for rep in range(3):
         eng = _engine(D, B, 1, flags=E.FLAG_FLAT_GRADS)
         _load(eng, case)
-        da = E.Engine.disc_args(_t(case.x_lab[0]), _t(case.labels[0], torch.int32), _t(case.x_unl[0]))
+        da = P.disc_args(case, 0, device_z=True)
         eng.disc_step(da, E.D_GEN, E.D_MAIN, want_outputs=False)
         cur = eng.get_slot(E.NET_D, 2)
         eng.disc_step(da, E.D_ADAM, E.D_ADAM)
-        ga = E.Engine.gen_args(_t(case.x_unl2[0]))
+        ga = P.gen_args(case, 0, device_z=True)
         eng.gen_step(ga, E.G_GEN, E.G_TAIL, want_outputs=False)
         cur += eng.get_slot(E.NET_G, 2)
         cur += [eng.debug_buffer(0, l, 2).cpu().numpy() for l in range(5)] + [eng.debug_buffer(1, l, 1).cpu().numpy() for l in range(5)]
@@ -575,10 +308,10 @@ def test_narrow_stack_bf16_matches_bf16_mirror():
     these stacks must take the per-layer launches (engine.hip: chain_ok) -- and the 64 x 64 tile path with ragged widths."""
     # (the loose direction bound against fp64 is wider than at the reference widths: with 64-column layers one bf16 ulp of an
     #  activation is a larger share of the gradient -- the mirror moves from fp64 by the same amount, and the mirror bound holds)
-    _grad_parity(72, 132, 1, 'bf16', tol=3e-3, tol_loss=5e-4, d_hidden=(200, 100, 64, 100, 64), g_hidden=(64, 100), eval_first=False,
+    P.grad_parity(P.DEFAULT, 72, 132, 1, 'bf16', tol=3e-3, tol_loss=5e-4, d_hidden=(200, 100, 64, 100, 64), g_hidden=(64, 100), eval_first=False,
                  loose=(0.98, 0.95, 0.3))
     # 128-column tail: the shortest reductions the chain accepts (exactly two k-tiles per product, D3 .. D5 and their dX products)
-    _grad_parity(72, 132, 1, 'bf16', tol=3e-3, tol_loss=5e-4, d_hidden=(200, 128, 128, 128, 128), g_hidden=(128, 128), eval_first=False,
+    P.grad_parity(P.DEFAULT, 72, 132, 1, 'bf16', tol=3e-3, tol_loss=5e-4, d_hidden=(200, 128, 128, 128, 128), g_hidden=(128, 128), eval_first=False,
                  loose=(0.98, 0.95, 0.3))
 
 
@@ -586,7 +319,7 @@ def test_wide_stack_bf16_matches_bf16_mirror():
     """BASELINE configs[4] geometry at one rank's share: hidden 4096 x 5 (generator 4096 x 2), D = 512, B = 8192 / 8 = 1024.
     The layer widths are literals in the reference (mr_gan.py:111-128); mrgan_config generalises them."""
     # (reductions of length 4096: the fp32 accumulation error, hence the residual against the mirror, is larger: frac 0.85)
-    _grad_parity(512, 1024, 1, 'bf16', tol=3e-3, tol_loss=5e-4, d_hidden=(4096,) * 5, g_hidden=(4096,) * 2, eval_first=False, frac=0.85)
+    P.grad_parity(P.DEFAULT, 512, 1024, 1, 'bf16', tol=3e-3, tol_loss=5e-4, d_hidden=(4096,) * 5, g_hidden=(4096,) * 2, eval_first=False, frac=0.85)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -606,14 +339,14 @@ def test_fp8_gradients_match_fp8_mirror(D, B, hidden):
     of what fp8 itself does to the gradients (measured ~0.25: scripts/parity_probe.py D B 2).  Loose bounds against fp64 say
     what fp8 costs: gradient direction cosine > 0.9."""
     kw = dict(d_hidden=(hidden,) * 5, g_hidden=(hidden,) * 2) if hidden else {}
-    _grad_parity(D, B, 2, 'fp8', tol=5e-3, tol_loss=2e-3, eval_first=hidden is None, frac=0.6 if hidden is None else 0.85,
+    P.grad_parity(P.DEFAULT, D, B, 2, 'fp8', tol=5e-3, tol_loss=2e-3, eval_first=hidden is None, frac=0.6 if hidden is None else 0.85,
                  loose=(0.9, 0.8, 0.6), **kw)
 
 
 def test_fp8_split_weight_gradient_of_a_narrow_first_layer():
     """a first layer with few output tiles (512 x 2048) splits its fp8 weight-gradient product over the batch rows into two
     fp32 slabs (engine.hip fp8_dw_splits); the other layers take the unsplit path"""
-    _grad_parity(512, 2048, 2, 'fp8', tol=5e-3, tol_loss=2e-3, eval_first=False, frac=0.7, loose=(0.9, 0.8, 0.6),
+    P.grad_parity(P.DEFAULT, 512, 2048, 2, 'fp8', tol=5e-3, tol_loss=2e-3, eval_first=False, frac=0.7, loose=(0.9, 0.8, 0.6),
                  d_hidden=(2048, 256, 256, 256, 256), g_hidden=(500, 500))
 
 
@@ -656,11 +389,11 @@ def test_fp8_large_tiles_equal_small_tiles():
         eng = _engine(512, 1024, 2, flags=E.FLAG_FLAT_GRADS, d_hidden=(1024,) * 5, g_hidden=(512, 512))
         eng.set_tuning(E.TUNE_KC_CFG, cfg)
         _load(eng, case)
-        da = E.Engine.disc_args(_t(case.x_lab[0]), _t(case.labels[0], torch.int32), _t(case.x_unl[0]))
+        da = P.disc_args(case, 0, device_z=True)
         eng.disc_step(da, E.D_GEN, E.D_MAIN, want_outputs=False)
         gd = eng.get_slot(E.NET_D, 2)
         out = eng.disc_step(da, E.D_ADAM, E.D_ADAM)
-        ga = E.Engine.gen_args(_t(case.x_unl2[0]))
+        ga = P.gen_args(case, 0, device_z=True)
         eng.gen_step(ga, E.G_GEN, E.G_TAIL, want_outputs=False)
         res.append((gd, out, eng.get_slot(E.NET_G, 2)))
         eng.close()
@@ -687,14 +420,14 @@ def test_forced_kc_tiles_equal_the_measured_table():
         eng = _engine(512, 1024, 1, flags=E.FLAG_FLAT_GRADS)
         eng.set_tuning(E.TUNE_KC_CFG, cfg)
         _load(eng, case)
-        da = E.Engine.disc_args(_t(case.x_lab[0]), _t(case.labels[0], torch.int32), _t(case.x_unl[0]))
+        da = P.disc_args(case, 0, device_z=True)
         eng.disc_step(da, E.D_GEN, E.D_MAIN, want_outputs=False)
         gd = eng.get_slot(E.NET_D, 2)
         out = eng.disc_step(da, E.D_ADAM, E.D_ADAM)
         if wd is None:
             wd = eng.get_weights(E.NET_D)
         eng.set_weights(E.NET_D, wd)
-        ga = E.Engine.gen_args(_t(case.x_unl2[0]))
+        ga = P.gen_args(case, 0, device_z=True)
         eng.gen_step(ga, E.G_GEN, E.G_TAIL, want_outputs=False)
         gg = eng.get_slot(E.NET_G, 2)
         res.append((cfg, gd, out, gg, eng.gen_step(ga, E.G_ADAM, E.G_ADAM)))
@@ -727,56 +460,14 @@ def test_forced_kc_tiles_equal_the_measured_table():
 
 def test_wide_stack_fp32_matches_oracle():
     """the same wide geometry through the fp32 MFMA path at a small batch, against the fp64 restatement"""
-    _grad_parity(64, 64, 0, None, tol=5e-5, tol_loss=1e-5, d_hidden=(1024, 512, 512, 320, 320), g_hidden=(320, 576), eval_first=False)
+    P.grad_parity(P.DEFAULT, 64, 64, 0, None, tol=5e-5, tol_loss=1e-5, d_hidden=(1024, 512, 512, 320, 320), g_hidden=(320, 576), eval_first=False)
 
 
 # ---------------------------------------------------------------------------------------------------------
 # data parallelism, emulated on one GPU: two rank handles whose "all-reduce" is a host-side add
 # ---------------------------------------------------------------------------------------------------------
 def test_two_rank_emulation_equals_full_batch():
-    from mr_gan_amd import engine as E
-    B, D = 64, 32
-    case = Case(D=D, B=B, steps=2, device_z=True)
-    ref = case.run_oracle()
-    flags = E.FLAG_FLAT_GRADS | E.FLAG_SYNC_STATS
-    ranks = [_engine(D, B // 2, 0, flags=flags, rank=r, world=2) for r in range(2)]
-    for e in ranks:
-        _load(e, case)
-
-    def allreduce(region):
-        views = [e.region(region) for e in ranks]
-        tot = views[0] + views[1]
-        for v in views:
-            v.copy_(tot)
-
-    h = B // 2
-    for t in range(case.steps):
-        da = [E.Engine.disc_args(_t(case.x_lab[t][r * h:(r + 1) * h]), _t(case.labels[t][r * h:(r + 1) * h], torch.int32),
-                                 _t(case.x_unl[t][r * h:(r + 1) * h])) for r in range(2)]
-        for e, a in zip(ranks, da):
-            e.disc_step(a, E.D_GEN, E.D_GEN, want_outputs=False)
-        allreduce(E.REGION_BN_STATS)
-        for e, a in zip(ranks, da):
-            e.disc_step(a, E.D_MAIN, E.D_MAIN, want_outputs=False)
-        allreduce(E.REGION_GRAD_D)
-        outs = [e.disc_step(a, E.D_ADAM, E.D_ADAM) for e, a in zip(ranks, da)]
-        np.testing.assert_allclose(outs[0], ref['disc'][t], rtol=3e-4, atol=3e-5)
-        np.testing.assert_allclose(outs[1], outs[0], rtol=0, atol=0)
-        ga = [E.Engine.gen_args(_t(case.x_unl2[t][r * h:(r + 1) * h])) for r in range(2)]
-        for ph, reg in ((E.G_GEN, E.REGION_BN_STATS), (E.G_FEAT, E.REGION_FM_MOMENTS), (E.G_BWD, E.REGION_BN_BWD),
-                        (E.G_TAIL, E.REGION_GRAD_G)):
-            for e, a in zip(ranks, ga):
-                e.gen_step(a, ph, ph, want_outputs=False)
-            allreduce(reg)
-        outs = [e.gen_step(a, E.G_ADAM, E.G_ADAM) for e, a in zip(ranks, ga)]
-        np.testing.assert_allclose(outs[0], ref['gen'][t], rtol=3e-3, atol=1e-9)
-    w0, w1 = ranks[0].get_weights(E.NET_D), ranks[1].get_weights(E.NET_D)
-    for a, b in zip(w0, w1):
-        np.testing.assert_array_equal(a, b)                    # replicas stay bit-identical
-    for i, (w, wr, wi) in enumerate(zip(w0, ref['d'], case.d0)):
-        assert update_rel_err(w, wr, wi) < 0.05, ("D", i)
-    for e in ranks:
-        e.close()
+    P.two_rank_emulation_equals_full_batch(P.DEFAULT)
 
 
 def test_two_rank_emulation_with_bf16_gradient_payload():
@@ -803,25 +494,11 @@ def test_two_rank_emulation_with_bf16_gradient_payload():
             for v in views:
                 v.copy_(tot)
 
-    h = B // 2
     for t in range(case.steps):
-        da = [E.Engine.disc_args(_t(case.x_lab[t][r * h:(r + 1) * h]), _t(case.labels[t][r * h:(r + 1) * h], torch.int32),
-                                 _t(case.x_unl[t][r * h:(r + 1) * h])) for r in range(2)]
-        for ph, reg in ((E.D_GEN, E.REGION_BN_STATS), (E.D_MAIN, E.REGION_GRAD_D)):
-            for e, a in zip(ranks, da):
-                e.disc_step(a, ph, ph, want_outputs=False)
-            allreduce(reg)
-        outs = [e.disc_step(a, E.D_ADAM, E.D_ADAM) for e, a in zip(ranks, da)]
+        d_out, _ = P.phase_walk(ranks, *P.rank_args(case, t), allreduce=allreduce)
         if t == 0:
-            np.testing.assert_allclose(outs[0], ref['disc'][t], rtol=3e-4, atol=3e-5)
-        np.testing.assert_allclose(outs[1], outs[0], rtol=0, atol=0)
-        ga = [E.Engine.gen_args(_t(case.x_unl2[t][r * h:(r + 1) * h])) for r in range(2)]
-        for ph, reg in ((E.G_GEN, E.REGION_BN_STATS), (E.G_FEAT, E.REGION_FM_MOMENTS), (E.G_BWD, E.REGION_BN_BWD), (E.G_TAIL, E.REGION_GRAD_G)):
-            for e, a in zip(ranks, ga):
-                e.gen_step(a, ph, ph, want_outputs=False)
-            allreduce(reg)
-        for e, a in zip(ranks, ga):
-            e.gen_step(a, E.G_ADAM, E.G_ADAM)
+            np.testing.assert_allclose(d_out[0], ref['disc'][t], rtol=3e-4, atol=3e-5)
+        np.testing.assert_allclose(d_out[1], d_out[0], rtol=0, atol=0)
     w0, w1 = ranks[0].get_weights(E.NET_D), ranks[1].get_weights(E.NET_D)
     for a, b in zip(w0 + ranks[0].get_weights(E.NET_G), w1 + ranks[1].get_weights(E.NET_G)):
         np.testing.assert_array_equal(a, b)                    # replicas stay bit-identical
@@ -846,14 +523,14 @@ def test_fp8_phase_protocol_equals_whole_steps(exact):
         probe = _engine(D, B, 2, flags=dp_flags(exact=True))
         _load(probe, case)
         with pytest.raises(E.MrganError, match="calibration"):
-            probe.disc_step(E.Engine.disc_args(_t(case.x_lab[0]), _t(case.labels[0], torch.int32), _t(case.x_unl[0])), E.D_GEN, E.D_GEN, want_outputs=False)
+            probe.disc_step(P.disc_args(case, 0, device_z=True), E.D_GEN, E.D_GEN, want_outputs=False)
         probe.close()
     for e in (plain, phased):
         _load(e, case)
     dp = DataParallel(EngineBackend(phased), exact=exact)
     for t in range(case.steps):
-        da = E.Engine.disc_args(_t(case.x_lab[t]), _t(case.labels[t], torch.int32), _t(case.x_unl[t]))
-        ga = E.Engine.gen_args(_t(case.x_unl2[t]))
+        da = P.disc_args(case, t, device_z=True)
+        ga = P.gen_args(case, t, device_z=True)
         plain.disc_step(da, want_outputs=False)
         plain.gen_step(ga, want_outputs=False)
         dp.disc_step(da)
@@ -1141,8 +818,8 @@ def _dp_worker(rank, world, port, exact, q):
     dp = DataParallel(EngineBackend(eng), exact=exact)
     sl = slice(rank * h, (rank + 1) * h)
     for t in range(steps):
-        dp.train_pair(E.Engine.disc_args(_t(case.x_lab[t][sl]), _t(case.labels[t][sl], torch.int32), _t(case.x_unl[t][sl])),
-                      E.Engine.gen_args(_t(case.x_unl2[t][sl])))
+        dp.train_pair(P.disc_args(case, t, True, sl),
+                      P.gen_args(case, t, True, sl))
     torch.cuda.synchronize()
     q.put((rank, eng.get_weights(E.NET_D), eng.get_weights(E.NET_G)))
     dist.barrier()

@@ -215,7 +215,7 @@ def test_bf16_mirror_stays_close_to_fp64_oracle():
 
 
 def test_fp32_arithmetic_alone_moves_post_adam_logits_by_more_than_1e3():
-    """Why tests/test_gpu_parity.py does not hold post-update logits to north_star's 1e-3 at (D, B) = (800, 256): the
+    """Why tests/parity.py (fp32_steps_match_oracle) does not hold post-update logits to north_star's 1e-3 at (D, B) = (800, 256): the
     restatement itself, evaluated in float32 instead of float64 on identical inputs, differs from its own fp64 run by
     MORE than that after three Adam updates (early Adam moves a weight by ~lr * sign(g), so a gradient element at
     rounding level may step the other way), while logits BEFORE any update agree to ~1e-6.  The GPU test therefore bounds
