@@ -64,9 +64,16 @@ void prof_done(mrgan_handle* h, const char* name, double flops, double bytes = 0
 // algo_flops / algo_bytes: the ALGORITHMIC work of the product: logical, unpadded shapes, 2 FLOP per MAC,
 // operands read once + outputs written once -- no padding, no split-K slabs, no re-reads
 int run_gemm(mrgan_handle* h, int epi, const GemmArgs& g, double algo_flops, double algo_bytes, hipStream_t s) {
-    const char* kname = "gemm";
+    const Epi& e = g.e;
+    const bool fp8 = e.qa != nullptr;                 // the description carries fp8 operands
+    const char* kname = fp8 ? "gemm_fp8" : "gemm";
     prof_arm(h);
-    const int r = h->bf16 ? launch_gemm_bf16(epi, g, s, &kname) : launch_gemm_f32(epi, g, s, &kname);
+    const int r = fp8 ? launch_gemm_fp8(epi, g, s, &kname) : h->bf16 ? launch_gemm_bf16(epi, g, s, &kname) : launch_gemm_f32(epi, g, s, &kname);
+    if (fp8) {
+        // operands are bytes; outputs: fp8 (+ transposed copy) or bf16, the weight gradient fp32
+        const double out_b = epi == EPI_SLAB ? 4.0 : (e.out ? 2.0 : 0.0) + (e.q8 ? 1.0 : 0.0) + (e.q8t ? 1.0 : 0.0);
+        algo_bytes = (double)g.nbatch * g.M * g.K + (double)g.K * g.N + (double)g.nbatch * g.M * g.N * out_b;
+    }
     prof_done(h, kname, algo_flops, algo_bytes);
     CHK(r);
     return 0;
@@ -87,94 +94,42 @@ GemmArgs with_handle(mrgan_handle* h, GemmArgs g) {
     e.seg_step = 1;
     return g;
 }
-void epi_mask(mrgan_handle* h, Epi& e, const uint16_t* mask, int ldm) {
-    e.mask = (uint16_t*)mask; e.mask_bs = mask_pitch(h->S, ldm); e.ldm = ldm;
-}
 
-// Y = act(X W + b): X [nb][S][Kp] -> out [nb][S][Np]
-int dense_fwd(mrgan_handle* h, const Dense& L, const void* x, int rows, int nb, void* out, int act, float sigma, uint32_t site,
-              uint32_t seg0, uint16_t* mask, int ldm, int cs_mode, float* cs1, float* cs2, bool noise_state, hipStream_t s,
-              int seg_step = 1, uint32_t iter_step = 0) {
-    GemmArgs g = with_handle(h, h->bf16 ? gemm_fwd_args(rows, L.Kp, L.Np, nb, x, (long)h->S * L.Kp, L.Kp, L.W->wt16, L.Kp, true)
-                                        : gemm_fwd_args(rows, L.Kp, L.Np, nb, x, (long)h->S * L.Kp, L.Kp, L.W->p, L.Np, false));
-    if (!noise_state) g.e.st = nullptr;
-    g.e.act = act; g.e.n_valid = L.N; g.e.bias = L.b->p;
-    g.e.out = out; g.e.out_bs = (long)h->S * L.Np; g.e.ldo = L.Np;
-    g.e.sigma = sigma; g.e.site = site; g.e.seg0 = seg0; g.e.seg_step = seg_step; g.e.iter_step = iter_step;
-    epi_mask(h, g.e, mask, ldm);
-    g.e.cs_mode = cs_mode; g.e.cs1 = cs1; g.e.cs2 = cs2; g.e.ldcs = L.Np;
-    return run_gemm(h, EPI_FWD, g, 2.0 * rows * nb * L.K * L.N, dense_bytes(h, (double)rows * nb, L), s);
-}
+// ---- what a dense product is told beside its operands ----
+// who runs it: a sub-step kind (which scaling slots a layer's fp8 images use), or the evaluation (learning phase 0: no noise
+// state, and bf16 operands whatever the layer owns)
+enum { KIND_EVAL = -1, KIND_D = 0, KIND_G = 1 };
+// GaussianNoise added to a forward product's output: drawn at (site, seg0 + batch * seg_step, iteration + batch * iter_step)
+struct NoiseSite { float sigma; uint32_t site, seg0; int seg_step; uint32_t iter_step; };
+const NoiseSite NO_NOISE = {0.f, 0, 0, 1, 0};
+struct ReluMask { const uint16_t* words; int ldm; };      // lane-native relu mask: written by a forward product, read by a dX
+const ReluMask NO_MASK = {nullptr, 0};
+struct ColSums { int mode; float* cs1; float* cs2; };     // column partial sums per 64 rows
+const ColSums NO_SUMS = {CS_NONE, nullptr, nullptr};
+// a layer with fp8 images (Fp8Images, engine_internal.h) reads its operand from them; this says how they are filled:
+//   to        the layer whose images take the product's output -- a forward product's next layer (its input images), a dX
+//             product's previous one (its gradient images); the bf16 tensor `out` is not stored then, nothing reads it
+//   wgrad     weight gradients follow in this sub-step: the transposed images are written too
+//   quant_in  the operand is a stored bf16 tensor (xin_0, BN(h1), dpre2 of the generator): a quantiser pass fills the
+//             layer's own images first
+struct Fp8Use { const Dense* to; bool wgrad, quant_in; };
+const Fp8Use NO_FP8 = {nullptr, false, false};
 
-// dX = (dY W^T) * act'(prev): dY [nb][S][Np] -> out [nb][S][Kp]
-int dense_dx(mrgan_handle* h, const Dense& L, const void* dy, int rows, int nb, void* out, int act, int n_valid,
-             const uint16_t* mask, int ldm, const void* hprev, int cs_mode, float* cs1, float* cs2, hipStream_t s) {
-    GemmArgs g = with_handle(h, gemm_dx_args(rows, L.Kp, L.Np, nb, dy, (long)h->S * L.Np, L.Np,
-                                             h->bf16 ? (const void*)L.W->w16 : (const void*)L.W->p, L.Np));
-    g.e.act = act; g.e.n_valid = n_valid;
-    g.e.out = out; g.e.out_bs = (long)h->S * L.Kp; g.e.ldo = L.Kp;
-    epi_mask(h, g.e, mask, ldm);
-    g.e.h = hprev; g.e.h_bs = (long)h->S * L.Kp; g.e.ldh = L.Kp;
-    g.e.cs_mode = cs_mode; g.e.cs1 = cs1; g.e.cs2 = cs2; g.e.ldcs = L.Kp;
-    g.e.bn_mu = h->bn_mu; g.e.bn_rstd = h->bn_rstd;
-    return run_gemm(h, EPI_DX, g, 2.0 * rows * nb * L.K * L.N, dense_bytes(h, (double)rows * nb, L), s);
+ReluMask relu_mask(const mrgan_handle* h, int l) { return ReluMask{h->mask[l], h->ldm[l]}; }
+void epi_mask(mrgan_handle* h, Epi& e, const ReluMask& m) {
+    e.mask = (uint16_t*)m.words; e.mask_bs = mask_pitch(h->S, m.ldm); e.ldm = m.ldm;
 }
-
-// dW slabs = X^T dY.  The nseg segments ([nseg][S] rows, `rows` valid in each) form ONE virtual reduction
-// range that is cut into L.splits slabs, so the Adam kernel sums at most MAX_SLABS slabs per tensor.
-double dw_args(mrgan_handle* h, GemmArgs& g, const Dense& L, const void* x, const void* dy, int rows, int nseg) {
-    // bf16: reduce over ALL S rows of every segment.  The rows >= `rows` of dY are never written by any kernel (they keep
-    // the zeros of mrgan_create) and those of X are finite, so they add exact zeros -- and the reduction range becomes
-    // dense, which is what the LDS-DMA weight-gradient kernel and the grouped launch need (a ragged batch such as the
-    // reference's 50 otherwise fell back to one register-staged launch per product).
-    const bool dense = h->bf16 != 0;
-    const int vrows = dense ? nseg * h->S : (nseg - 1) * h->S + rows;
-    g = with_handle(h, gemm_dw_args(L.Kp, L.Np, vrows, L.splits, gemm_dw_kchunk(vrows, L.splits), h->S, dense ? h->S : rows,
-                                    x, L.Kp, dy, L.Np, false, L.slabs));
-    return 2.0 * rows * nseg * L.K * L.N;
+void epi_sums(Epi& e, const ColSums& cs, int ldcs) { e.cs_mode = cs.mode; e.cs1 = cs.cs1; e.cs2 = cs.cs2; e.ldcs = ldcs; }
+// the product's output goes to fp8 images [nb][S][ld] (+ transposed, pitch ldt) under `slot` instead of the bf16 tensor
+void epi_images(mrgan_handle* h, Epi& e, unsigned char* img, unsigned char* imgt, int ld, int ldt, int slot) {
+    e.out = nullptr;
+    e.qo = h->slots + slot;
+    e.q8 = img; e.q8_bs = (long)h->S * ld; e.ldq8 = ld;
+    if (imgt) { e.q8t = imgt; e.q8t_bs = h->S; e.ldq8t = ldt; }
 }
+unsigned char* x8_view(const mrgan_handle* h, const Dense& L) { return L.q.x8 + (size_t)L.q.xseg * h->S * L.Kp; }
+unsigned char* x8t_view(const mrgan_handle* h, const Dense& L) { return L.q.x8t + (size_t)L.q.xseg * h->S; }
 
-struct DwJob { const Dense* L; const void* x; const void* dy; };
-
-// the weight-gradient products of one sub-step: one grouped launch when the bf16 fast path takes them all,
-// one launch per product otherwise
-int dense_dw_all(mrgan_handle* h, const DwJob* jobs, int n, int rows, int nseg, hipStream_t s, const FoldJob* fold = nullptr) {
-    GemmArgs gs[KS_GROUP_MAX];
-    double fl[KS_GROUP_MAX], total = 0.0;
-    if (n > KS_GROUP_MAX) return fail(-1, "dense_dw_all: too many products");
-    for (int i = 0; i < n; ++i) { fl[i] = dw_args(h, gs[i], *jobs[i].L, jobs[i].x, jobs[i].dy, rows, nseg); total += fl[i]; }
-    if (h->bf16) {
-        const char* kname = "gemm";
-        prof_arm(h);
-        const int r = launch_gemm_bf16_dw_group(gs, n, s, &kname, fold);
-        double bytes = 0.0;
-        for (int i = 0; i < n; ++i) bytes += dw_bytes(h, (double)rows * nseg, *jobs[i].L);
-        prof_done(h, kname, total, bytes);
-        if (r < 0) return fail(r, "grouped weight-gradient launch failed");
-        if (r == 0) return 0;
-    }
-    for (int i = 0; i < n; ++i) CHK(run_gemm(h, EPI_SLAB, gs[i], fl[i], dw_bytes(h, (double)rows * nseg, *jobs[i].L), s));
-    if (fold) PROF("reduce_partials_kernel", launch_reduce_partials(fold->src, fold->nsrc, fold->stride, fold->n, fold->ngroups, fold->dst, s));
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// fp8 mode: the discriminator's dense products on gemm_fp8.hip.  Activations / gradients live as fp8 copies x8[l] / g8[l]
-// ([3][S][width], written by the producing product's epilogue) and, when the sub-step computes weight gradients, their
-// transposes x8t[l] / g8t[l] ([width][3 S]); weights as w8 [K][N] and w8t [N][K], refreshed after the D sub-step's Adam.
-// ---------------------------------------------------------------------------------------------------
-int run_gemm_fp8(mrgan_handle* h, int epi, const GemmArgs& g, double algo_flops, hipStream_t s) {
-    const char* kname = "gemm_fp8";
-    prof_arm(h);
-    const int r = launch_gemm_fp8(epi, g, s, &kname);
-    // operands are bytes; outputs: fp8 (+ transposed copy) or bf16, the weight gradient fp32
-    const Epi& e = g.e;
-    const double out_b = epi == EPI_SLAB ? 4.0 : (e.out ? 2.0 : 0.0) + (e.q8 ? 1.0 : 0.0) + (e.q8t ? 1.0 : 0.0);
-    const double bytes = (double)g.nbatch * g.M * g.K + (double)g.K * g.N + (double)g.nbatch * g.M * g.N * out_b;
-    prof_done(h, kname, algo_flops, bytes);
-    if (r) return fail(r, "fp8 product launch failed (%d)", r);
-    return 0;
-}
 int fp8_quant(mrgan_handle* h, const void* src, long src_bs, int ld, int rows, int cols, int prow, int nb, unsigned char* dst, long dst_bs,
               int ldd, unsigned char* dstt, long dstt_bs, int lddt, int slot, int fmt, hipStream_t s) {
     Quant8Args q;
@@ -185,126 +140,126 @@ int fp8_quant(mrgan_handle* h, const void* src, long src_bs, int ld, int rows, i
     PROFB("quant8_kernel", launch_quant8(q, s), (double)nb * prow * cols * (2.0 + (dst ? 1.0 : 0.0) + (dstt ? 1.0 : 0.0)));
     return 0;
 }
-// the noisy input rows of dense 1 (xin[0] slots x0_slot .. + nb) -> x8[0] (+ transposed)
-int fp8_quant_x0(mrgan_handle* h, int kind, int x0_slot, int nb, bool want_t, hipStream_t s) {
-    const int S = h->S, Dp = h->Dp;
-    return fp8_quant(h, rowptr(h, h->xin[0], (long)x0_slot * S, Dp), (long)S * Dp, Dp, h->B, Dp, (int)round_up(h->B, 64), nb, h->x8[0],
-                     (long)S * Dp, Dp, want_t ? h->x8t[0] : nullptr, S, 3 * S, slot_x(kind, 0), FP8_E4M3, s);
+// a stored bf16 tensor [nb][S][width] -> fp8 images (row-major; transposed with pitch ldt where imgt is given)
+int fp8_quant_images(mrgan_handle* h, const void* src, int width, int nb, unsigned char* img, unsigned char* imgt, int ldt, int slot,
+                     int fmt, hipStream_t s) {
+    const long bs = (long)h->S * width;
+    return fp8_quant(h, src, bs, width, h->B, width, (int)round_up(h->B, 64), nb, img, bs, width, imgt, h->S, ldt, slot, fmt, s);
 }
+
+// Y = act(X W + b): X [nb][S][Kp] -> out [nb][S][Np]
+int dense_fwd(mrgan_handle* h, const Dense& L, int kind, const void* x, int rows, int nb, void* out, int act, const NoiseSite& nz,
+              const ReluMask& m, const ColSums& cs, hipStream_t s, const Fp8Use& f8 = NO_FP8) {
+    const Fp8Images& q = L.q;
+    const bool fp8 = q.on && kind != KIND_EVAL;
+    const long a_bs = (long)h->S * L.Kp;
+    if (fp8 && f8.quant_in)
+        CHK(fp8_quant_images(h, x, L.Kp, nb, x8_view(h, L), f8.wgrad ? x8t_view(h, L) : nullptr, q.ldxt, q.sx[kind], FP8_E4M3, s));
+    GemmArgs g = with_handle(h, fp8       ? gemm_fwd_args(rows, L.Kp, L.Np, nb, x8_view(h, L), a_bs, L.Kp, q.w8t, L.Kp, true)
+                                : h->bf16 ? gemm_fwd_args(rows, L.Kp, L.Np, nb, x, a_bs, L.Kp, L.W->wt16, L.Kp, true)
+                                          : gemm_fwd_args(rows, L.Kp, L.Np, nb, x, a_bs, L.Kp, L.W->p, L.Np, false));
+    Epi& e = g.e;
+    if (kind == KIND_EVAL) e.st = nullptr;
+    e.act = act; e.n_valid = L.N; e.bias = L.b->p;
+    e.out = out; e.out_bs = (long)h->S * L.Np; e.ldo = L.Np;
+    e.sigma = nz.sigma; e.site = nz.site; e.seg0 = nz.seg0; e.seg_step = nz.seg_step; e.iter_step = nz.iter_step;
+    epi_mask(h, e, m);
+    epi_sums(e, cs, L.Np);
+    if (fp8) {
+        e.qa = h->slots + q.sx[kind]; e.qb = h->slots + q.sw;
+        if (f8.to && f8.to->q.on) epi_images(h, e, f8.to->q.x8, f8.wgrad ? f8.to->q.x8t : nullptr, L.Np, f8.to->q.ldxt, f8.to->q.sx[kind]);
+    }
+    return run_gemm(h, EPI_FWD, g, 2.0 * rows * nb * L.K * L.N, dense_bytes(h, (double)rows * nb, L), s);
+}
+
+// dX = (dY W^T) * act'(prev): dY [nb][S][Np] -> out [nb][S][Kp]
+int dense_dx(mrgan_handle* h, const Dense& L, int kind, const void* dy, int rows, int nb, void* out, int act, int n_valid,
+             const ReluMask& m, const void* hprev, const ColSums& cs, hipStream_t s, const Fp8Use& f8 = NO_FP8) {
+    const Fp8Images& q = L.q;
+    const long a_bs = (long)h->S * L.Np;
+    if (q.on && f8.quant_in)
+        CHK(fp8_quant_images(h, dy, L.Np, nb, q.g8, f8.wgrad ? q.g8t : nullptr, q.ldgt, q.sg[kind], FP8_E5M2, s));
+    GemmArgs g = with_handle(h, q.on ? gemm_dx_args(rows, L.Kp, L.Np, nb, q.g8, a_bs, L.Np, q.w8, L.Np)
+                                     : gemm_dx_args(rows, L.Kp, L.Np, nb, dy, a_bs, L.Np,
+                                                    h->bf16 ? (const void*)L.W->w16 : (const void*)L.W->p, L.Np));
+    Epi& e = g.e;
+    e.act = act; e.n_valid = n_valid;
+    e.out = out; e.out_bs = (long)h->S * L.Kp; e.ldo = L.Kp;
+    epi_mask(h, e, m);
+    e.h = hprev; e.h_bs = (long)h->S * L.Kp; e.ldh = L.Kp;
+    epi_sums(e, cs, L.Kp);
+    e.bn_mu = h->bn_mu; e.bn_rstd = h->bn_rstd;
+    if (q.on) {
+        e.qa = h->slots + q.sg[kind]; e.qb = h->slots + q.sw;
+        if (f8.to && f8.to->q.on) epi_images(h, e, f8.to->q.g8, f8.wgrad ? f8.to->q.g8t : nullptr, L.Kp, f8.to->q.ldgt, f8.to->q.sg[kind]);
+    }
+    return run_gemm(h, EPI_DX, g, 2.0 * rows * nb * L.K * L.N, dense_bytes(h, (double)rows * nb, L), s);
+}
+
+// dW slabs = X^T dY.  The nseg segments ([nseg][S] rows, `rows` valid in each) form ONE virtual reduction
+// range that is cut into L.splits slabs, so the Adam kernel sums at most MAX_SLABS slabs per tensor.
+double dw_args(mrgan_handle* h, GemmArgs& g, const Dense& L, int kind, const void* x, const void* dy, int rows, int nseg) {
+    // bf16 and fp8: reduce over ALL S rows of every segment.  The rows >= `rows` of dY are never written by any kernel (they keep
+    // the zeros of mrgan_create; an fp8 image stores them as zeros) and those of X are finite, so they add exact zeros -- and the
+    // reduction range becomes dense, which is what the LDS-DMA weight-gradient kernel and the grouped launch need (a ragged batch
+    // such as the reference's 50 otherwise fell back to one register-staged launch per product).
+    const bool dense = h->bf16 != 0;
+    const int vrows = dense ? nseg * h->S : (nseg - 1) * h->S + rows;
+    if (L.q.on) {       // the transposed images: reduction index contiguous in both operands
+        g = with_handle(h, gemm_dw_args(L.Kp, L.Np, vrows, L.splits, vrows / L.splits, 0, 0, x8t_view(h, L), L.q.ldxt, L.q.g8t, L.q.ldgt,
+                                        true, L.slabs));
+        g.e.qa = h->slots + L.q.sx[kind]; g.e.qb = h->slots + L.q.sg[kind];
+    } else {
+        g = with_handle(h, gemm_dw_args(L.Kp, L.Np, vrows, L.splits, gemm_dw_kchunk(vrows, L.splits), h->S, dense ? h->S : rows,
+                                        x, L.Kp, dy, L.Np, false, L.slabs));
+    }
+    return 2.0 * rows * nseg * L.K * L.N;
+}
+
+struct DwJob { const Dense* L; const void* x; const void* dy; };
+
+// the weight-gradient products of sub-step `kind`: those of the bf16 fast path as one grouped launch, one launch per product
+// otherwise -- a layer with fp8 images, fp32, or a group the launcher declines -- with the fold as a launch of its own then
+int dense_dw_all(mrgan_handle* h, int kind, const DwJob* jobs, int n, int rows, int nseg, hipStream_t s, const FoldJob* fold = nullptr) {
+    GemmArgs gs[KS_GROUP_MAX];
+    DwJob js[KS_GROUP_MAX];
+    double fl[KS_GROUP_MAX], total = 0.0, bytes = 0.0;
+    if (n > KS_GROUP_MAX) return fail(-1, "dense_dw_all: too many products");
+    std::copy(jobs, jobs + n, js);
+    // the jobs without images first (order kept): the candidates of the grouped launch
+    const int ngroup = (int)(std::stable_partition(js, js + n, [](const DwJob& j) { return !j.L->q.on; }) - js);
+    for (int i = 0; i < n; ++i) fl[i] = dw_args(h, gs[i], *js[i].L, kind, js[i].x, js[i].dy, rows, nseg);
+    for (int i = 0; i < ngroup; ++i) { total += fl[i]; bytes += dw_bytes(h, (double)rows * nseg, *js[i].L); }
+    int first = 0;
+    if (h->bf16 && ngroup > 0) {
+        const char* kname = "gemm";
+        prof_arm(h);
+        const int r = launch_gemm_bf16_dw_group(gs, ngroup, s, &kname, fold);
+        prof_done(h, kname, total, bytes);
+        if (r < 0) return fail(r, "grouped weight-gradient launch failed");
+        if (r == 0) { first = ngroup; fold = nullptr; }
+    }
+    for (int i = first; i < n; ++i) CHK(run_gemm(h, EPI_SLAB, gs[i], fl[i], dw_bytes(h, (double)rows * nseg, *js[i].L), s));
+    if (fold) PROF("reduce_partials_kernel", launch_reduce_partials(fold->src, fold->nsrc, fold->stride, fold->n, fold->ngroups, fold->dst, s));
+    return 0;
+}
+
 }  // namespace
 int mrgan::fp8_update_scales(mrgan_handle* h, hipStream_t s) {
     PROF("fp8_update_scales_kernel", launch_fp8_update_scales(h->slots, FP8_NSLOT, s));
     return 0;
 }
+// the fp8 weight copies of the layers of `net` that own images, from the bf16 copies
 int mrgan::fp8_refresh_weights(mrgan_handle* h, int net, hipStream_t s) {
-    if (net == MRGAN_NET_G) {
-        const Dense& L = h->g[1];
-        return fp8_quant(h, L.W->w16, 0, L.Np, L.Kp, L.Np, L.Kp, 1, h->gw8, 0, L.Np, h->gw8t, 0, L.Kp, SLOT_GW, FP8_E4M3, s);
-    }
-    for (int l = 0; l < 5; ++l) {
-        const Dense& L = h->d[l];
-        CHK(fp8_quant(h, L.W->w16, 0, L.Np, L.Kp, L.Np, L.Kp, 1, h->w8[l], 0, L.Np, h->w8t[l], 0, L.Kp, slot_w(l), FP8_E4M3, s));
+    int n;
+    const Dense* Ls = net_layers(h, net, &n);
+    for (int l = 0; l < n; ++l) {
+        const Dense& L = Ls[l];
+        if (L.q.on) CHK(fp8_quant(h, L.W->w16, 0, L.Np, L.Kp, L.Np, L.Kp, 1, L.q.w8, 0, L.Np, L.q.w8t, 0, L.Kp, L.q.sw, FP8_E4M3, s));
     }
     return 0;
 }
 namespace {
-// generator layer G2 in fp8 (the one wide product of the generator): h2 = softplus(BN(h1) W2 + b2) over nb segments from the
-// current view; BN(h1) is quantised with its transpose (the weight gradient of the G sub-step reads it)
-int fp8_gen_g2_fwd(mrgan_handle* h, int nb, hipStream_t s) {
-    const Dense& L = h->g[1];
-    const int S = h->S;
-    unsigned char* x8 = h->hbn8 + (size_t)h->gen_seg * S * L.Kp;
-    CHK(fp8_quant(h, h->hbn, (long)S * L.Kp, L.Kp, h->B, L.Kp, (int)round_up(h->B, 64), nb, x8, (long)S * L.Kp, L.Kp,
-                  h->hbn8t + (size_t)h->gen_seg * S, S, 2 * S, SLOT_GX, FP8_E4M3, s));
-    GemmArgs g = with_handle(h, gemm_fwd_args(h->B, L.Kp, L.Np, nb, x8, (long)S * L.Kp, L.Kp, h->gw8t, L.Kp, true));
-    Epi& e = g.e;
-    e.act = ACT_SOFTPLUS; e.n_valid = L.N; e.bias = L.b->p;
-    e.out = h->h2; e.out_bs = (long)S * L.Np; e.ldo = L.Np;
-    e.qa = h->slots + SLOT_GX; e.qb = h->slots + SLOT_GW;
-    return run_gemm_fp8(h, EPI_FWD, g, 2.0 * h->B * nb * L.K * L.N, s);
-}
-// backward through G2: dpre2 (bf16, from the G3 dX product) -> e5m2 (+ transpose); d(BN out) = dpre2 W2^T with the BatchNorm
-// backward sums; dW2 = BN(h1)^T dpre2
-int fp8_gen_g2_bwd(mrgan_handle* h, hipStream_t s) {
-    const Dense& L = h->g[1];
-    const int S = h->S;
-    CHK(fp8_quant(h, h->dpre2g, 0, L.Np, h->B, L.Np, (int)round_up(h->B, 64), 1, h->dp2g8, 0, L.Np, h->dp2g8t, 0, S, SLOT_GG, FP8_E5M2, s));
-    GemmArgs g = with_handle(h, gemm_dx_args(h->B, L.Kp, L.Np, 1, h->dp2g8, 0, L.Np, h->gw8, L.Np));
-    Epi& e = g.e;
-    e.act = ACT_LINEAR; e.n_valid = h->g[0].N;
-    e.out = h->dhbn; e.ldo = L.Kp;
-    e.h = h->h1; e.ldh = L.Kp;
-    e.cs_mode = CS_SUM_XHAT; e.cs1 = h->cs_dbeta; e.cs2 = h->cs_dgamma; e.ldcs = L.Kp;
-    e.bn_mu = h->bn_mu; e.bn_rstd = h->bn_rstd;
-    e.qa = h->slots + SLOT_GG; e.qb = h->slots + SLOT_GW;
-    return run_gemm_fp8(h, EPI_DX, g, 2.0 * h->B * L.K * L.N, s);
-}
-int fp8_gen_g2_dw(mrgan_handle* h, hipStream_t s) {
-    const Dense& L = h->g[1];
-    const int S = h->S;
-    GemmArgs g = with_handle(h, gemm_dw_args(L.Kp, L.Np, S, 1, S, 0, 0, h->hbn8t + (size_t)h->gen_seg * S, 2 * S, h->dp2g8t, S, true, L.slabs));
-    g.e.qa = h->slots + SLOT_GX; g.e.qb = h->slots + SLOT_GG;
-    return run_gemm_fp8(h, EPI_SLAB, g, 2.0 * h->B * L.K * L.N, s);
-}
-// dense l + relu (+ the next layer's GaussianNoise): x8[l] -> x8[l + 1] (+ transposed), the feature layer -> feat (bf16)
-int fp8_fwd(mrgan_handle* h, int kind, int l, int nb, bool want_t, bool fm_sums, hipStream_t s) {
-    const Dense& L = h->d[l];
-    const int S = h->S;
-    const bool last = l == 4;
-    GemmArgs g = with_handle(h, gemm_fwd_args(h->B, L.Kp, L.Np, nb, h->x8[l], (long)S * L.Kp, L.Kp, h->w8t[l], L.Kp, true));
-    Epi& e = g.e;
-    e.act = ACT_RELU; e.n_valid = L.N; e.bias = L.b->p;
-    e.out = last ? h->feat : nullptr; e.out_bs = (long)S * L.Np; e.ldo = L.Np;
-    e.sigma = last ? 0.f : h->cfg.sigma[l + 1]; e.site = (uint32_t)(l + 1); e.seg0 = 0;
-    epi_mask(h, e, h->mask[l], h->ldm[l]);
-    e.cs_mode = (last && fm_sums) ? CS_SUM : CS_NONE; e.cs1 = h->cs_f; e.ldcs = L.Np;
-    e.qa = h->slots + slot_x(kind, l); e.qb = h->slots + slot_w(l);
-    if (!last) {
-        e.qo = h->slots + slot_x(kind, l + 1);
-        e.q8 = h->x8[l + 1]; e.q8_bs = (long)S * L.Np; e.ldq8 = L.Np;
-        if (want_t) { e.q8t = h->x8t[l + 1]; e.q8t_bs = S; e.ldq8t = 3 * S; }
-    }
-    return run_gemm_fp8(h, EPI_FWD, g, 2.0 * h->B * nb * L.K * L.N, s);
-}
-// dX through dense l: g8[l] -> g8[l - 1] (+ transposed) with the relu mask of layer l - 1 and its bias-gradient column sums;
-// l == 0: d loss / d(generator output) -> dxfake (bf16)
-int fp8_dx(mrgan_handle* h, int kind, int l, int nb, bool want_t, bool bias_sums, hipStream_t s) {
-    const Dense& L = h->d[l];
-    const int S = h->S;
-    GemmArgs g = with_handle(h, gemm_dx_args(h->B, L.Kp, L.Np, nb, h->g8[l], (long)S * L.Np, L.Np, h->w8[l], L.Np));
-    Epi& e = g.e;
-    e.qa = h->slots + slot_g(kind, l); e.qb = h->slots + slot_w(l);
-    e.ldcs = L.Kp;
-    if (l > 0) {
-        e.act = ACT_RELU; e.n_valid = h->d[l - 1].N;
-        epi_mask(h, e, h->mask[l - 1], h->ldm[l - 1]);
-        e.cs_mode = bias_sums ? CS_SUM : CS_NONE; e.cs1 = h->cs_db[l - 1];
-        e.qo = h->slots + slot_g(kind, l - 1);
-        e.q8 = h->g8[l - 1]; e.q8_bs = (long)S * L.Kp; e.ldq8 = L.Kp;
-        if (want_t) { e.q8t = h->g8t[l - 1]; e.q8t_bs = S; e.ldq8t = 3 * S; }
-    } else {
-        e.act = ACT_LINEAR; e.n_valid = h->cfg.d_in;
-        e.out = h->dxfake; e.out_bs = (long)S * L.Kp; e.ldo = L.Kp;
-        e.cs_mode = CS_SUM; e.cs1 = h->cs_db3g;
-    }
-    return run_gemm_fp8(h, EPI_DX, g, 2.0 * h->B * nb * L.K * L.N, s);
-}
-// dW_l = x8t[l] g8t[l]^T over the 3 S rows of the D sub-step (rows >= batch of a segment are zero in both), one fp32 slab
-int fp8_dw(mrgan_handle* h, int kind, int l, int nseg, hipStream_t s) {
-    const Dense& L = h->d[l];
-    const int S = h->S, splits = (nseg == 3) ? L.splits : 1;
-    GemmArgs g = with_handle(h, gemm_dw_args(L.Kp, L.Np, nseg * S, splits, nseg * S / splits, 0, 0, h->x8t[l], 3 * S, h->g8t[l], 3 * S,
-                                             true, L.slabs));
-    g.e.qa = h->slots + slot_x(kind, l); g.e.qb = h->slots + slot_g(kind, l);
-    return run_gemm_fp8(h, EPI_SLAB, g, 2.0 * h->B * nseg * L.K * L.N, s);
-}
-// the discriminator's five products of sub-step `kind`; the transposed copies only where weight gradients follow (D)
-int fp8_disc_fwd(mrgan_handle* h, int kind, int nb, bool fm_sums, int x0_slot, hipStream_t s) {
-    const bool want_t = kind == 0;
-    CHK(fp8_quant_x0(h, kind, x0_slot, nb, want_t, s));
-    for (int l = 0; l < 5; ++l) CHK(fp8_fwd(h, kind, l, nb, want_t, fm_sums, s));
-    return 0;
-}
 
 int run_adam(mrgan_handle* h, int net, int mode, bool with_metrics, hipStream_t s, int advance_batch = 0) {
     AdamArgs a;
@@ -333,9 +288,9 @@ int run_adam(mrgan_handle* h, int net, int mode, bool with_metrics, hipStream_t 
 // generator forward up to the BatchNorm statistics (phase *_GEN) and from there to the fake rows.
 // nb = 2 (pair_gen): segment 0 is this D sub-step's batch, segment 1 the following G sub-step's (its z, noise
 // iteration and noise segment id are those the G sub-step would use on its own, so the results are identical).
+// Either sub-step runs these passes as KIND_D: a paired pass serves both, so G2's images share their slots between the kinds.
 int gen_fwd_head(mrgan_handle* h, int nb, hipStream_t s) {
-    CHK(dense_fwd(h, h->g[0], h->zbuf, h->B, nb, h->h1, ACT_SOFTPLUS, 0.f, 0, 0, nullptr, 0, CS_SUM_SQ, h->cs_bn1, h->cs_bn2,
-                  true, s));
+    CHK(dense_fwd(h, h->g[0], KIND_D, h->zbuf, h->B, nb, h->h1, ACT_SOFTPLUS, NO_NOISE, NO_MASK, ColSums{CS_SUM_SQ, h->cs_bn1, h->cs_bn2}, s));
     if (h->sync_stats) {
         const int n = h->g[0].Np;          // both segments of a paired forward in one launch
         PROF("colsum_finalize_kernel", launch_colsum_finalize(h->cs_bn1, h->cs_bn2, h->tiles_m, n, n, h->r_bn_stats, s, nb));
@@ -353,26 +308,26 @@ int gen_fwd_tail(mrgan_handle* h, int nb, int fake_seg_slot, uint32_t fake_seg_i
     b.ldcs = n; b.count = h->stat_count; b.eps = h->cfg.bn_eps;
     b.gamma = h->gt[2].p; b.beta = h->gt[3].p; b.mu = h->bn_mu; b.rstd = h->bn_rstd;
     PROF("bn_apply_kernel", launch_bn_apply(h->bf16, b, s));
-    if (h->fp8) CHK(fp8_gen_g2_fwd(h, nb, s));
-    else CHK(dense_fwd(h, h->g[1], h->hbn, h->B, nb, h->h2, ACT_SOFTPLUS, 0.f, 0, 0, nullptr, 0, CS_NONE, nullptr, nullptr, true, s));
+    // fp8: BN(h1) is quantised with its transpose (the weight gradient of the G sub-step reads it, also after a paired pass)
+    CHK(dense_fwd(h, h->g[1], KIND_D, h->hbn, h->B, nb, h->h2, ACT_SOFTPLUS, NO_NOISE, NO_MASK, NO_SUMS, s, Fp8Use{nullptr, true, true}));
     // generator output + GaussianNoise(sigma0) = the discriminator's noisy input rows of the fake segment.
     // Paired: segment 1 lands in the next xin[0] slot and is drawn as (segment id 0, iteration + 1), the G sub-step's fake rows.
     void* out = rowptr(h, h->xin[0], (long)fake_seg_slot * h->S, h->Dp);
-    CHK(dense_fwd(h, h->g[2], h->h2, h->B, nb, out, ACT_LINEAR, h->cfg.sigma[0], 0, fake_seg_id, nullptr, 0, CS_NONE, nullptr,
-                  nullptr, true, s, nb > 1 ? -(int)fake_seg_id : 1, nb > 1 ? 1u : 0u));
+    const NoiseSite nz = {h->cfg.sigma[0], 0, fake_seg_id, nb > 1 ? -(int)fake_seg_id : 1, nb > 1 ? 1u : 0u};
+    CHK(dense_fwd(h, h->g[2], KIND_D, h->h2, h->B, nb, out, ACT_LINEAR, nz, NO_MASK, NO_SUMS, s));
     return 0;
 }
 
-// discriminator dense 1..5 over nb segments of sub-step `kind` (0 = D, 1 = G; learning phase 1: noise on)
+// discriminator dense 1..5 over nb segments of sub-step `kind` (learning phase 1: noise on).  fp8: the noisy input rows of
+// dense 1 are quantised, every product fills the next layer's images, transposed too where weight gradients follow (D)
 int disc_fwd_train(mrgan_handle* h, int kind, int nb, bool fm_sums, int x0_slot, hipStream_t s, int l_end = 5) {
-    if (h->fp8) return fp8_disc_fwd(h, kind, nb, fm_sums, x0_slot, s);
     for (int l = 0; l < l_end; ++l) {
         const void* in = l == 0 ? rowptr(h, h->xin[0], (long)x0_slot * h->S, h->Dp) : h->xin[l];
         void* out = l < 4 ? h->xin[l + 1] : h->feat;
-        const float sigma = l < 4 ? h->cfg.sigma[l + 1] : 0.f;
+        const NoiseSite nz = {l < 4 ? h->cfg.sigma[l + 1] : 0.f, (uint32_t)(l + 1), 0, 1, 0};
         const bool last = l == 4;
-        CHK(dense_fwd(h, h->d[l], in, h->B, nb, out, ACT_RELU, sigma, (uint32_t)(l + 1), 0, h->mask[l], h->ldm[l],
-                      (last && fm_sums) ? CS_SUM : CS_NONE, h->cs_f, nullptr, true, s));
+        CHK(dense_fwd(h, h->d[l], kind, in, h->B, nb, out, ACT_RELU, nz, relu_mask(h, l), ColSums{(last && fm_sums) ? CS_SUM : CS_NONE, h->cs_f, nullptr},
+                      s, Fp8Use{last ? nullptr : &h->d[l + 1], kind == KIND_D, l == 0}));
     }
     return 0;
 }
@@ -523,9 +478,10 @@ int disc_head(mrgan_handle* h, const mrgan_disc_args* a, hipStream_t s) {
     hd.inv_count = 1.0f / (float)h->Bg; hd.unl_weight = h->cfg.unlabeled_weight;
     if (h->fp8) {                 // the head writes the e5m2 copies of dpre itself (no bf16 dpre, no quantiser pass)
         hd.dpre = nullptr;
-        hd.q8 = h->g8[4]; hd.q8_bs = (long)h->S * h->Fp; hd.ldq8 = h->Fp;
-        hd.q8t = h->g8t[4]; hd.q8t_bs = h->S; hd.ldq8t = 3 * h->S;
-        hd.q8_slot = h->slots + slot_g(0, 4);
+        const Fp8Images& q = h->d[4].q;
+        hd.q8 = q.g8; hd.q8_bs = (long)h->S * h->Fp; hd.ldq8 = h->Fp;
+        hd.q8t = q.g8t; hd.q8t_bs = h->S; hd.ldq8t = q.ldgt;
+        hd.q8_slot = h->slots + q.sg[KIND_D];
     }
     if (h->dtail_chain()) {
         // D3 D4 D5 forward -> loss head -> dX through D5 D4 D3, one launch: the rows of a block never leave its CU
@@ -560,24 +516,17 @@ int disc_head(mrgan_handle* h, const mrgan_disc_args* a, hipStream_t s) {
     return 0;
 }
 
-// bf16 / fp32 backward of the discriminator stack below dpre[l_top], nseg segments: dX with the bias-gradient column sums
-// down to layer 1, then the five weight gradients as one grouped launch whose tail blocks fold the loss head's fold_rows
-// per-block partial rows
+// backward of the discriminator stack below dpre[l_top], nseg segments: dX with the bias-gradient column sums down to layer 1,
+// then the five weight gradients and the fold of the loss head's fold_rows per-block partial rows (dense_dw_all: bf16 as one
+// grouped launch whose tail blocks fold, fp8 one product per layer over the 3 S rows of the images)
 int disc_bwd(mrgan_handle* h, int nseg, int l_top, int fold_rows, hipStream_t s) {
     for (int l = l_top; l >= 1; --l)
-        CHK(dense_dx(h, h->d[l], h->dpre[l], h->B, nseg, h->dpre[l - 1], ACT_RELU, h->d[l - 1].N, h->mask[l - 1], h->ldm[l - 1],
-                     nullptr, CS_SUM, h->cs_db[l - 1], nullptr, s));
+        CHK(dense_dx(h, h->d[l], KIND_D, h->dpre[l], h->B, nseg, h->dpre[l - 1], ACT_RELU, h->d[l - 1].N, relu_mask(h, l - 1), nullptr,
+                     ColSums{CS_SUM, h->cs_db[l - 1], nullptr}, s, Fp8Use{&h->d[l - 1], true, false}));
     DwJob jobs[5];
     for (int l = 0; l < 5; ++l) jobs[l] = DwJob{&h->d[l], h->xin[l], h->dpre[l]};
     const FoldJob fold = {h->head_part, h->head_red, (long)h->head_stride, fold_rows, h->head_stride, h->head_groups, 0};
-    return dense_dw_all(h, jobs, 5, h->B, nseg, s, &fold);
-}
-// the same in fp8 (D sub-step): dX, one weight-gradient product per layer over the 3 S rows, the fold as a launch of its own
-int fp8_disc_bwd(mrgan_handle* h, hipStream_t s) {
-    for (int l = 4; l >= 1; --l) CHK(fp8_dx(h, 0, l, 3, true, true, s));
-    for (int l = 0; l < 5; ++l) CHK(fp8_dw(h, 0, l, 3, s));
-    PROF("reduce_partials_kernel", launch_reduce_partials(h->head_part, h->head_nblk, h->head_stride, h->head_stride, h->head_groups, h->head_red, s));
-    return 0;
+    return dense_dw_all(h, KIND_D, jobs, 5, h->B, nseg, s, &fold);
 }
 
 int disc_phase(mrgan_handle* h, const mrgan_disc_args* a, int phase, hipStream_t s) {
@@ -607,8 +556,7 @@ int disc_phase(mrgan_handle* h, const mrgan_disc_args* a, int phase, hipStream_t
         h->pair_gen = 0;                                                  // one D sub-step per hint
         CHK(disc_fwd_train(h, 0, 3, false, 0, s, h->dtail_chain() ? 2 : 5));
         CHK(disc_head(h, a, s));
-        if (h->fp8) CHK(fp8_disc_bwd(h, s));
-        else CHK(disc_bwd(h, 3, h->dtail_chain() ? 1 : 4, h->head_nblk, s));
+        CHK(disc_bwd(h, 3, h->dtail_chain() ? 1 : 4, h->head_nblk, s));
         if (h->flat_grads) CHK(run_adam(h, MRGAN_NET_D, ADAM_REDUCE_ONLY, true, s));
     } else if (phase == MRGAN_D_ADAM) {
         CHK(run_adam(h, MRGAN_NET_D, h->flat_grads ? ADAM_FROM_FLAT : ADAM_FUSED, true, s));
@@ -646,7 +594,7 @@ int fm_grad(mrgan_handle* h, hipStream_t s) {
     f.mask = h->mask[4]; f.ldm = h->ldm[4]; f.dpre = h->dpre[4]; f.ldd = h->Fp; f.rows = h->B;
     f.loss_out = h->step_out + 3; f.accum = h->accum + 3;
     f.lscratch = h->fm_scratch; f.lcount = h->fm_count;
-    if (h->fp8) { f.dpre = nullptr; f.q8 = h->g8[4]; f.ldq8 = h->Fp; f.q8_slot = h->slots + slot_g(1, 4); }
+    if (h->fp8) { f.dpre = nullptr; f.q8 = h->d[4].q.g8; f.ldq8 = h->Fp; f.q8_slot = h->slots + h->d[4].q.sg[KIND_G]; }
     if (!h->use_chain) {
         PROF("fm_kernel", launch_fm(h->bf16, f, s));
         return 0;
@@ -664,15 +612,11 @@ int fm_grad(mrgan_handle* h, hipStream_t s) {
 // dX through the discriminator layers fm_grad left, down to d loss / d(generator output) -> dxfake (noise is additive, so
 // this is also d / d(fake x)), with the column sums behind the generator's last bias gradient
 int disc_dx_to_input(mrgan_handle* h, hipStream_t s) {
-    if (h->fp8) {
-        for (int l = 4; l >= 0; --l) CHK(fp8_dx(h, 1, l, 1, false, false, s));
-        return 0;
-    }
     for (int l = h->use_chain ? 1 : 4; l >= 1; --l)
-        CHK(dense_dx(h, h->d[l], h->dpre[l], h->B, 1, h->dpre[l - 1], ACT_RELU, h->d[l - 1].N, h->mask[l - 1], h->ldm[l - 1],
-                     nullptr, CS_NONE, nullptr, nullptr, s));
-    return dense_dx(h, h->d[0], h->dpre[0], h->B, 1, h->dxfake, ACT_LINEAR, h->cfg.d_in, nullptr, 0, nullptr, CS_SUM, h->cs_db3g,
-                    nullptr, s);
+        CHK(dense_dx(h, h->d[l], KIND_G, h->dpre[l], h->B, 1, h->dpre[l - 1], ACT_RELU, h->d[l - 1].N, relu_mask(h, l - 1), nullptr,
+                     NO_SUMS, s, Fp8Use{&h->d[l - 1], false, false}));
+    return dense_dx(h, h->d[0], KIND_G, h->dpre[0], h->B, 1, h->dxfake, ACT_LINEAR, h->cfg.d_in, NO_MASK, nullptr,
+                    ColSums{CS_SUM, h->cs_db3g, nullptr}, s);
 }
 
 int gen_phase(mrgan_handle* h, const mrgan_gen_args* a, int phase, hipStream_t s) {
@@ -708,11 +652,11 @@ int gen_phase(mrgan_handle* h, const mrgan_gen_args* a, int phase, hipStream_t s
     } else if (phase == MRGAN_G_BWD) {
         CHK(fm_grad(h, s));
         CHK(disc_dx_to_input(h, s));
-        CHK(dense_dx(h, h->g[2], h->dxfake, B, 1, h->dpre2g, ACT_SOFTPLUS, h->g[1].N, nullptr, 0, h->h2, CS_SUM, h->cs_db2g,
-                     nullptr, s));
-        if (h->fp8) CHK(fp8_gen_g2_bwd(h, s));
-        else CHK(dense_dx(h, h->g[1], h->dpre2g, B, 1, h->dhbn, ACT_LINEAR, h->g[0].N, nullptr, 0, h->h1, CS_SUM_XHAT, h->cs_dbeta,
-                          h->cs_dgamma, s));
+        CHK(dense_dx(h, h->g[2], KIND_G, h->dxfake, B, 1, h->dpre2g, ACT_SOFTPLUS, h->g[1].N, NO_MASK, h->h2,
+                     ColSums{CS_SUM, h->cs_db2g, nullptr}, s));
+        // d(BN out) = dpre2 W2^T with the BatchNorm backward sums; fp8: dpre2 (bf16, from the G3 dX product) -> e5m2 (+ transpose)
+        CHK(dense_dx(h, h->g[1], KIND_G, h->dpre2g, B, 1, h->dhbn, ACT_LINEAR, h->g[0].N, NO_MASK, h->h1,
+                     ColSums{CS_SUM_XHAT, h->cs_dbeta, h->cs_dgamma}, s, Fp8Use{nullptr, true, true}));
         if (h->sync_stats) {
             PROF("colsum_finalize_kernel", launch_colsum_finalize(h->cs_dbeta, h->cs_dgamma, tm, N1p, N1p, h->r_bn_bwd, s));
         }
@@ -725,10 +669,9 @@ int gen_phase(mrgan_handle* h, const mrgan_gen_args* a, int phase, hipStream_t s
         b.ldcs = N1p; b.count = h->stat_count; b.gamma = h->gt[2].p; b.mu = h->bn_mu; b.rstd = h->bn_rstd;
         b.db_part = h->db1g_part;
         PROF("bn_bwd_kernel", launch_bn_bwd(h->bf16, b, s));
-        // the generator's weight gradients; in fp8 the wide one (G2) is a product of its own
+        // the generator's weight gradients; in fp8 the wide one (G2) is a product of its own, after the grouped launch
         const DwJob jobs[3] = {{&h->g[2], h->h2, h->dxfake}, {&h->g[0], h->zbuf, h->dpre1g}, {&h->g[1], h->hbn, h->dpre2g}};
-        CHK(dense_dw_all(h, jobs, h->fp8 ? 2 : 3, B, 1, s));
-        if (h->fp8) CHK(fp8_gen_g2_dw(h, s));
+        CHK(dense_dw_all(h, KIND_G, jobs, 3, B, 1, s));
         if (h->flat_grads) CHK(run_adam(h, MRGAN_NET_G, ADAM_REDUCE_ONLY, false, s));
     } else if (phase == MRGAN_G_ADAM) {
         CHK(run_adam(h, MRGAN_NET_G, h->flat_grads ? ADAM_FROM_FLAT : ADAM_FUSED, false, s, a->stream_mode ? 1 : 0));
@@ -790,8 +733,7 @@ int eval_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, cons
         PROF("stage_kernel", launch_stage(h->bf16, st, s));
         for (int l = 0; l < 5; ++l) {
             // one "segment" of `rows` contiguous rows: batch stride is irrelevant with nb = 1
-            CHK(dense_fwd(h, h->d[l], h->xin[l], rows, 1, l < 4 ? h->xin[l + 1] : h->feat, ACT_RELU, 0.f, 0, 0, nullptr, 0, CS_NONE,
-                          nullptr, nullptr, false, s));
+            CHK(dense_fwd(h, h->d[l], KIND_EVAL, h->xin[l], rows, 1, l < 4 ? h->xin[l + 1] : h->feat, ACT_RELU, NO_NOISE, NO_MASK, NO_SUMS, s));
         }
         HeadArgs hd = head_args(h, {labels ? HEAD_EVAL : HEAD_LOGITS}, rows, false);
         hd.labels = labels ? labels + r0 : nullptr;

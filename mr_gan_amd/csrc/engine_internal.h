@@ -34,6 +34,7 @@ int fail(int code, const char* fmt, ...);      // records the message behind mrg
 
 constexpr int SEG_ALIGN = 128; // segment row stride is a multiple of the GEMM block tile
 
+struct Dense;
 struct Tensor {                // one trainable tensor (padded fp32 master + Adam slots)
     int rows, cols;            // logical (1-D: rows = 1)
     int prow, pcol;            // padded
@@ -42,23 +43,34 @@ struct Tensor {                // one trainable tensor (padded fp32 master + Ada
     float* flat;               // position inside the flat gradient buffer
     __bf16* flat16;            // ... inside the bfloat16 one (MRGAN_FLAG_GRAD_BF16)
     const float* g; int nslab; long slab_stride;      // fused-mode gradient source
+    const Dense* layer;                               // the dense layer whose weight matrix this is (null: bias, BatchNorm)
+};
+
+// fp8 storage of a dense layer (gemm_fp8.hip): e4m3 images of its input and e5m2 images of its output gradient dpre, each
+// row-major [segments][S][width] and transposed [width][pitch] (segment b at column b S), written by the producing product's
+// epilogue, the loss head, the feature-matching kernel or a quantiser pass; e4m3 weight copies w8 [K][N] / w8t [N][K],
+// refreshed by the Adam kernel.  Forward reads x8 x w8t, dX g8 x w8, dW x8t x g8t over the whole pitch (rows >= batch of a
+// segment are zero in both).  Every image has a scaling slot per sub-step kind (0 = D, 1 = G).
+struct Fp8Images {
+    bool on;                                  // false: the layer's products take the bf16 / fp32 tensors
+    unsigned char *x8, *x8t; int ldxt;
+    unsigned char *g8, *g8t; int ldgt;
+    unsigned char *w8, *w8t;
+    int xseg;                                 // segment of x8 / x8t the products work on (G2: the generator view's, set_gen_view)
+    int sx[2], sg[2], sw;                     // slot indices: input and gradient per sub-step kind, weight
 };
 
 struct Dense {
     int K, N, Kp, Np, act;
     Tensor *W, *b;
     float* slabs; int splits;   // weight-gradient slabs [nseg*splits][Kp][Np]
+    Fp8Images q;                // fp8 handles: the discriminator's D1 .. D5 and the generator's wide layer G2
 };
 
 struct ProfRec { int cat; hipEvent_t start, stop; double flops, bytes; };      // device-side begin / end of one kernel (MRGAN_LAUNCH)
 
-// fp8 scaling slots: kind 0 = D sub-step, 1 = G sub-step; X = activations (e4m3), G = gradients (e5m2), W = weights (e4m3)
+// fp8 scaling slots (Fp8Images: activations and weights e4m3, gradients e5m2); layout() hands them out
 constexpr int FP8_NSLOT = 28, FP8_DRY_PASSES = MRGAN_FP8_DRY_PASSES;
-inline int slot_x(int kind, int l) { return kind * 10 + l; }
-inline int slot_g(int kind, int l) { return kind * 10 + 5 + l; }
-inline int slot_w(int l) { return 20 + l; }
-// the generator's 4096 x 4096-class layer G2 (hbn -> h2): input, output gradient, weight
-constexpr int SLOT_GX = 25, SLOT_GG = 26, SLOT_GW = 27;
 constexpr float FP8_TARGET_E4M3 = 224.0f, FP8_TARGET_E5M2 = 28672.0f;      // half the largest finite value: 2x headroom
 
 
@@ -105,12 +117,8 @@ struct mrgan_handle {
     float *head_part, *head_red, *loss_part; int head_stride, head_groups;
     int head_nblk;                        // partial rows of head_part / loss_part behind the last loss head (set where it is launched)
     int bnb_blocks;
-    // fp8 mode (gemm_fp8.hip): fp8 copies of the discriminator's activations x8 / gradients g8 (row-major and transposed),
-    // of its weights, and the scaling slots (index fp8_slot())
+    // fp8 mode (gemm_fp8.hip): the layers' Fp8Images and their scaling slots
     bool fp8; int fp8_cal[2];
-    unsigned char *x8[5], *x8t[5], *g8[5], *g8t[5], *w8[5], *w8t[5];
-    unsigned char *hbn8, *hbn8t, *dp2g8, *dp2g8t, *gw8, *gw8t;      // generator layer G2: BN(h1) [2][S][N1], dpre2 [S][N2], W2
-    int gen_seg;                                                  // segment the generator views point at (set_gen_view)
     Fp8Slot* slots; float* slot_targets; float* accum_save;
     float* fm_scratch; unsigned int* fm_count;       // feature-matching loss partials of a wide feature layer (aux_kernels.hip)
     int KP;                              // class pitch (aux_kernels.h): columns of W6 / b6 / logits / the head's partial rows
@@ -131,6 +139,7 @@ struct mrgan_handle {
 namespace mrgan {
 
 inline void* rowptr(mrgan_handle* h, void* base, long row, int ld) { return (char*)base + (size_t)row * ld * h->es; }
+inline Dense* net_layers(mrgan_handle* h, int net, int* n) { *n = net == MRGAN_NET_G ? 3 : 6; return net == MRGAN_NET_G ? h->g : h->d; }
 inline dim3 grid2d(int prow, int pcol) { return dim3(ceil_div(pcol, 64), ceil_div(prow, 4)); }
 // which of the two generator-activation segments the following kernels work on
 void set_gen_view(mrgan_handle* h, int seg);

@@ -18,7 +18,7 @@ int fail(int code, const char* fmt, ...) {
 }
 
 void set_gen_view(mrgan_handle* h, int seg) {
-    h->gen_seg = seg;
+    h->g[1].q.xseg = seg;
     const int N1p = h->g[0].Np;
     h->zbuf = rowptr(h, h->zbuf_all, (long)seg * h->S, h->nzp);
     h->h1 = rowptr(h, h->h1_all, (long)seg * h->S, N1p);
@@ -156,7 +156,8 @@ int layout(mrgan_handle* h, char* base, size_t* bytes_out) {
         const int K = gdim[l], N = gdim[l + 1], Kp = padded(K), Np = padded(N);
         mk(h->gt[gW[l]], K, N, Kp, Np, true);
         mk(h->gt[gb[l]], 1, N, 1, Np, false);
-        h->g[l] = Dense{K, N, Kp, Np, l < 2 ? ACT_SOFTPLUS : ACT_LINEAR, &h->gt[gW[l]], &h->gt[gb[l]], nullptr, 1};
+        h->g[l] = Dense{K, N, Kp, Np, l < 2 ? ACT_SOFTPLUS : ACT_LINEAR, &h->gt[gW[l]], &h->gt[gb[l]], nullptr, 1, Fp8Images()};
+        h->gt[gW[l]].layer = &h->g[l];
     }
     mk(h->gt[2], 1, gdim[1], 1, padded(gdim[1]), false);
     mk(h->gt[3], 1, gdim[1], 1, padded(gdim[1]), false);
@@ -164,7 +165,8 @@ int layout(mrgan_handle* h, char* base, size_t* bytes_out) {
         const int K = ddim[l], N = ddim[l + 1], Kp = padded(K), Np = (l == 5) ? KP : padded(N);
         mk(h->dt[2 * l], K, N, Kp, Np, l < 5);
         mk(h->dt[2 * l + 1], 1, N, 1, Np, false);
-        h->d[l] = Dense{K, N, Kp, Np, l < 5 ? ACT_RELU : ACT_LINEAR, &h->dt[2 * l], &h->dt[2 * l + 1], nullptr, 1};
+        h->d[l] = Dense{K, N, Kp, Np, l < 5 ? ACT_RELU : ACT_LINEAR, &h->dt[2 * l], &h->dt[2 * l + 1], nullptr, 1, Fp8Images()};
+        h->dt[2 * l].layer = &h->d[l];
     }
     // flat gradient buffers (padded layout, Keras order) + 4 scalars
     const bool g16 = (c.flags & MRGAN_FLAG_GRAD_BF16) != 0;
@@ -199,18 +201,22 @@ int layout(mrgan_handle* h, char* base, size_t* bytes_out) {
     }
     h->feat = act(3 * (size_t)S, h->Fp);
     if (h->fp8) {
-        for (int l = 0; l < 5; ++l) {
-            const Dense& L = h->d[l];
-            h->x8[l] = a.take<unsigned char>(3 * (size_t)S * L.Kp); h->x8t[l] = a.take<unsigned char>(3 * (size_t)S * L.Kp);
-            h->g8[l] = a.take<unsigned char>(3 * (size_t)S * L.Np); h->g8t[l] = a.take<unsigned char>(3 * (size_t)S * L.Np);
-            h->w8[l] = a.take<unsigned char>((size_t)L.Kp * L.Np); h->w8t[l] = a.take<unsigned char>((size_t)L.Kp * L.Np);
-        }
-        {
-            const Dense& L = h->g[1];
-            h->hbn8 = a.take<unsigned char>(2 * (size_t)S * L.Kp); h->hbn8t = a.take<unsigned char>(2 * (size_t)S * L.Kp);
-            h->dp2g8 = a.take<unsigned char>((size_t)S * L.Np); h->dp2g8t = a.take<unsigned char>((size_t)S * L.Np);
-            h->gw8 = a.take<unsigned char>((size_t)L.Kp * L.Np); h->gw8t = a.take<unsigned char>((size_t)L.Kp * L.Np);
-        }
+        // the images of a layer whose input spans xseg segments and whose gradient gseg; slots: input and gradient of the D and
+        // of the G sub-step, weight
+        auto images = [&](Dense& L, int xseg, int gseg, int sx0, int sx1, int sg0, int sg1, int sw) {
+            Fp8Images& q = L.q;
+            q.on = true; q.xseg = 0;
+            q.ldxt = xseg * S; q.ldgt = gseg * S;
+            q.x8 = a.take<unsigned char>((size_t)q.ldxt * L.Kp); q.x8t = a.take<unsigned char>((size_t)q.ldxt * L.Kp);
+            q.g8 = a.take<unsigned char>((size_t)q.ldgt * L.Np); q.g8t = a.take<unsigned char>((size_t)q.ldgt * L.Np);
+            q.w8 = a.take<unsigned char>((size_t)L.Kp * L.Np); q.w8t = a.take<unsigned char>((size_t)L.Kp * L.Np);
+            q.sx[0] = sx0; q.sx[1] = sx1; q.sg[0] = sg0; q.sg[1] = sg1; q.sw = sw;
+        };
+        // discriminator: the three segments of the D sub-step (the G sub-step uses two, then one), slots per sub-step kind
+        for (int l = 0; l < 5; ++l) images(h->d[l], 3, 3, l, 10 + l, 5 + l, 15 + l, 20 + l);      // slots [kind][x | g][l], then w[l]
+        // generator layer G2 (the one wide product of the generator): BN(h1) of both segments of a paired forward, dpre2 of the G
+        // sub-step; the D sub-step's generator pass may be the G sub-step's too, so the two kinds share their slots
+        images(h->g[1], 2, 1, 25, 25, 26, 26, 27);
         h->slots = a.take<Fp8Slot>(FP8_NSLOT); h->slot_targets = a.take<float>(FP8_NSLOT); h->accum_save = a.take<float>(4);
     }
     h->dxfake = act(S, h->Dp); h->dpre2g = act(S, h->g[1].Np); h->dhbn = act(S, N1p); h->dpre1g = act(S, N1p);
@@ -300,9 +306,10 @@ int upload_tiles(mrgan_handle* h, std::vector<Tensor>& ts, AdamTile* dev, int n,
                 a.w16 = t.w16 ? t.w16 + off : nullptr;
                 a.wt16 = t.wt16 ? t.wt16 + (long)c0 * t.prow + r0 : nullptr;
                 a.w8 = a.w8t = nullptr; a.w8_slot = nullptr;
-                for (int l = 0; l < 5 && h->fp8; ++l)
-                    if (&t == h->d[l].W) { a.w8 = h->w8[l] + off; a.w8t = h->w8t[l] + (long)c0 * t.prow + r0; a.w8_slot = h->slots + slot_w(l); }
-                if (h->fp8 && &t == h->g[1].W) { a.w8 = h->gw8 + off; a.w8t = h->gw8t + (long)c0 * t.prow + r0; a.w8_slot = h->slots + SLOT_GW; }
+                if (t.layer && t.layer->q.on) {
+                    const Fp8Images& q = t.layer->q;
+                    a.w8 = q.w8 + off; a.w8t = q.w8t + (long)c0 * t.prow + r0; a.w8_slot = h->slots + q.sw;
+                }
                 a.ld = t.pcol; a.ldt = t.prow;
                 a.rows = std::min(TR, t.prow - r0); a.cols = std::min(64, t.pcol - c0);
                 v.push_back(a);
@@ -391,11 +398,17 @@ int mrgan_create(const mrgan_config* cfg, void* workspace, size_t bytes, mrgan_s
     if (!r) r = upload_tiles(h, h->dt, h->tiles_d_dev, h->ntiles_d, s);
     if (r) { if (h->own_ws) hipFree(h->ws); delete h; return r; }
     if (h->fp8) {
-        float tg[FP8_NSLOT];
-        for (int k = 0; k < 2; ++k)
-            for (int l = 0; l < 5; ++l) { tg[slot_x(k, l)] = FP8_TARGET_E4M3; tg[slot_g(k, l)] = FP8_TARGET_E5M2; }
-        for (int l = 0; l < 5; ++l) tg[slot_w(l)] = FP8_TARGET_E4M3;
-        tg[SLOT_GX] = FP8_TARGET_E4M3; tg[SLOT_GG] = FP8_TARGET_E5M2; tg[SLOT_GW] = FP8_TARGET_E4M3;
+        float tg[FP8_NSLOT] = {};
+        for (int net : {MRGAN_NET_D, MRGAN_NET_G}) {
+            int n;
+            const Dense* Ls = net_layers(h, net, &n);
+            for (int l = 0; l < n; ++l) {
+                const Fp8Images& q = Ls[l].q;
+                if (!q.on) continue;
+                for (int k = 0; k < 2; ++k) { tg[q.sx[k]] = FP8_TARGET_E4M3; tg[q.sg[k]] = FP8_TARGET_E5M2; }
+                tg[q.sw] = FP8_TARGET_E4M3;
+            }
+        }
         CREATE_CHK(hipMemcpyAsync(h->slot_targets, tg, sizeof tg, hipMemcpyHostToDevice, s));
         CREATE_CHK(hipStreamSynchronize(s));
         if (launch_fp8_init_slots(h->slots, FP8_NSLOT, h->slot_targets, s) != 0) { if (h->own_ws) hipFree(h->ws); delete h; return fail(-10, "fp8 slot init failed"); }
@@ -436,8 +449,8 @@ int mrgan_set_weights(mrgan_handle* h, int net, int idx, const float* src, mrgan
     HIPCHK(hipMemcpy2DAsync(t->p, sizeof(float) * t->pcol, src, sizeof(float) * t->cols, sizeof(float) * t->cols, t->rows,
                             hipMemcpyDeviceToDevice, s));
     if (t->w16) hipLaunchKernelGGL(refresh_bf16_kernel, grid2d(t->prow, t->pcol), dim3(256), 0, s, t->p, t->w16, t->wt16, t->prow, t->pcol);
-    if (h->fp8 && t->w16 && (net == MRGAN_NET_D || t == h->g[1].W)) {
-        // fp8 copies of the discriminator's weights: the first pass only measures max |w|, the second stores with that scale
+    if (t->layer && t->layer->q.on) {
+        // fp8 copies of the network's weights: the first pass only measures max |w|, the second stores with that scale
         for (int pass = 0; pass < 2; ++pass) { CHK(fp8_refresh_weights(h, net, s)); CHK(fp8_update_scales(h, s)); }
     }
     return 0;

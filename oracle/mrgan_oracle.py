@@ -365,8 +365,8 @@ def _ident(x):
 
 
 FP8_FORMATS = {'e4m3': (3, -6, 448.0), 'e5m2': (2, -14, 57344.0)}      # OCP: mantissa bits, smallest normal exponent, largest finite
-FP8_TARGETS = {'e4m3': 224.0, 'e5m2': 28672.0}                          # engine.hip FP8_TARGET_*: half the largest finite value
-FP8_DRY_PASSES = 5                                                      # engine.hip FP8_DRY_PASSES
+FP8_TARGETS = {'e4m3': 224.0, 'e5m2': 28672.0}                          # engine_internal.h FP8_TARGET_*: half the largest finite value
+FP8_DRY_PASSES = 5                                                      # mrgan_abi.h MRGAN_FP8_DRY_PASSES
 
 
 def fp8_round(x, fmt):
@@ -403,6 +403,45 @@ class Fp8Slots(object):
             self.amax[key] = np.float32(0.0)
 
 
+class _Storage(object):
+    """How the mirror stores what a dense product reads, for quantize None / 'bf16': every tensor through q.  A layer's input
+    or gradient is named by the key of its scaling slot: ('x' | 'g', sub-step kind, layer), ('gx',) / ('gg',) for G2."""
+
+    def __init__(self, mirror):
+        self.m, self.q = mirror, mirror.q
+
+    def fresh(self, v, key, fmt):
+        """the fp32 result v of a product's epilogue, the loss head or the feature-matching kernel"""
+        return self.q(v)
+
+    def stored(self, v, key, fmt):
+        """v is a stored tensor already (xin_0, BN(h1), dpre2 of the generator)"""
+        return v
+
+    def w(self, l):
+        return self.q(self.m.d[2 * l])
+
+    def gw(self):
+        return self.q(self.m.g[4])
+
+
+class _Fp8Storage(_Storage):
+    """quantize 'fp8': the discriminator's dense layers and G2 read fp8 images under the delayed scale of their slot -- one
+    rounding from the fp32 value (no bf16 in between), or from the bf16 tensor where a quantiser pass converts a stored one --
+    and the fp8 weight copies"""
+
+    def fresh(self, v, key, fmt):
+        return self.m.slots.quant(v, key, fmt)
+
+    stored = fresh
+
+    def w(self, l):
+        return self.m.w8[l]
+
+    def gw(self):
+        return self.m.gw8
+
+
 class MRGANMirror(object):
     """train_batch_disc / train_batch_gen in the engine's dataflow.  Same call signatures as MRGANOracle."""
 
@@ -414,9 +453,11 @@ class MRGANMirror(object):
         self.uw = unlabeled_weight
         self.quantize = quantize
         self.q = {None: _ident, 'bf16': bf16_round, 'fp8': bf16_round}[quantize]
-        # fp8: the discriminator's dense products take e4m3 activations / weights and e5m2 gradients (gemm_fp8.hip); the
-        # generator, the loss head and predict_logits stay in the bf16 dataflow
+        # fp8: the discriminator's dense products and G2 take e4m3 activations / weights and e5m2 gradients (gemm_fp8.hip) in
+        # the training sub-steps; the rest of the generator, the loss head and predict_logits stay in the bf16 dataflow
         self.fp8 = quantize == 'fp8'
+        self.plain = _Storage(self)
+        self.store = _Fp8Storage(self) if self.fp8 else self.plain
         if self.fp8:
             self.slots = Fp8Slots()
             self.cal = [False, False]
@@ -434,56 +475,6 @@ class MRGANMirror(object):
         """the generator's second dense layer (the one wide product of the generator) also runs in fp8"""
         self.gw8 = self.slots.quant(bf16_round(self.g[4]), ('gw',), 'e4m3')
 
-    def _disc_fwd8(self, xin0, noise, kind):
-        """one segment through dense 1..5 with e4m3 operands; xin0 = the bf16 noisy input rows"""
-        q, sl = self.q, self.slots
-        nl = len(self.d) // 2
-        xin, masks = [sl.quant(xin0, ('x', kind, 0), 'e4m3')], []
-        a = None
-        for l in range(nl - 1):
-            a = relu(xin[l] @ self.w8[l] + self.d[2 * l + 1])
-            masks.append(a > 0)
-            if l < nl - 2:
-                # packed straight from the fp32 accumulator by the forward epilogue: one rounding (no bf16 in between)
-                xin.append(sl.quant(a + np.asarray(self.sigmas[l + 1], a.dtype) * noise[l + 1], ('x', kind, l + 1), 'e4m3'))
-        return dict(xin=xin, masks=masks, feat=a, feat_q=q(a))
-
-    def _disc_bwd8(self, c, dpre_top, kind, to_input=False):
-        """dX chain with e5m2 gradients; returns the dequantised g8[l], the bias sums, and (to_input) d loss / d x"""
-        q, sl = self.q, self.slots
-        nl = len(self.d) // 2
-        dpre, db = [None] * (nl - 1), [None] * (nl - 1)
-        dpre[nl - 2] = sl.quant(dpre_top, ('g', kind, nl - 2), 'e5m2')
-        for l in range(nl - 2, 0, -1):
-            v = (dpre[l] @ self.w8[l].T) * c['masks'][l - 1]
-            db[l - 1] = v.sum(axis=0)
-            dpre[l - 1] = sl.quant(v, ('g', kind, l - 1), 'e5m2')          # from the dX epilogue's accumulator, one rounding
-        dx = dpre[0] @ self.w8[0].T if to_input else None
-        return dpre, db, dx
-
-    def _disc_grads8(self, x_lab, labels, x_unl, z, n_lab, n_unl, n_fake):
-        q = self.q
-        nl = len(self.d) // 2
-        xf, _ = self._gen_fwd(z, n_fake[0])
-        segs = [self._disc_fwd8(self._stage(x_lab, n_lab[0]), n_lab, 0), self._disc_fwd8(self._stage(x_unl, n_unl[0]), n_unl, 0),
-                self._disc_fwd8(xf, n_fake, 0)]
-        W6, b6 = self.d[-2], self.d[-1]
-        logits = [c['feat_q'] @ W6 + b6 for c in segs]
-        out = disc_losses(logits[0], labels, logits[1], logits[2])
-        dls = disc_loss_grads(logits[0], labels, logits[1], logits[2], self.uw)
-        grads = [np.zeros_like(p) for p in self.d]
-        for c, dl in zip(segs, dls):
-            grads[-2] += c['feat_q'].T @ dl
-            grads[-1] += dl.sum(axis=0)
-            dp = (dl @ W6.T) * (c['feat_q'] > 0)
-            grads[2 * (nl - 2) + 1] += dp.sum(axis=0)
-            dpre, db, _ = self._disc_bwd8(c, dp, 0)            # the loss head packs e5m2 from the fp32 value
-            for l in range(nl - 1):
-                grads[2 * l] += c['xin'][l].T @ dpre[l]
-                if l < nl - 2:
-                    grads[2 * l + 1] += db[l]
-        return out, grads, dict(l_lab=logits[0], l_unl=logits[1], l_fake=logits[2])
-
     def _calibrate(self, kind, fn):
         """first sub-step of a kind: dry passes settle the delayed scales (mrgan_disc_step / mrgan_gen_step)"""
         if self.fp8 and not self.cal[kind]:
@@ -494,7 +485,7 @@ class MRGANMirror(object):
 
     # ---- generator forward (engine: stage z -> G1+stats -> bn_apply -> G2 -> G3(+noise)) ----
     def _gen_fwd(self, z, n0):
-        q = self.q
+        q, st = self.q, self.store
         W1, b1, gamma, beta, W2, b2, W3, b3 = self.g
         zq = q(z)
         h1 = softplus(zq @ q(W1) + b1)
@@ -504,73 +495,73 @@ class MRGANMirror(object):
         rstd = 1.0 / np.sqrt(var + BN_EPS)
         h1q = q(h1)
         scale = gamma * rstd
-        hbn = q(h1q * scale + (beta - mu * scale))
-        if getattr(self, 'fp8', False):
-            hbn = self.slots.quant(hbn, ('gx',), 'e4m3')       # e4m3 copy of BN(h1): operand of G2's forward and weight gradient
-            h2q = q(softplus(hbn @ self.gw8 + b2))
-        else:
-            h2q = q(softplus(hbn @ q(W2) + b2))
+        hbn = st.stored(q(h1q * scale + (beta - mu * scale)), ('gx',), 'e4m3')      # operand of G2's forward and weight gradient
+        h2q = q(softplus(hbn @ st.gw() + b2))
         x = h2q @ q(W3) + b3
         xin = q(x + np.asarray(self.sigmas[0], x.dtype) * n0) if n0 is not None else q(x)
         return xin, dict(zq=zq, h1q=h1q, mu=mu, rstd=rstd, hbn=hbn, h2q=h2q, B=B)
 
-    # ---- discriminator forward over one segment whose (noisy, rounded) first-layer input is xin0 ----
-    def _disc_fwd(self, xin0, noise):
-        q = self.q
+    # ---- discriminator forward over one segment whose (noisy, rounded) first-layer input is xin0; kind: the training sub-step
+    # (0 = D, 1 = G), or None for the evaluation, which stays in the bf16 dataflow ----
+    def _disc_fwd(self, xin0, noise, kind):
+        q, st = self.q, (self.plain if kind is None else self.store)
         nl = len(self.d) // 2
-        xin, masks = [xin0], []
+        xin, masks = [st.stored(xin0, ('x', kind, 0), 'e4m3')], []
         a = None
         for l in range(nl - 1):
-            pre = xin[l] @ q(self.d[2 * l]) + self.d[2 * l + 1]
-            a = relu(pre)
+            a = relu(xin[l] @ st.w(l) + self.d[2 * l + 1])
             masks.append(a > 0)
             if l < nl - 2:
-                xin.append(q(a + np.asarray(self.sigmas[l + 1], a.dtype) * noise[l + 1]) if noise is not None else q(a))
-        feat_q = q(a)
-        return dict(xin=xin, masks=masks, feat=a, feat_q=feat_q)
+                v = a + np.asarray(self.sigmas[l + 1], a.dtype) * noise[l + 1] if noise is not None else a
+                xin.append(st.fresh(v, ('x', kind, l + 1), 'e4m3'))
+        return dict(xin=xin, masks=masks, feat=a, feat_q=q(a))
 
     def _stage(self, x, n0):
         return self.q(x + np.asarray(self.sigmas[0], x.dtype) * n0)
 
-    # dX chain from dpre of the feature layer down to layer `stop`; returns the list of (rounded) dpre_l and bias sums
-    def _disc_bwd(self, c, dpre_top, want_bias):
-        q = self.q
+    # dX chain from the (unrounded) dpre of the feature layer down to layer 0; returns the stored dpre_l, the bias sums
+    # and (to_input) d loss / d x
+    def _disc_bwd(self, c, dpre_top, kind, to_input=False):
+        st = self.store
         nl = len(self.d) // 2
-        dpre = [None] * (nl - 1)
-        db = [None] * (nl - 1)
-        dpre[nl - 2] = dpre_top
+        dpre, db = [None] * (nl - 1), [None] * (nl - 1)
+        dpre[nl - 2] = st.fresh(dpre_top, ('g', kind, nl - 2), 'e5m2')
         for l in range(nl - 2, 0, -1):
-            v = (dpre[l] @ q(self.d[2 * l]).T) * c['masks'][l - 1]
-            if want_bias:
-                db[l - 1] = v.sum(axis=0)
-            dpre[l - 1] = q(v)
-        return dpre, db
+            v = (dpre[l] @ st.w(l).T) * c['masks'][l - 1]
+            db[l - 1] = v.sum(axis=0)
+            dpre[l - 1] = st.fresh(v, ('g', kind, l - 1), 'e5m2')
+        dx = dpre[0] @ st.w(0).T if to_input else None
+        return dpre, db, dx
 
-    def disc_grads(self, x_lab, labels, x_unl, z, n_lab, n_unl, n_fake):
-        if self.fp8:
-            a = (x_lab, labels, x_unl, z, n_lab, n_unl, n_fake)
-            self._calibrate(0, lambda: self._disc_grads8(*a))
-            return self._disc_grads8(*a)
-        q = self.q
+    # loss head and backward of the discriminator's segments: loss_grads(logits) -> d loss / d logits per segment
+    def _disc_param_grads(self, segs, loss_grads):
         nl = len(self.d) // 2
-        xf, _ = self._gen_fwd(z, n_fake[0])
-        segs = [self._disc_fwd(self._stage(x_lab, n_lab[0]), n_lab), self._disc_fwd(self._stage(x_unl, n_unl[0]), n_unl),
-                self._disc_fwd(xf, n_fake)]
         W6, b6 = self.d[-2], self.d[-1]
         logits = [c['feat_q'] @ W6 + b6 for c in segs]
-        out = disc_losses(logits[0], labels, logits[1], logits[2])
-        dls = disc_loss_grads(logits[0], labels, logits[1], logits[2], self.uw)
         grads = [np.zeros_like(p) for p in self.d]
-        for c, dl in zip(segs, dls):
+        for c, dl in zip(segs, loss_grads(logits)):
             grads[-2] += c['feat_q'].T @ dl
             grads[-1] += dl.sum(axis=0)
             dp = (dl @ W6.T) * (c['feat_q'] > 0)
             grads[2 * (nl - 2) + 1] += dp.sum(axis=0)
-            dpre, db = self._disc_bwd(c, q(dp), True)
+            dpre, db, _ = self._disc_bwd(c, dp, 0)
             for l in range(nl - 1):
                 grads[2 * l] += c['xin'][l].T @ dpre[l]
                 if l < nl - 2:
                     grads[2 * l + 1] += db[l]
+        return logits, grads
+
+    def disc_grads(self, x_lab, labels, x_unl, z, n_lab, n_unl, n_fake):
+        a = (x_lab, labels, x_unl, z, n_lab, n_unl, n_fake)
+        self._calibrate(0, lambda: self._disc_grads(*a))
+        return self._disc_grads(*a)
+
+    def _disc_grads(self, x_lab, labels, x_unl, z, n_lab, n_unl, n_fake):
+        xf, _ = self._gen_fwd(z, n_fake[0])
+        segs = [self._disc_fwd(self._stage(x_lab, n_lab[0]), n_lab, 0), self._disc_fwd(self._stage(x_unl, n_unl[0]), n_unl, 0),
+                self._disc_fwd(xf, n_fake, 0)]
+        logits, grads = self._disc_param_grads(segs, lambda lg: disc_loss_grads(lg[0], labels, lg[1], lg[2], self.uw))
+        out = disc_losses(logits[0], labels, logits[1], logits[2])
         return out, grads, dict(l_lab=logits[0], l_unl=logits[1], l_fake=logits[2])
 
     def disc_step(self, *a, **k):
@@ -583,23 +574,12 @@ class MRGANMirror(object):
 
     # supervised step of the NN baseline in the engine's dataflow (engine.hip sup_step)
     def sup_grads(self, x, labels, noise):
-        q = self.q
-        nl = len(self.d) // 2
-        c = self._disc_fwd(self._stage(x, noise[0]), noise)
-        W6, b6 = self.d[-2], self.d[-1]
-        logits = c['feat_q'] @ W6 + b6
-        loss, err, dl = mse_loss_grad(logits, labels)
-        grads = [np.zeros_like(p) for p in self.d]
-        grads[-2] = c['feat_q'].T @ dl
-        grads[-1] = dl.sum(axis=0)
-        dp = (dl @ W6.T) * (c['feat_q'] > 0)
-        grads[2 * (nl - 2) + 1] = dp.sum(axis=0)
-        dpre, db = self._disc_bwd(c, q(dp), True)
-        for l in range(nl - 1):
-            grads[2 * l] = c['xin'][l].T @ dpre[l]
-            if l < nl - 2:
-                grads[2 * l + 1] = db[l]
-        return (loss, err), grads, dict(logits=logits)
+        if self.fp8:
+            raise ValueError("sup_step: the fp8 mode covers the GAN step only")
+        logits, grads = self._disc_param_grads([self._disc_fwd(self._stage(x, noise[0]), noise, 0)],
+                                               lambda lg: [mse_loss_grad(lg[0], labels)[2]])
+        loss, err, _ = mse_loss_grad(logits[0], labels)
+        return (loss, err), grads, dict(logits=logits[0])
 
     def sup_step(self, x, labels, noise):
         out, grads, _ = self.sup_grads(x, labels, noise)
@@ -607,42 +587,28 @@ class MRGANMirror(object):
         return out
 
     def gen_grads(self, x_unl, z, n_fake, n_real):
-        if self.fp8:
-            self._calibrate(1, lambda: self._gen_grads(x_unl, z, n_fake, n_real))
+        self._calibrate(1, lambda: self._gen_grads(x_unl, z, n_fake, n_real))
         return self._gen_grads(x_unl, z, n_fake, n_real)
 
     def _gen_grads(self, x_unl, z, n_fake, n_real):
-        q = self.q
+        q, st = self.q, self.store
         W1, b1, gamma, beta, W2, b2, W3, b3 = self.g
         xf, gc = self._gen_fwd(z, n_fake[0])
-        if self.fp8:
-            cf = self._disc_fwd8(xf, n_fake, 1)
-            cr = self._disc_fwd8(self._stage(x_unl, n_real[0]), n_real, 1)
-        else:
-            cf = self._disc_fwd(xf, n_fake)
-            cr = self._disc_fwd(self._stage(x_unl, n_real[0]), n_real)
+        cf = self._disc_fwd(xf, n_fake, 1)
+        cr = self._disc_fwd(self._stage(x_unl, n_real[0]), n_real, 1)
         B, J = cf['feat'].shape
         diff = cf['feat'].sum(axis=0) / B - cr['feat'].sum(axis=0) / B          # moments of the unrounded features
         loss = np.mean(diff * diff)
         gj = (2.0 / (J * B)) * diff
-        if self.fp8:
-            _, _, v = self._disc_bwd8(cf, np.where(cf['masks'][-1], gj, 0.0), 1, to_input=True)     # fm_kernel: e5m2 from fp32
-        else:
-            dpre, _ = self._disc_bwd(cf, q(np.where(cf['masks'][-1], gj, 0.0)), False)
-            v = dpre[0] @ q(self.d[0]).T                                          # d loss / d x_fake (noise is additive)
+        _, _, v = self._disc_bwd(cf, np.where(cf['masks'][-1], gj, 0.0), 1, to_input=True)     # d loss / d x_fake (noise is additive)
         db3 = v.sum(axis=0)
         dxf = q(v)
         dW3 = gc['h2q'].T @ dxf
         v = (dxf @ q(W3).T) * (-np.expm1(-gc['h2q']))                             # softplus'(pre) = 1 - exp(-h)
         db2 = v.sum(axis=0)
-        dpre2 = q(v)
-        if self.fp8:
-            dpre2 = self.slots.quant(dpre2, ('gg',), 'e5m2')
-            dW2 = gc['hbn'].T @ dpre2
-            v = dpre2 @ self.gw8.T
-        else:
-            dW2 = gc['hbn'].T @ dpre2
-            v = dpre2 @ q(W2).T
+        dpre2 = st.stored(q(v), ('gg',), 'e5m2')
+        dW2 = gc['hbn'].T @ dpre2
+        v = dpre2 @ st.gw().T
         xh = (gc['h1q'] - gc['mu']) * gc['rstd']
         dbeta = v.sum(axis=0)
         dgamma = (v * xh).sum(axis=0)
@@ -662,7 +628,7 @@ class MRGANMirror(object):
         return loss
 
     def predict_logits(self, x):
-        c = self._disc_fwd(self.q(x), None)
+        c = self._disc_fwd(self.q(x), None, None)
         return c['feat_q'] @ self.d[-2] + self.d[-1]
 
     def test_error(self, x, labels):

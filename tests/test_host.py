@@ -144,6 +144,20 @@ def test_tuning_knobs_match_header():
     assert python == header
 
 
+def test_fp8_constants_match_headers():
+    """the mirror's dry-pass count and scaling targets are the engine's: MRGAN_FP8_DRY_PASSES (mrgan_abi.h), FP8_TARGET_E4M3 /
+    FP8_TARGET_E5M2 (engine_internal.h)"""
+    from oracle import mrgan_oracle as O
+    abi = open(os.path.join(ROOT, "include", "mrgan_abi.h")).read()
+    internal = open(os.path.join(ROOT, "mr_gan_amd", "csrc", "engine_internal.h")).read()
+    dry = re.search(r"\bMRGAN_FP8_DRY_PASSES\s*=\s*(\d+)", abi)
+    targets = {m.group(1).lower(): float(m.group(2)) for m in re.finditer(r"\bFP8_TARGET_(E4M3|E5M2)\s*=\s*([0-9.]+)f", internal)}
+    assert dry and O.FP8_DRY_PASSES == int(dry.group(1))
+    assert sorted(targets) == ['e4m3', 'e5m2'] and O.FP8_TARGETS == targets
+    # half the largest finite value of each format
+    assert all(O.FP8_TARGETS[f] == O.FP8_FORMATS[f][2] / 2 for f in targets)
+
+
 def test_default_config_and_workspace_size_without_gpu():
     from mr_gan_amd import engine as E
     cfg = E.default_config(512, 4096)
