@@ -20,63 +20,60 @@ constexpr int CH_ROWS = 64;            // rows per block
 constexpr int CH_THREADS = 512;        // 8 waves: wave w owns columns [32 w, 32 w + 32) of a 256-column pass, all 64 rows
 constexpr int CH_PW = 256;             // output columns per pass (wider layers take several passes over the resident A)
 constexpr int CH_KMAX = 512;           // widest resident activation (reduction length of any product in a chain)
-constexpr int CH_MAX_OPS = 8;
-// LDS map (bytes): two activation images and a 2-stage ring of weight tiles [256 columns][64 k]
-constexpr int CH_BUF0 = 0, CH_BUF0_BYTES = CH_ROWS * CH_KMAX * 2;                  // 64 KiB: up to 512 columns
-constexpr int CH_BUF1 = CH_BUF0 + CH_BUF0_BYTES, CH_BUF1_BYTES = CH_ROWS * CH_PW * 2;   // 32 KiB: up to 256 columns
-constexpr int CH_RING = CH_BUF1 + CH_BUF1_BYTES, CH_STAGE_BYTES = CH_PW * 128;     // 32 KiB per stage
-constexpr int CH_LDS_BYTES = CH_RING + 2 * CH_STAGE_BYTES;                         // 160 KiB: the whole CU
-// the same map for blocks of `rows` rows (64, or 32 for launches with few row blocks): image 0 | image 1 | the 2-stage ring
+constexpr int CH_STAGE_BYTES = CH_PW * 128;      // one ring stage: a weight tile [256 columns][64 k], 32 KiB
+// LDS map (bytes) of a block of `rows` rows (64, or 32 for launches with few row blocks):
+//     image 0 (up to 512 columns) | image 1 (up to 256 columns) | the ring of weight tiles          64 rows: 64 + 32 + 2 x 32 KiB, the whole CU
+// Which image holds what is fixed, and compiled into the kernel:
+//   * product j (0, 1, 2) of a run of three reads image j & 1 and writes the other one; the first A image of every chain
+//     (the inputs of D3, or the feature-matching gradient) is therefore image 0, and the features land in image 1;
+//   * the loss head reads the features in image 1 and writes dL/d(pre5) into image 0, the A image of the first dX product;
+//     the upper half of image 0 is its scratch, and image 0's lower half holds the partial logits until dL/d(pre5) is written;
+//   * chain_fmgrad builds its image in image 0 and keeps the folded moments in image 1, idle until the first epilogue.
 constexpr int chain_buf0(int rows) { return 0; }
 constexpr int chain_buf1(int rows) { return rows * CH_KMAX * 2; }
 constexpr int chain_ring(int rows) { return rows * (CH_KMAX + CH_PW) * 2; }
 constexpr int chain_stages(int rows) { return rows <= 32 ? 3 : 2; }      // ring depth: what fits beside the images in 160 KiB
 constexpr int chain_lds_bytes(int rows) { return chain_ring(rows) + chain_stages(rows) * CH_STAGE_BYTES; }
+constexpr int chain_img(int rows, int i) { return (i & 1) ? chain_buf1(rows) : chain_buf0(rows); }
+constexpr int chain_head_scratch() { return chain_buf0(CH_ROWS) + CH_ROWS * CH_KMAX; }      // (64-row blocks only)
 
-enum { CH_OP_GEMM = 0, CH_OP_HEAD = 1 };
 enum { CH_FWD_RELU = 0, CH_DX_RELU = 1 };
-enum { CH_A_GLOBAL = 0, CH_A_LDS = 1, CH_A_FMGRAD = 2 };
-// the three chains of a training step: op lists [F F F H X X X], [F F F], [X X X] (F forward, H loss head, X dX)
+// the three chains of a training step: [F F F H X X X], [F F F], [X X X] (F forward, H loss head, X dX)
 enum { CH_V_DTAIL = 0, CH_V_GFWD = 1, CH_V_GBWD = 2 };
 // timing experiments (results are wrong): skip the loss head / the copies to HBM / the MFMAs / the weight stream / the epilogue math
 enum { CH_ABL_HEAD = 256, CH_ABL_COPY = 512, CH_ABL_MFMA = 1024, CH_ABL_STREAM = 2048, CH_ABL_EPI = 4096 };
 
+// one dense product: out[rows][N] = epilogue(A[rows][K] Bt[N][K]^T)
 struct ChainOp {
-    int kind;                          // CH_OP_*
-    // ---- CH_OP_GEMM: out[64][N] = epilogue(A[64][K] Bt[N][K]^T) ----
     int K, N, n_valid;                 // padded reduction / output widths (multiples of 64), logical output width
     const __bf16* W;                   // Bt: [N][K], reduction index contiguous (forward: W^T copy; dX: W copy)
-    int a_off, o_off;                  // LDS byte offsets of the A image and of the output image
-    int mode;                          // CH_FWD_RELU | CH_DX_RELU
     const float* bias;                 // forward
     float sigma; uint32_t site;        // forward: out += sigma * N(0,1) (the next layer's GaussianNoise); site of the draw
     __bf16* out; long out_bs; int ldo; // global copy of the output [seg][S][ldo]
-    uint16_t* mask; long mask_bs; int ldm;      // lane-native relu mask (gemm.h): written by CH_FWD_RELU, read by CH_DX_RELU
+    uint16_t* mask; long mask_bs; int ldm;      // lane-native relu mask (gemm.h): written by a forward product, read by a dX product
     float* cs; int ldcs;               // optional column sums of the (unrounded) output: one partial row per (segment, row block)
 };
 
 struct ChainArgs {
     int variant;                       // CH_V_*
-    int nops; ChainOp op[CH_MAX_OPS];
-    int rows, nseg, S;                 // valid rows per segment, segments, segment stride (rows)
+    ChainOp fwd[3];                    // D3 D4 D5 forward (CH_V_DTAIL, CH_V_GFWD)
+    ChainOp dx[3];                     // dX through D5 D4 D3 (CH_V_DTAIL, CH_V_GBWD)
+    int rows, nseg;                    // valid rows per segment, segments
     int block_rows;                    // rows per block: 64, or 32 (CH_V_GFWD / CH_V_GBWD only)
-    int a_kind;                        // how the first A image is produced
-    const __bf16* a; long a_bs; int lda; int a_cols;      // CH_A_GLOBAL: rows of a[seg][S][lda], a_cols (padded) columns
-    // CH_A_FMGRAD: A = relu-mask ? gj : 0 with gj from the feature-matching moments (mr_gan.py:152-154)
+    const __bf16* a; long a_bs; int lda; int a_cols;      // forward chains: the first A image, rows of a[seg][S][lda], a_cols (padded) columns
+    // CH_V_GBWD: the first A image = relu-mask ? gj : 0 with gj from the feature-matching moments (mr_gan.py:152-154)
     FmArgs fm;
     const __bf16* fm_feat; int fm_ldf;                     // features of the generated rows [rows][fm_ldf] (their sign is the relu mask)
-    // CH_OP_HEAD
-    HeadArgs head;
-    int head_f_off, head_scratch_off, head_o_off;         // LDS offsets: features in, scratch, dpre out
+    HeadArgs head;                     // CH_V_DTAIL
     int seg0;                          // noise segment id of segment 0
     uint64_t seed; uint32_t row0; const DevState* st;
     int gauss;                         // layer noise of the forward products: 0 = Irwin-Hall, 1 = true Gaussian (MRGAN_FLAG_GAUSS_NOISE)
     unsigned long long* stamps;        // diagnostic build only (make STAMPS=1): [block][8] cycles per phase
     int ablate;                        // timing experiments only (mrgan_debug_ablate): CH_ABL_* bits
-
 };
 
 int launch_chain(const ChainArgs& a, hipStream_t s);
+int chain_init_attributes();           // the dynamic-LDS limit of every chain kernel: once per handle, outside any stream capture
 
 // ---- device side: the activation image [K/64 k-tiles][ROWS rows][64 k] bf16, 16-byte chunks XOR-swizzled per row (kc_off) ----
 // byte offset of element (row, col) inside an activation image
@@ -97,18 +94,21 @@ __device__ __forceinline__ int img_elem_off(const int (&obase)[4], int mi, int r
     return obase[((r >> 1) & 1) | (((r >> 2) & 1) << 1)] + (mi * 32 + acc_row(r, 0)) * 128;
 }
 
-// Stand-alone loss head on the matrix cores for what the chain cannot hold: feature layers wider than 256 columns (BASELINE
-// configs[4]: 4096), and more than 8 classes (class pitch 32) at any multiple of 256 columns: the three products of chain_head
-// over 64-row blocks, the feature dimension walked in 256-column chunks.
-// feat % 256 == 0; bf16 features; segment kinds LAB / UNL / FAKE (training); mask = the feature layer's lane-native relu mask.
-struct HeadWideArgs {
-    HeadArgs h;
-    const uint16_t* mask; long mask_bs; int ldm;
-    __bf16* w6c; __bf16* w6r;          // scratch: the bf16 addends of W6, class-major [3][KP][feat] and row-major [3][feat][KP] (KP = h.ldw)
-};
-constexpr int HEAD_WIDE_ROWS = CH_ROWS;
-int launch_w6_split(const HeadWideArgs& a, hipStream_t s);       // first: the addends of the current W6
-int launch_head_wide(const HeadWideArgs& a, hipStream_t s);
-int chain_init_attributes();
+// LDS writes of every wave visible to every wave; VMEM left in flight
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+// copy a [ROWS rows][256 columns] bf16 LDS image (columns col0 .. of the global tensor) out with 16-byte stores
+template <int ROWS = CH_ROWS>
+__device__ __forceinline__ void copy_out(const char* img, __bf16* out, int ldo, int col0, int ncols, int rows_valid, int t) {
+#pragma unroll
+    for (int u = 0; u < ROWS * CH_PW / 8 / CH_THREADS; ++u) {
+        const int q = t + CH_THREADS * u, r = q >> 5, cch = q & 31;
+        if (r < rows_valid && col0 + cch * 8 < ncols)
+            *(u32x4*)(out + (long)r * ldo + col0 + cch * 8) = *(const u32x4*)(img + (cch >> 3) * (ROWS * 128) + kc_off(r, cch & 7));
+    }
+}
 
 }  // namespace mrgan

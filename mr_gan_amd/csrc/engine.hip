@@ -333,24 +333,23 @@ int disc_fwd_train(mrgan_handle* h, int kind, int nb, bool fm_sums, int x0_slot,
 }
 
 // ---- row-block chain launches for the tail D3..D5 (+ head) of the discriminator (gemm_chain.hip) ----
-ChainOp chain_fwd_op(mrgan_handle* h, int l, int a_off, int o_off, bool fm_sums) {
+ChainOp chain_fwd_op(mrgan_handle* h, int l, bool fm_sums) {
     const Dense& L = h->d[l];
     ChainOp o;
     memset(&o, 0, sizeof o);
-    o.kind = CH_OP_GEMM; o.K = L.Kp; o.N = L.Np; o.n_valid = L.N; o.W = L.W->wt16; o.a_off = a_off; o.o_off = o_off;
-    o.mode = CH_FWD_RELU; o.bias = L.b->p; o.sigma = l < 4 ? h->cfg.sigma[l + 1] : 0.f; o.site = (uint32_t)(l + 1);
+    o.K = L.Kp; o.N = L.Np; o.n_valid = L.N; o.W = L.W->wt16;
+    o.bias = L.b->p; o.sigma = l < 4 ? h->cfg.sigma[l + 1] : 0.f; o.site = (uint32_t)(l + 1);
     o.out = (__bf16*)(l < 4 ? h->xin[l + 1] : h->feat); o.out_bs = (long)h->S * L.Np; o.ldo = L.Np;
     o.mask = h->mask[l]; o.mask_bs = mask_pitch(h->S, h->ldm[l]); o.ldm = h->ldm[l];
     if (fm_sums) { o.cs = h->cs_f; o.ldcs = L.Np; }
     return o;
 }
 // dX of layer l: dpre[l] -> dpre[l-1]
-ChainOp chain_dx_op(mrgan_handle* h, int l, int a_off, int o_off, bool bias_sums) {
+ChainOp chain_dx_op(mrgan_handle* h, int l, bool bias_sums) {
     const Dense& L = h->d[l];
     ChainOp o;
     memset(&o, 0, sizeof o);
-    o.kind = CH_OP_GEMM; o.K = L.Np; o.N = L.Kp; o.n_valid = h->d[l - 1].N; o.W = L.W->w16; o.a_off = a_off; o.o_off = o_off;
-    o.mode = CH_DX_RELU;
+    o.K = L.Np; o.N = L.Kp; o.n_valid = h->d[l - 1].N; o.W = L.W->w16;
     o.out = (__bf16*)h->dpre[l - 1]; o.out_bs = (long)h->S * L.Kp; o.ldo = L.Kp;
     o.mask = h->mask[l - 1]; o.mask_bs = mask_pitch(h->S, h->ldm[l - 1]); o.ldm = h->ldm[l - 1];
     if (bias_sums) { o.cs = h->cs_db[l - 1]; o.ldcs = L.Kp; }
@@ -385,8 +384,8 @@ int run_chain(mrgan_handle* h, const ChainArgs& c0, double flops, hipStream_t s)
         hipMemcpy(hs.data(), stamps, hs.size() * 8, hipMemcpyDeviceToHost);
         double tot[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int nb = 0;
         for (int b = 0; b < 4096; ++b) if (hs[b * 8]) { ++nb; for (int i = 0; i < 8; ++i) tot[i] += (double)hs[b * 8 + i]; }
-        if (nb) fprintf(stderr, "chain stamps (kcycles per block, %d blocks, %d ops): prologue %.1f | pass setup %.1f | head %.1f | tile wait %.1f | barrier %.1f | "
-                        "issue+reads+mfma %.1f | epilogue %.1f | image barrier+copy-out %.1f\n", nb, c.nops, tot[0] / nb / 1e3, tot[1] / nb / 1e3,
+        if (nb) fprintf(stderr, "chain stamps (kcycles per block, %d blocks): prologue %.1f | pass setup %.1f | head %.1f | tile wait %.1f | barrier %.1f | "
+                        "issue+reads+mfma %.1f | epilogue %.1f | image barrier+copy-out %.1f\n", nb, tot[0] / nb / 1e3, tot[1] / nb / 1e3,
                         tot[2] / nb / 1e3, tot[3] / nb / 1e3, tot[4] / nb / 1e3, tot[5] / nb / 1e3, tot[6] / nb / 1e3, tot[7] / nb / 1e3);
     }
 #endif
@@ -460,10 +459,10 @@ ChainArgs chain_args(mrgan_handle* h, int variant, int nseg, int block_rows) {
     ChainArgs c;
     memset(&c, 0, sizeof c);
     c.variant = variant; c.block_rows = block_rows;
-    c.rows = h->B; c.nseg = nseg; c.S = h->S; c.seg0 = 0;
+    c.rows = h->B; c.nseg = nseg; c.seg0 = 0;
     c.seed = h->cfg.seed; c.row0 = (uint32_t)(h->cfg.rank * h->B); c.st = h->state + h->cur; c.gauss = h->gauss;
     c.ablate = h->ablate;
-    if (variant != CH_V_GBWD) { c.a_kind = CH_A_GLOBAL; c.a = (const __bf16*)h->xin[2]; c.a_bs = (long)h->S * h->d[2].Kp; c.lda = h->d[2].Kp; c.a_cols = h->d[2].Kp; }
+    if (variant != CH_V_GBWD) { c.a = (const __bf16*)h->xin[2]; c.a_bs = (long)h->S * h->d[2].Kp; c.lda = h->d[2].Kp; c.a_cols = h->d[2].Kp; }
     return c;
 }
 
@@ -486,18 +485,11 @@ int disc_head(mrgan_handle* h, const mrgan_disc_args* a, hipStream_t s) {
     if (h->dtail_chain()) {
         // D3 D4 D5 forward -> loss head -> dX through D5 D4 D3, one launch: the rows of a block never leave its CU
         ChainArgs c = chain_args(h, CH_V_DTAIL, 3, CH_ROWS);
-        c.op[0] = chain_fwd_op(h, 2, CH_BUF0, CH_BUF1, false);
-        c.op[1] = chain_fwd_op(h, 3, CH_BUF1, CH_BUF0, false);
-        c.op[2] = chain_fwd_op(h, 4, CH_BUF0, CH_BUF1, false);
         // the relu masks of D3 .. D5 never leave the launch's registers (their dX products follow in the same launch, and
         // nothing else reads them in a D sub-step): no copies to HBM
-        for (int i = 0; i < 3; ++i) c.op[i].mask = nullptr;
-        c.op[3].kind = CH_OP_HEAD;
-        c.head = hd; c.head_f_off = CH_BUF1; c.head_o_off = CH_BUF0; c.head_scratch_off = CH_BUF0 + CH_BUF0_BYTES / 2;
-        c.op[4] = chain_dx_op(h, 4, CH_BUF0, CH_BUF1, true);
-        c.op[5] = chain_dx_op(h, 3, CH_BUF1, CH_BUF0, true);
-        c.op[6] = chain_dx_op(h, 2, CH_BUF0, CH_BUF1, true);
-        c.nops = 7;
+        for (int i = 0; i < 3; ++i) { c.fwd[i] = chain_fwd_op(h, 2 + i, false); c.fwd[i].mask = nullptr; }
+        c.head = hd;
+        for (int i = 0; i < 3; ++i) c.dx[i] = chain_dx_op(h, 4 - i, true);
         h->head_nblk = 3 * ceil_div(h->B, CH_ROWS);
         return run_chain(h, c, chain_flops(h, c, true), s);
     }
@@ -576,11 +568,7 @@ int fm_parts(const mrgan_handle* h) { return h->use_chain ? ceil_div(h->B, chain
 // D3 D4 D5 forward over (generated, real) rows + the feature-matching column sums, one launch
 int gen_chain_fwd(mrgan_handle* h, hipStream_t s) {
     ChainArgs c = chain_args(h, CH_V_GFWD, 2, chain_block_rows(h, 2));
-    const int b0 = chain_buf0(c.block_rows), b1 = chain_buf1(c.block_rows);
-    c.op[0] = chain_fwd_op(h, 2, b0, b1, false);
-    c.op[1] = chain_fwd_op(h, 3, b1, b0, false);
-    c.op[2] = chain_fwd_op(h, 4, b0, b1, true);       // + the feature-matching column sums (one partial row per row block)
-    c.nops = 3;
+    for (int i = 0; i < 3; ++i) c.fwd[i] = chain_fwd_op(h, 2 + i, i == 2);      // D5: + the feature-matching column sums (one partial row per row block)
     return run_chain(h, c, chain_flops(h, c, false), s);
 }
 
@@ -600,12 +588,8 @@ int fm_grad(mrgan_handle* h, hipStream_t s) {
         return 0;
     }
     ChainArgs c = chain_args(h, CH_V_GBWD, 1, chain_block_rows(h, 1));
-    const int b0 = chain_buf0(c.block_rows), b1 = chain_buf1(c.block_rows);
-    c.a_kind = CH_A_FMGRAD; c.fm = f; c.fm_feat = (const __bf16*)h->feat; c.fm_ldf = h->Fp;
-    c.op[0] = chain_dx_op(h, 4, b0, b1, false);
-    c.op[1] = chain_dx_op(h, 3, b1, b0, false);
-    c.op[2] = chain_dx_op(h, 2, b0, b1, false);
-    c.nops = 3;
+    c.fm = f; c.fm_feat = (const __bf16*)h->feat; c.fm_ldf = h->Fp;
+    for (int i = 0; i < 3; ++i) c.dx[i] = chain_dx_op(h, 4 - i, false);
     return run_chain(h, c, chain_flops(h, c, false), s);
 }
 

@@ -15,6 +15,7 @@
 #include "../../include/mrgan_debug.h"
 #include "aux_kernels.h"
 #include "chain.h"
+#include "head_wide.h"
 #include "logmel.h"
 #include "gemm.h"
 
@@ -124,7 +125,7 @@ struct mrgan_handle {
     int KP;                              // class pitch (aux_kernels.h): columns of W6 / b6 / logits / the head's partial rows
     bool chain_ok, use_chain;            // the 256-wide tail of the discriminator runs as row-block chain launches (gemm_chain.hip)
     bool dtail_chain() const { return use_chain && KP == KMAX; }   // ... the D sub-step's too: its head is an 8-class kernel
-    bool head_wide_ok, head_wide; __bf16 *w6c, *w6r;   // feature layers wider than the chain holds, or more than 8 classes: the stand-alone MFMA loss head (chain.h: HeadWideArgs)
+    bool head_wide_ok, head_wide; __bf16 *w6c, *w6r;   // feature layers wider than the chain holds, or more than 8 classes: the stand-alone MFMA loss head (head_wide.h: HeadWideArgs)
     int tune_kc_cfg, tune_bits, tune_pair_gen;      // mrgan_set_tuning
     int ablate;                                      // mrgan_debug_ablate (timing experiments)
     AdamTile *tiles_g_dev, *tiles_d_dev; int ntiles_g, ntiles_d;

@@ -381,7 +381,7 @@ int mrgan_create(const mrgan_config* cfg, void* workspace, size_t bytes, mrgan_s
     h->pair_gen = h->gen_ready = 0; h->pair_g = nullptr; h->real_staged = 0;
     h->tune_kc_cfg = -1; h->tune_bits = 0; h->tune_pair_gen = 1; h->ablate = 0;
     h->head_nblk = 0; h->fp8_cal[0] = h->fp8_cal[1] = 0;
-    if (init_kernel_attributes() != 0 || chain_init_attributes() != 0) { if (h->own_ws) hipFree(h->ws); delete h; return fail(-10, "hipFuncSetAttribute failed"); }
+    if (init_kernel_attributes() != 0 || chain_init_attributes() != 0 || head_wide_init_attributes() != 0) { if (h->own_ws) hipFree(h->ws); delete h; return fail(-10, "hipFuncSetAttribute failed"); }
 #define CREATE_CHK(x)                                           \
     do {                                                        \
         if ((x) != hipSuccess) {                                \

@@ -19,11 +19,6 @@
 namespace mrgan {
 namespace {
 
-__device__ __forceinline__ void lds_barrier() {          // LDS writes of every wave visible to every wave; VMEM left in flight
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 // wait until at most n of this wave's vector-memory operations are outstanding (they retire in issue order)
 __device__ __forceinline__ void wait_vm(int n) {
     switch (n) {
@@ -36,9 +31,20 @@ __device__ __forceinline__ void wait_vm(int n) {
     }
 }
 
+// per-phase cycle counters of the diagnostic build (make STAMPS=1: [block][8] to ChainArgs::stamps); empty otherwise, and
+// passed along all the same
 #ifdef MRGAN_STAMPS
-#define CH_STAMP(i) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); st_acc[i] += n_ - st_prev; st_prev = n_; } while (0)
+struct Stamps {
+    unsigned long long acc[8], prev;
+    __device__ void start() { for (int i = 0; i < 8; ++i) acc[i] = 0; prev = __builtin_amdgcn_s_memtime(); }
+    __device__ void store(unsigned long long* out) const { if (out) for (int i = 0; i < 8; ++i) out[(long)blockIdx.x * 8 + i] = acc[i]; }
+};
+#define CH_STAMP(i) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); st.acc[i] += n_ - st.prev; st.prev = n_; } while (0)
 #else
+struct Stamps {
+    __device__ void start() {}
+    __device__ void store(unsigned long long*) const {}
+};
 #define CH_STAMP(i)
 #endif
 
@@ -63,17 +69,6 @@ __device__ __forceinline__ void btile_setup(BTile& b, const __bf16* W, int K, in
 __device__ __forceinline__ void issue_btile(const BTile& b, int pass, int kt, char* stage, int wave) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) glds16(b.rs, stage + (wave * 4 + i) * 1024, b.voff[i] + pass * b.pass_bytes, kt * 128);
-}
-
-// copy a [64 rows][256 columns] bf16 LDS image (columns col0 .. of the global tensor) out with 16-byte stores
-template <int ROWS = CH_ROWS>
-__device__ __forceinline__ void copy_out(const char* img, __bf16* out, int ldo, int col0, int ncols, int rows_valid, int t) {
-#pragma unroll
-    for (int u = 0; u < ROWS * CH_PW / 8 / CH_THREADS; ++u) {
-        const int q = t + CH_THREADS * u, r = q >> 5, cch = q & 31;
-        if (r < rows_valid && col0 + cch * 8 < ncols)
-            *(u32x4*)(out + (long)r * ldo + col0 + cch * 8) = *(const u32x4*)(img + (cch >> 3) * (ROWS * 128) + kc_off(r, cch & 7));
-    }
 }
 
 // Shared state of the weight-tile stream of one block (all wave-uniform)
@@ -133,9 +128,9 @@ __device__ __forceinline__ void head_prefetch(const ChainArgs& a, HeadInputs& hi
 __device__ __forceinline__ void chain_head(const ChainArgs& a, char* lds, Stream& sm, const HeadInputs& hi, const uint32_t (&mw)[2][2], int seg,
                                            int rb, int nrb, int row_blk, int rows_valid, int t) {
     const HeadArgs& h = a.head;
-    const char* fimg = lds + a.head_f_off;
-    char* oimg = lds + a.head_o_off;
-    __bf16* w6t = (__bf16*)(lds + a.head_scratch_off);        // [3][KMAX][CH_PW]
+    const char* fimg = lds + chain_img(CH_ROWS, 1);           // the features: the third forward product's output (chain.h)
+    char* oimg = lds + chain_img(CH_ROWS, 0);                 // dL/d(pre5): the first dX product's A image
+    __bf16* w6t = (__bf16*)(lds + chain_head_scratch());      // [3][KMAX][CH_PW]
     __bf16* dl_rc = w6t + 3 * KMAX * CH_PW;                   // [3][CH_ROWS][KMAX]   dlogits addends, row-major
     __bf16* dl_t = dl_rc + 3 * CH_ROWS * KMAX;                // [3][KMAX][CH_ROWS]   ... class-major
     float* red = (float*)(dl_t + 3 * KMAX * CH_ROWS);         // [3 + KMAX][CH_ROWS]  per-row loss terms and dlogits (fp32)
@@ -247,11 +242,7 @@ __device__ __forceinline__ void chain_head(const ChainArgs& a, char* lds, Stream
 // feature-matching gradient as the first A image (mr_gan.py:152-154): dL/d(pre5) = relu-mask ? 2/(J B) (m_gen - m_real) : 0
 // ------------------------------------------------------------------------------------------------------------------
 template <int ROWS>
-__device__ __forceinline__ void chain_fmgrad(const ChainArgs& a, char* lds, int a_off, int rb, int row_blk, int rows_valid, int t
-#ifdef MRGAN_STAMPS
-                                             , unsigned long long (&st_acc)[8], unsigned long long& st_prev
-#endif
-) {
+__device__ __forceinline__ void chain_fmgrad(const ChainArgs& a, char* lds, int rb, int row_blk, int rows_valid, int t, Stamps& st) {
     const FmArgs& f = a.fm;
     // the stored features of this block's rows (their sign is relu'(pre5), used at the end): requested first, so that their round
     // trip runs beside the fold of the partial sums instead of behind it
@@ -263,7 +254,7 @@ __device__ __forceinline__ void chain_fmgrad(const ChainArgs& a, char* lds, int 
         const bool ok = r < rows_valid && c0 < f.feat;
         fv[u] = *(const bf16x8*)(a.fm_feat + (long)(row_blk + (ok ? r : 0)) * a.fm_ldf + (ok ? c0 : 0));
     }
-    float* gj = (float*)(lds + a.op[0].o_off);               // 9 KiB in the first product's output image: idle until its epilogue (both ring stages are in flight)
+    float* gj = (float*)(lds + chain_img(ROWS, 1));          // 9 KiB in the first product's output image: idle until its epilogue (both ring stages are in flight)
     float* scr = gj + CH_PW;                                  // [8][256]
     const float* cs_real = f.cs + (long)f.npart_fake * f.ldcs;
     // fold the per-row-block partial sums: thread <-> (4 columns, every 8th partial row), 64 partial rows of both streams per
@@ -316,7 +307,7 @@ __device__ __forceinline__ void chain_fmgrad(const ChainArgs& a, char* lds, int 
     }
     __syncthreads();
     CH_STAMP(2);
-    char* img = lds + a_off;
+    char* img = lds + chain_img(ROWS, 0);
     // thread <-> (row, 8 columns): one 16-byte chunk of the image.  relu'(pre5) comes from the stored features of the
     // generated rows (f > 0 <=> pre5 > 0; bf16 keeps every positive value positive): one unconditional 16-byte load per chunk
     // from a clamped row, all four in flight together.  (Decoding the lane-native mask words here instead costs 8 scattered
@@ -335,23 +326,20 @@ __device__ __forceinline__ void chain_fmgrad(const ChainArgs& a, char* lds, int 
     CH_STAMP(7);        // (the image's copy to HBM is deferred to the end of the first product's k-loop: see Stream)
 }
 
-// one dense product of the chain on the block's rows.  MODE is compile-time; `bias` (forward) and `mw` (the relu-mask words
+// one dense product of the chain on the block's rows.  MODE and J, the product's place in its run of three (which decides its
+// images: chain.h), are compile-time; `bias` (forward) and `mw` (the relu-mask words
 // of the output tile: read by dX, returned by forward) live in registers, loaded or produced before this call.
 // GAUSS: forward noise from the true-Gaussian generator (common.h: gauss_block; rowhash[] then holds row-pair hashes)
-template <int MODE, int MI, bool GAUSS>
+template <int MODE, int J, int MI, bool GAUSS>
 __device__ __forceinline__ void chain_gemm(const ChainArgs& a, const ChainOp& op, const __bf16* nextW, const int nextK, const int nextN,
                                            char* lds, Stream& sm, const float bias,
                                            uint32_t (&mw)[2][MI], const int seg, const int nrb, const int rb, const int row_blk,
-                                           const int rows_valid, const uint32_t iter, const i32x4 hfrag, const int t
-#ifdef MRGAN_STAMPS
-                                           , unsigned long long (&st_acc)[8], unsigned long long& st_prev
-#endif
-) {
+                                           const int rows_valid, const uint32_t iter, const i32x4 hfrag, const int t, Stamps& st) {
     const int lane = t & 63, lc = lane & 31, lh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     constexpr bool fwd = MODE == CH_FWD_RELU;
-    constexpr int ROWS = 32 * MI, NS = chain_stages(ROWS);
-    const int K = op.K, N = op.N, a_off = op.a_off, o_off = op.o_off;
+    constexpr int ROWS = 32 * MI, NS = chain_stages(ROWS), a_off = chain_img(ROWS, J), o_off = chain_img(ROWS, J + 1);
+    const int K = op.K, N = op.N;
     const int npass = (N + CH_PW - 1) / CH_PW, nk = K / 64;
     const bool noisy = fwd && op.sigma > 0.f;
     uint32_t rowhash[MI];
@@ -557,13 +545,7 @@ __device__ __forceinline__ void load_mask_words(const ChainArgs& a, const ChainO
     }
 }
 
-#ifdef MRGAN_STAMPS
-#define CH_ST_ARGS , st_acc, st_prev
-#else
-#define CH_ST_ARGS
-#endif
-
-// VARIANT: the three chains of one training step (chain.h).  The op list is fixed per variant, so the loop over products is
+// VARIANT: the three chains of one training step (chain.h).  The list of products is fixed per variant, so the loop over products is
 // unrolled at compile time: epilogue inputs are loaded once at the top (before the weight stream loads the memory
 // pipeline), relu masks of products whose forward ran in this launch never leave registers, and no per-op descriptor
 // reload sits between two products.
@@ -580,9 +562,8 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
     const int seg = blockIdx.x / nrb, rb = blockIdx.x - seg * nrb;
     const int row_blk = rb * ROWS, rows_valid = min(ROWS, a.rows - row_blk);
 
-#ifdef MRGAN_STAMPS
-    unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev = __builtin_amdgcn_s_memtime();
-#endif
+    Stamps st;
+    st.start();
     // Keras iteration of this sub-step (noise key): loaded before the weight stream starts and pinned in an SGPR -- sunk to its
     // first use, the load would sit behind a vmcnt(0) that also drains the weight-tile DMA
     uint32_t iter = a.st ? __builtin_amdgcn_readfirstlane((int)a.st->iter) : 0u;
@@ -597,19 +578,19 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
         for (int mi = 0; mi < MI; ++mi) { mwA[p_][mi] = 0u; mwB[p_][mi] = 0u; mwC[p_][mi] = 0u; }
     if constexpr (VARIANT != CH_V_GBWD) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) { const float bv = a.op[i].bias[min(col0, a.op[i].n_valid - 1)]; bias[i] = col0 < a.op[i].n_valid ? bv : 0.f; }
+        for (int i = 0; i < 3; ++i) { const float bv = a.fwd[i].bias[min(col0, a.fwd[i].n_valid - 1)]; bias[i] = col0 < a.fwd[i].n_valid ? bv : 0.f; }
     }
-    if constexpr (VARIANT == CH_V_DTAIL) load_mask_words<MI>(a, a.op[6], mwC, seg, row_blk, wave, lc, lh);      // dX through D3 needs D2's mask
+    if constexpr (VARIANT == CH_V_DTAIL) load_mask_words<MI>(a, a.dx[2], mwC, seg, row_blk, wave, lc, lh);      // dX through D3 needs D2's mask
     HeadInputs hin;
     if constexpr (VARIANT == CH_V_DTAIL) head_prefetch(a, hin, seg, row_blk, rows_valid, t);
     if constexpr (VARIANT == CH_V_GBWD) {
-        load_mask_words<MI>(a, a.op[0], mwA, seg, row_blk, wave, lc, lh);
-        load_mask_words<MI>(a, a.op[1], mwB, seg, row_blk, wave, lc, lh);
-        load_mask_words<MI>(a, a.op[2], mwC, seg, row_blk, wave, lc, lh);
+        load_mask_words<MI>(a, a.dx[0], mwA, seg, row_blk, wave, lc, lh);
+        load_mask_words<MI>(a, a.dx[1], mwB, seg, row_blk, wave, lc, lh);
+        load_mask_words<MI>(a, a.dx[2], mwC, seg, row_blk, wave, lc, lh);
     }
 
     // ---- first A image ----
-    const int a0_off = a.op[0].a_off;
+    constexpr int a0_off = chain_img(ROWS, 0);
     if constexpr (VARIANT != CH_V_GBWD) {
         const __bf16* src = a.a + (long)seg * a.a_bs;
         const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, (int)((long)a.rows * a.lda * 2), 0x00020000);
@@ -627,8 +608,9 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
     constexpr int AHEAD = 2;       // tiles in flight (see chain_gemm)
     sm.gtile = 0; sm.cp_img = nullptr; sm.inflight = AHEAD;
     {
+        const ChainOp& first = VARIANT == CH_V_GBWD ? a.dx[0] : a.fwd[0];
         BTile b0;
-        btile_setup(b0, a.op[0].W, a.op[0].K, a.op[0].N, wave, lane);
+        btile_setup(b0, first.W, first.K, first.N, wave, lane);
 #pragma unroll
         for (int i = 0; i < AHEAD; ++i) issue_btile(b0, 0, i, lds + chain_ring(ROWS) + i * CH_STAGE_BYTES, wave);
     }
@@ -637,395 +619,91 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
         __builtin_amdgcn_s_barrier();      // ... everyone's: the k-loops below run without workgroup barriers
         asm volatile("" ::: "memory");
     } else {
-        chain_fmgrad<ROWS>(a, lds, a0_off, rb, row_blk, rows_valid, t CH_ST_ARGS);      // (ends with a workgroup barrier)
+        chain_fmgrad<ROWS>(a, lds, rb, row_blk, rows_valid, t, st);      // (ends with a workgroup barrier)
         sm.cp_img = lds + a0_off; sm.cp_out = (__bf16*)a.fm.dpre + (long)row_blk * a.fm.ldd;
         sm.cp_ldo = a.fm.ldd; sm.cp_col0 = 0; sm.cp_ncols = a.fm.feat;
     }
     CH_STAMP(0);                   // prologue (epilogue inputs, first tile issue, A image)
 
     const i32x4 hfrag = hadamard_frag(lane);
-    // the op index goes through an opaque asm so that the descriptor's scalar loads happen at the product's start: hoisted to
+    // the product's index goes through an opaque asm so that the descriptor's scalar loads happen at the product's start: hoisted to
     // the top of the kernel (what hipcc does with a constant index) seven descriptors overflow the SGPR file and every
     // pass pays ~2 k cycles of spill traffic
     auto opq = [](int i) { asm volatile("" : "+s"(i)); return i; };
     // ... and the descriptor is copied as a whole (wide scalar loads, one wait) instead of field by field at the points of use
-    // NEXT: index of the product that follows (-1: none) -- its first weight tile is issued during this product's last k-tile
-#define CH_GEMM(MODE, I, NEXT, BIAS, MW) do { const ChainOp op_ = a.op[opq(I)];                                                          \
+    // OPS[J]: the product (fwd or dx: its direction); NOPS[NEXT]: the product that follows (NEXT = -1: none) -- its first weight
+    // tile is issued during this product's last k-tile
+#define CH_GEMM(OPS, J, NOPS, NEXT, BIAS, MW) do { const ChainOp op_ = a.OPS[opq(J)];                                                    \
         const int nx_ = opq(NEXT < 0 ? 0 : NEXT);                                                                                      \
-        chain_gemm<MODE, MI, GAUSS>(a, op_, NEXT < 0 ? nullptr : a.op[nx_].W, a.op[nx_].K, a.op[nx_].N, lds, sm, BIAS, MW, seg, nrb, rb, row_blk,  \
-                         rows_valid, iter, hfrag, t CH_ST_ARGS); } while (0)
+        chain_gemm<CH_GEMM_MODE_##OPS, J, MI, GAUSS>(a, op_, NEXT < 0 ? nullptr : a.NOPS[nx_].W, a.NOPS[nx_].K, a.NOPS[nx_].N, lds, sm, BIAS, MW,   \
+                         seg, nrb, rb, row_blk, rows_valid, iter, hfrag, t, st); } while (0)
+    constexpr int CH_GEMM_MODE_fwd = CH_FWD_RELU, CH_GEMM_MODE_dx = CH_DX_RELU;
     if constexpr (VARIANT == CH_V_DTAIL) {
         // D3 D4 D5 forward: the masks of D3 / D4 stay in registers for the way back
         uint32_t mw4[2][MI];
-        CH_GEMM(CH_FWD_RELU, 0, 1, bias[0], mwB);
-        CH_GEMM(CH_FWD_RELU, 1, 2, bias[1], mwA);
-        CH_GEMM(CH_FWD_RELU, 2, 4, bias[2], mw4);
+        CH_GEMM(fwd, 0, fwd, 1, bias[0], mwB);
+        CH_GEMM(fwd, 1, fwd, 2, bias[1], mwA);
+        CH_GEMM(fwd, 2, dx, 0, bias[2], mw4);
         CH_STAMP(1);               // (the feature image is complete: chain_gemm ended with the image barrier; the weight tile in
                                    //  flight lands in the ring, which the head does not touch)
         if constexpr (MI == 2) { if (!(a.ablate & CH_ABL_HEAD)) chain_head(a, lds, sm, hin, mw4, seg, rb, nrb, row_blk, rows_valid, t); }
         CH_STAMP(2);               // loss head
-        CH_GEMM(CH_DX_RELU, 4, 5, 0.f, mwA);       // dX through D5 * relu'(D4)
-        CH_GEMM(CH_DX_RELU, 5, 6, 0.f, mwB);       // dX through D4 * relu'(D3)
-        CH_GEMM(CH_DX_RELU, 6, -1, 0.f, mwC);       // dX through D3 * relu'(D2)
+        CH_GEMM(dx, 0, dx, 1, 0.f, mwA);       // dX through D5 * relu'(D4)
+        CH_GEMM(dx, 1, dx, 2, 0.f, mwB);       // dX through D4 * relu'(D3)
+        CH_GEMM(dx, 2, dx, -1, 0.f, mwC);      // dX through D3 * relu'(D2)
     } else if constexpr (VARIANT == CH_V_GFWD) {
         uint32_t mwx[2][MI];
-        CH_GEMM(CH_FWD_RELU, 0, 1, bias[0], mwx);
-        CH_GEMM(CH_FWD_RELU, 1, 2, bias[1], mwx);
-        CH_GEMM(CH_FWD_RELU, 2, -1, bias[2], mwx);
+        CH_GEMM(fwd, 0, fwd, 1, bias[0], mwx);
+        CH_GEMM(fwd, 1, fwd, 2, bias[1], mwx);
+        CH_GEMM(fwd, 2, fwd, -1, bias[2], mwx);
     } else {
-        CH_GEMM(CH_DX_RELU, 0, 1, 0.f, mwA);
-        CH_GEMM(CH_DX_RELU, 1, 2, 0.f, mwB);
-        CH_GEMM(CH_DX_RELU, 2, -1, 0.f, mwC);
+        CH_GEMM(dx, 0, dx, 1, 0.f, mwA);
+        CH_GEMM(dx, 1, dx, 2, 0.f, mwB);
+        CH_GEMM(dx, 2, dx, -1, 0.f, mwC);
     }
 #undef CH_GEMM
     if (!(a.ablate & CH_ABL_COPY)) flush_copy<ROWS>(sm, rows_valid, t);      // the last image
-#ifdef MRGAN_STAMPS
-    if (a.stamps && t == 0)
-        for (int i = 0; i < 8; ++i) a.stamps[(long)blockIdx.x * 8 + i] = st_acc[i];
-#endif
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Stand-alone loss head for wide feature layers (chain.h: HeadWideArgs).  The same three MFMA products as chain_head, with the
-// feature dimension walked in chunks of 256 columns: the block's 64 rows x 256 features arrive by LDS-DMA into one of two
-// images (the next chunk is in flight while the current one is consumed), wave w owns features [32 w, 32 w + 32) of a chunk.
-//   pass 1 (chunks ascending): logits partial products, accumulated over ALL chunks in the wave's registers
-//   row phase (wave 0): losses, error, dlogits as bf16 addends
-//   pass 2 (chunks descending: the last chunk is still resident): dL/d(pre5) of the chunk -> output images -> HBM, dW6^T
-// W6 enters as bf16 addends prepared once per launch by w6_split_kernel (class-major for the logits' B operand, row-major for
-// dL/d(pre5)'s), so a fragment is one 16-byte load from a 200 KB array that stays in L2.
-// Q8: dL/d(pre5) leaves as the two e5m2 images the fp8 products read (row-major and transposed), packed from the accumulators:
-// a lane's four consecutive rows of one column are one dword of the transposed image, the row-major dword comes from a 4 x 4
-// byte transpose inside the lane quad (gemm.h does the same in the fp8 epilogues); both images are assembled in LDS and leave
-// as 16-byte stores.  Otherwise dL/d(pre5) leaves as bf16 through the chain's image + copy_out.
-// KP: the class pitch.  KP = 32 (9 .. 32 classes, bf16 only) keeps all 32 columns of the logits product, folds the eight partial
-// logits tiles into four LDS slots in two rounds (head.h: head_logits_fold), runs dL/d(pre5) as two k-steps and stores all
-// sixteen registers of dW6^T; it also serves a 256-wide feature layer as a single chunk (the D-tail chain is an 8-class kernel).
-// ------------------------------------------------------------------------------------------------------------------
-constexpr int HW_FIMG = CH_ROWS * CH_PW * 2;                  // 32 KiB per feature image
-constexpr int HW_TPITCH = CH_ROWS + 16, HW_RPITCH = CH_PW + 16;
-constexpr int HW_X = 2 * HW_FIMG, HW_X_BYTES = 40 * 1024;     // pass 1: logits partials; pass 2: output image(s)
-constexpr int HW_SMALL = HW_X + HW_X_BYTES;
-constexpr int hw_lds(int KP) { return HW_SMALL + 2 * 3 * CH_ROWS * KP * 2 + (3 + KP) * CH_ROWS * 4; }
-constexpr int HW_LDS = hw_lds(KMAX);
-static_assert(CH_PW * HW_TPITCH + CH_ROWS * HW_RPITCH <= HW_X_BYTES && 8 * CH_ROWS * KMAX * 4 <= HW_X_BYTES, "head_wide LDS map");
-static_assert(head_lslots(KWIDE) * CH_ROWS * head_lpitch(KWIDE) * 4 <= HW_X_BYTES && hw_lds(KWIDE) <= 160 * 1024, "head_wide LDS map, 32 classes");
-
-template <int KP>
-__global__ __launch_bounds__(256) void w6_split_kernel(const float* w, int ldw, int feat, int feat_valid, int classes, __bf16* w6c, __bf16* w6r) {
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= feat) return;
-#pragma unroll
-    for (int c = 0; c < KP; ++c) {
-        const float v = (j < feat_valid && c < classes) ? w[(long)j * ldw + c] : 0.f;
-        __bf16 p0, p1, p2;
-        split3(v, p0, p1, p2);
-        w6c[(0L * KP + c) * feat + j] = p0; w6c[(1L * KP + c) * feat + j] = p1; w6c[(2L * KP + c) * feat + j] = p2;
-        w6r[(0L * feat + j) * KP + c] = p0; w6r[(1L * feat + j) * KP + c] = p1; w6r[(2L * feat + j) * KP + c] = p2;
-    }
-}
-
-template <bool Q8, int KP = KMAX>
-__global__ __launch_bounds__(CH_THREADS) void head_wide_kernel(const HeadWideArgs a) {
-    static_assert(KP == KMAX || !Q8, "the e5m2 epilogue exists at the 8-class pitch only");
-    constexpr int NKS = KP == KMAX ? 1 : KP / 16;             // k-steps of the dL/d(pre5) product
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const HeadArgs& h = a.h;
-    char* xreg = lds + HW_X;
-    __bf16* dl_rc = (__bf16*)(lds + HW_SMALL);                // [3][CH_ROWS][KP]   dlogits addends, row-major
-    __bf16* dl_t = dl_rc + 3 * CH_ROWS * KP;                  // [3][KP][CH_ROWS]   ... class-major
-    float* red = (float*)(dl_t + 3 * KP * CH_ROWS);           // [3 + KP][CH_ROWS]
-    const int t = threadIdx.x, lane = t & 63, lc = lane & 31, lh = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int seg = blockIdx.y, rb = blockIdx.x, nrb = gridDim.x, kind = h.seg_kind[seg];
-    const int row_blk = rb * CH_ROWS, rows_valid = min(CH_ROWS, h.rows - row_blk), blk = seg * nrb + rb;
-    const int nch = h.feat / CH_PW;
-
-    // ---- feature chunks by LDS-DMA: [4 k-tiles][64 rows][64 k] with the chain's swizzle; rows >= h.rows arrive as zeros ----
-    const __bf16* fseg = (const __bf16*)h.f + (long)seg * h.f_bs;
-    const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void*)fseg, 0, (int)((long)h.rows * h.ldf * 2), 0x00020000);
-    int fvoff[4], fdst[4];
-    {
-        const int lrow = lane >> 3, lp = lane & 7;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int pce = wave + 8 * i, kt = pce >> 3, pr = pce & 7, R = pr * 8 + lrow;
-            fvoff[i] = (int)(((long)(row_blk + R) * h.ldf + kt * 64 + ((lp ^ ((R >> 1) & 7)) << 3)) * 2);
-            fdst[i] = kt * (CH_ROWS * 128) + pr * 1024;
-        }
-    }
-    auto issue_chunk = [&](int c) {
-        char* img = lds + (c & 1) * HW_FIMG;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) glds16(rsF, img + fdst[i], fvoff[i], c * (CH_PW * 2));
-    };
-    // B fragments of the logits product for chunk c: lane <-> (class lc, features 16 (2 wave + u) + 8 lh .. + 7 of the chunk)
-    auto load_w6c = [&](int c, bf16x8 (&fb)[2][3]) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                const bf16x8 v = *(const bf16x8*)(a.w6c + ((long)p * KP + (lc & (KP - 1))) * h.feat + c * CH_PW + 16 * (2 * wave + u) + 8 * lh);
-                fb[u][p] = (KP == 32 || lc < KP) ? v : zero8();   // KP = 8: columns 8 .. 31 of the product are padding; KP = 32:
-                                                                // w6_split_kernel left zeros in the columns >= classes
-            }
-    };
-
-    // =========================== pass 1: logits ===========================
-    f32x16 lacc[2];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) lacc[mi][r] = 0.f;
-    bf16x8 fbn[2][3];
-    issue_chunk(0);
-    load_w6c(0, fbn);
-    for (int c = 0; c < nch; ++c) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's pieces of chunk c and its W6 fragments
-        __builtin_amdgcn_s_barrier();                         // ... everyone's pieces; everyone is done with chunk c - 1
-        asm volatile("" ::: "memory");
-        bf16x8 fb[2][3];
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) fb[u][p] = fbn[u][p];
-        if (c + 1 < nch) { issue_chunk(c + 1); load_w6c(c + 1, fbn); }
-        const char* fimg = lds + (c & 1) * HW_FIMG;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) head_logits_step(lacc, fimg, 2 * wave + u, fb[u], lc, lh);
-    }
-    float* lpart = (float*)xreg;                              // [head_lslots(KP)][CH_ROWS][head_lpitch(KP)]
-    if constexpr (KP == KMAX) {
-        head_logits_scatter(lacc, lpart, wave, lc, lh);
-    } else {
-        // eight [64][32] tiles into four slots: waves 0 .. 3 store, then wave 4 + i adds to slot i (a fixed order of the sum)
-        if (wave < head_lslots(KP)) head_logits_scatter<KP>(lacc, lpart, wave, lc, lh);
-        lds_barrier();
-        if (wave >= head_lslots(KP)) head_logits_fold<KP>(lacc, lpart, wave - head_lslots(KP), lc, lh);
-    }
-    lds_barrier();
-    // the chunk before the last one is needed next (pass 2 walks downwards): its image is free now
-    if (nch > 1) issue_chunk(nch - 2);
-
-    // =========================== row phase (wave 0: lane <-> row), as chain_head step 3 ===========================
-    float* part_row = h.part + (long)blk * h.part_stride;
-    if (wave == 0) {
-        const int r = lane;
-        const bool rowvalid = r < rows_valid;
-        float l[KP];
-        head_logits_gather(lpart, r, l);
-        float b[KP];
-#pragma unroll
-        for (int c = 0; c < KP; ++c) b[c] = (c < h.classes) ? h.b[c] : 0.f;
-        int y = 0;
-        if (rowvalid && kind == HEAD_LAB) {
-            const long lo = h.labels_stream ? (long)h.st->batch * h.rows : 0;
-            y = h.labels[lo + row_blk + r];
-        }
-        float loss0, loss1, err, dl[KP];
-        head_row<false>(l, b, kind, y, h.classes, h.inv_count, h.unl_weight, rowvalid, loss0, loss1, err, dl);
-        if (rowvalid && h.logits) {
-            float* lp = h.logits + (long)seg * h.logits_bs + (long)(row_blk + r) * KP;
-#pragma unroll
-            for (int c = 0; c < KP; ++c) lp[c] = (c < h.classes) ? l[c] : 0.f;
-        }
-        head_rows_to_lds(dl, loss0, loss1, err, r, dl_rc, dl_t, red);
-    }
-    lds_barrier();
-    head_block_sums<KP>(red, h, blk, part_row, wave, lane);
-
-    // =========================== pass 2: dL/d(pre5) and dW6^T, chunk by chunk ===========================
-    // A operands that do not depend on the chunk, in registers for the whole pass
-    bf16x8 da[NKS][2][3], dt[4][3];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) head_load_dl_rows<KP>(dl_rc, lc, lh, da[ks], ks);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) head_load_dl_cols<KP>(dl_t, ks, lc, lh, dt[ks]);
-    const uint16_t* mseg = a.mask + (long)seg * a.mask_bs;
-    // per chunk: the W6 rows of this lane's feature as bf16 addends (B operand, k = class) and the relu-mask words of its column
-    // (KP = 32: k-step ks holds classes 16 ks + 8 lh .. + 7)
-    auto load_chunk_inputs = [&](int c, bf16x8 (&bw)[NKS][3], uint32_t (&mw)[2]) {
-        const int col = c * CH_PW + wave * 32 + lc;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            if constexpr (KP == KMAX) {
-                const bf16x8 v = *(const bf16x8*)(a.w6r + ((long)q * h.feat + col) * KMAX);
-                bw[0][q] = lh ? zero8() : v;                    // lh = 1: k = 8 .. 15, zeros
-            } else {
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks) bw[ks][q] = *(const bf16x8*)(a.w6r + ((long)q * h.feat + col) * KP + 16 * ks + 8 * lh);
-            }
-        }
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-            const bool ok = row_blk + mi * 32 < h.rows;
-            const uint32_t w = mseg[((long)((ok ? row_blk + mi * 32 : 0) >> 5) * a.ldm + col) * 2 + lh];
-            mw[mi] = ok ? w : 0u;
-        }
-    };
-    const float q8s = Q8 ? h.q8_slot->scale : 1.f;
-    float q8_amax = 0.f;
-    bf16x8 bwn[NKS][3];
-    uint32_t mwn[2];
-    load_chunk_inputs(nch - 1, bwn, mwn);
-    for (int c = nch - 1; c >= 0; --c) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // chunk c (this wave's pieces), its inputs; the previous copy-out
-        __builtin_amdgcn_s_barrier();                         // ... everyone's: the output region and chunk c + 1's image are free
-        asm volatile("" ::: "memory");
-        bf16x8 bw[NKS][3];
-        uint32_t mw[2];
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) bw[ks][q] = bwn[ks][q];
-        mw[0] = mwn[0]; mw[1] = mwn[1];
-        if (c >= 1) load_chunk_inputs(c - 1, bwn, mwn);
-        if (c >= 1 && c != nch - 1) issue_chunk(c - 1);       // (chunk nch - 2 was issued before the row phase)
-        const char* fimg = lds + (c & 1) * HW_FIMG;
-        const int c0 = c * CH_PW, cip = wave * 32 + lc;
-        // ---- dL/d(pre5) = (dlogits W6^T) * relu'(pre5): NKS 16-deep k-steps x 6 addend pairs ----
-        {
-            f32x16 acc[2];
-            head_dpre_product<NKS>(acc, da, bw);
-            float s1 = 0.f;
-            if constexpr (Q8) {
-                unsigned char* timg = (unsigned char*)xreg;
-                unsigned char* rimg = timg + CH_PW * HW_TPITCH;
-                const int kq = lane & 3;
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        float o4[4];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const int r = 4 * g + j;
-                            const float av = acc[mi][r];
-                            o4[j] = ((mw[mi] >> r) & 1u) ? av : 0.f;              // (a select: see chain_gemm)
-                            s1 += o4[j];
-                            q8_amax = fmaxf(q8_amax, fabsf(o4[j]));
-                        }
-                        const uint32_t w = fp8_pack4<FP8_E5M2>(o4[0], o4[1], o4[2], o4[3], q8s);
-                        const int rl = mi * 32 + 8 * g + 4 * lh;                    // rows rl .. rl + 3 of column cip
-                        *(uint32_t*)(timg + cip * HW_TPITCH + rl) = w;
-                        *(uint32_t*)(rimg + (rl + kq) * HW_RPITCH + (cip - kq)) = quad_byte_transpose(w);
-                    }
-            } else {
-                s1 = head_dpre_to_image(acc, mw, xreg, cip, lh);
-            }
-            s1 += __shfl_xor(s1, 32, 64);
-            if (lh == 0) part_row[h.off_dbf + c0 + cip] = s1;                   // bias gradient of the feature layer
-        }
-        // ---- dW6^T [class][feature] = dlogits^T F for this wave's 32 features of the chunk ----
-        {
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < CH_ROWS / 16; ++ks) head_dw6t_step(acc, fimg, ks, dt[ks], wave, lane);
-#pragma unroll
-            for (int g = 0; g < KP / 8; ++g)                  // registers 4 g .. 4 g + 3 = classes 8 g + 4 lh .. + 3
-                *(f32x4*)(part_row + (long)(c0 + cip) * KP + 8 * g + 4 * lh) = (f32x4){acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-        }
-        lds_barrier();                                        // the output image(s) of the chunk are complete
-        if constexpr (Q8) {
-            const unsigned char* timg = (const unsigned char*)xreg;
-            const unsigned char* rimg = timg + CH_PW * HW_TPITCH;
-            unsigned char* q8t = h.q8t ? h.q8t + (long)seg * h.q8t_bs : nullptr;
-            unsigned char* q8 = h.q8 ? h.q8 + (long)seg * h.q8_bs : nullptr;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int qi = t + CH_THREADS * u;
-                // transposed copy: column (row of q8t) x 16 rows; rows >= h.rows of the block are zero bytes (zero dlogits)
-                if (q8t) *(u32x4*)(q8t + (long)(c0 + (qi >> 2)) * h.ldq8t + row_blk + 16 * (qi & 3)) = *(const u32x4*)(timg + (qi >> 2) * HW_TPITCH + 16 * (qi & 3));
-                if (q8 && (qi >> 4) < rows_valid) *(u32x4*)(q8 + (long)(row_blk + (qi >> 4)) * h.ldq8 + c0 + 16 * (qi & 15)) = *(const u32x4*)(rimg + (qi >> 4) * HW_RPITCH + 16 * (qi & 15));
-            }
-        } else {
-            copy_out<CH_ROWS>(xreg, (__bf16*)h.dpre + (long)seg * h.dpre_bs + (long)row_blk * h.ldd, h.ldd, c0, h.feat, rows_valid, t);
-        }
-    }
-    if constexpr (Q8) fp8_amax_commit(h.q8_slot, q8_amax);
+    if (t == 0) st.store(a.stamps);
 }
 
 }  // namespace
 
-// the bf16 addends of W6 for launch_head_wide (once per D sub-step: W6 changes with every Adam update)
-int launch_w6_split(const HeadWideArgs& a, hipStream_t s) {
-    const HeadArgs& h = a.h;
-    if (!a.w6c || !a.w6r || !h.w) return -3;
-    if (h.ldw == KWIDE) MRGAN_LAUNCH(w6_split_kernel<KWIDE>, dim3((h.feat + 255) / 256), dim3(256), 0, s, h.w, h.ldw, h.feat, h.feat_valid, h.classes, a.w6c, a.w6r);
-    else MRGAN_LAUNCH(w6_split_kernel<KMAX>, dim3((h.feat + 255) / 256), dim3(256), 0, s, h.w, h.ldw, h.feat, h.feat_valid, h.classes, a.w6c, a.w6r);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-int launch_head_wide(const HeadWideArgs& a, hipStream_t s) {
-    const HeadArgs& h = a.h;
-    const int kp = h.ldw;                                     // the class pitch of W6, its addends, the logits and the partial rows
-    if ((h.feat % CH_PW) != 0 || (kp != KMAX && kp != KWIDE) || h.classes > kp || !a.mask || !a.w6c || !a.w6r || !h.part || !h.loss_part) return -3;
-    for (int i = 0; i < h.nseg; ++i)
-        if (h.seg_kind[i] != HEAD_LAB && h.seg_kind[i] != HEAD_UNL && h.seg_kind[i] != HEAD_FAKE) return -3;
-    if ((long)h.rows * h.ldf * 2 >= (1L << 31)) return -3;
-    const bool q8 = h.q8_slot != nullptr;
-    if (q8 ? !(h.q8 || h.q8t) : !h.dpre) return -3;
-    // (the dynamic-LDS limit of both instantiations is raised by chain_init_attributes, outside any stream capture)
-    const dim3 grid((h.rows + CH_ROWS - 1) / CH_ROWS, h.nseg), block(CH_THREADS);
-    if (kp == KWIDE) {
-        if (q8) return -3;
-        MRGAN_LAUNCH((head_wide_kernel<false, KWIDE>), grid, block, hw_lds(KWIDE), s, a);
-    } else if (q8) MRGAN_LAUNCH((head_wide_kernel<true>), grid, block, HW_LDS, s, a);
-    else MRGAN_LAUNCH((head_wide_kernel<false>), grid, block, HW_LDS, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
+// every instantiation of chain_kernel: launch_chain picks its kernel here, chain_init_attributes raises the LDS limit of each
+struct ChainKernel { int variant, block_rows, gauss; void (*kernel)(const ChainArgs); };
+static const ChainKernel chain_kernels[] = {
+    {CH_V_DTAIL, 64, 0, chain_kernel<CH_V_DTAIL, 2>},      {CH_V_GFWD, 64, 0, chain_kernel<CH_V_GFWD, 2>},       {CH_V_GBWD, 64, 0, chain_kernel<CH_V_GBWD, 2>},
+    {CH_V_GFWD, 32, 0, chain_kernel<CH_V_GFWD, 1>},        {CH_V_GBWD, 32, 0, chain_kernel<CH_V_GBWD, 1>},
+    {CH_V_DTAIL, 64, 1, chain_kernel<CH_V_DTAIL, 2, true>}, {CH_V_GFWD, 64, 1, chain_kernel<CH_V_GFWD, 2, true>}, {CH_V_GFWD, 32, 1, chain_kernel<CH_V_GFWD, 1, true>},
+};
 
 int chain_init_attributes() {
-    hipError_t e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_DTAIL, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(64));
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_GFWD, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(64));
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_GBWD, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(64));
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_GFWD, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(32));
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_GBWD, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(32));
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_DTAIL, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(64));
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_GFWD, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(64));
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)chain_kernel<CH_V_GFWD, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(32));
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, HW_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_wide_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, HW_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_wide_kernel<false, KWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, hw_lds(KWIDE));
-    return e == hipSuccess ? 0 : -2;
+    for (const ChainKernel& k : chain_kernels)
+        if (hipFuncSetAttribute((const void*)k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, chain_lds_bytes(k.block_rows)) != hipSuccess) return -2;
+    return 0;
+}
+
+// one product's shape limits; fwd: a forward product (its output is the next product's A image), else a dX product
+static bool chain_op_ok(const ChainOp& op, bool fwd) {
+    if ((op.K % 64) || (op.N % 64) || op.K > CH_KMAX || op.K < 128 || op.N > 2 * CH_PW || !op.W) return false;
+    if (fwd ? (op.N > CH_PW || !op.bias) : !op.mask) return false;
+    return (long)op.N * op.K * 2 < (1L << 31);
 }
 
 int launch_chain(const ChainArgs& a, hipStream_t s) {
-    // the three fixed op lists (chain.h)
-    static const int want[3][CH_MAX_OPS] = {{CH_OP_GEMM, CH_OP_GEMM, CH_OP_GEMM, CH_OP_HEAD, CH_OP_GEMM, CH_OP_GEMM, CH_OP_GEMM, -1},
-                                            {CH_OP_GEMM, CH_OP_GEMM, CH_OP_GEMM, -1, -1, -1, -1, -1},
-                                            {CH_OP_GEMM, CH_OP_GEMM, CH_OP_GEMM, -1, -1, -1, -1, -1}};
-    static const int nops[3] = {7, 3, 3};
-    if (a.variant < 0 || a.variant > 2 || a.nops != nops[a.variant]) return -3;
-    if (a.block_rows != 64 && !(a.block_rows == 32 && a.variant != CH_V_DTAIL)) return -3;
+    const bool has_fwd = a.variant != CH_V_GBWD, has_dx = a.variant != CH_V_GFWD;
+    // (the 32-row blocks have no D-tail kernel; the dX products draw no noise, so CH_V_GBWD has one kernel for both generators)
+    const int gauss = has_fwd && a.gauss;
+    const ChainKernel* k = nullptr;
+    for (const ChainKernel& c : chain_kernels)
+        if (c.variant == a.variant && c.block_rows == a.block_rows && c.gauss == gauss) k = &c;
+    if (!k) return -3;
     // the head inside the D-tail chain is an 8-class kernel (its scratch is half of image 0)
     if (a.variant == CH_V_DTAIL && (a.head.classes > KMAX || a.head.ldw != KMAX)) return -3;
-    for (int i = 0; i < a.nops; ++i) {
-        const ChainOp& op = a.op[i];
-        if (op.kind != want[a.variant][i]) return -3;
-        if (op.kind != CH_OP_GEMM) continue;
-        const bool fwd = a.variant == CH_V_GFWD || (a.variant == CH_V_DTAIL && i < 3);
-        if (op.mode != (fwd ? CH_FWD_RELU : CH_DX_RELU)) return -3;
-        if ((op.K % 64) || (op.N % 64) || op.K > CH_KMAX || op.K < 128 || op.N > 2 * CH_PW || !op.W) return -3;
-        if (fwd && op.N > CH_PW) return -3;                    // a forward output is the next product's A image
-        if (!fwd && !op.mask) return -3;
-        if (fwd && !op.bias) return -3;
-        if ((long)op.N * op.K * 2 >= (1L << 31)) return -3;
-    }
-    if (a.variant != CH_V_GBWD && ((a.a_cols % 64) || a.a_cols > CH_KMAX || a.a_cols != a.op[0].K || (long)a.rows * a.lda * 2 >= (1L << 31))) return -3;
+    for (int i = 0; i < 3; ++i)
+        if ((has_fwd && !chain_op_ok(a.fwd[i], true)) || (has_dx && !chain_op_ok(a.dx[i], false))) return -3;
+    if (has_fwd && ((a.a_cols % 64) || a.a_cols > CH_KMAX || a.a_cols != a.fwd[0].K || (long)a.rows * a.lda * 2 >= (1L << 31))) return -3;
     const int nrb = (a.rows + a.block_rows - 1) / a.block_rows;
-    const dim3 grid(nrb * a.nseg), block(CH_THREADS);
-    const int lds = chain_lds_bytes(a.block_rows);
-    if (a.gauss && a.variant == CH_V_DTAIL) MRGAN_LAUNCH((chain_kernel<CH_V_DTAIL, 2, true>), grid, block, lds, s, a);
-    else if (a.gauss && a.variant == CH_V_GFWD && a.block_rows == 64) MRGAN_LAUNCH((chain_kernel<CH_V_GFWD, 2, true>), grid, block, lds, s, a);
-    else if (a.gauss && a.variant == CH_V_GFWD) MRGAN_LAUNCH((chain_kernel<CH_V_GFWD, 1, true>), grid, block, lds, s, a);
-    else if (a.variant == CH_V_DTAIL) MRGAN_LAUNCH((chain_kernel<CH_V_DTAIL, 2>), grid, block, lds, s, a);
-    else if (a.variant == CH_V_GFWD && a.block_rows == 64) MRGAN_LAUNCH((chain_kernel<CH_V_GFWD, 2>), grid, block, lds, s, a);
-    else if (a.variant == CH_V_GFWD) MRGAN_LAUNCH((chain_kernel<CH_V_GFWD, 1>), grid, block, lds, s, a);
-    else if (a.block_rows == 64) MRGAN_LAUNCH((chain_kernel<CH_V_GBWD, 2>), grid, block, lds, s, a);
-    else MRGAN_LAUNCH((chain_kernel<CH_V_GBWD, 1>), grid, block, lds, s, a);
+    MRGAN_LAUNCH(k->kernel, dim3(nrb * a.nseg), dim3(CH_THREADS), chain_lds_bytes(a.block_rows), s, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

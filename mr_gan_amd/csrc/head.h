@@ -1,6 +1,6 @@
 // Loss head, device side (mr_gan.py:128, :146-149, :161): the pieces the head kernels share.
 //   head_row                      per-row softmax, losses, train error, closed-form dlogits: head_kernel (aux_kernels.hip, scalar
-//                                 fmaf products) and the two matrix-core heads of gemm_chain.hip
+//                                 fmaf products) and the two matrix-core heads (gemm_chain.hip, head_wide.hip)
 //   everything else               the matrix-core heads only (chain_head inside the D-tail chain launch, head_wide_kernel for
 //                                 feature layers wider than 256 columns): the three small products as MFMAs at fp32 accuracy
 //                                 (see chain_head) over a block of CH_ROWS rows and the 256 feature columns of one LDS image.

@@ -274,7 +274,7 @@ def _dpre_within_one_ulp(a, b, what):
 
 def matrix_core_loss_head_equals_scalar_head(variant, dtype, B, kernel_names=False):
     """Feature layers wider than the chain holds (here 512 columns = two chunks; BASELINE configs[4]: 4096) run the loss head of
-    the D sub-step as the stand-alone MFMA kernel over 64-row blocks (gemm_chain.hip: head_wide_kernel; TUNE_HEAD_MFMA = 1, the
+    the D sub-step as the stand-alone MFMA kernel over 64-row blocks (head_wide.hip: head_wide_kernel; TUNE_HEAD_MFMA = 1, the
     default) instead of head_kernel's fmaf loops over 32-row blocks.  Same rule as the chain body below: three-addend bf16 splits
     make every product exact, only the fp32 summation order differs -- losses to 1e-6, the bf16 dL/d(pre5) within one ulp on a few
     rows (fp8 mode: the e5m2 copies are what leaves the kernel; compared through the weight gradients), D gradients to 5e-4.

@@ -106,7 +106,8 @@ def test_fp8_gradients_match_fp8_mirror_gaussian():
     P.grad_parity(P.GAUSSIAN, 512, 1024, 2, 'fp8', tol=5e-3, tol_loss=2e-3, eval_first=False, frac=0.85, loose=(0.9, 0.8, 0.6), **kw)
 
 
-@pytest.mark.parametrize("D,B", [(400, 256), (96, 50)])
+@pytest.mark.parametrize("D,B", [(400, 256), (96, 50),
+                                 (64, 8200)])     # the 64-row blocks of the G sub-step's forward chain (see test_gpu_parity.py)
 def test_chain_launches_equal_per_layer_launches_gaussian(D, B):
     P.chain_launches_equal_per_layer_launches(P.GAUSSIAN, D, B)
 

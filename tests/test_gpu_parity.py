@@ -264,7 +264,8 @@ def test_bf16_gradients_match_bf16_mirror(D, B):
     P.grad_parity(P.DEFAULT, D, B, 1, 'bf16', tol=3e-3, tol_loss=5e-4)
 
 
-@pytest.mark.parametrize("D,B", [(400, 256), (96, 50), (512, 1024)])
+@pytest.mark.parametrize("D,B", [(400, 256), (96, 50), (512, 1024),
+                                 (64, 8200)])     # 129 row blocks per segment: the 64-row blocks of both G sub-step chains, last block 8 rows
 def test_chain_launches_equal_per_layer_launches(D, B):
     P.chain_launches_equal_per_layer_launches(P.DEFAULT, D, B)
 
