@@ -25,7 +25,9 @@ int mrgan_debug_gemm_time(int op, int m, int n, int k, int nbatch, int splits, i
 /* One GEMM launch described field by field, for kernel-level tests of every tile and epilogue variant.  Nothing is allocated,
  * converted or cleared except the DevState that carries `iter`: every buffer is the caller's device memory in the kernel's own
  * element type (dtype MRGAN_BF16: bf16 operands / h / out; MRGAN_F32: float), so a caller that pre-fills the buffers sees
- * every element the kernel did not write.
+ * every element the kernel did not write.  dtype MRGAN_FP8 (csrc/gemm_fp8.hip): `a` and `b` are the caller's fp8 bytes in the
+ * product's formats (op 0: e4m3 x e4m3, 1: e5m2 x e4m3, 2: e4m3 x e5m2), strides in bytes, both operands reduction-contiguous
+ * (a_sk == b_sk == 1) for all three ops; the output is bf16 (`out`) or the fp8 images q8 / q8t.
  *   op 0 (forward) / 1 (input gradient): out[b][i][j] = epilogue(sum_k A(b,i,k) B(b,k,j)), i < m, j < n, reduction length k
  *   op 2 (weight gradient): slab[split][i][j] = sum of A(i,v) B(v,j) over the reduction rows v of that split, v < k
  *   A(b,i,k) at a + b*a_bs + i*a_si + k*a_sk ; B(b,k,j) at b + b*b_bs + k*b_sk + j*b_sj  (strides in elements).
@@ -49,6 +51,13 @@ typedef struct mrgan_debug_gemm_desc {
     int32_t cs_mode; float* cs1; float* cs2; int32_t ldcs;
     const float* bn_mu; const float* bn_rstd;
     float* slab; int64_t slab_stride;
+    /* MRGAN_FP8 only (Epi of csrc/gemm.h): the fp8 images of the output, row-major [b][i][ldq8] and transposed [j][ldq8t] with
+     * batch b at byte b * q8t_bs; device slots {amax_bits, scale, inv_scale, target} (4 x 32 bits) of operand A, operand B (both
+     * null: the accumulator is taken as it is) and of the output */
+    void* q8; int64_t q8_bs; int32_t ldq8;
+    void* q8t; int64_t q8t_bs; int32_t ldq8t;
+    const void* slot_a; const void* slot_b; void* slot_o;
+    int32_t gauss;                       /* forward noise from the true-Gaussian generator (row0 even) */
 } mrgan_debug_gemm_desc;
 /* per-block partial rows folded by the tail blocks of a grouped weight-gradient launch:
  * dst[g][i] = sum of src[p][i] over p = g, g + ngroups, ... < nsrc  (i < n, rows `stride` floats apart) */
@@ -65,6 +74,15 @@ int mrgan_debug_gemm_launch(const mrgan_debug_gemm_desc* d, int count, int group
  * kc_cfg: -1 = the launcher's choice, 1 = 128x128 blocks, 3 = 256x256 blocks. */
 int mrgan_debug_gemm_fp8(int m, int n, int k, const float* a_dev, const float* b_dev, const float* bias_dev, int act, float scale_a,
                          float scale_b, float* out_dev, int reps, float* avg_us, int kc_cfg, mrgan_stream stream);
+
+/* One launch of the bf16 -> fp8 quantiser (csrc/gemm.h Quant8Args, every buffer the caller's): src [nb][rows][ld] bf16 ->
+ * dst [nb][prow][ldd] and / or the transposed dstt [cols][lddt] (batch b at byte b * dstt_bs) = fp8(v * slot->scale), fmt 0 =
+ * e4m3, 1 = e5m2; rows [rows, prow) are written as zeros; max |v| goes to the device slot.  Returns the launcher's -3 for
+ * arguments it refuses.  Synchronises the stream. */
+int mrgan_debug_quant8(const void* src, int64_t src_bs, int ld, int rows, int cols, int nb, int prow, void* dst, int64_t dst_bs, int ldd,
+                       void* dstt, int64_t dstt_bs, int lddt, void* slot_dev, int fmt, mrgan_stream stream);
+/* the delayed-scaling update on the caller's array of n device slots.  Synchronises the stream. */
+int mrgan_debug_fp8_update_scales(void* slots_dev, int n, mrgan_stream stream);
 
 #ifdef __cplusplus
 }

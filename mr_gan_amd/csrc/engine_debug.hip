@@ -199,8 +199,8 @@ int mrgan_debug_tr_probe(uint16_t* out, mrgan_stream stream) {
 
 // one descriptor -> the launchers' argument block; the checks are the preconditions the kernels state for themselves
 static int debug_gemm_args(const mrgan_debug_gemm_desc& d, const DevState* st, GemmArgs& g, int& epi) {
-    const bool bf = d.dtype == MRGAN_BF16;
-    if (d.dtype != MRGAN_BF16 && d.dtype != MRGAN_F32) return fail(-1, "debug_gemm_launch: dtype must be fp32 or bf16");
+    const bool bf = d.dtype == MRGAN_BF16, f8 = d.dtype == MRGAN_FP8;
+    if (!bf && !f8 && d.dtype != MRGAN_F32) return fail(-1, "debug_gemm_launch: dtype must be fp32, bf16 or fp8");
     if (d.op < 0 || d.op > 2) return fail(-1, "debug_gemm_launch: op must be 0, 1 or 2");
     if (!kc_cfg_supported(d.kc_cfg)) return fail(-1, "debug_gemm_launch: kc_cfg %d is not a block tile", d.kc_cfg);
     if (d.m < 1 || d.n < 1 || d.k < 1 || d.nbatch < 1 || d.splits < 1 || !d.a || !d.b) return fail(-1, "debug_gemm_launch: empty problem");
@@ -209,6 +209,7 @@ static int debug_gemm_args(const mrgan_debug_gemm_desc& d, const DevState* st, G
     epi = d.op == 0 ? EPI_FWD : d.op == 1 ? EPI_DX : EPI_SLAB;
     if (epi == EPI_FWD) g = gemm_fwd_args(d.m, d.k, d.n, d.nbatch, d.a, d.a_bs, d.a_si, d.b, d.b_sj, true);
     else if (epi == EPI_DX) g = gemm_dx_args(d.m, d.n, d.k, d.nbatch, d.a, d.a_bs, d.a_si, d.b, d.b_sj);
+    else if (f8) g = gemm_dw_args(d.m, d.n, d.k, 1, d.k, 0, 0, d.a, d.a_si, d.b, d.b_sj, true, d.slab);
     else g = gemm_dw_args(d.m, d.n, d.k, 1, d.k, 0, 0, d.a, d.a_sk, d.b, d.b_sk, false, d.slab);
     // the descriptor states every stride, the split and the holes of the reduction itself: the tests also describe launches
     // the engine never makes, to see them refused
@@ -226,14 +227,26 @@ static int debug_gemm_args(const mrgan_debug_gemm_desc& d, const DevState* st, G
     e.cs_mode = d.cs_mode; e.cs1 = d.cs1; e.cs2 = d.cs2; e.ldcs = d.ldcs; e.bn_mu = d.bn_mu; e.bn_rstd = d.bn_rstd;
     e.slab = d.slab; e.slab_stride = d.slab_stride;
     e.st = st; e.acc_scale = 1.f; e.tune_kc_cfg = d.kc_cfg; e.tune_bits = d.tune_bits;
-    if (epi == EPI_SLAB) {
+    e.gauss = d.gauss;
+    if (f8) {
+        // which products, operand layouts, output forms and slots exist is the launcher's to refuse (-3); the entry refuses only
+        // what the launcher takes on trust: images narrower than the tile rows they receive, the bf16 tile's 16-byte stores
+        e.q8 = d.q8; e.q8_bs = d.q8_bs; e.ldq8 = d.ldq8; e.q8t = d.q8t; e.q8t_bs = d.q8t_bs; e.ldq8t = d.ldq8t;
+        e.qa = (const Fp8Slot*)d.slot_a; e.qb = (const Fp8Slot*)d.slot_b; e.qo = (Fp8Slot*)d.slot_o;
+        if (epi == EPI_SLAB ? d.ldo < d.n : (d.out && (d.ldo < d.n || (d.ldo % 8)))) return fail(-1, "debug_gemm_launch: fp8 product needs ldo >= n (bf16: a multiple of 8)");
+        if ((d.a_si % 16) || (d.b_sj % 16) || (d.a_bs % 16) || (d.b_bs % 16)) return fail(-1, "debug_gemm_launch: fp8 row and batch pitches must be multiples of 16 bytes");
+        if (d.q8 && (d.q8_bs % 16)) return fail(-1, "debug_gemm_launch: q8_bs must be a multiple of 16");
+        if (d.q8 && d.ldq8 < d.n) return fail(-1, "debug_gemm_launch: ldq8 >= n");
+        if (d.q8t && (d.q8t_bs < 0 || d.ldq8t < (d.nbatch - 1) * d.q8t_bs + round_up(d.m, 16))) return fail(-1, "debug_gemm_launch: ldq8t must hold nbatch batches of round_up(m, 16) bytes");
+    }
+    if (epi == EPI_SLAB && !f8) {
         const int bk = bf ? 64 : 16;
         if (!d.slab || d.ldo < d.n) return fail(-1, "debug_gemm_launch: weight gradient needs slab and ldo >= n");
         if ((g.kchunk % bk) || (g.seg_stride % bk)) return fail(-1, "debug_gemm_launch: kchunk and seg_stride must be multiples of %d", bk);
         // 16-byte operand loads of the bf16 kernels: 8 elements per predicate
         if (bf && ((d.a_sk % 8) || (d.b_sk % 8) || d.a_sk < round_up(d.m, 8))) return fail(-1, "debug_gemm_launch: bf16 row pitches must be multiples of 8");
-    } else {
-        if (!d.out || d.ldo < d.n || d.n_valid < 0 || d.n_valid > d.n) return fail(-1, "debug_gemm_launch: needs out, ldo >= n and n_valid <= n");
+    } else if (epi != EPI_SLAB) {
+        if ((!f8 && !d.out) || (d.out && d.ldo < d.n) || d.n_valid < 0 || d.n_valid > d.n) return fail(-1, "debug_gemm_launch: needs out, ldo >= n and n_valid <= n");
         if (bf && ((d.ldo % 8) || (d.a_si % 8) || (d.b_sj % 8))) return fail(-1, "debug_gemm_launch: bf16 row pitches must be multiples of 8");
         if (d.cs_mode != CS_NONE && (!d.cs1 || d.ldcs < d.n || (d.cs_mode != CS_SUM && !d.cs2))) return fail(-1, "debug_gemm_launch: column sums need cs1 / cs2 and ldcs >= n");
         if (d.cs_mode == CS_SUM_XHAT && (epi != EPI_DX || !d.bn_mu || !d.bn_rstd || !d.h)) return fail(-1, "debug_gemm_launch: xhat sums need bn_mu, bn_rstd and h on a dX product");
@@ -264,7 +277,9 @@ int mrgan_debug_gemm_launch(const mrgan_debug_gemm_desc* d, int count, int group
         if (count != 1) r = fail(-1, "debug_gemm_launch: one product per plain launch");
         if (!r) r = debug_gemm_args(d[0], st, g, epi);
         if (!r) {
-            r = d[0].dtype == MRGAN_BF16 ? launch_gemm_bf16(epi, g, s, &name) : launch_gemm_f32(epi, g, s, &name);
+            r = d[0].dtype == MRGAN_FP8    ? launch_gemm_fp8(epi, g, s, &name)
+                : d[0].dtype == MRGAN_BF16 ? launch_gemm_bf16(epi, g, s, &name)
+                                           : launch_gemm_f32(epi, g, s, &name);
             if (r) fail(r, "debug_gemm_launch: launch refused (%d)", r);
         }
     } else if (!r) {
@@ -292,6 +307,31 @@ int mrgan_debug_gemm_launch(const mrgan_debug_gemm_desc* d, int count, int group
     if (!r && he != hipSuccess) return fail(-10, "debug_gemm_launch: %s", hipGetErrorString(he));
     if (!r && kname && kname_len > 0) snprintf(kname, (size_t)kname_len, "%s", name);
     return r;
+}
+
+int mrgan_debug_quant8(const void* src, int64_t src_bs, int ld, int rows, int cols, int nb, int prow, void* dst, int64_t dst_bs, int ldd,
+                       void* dstt, int64_t dstt_bs, int lddt, void* slot, int fmt, mrgan_stream stream) {
+    if (!src || rows < 0 || rows > prow || cols < 1 || cols > ld || (fmt != FP8_E4M3 && fmt != FP8_E5M2)) return fail(-1, "debug_quant8: bad argument");
+    if ((dst && ldd < cols) || (dstt && (dstt_bs < 0 || lddt < (int64_t)(nb - 1) * dstt_bs + prow))) return fail(-1, "debug_quant8: ldd >= cols, lddt >= nb batches of prow bytes");
+    Quant8Args a;
+    memset(&a, 0, sizeof a);
+    a.src = (const __bf16*)src; a.src_bs = src_bs; a.ld = ld; a.rows = rows; a.cols = cols; a.nb = nb; a.prow = prow;
+    a.dst = (unsigned char*)dst; a.dst_bs = dst_bs; a.ldd = ldd;
+    a.dstt = (unsigned char*)dstt; a.dstt_bs = dstt_bs; a.lddt = lddt;
+    a.slot = (Fp8Slot*)slot; a.fmt = fmt;
+    hipStream_t s = (hipStream_t)stream;
+    const int r = launch_quant8(a, s);
+    if (r) return fail(r, "debug_quant8: launch refused (%d)", r);
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int mrgan_debug_fp8_update_scales(void* slots, int n, mrgan_stream stream) {
+    if (!slots || n < 1) return fail(-1, "debug_fp8_update_scales: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    CHK(launch_fp8_update_scales((Fp8Slot*)slots, n, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
 }
 
 }  // extern "C"

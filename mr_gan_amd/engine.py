@@ -29,6 +29,7 @@ EXPORTS = [
     "mrgan_set_slot", "mrgan_get_iterations", "mrgan_set_iterations", "mrgan_disc_step", "mrgan_gen_step",
     "mrgan_train_pair", "mrgan_sup_step", "mrgan_fp8_calibration", "mrgan_logmel", "mrgan_logmel_frames", "mrgan_region", "mrgan_eval_error", "mrgan_predict_logits", "mrgan_read_metrics",
     "mrgan_pair_hint", "mrgan_set_tuning", "mrgan_debug_noise", "mrgan_debug_tr_probe", "mrgan_debug_gemm_launch", "mrgan_profile_begin", "mrgan_profile_end", "mrgan_debug_ablate", "mrgan_debug_gemm_time", "mrgan_debug_buffer", "mrgan_debug_gemm_fp8",
+    "mrgan_debug_quant8", "mrgan_debug_fp8_update_scales",
 ]
 PROF_NAME_LEN = 96
 
@@ -390,6 +391,10 @@ class DebugGemmDesc(C.Structure):
         ("cs_mode", C.c_int32), ("cs1", C.c_void_p), ("cs2", C.c_void_p), ("ldcs", C.c_int32),
         ("bn_mu", C.c_void_p), ("bn_rstd", C.c_void_p),
         ("slab", C.c_void_p), ("slab_stride", C.c_int64),
+        ("q8", C.c_void_p), ("q8_bs", C.c_int64), ("ldq8", C.c_int32),
+        ("q8t", C.c_void_p), ("q8t_bs", C.c_int64), ("ldq8t", C.c_int32),
+        ("slot_a", C.c_void_p), ("slot_b", C.c_void_p), ("slot_o", C.c_void_p),
+        ("gauss", C.c_int32),
     ]
 
 
@@ -456,6 +461,33 @@ def debug_gemm(dtype, op, a, b, bias=None, act=0, splits=1):
     for s in range(1, splits if op == 2 else 0):
         out[0] += out[s]
     return out[0] if op == 2 else out.float()
+
+
+def fp8_slots(rows, device="cuda:0"):
+    """[(amax, scale, inv_scale, target)] -> device tensor int32 [n][4], the words of n Fp8Slot (csrc/common.h); row i is the
+    slot pointer a descriptor takes"""
+    return torch.from_numpy(np.array(rows, dtype=np.float32).reshape(-1, 4).view(np.int32)).to(device)
+
+
+def fp8_slots_read(slots):
+    """-> (amax_bits uint32 [n], float32 [n][3] = scale, inv_scale, target)"""
+    w = slots.cpu().numpy()
+    return w[:, 0].view(np.uint32).copy(), w[:, 1:].copy().view(np.float32)
+
+
+def debug_quant8(src, src_bs, ld, rows, cols, nb, prow, slot, fmt, dst=None, dst_bs=0, ldd=0, dstt=None, dstt_bs=0, lddt=0):
+    """One launch of the bf16 -> fp8 quantiser through mrgan_debug_quant8 -> return code (0, or the refusals -1 / -3)"""
+    rc = load_library().mrgan_debug_quant8(_ptr(src), C.c_int64(src_bs), int(ld), int(rows), int(cols), int(nb), int(prow), _ptr(dst),
+                                           C.c_int64(dst_bs), int(ldd), _ptr(dstt), C.c_int64(dstt_bs), int(lddt), _ptr(slot), int(fmt),
+                                           _stream())
+    if rc not in (0, -1, -3):
+        _check(rc)
+    return rc
+
+
+def debug_fp8_update_scales(slots):
+    """the delayed-scaling update on a tensor of slots (fp8_slots), in place"""
+    _check(load_library().mrgan_debug_fp8_update_scales(_ptr(slots), int(slots.shape[0]), _stream()))
 
 
 def debug_tr_probe(device="cuda:0"):

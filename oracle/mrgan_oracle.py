@@ -397,9 +397,12 @@ class Fp8Slots(object):
     def update(self):
         for key, a in self.amax.items():
             if a > 0:
-                ratio = np.float32(FP8_TARGETS[self.fmt[key]]) / np.float32(a)
-                _, e = np.frexp(ratio)
-                self.scale[key] = np.float32(2.0) ** int(np.clip(e - 1, -100, 100))
+                with np.errstate(over='ignore'):
+                    ratio = np.float32(FP8_TARGETS[self.fmt[key]]) / np.float32(a)
+                # the exponent field of the fp32 quotient, as the kernel reads it: an amax so small that the quotient overflows
+                # (infinity: field 255) lands on the upper clamp
+                e = int((np.asarray(ratio, np.float32).view(np.uint32) >> np.uint32(23)) & np.uint32(0xFF)) - 127
+                self.scale[key] = np.float32(2.0) ** int(np.clip(e, -100, 100))
             self.amax[key] = np.float32(0.0)
 
 

@@ -163,6 +163,57 @@ def colsum_groups(v):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------
+# pieces the kernel-level test files share (test_gemm_kernels.py, test_fp8_kernels.py).  torch is imported inside them: this
+# module is also loaded by worker processes that must stay numpy-only (oracle_fit_job)
+# ---------------------------------------------------------------------------------------------------------
+DEV = "cuda:0"
+SENT = -768.0                    # sentinel of every output buffer: exact in bf16, far outside the value range
+
+
+def _rng(*key):
+    return np.random.default_rng([int(k) & 0xFFFFFFFF for k in key])
+
+
+def _embed(x, rows, ld, dtype, fill=float("nan")):
+    """[nb][m][n] -> buffer [nb][rows][ld] of `dtype`, everything outside [m][n] holding `fill`"""
+    import torch
+    nb, m, n = x.shape
+    t = torch.full((nb, rows, ld), fill, dtype=dtype, device=DEV)
+    t[:, :m, :n] = x.to(dtype)
+    return t
+
+
+def _usage(err, bound):
+    """largest err / bound and where (0 / 0 = 0, x / 0 = inf, NaN = inf)"""
+    import torch
+    inf = torch.full_like(err, float("inf"))
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, inf, torch.zeros_like(err)))
+    ratio = torch.where(torch.isnan(err), inf, ratio)
+    i = int(torch.argmax(ratio))
+    return float(ratio.reshape(-1)[i]), tuple(int(v) for v in np.unravel_index(i, tuple(ratio.shape)))
+
+
+def _assert_close(label, got, ref, bound, acc_bound=None):
+    err = (got - ref).abs()
+    use, at = _usage(err, bound)
+    msg = "%s: usage %.3f at %s (got %r want %r bound %.3g)" % (label, use, at, float(got[at]), float(ref[at]), float(bound[at]))
+    if acc_bound is not None:
+        msg += " | accumulation term used %.4f" % _usage(err, acc_bound)[0]
+    print(msg)
+    assert use <= 1.0, msg
+    return use
+
+
+def _assert_sentinel(label, buf, inside, value=SENT):
+    """every element of `buf` outside the boolean region `inside` still holds the sentinel"""
+    import torch
+    bad = (buf != value) & ~inside
+    if bool(bad.any()):
+        at = tuple(int(v[0]) for v in torch.nonzero(bad, as_tuple=True))
+        raise AssertionError("%s: sentinel overwritten at %s (%d elements), holds %r" % (label, at, int(bad.sum()), float(buf[at])))
+
+
 def oracle_logmel(contacts, sr=48000, n_mels=128):
     """CPU stand-in for the GPU front end of dataset() (the suite runs without a GPU; tests/test_gpu_parity.py holds the HIP
     kernel to it)"""

@@ -21,11 +21,10 @@ import pytest
 import torch
 
 from oracle import mrgan_oracle as O
-from tests.helpers import colsum_groups, colsum_rows, mask_decode, mask_encode
+from tests.helpers import DEV, SENT, _assert_close, _assert_sentinel, _embed, _rng, _usage, colsum_groups, colsum_rows, mask_decode, mask_encode
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 F32, BF16 = 0, 1
 FWD, DX, SLAB = 0, 1, 2
 LIN, RELU, SOFTPLUS = 0, 1, 2
@@ -43,7 +42,6 @@ BF16_RND = 2.0 ** -8             # a float32 matmul of bf16 operands rounded to 
 SOFTPLUS_ABS, SOFTPLUS_REL = 2.0 ** -20, 2.0 ** -22
 # one_minus_exp_neg_fast(h) = 1 - exp2(-log2e h), h >= 0: exp2 as above (<= 1.4 * 2^-23) + the subtraction's 2^-24; twice that
 SIGMOID_ABS = 2.0 ** -21
-SENT = -768.0                    # sentinel of every output buffer: exact in bf16, far outside the value range
 MASK_SENT = 0x5A5A
 PAD, GAP = 64, 5                 # extra columns of every leading dimension, extra rows between batches
 TILE = {0: (64, 128, 2, 2, 3), 1: (128, 128, 2, 2, 2), 3: (256, 256, 2, 4, 2), 5: (64, 128, 2, 2, 2), 7: (128, 128, 2, 4, 2),
@@ -67,55 +65,15 @@ def f32_name(epi, m, n, nbatch=1, splits=1):
     return "gemm_f32_kernel<%d, %d>" % (epi, 128 if blocks128 >= 128 else 64)
 
 
-def _rng(*key):
-    return np.random.default_rng([int(k) & 0xFFFFFFFF for k in key])
-
-
 def _draw(rng, shape, scale=1.0):
     """N(0, scale^2) rounded to bf16, as float64 on the device"""
     return torch.from_numpy(rng.standard_normal(shape) * scale).to(torch.bfloat16).to(DEV, torch.float64)
-
-
-def _embed(x, rows, ld, dtype, fill=float("nan")):
-    """[nb][m][n] -> buffer [nb][rows][ld] of `dtype`, everything outside [m][n] holding `fill`"""
-    nb, m, n = x.shape
-    t = torch.full((nb, rows, ld), fill, dtype=dtype, device=DEV)
-    t[:, :m, :n] = x.to(dtype)
-    return t
 
 
 def _launch(E, desc, **kw):
     rc, name = E.debug_gemm_launch(desc, **kw)
     assert rc == 0, (rc, E.load_library().mrgan_last_error())
     return name
-
-
-def _usage(err, bound):
-    """largest err / bound and where (0 / 0 = 0, x / 0 = inf, NaN = inf)"""
-    inf = torch.full_like(err, float("inf"))
-    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, inf, torch.zeros_like(err)))
-    ratio = torch.where(torch.isnan(err), inf, ratio)
-    i = int(torch.argmax(ratio))
-    return float(ratio.reshape(-1)[i]), tuple(int(v) for v in np.unravel_index(i, tuple(ratio.shape)))
-
-
-def _assert_close(label, got, ref, bound, acc_bound=None):
-    err = (got - ref).abs()
-    use, at = _usage(err, bound)
-    msg = "%s: usage %.3f at %s (got %r want %r bound %.3g)" % (label, use, at, float(got[at]), float(ref[at]), float(bound[at]))
-    if acc_bound is not None:
-        msg += " | accumulation term used %.4f" % _usage(err, acc_bound)[0]
-    print(msg)
-    assert use <= 1.0, msg
-    return use
-
-
-def _assert_sentinel(label, buf, inside, value=SENT):
-    """every element of `buf` outside the boolean region `inside` still holds the sentinel"""
-    bad = (buf != value) & ~inside
-    if bool(bad.any()):
-        at = tuple(int(v[0]) for v in torch.nonzero(bad, as_tuple=True))
-        raise AssertionError("%s: sentinel overwritten at %s (%d elements), holds %r" % (label, at, int(bad.sum()), float(buf[at])))
 
 
 def run_kc(dtype, op, m, n, k, cfg=-1, act=LIN, nbatch=1, n_valid=None, noise=None, mask=None, cs_mode=CS_NONE, key=0,

@@ -134,6 +134,54 @@ int main(void) {
                     ctypes.sizeof(E.DiscArgs), ctypes.sizeof(E.GenArgs)]
 
 
+def test_debug_gemm_desc_layout_matches_header():
+    """mrgan_debug_gemm_desc (mrgan_debug.h) against engine.DebugGemmDesc: size, the last field from before the fp8 fields, and
+    the first and last of those"""
+    from mr_gan_amd import engine as E
+    prog = r'''
+#include <stdio.h>
+#include <stddef.h>
+#include "mrgan_debug.h"
+int main(void) {
+  printf("%zu %zu %zu %zu %zu %zu\n", sizeof(mrgan_debug_gemm_desc), offsetof(mrgan_debug_gemm_desc, seed),
+         offsetof(mrgan_debug_gemm_desc, slab_stride), offsetof(mrgan_debug_gemm_desc, q8), offsetof(mrgan_debug_gemm_desc, gauss),
+         sizeof(mrgan_debug_fold));
+  return 0; }'''
+    with tempfile.TemporaryDirectory() as d:
+        c = os.path.join(d, "t.c")
+        open(c, "w").write(prog)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", os.path.join(d, "t")])
+        vals = [int(v) for v in subprocess.check_output([os.path.join(d, "t")]).split()]
+    D = E.DebugGemmDesc
+    assert vals == [ctypes.sizeof(D), D.seed.offset, D.slab_stride.offset, D.q8.offset, D.gauss.offset, ctypes.sizeof(E.DebugFold)]
+    assert D._fields_[-1][0] == "gauss" and D.q8.offset == D.slab_stride.offset + 8
+
+
+def test_fp8_round_equals_torch_casts_on_every_bf16_value():
+    """The kernel-level fp8 tests encode operands and decode outputs with torch's float8 casts (tensor.view(torch.uint8)); the
+    mirror rounds with oracle.fp8_round.  Both are the same grid: every finite bf16 bit pattern, times a power-of-two slot scale,
+    clamped to the format's largest finite value as the packer does, gives the same dequantised value."""
+    import torch
+    bits = np.arange(65536, dtype=np.uint32)
+    bits = bits[((bits >> 7) & 0xFF) != 0xFF]                    # exponent 255: infinities and NaNs
+    assert bits.size == 65280
+    x = (bits << 16).astype(np.uint32).view(np.float32)
+    for fmt, tdt in (('e4m3', torch.float8_e4m3fn), ('e5m2', torch.float8_e5m2)):
+        lim = np.float32(O.FP8_FORMATS[fmt][2])
+        for scale in (1.0, 2.0 ** -7, 2.0 ** 9):
+            with np.errstate(over='ignore'):                     # the largest bf16 values times 2^9: infinity, then the clamp
+                v = np.clip(x * np.float32(scale), -lim, lim)
+            got = torch.from_numpy(v).to(tdt)
+            want = O.fp8_round(v, fmt)
+            diff = int((got.to(torch.float64).numpy() != want).sum())
+            assert diff == 0, (fmt, scale, diff)
+            # and the byte decoder: bytes -> values is the inverse on the grid
+            back = got.view(torch.uint8).view(tdt).to(torch.float64).numpy()
+            assert np.array_equal(back, want)
+            # 0x7F / 0xFF (NaN in both formats) is never emitted: the byte the GPU tests use as sentinel and as poison
+            assert not ((got.view(torch.uint8).numpy() & 0x7F) == 0x7F).any()
+
+
 def test_tuning_knobs_match_header():
     """engine.TUNE_* carry the values of the MRGAN_TUNE_* enumerators, and nothing else (retired knob numbers stay retired)"""
     from mr_gan_amd import engine as E
