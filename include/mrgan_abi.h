@@ -54,10 +54,11 @@ enum {
                                   * and a slower epilogue in every noisy forward product and in the staging kernel.  Every
                                   * entry honours it: mrgan_disc_step / mrgan_gen_step and their phases, mrgan_train_pair
                                   * with and without graph replay, data-parallel shards (rows stay global: the shards of a
-                                  * batch draw what the full batch would), mrgan_sup_step.  Host-supplied z is untouched.  */
+                                  * batch draw what the full batch would), mrgan_sup_step, mrgan_sup_step_group.  Host-supplied z is untouched.  */
 };
 
 #define MRGAN_MAX_CLASSES 32   /* largest mrgan_config.num_classes */
+#define MRGAN_MAX_MODELS 16    /* largest mrgan_config.models */
 
 /* Hyper-parameters are literals inside mr_gan() in the reference (mr_gan.py:77-79, :111-128, :165);
  * mrgan_default_config() fills exactly those values. */
@@ -78,7 +79,9 @@ typedef struct mrgan_config {
     uint64_t seed;            /* key of the device Philox streams (layer noise, z) */
     int32_t rank, world;      /* data-parallel position: global batch = batch*world, noise rows offset by rank*batch */
     int32_t flags;
-    int32_t reserved;
+    int32_t models;           /* 0 or 1: one model (the handle every other entry describes).  2 .. MRGAN_MAX_MODELS: a GROUP handle,
+                               * `models` independent trainings of this shape that step together in one launch set
+                               * (mrgan_sup_step_group).  Model m draws what a single handle with seed + m draws.             */
 } mrgan_config;
 
 int mrgan_default_config(mrgan_config* cfg, int32_t d_in, int32_t batch);
@@ -89,6 +92,17 @@ int mrgan_workspace_bytes(const mrgan_config* cfg, size_t* bytes);
 int mrgan_create(const mrgan_config* cfg, void* workspace_dev, size_t bytes, mrgan_stream stream, mrgan_handle** out);
 int mrgan_destroy(mrgan_handle* h);
 const char* mrgan_last_error(void);
+
+/* Group handles (mrgan_config.models > 1): G trainings of equal shape with different weights whose supervised step runs as
+ * ONE launch set (one launch per kernel kind, whatever G is).  The workspace holds the single-model layout once per model
+ * (mrgan_workspace_bytes = models x the single size rounded up to 256 B); the iteration counter and the batch counter are
+ * shared, all models step together.  mrgan_create refuses models > 1 together with MRGAN_FP8, MRGAN_FLAG_FLAT_GRADS,
+ * MRGAN_FLAG_SYNC_STATS or world != 1.  A group handle trains through mrgan_sup_step_group only: mrgan_disc_step,
+ * mrgan_gen_step, mrgan_train_pair, mrgan_fp8_calibration and mrgan_sup_step fail with status -3 (the grouped GAN step is not
+ * built).  mrgan_select_model chooses the model (default 0) that mrgan_set_weights / mrgan_get_weights, mrgan_get_slot /
+ * mrgan_set_slot, mrgan_eval_error and mrgan_predict_logits address; evaluation runs model by model with the single-model
+ * kernels.  mrgan_tensor_shape, mrgan_num_tensors and mrgan_get_iterations are the same for every model. */
+int mrgan_select_model(mrgan_handle* h, int model);
 
 /* Weights in Keras order.  G: W1 b1 gamma beta W2 b2 W3 b3 (generator.trainable_weights, mr_gan.py:131);
  * D: (W,b) x 6 (discriminator.trainable_weights, mr_gan.py:132).  Dense fp32 [rows, cols] row-major. */
@@ -154,6 +168,18 @@ typedef struct mrgan_sup_args {
     int32_t stream_mode, rows_valid;
 } mrgan_sup_args;
 int mrgan_sup_step(mrgan_handle* h, const mrgan_sup_args* a, float* out2_host, mrgan_stream stream);
+/* mrgan_sup_step once per model of a group handle, as one launch set.  Model m reads x_dev + m * x_model_stride (row pitch
+ * ld_x), idx_dev + m * idx_model_stride (when idx_dev is given) and labels_dev + m * labels_model_stride; the strides count
+ * elements.  x_model_stride = 0 lets every model gather from one matrix through its own index vector.  rows_valid and
+ * stream_mode are common to all models.  out2_host (optional): [models][2] = loss, training error per model.  A single-model
+ * handle refuses this entry (status -3). */
+typedef struct mrgan_sup_group_args {
+    const float* x_dev; const int32_t* idx_dev; const int32_t* labels_dev;
+    int64_t ld_x;
+    int64_t x_model_stride, idx_model_stride, labels_model_stride;
+    int32_t stream_mode, rows_valid;
+} mrgan_sup_group_args;
+int mrgan_sup_step_group(mrgan_handle* h, const mrgan_sup_group_args* a, float* out2_host, mrgan_stream stream);
 
 /* Log-mel front end of the contact-microphone modality (mr_gan.py:42-47: librosa.feature.melspectrogram(y, sr, n_mels=128)
  * followed by librosa.logamplitude(S, ref_power=np.max); n_fft 2048, hop 512, Slaney mel basis, -80 dB floor).  No handle:

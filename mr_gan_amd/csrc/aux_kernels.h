@@ -19,12 +19,18 @@ struct StageSeg {
     int gen;                                        // 1: out = N(0,1) only (z drawn on device), src ignored
     int stream;                                     // 1: o = batch * rows from the device batch counter
     uint32_t iter_off;                              // noise key uses DevState::iter + iter_off (z of a later sub-step)
+    // Model groups: the segment once per model (0 or 1: one model; the same count in every segment of a launch).  Model m reads
+    // src + m * src_ms and idx + m * idx_ms (elements; src_ms = 0: every model gathers from one matrix), writes out + m * out_ms
+    // (bytes) and draws its noise with seed + m.
+    int models; long src_ms, idx_ms, out_ms;
 };
 struct StageArgs {
     StageSeg s[5]; int nseg;
     uint64_t seed; uint32_t row0;
     const DevState* cur;
     int gauss;                                      // 0 = Irwin-Hall noise / z, 1 = true Gaussian (MRGAN_FLAG_GAUSS_NOISE)
+    // set by launch_stage: grid.y = model * ry + row block, model = (blockIdx.y * ry_mul) >> 16 (ry_mul = 0: one model)
+    int ry; uint32_t ry_mul;
 };
 int launch_stage(int bf16, const StageArgs& a, hipStream_t s);
 
@@ -67,6 +73,9 @@ struct HeadArgs {
     float* part; long part_stride;             // per-block partial gradients: part[blk][0 .. feat*KP) = dW6,
     int off_db, off_dbf;                       //   [off_db .. +KP) = db6, [off_dbf .. +feat) = bias grad of the feature layer
     float* loss_part;                          // [blk][4] : sum loss_lab, sum loss_unl terms, sum err, 0
+    // Model groups: grid.z = models (0 or 1: one model).  Model m's f, w, b, logits, dpre, part and loss_part lie model_stride
+    // BYTES behind model 0's, its labels labels_ms elements behind; st is shared.  Training heads without fp8 copies only.
+    int models; long model_stride, labels_ms;
     int* err_count;                            // HEAD_EVAL: integer count of argmax != label
     // fp8 mode: dpre leaves as e5m2 copies scaled by q8_slot->scale (row-major [seg][rows][ldq8] and transposed [feat][ldq8t] with
     // segment s at row offset s * q8t_bs), max |dpre| -> q8_slot; dpre itself may then be null
@@ -76,7 +85,9 @@ struct HeadArgs {
 };
 int launch_head(int bf16, const HeadArgs& a, hipStream_t s);
 // dst[g][i] = sum over partial rows p = g, g+ngroups, ... of src[p][i]  (i < n, rows `stride` apart)
-int launch_reduce_partials(const float* src, int nsrc, long stride, int n, int ngroups, float* dst, hipStream_t s);
+// (model groups: the fold once per model, src / dst of model m model_stride bytes behind model 0's)
+int launch_reduce_partials(const float* src, int nsrc, long stride, int n, int ngroups, float* dst, hipStream_t s, int models = 1,
+                           long model_stride = 0);
 int init_kernel_attributes();
 
 // ---- feature matching (mr_gan.py:152-154) ----
@@ -120,6 +131,9 @@ struct AdamArgs {
     // The updating launch is the last kernel of a sub-step: it publishes the next sub-step's DevState slot
     // (iterations + 1, batch counter + advance_batch, lr_t of the new iteration).  Null for ADAM_REDUCE_ONLY.
     DevState* next; int advance_batch; float lr;
+    // Model groups: grid.y = models (0 or 1: one model).  Model m's tensors (every pointer of a tile), loss_part, step_out and
+    // accum lie model_stride BYTES behind model 0's; st / next are shared, and model 0's block 0 alone publishes `next`.
+    int models; long model_stride;
 };
 int launch_adam(const AdamArgs& a, hipStream_t s);
 

@@ -50,24 +50,30 @@ __global__ __launch_bounds__(256) void stage_kernel(const StageArgs a) {
     float (*glds)[32][32 + 4] = (float (*)[32][32 + 4])nraw;
     const DevState st = *a.cur;
     const StageSeg& sg = a.s[blockIdx.z];
+    // model groups (StageSeg::models): grid.y = model * ry + row block; a multiply instead of a division, and nothing the
+    // segment's fields wait for
+    const int model = (int)((blockIdx.y * a.ry_mul) >> 16), yblk = (int)blockIdx.y - model * a.ry;
+    const uint64_t seed = a.seed + (uint64_t)model;
     const int lane = threadIdx.x & 63, lc = lane & 31, lh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int rbase = (blockIdx.y * 4 + wave) * 32, cbase = (int)blockIdx.x * 128;
+    const int rbase = (yblk * 4 + wave) * 32, cbase = (int)blockIdx.x * 128;
     if (rbase >= sg.rows || cbase >= sg.cols_pad) return;          // wave-uniform; no block-level barrier below
     const long o = sg.stream ? (long)st.batch * sg.rows : 0;
-    T* out = (T*)sg.out;
+    T* out = (T*)((char*)sg.out + (long)model * sg.out_ms);
+    const float* const xsrc = sg.src + (long)model * sg.src_ms;
+    const int32_t* const xidx = sg.idx ? sg.idx + (long)model * sg.idx_ms : nullptr;
     const bool noisy = sg.gen || sg.sigma > 0.f;
     const float sigs = (sg.gen ? 1.0f : sg.sigma) * (GAUSS ? 1.0f : NOISE_SCALE);
     const int cg = (lane & 15) * 8, rl = lane >> 4;                // lane <-> (8 columns, every 4th row)
     const int col = cbase + cg;
-    const bool vec_ok = !sg.gen && (sg.ld & 3) == 0 && ((uintptr_t)sg.src & 15) == 0 && col + 7 < sg.cols;
+    const bool vec_ok = !sg.gen && (sg.ld & 3) == 0 && ((uintptr_t)xsrc & 15) == 0 && col + 7 < sg.cols;
     // source rows first, then every row's loads in flight together (a dependent index -> row chain per iteration is
     // latency-bound: this kernel is 40 MB of traffic and must not take longer than a GEMM)
     long srow[8];
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
         const int row = rbase + it * 4 + rl;
-        srow[it] = (!sg.gen && row < sg.rows) ? (sg.idx ? (long)sg.idx[o + row] : (o + row)) : 0;
+        srow[it] = (!sg.gen && row < sg.rows) ? (xidx ? (long)xidx[o + row] : (o + row)) : 0;
     }
     float v[8][8];
 #pragma unroll
@@ -76,7 +82,7 @@ __global__ __launch_bounds__(256) void stage_kernel(const StageArgs a) {
         for (int c = 0; c < 8; ++c) v[it][c] = 0.f;
         const int row = rbase + it * 4 + rl;
         if (!sg.gen && row < sg.rows) {
-            const float* src = sg.src + srow[it] * sg.ld + col;
+            const float* src = xsrc + srow[it] * sg.ld + col;
             if (vec_ok) load8<float>(src, v[it]);
             else {
 #pragma unroll
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(256) void stage_kernel(const StageArgs a) {
     // round 2, with nothing in flight)
     if constexpr (GAUSS) {
         if (noisy) {
-            const uint32_t ph = gauss_pairhash(noise_key(a.seed, sg.site * 256u + sg.seg, st.iter + sg.iter_off), a.row0 + (uint32_t)rbase, lane);
+            const uint32_t ph = gauss_pairhash(noise_key(seed, sg.site * 256u + sg.seg, st.iter + sg.iter_off), a.row0 + (uint32_t)rbase, lane);
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) {
                 const int c0 = cbase + cb * 32;
@@ -114,7 +120,7 @@ __global__ __launch_bounds__(256) void stage_kernel(const StageArgs a) {
             }
         }
     } else if (noisy) {
-        const uint32_t rowhash = noise_rowhash(noise_key(a.seed, sg.site * 256u + sg.seg, st.iter + sg.iter_off), a.row0 + (uint32_t)(rbase + lc));
+        const uint32_t rowhash = noise_rowhash(noise_key(seed, sg.site * 256u + sg.seg, st.iter + sg.iter_off), a.row0 + (uint32_t)(rbase + lc));
         const i32x4 hfrag = hadamard_frag(lane);
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) {
@@ -300,7 +306,9 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
     const int seg = blockIdx.y, kind = a.seg_kind[seg];
     const int row_blk = blockIdx.x * HR;
     const int blk = seg * gridDim.x + blockIdx.x;
-    const T* f = (const T*)a.f + (long)seg * a.f_bs;
+    const long moff = (long)blockIdx.z * a.model_stride;          // model groups (HeadArgs::models): this model's tensors
+    const T* f = (const T*)((const char*)a.f + moff) + (long)seg * a.f_bs;
+    const float* const w6 = (const float*)((const char*)a.w + moff);
 
     const int cpr = CH / 8;                    // 8-element chunks per row
     auto load_chunk = [&](int c0) {
@@ -317,7 +325,7 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
             for (int g = 0; g < KG; ++g) w[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
             if (c0 + k < a.feat_valid) {
 #pragma unroll
-                for (int g = 0; g < KG; ++g) w[g] = *(const f32x4*)(a.w + (long)(c0 + k) * a.ldw + 4 * g);
+                for (int g = 0; g < KG; ++g) w[g] = *(const f32x4*)(w6 + (long)(c0 + k) * a.ldw + 4 * g);
             }
 #pragma unroll
             for (int c = 0; c < 4; ++c)
@@ -362,11 +370,11 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
     const bool rowvalid = row < a.rows;
     float b[KP];
 #pragma unroll
-    for (int c = 0; c < KP; ++c) b[c] = (c < a.classes) ? a.b[c] : 0.f;
+    for (int c = 0; c < KP; ++c) b[c] = (c < a.classes) ? ((const float*)((const char*)a.b + moff))[c] : 0.f;
     int y = 0;
     if (rowvalid && head_kind_has_label(kind)) {
         const long lo = a.labels_stream ? (long)a.st->batch * a.rows : 0;
-        y = a.labels[lo + row];
+        y = a.labels[(long)blockIdx.z * a.labels_ms + lo + row];
     }
     float loss0, loss1, err, dl[KP];
     head_row<true>(l, b, kind, y, a.classes, a.inv_count, a.unl_weight, rowvalid, loss0, loss1, err, dl);
@@ -374,7 +382,7 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
 #pragma unroll
         for (int g = 0; g < KG; ++g) *(f32x4*)(dl_lds + r * KP + 4 * g) = (f32x4){dl[4 * g], dl[4 * g + 1], dl[4 * g + 2], dl[4 * g + 3]};
         if (a.logits && rowvalid) {
-            float* lp = a.logits + (long)seg * a.logits_bs + (long)row * KP;
+            float* lp = (float*)((char*)a.logits + moff) + (long)seg * a.logits_bs + (long)row * KP;
 #pragma unroll
             for (int c = 0; c < KP; ++c) lp[c] = (c < a.classes) ? l[c] : 0.f;
         }
@@ -387,20 +395,21 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
         for (int w = 0; w < 4; ++w) { s0 += red[w * 4 + 0]; s1 += red[w * 4 + 1]; s2 += red[w * 4 + 2]; }
         if (kind == HEAD_EVAL) { if (a.err_count) atomicAdd(a.err_count, (int)(s2 + 0.5f)); }
         else if (kind != HEAD_LOGITS) {
-            a.loss_part[blk * 4 + 0] = s0; a.loss_part[blk * 4 + 1] = s1;
-            a.loss_part[blk * 4 + 2] = s2; a.loss_part[blk * 4 + 3] = 0.f;
+            float* lpart = (float*)((char*)a.loss_part + moff);
+            lpart[blk * 4 + 0] = s0; lpart[blk * 4 + 1] = s1;
+            lpart[blk * 4 + 2] = s2; lpart[blk * 4 + 3] = 0.f;
         }
     }
     if (kind == HEAD_EVAL || kind == HEAD_LOGITS) return;
 
     // ---- backward of the last dense: thread <-> feature column j ----
-    float* part_row = a.part + (long)blk * a.part_stride;
+    float* part_row = (float*)((char*)a.part + moff) + (long)blk * a.part_stride;
     if (t < KP) {
         float s = 0.f;
         for (int rr = 0; rr < HR; ++rr) s += dl_lds[rr * KP + t];
         part_row[a.off_db + t] = s;
     }
-    T* dpre = a.dpre ? (T*)a.dpre + (long)seg * a.dpre_bs : nullptr;
+    T* dpre = a.dpre ? (T*)((char*)a.dpre + moff) + (long)seg * a.dpre_bs : nullptr;
     // fp8 mode: the e5m2 copies of dpre that the dX / dW products read (one column's HR rows = HR contiguous bytes of the
     // transposed copy); packed from the fp32 value
     const float q8s = a.q8_slot ? a.q8_slot->scale : 1.f;
@@ -474,9 +483,12 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
 }
 
 // dst[g][i] = sum of src[p][i] over the partial rows p of group g (p = g, g + ngroups, ...)
-__global__ __launch_bounds__(256) void reduce_partials_kernel(const float* src, int nsrc, long stride, int n, int ngroups, float* dst) {
+__global__ __launch_bounds__(256) void reduce_partials_kernel(const float* src, int nsrc, long stride, int n, int ngroups, float* dst,
+                                                              long model_stride) {
     const int i = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
     if (i >= n) return;
+    src = (const float*)((const char*)src + (long)blockIdx.z * model_stride);      // model groups: grid.z = models
+    dst = (float*)((char*)dst + (long)blockIdx.z * model_stride);
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     int p = g;
     for (; p + 3 * ngroups < nsrc; p += 4 * ngroups) {
@@ -632,6 +644,9 @@ __device__ __forceinline__ void flat_store(const AdamTile& tile, long off, const
     else *(f32x4*)(tile.flat + off) = g;
 }
 
+template <typename P>
+__device__ __forceinline__ void shift_ptr(P*& p, long bytes) { if (p) p = (P*)((char*)p + bytes); }
+
 __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
     __shared__ float tl[64 * 65];
     const int t = threadIdx.x;
@@ -639,7 +654,12 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
     // in dispatch order, so that it runs beside the tile blocks instead of behind them
     const int tile_id = (int)blockIdx.x - 1;
     if (tile_id >= 0) {
-    const AdamTile tile = a.tiles[tile_id];
+    AdamTile tile = a.tiles[tile_id];
+    {   // model groups (AdamArgs::models): the table describes model 0, this block works on model blockIdx.y
+        const long mo = (long)blockIdx.y * a.model_stride;
+        shift_ptr(tile.p, mo); shift_ptr(tile.m, mo); shift_ptr(tile.v, mo); shift_ptr(tile.g, mo); shift_ptr(tile.flat, mo);
+        shift_ptr(tile.flat16, mo); shift_ptr(tile.w16, mo); shift_ptr(tile.wt16, mo);
+    }
     const float lr_t = a.st->lr_t;
     const int qpr = tile.cols >> 2;                       // four-element groups per row
     const int nq = tile.rows * qpr;
@@ -742,7 +762,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
     if (tile.w8_slot && a.mode != ADAM_REDUCE_ONLY) fp8_amax_commit(tile.w8_slot, w8_amax);
     }
     // ---- block 0: the next sub-step's DevState, and this sub-step's loss partials ----
-    if (tile_id < 0 && t == 0 && a.next && a.mode != ADAM_REDUCE_ONLY) {
+    if (tile_id < 0 && t == 0 && blockIdx.y == 0 && a.next && a.mode != ADAM_REDUCE_ONLY) {
         const DevState st = *a.st;
         DevState nx;
         nx.iter = st.iter + 1;
@@ -754,11 +774,15 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
     }
     if (tile_id < 0 && a.step_out) {
         __shared__ float ms[3][256];
+        const long mo = (long)blockIdx.y * a.model_stride;         // the metrics finish runs per model
+        const float* const loss_part = (const float*)((const char*)a.loss_part + mo);
+        float* const step_out = (float*)((char*)a.step_out + mo);
+        float* const accum = (float*)((char*)a.accum + mo);
         float s[3] = {0.f, 0.f, 0.f};
         if (a.mode == ADAM_FROM_FLAT) { if (t == 0) for (int i = 0; i < 3; ++i) s[i] = a.flat_tail[i]; }
         else {
             for (int b = t; b < a.nloss_part; b += 256)
-                for (int i = 0; i < 3; ++i) s[i] += a.loss_part[b * 4 + i];
+                for (int i = 0; i < 3; ++i) s[i] += loss_part[b * 4 + i];
             for (int i = 0; i < 3; ++i) ms[i][t] = s[i];
             __syncthreads();
             if (t == 0) {
@@ -771,7 +795,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
         }
         if (t == 0) {
             if (a.mode == ADAM_REDUCE_ONLY) { for (int i = 0; i < 3; ++i) a.flat_tail[i] = s[i]; a.flat_tail[3] = 0.f; }
-            else { for (int i = 0; i < 3; ++i) { a.step_out[i] = s[i]; a.accum[i] += s[i]; } }
+            else { for (int i = 0; i < 3; ++i) { step_out[i] = s[i]; accum[i] += s[i]; } }
         }
     }
 }
@@ -809,13 +833,21 @@ __global__ __launch_bounds__(64) void noise_debug_kernel(int gauss, uint64_t see
 #define RET_LAUNCH return hipGetLastError() == hipSuccess ? 0 : -2
 
 int launch_stage(int bf16, const StageArgs& a, hipStream_t s) {
-    int maxc = 0, maxr = 0;
-    for (int i = 0; i < a.nseg; ++i) { maxc = max(maxc, a.s[i].cols_pad); maxr = max(maxr, a.s[i].rows); }
-    dim3 grid(ceil_div(maxc, 128), ceil_div(maxr, 128), a.nseg);
+    int maxc = 0, maxr = 0, maxm = 1;
+    for (int i = 0; i < a.nseg; ++i) { maxc = max(maxc, a.s[i].cols_pad); maxr = max(maxr, a.s[i].rows); maxm = max(maxm, a.s[i].models); }
+    for (int i = 0; i < a.nseg; ++i) if (max(1, a.s[i].models) != maxm) return -3;      // every segment of a launch once per model
+    StageArgs b = a;
+    b.ry = ceil_div(maxr, 128); b.ry_mul = 0;
+    if (maxm > 1) {
+        // the kernel's multiply-shift is the exact quotient while grid.y * ry < 65536 (batches up to 8192 rows at 16 models)
+        if ((long)b.ry * maxm * b.ry >= 65536) return -3;
+        b.ry_mul = (65536u + (uint32_t)b.ry - 1) / (uint32_t)b.ry + ((65536u % (uint32_t)b.ry) == 0 ? 1u : 0u);
+    }
+    dim3 grid(ceil_div(maxc, 128), b.ry * maxm, a.nseg);
     if (a.gauss) {
-        if (bf16) MRGAN_LAUNCH((stage_kernel<__bf16, true>), grid, dim3(256), 0, s, a);
-        else MRGAN_LAUNCH((stage_kernel<float, true>), grid, dim3(256), 0, s, a);
-    } else LAUNCH_T(stage_kernel, grid, dim3(256), 0, s, a);
+        if (bf16) MRGAN_LAUNCH((stage_kernel<__bf16, true>), grid, dim3(256), 0, s, b);
+        else MRGAN_LAUNCH((stage_kernel<float, true>), grid, dim3(256), 0, s, b);
+    } else LAUNCH_T(stage_kernel, grid, dim3(256), 0, s, b);
     RET_LAUNCH;
 }
 
@@ -850,7 +882,8 @@ int launch_head(int bf16, const HeadArgs& a, hipStream_t s) {
     const int kp = a.ldw;                      // the class pitch of W6, the logits and the partial-gradient rows
     if ((a.feat % 64) != 0 || (kp != KMAX && kp != KWIDE) || a.classes > kp) return -3;
     const size_t smem = sizeof(float) * ((size_t)HR * (ch + 8) + (size_t)ch * kp + HR * kp + 16);
-    dim3 grid(ceil_div(a.rows, HR), a.nseg);
+    dim3 grid(ceil_div(a.rows, HR), a.nseg, std::max(1, a.models));
+    if (a.models > 1 && (a.q8_slot || a.err_count)) return -3;      // model groups: training heads without fp8 copies
     if (kp == KWIDE) {
         if (a.q8_slot) return -3;              // the e5m2 packing epilogue exists at the 8-class pitch only
         if (bf16) MRGAN_LAUNCH((head_kernel<__bf16, false, KWIDE>), grid, dim3(256), smem, s, a);
@@ -869,8 +902,10 @@ int launch_head(int bf16, const HeadArgs& a, hipStream_t s) {
     RET_LAUNCH;
 }
 
-int launch_reduce_partials(const float* src, int nsrc, long stride, int n, int ngroups, float* dst, hipStream_t s) {
-    MRGAN_LAUNCH(reduce_partials_kernel, dim3(ceil_div(n, 256), ngroups), dim3(256), 0, s, src, nsrc, stride, n, ngroups, dst);
+int launch_reduce_partials(const float* src, int nsrc, long stride, int n, int ngroups, float* dst, hipStream_t s, int models,
+                           long model_stride) {
+    MRGAN_LAUNCH(reduce_partials_kernel, dim3(ceil_div(n, 256), ngroups, std::max(1, models)), dim3(256), 0, s, src, nsrc, stride, n, ngroups,
+                 dst, model_stride);
     RET_LAUNCH;
 }
 
@@ -896,7 +931,8 @@ int launch_colsum_finalize(const float* part1, const float* part2, int npart, in
 }
 
 int launch_adam(const AdamArgs& a, hipStream_t s) {
-    MRGAN_LAUNCH(adam_kernel, dim3(a.ntiles + 1), dim3(256), 0, s, a);
+    if (a.models > 1 && a.mode != ADAM_FUSED) return -3;      // model groups: the fused update only
+    MRGAN_LAUNCH(adam_kernel, dim3(a.ntiles + 1, std::max(1, a.models)), dim3(256), 0, s, a);
     RET_LAUNCH;
 }
 

@@ -67,6 +67,7 @@ int run_gemm(mrgan_handle* h, int epi, const GemmArgs& g, double algo_flops, dou
     const Epi& e = g.e;
     const bool fp8 = e.qa != nullptr;                 // the description carries fp8 operands
     const char* kname = fp8 ? "gemm_fp8" : "gemm";
+    algo_flops *= gemm_models(g); algo_bytes *= gemm_models(g);      // (a model group: the caller counted one model)
     prof_arm(h);
     const int r = fp8 ? launch_gemm_fp8(epi, g, s, &kname) : h->bf16 ? launch_gemm_bf16(epi, g, s, &kname) : launch_gemm_f32(epi, g, s, &kname);
     if (fp8) {
@@ -92,7 +93,8 @@ GemmArgs with_handle(mrgan_handle* h, GemmArgs g) {
     e.st = h->state + h->cur;
     e.ablate = h->ablate; e.tune_kc_cfg = h->tune_kc_cfg; e.tune_bits = h->tune_bits;
     e.seg_step = 1;
-    return g;
+    // a grouped step: the launch covers every model, model m's tensors W bytes behind model m - 1's
+    return gemm_group(g, h->grouped, (long)h->W);
 }
 
 // ---- what a dense product is told beside its operands ----
@@ -159,8 +161,11 @@ int dense_fwd(mrgan_handle* h, const Dense& L, int kind, const void* x, int rows
                                 : h->bf16 ? gemm_fwd_args(rows, L.Kp, L.Np, nb, x, a_bs, L.Kp, L.W->wt16, L.Kp, true)
                                           : gemm_fwd_args(rows, L.Kp, L.Np, nb, x, a_bs, L.Kp, L.W->p, L.Np, false));
     Epi& e = g.e;
-    if (kind == KIND_EVAL) e.st = nullptr;
     e.act = act; e.n_valid = L.N; e.bias = L.b->p;
+    if (kind == KIND_EVAL) {        // evaluation runs model by model: the selected model's weights (x and out are the caller's)
+        e.st = nullptr;
+        g.B = selected(h, g.B); e.bias = selected(h, e.bias);
+    }
     e.out = out; e.out_bs = (long)h->S * L.Np; e.ldo = L.Np;
     e.sigma = nz.sigma; e.site = nz.site; e.seg0 = nz.seg0; e.seg_step = nz.seg_step; e.iter_step = nz.iter_step;
     epi_mask(h, e, m);
@@ -229,7 +234,7 @@ int dense_dw_all(mrgan_handle* h, int kind, const DwJob* jobs, int n, int rows, 
     // the jobs without images first (order kept): the candidates of the grouped launch
     const int ngroup = (int)(std::stable_partition(js, js + n, [](const DwJob& j) { return !j.L->q.on; }) - js);
     for (int i = 0; i < n; ++i) fl[i] = dw_args(h, gs[i], *js[i].L, kind, js[i].x, js[i].dy, rows, nseg);
-    for (int i = 0; i < ngroup; ++i) { total += fl[i]; bytes += dw_bytes(h, (double)rows * nseg, *js[i].L); }
+    for (int i = 0; i < ngroup; ++i) { total += fl[i] * h->grouped; bytes += dw_bytes(h, (double)rows * nseg, *js[i].L) * h->grouped; }
     int first = 0;
     if (h->bf16 && ngroup > 0) {
         const char* kname = "gemm";
@@ -240,7 +245,8 @@ int dense_dw_all(mrgan_handle* h, int kind, const DwJob* jobs, int n, int rows, 
         if (r == 0) { first = ngroup; fold = nullptr; }
     }
     for (int i = first; i < n; ++i) CHK(run_gemm(h, EPI_SLAB, gs[i], fl[i], dw_bytes(h, (double)rows * nseg, *js[i].L), s));
-    if (fold) PROF("reduce_partials_kernel", launch_reduce_partials(fold->src, fold->nsrc, fold->stride, fold->n, fold->ngroups, fold->dst, s));
+    if (fold) PROF("reduce_partials_kernel", launch_reduce_partials(fold->src, fold->nsrc, fold->stride, fold->n, fold->ngroups, fold->dst, s,
+                                                                    h->grouped, fold->model_stride));
     return 0;
 }
 
@@ -274,6 +280,7 @@ int run_adam(mrgan_handle* h, int net, int mode, bool with_metrics, hipStream_t 
         a.step_out = h->step_out; a.accum = h->accum;
         a.flat_tail = h->flat_d + h->flat_d_n;
     }
+    a.models = h->grouped; a.model_stride = (long)h->W;
     {
         // Keras Adam reads p, m, v and the gradient and writes p, m, v: 28 B per parameter (+ the extra gradient slabs and the
         // two bf16 weight copies of the bf16 mode)
@@ -517,7 +524,8 @@ int disc_bwd(mrgan_handle* h, int nseg, int l_top, int fold_rows, hipStream_t s)
                      ColSums{CS_SUM, h->cs_db[l - 1], nullptr}, s, Fp8Use{&h->d[l - 1], true, false}));
     DwJob jobs[5];
     for (int l = 0; l < 5; ++l) jobs[l] = DwJob{&h->d[l], h->xin[l], h->dpre[l]};
-    const FoldJob fold = {h->head_part, h->head_red, (long)h->head_stride, fold_rows, h->head_stride, h->head_groups, 0};
+    const FoldJob fold = {h->head_part, h->head_red, (long)h->head_stride, fold_rows, h->head_stride, h->head_groups, 0,
+                          h->grouped > 1 ? (long)h->W : 0};
     return dense_dw_all(h, KIND_D, jobs, 5, h->B, nseg, s, &fold);
 }
 
@@ -691,6 +699,41 @@ int sup_step(mrgan_handle* h, const mrgan_sup_args* a, hipStream_t s) {
     return 0;
 }
 
+// The same step for every model of a group handle, as ONE launch set: each launch below is the launch of sup_step with the
+// model as a further grid index (h->grouped: with_handle / gemm_group for the products, the model fields of StageSeg, HeadArgs,
+// FoldJob and AdamArgs for the rest).  Model m stages its own rows, draws its noise with seed + m and updates its own copy of
+// the weights; the iteration counter is shared.
+int sup_step_group(mrgan_handle* h, const mrgan_sup_group_args* a, hipStream_t s) {
+    const int B = h->B;
+    struct Grouped { mrgan_handle* h; ~Grouped() { h->grouped = 1; } } scope{h};      // (every return path leaves the handle single)
+    h->grouped = h->models;
+    prof_backlog(h, s);
+    StageArgs st;
+    memset(&st, 0, sizeof st);
+    data_seg(st.s[0], h, a->x_dev, a->idx_dev, a->ld_x, 0, 0, a->stream_mode);
+    st.s[0].models = h->models; st.s[0].src_ms = a->x_model_stride; st.s[0].idx_ms = a->idx_model_stride; st.s[0].out_ms = (long)h->W;
+    st.nseg = 1;
+    stage_common(st, h, nullptr, 0, -1);
+    PROF("stage_kernel", launch_stage(h->bf16, st, s));
+    CHK(disc_fwd_train(h, 0, 1, false, 0, s, 5));
+    HeadArgs hd = head_args(h, {HEAD_MSE}, B, true);
+    hd.labels = a->labels_dev; hd.labels_stream = a->stream_mode;
+    hd.inv_count = 1.0f / (float)(a->rows_valid > 0 ? a->rows_valid : B); hd.unl_weight = 0.f;
+    hd.models = h->models; hd.model_stride = (long)h->W; hd.labels_ms = a->labels_model_stride;
+    PROF("head_kernel", launch_head(h->bf16, hd, s));
+    h->head_nblk = 3 * ceil_div(B, HEAD_ROWS);           // (as sup_step: the partial rows of the two other segments stay zero)
+    CHK(disc_bwd(h, 1, 4, ceil_div(B, HEAD_ROWS), s));
+    CHK(run_adam(h, MRGAN_NET_D, ADAM_FUSED, true, s, a->stream_mode ? 1 : 0));
+    h->cur ^= 1;
+    return 0;
+}
+
+// what a group handle does not do (status -3)
+int refuse_group(const mrgan_handle* h, const char* entry) {
+    if (h->models <= 1) return 0;
+    return fail(-3, "%s: a group handle (models = %d) trains through mrgan_sup_step_group only; the grouped GAN step (generator, BatchNorm, feature matching, chains) is not built", entry, h->models);
+}
+
 int check_disc_args(const mrgan_handle* h, const mrgan_disc_args* a) {
     if (!a || !a->x_lab_dev || !a->x_unl_dev || !a->labels_dev) return fail(-2, "disc_step: x_lab, x_unl and labels are required");
     if (a->ld_x_lab < h->cfg.d_in || a->ld_x_unl < h->cfg.d_in) return fail(-2, "disc_step: row pitch smaller than d_in");
@@ -712,19 +755,22 @@ int eval_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, cons
         memset(&st, 0, sizeof st);
         StageSeg& sg = st.s[0];
         sg.src = idx ? x : x + r0 * ld; sg.idx = idx ? idx + r0 : nullptr; sg.ld = ld; sg.rows = rows;
-        sg.cols = h->cfg.d_in; sg.cols_pad = h->Dp; sg.out = h->xin[0]; sg.ldo = h->Dp;
+        sg.cols = h->cfg.d_in; sg.cols_pad = h->Dp; sg.out = selected(h, h->xin[0]); sg.ldo = h->Dp;
         st.nseg = 1; st.seed = h->cfg.seed; st.cur = h->state + h->cur;
         PROF("stage_kernel", launch_stage(h->bf16, st, s));
         for (int l = 0; l < 5; ++l) {
             // one "segment" of `rows` contiguous rows: batch stride is irrelevant with nb = 1
-            CHK(dense_fwd(h, h->d[l], KIND_EVAL, h->xin[l], rows, 1, l < 4 ? h->xin[l + 1] : h->feat, ACT_RELU, NO_NOISE, NO_MASK, NO_SUMS, s));
+            // (a group handle evaluates the selected model: its activations here, its weights in dense_fwd)
+            CHK(dense_fwd(h, h->d[l], KIND_EVAL, selected(h, h->xin[l]), rows, 1, selected(h, l < 4 ? h->xin[l + 1] : h->feat), ACT_RELU, NO_NOISE,
+                          NO_MASK, NO_SUMS, s));
         }
         HeadArgs hd = head_args(h, {labels ? HEAD_EVAL : HEAD_LOGITS}, rows, false);
+        hd.f = selected(h, hd.f); hd.w = selected(h, hd.w); hd.b = selected(h, hd.b); hd.logits = selected(h, hd.logits);
         hd.labels = labels ? labels + r0 : nullptr;
         hd.err_count = labels ? h->err_count : nullptr;
         PROF("head_kernel", launch_head(h->bf16, hd, s));
         if (logits_out)
-            HIPCHK(hipMemcpy2DAsync(logits_out + r0 * h->cfg.num_classes, sizeof(float) * h->cfg.num_classes, h->logits,
+            HIPCHK(hipMemcpy2DAsync(logits_out + r0 * h->cfg.num_classes, sizeof(float) * h->cfg.num_classes, selected(h, h->logits),
                                     sizeof(float) * h->KP, sizeof(float) * h->cfg.num_classes, rows, hipMemcpyDeviceToDevice, s));
     }
     // The evaluation used the training activations as scratch and filled rows [0, 3S) of every layer input, i.e. also the
@@ -734,7 +780,7 @@ int eval_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, cons
     if (h->B < h->S) {
         for (int l = 0; l < 5; ++l)
             for (int sg = 0; sg < (l == 0 ? 5 : 3); ++sg) {
-                char* p = (char*)h->xin[l] + ((size_t)sg * h->S + h->B) * h->d[l].Kp * h->es;
+                char* p = (char*)selected(h, h->xin[l]) + ((size_t)sg * h->S + h->B) * h->d[l].Kp * h->es;
                 HIPCHK(hipMemsetAsync(p, 0, (size_t)(h->S - h->B) * h->d[l].Kp * h->es, s));
             }
     }
@@ -768,7 +814,8 @@ extern "C" {
 
 int mrgan_disc_step(mrgan_handle* h, const mrgan_disc_args* a, int p0, int p1, float* out3, mrgan_stream stream) {
     if (!h) return fail(-1, "null handle");
-    int r = check_disc_args(h, a);
+    int r = refuse_group(h, "disc_step");
+    if (!r) r = check_disc_args(h, a);
     if (r) return r;
     hipStream_t s = (hipStream_t)stream;
     if (p1 < 0) p1 = MRGAN_D_NPHASES - 1;
@@ -793,7 +840,8 @@ int mrgan_disc_step(mrgan_handle* h, const mrgan_disc_args* a, int p0, int p1, f
 
 int mrgan_gen_step(mrgan_handle* h, const mrgan_gen_args* a, int p0, int p1, float* out1, mrgan_stream stream) {
     if (!h) return fail(-1, "null handle");
-    int r = check_gen_args(h, a);
+    int r = refuse_group(h, "gen_step");
+    if (!r) r = check_gen_args(h, a);
     if (r) return r;
     hipStream_t s = (hipStream_t)stream;
     if (p1 < 0) p1 = MRGAN_G_NPHASES - 1;
@@ -818,6 +866,7 @@ int mrgan_gen_step(mrgan_handle* h, const mrgan_gen_args* a, int p0, int p1, flo
 
 int mrgan_fp8_calibration(mrgan_handle* h, int kind, int action, mrgan_stream stream) {
     if (!h || kind < 0 || kind > 1) return fail(-1, "fp8_calibration: bad handle or kind");
+    if (refuse_group(h, "fp8_calibration")) return -3;
     hipStream_t s = (hipStream_t)stream;
     if (action == MRGAN_FP8_CAL_QUERY) return (!h->fp8 || h->fp8_cal[kind] == 1) ? 1 : 0;
     if (!h->fp8) return 0;
@@ -841,6 +890,7 @@ int mrgan_logmel(const float* y_dev, int64_t n_trials, int64_t n_samples, int64_
 
 int mrgan_sup_step(mrgan_handle* h, const mrgan_sup_args* a, float* out2, mrgan_stream stream) {
     if (!h || !a || !a->x_dev || !a->labels_dev) return fail(-1, "sup_step: x and labels are required");
+    if (refuse_group(h, "sup_step")) return -3;
     if (a->ld_x < h->cfg.d_in) return fail(-2, "sup_step: row pitch smaller than d_in");
     if (h->flat_grads || h->cfg.world != 1) return fail(-3, "sup_step: single-GPU handles only");
     if (h->fp8) return fail(-3, "sup_step: the fp8 mode covers the GAN step only");
@@ -859,9 +909,31 @@ int mrgan_sup_step(mrgan_handle* h, const mrgan_sup_args* a, float* out2, mrgan_
     return 0;
 }
 
+int mrgan_sup_step_group(mrgan_handle* h, const mrgan_sup_group_args* a, float* out2, mrgan_stream stream) {
+    if (!h || !a || !a->x_dev || !a->labels_dev) return fail(-1, "sup_step_group: x and labels are required");
+    if (h->models <= 1) return fail(-3, "sup_step_group: not a group handle (mrgan_config.models = %d); a single model steps through mrgan_sup_step", (int)h->cfg.models);
+    if (a->ld_x < h->cfg.d_in) return fail(-2, "sup_step_group: row pitch smaller than d_in");
+    if (a->rows_valid < 0 || a->rows_valid > h->B) return fail(-2, "sup_step_group: rows_valid outside [0, batch]");
+    if (a->rows_valid && a->stream_mode) return fail(-2, "sup_step_group: a short batch cannot be combined with stream mode");
+    if (a->x_model_stride < 0 || a->idx_model_stride < 0 || a->labels_model_stride < 0) return fail(-2, "sup_step_group: negative model stride");
+    hipStream_t s = (hipStream_t)stream;
+    int r = sup_step_group(h, a, s);
+    if (r) return r;
+    if (out2) {
+        float o[MRGAN_MAX_MODELS][3];
+        for (int m = 0; m < h->models; ++m)
+            HIPCHK(hipMemcpyAsync(o[m], model_at(h, h->step_out, m), 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const float k = a->rows_valid > 0 ? (float)h->B / (float)a->rows_valid : 1.f;     // the metrics pass divides by the batch
+        for (int m = 0; m < h->models; ++m) { out2[2 * m] = o[m][0] * k; out2[2 * m + 1] = o[m][2] * k; }
+    }
+    return 0;
+}
+
 int mrgan_train_pair(mrgan_handle* h, const mrgan_disc_args* d, const mrgan_gen_args* g, mrgan_stream stream) {
     if (!h) return fail(-1, "null handle");
-    int r = check_disc_args(h, d);
+    int r = refuse_group(h, "train_pair");
+    if (!r) r = check_disc_args(h, d);
     if (!r) r = check_gen_args(h, g);
     if (r) return r;
     hipStream_t s = (hipStream_t)stream;

@@ -40,9 +40,9 @@ int mrgan_debug_ablate(mrgan_handle* h, int bits) {
 int mrgan_debug_buffer(mrgan_handle* h, int kind, int l, void** ptr, int* rows_per_seg, int* ld, int* elem_size) {
     if (!h || !ptr || l < 0 || l > 4) return fail(-1, "debug_buffer: bad argument");
     switch (kind) {
-        case 0: *ptr = h->xin[l]; *ld = h->d[l].Kp; break;
-        case 1: *ptr = h->dpre[l]; *ld = h->d[l].Np; break;
-        case 2: *ptr = h->feat; *ld = h->Fp; break;
+        case 0: *ptr = selected(h, h->xin[l]); *ld = h->d[l].Kp; break;      // (group handles: the selected model's buffer)
+        case 1: *ptr = selected(h, h->dpre[l]); *ld = h->d[l].Np; break;
+        case 2: *ptr = selected(h, h->feat); *ld = h->Fp; break;
         default: return fail(-1, "debug_buffer: unknown kind");
     }
     *rows_per_seg = h->S; *elem_size = h->es;

@@ -88,6 +88,13 @@ struct mrgan_handle {
     float stat_count, fm_scale;           // rows behind a batch statistic; 1/world when statistics stay per-shard
     int Dp, nzp, Fp, F;                   // padded input / z / feature widths
     char* ws; size_t ws_bytes;
+    // Model groups (mrgan_config.models > 1).  The workspace holds the single-model layout once per model, W bytes apart (W = 0
+    // for a single model); every pointer of this struct is MODEL 0's, model m's tensor lies m * W bytes behind it (model_at).
+    // The two DevState slots alone are shared: all models step together.
+    int models;                           // >= 1
+    size_t W;                             // model stride in bytes
+    int sel;                              // mrgan_select_model: the model the per-model entries address
+    int grouped;                          // models while a grouped step builds its launches (every launch covers all models), else 1
 
     std::vector<Tensor> gt, dt;           // Keras order
     Dense g[3], d[6];
@@ -139,6 +146,9 @@ struct mrgan_handle {
 
 namespace mrgan {
 
+// model m's copy of a per-model tensor of the workspace
+template <typename P> inline P* model_at(const mrgan_handle* h, P* p, int m) { return p ? (P*)((char*)p + (size_t)m * h->W) : p; }
+template <typename P> inline P* selected(const mrgan_handle* h, P* p) { return model_at(h, p, h->sel); }
 inline void* rowptr(mrgan_handle* h, void* base, long row, int ld) { return (char*)base + (size_t)row * ld * h->es; }
 inline Dense* net_layers(mrgan_handle* h, int net, int* n) { *n = net == MRGAN_NET_G ? 3 : 6; return net == MRGAN_NET_G ? h->g : h->d; }
 inline dim3 grid2d(int prow, int pcol) { return dim3(ceil_div(pcol, 64), ceil_div(prow, 4)); }

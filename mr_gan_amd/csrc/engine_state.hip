@@ -92,6 +92,14 @@ int validate(const mrgan_config& c) {
     if ((c.flags & MRGAN_FLAG_GRAD_BF16) && !(c.flags & MRGAN_FLAG_FLAT_GRADS)) return fail(-1, "MRGAN_FLAG_GRAD_BF16 requires MRGAN_FLAG_FLAT_GRADS");
     for (int i = 0; i < 5; ++i) if (c.d_hidden[i] < 1) return fail(-1, "bad d_hidden");
     if (c.g_hidden[0] < 1 || c.g_hidden[1] < 1 || c.noise_size < 1) return fail(-1, "bad generator sizes");
+    if (c.models < 0 || c.models > MRGAN_MAX_MODELS) return fail(-1, "models must be in [0,%d]", MRGAN_MAX_MODELS);
+    if (c.models > 1) {
+        // a group trains through mrgan_sup_step_group: fp32 / bf16, fused Adam, one device
+        if (c.world != 1) return fail(-3, "a model group (models = %d) needs world = 1: data-parallel groups are not built", c.models);
+        if (c.dtype == MRGAN_FP8) return fail(-3, "a model group (models = %d) cannot be an fp8 handle: the grouped step is the supervised one", c.models);
+        if (c.flags & (MRGAN_FLAG_FLAT_GRADS | MRGAN_FLAG_SYNC_STATS))
+            return fail(-3, "a model group (models = %d) cannot have MRGAN_FLAG_FLAT_GRADS or MRGAN_FLAG_SYNC_STATS: data-parallel groups are not built", c.models);
+    }
     return 0;
 }
 
@@ -110,8 +118,8 @@ int count_adam_tiles(const std::vector<Tensor>& ts) {
     return n;
 }
 
-// carve the workspace; with base == nullptr only computes the size
-int layout(mrgan_handle* h, char* base, size_t* bytes_out) {
+// carve the workspace of ONE model; with base == nullptr only computes the size
+int layout_model(mrgan_handle* h, char* base, size_t* bytes_out) {
     const mrgan_config& c = h->cfg;
     h->fp8 = c.dtype == MRGAN_FP8;
     h->bf16 = c.dtype == MRGAN_BF16 || h->fp8;            // the fp8 mode keeps the whole bf16 machinery (generator, head, evaluation)
@@ -292,6 +300,19 @@ int layout(mrgan_handle* h, char* base, size_t* bytes_out) {
     return 0;
 }
 
+// The whole workspace: the layout above once per model, W bytes apart.  Everything -- split counts, slab
+// and tile counts, the Adam tile tables -- is chosen from the per-model shape and describes model 0; a grouped launch reaches
+// model m's copy with the one stride W.  The generator's regions are present and unused in every copy; the DevState slots of
+// model 0's copy are the shared ones.
+int layout(mrgan_handle* h, char* base, size_t* bytes_out) {
+    size_t one = 0;
+    const int r = layout_model(h, base, &one);
+    h->models = std::max(1, (int)h->cfg.models);
+    h->W = h->models > 1 ? one : 0;                 // (already a multiple of 256)
+    *bytes_out = one * (size_t)h->models;
+    return r;
+}
+
 int upload_tiles(mrgan_handle* h, std::vector<Tensor>& ts, AdamTile* dev, int n, hipStream_t s) {
     std::vector<AdamTile> v;
     const int TR = adam_tile_rows(ts);
@@ -381,6 +402,7 @@ int mrgan_create(const mrgan_config* cfg, void* workspace, size_t bytes, mrgan_s
     h->pair_gen = h->gen_ready = 0; h->pair_g = nullptr; h->real_staged = 0;
     h->tune_kc_cfg = -1; h->tune_bits = 0; h->tune_pair_gen = 1; h->ablate = 0;
     h->head_nblk = 0; h->fp8_cal[0] = h->fp8_cal[1] = 0;
+    h->sel = 0; h->grouped = 1;
     if (init_kernel_attributes() != 0 || chain_init_attributes() != 0 || head_wide_init_attributes() != 0) { if (h->own_ws) hipFree(h->ws); delete h; return fail(-10, "hipFuncSetAttribute failed"); }
 #define CREATE_CHK(x)                                           \
     do {                                                        \
@@ -415,7 +437,8 @@ int mrgan_create(const mrgan_config* cfg, void* workspace, size_t bytes, mrgan_s
     }
     // BN gamma defaults to one (Keras); dense weights stay zero until mrgan_set_weights
     std::vector<float> ones(h->gt[2].cols, 1.0f);
-    CREATE_CHK(hipMemcpyAsync(h->gt[2].p, ones.data(), sizeof(float) * ones.size(), hipMemcpyHostToDevice, s));
+    for (int m = 0; m < h->models; ++m)
+        CREATE_CHK(hipMemcpyAsync(model_at(h, h->gt[2].p, m), ones.data(), sizeof(float) * ones.size(), hipMemcpyHostToDevice, s));
     CREATE_CHK(hipStreamSynchronize(s));
     *out = h;
     return 0;
@@ -442,13 +465,21 @@ int mrgan_tensor_shape(const mrgan_handle* h, int net, int idx, int* rows, int* 
     return 0;
 }
 
+int mrgan_select_model(mrgan_handle* h, int model) {
+    if (!h) return fail(-1, "null handle");
+    if (model < 0 || model >= h->models) return fail(-1, "select_model: model %d outside [0,%d)", model, h->models);
+    h->sel = model;
+    return 0;
+}
+
+// (the per-model entries below address the selected model's copy of the tensor: selected(), engine_internal.h)
 int mrgan_set_weights(mrgan_handle* h, int net, int idx, const float* src, mrgan_stream stream) {
     Tensor* t = find_tensor(h, net, idx);
     if (!t || !src) return fail(-1, "set_weights: bad tensor or null source");
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemcpy2DAsync(t->p, sizeof(float) * t->pcol, src, sizeof(float) * t->cols, sizeof(float) * t->cols, t->rows,
+    HIPCHK(hipMemcpy2DAsync(selected(h, t->p), sizeof(float) * t->pcol, src, sizeof(float) * t->cols, sizeof(float) * t->cols, t->rows,
                             hipMemcpyDeviceToDevice, s));
-    if (t->w16) hipLaunchKernelGGL(refresh_bf16_kernel, grid2d(t->prow, t->pcol), dim3(256), 0, s, t->p, t->w16, t->wt16, t->prow, t->pcol);
+    if (t->w16) hipLaunchKernelGGL(refresh_bf16_kernel, grid2d(t->prow, t->pcol), dim3(256), 0, s, selected(h, t->p), selected(h, t->w16), selected(h, t->wt16), t->prow, t->pcol);
     if (t->layer && t->layer->q.on) {
         // fp8 copies of the network's weights: the first pass only measures max |w|, the second stores with that scale
         for (int pass = 0; pass < 2; ++pass) { CHK(fp8_refresh_weights(h, net, s)); CHK(fp8_update_scales(h, s)); }
@@ -459,7 +490,7 @@ int mrgan_set_weights(mrgan_handle* h, int net, int idx, const float* src, mrgan
 int mrgan_get_weights(mrgan_handle* h, int net, int idx, float* dst, mrgan_stream stream) {
     Tensor* t = find_tensor(h, net, idx);
     if (!t || !dst) return fail(-1, "get_weights: bad tensor or null destination");
-    HIPCHK(hipMemcpy2DAsync(dst, sizeof(float) * t->cols, t->p, sizeof(float) * t->pcol, sizeof(float) * t->cols, t->rows,
+    HIPCHK(hipMemcpy2DAsync(dst, sizeof(float) * t->cols, selected(h, t->p), sizeof(float) * t->pcol, sizeof(float) * t->cols, t->rows,
                             hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
@@ -468,7 +499,7 @@ int mrgan_get_slot(mrgan_handle* h, int net, int idx, int which, float* dst, mrg
     Tensor* t = find_tensor(h, net, idx);
     if (!t || !dst || which < 0 || which > 2) return fail(-1, "get_slot: bad argument");
     if (which == 2 && t->flat16) return fail(-3, "get_slot: the flat gradients of this handle are bfloat16 (MRGAN_REGION_GRAD_*_BF16)");
-    const float* src = which == 0 ? t->m : which == 1 ? t->v : t->flat;
+    const float* src = selected(h, which == 0 ? t->m : which == 1 ? t->v : t->flat);
     HIPCHK(hipMemcpy2DAsync(dst, sizeof(float) * t->cols, src, sizeof(float) * t->pcol, sizeof(float) * t->cols, t->rows,
                             hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
@@ -477,7 +508,7 @@ int mrgan_get_slot(mrgan_handle* h, int net, int idx, int which, float* dst, mrg
 int mrgan_set_slot(mrgan_handle* h, int net, int idx, int which, const float* src, mrgan_stream stream) {
     Tensor* t = find_tensor(h, net, idx);
     if (!t || !src || which < 0 || which > 1) return fail(-1, "set_slot: bad argument");
-    float* dst = which == 0 ? t->m : t->v;
+    float* dst = selected(h, which == 0 ? t->m : t->v);
     HIPCHK(hipMemcpy2DAsync(dst, sizeof(float) * t->pcol, src, sizeof(float) * t->cols, sizeof(float) * t->cols, t->rows,
                             hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
@@ -554,9 +585,9 @@ int mrgan_region(mrgan_handle* h, int region, void** ptr, size_t* bytes) {
 int mrgan_read_metrics(mrgan_handle* h, float* out8, int reset, mrgan_stream stream) {
     if (!h || !out8) return fail(-1, "null argument");
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemcpyAsync(out8, h->accum, 4 * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(out8 + 4, h->step_out, 4 * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (reset) HIPCHK(hipMemsetAsync(h->accum, 0, 4 * sizeof(float), s));
+    HIPCHK(hipMemcpyAsync(out8, selected(h, h->accum), 4 * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out8 + 4, selected(h, h->step_out), 4 * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (reset) HIPCHK(hipMemsetAsync(selected(h, h->accum), 0, 4 * sizeof(float), s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
 }

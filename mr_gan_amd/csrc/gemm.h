@@ -56,6 +56,13 @@ struct Epi {
     void* q8t; long q8t_bs; int ldq8t;        // transposed fp8 copy [cols][ldq8t], batch b at element offset b * q8t_bs
     int tune_kc_cfg;         // forward / dX tile config forced by mrgan_set_tuning (-1 = measured table)
     int tune_bits;           // TUNE_BIT_* of the handle
+    // Model groups (mrgan_config.models > 1; gemm_group below sets these): the batch index of the launch counts (model, segment)
+    // pairs, batch = model * segs + segment.  Everything the batch strides address is the SEGMENT's; model m's weight operand,
+    // bias, output, mask, h, column sums and slabs lie model_stride BYTES behind model 0's, and its noise seed is seed + m.
+    // All zero for a single model: model 0, segment = batch.
+    long model_stride;
+    int segs;                // segments per model
+    uint32_t model_mul;      // model = (batch * model_mul) >> 16: ceil(65536 / segs) (+ 1 when segs divides 65536), exact below 1024 batches
 };
 
 struct GemmArgs {
@@ -68,6 +75,15 @@ struct GemmArgs {
     const void* B; long b_bs, b_sk, b_sj;   // B(k,j) at B + b*b_bs + k*b_sk + j*b_sj
     Epi e;
 };
+
+// (model, segment) of a launch's batch index (Epi::segs); wave-uniform, scalar arithmetic only
+__device__ __forceinline__ int batch_model(const Epi& e, int batch) { return (int)(((uint32_t)batch * e.model_mul) >> 16); }
+__device__ __forceinline__ int batch_segment(const Epi& e, int batch, int model) { return batch - model * e.segs; }
+// model m's copy of a per-model pointer (null stays null only where the caller tests the original)
+template <typename P>
+__device__ __forceinline__ P* model_ptr(P* p, const Epi& e, int model) { return (P*)((char*)p + (long)model * e.model_stride); }
+template <typename P>
+__device__ __forceinline__ const P* model_ptr(const P* p, const Epi& e, int model) { return (const P*)((const char*)p + (long)model * e.model_stride); }
 
 // bit of element (row, col) in the lane-native mask layout
 __device__ __forceinline__ uint32_t relu_mask_bit(const uint16_t* mask, int ldm, int row, int col) {
@@ -97,8 +113,8 @@ __device__ __host__ __forceinline__ bool dx_needs_h(const Epi& e) {
 }
 
 template <typename T, int EPI, int MR, int NR, int VAR>
-__device__ __forceinline__ void epilogue_prefetch(EpiPrefetch<MR, NR>& pf, const GemmArgs& g, int batch, int row_blk, int col_blk,
-                                                  int wm, int wn, int lane) {
+__device__ __forceinline__ void epilogue_prefetch(EpiPrefetch<MR, NR>& pf, const GemmArgs& g, int batch /* segment */, int model,
+                                                  int row_blk, int col_blk, int wm, int wn, int lane) {
     const Epi& e = g.e;
     const int lc = lane & 31, lh = lane >> 5;
     const int act = (VAR & 64) ? e.act : (VAR & 3);
@@ -108,7 +124,7 @@ __device__ __forceinline__ void epilogue_prefetch(EpiPrefetch<MR, NR>& pf, const
     for (int ni = 0; ni < NR; ++ni) {
         const int col = col_blk + (wn * NR + ni) * 32 + lc;
         pf.bias[ni] = 0.f; pf.mu[ni] = 0.f; pf.rstd[ni] = 0.f;
-        if constexpr (EPI == EPI_FWD) { if (col < e.n_valid && e.bias) pf.bias[ni] = e.bias[col]; }
+        if constexpr (EPI == EPI_FWD) { if (col < e.n_valid && e.bias) pf.bias[ni] = model_ptr(e.bias, e, model)[col]; }
         if constexpr (EPI == EPI_DX) {
             // (inside the column-sum pass these two loads were an exposed round trip per launch: 7.6 k cycles in the stamps of the
             // generator's d(BatchNorm output) product)
@@ -125,7 +141,7 @@ __device__ __forceinline__ void epilogue_prefetch(EpiPrefetch<MR, NR>& pf, const
             if constexpr (EPI == EPI_DX) {
                 const int rsub = row_blk + (wm * MR + mi) * 32;
                 if (act == ACT_RELU && e.mask && col < g.N && rsub < g.M)
-                    pf.mbits[mi][ni] = (e.mask + (long)batch * e.mask_bs)[((long)(rsub >> 5) * e.ldm + col) * 2 + lh];
+                    pf.mbits[mi][ni] = (model_ptr(e.mask, e, model) + (long)batch * e.mask_bs)[((long)(rsub >> 5) * e.ldm + col) * 2 + lh];
             }
         }
     }
@@ -140,7 +156,7 @@ __device__ __forceinline__ void epilogue_prefetch(EpiPrefetch<MR, NR>& pf, const
 // column per accumulator quad, i.e. exactly one dword of the transposed image; max |v| goes to e.qo.  Rows >= M are stored as
 // zeros.  The caller copies the two images out (gemm_fp8.hip copy_tile).
 template <typename T, int EPI, int MR, int NR, int WM, bool STAGED = false, int VAR = VAR_DYN, int Q8 = -1>
-__device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& g, int batch, int split,
+__device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& g, int batch /* segment */, int model, int split,
                                          int tile_m, int row_blk, int col_blk, int wm, int wn, int lane,
                                          float* lds /* >= 2*WM*bn floats of scratch, disjoint from `tile` */,
                                          int bn /* block tile width */, T* tile = nullptr,
@@ -159,7 +175,7 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
     if (e.ablate & 2) { if (acc[0][0][0] == 12345.678f) ((float*)e.out)[0] = 1.f; return; }
 
     if constexpr (EPI == EPI_SLAB) {
-        float* dst = e.slab + (long)(batch * g.splits + split) * e.slab_stride;
+        float* dst = model_ptr(e.slab, e, model) + (long)(batch * g.splits + split) * e.slab_stride;
 #pragma unroll
         for (int mi = 0; mi < MR; ++mi)
 #pragma unroll
@@ -176,13 +192,15 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
         constexpr bool DYN = (VAR & VAR_DYN) != 0;
         const int act = DYN ? e.act : (VAR & VAR_ACT_MASK);
         constexpr bool fast_math = sizeof(T) == 2;
-        T* out = (T*)e.out + (long)batch * e.out_bs;
+        T* out = (T*)model_ptr(e.out, e, model) + (long)batch * e.out_bs;
         // specialised variants decide mask / noise at compile time (the launcher guarantees the pointers)
         constexpr bool MASKED = !DYN && (EPI == EPI_DX || (VAR & VAR_MASK));
         uint16_t* mask = nullptr;
-        if constexpr (MASKED) mask = e.mask + (long)batch * e.mask_bs;
-        else if (DYN && e.mask) mask = e.mask + (long)batch * e.mask_bs;
-        const T* hprev = e.h ? (const T*)e.h + (long)batch * e.h_bs : nullptr;
+        if constexpr (MASKED) mask = model_ptr(e.mask, e, model) + (long)batch * e.mask_bs;
+        else if (DYN && e.mask) mask = model_ptr(e.mask, e, model) + (long)batch * e.mask_bs;
+        const T* hprev = e.h ? (const T*)model_ptr(e.h, e, model) + (long)batch * e.h_bs : nullptr;
+        float* const cs1p = model_ptr(e.cs1, e, model);
+        float* const cs2p = model_ptr(e.cs2, e, model);
         const bool noisy = EPI == EPI_FWD && (DYN ? e.sigma > 0.f : (VAR & VAR_NOISE) != 0);
         constexpr bool GAUSS = (VAR & VAR_GAUSS) != 0;     // rowhash[] then holds the row-pair hashes, sixteen per 32-row block
         // GaussianNoise of the NEXT layer's input (mr_gan.py:120-126), drawn per 32x32 accumulator tile by one integer
@@ -192,7 +210,7 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
         const float sigs = GAUSS ? e.sigma : e.sigma * NOISE_SCALE;
         if constexpr (EPI == EPI_FWD) {
             if (noisy) {
-                const uint32_t nkey = noise_key(e.seed, e.site * 256u + e.seg0 + (uint32_t)(batch * e.seg_step),
+                const uint32_t nkey = noise_key(e.seed + (uint64_t)model, e.site * 256u + e.seg0 + (uint32_t)(batch * e.seg_step),
                                                 (pf ? pf->iter : (e.st ? e.st->iter : 0u)) + (uint32_t)batch * e.iter_step);
                 if constexpr (!GAUSS) hfrag = hadamard_frag(lane);
 #pragma unroll
@@ -223,7 +241,7 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
             float bias = 0.f;
             if constexpr (EPI == EPI_FWD) {
                 if (pf) bias = pf->bias[ni];
-                else if (colvalid && e.bias) bias = e.bias[col];
+                else if (colvalid && e.bias) bias = model_ptr(e.bias, e, model)[col];
             }
             const float sig = (noisy && colvalid) ? sigs : 0.f;
 #pragma unroll
@@ -344,7 +362,7 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
                         s1 += __shfl_xor(s1, 32, 64);                     // lanes l and l ^ 32 hold the same column
                         const int col = col_blk + (wn * NR + ni) * 32 + lc;
                         const long pr = prow0 + wm * (MR / 2) + hh;
-                        if (lh == 0 && col < g.N && col < e.ldcs && row_blk + (wm * (MR / 2) + hh) * 64 < M) e.cs1[pr * e.ldcs + col] = s1;
+                        if (lh == 0 && col < g.N && col < e.ldcs && row_blk + (wm * (MR / 2) + hh) * 64 < M) cs1p[pr * e.ldcs + col] = s1;
                     }
             }
         } else if (e.cs_mode != CS_NONE) {
@@ -399,8 +417,8 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
                             const long pr = prow0 + wm * NH + hh;
                             // (col < N: a block tile wider than the last columns of N must not touch a row's pad up to ldcs)
                             if (col < g.N && col < e.ldcs && row_blk + (wm * NH + hh) * 64 < M) {
-                                e.cs1[pr * e.ldcs + col] = cs1[hh][ni];
-                                if (e.cs_mode != CS_SUM) e.cs2[pr * e.ldcs + col] = cs2[hh][ni];
+                                cs1p[pr * e.ldcs + col] = cs1[hh][ni];
+                                if (e.cs_mode != CS_SUM) cs2p[pr * e.ldcs + col] = cs2[hh][ni];
                             }
                         }
                 }
@@ -423,8 +441,8 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
 #pragma unroll
                     for (int w = 0; w < WM; ++w) { s1 += lds[(w * 2 + 0) * bn + t]; s2 += lds[(w * 2 + 1) * bn + t]; }
                     if (col_blk + t < g.N && col_blk + t < e.ldcs) {
-                        e.cs1[prow0 * e.ldcs + col_blk + t] = s1;
-                        if (e.cs_mode != CS_SUM) e.cs2[prow0 * e.ldcs + col_blk + t] = s2;
+                        cs1p[prow0 * e.ldcs + col_blk + t] = s1;
+                        if (e.cs_mode != CS_SUM) cs2p[prow0 * e.ldcs + col_blk + t] = s2;
                     }
                 }
             }
@@ -443,7 +461,8 @@ inline bool kc_cfg_supported(int cfg) {
 constexpr int KS_GROUP_MAX = 6;
 // a fold of per-block partial rows that rides along in the grouped launch (the loss head's weight-gradient partials):
 // dst[grp][i] = sum of src[p][i] over p = grp, grp + ngroups, ...   ; blocks_x * ngroups extra blocks of 256 threads
-struct FoldJob { const float* src; float* dst; long stride; int nsrc, n, ngroups, blocks_x; };
+// model_stride: bytes between the partial rows (and the folded rows) of consecutive models of a model group (0: one model)
+struct FoldJob { const float* src; float* dst; long stride; int nsrc, n, ngroups, blocks_x; long model_stride; };
 struct KsGroup {
     int n;
     int blk_end[KS_GROUP_MAX];       // exclusive prefix sums of the problems' block counts
@@ -521,6 +540,19 @@ inline GemmArgs gemm_dw_args(int K, int N, int vrows, int splits, int kchunk, in
     g.e.slab = slab; g.e.slab_stride = (long)K * N; g.e.ldo = N;
     return g;
 }
+// The launch described by g as `models` launches in one (models <= 1: as it is): g describes model 0 with its nbatch segments,
+// model m's per-model tensors (Epi) lie model_stride bytes behind.  The batch index then counts (model, segment) pairs.
+inline GemmArgs gemm_group(GemmArgs g, int models, long model_stride) {
+    if (models <= 1) return g;
+    g.e.segs = g.nbatch; g.e.model_stride = model_stride;
+    g.e.model_mul = (65536u + (uint32_t)g.nbatch - 1) / (uint32_t)g.nbatch + ((65536u % (uint32_t)g.nbatch) == 0 ? 1u : 0u);
+    g.nbatch *= models;
+    return g;
+}
+// batches of one model: what tile choices count, so that a group's launch picks the tile (and sums in the order) a single
+// model's launch picks
+inline int gemm_model_batches(const GemmArgs& g) { return g.e.segs > 0 ? g.e.segs : g.nbatch; }
+inline int gemm_models(const GemmArgs& g) { return g.e.segs > 0 ? g.nbatch / g.e.segs : 1; }
 // words between two segments of seg_rows rows in a lane-native relu mask of pitch ldm (2 x u16 per (32 rows, column))
 inline long mask_pitch(int seg_rows, int ldm) { return (long)(seg_rows / 32) * ldm * 2; }
 

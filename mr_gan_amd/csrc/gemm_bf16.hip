@@ -49,7 +49,7 @@ struct KcStamps { unsigned long long acc[6], prev, epi[5]; };      // make STAMP
 // one output tile (batch, tile_m, tile_n) of the product described by g: prologue, main loop, epilogue, ending with
 // the barrier after which the LDS ring may be refilled
 template <int EPI, int BM, int BNT, int WM, int WN, int NS, int VAR>
-__device__ __forceinline__ void kc_tile(const GemmArgs& g, const int batch, const int tile_m, const int tile_n, char* lds KC_STAMPS_PARAM) {
+__device__ __forceinline__ void kc_tile(const GemmArgs& g, const int batch /* segment */, const int model, const int tile_m, const int tile_n, char* lds KC_STAMPS_PARAM) {
     constexpr int NW = WM * WN;
     constexpr int MR = BM / WM / 32, NR = BNT / WN / 32;   // 32x32 accumulators per wave
     constexpr int A_BYTES = BM * 128, B_BYTES = BNT * 128, STAGE = A_BYTES + B_BYTES;
@@ -70,8 +70,8 @@ __device__ __forceinline__ void kc_tile(const GemmArgs& g, const int batch, cons
         const int row_blk = tile_m * BM, col_blk = tile_n * BNT;
 
         // descriptors bounded at the operand's end: rows >= M (A) / >= N (Bt) read as zeros
-        const __bf16* Ab = (const __bf16*)g.A + (long)batch * g.a_bs;
-        const __bf16* Bb = (const __bf16*)g.B + (long)batch * g.b_bs;
+        const __bf16* Ab = model_ptr((const __bf16*)g.A, g.e, model) + (long)batch * g.a_bs;
+        const __bf16* Bb = model_ptr((const __bf16*)g.B, g.e, model) + (long)batch * g.b_bs;
         const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, 0, (int)((long)g.M * g.a_si * 2), 0x00020000);
         const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, 0, (int)((long)g.N * g.b_sj * 2), 0x00020000);
         int voffA[A_INSTR], voffB[B_INSTR];          // swizzled per-lane source offsets
@@ -107,7 +107,7 @@ __device__ __forceinline__ void kc_tile(const GemmArgs& g, const int batch, cons
             if (dx_needs_h<VAR>(g.e)) {
                 constexpr int OUTB = BM * BNT * 2 + 4 * WM * BNT * 4, RING = NS * STAGE;
                 char* hdst = lds + (RING > OUTB ? RING : OUTB);
-                const __bf16* hb = (const __bf16*)g.e.h + (long)batch * g.e.h_bs;
+                const __bf16* hb = model_ptr((const __bf16*)g.e.h, g.e, model) + (long)batch * g.e.h_bs;
                 const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc((void*)hb, 0, (int)((long)g.M * g.e.ldh * 2), 0x00020000);
                 constexpr int RPI = 1024 / (BNT * 2);              // tile rows per wave-instruction
                 constexpr int LPR = 64 / RPI;                      // lanes per row
@@ -133,7 +133,7 @@ __device__ __forceinline__ void kc_tile(const GemmArgs& g, const int batch, cons
         // bias / relu-mask words of this wave's sub-tiles: their global-load latency hides under the main loop.
         // (issued after the LDS-DMA groups so that the counted waits below still cover every DMA group)
         EpiPrefetch<MR, NR> pf;
-        epilogue_prefetch<__bf16, EPI, MR, NR, VAR>(pf, g, batch, row_blk, col_blk, wm, wn, lane);
+        epilogue_prefetch<__bf16, EPI, MR, NR, VAR>(pf, g, batch, model, row_blk, col_blk, wm, wn, lane);
 
 #define KC_FRAG_A(As, mi, ks) *(const bf16x8*)(As + kc_off((wm * MR + mi) * 32 + lr, (ks) * 2 + lh))
 #define KC_FRAG_B(Bs, ni, ks) *(const bf16x8*)(Bs + kc_off((wn * NR + ni) * 32 + lr, (ks) * 2 + lh))
@@ -144,7 +144,7 @@ __device__ __forceinline__ void kc_tile(const GemmArgs& g, const int batch, cons
         __syncthreads();
         STAMP(3);               // barrier after the main loop
         // the BM x BNT bf16 output tile is assembled at the start of the (now dead) ring, column-sum scratch behind it
-        epilogue<__bf16, EPI, MR, NR, WM, true, VAR>(acc, g, batch, 0, tile_m, row_blk, col_blk, wm, wn, lane,
+        epilogue<__bf16, EPI, MR, NR, WM, true, VAR>(acc, g, batch, model, 0, tile_m, row_blk, col_blk, wm, wn, lane,
                                                      (float*)(lds + BM * BNT * 2), BNT, (__bf16*)lds, &pf, htile
 #ifdef MRGAN_STAMPS
                                                      , stamps_.epi
@@ -169,14 +169,15 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kc_kernel(const GemmAr
 #endif
     for (int tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
         const int tidx = xcd_tile(tl, ntiles);
-        const int batch = tidx / (ntn * ntm), rem = tidx - batch * (ntn * ntm);
+        const int bidx = tidx / (ntn * ntm), rem = tidx - bidx * (ntn * ntm);
+        const int model = batch_model(g.e, bidx), batch = batch_segment(g.e, bidx, model);      // (model groups: gemm.h, Epi::segs)
         // large problems only (operands beyond an XCD's L2): patches of 4 tile rows (lds_ring.h, tile order)
         int tile_m, tile_n;
         if ((ntm & 3) == 0 && ntn >= 8 && g.K >= 2048) {
             const int grp = rem / (4 * ntn), in = rem - grp * (4 * ntn);
             tile_m = grp * 4 + (in & 3); tile_n = in >> 2;
         } else { tile_m = rem / ntn; tile_n = rem - tile_m * ntn; }
-        kc_tile<EPI, BM, BNT, WM, WN, NS, VAR>(g, batch, tile_m, tile_n, lds KC_STAMPS_ARG);
+        kc_tile<EPI, BM, BNT, WM, WN, NS, VAR>(g, batch, model, tile_m, tile_n, lds KC_STAMPS_ARG);
     }
 #ifdef MRGAN_STAMPS
     if (g.e.slab && threadIdx.x == 0)
@@ -221,7 +222,7 @@ __device__ __forceinline__ bf16x8 ks_frag_swz(const char* tile, int fb, int ks, 
 }
 
 template <int NS, int WM, int WN>
-__device__ __forceinline__ void ks_fast_body(const GemmArgs& g, const int bid) {
+__device__ __forceinline__ void ks_fast_body(const GemmArgs& g, const int bid, const int model /* model groups: blockIdx.y */) {
     constexpr int NW = WM * WN;
     constexpr int MR = 128 / WM / 32, NR = 128 / WN / 32;
     constexpr int T_BYTES = 64 * 256, STAGE = 2 * T_BYTES;
@@ -245,8 +246,8 @@ __device__ __forceinline__ void ks_fast_body(const GemmArgs& g, const int bid) {
     const int k_begin = split * g.kchunk;
     const int k_end = (g.e.ablate & 4) ? k_begin : min(g.K, k_begin + g.kchunk);
 
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)g.A, 0, (int)((long)g.K * g.a_sk * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)g.B, 0, (int)((long)g.K * g.b_sk * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)model_ptr(g.A, g.e, model), 0, (int)((long)g.K * g.a_sk * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)model_ptr(g.B, g.e, model), 0, (int)((long)g.K * g.b_sk * 2), 0x00020000);
     // a wave-instruction covers 4 k-rows x 256 B; lane -> (k-row, swizzled source chunk)
     const int lrow = lane >> 4, lp = lane & 15;
     int voffA[T_INSTR], voffB[T_INSTR];
@@ -286,12 +287,12 @@ __device__ __forceinline__ void ks_fast_body(const GemmArgs& g, const int bid) {
 #undef KS_FRAG_B
 #undef KS_NO_STAMP
     __syncthreads();
-    epilogue<__bf16, EPI_SLAB, MR, NR, WM>(acc, g, 0, split, tile_m, row_blk, col_blk, wm, wn, lane, (float*)lds, BN);
+    epilogue<__bf16, EPI_SLAB, MR, NR, WM>(acc, g, 0, model, split, tile_m, row_blk, col_blk, wm, wn, lane, (float*)lds, BN);
 }
 
 template <int NS, int WM, int WN>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_ks_fast_kernel(const GemmArgs g) {
-    ks_fast_body<NS, WM, WN>(g, blockIdx.x);
+    ks_fast_body<NS, WM, WN>(g, blockIdx.x, blockIdx.y);
 }
 
 // All weight-gradient products of one sub-step in ONE launch: they have no consumer before the Adam kernel, each is
@@ -304,24 +305,26 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_ks_group_kernel(const 
     if ((int)blockIdx.x >= ngemm) {
         // the fold job's blocks (see FoldJob): only the first 256 threads of a block take part
         const FoldJob& f = grp.fold;
+        const float* fsrc = (const float*)((const char*)f.src + (long)blockIdx.y * f.model_stride);      // (model groups: this model's partial rows)
+        float* fdst = (float*)((char*)f.dst + (long)blockIdx.y * f.model_stride);
         const int fb = (int)blockIdx.x - ngemm, gidx = fb / f.blocks_x;
         const int i = (fb - gidx * f.blocks_x) * 256 + (int)threadIdx.x;
         if (threadIdx.x >= 256 || i >= f.n) return;
         float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
         int p = gidx;
         for (; p + 3 * f.ngroups < f.nsrc; p += 4 * f.ngroups) {
-            s0 += f.src[(long)p * f.stride + i]; s1 += f.src[(long)(p + f.ngroups) * f.stride + i];
-            s2 += f.src[(long)(p + 2 * f.ngroups) * f.stride + i]; s3 += f.src[(long)(p + 3 * f.ngroups) * f.stride + i];
+            s0 += fsrc[(long)p * f.stride + i]; s1 += fsrc[(long)(p + f.ngroups) * f.stride + i];
+            s2 += fsrc[(long)(p + 2 * f.ngroups) * f.stride + i]; s3 += fsrc[(long)(p + 3 * f.ngroups) * f.stride + i];
         }
-        for (; p < f.nsrc; p += f.ngroups) s0 += f.src[(long)p * f.stride + i];
-        f.dst[(long)gidx * f.stride + i] = (s0 + s1) + (s2 + s3);
+        for (; p < f.nsrc; p += f.ngroups) s0 += fsrc[(long)p * f.stride + i];
+        fdst[(long)gidx * f.stride + i] = (s0 + s1) + (s2 + s3);
         return;
     }
     int i = 0, b0 = 0;
 #pragma unroll
     for (int j = 0; j < KS_GROUP_MAX - 1; ++j)
         if (j + 1 < grp.n && (int)blockIdx.x >= grp.blk_end[j]) { i = j + 1; b0 = grp.blk_end[j]; }
-    ks_fast_body<NS, WM, WN>(grp.g[i], (int)blockIdx.x - b0);
+    ks_fast_body<NS, WM, WN>(grp.g[i], (int)blockIdx.x - b0, blockIdx.y);
 }
 
 template <int NS, int WM, int WN>
@@ -329,7 +332,7 @@ int launch_ks_fast(const GemmArgs& g, hipStream_t s) {
     static const std::string name = "gemm_bf16_ks_fast_kernel<" + std::to_string(NS) + ", " + std::to_string(WM) + ", " + std::to_string(WN) + ">";
     g_last_kernel = name.c_str();
     constexpr int STAGE = 2 * 64 * 256;
-    dim3 grid(ceil_div(g.N, 128) * ceil_div(g.M, 128) * g.splits);
+    dim3 grid(ceil_div(g.N, 128) * ceil_div(g.M, 128) * g.splits, gemm_models(g));
     return launch_with_dyn_lds<gemm_bf16_ks_fast_kernel<NS, WM, WN>, NS * STAGE>(grid, dim3(64 * WM * WN), s, g);
 }
 
@@ -357,13 +360,14 @@ __global__ __launch_bounds__(256) void gemm_bf16_ks_kernel(const GemmArgs g) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int tile_n = blockIdx.x, tile_m = blockIdx.y;
-    const int batch = blockIdx.z / g.splits, split = blockIdx.z % g.splits;
+    const int bidx = blockIdx.z / g.splits, split = blockIdx.z % g.splits;
+    const int model = batch_model(g.e, bidx), batch = batch_segment(g.e, bidx, model);      // (model groups: gemm.h, Epi::segs)
     const int row_blk = tile_m * 128, col_blk = tile_n * BN;
     const int k_begin = split * g.kchunk;
     const int k_end = (g.e.ablate & 4) ? k_begin : min(g.K, k_begin + g.kchunk);
 
-    const __bf16* A = (const __bf16*)g.A + (long)batch * g.a_bs;
-    const __bf16* B = (const __bf16*)g.B + (long)batch * g.b_bs;
+    const __bf16* A = model_ptr((const __bf16*)g.A, g.e, model) + (long)batch * g.a_bs;
+    const __bf16* B = model_ptr((const __bf16*)g.B, g.e, model) + (long)batch * g.b_bs;
 
     f32x16 acc[2][2];
 #pragma unroll
@@ -417,7 +421,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_ks_kernel(const GemmArgs g) {
         }
     }
     __syncthreads();
-    epilogue<__bf16, EPI_SLAB, 2, 2, 2>(acc, g, batch, split, tile_m, row_blk, col_blk, wm, wn, lane, (float*)lds, BN);
+    epilogue<__bf16, EPI_SLAB, 2, 2, 2>(acc, g, batch, model, split, tile_m, row_blk, col_blk, wm, wn, lane, (float*)lds, BN);
 }
 
 // diagnostic: out[0..511]  = what ds_read_b64_tr_b16 returns when lane l supplies the address of u16 elements
@@ -451,8 +455,11 @@ static int launch_kc_tile(const GemmArgs& g, hipStream_t s) {
     int cfg = g.e.tune_kc_cfg;
     if (cfg < 0) {
         // measured on MI355X (scripts/gemm_bench.py): bigger tiles win once they still give >= ~1.5 blocks per CU
-        const int t128 = ceil_div(g.M, 128) * ceil_div(g.N, 128) * g.nbatch;
-        const int t256 = ceil_div(g.M, 256) * ceil_div(g.N, 256) * g.nbatch;
+        // (a model group counts the tiles of ONE model, so it takes the tile a single model's launch takes: the same kernels and,
+        //  element by element, the same sums; tiles for whole groups have not been measured)
+        const int nbm = gemm_model_batches(g);
+        const int t128 = ceil_div(g.M, 128) * ceil_div(g.N, 128) * nbm;
+        const int t256 = ceil_div(g.M, 256) * ceil_div(g.N, 256) * nbm;
         // 128 x 128 tiles as EIGHT waves of 64 x 32 (cfg 7; two blocks = 16 waves per CU): more waves hide the barrier -> LDS read ->
         // MFMA chain of the short k-loops better than four waves of 64 x 64 (cfg 1) although they read 1.5 instead of 1.0
         // fragments per MFMA: D1 forward over 3 segments 22.9 -> 21.3 us, dX through D2 20.3 -> 18.7 us (scripts/gemm_bench.py)
@@ -469,7 +476,7 @@ static int launch_kc_tile(const GemmArgs& g, hipStream_t s) {
         // launches with at most one 64x128 tile per CU (the one-segment products of the G sub-step, small batches): 64x64 tiles
         // put twice as many blocks on the chip -- dX through D1 11.5 -> 9.7 us, d(BatchNorm output) 11.0 -> 8.5, G2 forward of one
         // segment 8.6 -> 7.4; with two tiles per CU already (two-segment launches) the smaller tile loses (10.5 -> 12.4)
-        if (cfg == 0 && ceil_div(g.M, 64) * ceil_div(g.N, 128) * g.nbatch <= 256) cfg = 9;
+        if (cfg == 0 && ceil_div(g.M, 64) * ceil_div(g.N, 128) * nbm <= 256) cfg = 9;
     }
     if (cfg >= 2 && cfg != 9 && (g.N % 128) != 0) cfg = 0;
     if (cfg == 3 && (g.N % 256) != 0) cfg = 1;
@@ -509,7 +516,8 @@ static int launch_kc_any(int epi, const GemmArgs& g, hipStream_t s) {
 }
 
 static bool ks_dense_k(const GemmArgs& g) {
-    return g.a_si == 1 && g.b_sj == 1 && g.nbatch == 1 && (g.K % BK) == 0 && (g.kchunk % BK) == 0 &&
+    // (one segment: nbatch = the number of models, which the launch spreads over grid.y)
+    return g.a_si == 1 && g.b_sj == 1 && gemm_model_batches(g) == 1 && (g.K % BK) == 0 && (g.kchunk % BK) == 0 &&
            (g.seg_rows >= g.seg_stride || g.K <= g.seg_rows) &&
            (long)g.K * g.a_sk * 2 < (1L << 31) && (long)g.K * g.b_sk * 2 < (1L << 31);
 }
@@ -522,8 +530,9 @@ int launch_gemm_bf16_dw_group(const GemmArgs* gs, int n, hipStream_t s, const ch
     memset(&grp, 0, sizeof grp);
     grp.n = n;
     int total = 0;
+    const int models = gemm_models(gs[0]);      // model groups: every block of the launch once per model (grid.y)
     for (int i = 0; i < n; ++i) {
-        if (!ks_dense_k(gs[i])) return 1;
+        if (!ks_dense_k(gs[i]) || gemm_models(gs[i]) != models) return 1;
         const int blocks = ceil_div(gs[i].N, 128) * ceil_div(gs[i].M, 128) * gs[i].splits;
         total += blocks;
         grp.blk_end[i] = total;
@@ -539,7 +548,7 @@ int launch_gemm_bf16_dw_group(const GemmArgs* gs, int n, hipStream_t s, const ch
     // reads per MFMA): 64.7 us; 8 waves with a 3-stage ring, one block per CU: 89 us.  More resident waves hide the
     // barrier -> LDS read -> MFMA chain; the LDS read rate is not the limit at two blocks per CU.
     constexpr int STAGE = 2 * 64 * 256, LDS = 2 * STAGE;
-    if (const int r = launch_with_dyn_lds<gemm_bf16_ks_group_kernel<2, 2, 4>, LDS>(dim3(total), dim3(512), s, grp)) return r;
+    if (const int r = launch_with_dyn_lds<gemm_bf16_ks_group_kernel<2, 2, 4>, LDS>(dim3(total, models), dim3(512), s, grp)) return r;
     if (kname) *kname = "gemm_bf16_ks_group_kernel<2, 2, 4>";
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

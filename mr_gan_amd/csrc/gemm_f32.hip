@@ -26,13 +26,14 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmArgs g) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int tile_n = blockIdx.x, tile_m = blockIdx.y;
-    const int batch = blockIdx.z / g.splits, split = blockIdx.z % g.splits;
+    const int bidx = blockIdx.z / g.splits, split = blockIdx.z % g.splits;
+    const int model = batch_model(g.e, bidx), batch = batch_segment(g.e, bidx, model);      // (model groups: gemm.h, Epi::segs)
     const int row_blk = tile_m * BM, col_blk = tile_n * BN;
     const int k_begin = split * g.kchunk;
     const int k_end = min(g.K, k_begin + g.kchunk);
 
-    const float* A = (const float*)g.A + (long)batch * g.a_bs;
-    const float* B = (const float*)g.B + (long)batch * g.b_bs;
+    const float* A = model_ptr((const float*)g.A, g.e, model) + (long)batch * g.a_bs;
+    const float* B = model_ptr((const float*)g.B, g.e, model) + (long)batch * g.b_bs;
 
     // staging map: thread -> (element t % TS along the free dim, KPT consecutive k starting at (t / TS) * KPT)
     const int si = t % TS, sk = (t / TS) * KPT;
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmArgs g) {
         }
     }
     __syncthreads();
-    epilogue<float, EPI, MR, MR, 2, false, VAR>(acc, g, batch, split, tile_m, row_blk, col_blk, wm, wn, lane, lds, BN);
+    epilogue<float, EPI, MR, MR, 2, false, VAR>(acc, g, batch, model, split, tile_m, row_blk, col_blk, wm, wn, lane, lds, BN);
 }
 }  // namespace
 
@@ -116,7 +117,8 @@ static int launch_f32_ts(int epi, const GemmArgs& g, hipStream_t s) {
 int launch_gemm_f32(int epi, const GemmArgs& g, hipStream_t s, const char** kname) {
     // 64x64 blocks while 128x128 ones would leave most CUs without work (small batches); the choice never changes
     // the result: every output element is the same k-ordered fmaf chain in both
-    const int blocks128 = ceil_div(g.N, 128) * ceil_div(g.M, 128) * g.nbatch * g.splits;
+    // (a model group counts the blocks of one model: the same tile, hence the same kernels, as a single model's launch)
+    const int blocks128 = ceil_div(g.N, 128) * ceil_div(g.M, 128) * gemm_model_batches(g) * g.splits;
     const bool small = blocks128 < 128;
     static const char* names[2][3] = {{"gemm_f32_kernel<0, 128>", "gemm_f32_kernel<1, 128>", "gemm_f32_kernel<2, 128>"},
                                       {"gemm_f32_kernel<0, 64>", "gemm_f32_kernel<1, 64>", "gemm_f32_kernel<2, 64>"}};

@@ -130,7 +130,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_fp8_kc_kernel(const GemmArg
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
         EpiPrefetch<MR, NR> pf;
-        epilogue_prefetch<__bf16, EPI, MR, NR, VAR>(pf, g, batch, row_blk, col_blk, wm, wn, lane);
+        epilogue_prefetch<__bf16, EPI, MR, NR, VAR>(pf, g, batch, 0, row_blk, col_blk, wm, wn, lane);
         int buf = 0;
 #ifdef MRGAN_STAMPS
         const unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_fp8_kc_kernel(const GemmArg
                 for (int r = 0; r < 16; ++r) acc[i][j][r] *= us;
         __syncthreads();
         if constexpr (EPI == EPI_SLAB) {
-            epilogue<__bf16, EPI_SLAB, MR, NR, WM, false, VAR>(acc, g, batch, split, tile_m, row_blk, col_blk, wm, wn, lane, (float*)lds, BNT);
+            epilogue<__bf16, EPI_SLAB, MR, NR, WM, false, VAR>(acc, g, batch, 0, split, tile_m, row_blk, col_blk, wm, wn, lane, (float*)lds, BNT);
         } else {
             // shared epilogue (bias / activation / mask / noise / column sums).  An fp8 output (e4m3 after a forward product,
             // e5m2 after a dX product) is packed straight from the accumulators into two LDS byte images and copied out;
@@ -211,12 +211,12 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_fp8_kc_kernel(const GemmArg
             if constexpr (OUT8) {
                 constexpr int QFMT = EPI == EPI_FWD ? FP8_E4M3 : FP8_E5M2;
                 constexpr int Q_BYTES = BM * (BNT + 16) + BNT * (BM + 16);
-                epilogue<__bf16, EPI, MR, NR, WM, true, VAR, QFMT>(acc, g, batch, 0, tile_m, row_blk, col_blk, wm, wn, lane,
+                epilogue<__bf16, EPI, MR, NR, WM, true, VAR, QFMT>(acc, g, batch, 0, 0, tile_m, row_blk, col_blk, wm, wn, lane,
                                                                    (float*)(lds + Q_BYTES), BNT, (__bf16*)lds, &pf, nullptr);
                 __syncthreads();
                 copy_tile<BM, BNT, 64 * NW>((const unsigned char*)lds, g.e, batch, row_blk, col_blk, g.M, g.N);
             } else {
-                epilogue<__bf16, EPI, MR, NR, WM, true, VAR>(acc, g, batch, 0, tile_m, row_blk, col_blk, wm, wn, lane,
+                epilogue<__bf16, EPI, MR, NR, WM, true, VAR>(acc, g, batch, 0, 0, tile_m, row_blk, col_blk, wm, wn, lane,
                                                              (float*)(lds + BM * BNT * 2), BNT, (__bf16*)lds, &pf, nullptr);
             }
         }

@@ -30,7 +30,9 @@ EXPORTS = [
     "mrgan_train_pair", "mrgan_sup_step", "mrgan_fp8_calibration", "mrgan_logmel", "mrgan_logmel_frames", "mrgan_region", "mrgan_eval_error", "mrgan_predict_logits", "mrgan_read_metrics",
     "mrgan_pair_hint", "mrgan_set_tuning", "mrgan_debug_noise", "mrgan_debug_tr_probe", "mrgan_debug_gemm_launch", "mrgan_profile_begin", "mrgan_profile_end", "mrgan_debug_ablate", "mrgan_debug_gemm_time", "mrgan_debug_buffer", "mrgan_debug_gemm_fp8",
     "mrgan_debug_quant8", "mrgan_debug_fp8_update_scales",
+    "mrgan_select_model", "mrgan_sup_step_group",
 ]
+MAX_MODELS = 16
 PROF_NAME_LEN = 96
 
 
@@ -43,7 +45,7 @@ class Config(C.Structure):
         ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float),
         ("bn_eps", C.c_float), ("unlabeled_weight", C.c_float),
         ("seed", C.c_uint64),
-        ("rank", C.c_int32), ("world", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+        ("rank", C.c_int32), ("world", C.c_int32), ("flags", C.c_int32), ("models", C.c_int32),
     ]
 
 
@@ -68,6 +70,16 @@ class SupArgs(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("idx", C.c_void_p), ("labels", C.c_void_p),
         ("ld_x", C.c_int64),
+        ("stream_mode", C.c_int32), ("rows_valid", C.c_int32),
+    ]
+
+
+class SupGroupArgs(C.Structure):
+    """mrgan_sup_group_args: the model strides count elements"""
+    _fields_ = [
+        ("x", C.c_void_p), ("idx", C.c_void_p), ("labels", C.c_void_p),
+        ("ld_x", C.c_int64),
+        ("x_model_stride", C.c_int64), ("idx_model_stride", C.c_int64), ("labels_model_stride", C.c_int64),
         ("stream_mode", C.c_int32), ("rows_valid", C.c_int32),
     ]
 
@@ -282,6 +294,36 @@ class Engine(object):
         out = (C.c_float * 2)()
         _check(self.lib.mrgan_sup_step(self.handle, C.byref(args), out if want_outputs else None, _stream()))
         return tuple(out) if want_outputs else None
+
+    # ---- model groups (cfg.models > 1): G equal-shape trainings in one launch set ----------------------------------
+    @property
+    def models(self):
+        return max(1, int(self.cfg.models))
+
+    def select_model(self, model):
+        """the model that set_weights / get_weights, get_slot / set_slot, eval_error, predict_logits (and debug_buffer) address"""
+        _check(self.lib.mrgan_select_model(self.handle, int(model)))
+
+    @staticmethod
+    def sup_group_args(x, labels, idx=None, stream_mode=0, rows_valid=0, x_model_stride=None, idx_model_stride=None,
+                       labels_model_stride=None):
+        """x [models, rows, D] (or [rows, D] with x_model_stride = 0: one matrix, gathered through idx [models, n]); labels
+        [models, n].  The strides default to those of the tensors' first dimension."""
+        a = SupGroupArgs()
+        a.x, a.idx, a.labels = _ptr(x), _ptr(idx), _ptr(labels)
+        a.ld_x = x.stride(-2)
+        a.x_model_stride = (x.stride(0) if x.dim() == 3 else 0) if x_model_stride is None else x_model_stride
+        a.idx_model_stride = (idx.stride(0) if idx is not None and idx.dim() == 2 else 0) if idx_model_stride is None else idx_model_stride
+        a.labels_model_stride = (labels.stride(0) if labels.dim() == 2 else 0) if labels_model_stride is None else labels_model_stride
+        a.stream_mode, a.rows_valid = stream_mode, rows_valid
+        a._refs = (x, labels, idx)
+        return a
+
+    def sup_step_group(self, args, want_outputs=True):
+        """sup_step once per model of a group handle, as one launch set -> [(mse loss, training error)] per model"""
+        out = (C.c_float * (2 * MAX_MODELS))()
+        _check(self.lib.mrgan_sup_step_group(self.handle, C.byref(args), out if want_outputs else None, _stream()))
+        return [(out[2 * m], out[2 * m + 1]) for m in range(self.models)] if want_outputs else None
 
     FP8_DRY_PASSES = 5
     FP8_CAL_QUERY, FP8_CAL_BEGIN, FP8_CAL_END_PASS, FP8_CAL_DONE = 0, 1, 2, 3

@@ -49,8 +49,10 @@ def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None
     return testerror
 
 
-def baseline_tables(tables, fn, dataset_fn, verbose=False):
-    """The --tables 2 4 loops shared by mr_svm.py:126-166 and mr_nn.py:128-168 (identical up to the function called)."""
+def baseline_tables(tables, fn, dataset_fn, verbose=False, folds_fn=None):
+    """The --tables 2 4 loops shared by mr_svm.py:126-166 and mr_nn.py:128-168 (identical up to the function called).
+    folds_fn (mr_nn --group-folds): table 2 hands the six folds of a (modality, percentage) to
+    folds_fn(sets, percentlabeled=, verbose=) -> their test errors in fold order, instead of calling fn once per fold."""
     from sklearn.model_selection import StratifiedKFold
     if '2' in tables:
         print('\n', '-' * 25, 'Testing various amounts of labeled training data', '-' * 25)
@@ -62,9 +64,12 @@ def baseline_tables(tables, fn, dataset_fn, verbose=False):
                 print('-' * 15, 'Percentage of training data labeled: %d%%' % percent, '-' * 15)
                 errors = []
                 skf = StratifiedKFold(n_splits=6, shuffle=True)
-                for trainIdx, testIdx in skf.split(X, y):
-                    errors.append(fn(None, None, percentlabeled=percent, trainTestSets=[X[trainIdx], X[testIdx], y[trainIdx], y[testIdx]],
-                                     verbose=verbose))
+                sets = [[X[trainIdx], X[testIdx], y[trainIdx], y[testIdx]] for trainIdx, testIdx in skf.split(X, y)]
+                if folds_fn is not None:
+                    errors = list(folds_fn(sets, percentlabeled=percent, verbose=verbose))
+                    sys.stdout.flush()
+                for s in sets if folds_fn is None else []:
+                    errors.append(fn(None, None, percentlabeled=percent, trainTestSets=s, verbose=verbose))
                     sys.stdout.flush()
                 print('Average error:', np.mean(errors), 'Average accuracy:', np.mean(1.0 - np.array(errors)))
                 sys.stdout.flush()
