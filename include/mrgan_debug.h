@@ -84,6 +84,154 @@ int mrgan_debug_quant8(const void* src, int64_t src_bs, int ld, int rows, int co
 /* the delayed-scaling update on the caller's array of n device slots.  Synchronises the stream. */
 int mrgan_debug_fp8_update_scales(void* slots_dev, int n, mrgan_stream stream);
 
+/* ---- one launch of a non-GEMM kernel (csrc/aux_kernels.h), for kernel-level tests ----
+ * One entry per launcher; every descriptor mirrors the launcher's argument block field by field (csrc/aux_kernels.h documents
+ * the fields), `dtype` (MRGAN_F32 / MRGAN_BF16) is the launcher's element-type argument.  Every data buffer is the caller's
+ * device memory in the kernel's own element type; nothing is converted or cleared, so a caller that pre-fills a buffer sees
+ * every element the kernel did not write.  The entries allocate only the DevState a kernel reads as launch state.  They
+ * synchronise the stream, return the launcher's -3 unchanged, and refuse with -1 only what the launcher takes on trust: the
+ * alignment of the 16-byte accesses and pitches smaller than the logical widths (message behind mrgan_last_error). */
+
+/* stage_kernel through launch_stage (StageArgs / StageSeg; `ry` / `ry_mul` are the launcher's).  iter / batch: the DevState of the
+ * launch.  Written per segment and model: out[r][0 .. cols_pad) for r < rows, columns >= cols zeros; nothing else.  The
+ * kernel itself chooses between 16-byte and scalar source loads (ld % 4, the alignment of src); the entry refuses only the
+ * output side: out / out_ms not 16-byte aligned, ldo not a multiple of 8 or below cols_pad, cols_pad not a multiple of 8 or
+ * below cols, ld below cols, and an odd row0 with the true-Gaussian generator (it draws whole row pairs). */
+typedef struct mrgan_debug_stage_seg {
+    const float* src; const int32_t* idx; int64_t ld;
+    int32_t rows, cols, cols_pad;
+    void* out; int32_t ldo;
+    float sigma; uint32_t site, seg;
+    int32_t gen, stream; uint32_t iter_off;
+    int32_t models; int64_t src_ms, idx_ms, out_ms;
+} mrgan_debug_stage_seg;
+typedef struct mrgan_debug_stage_desc {
+    int32_t dtype;
+    mrgan_debug_stage_seg s[5]; int32_t nseg;
+    uint64_t seed; uint32_t row0;
+    uint32_t iter, batch;
+    int32_t gauss;
+} mrgan_debug_stage_desc;
+int mrgan_debug_stage(const mrgan_debug_stage_desc* d, mrgan_stream stream);
+
+/* dst[g][i] = sum of src[p][i] over p = g, g + ngroups, ... < nsrc (i < n, rows `stride` floats apart), once per model
+ * (model m's src / dst model_stride BYTES behind model 0's).  Written: dst[g][0 .. n) for g < ngroups, nothing else. */
+int mrgan_debug_reduce_partials(const float* src, int nsrc, int64_t stride, int n, int ngroups, float* dst, int models,
+                                int64_t model_stride, mrgan_stream stream);
+/* out[seg][0][0 .. n) = column sums of part1's npart rows of segment seg (rows ld floats apart, segments npart * ld floats
+ * apart), out[seg][1][0 .. n) those of part2.  Written: exactly those 2 n floats per segment.  n % 4 != 0: -3. */
+int mrgan_debug_colsum_finalize(const float* part1, const float* part2, int npart, int ld, int n, float* out, int nseg,
+                                mrgan_stream stream);
+
+/* BatchNorm forward from column partial sums (BnApplyArgs).  The kernel works on all `ld` columns: it writes out[r][0 .. ld) for
+ * r < rows of every segment (columns >= cols: h * 0 + 0, zeros for finite h) and mu / rstd [seg][0 .. ld) (columns >= cols:
+ * the statistics of whatever the partial sums hold there). */
+typedef struct mrgan_debug_bn_apply_desc {
+    int32_t dtype;
+    const void* h; void* out; int32_t ld, rows, cols;
+    const float* cs1; const float* cs2; int32_t npart, ldcs;
+    float count, eps;
+    const float* gamma; const float* beta;
+    float* mu; float* rstd;
+    int64_t cs_seg_stride;
+    int32_t nseg; int64_t seg_rows;
+} mrgan_debug_bn_apply_desc;
+int mrgan_debug_bn_apply(const mrgan_debug_bn_apply_desc* d, mrgan_stream stream);
+
+/* BatchNorm backward fused with the softplus derivative (BnBwdArgs).  Written: dpre[r][0 .. ld) for r < rows (columns >= cols
+ * are zeros: gamma, mu and rstd count as 0 there) and db_part[blk][0 .. ld) for blk < ceil(rows / 64). */
+typedef struct mrgan_debug_bn_bwd_desc {
+    int32_t dtype;
+    const void* dy; const void* h; void* dpre; int32_t ld, rows, cols;
+    const float* cs1; const float* cs2; int32_t npart, ldcs;
+    float count;
+    const float* gamma; const float* mu; const float* rstd;
+    float* db_part;
+} mrgan_debug_bn_bwd_desc;
+int mrgan_debug_bn_bwd(const mrgan_debug_bn_bwd_desc* d, mrgan_stream stream);
+
+/* head_kernel through launch_head (HeadArgs); `batch` is DevState::batch of the launch (labels_stream).  Written, per model and
+ * segment: logits[row][0 .. KP) (KP = ldw; zeros in columns >= classes), dpre[row][0 .. feat), and per 32-row block blk =
+ * seg * ceil(rows / 32) + b: loss_part[blk][0 .. 4), part[blk][0 .. feat * KP) = dW6, [off_db .. + KP) = db6,
+ * [off_dbf .. + feat) = the feature layer's bias gradient.  HEAD_EVAL adds to *err_count and writes nothing else but logits;
+ * HEAD_LOGITS writes logits only.  q8 / q8t (fp8 mode): e5m2 bytes [row][0 .. feat) and [col][0 .. round_up(rows, 32)) (rows
+ * beyond `rows` zero), max |dpre| into q8_slot. */
+typedef struct mrgan_debug_head_desc {
+    int32_t dtype;
+    const void* f; int64_t f_bs; int32_t ldf;
+    int32_t rows, nseg, seg_kind[3];
+    int32_t feat, feat_valid, classes;
+    const float* w; int32_t ldw; const float* b;
+    const int32_t* labels; int32_t labels_stream; uint32_t batch;
+    float inv_count, unl_weight;
+    float* logits; int64_t logits_bs;
+    void* dpre; int64_t dpre_bs; int32_t ldd;
+    float* part; int64_t part_stride; int32_t off_db, off_dbf;
+    float* loss_part;
+    int32_t models; int64_t model_stride, labels_ms;
+    int32_t* err_count;
+    void* q8; int64_t q8_bs; int32_t ldq8;
+    void* q8t; int64_t q8t_bs; int32_t ldq8t;
+    void* q8_slot;
+} mrgan_debug_head_desc;
+int mrgan_debug_head(const mrgan_debug_head_desc* d, mrgan_stream stream);
+
+/* The matrix-core head (csrc/head_wide.h: HeadWideArgs): launch_w6_split, then launch_head_wide, on one descriptor.  h: as above
+ * with bf16 features (h.dtype is ignored), one model, training kinds, feat % 256 == 0; blocks are 64 rows, so blk = seg *
+ * ceil(rows / 64) + b in loss_part / part.  mask: the feature layer's lane-native relu mask (csrc/gemm.h), segment s mask_bs
+ * uint16 words behind segment 0, [ceil(rows / 32)][ldm][2] words each: dL/d(pre5) follows its bits, not f > 0.  w6c / w6r:
+ * scratch the split kernel writes in full, the bf16 addends of W6 class-major [3][ldw][feat] and row-major [3][feat][ldw] (zeros
+ * for rows >= feat_valid and columns >= classes; the three addends sum to W6 exactly).  With h.q8_slot the head writes no dpre
+ * but the e5m2 images: q8[row][0 .. feat), q8t[col][0 .. round_up(rows, 64)) per segment, 16 bytes at a time. */
+typedef struct mrgan_debug_head_wide_desc {
+    mrgan_debug_head_desc h;
+    const uint16_t* mask; int64_t mask_bs; int32_t ldm;
+    void* w6c; void* w6r;
+} mrgan_debug_head_wide_desc;
+int mrgan_debug_head_wide(const mrgan_debug_head_wide_desc* d, mrgan_stream stream);
+
+/* feature matching (FmArgs; `rb` is the launcher's).  Written: dpre[r][0 .. feat) for r < rows (zeros in columns >= feat_valid
+ * and where the mask bit is clear), *loss_out, *accum += loss; with q8_slot the e5m2 bytes q8[r][0 .. feat) and the slot's amax.
+ * lscratch / lcount select the distributed loss when feat >= 1024: lscratch[0 .. feat / 64) is written, *lcount must be zero
+ * before the launch and is zero after it. */
+typedef struct mrgan_debug_fm_desc {
+    int32_t dtype;
+    const float* cs; int32_t npart_fake, npart_real, ldcs;
+    float count, grad_scale; int32_t feat, feat_valid;
+    const uint16_t* mask; int32_t ldm;
+    void* dpre; int32_t ldd; int32_t rows;
+    float* loss_out; float* accum;
+    void* q8; int32_t ldq8; void* q8_slot;
+    float* lscratch; uint32_t* lcount;
+} mrgan_debug_fm_desc;
+int mrgan_debug_fm(const mrgan_debug_fm_desc* d, mrgan_stream stream);
+
+/* multi-tensor Adam (AdamArgs).  `tiles` is a HOST array of ntiles tile descriptors (copied to the device by the entry); every
+ * pointer inside is device memory.  iter / batch / lr_t: the DevState the launch reads.  publish_next != 0: the launch gets a
+ * `next` slot, pre-filled with 0xA5 bytes, whose four words are returned in next_out (an updating launch writes
+ * {iter + 1, batch + advance_batch, bits of lr_t(iter + 2), 0}; a launch that publishes nothing leaves 0xA5A5A5A5).
+ * Written per tile (rows x cols, cols % 4 == 0, both <= 64): m, v, p, w16 (and w8) [r][0 .. cols); with wt16 the transposed
+ * copy wt16 (and w8t) [c][0 .. round_up(rows, 16)) for c < cols, zeros beyond `rows`; ADAM_REDUCE_ONLY writes flat / flat16
+ * [r][0 .. cols) and flat_tail[0 .. 4) only.  The metrics finish (step_out != null) writes step_out[0 .. 3), accum[0 .. 3) +=. */
+typedef struct mrgan_debug_adam_tile {
+    float* p; float* m; float* v;
+    const float* g; int32_t nslab; int64_t slab_stride;
+    float* flat; void* flat16;
+    void* w16; void* wt16;
+    void* w8; void* w8t; void* w8_slot;
+    int32_t ld, ldt, rows, cols;
+} mrgan_debug_adam_tile;
+typedef struct mrgan_debug_adam_desc {
+    const mrgan_debug_adam_tile* tiles; int32_t ntiles, mode;
+    float b1, b2, eps;
+    uint32_t iter, batch; float lr_t;
+    const float* loss_part; int32_t nloss_part; float inv_rows; float* step_out; float* accum;
+    float* flat_tail;
+    int32_t publish_next, advance_batch; float lr;
+    int32_t models; int64_t model_stride;
+} mrgan_debug_adam_desc;
+int mrgan_debug_adam(const mrgan_debug_adam_desc* d, uint32_t next_out[4], mrgan_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -334,4 +334,282 @@ int mrgan_debug_fp8_update_scales(void* slots, int n, mrgan_stream stream) {
     return 0;
 }
 
+// ---- the non-GEMM kernels (aux_kernels.h), one entry per launcher.  The checks are what the launchers take on trust: 16-byte
+// accesses and pitches that hold the logical widths. ----
+static inline bool al(const void* p, uintptr_t a) { return ((uintptr_t)p % a) == 0; }
+// the launcher's code after the stream has drained: -3 unchanged, a failed synchronisation as -10
+static int debug_finish(const char* who, int r, hipStream_t s) {
+    const hipError_t he = hipStreamSynchronize(s);
+    if (r == -3) return fail(-3, "%s: launch refused (-3)", who);
+    if (r) return fail(r, "%s: launch failed (%d)", who, r);
+    if (he != hipSuccess) return fail(-10, "%s: %s", who, hipGetErrorString(he));
+    return 0;
+}
+static void debug_head_args(const mrgan_debug_head_desc* d, const DevState* st, HeadArgs& a);     // descriptor -> HeadArgs, field by field
+// a DevState pair on the device (the kernels read slot 0)
+static int debug_devstate(uint32_t iter, uint32_t batch, float lr_t, DevState** out) {
+    DevState hst[2];
+    memset(hst, 0, sizeof hst);
+    hst[0].iter = hst[1].iter = iter; hst[0].batch = hst[1].batch = batch; hst[0].lr_t = hst[1].lr_t = lr_t;
+    HIPCHK(hipMalloc((void**)out, sizeof hst));
+    const hipError_t he = hipMemcpy(*out, hst, sizeof hst, hipMemcpyHostToDevice);
+    if (he != hipSuccess) { hipFree(*out); *out = nullptr; return fail(-10, "hipMemcpy failed: %s", hipGetErrorString(he)); }
+    return 0;
+}
+
+int mrgan_debug_stage(const mrgan_debug_stage_desc* d, mrgan_stream stream) {
+    if (!d || d->nseg < 1 || d->nseg > 5) return fail(-1, "debug_stage: 1 .. 5 segments");
+    if (d->dtype != MRGAN_F32 && d->dtype != MRGAN_BF16) return fail(-1, "debug_stage: dtype must be fp32 or bf16");
+    if (d->gauss && (d->row0 & 1u)) return fail(-1, "debug_stage: the true-Gaussian generator draws row pairs, row0 must be even");
+    StageArgs a;
+    memset(&a, 0, sizeof a);
+    for (int i = 0; i < d->nseg; ++i) {
+        const mrgan_debug_stage_seg& g = d->s[i];
+        StageSeg& o = a.s[i];
+        if (!g.out || g.rows < 1 || g.cols < 1 || (!g.gen && !g.src)) return fail(-1, "debug_stage: segment %d: null argument", i);
+        if (g.cols_pad < g.cols || (g.cols_pad % 8) || g.ldo < g.cols_pad || (g.ldo % 8) || !al(g.out, 16) || (g.out_ms % 16))
+            return fail(-1, "debug_stage: segment %d: rows of out are stored 8 elements at a time (out, out_ms, ldo %% 8, cols <= cols_pad <= ldo, cols_pad %% 8)", i);
+        if (!g.gen && g.ld < g.cols) return fail(-1, "debug_stage: segment %d: ld >= cols", i);
+        o.src = g.src; o.idx = g.idx; o.ld = g.ld; o.rows = g.rows; o.cols = g.cols; o.cols_pad = g.cols_pad;
+        o.out = g.out; o.ldo = g.ldo; o.sigma = g.sigma; o.site = g.site; o.seg = g.seg; o.gen = g.gen; o.stream = g.stream;
+        o.iter_off = g.iter_off; o.models = g.models; o.src_ms = g.src_ms; o.idx_ms = g.idx_ms; o.out_ms = g.out_ms;
+    }
+    a.nseg = d->nseg; a.seed = d->seed; a.row0 = d->row0; a.gauss = d->gauss;
+    DevState* st = nullptr;
+    if (int r = debug_devstate(d->iter, d->batch, 0.f, &st)) return r;
+    a.cur = st;
+    hipStream_t s = (hipStream_t)stream;
+    const int r = debug_finish("debug_stage", launch_stage(d->dtype == MRGAN_BF16, a, s), s);
+    hipFree(st);
+    return r;
+}
+
+int mrgan_debug_reduce_partials(const float* src, int nsrc, int64_t stride, int n, int ngroups, float* dst, int models, int64_t model_stride,
+                                mrgan_stream stream) {
+    if (!src || !dst || nsrc < 1 || n < 1 || ngroups < 1 || models < 1) return fail(-1, "debug_reduce_partials: empty problem");
+    if (stride < n) return fail(-1, "debug_reduce_partials: stride >= n");
+    if (model_stride % 4) return fail(-1, "debug_reduce_partials: model_stride counts bytes of whole floats");
+    hipStream_t s = (hipStream_t)stream;
+    return debug_finish("debug_reduce_partials", launch_reduce_partials(src, nsrc, stride, n, ngroups, dst, s, models, model_stride), s);
+}
+
+int mrgan_debug_colsum_finalize(const float* part1, const float* part2, int npart, int ld, int n, float* out, int nseg, mrgan_stream stream) {
+    if (!part1 || !part2 || !out || npart < 1 || n < 1 || nseg < 1) return fail(-1, "debug_colsum_finalize: empty problem");
+    if (!al(part1, 16) || !al(part2, 16) || (ld % 4)) return fail(-1, "debug_colsum_finalize: partial rows are read 16 bytes at a time (pointers, ld %% 4)");
+    if (ld < n) return fail(-1, "debug_colsum_finalize: ld >= n");
+    hipStream_t s = (hipStream_t)stream;
+    return debug_finish("debug_colsum_finalize", launch_colsum_finalize(part1, part2, npart, ld, n, out, s, nseg), s);
+}
+
+// column partial sums as fold_partials reads them: four floats at a time over the `width` columns the kernel works on
+static int debug_cs_check(const char* who, const float* cs1, const float* cs2, int npart, int ldcs, int width) {
+    if (!cs1 || !cs2 || npart < 1) return fail(-1, "%s: column partial sums missing", who);
+    if (!al(cs1, 16) || !al(cs2, 16) || (ldcs % 4)) return fail(-1, "%s: partial sums are read 16 bytes at a time (pointers, ldcs %% 4)", who);
+    if (ldcs < width) return fail(-1, "%s: ldcs must hold the %d columns the kernel folds", who, width);
+    return 0;
+}
+
+int mrgan_debug_bn_apply(const mrgan_debug_bn_apply_desc* d, mrgan_stream stream) {
+    if (!d || !d->h || !d->out || !d->gamma || !d->beta || !d->mu || !d->rstd || d->rows < 1 || d->cols < 1) return fail(-1, "debug_bn_apply: null argument");
+    if (d->dtype != MRGAN_F32 && d->dtype != MRGAN_BF16) return fail(-1, "debug_bn_apply: dtype must be fp32 or bf16");
+    if (int r = debug_cs_check("debug_bn_apply", d->cs1, d->cs2, d->npart, d->ldcs, d->ld)) return r;
+    if (d->ld < d->cols || (d->ld % 8) || !al(d->h, 16) || !al(d->out, 16)) return fail(-1, "debug_bn_apply: ld >= cols, ld %% 8 == 0 and 16-byte aligned h / out");
+    if (d->nseg > 1 && ((d->cs_seg_stride % 4) || d->seg_rows < d->rows)) return fail(-1, "debug_bn_apply: cs_seg_stride %% 4 == 0 and seg_rows >= rows");
+    BnApplyArgs a;
+    memset(&a, 0, sizeof a);
+    a.h = d->h; a.out = d->out; a.ld = d->ld; a.rows = d->rows; a.cols = d->cols;
+    a.cs1 = d->cs1; a.cs2 = d->cs2; a.npart = d->npart; a.ldcs = d->ldcs; a.count = d->count; a.eps = d->eps;
+    a.gamma = d->gamma; a.beta = d->beta; a.mu = d->mu; a.rstd = d->rstd;
+    a.cs_seg_stride = d->cs_seg_stride; a.nseg = d->nseg; a.seg_rows = d->seg_rows;
+    hipStream_t s = (hipStream_t)stream;
+    return debug_finish("debug_bn_apply", launch_bn_apply(d->dtype == MRGAN_BF16, a, s), s);
+}
+
+int mrgan_debug_bn_bwd(const mrgan_debug_bn_bwd_desc* d, mrgan_stream stream) {
+    if (!d || !d->dy || !d->h || !d->dpre || !d->gamma || !d->mu || !d->rstd || !d->db_part || d->rows < 1 || d->cols < 1) return fail(-1, "debug_bn_bwd: null argument");
+    if (d->dtype != MRGAN_F32 && d->dtype != MRGAN_BF16) return fail(-1, "debug_bn_bwd: dtype must be fp32 or bf16");
+    if (int r = debug_cs_check("debug_bn_bwd", d->cs1, d->cs2, d->npart, d->ldcs, d->ld)) return r;
+    if (d->ld < d->cols || (d->ld % 8) || !al(d->h, 16) || !al(d->dy, 16) || !al(d->dpre, 16)) return fail(-1, "debug_bn_bwd: ld >= cols, ld %% 8 == 0 and 16-byte aligned dy / h / dpre");
+    BnBwdArgs a;
+    memset(&a, 0, sizeof a);
+    a.dy = d->dy; a.h = d->h; a.dpre = d->dpre; a.ld = d->ld; a.rows = d->rows; a.cols = d->cols;
+    a.cs1 = d->cs1; a.cs2 = d->cs2; a.npart = d->npart; a.ldcs = d->ldcs; a.count = d->count;
+    a.gamma = d->gamma; a.mu = d->mu; a.rstd = d->rstd; a.db_part = d->db_part;
+    hipStream_t s = (hipStream_t)stream;
+    return debug_finish("debug_bn_bwd", launch_bn_bwd(d->dtype == MRGAN_BF16, a, s), s);
+}
+
+int mrgan_debug_head(const mrgan_debug_head_desc* d, mrgan_stream stream) {
+    if (!d || !d->f || !d->w || !d->b || d->rows < 1 || d->nseg < 1 || d->nseg > 3 || d->feat < 1 || d->classes < 1) return fail(-1, "debug_head: null argument");
+    if (d->dtype != MRGAN_F32 && d->dtype != MRGAN_BF16) return fail(-1, "debug_head: dtype must be fp32 or bf16");
+    const int es = d->dtype == MRGAN_BF16 ? 2 : 4, kp = d->ldw;
+    bool losses = false, labels = false;       // losses: a training kind, which also writes gradients
+    for (int i = 0; i < d->nseg; ++i) {
+        const int k = d->seg_kind[i];
+        if (k < HEAD_LAB || k > HEAD_MSE) return fail(-1, "debug_head: unknown segment kind %d", k);
+        losses |= k != HEAD_EVAL && k != HEAD_LOGITS;
+        labels |= k == HEAD_LAB || k == HEAD_EVAL || k == HEAD_MSE;
+    }
+    if (d->feat_valid < 0 || d->feat_valid > d->feat || d->ldf < d->feat) return fail(-1, "debug_head: feat_valid <= feat <= ldf");
+    // the feature rows are read 8 elements at a time, W6 / the partial rows / the logits' LDS image four floats at a time
+    if (!al(d->f, 16) || ((int64_t)d->ldf * es % 16) || (d->f_bs * es % 16)) return fail(-1, "debug_head: feature rows are read 16 bytes at a time (f, ldf, f_bs)");
+    if (!al(d->w, 16)) return fail(-1, "debug_head: w must be 16-byte aligned");
+    if (labels && !d->labels) return fail(-1, "debug_head: the segment kinds need labels");
+    if (losses && !d->loss_part) return fail(-1, "debug_head: training kinds need loss_part");
+    if (losses && (!d->part || !al(d->part, 16) || (d->part_stride % 4) || (d->off_db % 4) || d->off_db < (int64_t)d->feat * kp || d->off_dbf < d->off_db + kp ||
+                  d->part_stride < (int64_t)d->off_dbf + d->feat))
+        return fail(-1, "debug_head: part rows hold dW6 [feat * ldw), db6 at off_db, the bias gradient at off_dbf, 16-byte aligned");
+    if (d->dpre && d->ldd < d->feat) return fail(-1, "debug_head: ldd >= feat");
+    if (d->models > 1 && (d->model_stride % 16)) return fail(-1, "debug_head: model_stride must keep the 16-byte alignments");
+    if (d->q8_slot) {
+        if (d->q8 && (!al(d->q8, 4) || (d->ldq8 % 4) || (d->q8_bs % 4) || d->ldq8 < d->feat)) return fail(-1, "debug_head: q8 is stored 4 bytes at a time, ldq8 >= feat");
+        if (d->q8t && (!al(d->q8t, 16) || (d->ldq8t % 16) || (d->q8t_bs % 16) || d->q8t_bs < 0 ||
+                       d->ldq8t < (int64_t)(d->nseg - 1) * d->q8t_bs + round_up(d->rows, HEAD_ROWS)))
+            return fail(-1, "debug_head: q8t is stored 16 bytes at a time and holds nseg segments of round_up(rows, 32) bytes");
+    }
+    DevState* st = nullptr;
+    if (int r = debug_devstate(0, d->batch, 0.f, &st)) return r;
+    HeadArgs a;
+    debug_head_args(d, st, a);
+    hipStream_t s = (hipStream_t)stream;
+    // the dynamic-LDS limits mrgan_create raises for a handle: no handle here, so once per process
+    static int attr = init_kernel_attributes();
+    int r = attr;
+    if (!r) r = launch_head(d->dtype == MRGAN_BF16, a, s);
+    r = debug_finish("debug_head", r, s);
+    hipFree(st);
+    return r;
+}
+
+static void debug_head_args(const mrgan_debug_head_desc* d, const DevState* st, HeadArgs& a) {
+    memset(&a, 0, sizeof a);
+    a.f = d->f; a.f_bs = d->f_bs; a.ldf = d->ldf; a.rows = d->rows; a.nseg = d->nseg;
+    for (int i = 0; i < 3; ++i) a.seg_kind[i] = d->seg_kind[i];
+    a.feat = d->feat; a.feat_valid = d->feat_valid; a.classes = d->classes;
+    a.w = d->w; a.ldw = d->ldw; a.b = d->b; a.labels = d->labels; a.st = st; a.labels_stream = d->labels_stream;
+    a.inv_count = d->inv_count; a.unl_weight = d->unl_weight;
+    a.logits = d->logits; a.logits_bs = d->logits_bs; a.dpre = d->dpre; a.dpre_bs = d->dpre_bs; a.ldd = d->ldd;
+    a.part = d->part; a.part_stride = d->part_stride; a.off_db = d->off_db; a.off_dbf = d->off_dbf; a.loss_part = d->loss_part;
+    a.models = d->models; a.model_stride = d->model_stride; a.labels_ms = d->labels_ms; a.err_count = d->err_count;
+    a.q8 = (unsigned char*)d->q8; a.q8_bs = d->q8_bs; a.ldq8 = d->ldq8;
+    a.q8t = (unsigned char*)d->q8t; a.q8t_bs = d->q8t_bs; a.ldq8t = d->ldq8t; a.q8_slot = (Fp8Slot*)d->q8_slot;
+}
+
+int mrgan_debug_head_wide(const mrgan_debug_head_wide_desc* w, mrgan_stream stream) {
+    if (!w || !w->h.f || !w->h.w || !w->h.b || w->h.rows < 1 || w->h.nseg < 1 || w->h.nseg > 3 || w->h.feat < 1 || w->h.classes < 1)
+        return fail(-1, "debug_head_wide: null argument");
+    const mrgan_debug_head_desc* d = &w->h;
+    const int kp = d->ldw;
+    if (d->models > 1) return fail(-1, "debug_head_wide: one model");
+    if (d->feat_valid < 0 || d->feat_valid > d->feat || d->ldf < d->feat) return fail(-1, "debug_head_wide: feat_valid <= feat <= ldf");
+    // the feature rows arrive 16 bytes at a time (LDS-DMA), the addends of W6 are read and dpre is stored 16 bytes at a time
+    if (!al(d->f, 16) || (d->ldf % 8) || (d->f_bs % 8)) return fail(-1, "debug_head_wide: feature rows are read 16 bytes at a time (f, ldf, f_bs)");
+    if (w->w6c && w->w6r && (!al(w->w6c, 16) || !al(w->w6r, 16))) return fail(-1, "debug_head_wide: w6c / w6r must be 16-byte aligned");
+    if (w->mask && w->ldm < d->feat) return fail(-1, "debug_head_wide: ldm >= feat");
+    if (!d->labels) return fail(-1, "debug_head_wide: labels");
+    if (d->part && (!al(d->part, 16) || (d->part_stride % 4) || (d->off_db % 4) || d->off_db < (int64_t)d->feat * kp || d->off_dbf < d->off_db + kp ||
+                    d->part_stride < (int64_t)d->off_dbf + d->feat))
+        return fail(-1, "debug_head_wide: part rows hold dW6 [feat * ldw), db6 at off_db, the bias gradient at off_dbf, 16-byte aligned");
+    if (d->dpre && (!al(d->dpre, 16) || (d->ldd % 8) || (d->dpre_bs % 8) || d->ldd < d->feat)) return fail(-1, "debug_head_wide: dpre is stored 16 bytes at a time, ldd >= feat");
+    if (d->q8_slot) {
+        if (d->q8 && (!al(d->q8, 16) || (d->ldq8 % 16) || (d->q8_bs % 16) || d->ldq8 < d->feat)) return fail(-1, "debug_head_wide: q8 is stored 16 bytes at a time, ldq8 >= feat");
+        if (d->q8t && (!al(d->q8t, 16) || (d->ldq8t % 16) || (d->q8t_bs % 16) || d->q8t_bs < 0 ||
+                       d->ldq8t < (int64_t)(d->nseg - 1) * d->q8t_bs + round_up(d->rows, HEAD_WIDE_ROWS)))
+            return fail(-1, "debug_head_wide: q8t is stored 16 bytes at a time and holds nseg segments of round_up(rows, 64) bytes");
+    }
+    DevState* st = nullptr;
+    if (int r = debug_devstate(0, d->batch, 0.f, &st)) return r;
+    HeadWideArgs a;
+    debug_head_args(d, st, a.h);
+    a.mask = w->mask; a.mask_bs = w->mask_bs; a.ldm = w->ldm; a.w6c = (__bf16*)w->w6c; a.w6r = (__bf16*)w->w6r;
+    hipStream_t s = (hipStream_t)stream;
+    static int attr = head_wide_init_attributes();          // as in debug_head: once per process
+    int r = attr;
+    if (!r) r = launch_w6_split(a, s);
+    if (!r) r = launch_head_wide(a, s);
+    r = debug_finish("debug_head_wide", r, s);
+    hipFree(st);
+    return r;
+}
+
+int mrgan_debug_fm(const mrgan_debug_fm_desc* d, mrgan_stream stream) {
+    if (!d || !d->cs || !d->mask || d->rows < 1 || d->feat < 1 || d->npart_fake < 1 || d->npart_real < 1) return fail(-1, "debug_fm: null argument");
+    if (d->dtype != MRGAN_F32 && d->dtype != MRGAN_BF16) return fail(-1, "debug_fm: dtype must be fp32 or bf16");
+    const int es = d->dtype == MRGAN_BF16 ? 2 : 4;
+    if (!d->dpre && !d->q8_slot) return fail(-1, "debug_fm: needs dpre or the fp8 copy");
+    if (d->feat_valid < 1 || d->feat_valid > d->feat) return fail(-1, "debug_fm: feat_valid <= feat");
+    if (!al(d->cs, 16) || (d->ldcs % 4) || d->ldcs < d->feat) return fail(-1, "debug_fm: partial sums are read 16 bytes at a time, ldcs >= feat");
+    if (!al(d->mask, 4) || d->ldm < d->feat) return fail(-1, "debug_fm: mask words are read in pairs, ldm >= feat");
+    if (d->dpre && (!al(d->dpre, 16) || ((int64_t)d->ldd * es % 16) || d->ldd < d->feat)) return fail(-1, "debug_fm: dpre is stored 16 bytes at a time, ldd >= feat");
+    if (d->q8_slot && (!d->q8 || !al(d->q8, 8) || (d->ldq8 % 8) || d->ldq8 < d->feat)) return fail(-1, "debug_fm: q8 is stored 8 bytes at a time, ldq8 >= feat");
+    FmArgs a;
+    memset(&a, 0, sizeof a);
+    a.cs = d->cs; a.npart_fake = d->npart_fake; a.npart_real = d->npart_real; a.ldcs = d->ldcs;
+    a.count = d->count; a.grad_scale = d->grad_scale; a.feat = d->feat; a.feat_valid = d->feat_valid;
+    a.mask = d->mask; a.ldm = d->ldm; a.dpre = d->dpre; a.ldd = d->ldd; a.rows = d->rows;
+    a.loss_out = d->loss_out; a.accum = d->accum;
+    a.q8 = (unsigned char*)d->q8; a.ldq8 = d->ldq8; a.q8_slot = (Fp8Slot*)d->q8_slot;
+    a.lscratch = d->lscratch; a.lcount = d->lcount;
+    hipStream_t s = (hipStream_t)stream;
+    return debug_finish("debug_fm", launch_fm(d->dtype == MRGAN_BF16, a, s), s);
+}
+
+int mrgan_debug_adam(const mrgan_debug_adam_desc* d, uint32_t next_out[4], mrgan_stream stream) {
+    if (!d || !d->tiles || d->ntiles < 1 || d->ntiles > 4096) return fail(-1, "debug_adam: null argument");
+    if (d->mode < ADAM_FUSED || d->mode > ADAM_FROM_FLAT) return fail(-1, "debug_adam: unknown mode %d", d->mode);
+    if (d->models > 1 && (d->model_stride % 16)) return fail(-1, "debug_adam: model_stride must keep the 16-byte alignments");
+    if (d->step_out && (!d->accum || (d->mode == ADAM_FROM_FLAT ? !d->flat_tail : (!d->loss_part || d->nloss_part < 0)))) return fail(-1, "debug_adam: the metrics finish needs loss_part (or flat_tail) and accum");
+    if (d->mode == ADAM_REDUCE_ONLY && d->step_out && !d->flat_tail) return fail(-1, "debug_adam: ADAM_REDUCE_ONLY needs flat_tail");
+    std::vector<AdamTile> tiles((size_t)d->ntiles);
+    for (int i = 0; i < d->ntiles; ++i) {
+        const mrgan_debug_adam_tile& t = d->tiles[i];
+        AdamTile& o = tiles[(size_t)i];
+        if (t.rows < 1 || t.rows > 64 || t.cols < 4 || t.cols > 64 || (t.cols % 4)) return fail(-1, "debug_adam: tile %d: rows in 1 .. 64, cols a multiple of 4 in 4 .. 64", i);
+        if (t.ld < t.cols || (t.ld % 4)) return fail(-1, "debug_adam: tile %d: ld >= cols, ld %% 4 == 0", i);
+        const bool upd = d->mode != ADAM_REDUCE_ONLY, slabs = d->mode != ADAM_FROM_FLAT;
+        if (upd && (!t.p || !t.m || !t.v || !al(t.p, 16) || !al(t.m, 16) || !al(t.v, 16))) return fail(-1, "debug_adam: tile %d: p / m / v are read 16 bytes at a time", i);
+        if (slabs && (!t.g || !al(t.g, 16) || t.nslab < 1 || (t.slab_stride % 4))) return fail(-1, "debug_adam: tile %d: gradient slabs are read 16 bytes at a time", i);
+        if (!slabs || !upd) {
+            if (!t.flat && !t.flat16) return fail(-1, "debug_adam: tile %d: the mode needs flat or flat16", i);
+            if ((t.flat && !al(t.flat, 16)) || (t.flat16 && !al(t.flat16, 8))) return fail(-1, "debug_adam: tile %d: flat / flat16 alignment", i);
+        }
+        if (t.w16 && !al(t.w16, 8)) return fail(-1, "debug_adam: tile %d: w16 is stored 8 bytes at a time", i);
+        if (t.wt16 && (!t.w16 || !al(t.wt16, 16) || (t.ldt % 8) || t.ldt < round_up(t.rows, 16))) return fail(-1, "debug_adam: tile %d: wt16 is stored 16 bytes at a time, ldt >= round_up(rows, 16)", i);
+        if (t.w8_slot && (!t.w16 || !t.w8 || !al(t.w8, 4) || (t.wt16 && (!t.w8t || !al(t.w8t, 16) || (t.ldt % 16))))) return fail(-1, "debug_adam: tile %d: the e4m3 copies follow w16 / wt16 (w8 4-byte, w8t 16-byte stores)", i);
+        o.p = t.p; o.m = t.m; o.v = t.v; o.g = t.g; o.nslab = t.nslab; o.slab_stride = t.slab_stride;
+        o.flat = t.flat; o.flat16 = (__bf16*)t.flat16; o.w16 = (__bf16*)t.w16; o.wt16 = (__bf16*)t.wt16;
+        o.w8 = (unsigned char*)t.w8; o.w8t = (unsigned char*)t.w8t; o.w8_slot = (Fp8Slot*)t.w8_slot;
+        o.ld = t.ld; o.ldt = t.ldt; o.rows = t.rows; o.cols = t.cols;
+    }
+    DevState* st = nullptr;
+    if (int r = debug_devstate(d->iter, d->batch, d->lr_t, &st)) return r;
+    AdamTile* dt = nullptr;
+    DevState* next = nullptr;
+    hipError_t he = hipMalloc((void**)&dt, tiles.size() * sizeof(AdamTile));
+    if (he == hipSuccess) he = hipMemcpy(dt, tiles.data(), tiles.size() * sizeof(AdamTile), hipMemcpyHostToDevice);
+    if (he == hipSuccess && d->publish_next) {
+        he = hipMalloc((void**)&next, sizeof(DevState));
+        if (he == hipSuccess) he = hipMemset(next, 0xA5, sizeof(DevState));
+    }
+    int r = he == hipSuccess ? 0 : fail(-10, "debug_adam: %s", hipGetErrorString(he));
+    hipStream_t s = (hipStream_t)stream;
+    if (!r) {
+        AdamArgs a;
+        memset(&a, 0, sizeof a);
+        a.tiles = dt; a.ntiles = d->ntiles; a.mode = d->mode; a.b1 = d->b1; a.b2 = d->b2; a.eps = d->eps; a.st = st;
+        a.loss_part = d->loss_part; a.nloss_part = d->nloss_part; a.inv_rows = d->inv_rows; a.step_out = d->step_out; a.accum = d->accum;
+        a.flat_tail = d->flat_tail; a.next = next; a.advance_batch = d->advance_batch; a.lr = d->lr;
+        a.models = d->models; a.model_stride = d->model_stride;
+        r = debug_finish("debug_adam", launch_adam(a, s), s);
+    }
+    if (!r && next && next_out) {
+        he = hipMemcpy(next_out, next, sizeof(DevState), hipMemcpyDeviceToHost);
+        if (he != hipSuccess) r = fail(-10, "debug_adam: %s", hipGetErrorString(he));
+    }
+    hipFree(st);
+    if (dt) hipFree(dt);
+    if (next) hipFree(next);
+    return r;
+}
+
 }  // extern "C"

@@ -30,6 +30,8 @@ EXPORTS = [
     "mrgan_train_pair", "mrgan_sup_step", "mrgan_fp8_calibration", "mrgan_logmel", "mrgan_logmel_frames", "mrgan_region", "mrgan_eval_error", "mrgan_predict_logits", "mrgan_read_metrics",
     "mrgan_pair_hint", "mrgan_set_tuning", "mrgan_debug_noise", "mrgan_debug_tr_probe", "mrgan_debug_gemm_launch", "mrgan_profile_begin", "mrgan_profile_end", "mrgan_debug_ablate", "mrgan_debug_gemm_time", "mrgan_debug_buffer", "mrgan_debug_gemm_fp8",
     "mrgan_debug_quant8", "mrgan_debug_fp8_update_scales",
+    "mrgan_debug_stage", "mrgan_debug_reduce_partials","mrgan_debug_colsum_finalize", "mrgan_debug_bn_apply", "mrgan_debug_bn_bwd", "mrgan_debug_head", "mrgan_debug_head_wide",
+    "mrgan_debug_fm", "mrgan_debug_adam",
     "mrgan_select_model", "mrgan_sup_step_group",
 ]
 MAX_MODELS = 16
@@ -474,6 +476,188 @@ def debug_gemm_launch(descs, grouped=False, fold=None):
     if rc not in (0, 1, -1, -3):
         _check(rc)
     return rc, name.value.decode()
+
+
+# ---- the non-GEMM kernels: one descriptor per launcher (include/mrgan_debug.h) ----------------------------------------
+HEAD_LAB, HEAD_UNL, HEAD_FAKE, HEAD_EVAL, HEAD_LOGITS, HEAD_MSE = range(6)
+ADAM_FUSED, ADAM_REDUCE_ONLY, ADAM_FROM_FLAT = range(3)
+
+
+class DebugStageSeg(C.Structure):
+    """mrgan_debug_stage_seg"""
+    _fields_ = [
+        ("src", C.c_void_p), ("idx", C.c_void_p), ("ld", C.c_int64),
+        ("rows", C.c_int32), ("cols", C.c_int32), ("cols_pad", C.c_int32),
+        ("out", C.c_void_p), ("ldo", C.c_int32),
+        ("sigma", C.c_float), ("site", C.c_uint32), ("seg", C.c_uint32),
+        ("gen", C.c_int32), ("stream", C.c_int32), ("iter_off", C.c_uint32),
+        ("models", C.c_int32), ("src_ms", C.c_int64), ("idx_ms", C.c_int64), ("out_ms", C.c_int64),
+    ]
+
+
+class DebugStageDesc(C.Structure):
+    """mrgan_debug_stage_desc"""
+    _fields_ = [
+        ("dtype", C.c_int32), ("s", DebugStageSeg * 5), ("nseg", C.c_int32),
+        ("seed", C.c_uint64), ("row0", C.c_uint32), ("iter", C.c_uint32), ("batch", C.c_uint32), ("gauss", C.c_int32),
+    ]
+
+
+class DebugBnApplyDesc(C.Structure):
+    """mrgan_debug_bn_apply_desc"""
+    _fields_ = [
+        ("dtype", C.c_int32), ("h", C.c_void_p), ("out", C.c_void_p), ("ld", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+        ("cs1", C.c_void_p), ("cs2", C.c_void_p), ("npart", C.c_int32), ("ldcs", C.c_int32),
+        ("count", C.c_float), ("eps", C.c_float), ("gamma", C.c_void_p), ("beta", C.c_void_p),
+        ("mu", C.c_void_p), ("rstd", C.c_void_p), ("cs_seg_stride", C.c_int64), ("nseg", C.c_int32), ("seg_rows", C.c_int64),
+    ]
+
+
+class DebugBnBwdDesc(C.Structure):
+    """mrgan_debug_bn_bwd_desc"""
+    _fields_ = [
+        ("dtype", C.c_int32), ("dy", C.c_void_p), ("h", C.c_void_p), ("dpre", C.c_void_p),
+        ("ld", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+        ("cs1", C.c_void_p), ("cs2", C.c_void_p), ("npart", C.c_int32), ("ldcs", C.c_int32), ("count", C.c_float),
+        ("gamma", C.c_void_p), ("mu", C.c_void_p), ("rstd", C.c_void_p), ("db_part", C.c_void_p),
+    ]
+
+
+class DebugHeadDesc(C.Structure):
+    """mrgan_debug_head_desc"""
+    _fields_ = [
+        ("dtype", C.c_int32), ("f", C.c_void_p), ("f_bs", C.c_int64), ("ldf", C.c_int32),
+        ("rows", C.c_int32), ("nseg", C.c_int32), ("seg_kind", C.c_int32 * 3),
+        ("feat", C.c_int32), ("feat_valid", C.c_int32), ("classes", C.c_int32),
+        ("w", C.c_void_p), ("ldw", C.c_int32), ("b", C.c_void_p),
+        ("labels", C.c_void_p), ("labels_stream", C.c_int32), ("batch", C.c_uint32),
+        ("inv_count", C.c_float), ("unl_weight", C.c_float),
+        ("logits", C.c_void_p), ("logits_bs", C.c_int64),
+        ("dpre", C.c_void_p), ("dpre_bs", C.c_int64), ("ldd", C.c_int32),
+        ("part", C.c_void_p), ("part_stride", C.c_int64), ("off_db", C.c_int32), ("off_dbf", C.c_int32),
+        ("loss_part", C.c_void_p),
+        ("models", C.c_int32), ("model_stride", C.c_int64), ("labels_ms", C.c_int64),
+        ("err_count", C.c_void_p),
+        ("q8", C.c_void_p), ("q8_bs", C.c_int64), ("ldq8", C.c_int32),
+        ("q8t", C.c_void_p), ("q8t_bs", C.c_int64), ("ldq8t", C.c_int32),
+        ("q8_slot", C.c_void_p),
+    ]
+
+
+class DebugHeadWideDesc(C.Structure):
+    """mrgan_debug_head_wide_desc"""
+    _fields_ = [("h", DebugHeadDesc), ("mask", C.c_void_p), ("mask_bs", C.c_int64), ("ldm", C.c_int32), ("w6c", C.c_void_p), ("w6r", C.c_void_p)]
+
+
+class DebugFmDesc(C.Structure):
+    """mrgan_debug_fm_desc"""
+    _fields_ = [
+        ("dtype", C.c_int32), ("cs", C.c_void_p), ("npart_fake", C.c_int32), ("npart_real", C.c_int32), ("ldcs", C.c_int32),
+        ("count", C.c_float), ("grad_scale", C.c_float), ("feat", C.c_int32), ("feat_valid", C.c_int32),
+        ("mask", C.c_void_p), ("ldm", C.c_int32), ("dpre", C.c_void_p), ("ldd", C.c_int32), ("rows", C.c_int32),
+        ("loss_out", C.c_void_p), ("accum", C.c_void_p),
+        ("q8", C.c_void_p), ("ldq8", C.c_int32), ("q8_slot", C.c_void_p),
+        ("lscratch", C.c_void_p), ("lcount", C.c_void_p),
+    ]
+
+
+class DebugAdamTile(C.Structure):
+    """mrgan_debug_adam_tile"""
+    _fields_ = [
+        ("p", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
+        ("g", C.c_void_p), ("nslab", C.c_int32), ("slab_stride", C.c_int64),
+        ("flat", C.c_void_p), ("flat16", C.c_void_p), ("w16", C.c_void_p), ("wt16", C.c_void_p),
+        ("w8", C.c_void_p), ("w8t", C.c_void_p), ("w8_slot", C.c_void_p),
+        ("ld", C.c_int32), ("ldt", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+    ]
+
+
+class DebugAdamDesc(C.Structure):
+    """mrgan_debug_adam_desc"""
+    _fields_ = [
+        ("tiles", C.POINTER(DebugAdamTile)), ("ntiles", C.c_int32), ("mode", C.c_int32),
+        ("b1", C.c_float), ("b2", C.c_float), ("eps", C.c_float),
+        ("iter", C.c_uint32), ("batch", C.c_uint32), ("lr_t", C.c_float),
+        ("loss_part", C.c_void_p), ("nloss_part", C.c_int32), ("inv_rows", C.c_float), ("step_out", C.c_void_p), ("accum", C.c_void_p),
+        ("flat_tail", C.c_void_p),
+        ("publish_next", C.c_int32), ("advance_batch", C.c_int32), ("lr", C.c_float),
+        ("models", C.c_int32), ("model_stride", C.c_int64),
+    ]
+
+
+def _debug_fill(d, kw):
+    """keywords -> fields of a descriptor; tensors become device pointers (and are kept alive by the descriptor)"""
+    d._refs = []
+    for name, v in kw.items():
+        if isinstance(v, torch.Tensor):
+            d._refs.append(v)
+            v = v.data_ptr()
+        elif name == "seg_kind":
+            v = (C.c_int32 * 3)(*(list(v) + [0] * (3 - len(v))))
+        setattr(d, name, v)
+    return d
+
+
+def _debug_rc(rc):
+    """the launchers' refusal (-3) and the entries' own (-1) are returned, anything else raises"""
+    if rc not in (0, -1, -3):
+        _check(rc)
+    return rc
+
+
+def debug_stage(segs, **kw):
+    """segs: [dict of DebugStageSeg fields], at most five; kw: the launch's own fields"""
+    d = _debug_fill(DebugStageDesc(), kw)
+    keep = [_debug_fill(DebugStageSeg(), s) for s in segs]
+    for i, s in enumerate(keep[:5]):
+        d.s[i] = s
+    d.nseg = len(segs)
+    return _debug_rc(load_library().mrgan_debug_stage(C.byref(d), _stream()))
+
+
+def debug_reduce_partials(src, nsrc, stride, n, ngroups, dst, models=1, model_stride=0):
+    return _debug_rc(load_library().mrgan_debug_reduce_partials(_ptr(src), int(nsrc), C.c_int64(stride), int(n), int(ngroups), _ptr(dst),
+                                                                int(models), C.c_int64(model_stride), _stream()))
+
+
+def debug_colsum_finalize(part1, part2, npart, ld, n, out, nseg=1):
+    return _debug_rc(load_library().mrgan_debug_colsum_finalize(_ptr(part1), _ptr(part2), int(npart), int(ld), int(n), _ptr(out), int(nseg),
+                                                                _stream()))
+
+
+def debug_bn_apply(**kw):
+    return _debug_rc(load_library().mrgan_debug_bn_apply(C.byref(_debug_fill(DebugBnApplyDesc(), kw)), _stream()))
+
+
+def debug_bn_bwd(**kw):
+    return _debug_rc(load_library().mrgan_debug_bn_bwd(C.byref(_debug_fill(DebugBnBwdDesc(), kw)), _stream()))
+
+
+def debug_head(**kw):
+    return _debug_rc(load_library().mrgan_debug_head(C.byref(_debug_fill(DebugHeadDesc(), kw)), _stream()))
+
+
+def debug_head_wide(mask=None, mask_bs=0, ldm=0, w6c=None, w6r=None, **kw):
+    """launch_w6_split + launch_head_wide; kw: the fields of the head descriptor"""
+    d = DebugHeadWideDesc()
+    d.h = _debug_fill(DebugHeadDesc(), kw)
+    _debug_fill(d, dict(mask=mask, mask_bs=mask_bs, ldm=ldm, w6c=w6c, w6r=w6r))
+    return _debug_rc(load_library().mrgan_debug_head_wide(C.byref(d), _stream()))
+
+
+def debug_fm(**kw):
+    return _debug_rc(load_library().mrgan_debug_fm(C.byref(_debug_fill(DebugFmDesc(), kw)), _stream()))
+
+
+def debug_adam(tiles, **kw):
+    """tiles: [dict of DebugAdamTile fields] -> (return code, the four words of the published `next` DevState as uint32, or
+    None when publish_next is not set)"""
+    arr = (DebugAdamTile * len(tiles))(*[_debug_fill(DebugAdamTile(), t) for t in tiles])
+    d = _debug_fill(DebugAdamDesc(), kw)
+    d.tiles, d.ntiles = arr, len(tiles)
+    nxt = (C.c_uint32 * 4)()
+    rc = _debug_rc(load_library().mrgan_debug_adam(C.byref(d), nxt, _stream()))
+    return rc, (np.array(list(nxt), dtype=np.uint32) if d.publish_next and rc == 0 else None)
 
 
 def debug_gemm(dtype, op, a, b, bias=None, act=0, splits=1):

@@ -157,6 +157,33 @@ int main(void) {
     assert D._fields_[-1][0] == "gauss" and D.q8.offset == D.slab_stride.offset + 8
 
 
+def test_debug_aux_desc_layouts_match_header():
+    """the descriptors of the non-GEMM debug entries (mrgan_debug.h) against their ctypes twins: size, one field from the middle
+    and the last field of each"""
+    from mr_gan_amd import engine as E
+    pins = [("mrgan_debug_stage_seg", E.DebugStageSeg, ("ld", "out", "sigma", "iter_off", "out_ms")),
+            ("mrgan_debug_stage_desc", E.DebugStageDesc, ("s", "nseg", "seed", "gauss")),
+            ("mrgan_debug_bn_apply_desc", E.DebugBnApplyDesc, ("cs1", "gamma", "seg_rows")),
+            ("mrgan_debug_bn_bwd_desc", E.DebugBnBwdDesc, ("cs1", "count", "db_part")),
+            ("mrgan_debug_head_desc", E.DebugHeadDesc, ("seg_kind", "labels", "batch", "part_stride", "model_stride", "err_count", "q8_slot")),
+            ("mrgan_debug_head_wide_desc", E.DebugHeadWideDesc, ("mask", "ldm", "w6r")),
+            ("mrgan_debug_fm_desc", E.DebugFmDesc, ("mask", "loss_out", "ldq8", "lcount")),
+            ("mrgan_debug_adam_tile", E.DebugAdamTile, ("slab_stride", "w8_slot", "cols")),
+            ("mrgan_debug_adam_desc", E.DebugAdamDesc, ("lr_t", "loss_part", "flat_tail", "lr", "model_stride"))]
+    body = "".join('  printf("%%zu", sizeof(%s));%s  printf("\\n");\n'
+                   % (c, "".join(' printf(" %%zu", offsetof(%s, %s));' % (c, f) for f in fields)) for c, _, fields in pins)
+    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "mrgan_debug.h"\nint main(void) {\n%s  return 0; }\n' % body
+    with tempfile.TemporaryDirectory() as d:
+        c = os.path.join(d, "t.c")
+        open(c, "w").write(prog)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", os.path.join(d, "t")])
+        lines = subprocess.check_output([os.path.join(d, "t")]).decode().splitlines()
+    assert len(lines) == len(pins)
+    for line, (cname, S, fields) in zip(lines, pins):
+        assert [int(v) for v in line.split()] == [ctypes.sizeof(S)] + [getattr(S, f).offset for f in fields], cname
+        assert S._fields_[-1][0] == fields[-1], cname
+
+
 def test_fp8_round_equals_torch_casts_on_every_bf16_value():
     """The kernel-level fp8 tests encode operands and decode outputs with torch's float8 casts (tensor.view(torch.uint8)); the
     mirror rounds with oracle.fp8_round.  Both are the same grid: every finite bf16 bit pattern, times a power-of-two slot scale,
