@@ -54,7 +54,7 @@ enum {
                                   * and a slower epilogue in every noisy forward product and in the staging kernel.  Every
                                   * entry honours it: mrgan_disc_step / mrgan_gen_step and their phases, mrgan_train_pair
                                   * with and without graph replay, data-parallel shards (rows stay global: the shards of a
-                                  * batch draw what the full batch would), mrgan_sup_step, mrgan_sup_step_group.  Host-supplied z is untouched.  */
+                                  * batch draw what the full batch would), mrgan_sup_step, the _group entries.  Host-supplied z is untouched.  */
 };
 
 #define MRGAN_MAX_CLASSES 32   /* largest mrgan_config.num_classes */
@@ -81,7 +81,7 @@ typedef struct mrgan_config {
     int32_t flags;
     int32_t models;           /* 0 or 1: one model (the handle every other entry describes).  2 .. MRGAN_MAX_MODELS: a GROUP handle,
                                * `models` independent trainings of this shape that step together in one launch set
-                               * (mrgan_sup_step_group).  Model m draws what a single handle with seed + m draws.             */
+                               * (the _group entries).  Model m draws what a single handle with seed + m draws.             */
 } mrgan_config;
 
 int mrgan_default_config(mrgan_config* cfg, int32_t d_in, int32_t batch);
@@ -93,13 +93,13 @@ int mrgan_create(const mrgan_config* cfg, void* workspace_dev, size_t bytes, mrg
 int mrgan_destroy(mrgan_handle* h);
 const char* mrgan_last_error(void);
 
-/* Group handles (mrgan_config.models > 1): G trainings of equal shape with different weights whose supervised step runs as
- * ONE launch set (one launch per kernel kind, whatever G is).  The workspace holds the single-model layout once per model
+/* Group handles (mrgan_config.models > 1): G trainings of equal shape with different weights whose steps -- the supervised
+ * step and the GAN sub-steps -- run as ONE launch set each (one launch per kernel kind, whatever G is).  The workspace holds the single-model layout once per model
  * (mrgan_workspace_bytes = models x the single size rounded up to 256 B); the iteration counter and the batch counter are
  * shared, all models step together.  mrgan_create refuses models > 1 together with MRGAN_FP8, MRGAN_FLAG_FLAT_GRADS,
- * MRGAN_FLAG_SYNC_STATS or world != 1.  A group handle trains through mrgan_sup_step_group only: mrgan_disc_step,
- * mrgan_gen_step, mrgan_train_pair, mrgan_fp8_calibration and mrgan_sup_step fail with status -3 (the grouped GAN step is not
- * built).  mrgan_select_model chooses the model (default 0) that mrgan_set_weights / mrgan_get_weights, mrgan_get_slot /
+ * MRGAN_FLAG_SYNC_STATS or world != 1.  A group handle trains through the _group entries only (mrgan_sup_step_group,
+ * mrgan_disc_step_group, mrgan_gen_step_group, mrgan_train_pair_group): mrgan_disc_step, mrgan_gen_step, mrgan_train_pair,
+ * mrgan_fp8_calibration and mrgan_sup_step fail with status -3.  mrgan_select_model chooses the model (default 0) that mrgan_set_weights / mrgan_get_weights, mrgan_get_slot /
  * mrgan_set_slot, mrgan_eval_error and mrgan_predict_logits address; evaluation runs model by model with the single-model
  * kernels.  mrgan_tensor_shape, mrgan_num_tensors and mrgan_get_iterations are the same for every model. */
 int mrgan_select_model(mrgan_handle* h, int model);
@@ -198,6 +198,39 @@ int mrgan_train_pair(mrgan_handle* h, const mrgan_disc_args* d, const mrgan_gen_
  * MRGAN_FLAG_SYNC_STATS the BN_STATS region then holds both segments and ONE all-reduce after D_GEN serves both
  * sub-steps: the host skips the exchange after that G sub-step's G_GEN.  One D sub-step per hint. */
 int mrgan_pair_hint(mrgan_handle* h, int on);
+
+/* The GAN hot loop of a group handle: mrgan_disc_step / mrgan_gen_step / mrgan_train_pair once per model, each sub-step as ONE
+ * launch set with the kernel names and launch counts of a single handle's (no host loop over models).  Model m is bit-identical
+ * to a single handle created with seed + m that holds model m's weights.  The fields are those of mrgan_disc_args /
+ * mrgan_gen_args plus element strides between models: model m reads x_* + m * x_*_model_stride (row pitch ld_x_*), idx_* +
+ * m * idx_*_model_stride (when the index vector is given), labels + m * labels_model_stride and z + m * z_model_stride.  An
+ * x_*_model_stride of 0 lets every model gather from one matrix through its own index vector; z_dev = NULL: model m draws z on
+ * the device with seed + m.  stream_mode is common to all models.  Whole sub-steps only (no phase range: groups stay on one
+ * GPU).  out3_host (optional): [models][3] = loss_lab, loss_unl, train_err per model; out1_host (optional): [models] loss_gen.
+ * step_out / accum are per model (mrgan_read_metrics addresses the selected model).  A group handle's D sub-step runs the
+ * chain head at the 8-class pitch and the scalar head kernel wherever a single handle would take the matrix-core head
+ * (feature layers wider than 256, the 32-class pitch): there the single handle to compare with has MRGAN_TUNE_HEAD_MFMA = 0.
+ * mrgan_train_pair_group replays a captured graph under the conditions of mrgan_train_pair; its two generator forwards run
+ * separately (bit-identical to the paired pass).  A single-model handle refuses these entries (status -3). */
+typedef struct mrgan_disc_group_args {
+    const float* x_lab_dev; const int32_t* idx_lab_dev; const int32_t* labels_dev;
+    const float* x_unl_dev; const int32_t* idx_unl_dev;
+    const float* z_dev;
+    int64_t ld_x_lab, ld_x_unl;
+    int64_t x_lab_model_stride, idx_lab_model_stride, labels_model_stride;
+    int64_t x_unl_model_stride, idx_unl_model_stride, z_model_stride;
+    int32_t stream_mode, reserved;
+} mrgan_disc_group_args;
+typedef struct mrgan_gen_group_args {
+    const float* x_unl_dev; const int32_t* idx_unl_dev;
+    const float* z_dev;
+    int64_t ld_x_unl;
+    int64_t x_unl_model_stride, idx_unl_model_stride, z_model_stride;
+    int32_t stream_mode, reserved;
+} mrgan_gen_group_args;
+int mrgan_disc_step_group(mrgan_handle* h, const mrgan_disc_group_args* a, float* out3_host, mrgan_stream stream);
+int mrgan_gen_step_group(mrgan_handle* h, const mrgan_gen_group_args* a, float* out1_host, mrgan_stream stream);
+int mrgan_train_pair_group(mrgan_handle* h, const mrgan_disc_group_args* d, const mrgan_gen_group_args* g, mrgan_stream stream);
 
 /* Launch-structure knobs of one handle (results stay within rounding; defaults are the measured best).  Call between
  * steps, never inside a captured pair.  Knobs 2 and 3 are retired: mrgan_set_tuning refuses them, and their numbers are

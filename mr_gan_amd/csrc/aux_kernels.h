@@ -44,6 +44,9 @@ struct BnApplyArgs {
     long cs_seg_stride;                                        // floats between the partial sums of consecutive segments
     int nseg; long seg_rows;                                   // nseg independent batches, seg_rows rows apart in h / out; their
                                                                // partial sums follow each other (npart rows each), mu / rstd ld apart
+    // Model groups: grid.z = model * nseg + segment (0 or 1: one model), model = (blockIdx.z * seg_mul) >> 16 (set by
+    // launch_bn_apply).  Model m's h, out, cs1 / cs2, gamma, beta, mu and rstd lie model_stride BYTES behind model 0's.
+    int models; long model_stride; uint32_t seg_mul;
 };
 int launch_bn_apply(int bf16, const BnApplyArgs& a, hipStream_t s);
 
@@ -53,6 +56,9 @@ struct BnBwdArgs {
     float count;
     const float* gamma; const float* mu; const float* rstd;
     float* db_part;                                            // [stat_row_blocks(rows)][ld] column sums of dpre
+    // Model groups: grid.z = models (0 or 1: one model).  Model m's dy, h, dpre, cs1 / cs2, gamma, mu, rstd and db_part lie
+    // model_stride BYTES behind model 0's.
+    int models; long model_stride;
 };
 int launch_bn_bwd(int bf16, const BnBwdArgs& a, hipStream_t s);
 int stat_row_blocks(int rows);                                 // row blocks of the column-statistic kernels
@@ -102,6 +108,9 @@ struct FmArgs {
     // wide feature layers: the loss is assembled from per-column-block partials (lscratch[gridDim.x]) by the last block to
     // arrive (*lcount: ticket, left at zero again) in a fixed order, instead of by one extra block that walks every column
     float* lscratch; unsigned int* lcount;
+    // Model groups: grid.z = models (0 or 1: one model).  Model m's cs, mask, dpre, loss_out, accum, lscratch and lcount (its own
+    // ticket) lie model_stride BYTES behind model 0's.  Without fp8 copies only.
+    int models; long model_stride;
 };
 int launch_fm(int bf16, const FmArgs& a, hipStream_t s);
 

@@ -184,9 +184,16 @@ template <typename T>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const BnApplyArgs a) {
     __shared__ float sc[CB], sh[CB];
     __shared__ float scr[16][CB], f1[CB], f2[CB];
-    const int t = threadIdx.x, col0 = blockIdx.x * CB, seg = blockIdx.z;
-    fold_partials(a.cs1 + (long)seg * a.cs_seg_stride, a.npart, a.ldcs, col0, a.ld, scr, f1);
-    fold_partials(a.cs2 + (long)seg * a.cs_seg_stride, a.npart, a.ldcs, col0, a.ld, scr, f2);
+    const int t = threadIdx.x, col0 = blockIdx.x * CB;
+    // model groups (BnApplyArgs::models): grid.z = model * nseg + segment; seg_mul = 0: one model
+    const int model = (int)((blockIdx.z * a.seg_mul) >> 16), seg = (int)blockIdx.z - model * a.nseg;
+    const long moff = (long)model * a.model_stride;
+    const float* const gamma = (const float*)((const char*)a.gamma + moff);
+    const float* const beta = (const float*)((const char*)a.beta + moff);
+    float* const mu = (float*)((char*)a.mu + moff);
+    float* const rstd_out = (float*)((char*)a.rstd + moff);
+    fold_partials((const float*)((const char*)a.cs1 + moff) + (long)seg * a.cs_seg_stride, a.npart, a.ldcs, col0, a.ld, scr, f1);
+    fold_partials((const float*)((const char*)a.cs2 + moff) + (long)seg * a.cs_seg_stride, a.npart, a.ldcs, col0, a.ld, scr, f2);
     if (t < CB) {
         const int col = col0 + t;
         float scale = 0.f, shift = 0.f;
@@ -194,16 +201,16 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const BnApplyArgs a) {
             const float mean = f1[t] / a.count;
             const float var = fmaxf(f2[t] / a.count - mean * mean, 0.f);
             const float rstd = 1.0f / sqrtf(var + a.eps);
-            if (col < a.cols) { scale = a.gamma[col] * rstd; shift = a.beta[col] - mean * scale; }
-            if (blockIdx.y == 0) { a.mu[(long)seg * a.ld + col] = mean; a.rstd[(long)seg * a.ld + col] = rstd; }
+            if (col < a.cols) { scale = gamma[col] * rstd; shift = beta[col] - mean * scale; }
+            if (blockIdx.y == 0) { mu[(long)seg * a.ld + col] = mean; rstd_out[(long)seg * a.ld + col] = rstd; }
         }
         sc[t] = scale; sh[t] = shift;
     }
     __syncthreads();
     const int cg = t & 7, rl = t >> 3, c0 = col0 + cg * 8;
     if (c0 >= a.ld) return;
-    const T* h = (const T*)a.h + (long)seg * a.seg_rows * a.ld;
-    T* out = (T*)a.out + (long)seg * a.seg_rows * a.ld;
+    const T* h = (const T*)((const char*)a.h + moff) + (long)seg * a.seg_rows * a.ld;
+    T* out = (T*)((char*)a.out + moff) + (long)seg * a.seg_rows * a.ld;
     const int r1 = min(a.rows, (int)(blockIdx.y + 1) * RB);
     for (int r = blockIdx.y * RB + rl; r < r1; r += 32) {
         float v[8];
@@ -221,12 +228,16 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(const BnBwdArgs a) {
     __shared__ float cA[CB], cB[CB], cM[CB], cR[CB], cG[CB];   // gamma*rstd/count ; dbeta ; mu ; rstd ; dgamma
     __shared__ float red[32][CB];
     const int t = threadIdx.x, col0 = blockIdx.x * CB;
-    fold_partials(a.cs1, a.npart, a.ldcs, col0, a.ld, red, cB);
-    fold_partials(a.cs2, a.npart, a.ldcs, col0, a.ld, red, cG);
+    const long moff = (long)blockIdx.z * a.model_stride;          // model groups (BnBwdArgs::models): this model's tensors
+    fold_partials((const float*)((const char*)a.cs1 + moff), a.npart, a.ldcs, col0, a.ld, red, cB);
+    fold_partials((const float*)((const char*)a.cs2 + moff), a.npart, a.ldcs, col0, a.ld, red, cG);
     if (t < CB) {
         const int col = col0 + t;
         float g = 0.f, mu = 0.f, rs = 0.f;
-        if (col < a.cols) { g = a.gamma[col]; mu = a.mu[col]; rs = a.rstd[col]; }
+        if (col < a.cols) {
+            g = ((const float*)((const char*)a.gamma + moff))[col]; mu = ((const float*)((const char*)a.mu + moff))[col];
+            rs = ((const float*)((const char*)a.rstd + moff))[col];
+        }
         cA[t] = g * rs / a.count; cM[t] = mu; cR[t] = rs;
     }
     __syncthreads();
@@ -235,9 +246,9 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(const BnBwdArgs a) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] = 0.f;
     if (c0 < a.ld) {
-        const T* dy = (const T*)a.dy;
-        const T* h = (const T*)a.h;
-        T* dpre = (T*)a.dpre;
+        const T* dy = (const T*)((const char*)a.dy + moff);
+        const T* h = (const T*)((const char*)a.h + moff);
+        T* dpre = (T*)((char*)a.dpre + moff);
         const int r1 = min(a.rows, (int)(blockIdx.y + 1) * RB);
         for (int r = blockIdx.y * RB + rl; r < r1; r += 32) {
             float hv[8], d[8], o[8];
@@ -261,7 +272,7 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(const BnBwdArgs a) {
         float s = 0.f;
 #pragma unroll
         for (int k = 0; k < 32; ++k) s += red[k][t];
-        a.db_part[(long)blockIdx.y * a.ld + col0 + t] = s;
+        ((float*)((char*)a.db_part + moff))[(long)blockIdx.y * a.ld + col0 + t] = s;
     }
 }
 
@@ -508,8 +519,12 @@ __global__ __launch_bounds__(256) void fm_kernel(const FmArgs a) {
     __shared__ float gj_lds[CB];
     __shared__ float scr[16][CB], sf[CB], sr[CB];
     const int t = threadIdx.x, col0 = blockIdx.x * CB;
-    const float* cs_real = a.cs + (long)a.npart_fake * a.ldcs;
+    const long moff = (long)blockIdx.z * a.model_stride;          // model groups (FmArgs::models): this model's tensors
+    const float* const cs = (const float*)((const char*)a.cs + moff);
+    const float* cs_real = cs + (long)a.npart_fake * a.ldcs;
     const bool dist_loss = a.lscratch != nullptr;
+    float* const loss_out = a.loss_out ? (float*)((char*)a.loss_out + moff) : nullptr;
+    float* const accum = a.accum ? (float*)((char*)a.accum + moff) : nullptr;
     if (!dist_loss && blockIdx.y == gridDim.y - 1) {
         // the extra block row: block x == 0 produces the loss scalar, which needs every column.  Thread = 4 columns x
         // every 4th partial row, all loads independent, so this block is no slower than the row blocks.
@@ -525,10 +540,10 @@ __global__ __launch_bounds__(256) void fm_kernel(const FmArgs a) {
                 f32x4 s0 = d, s1 = d, s2 = d, s3 = d;
                 int p = pl;
                 for (; p + 12 < a.npart_fake; p += 16) {
-                    s0 += *(const f32x4*)(a.cs + (long)p * a.ldcs + c0 + q); s1 += *(const f32x4*)(a.cs + (long)(p + 4) * a.ldcs + c0 + q);
-                    s2 += *(const f32x4*)(a.cs + (long)(p + 8) * a.ldcs + c0 + q); s3 += *(const f32x4*)(a.cs + (long)(p + 12) * a.ldcs + c0 + q);
+                    s0 += *(const f32x4*)(cs + (long)p * a.ldcs + c0 + q); s1 += *(const f32x4*)(cs + (long)(p + 4) * a.ldcs + c0 + q);
+                    s2 += *(const f32x4*)(cs + (long)(p + 8) * a.ldcs + c0 + q); s3 += *(const f32x4*)(cs + (long)(p + 12) * a.ldcs + c0 + q);
                 }
-                for (; p < a.npart_fake; p += 4) s0 += *(const f32x4*)(a.cs + (long)p * a.ldcs + c0 + q);
+                for (; p < a.npart_fake; p += 4) s0 += *(const f32x4*)(cs + (long)p * a.ldcs + c0 + q);
                 p = pl;
                 for (; p + 12 < a.npart_real; p += 16) {
                     s0 -= *(const f32x4*)(cs_real + (long)p * a.ldcs + c0 + q); s1 -= *(const f32x4*)(cs_real + (long)(p + 4) * a.ldcs + c0 + q);
@@ -549,12 +564,12 @@ __global__ __launch_bounds__(256) void fm_kernel(const FmArgs a) {
         }
         if (t == 0) {
             const float loss = tot / (float)a.feat_valid;
-            if (a.loss_out) *a.loss_out = loss;
-            if (a.accum) *a.accum += loss;
+            if (loss_out) *loss_out = loss;
+            if (accum) *accum += loss;
         }
         return;
     }
-    fold_partials(a.cs, a.npart_fake, a.ldcs, col0, a.feat, scr, sf);
+    fold_partials(cs, a.npart_fake, a.ldcs, col0, a.feat, scr, sf);
     fold_partials(cs_real, a.npart_real, a.ldcs, col0, a.feat, scr, sr);
     if (t < CB) {
         const float diff = (col0 + t < a.feat_valid) ? (sf[t] - sr[t]) / a.count : 0.f;
@@ -563,33 +578,36 @@ __global__ __launch_bounds__(256) void fm_kernel(const FmArgs a) {
             // this column block's share of sum_j diff_j^2 (one wave: CB == 64), then the ticket
             const float part = wave_sum(diff * diff);
             __shared__ unsigned int ticket;
+            float* const lscratch = (float*)((char*)a.lscratch + moff);              // (each model its own partials and ticket)
+            unsigned int* const lcount = (unsigned int*)((char*)a.lcount + moff);
             if (t == 0) {
-                a.lscratch[blockIdx.x] = part;
+                lscratch[blockIdx.x] = part;
                 __threadfence();
-                ticket = atomicAdd(a.lcount, 1u);
+                ticket = atomicAdd(lcount, 1u);
             }
             if (t == 0 && ticket == gridDim.x - 1) {
                 __threadfence();
                 float tot = 0.f;
-                for (unsigned int i = 0; i < gridDim.x; ++i) tot += ((volatile float*)a.lscratch)[i];      // fixed order: reproducible
+                for (unsigned int i = 0; i < gridDim.x; ++i) tot += ((volatile float*)lscratch)[i];      // fixed order: reproducible
                 const float loss = tot / (float)a.feat_valid;
-                if (a.loss_out) *a.loss_out = loss;
-                if (a.accum) *a.accum += loss;
-                *a.lcount = 0u;
+                if (loss_out) *loss_out = loss;
+                if (accum) *accum += loss;
+                *lcount = 0u;
             }
         }
     }
     __syncthreads();
     const int cg = t & 7, rl = t >> 3, c0 = col0 + cg * 8;
     if (c0 >= a.feat) return;
-    T* dpre = (T*)a.dpre;
+    T* dpre = a.dpre ? (T*)((char*)a.dpre + moff) : nullptr;
+    const uint16_t* const mask = (const uint16_t*)((const char*)a.mask + moff);
     const float q8s = a.q8_slot ? a.q8_slot->scale : 1.f;
     float q8_amax = 0.f;
     const int r1 = min(a.rows, (int)(blockIdx.y + 1) * a.rb);
     for (int r = blockIdx.y * a.rb + rl; r < r1; r += 32) {
         // lane-native mask layout (gemm.h): per (32-row block, column) two u16 words, one per lane half
         const int rr = r & 31, half = (rr >> 2) & 1, bit = (rr & 3) | ((rr >> 3) << 2);
-        const uint32_t* mp = (const uint32_t*)(a.mask + ((long)(r >> 5) * a.ldm + c0) * 2);
+        const uint32_t* mp = (const uint32_t*)(mask + ((long)(r >> 5) * a.ldm + c0) * 2);
         float v[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = (((mp[i] >> (16 * half)) >> bit) & 1u) ? gj_lds[cg * 8 + i] : 0.f;
@@ -841,7 +859,7 @@ int launch_stage(int bf16, const StageArgs& a, hipStream_t s) {
     if (maxm > 1) {
         // the kernel's multiply-shift is the exact quotient while grid.y * ry < 65536 (batches up to 8192 rows at 16 models)
         if ((long)b.ry * maxm * b.ry >= 65536) return -3;
-        b.ry_mul = (65536u + (uint32_t)b.ry - 1) / (uint32_t)b.ry + ((65536u % (uint32_t)b.ry) == 0 ? 1u : 0u);
+        b.ry_mul = div_mul16(b.ry);
     }
     dim3 grid(ceil_div(maxc, 128), b.ry * maxm, a.nseg);
     if (a.gauss) {
@@ -852,15 +870,19 @@ int launch_stage(int bf16, const StageArgs& a, hipStream_t s) {
 }
 
 int launch_bn_apply(int bf16, const BnApplyArgs& a, hipStream_t s) {
-    dim3 grid(ceil_div(a.ld, CB), ceil_div(a.rows, RB), std::max(1, a.nseg));
-    LAUNCH_T(bn_apply_kernel, grid, dim3(256), 0, s, a);
+    BnApplyArgs b = a;
+    b.nseg = std::max(1, a.nseg);
+    const int models = std::max(1, a.models);
+    b.seg_mul = models > 1 ? div_mul16(b.nseg) : 0u;      // (exact far beyond MRGAN_MAX_MODELS x 2 segments)
+    dim3 grid(ceil_div(a.ld, CB), ceil_div(a.rows, RB), b.nseg * models);
+    LAUNCH_T(bn_apply_kernel, grid, dim3(256), 0, s, b);
     RET_LAUNCH;
 }
 
 int stat_row_blocks(int rows) { return ceil_div(rows, RB); }
 
 int launch_bn_bwd(int bf16, const BnBwdArgs& a, hipStream_t s) {
-    dim3 grid(ceil_div(a.ld, CB), ceil_div(a.rows, RB));
+    dim3 grid(ceil_div(a.ld, CB), ceil_div(a.rows, RB), std::max(1, a.models));
     LAUNCH_T(bn_bwd_kernel, grid, dim3(256), 0, s, a);
     RET_LAUNCH;
 }
@@ -911,6 +933,7 @@ int launch_reduce_partials(const float* src, int nsrc, long stride, int n, int n
 
 int launch_fm(int bf16, const FmArgs& a, hipStream_t s) {
     if ((a.feat % 8) != 0) return -3;
+    if (a.models > 1 && a.q8_slot) return -3;      // model groups: without fp8 copies
     // every block first folds the column partial sums of its 64 columns (all row tiles): with a wide feature layer that
     // prologue would be repeated by thousands of 64-row blocks (0.34 ms at 4096 features x 8192 rows), so blocks take more rows
     // once ~512 of them exist
@@ -919,7 +942,7 @@ int launch_fm(int bf16, const FmArgs& a, hipStream_t s) {
     b.rb = std::max(RB, (int)round_up(ceil_div(a.rows, std::max(1, 512 / gx)), 32));
     const bool dist = gx >= 16 && a.lscratch && a.lcount;
     if (!dist) { b.lscratch = nullptr; b.lcount = nullptr; }
-    dim3 grid(gx, ceil_div(a.rows, b.rb) + (dist ? 0 : 1));      // + the loss block row of the narrow form
+    dim3 grid(gx, ceil_div(a.rows, b.rb) + (dist ? 0 : 1), std::max(1, a.models));      // + the loss block row of the narrow form
     LAUNCH_T(fm_kernel, grid, dim3(256), 0, s, b);
     RET_LAUNCH;
 }

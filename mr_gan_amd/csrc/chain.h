@@ -59,6 +59,10 @@ struct ChainArgs {
     ChainOp fwd[3];                    // D3 D4 D5 forward (CH_V_DTAIL, CH_V_GFWD)
     ChainOp dx[3];                     // dX through D5 D4 D3 (CH_V_DTAIL, CH_V_GBWD)
     int rows, nseg;                    // valid rows per segment, segments
+    // Model groups (the GROUP instantiations): grid.y = models (0 or 1: one model); the row block index (grid.x) and the LDS choreography are a single
+    // model's.  Model m's tensors -- W, bias, out, mask and cs of every ChainOp, a, fm_feat, and cs / dpre / loss_out / accum of
+    // fm -- lie model_stride BYTES behind model 0's; the head's follow HeadArgs::model_stride / labels_ms; noise seed + m.
+    long model_stride; int models;
     int block_rows;                    // rows per block: 64, or 32 (CH_V_GFWD / CH_V_GBWD only)
     const __bf16* a; long a_bs; int lda; int a_cols;      // forward chains: the first A image, rows of a[seg][S][lda], a_cols (padded) columns
     // CH_V_GBWD: the first A image = relu-mask ? gj : 0 with gj from the feature-matching moments (mr_gan.py:152-154)
@@ -93,6 +97,30 @@ __device__ __forceinline__ void img_col_bases(int (&obase)[4], int cip, int lh) 
 __device__ __forceinline__ int img_elem_off(const int (&obase)[4], int mi, int r) {
     return obase[((r >> 1) & 1) | (((r >> 2) & 1) << 1)] + (mi * 32 + acc_row(r, 0)) * 128;
 }
+
+// Model groups are a compile-time property of a chain kernel (GROUP): the D-tail chain sits at the SGPR limit, and the
+// offset arithmetic in the prologue of the two forward chains cost a single handle 0.5 .. 0.8 us per launch when it was
+// run-time.  A single handle's instantiation (GROUP = false) has offset 0 and model 0 as constants,
+// so everything below folds away.
+// bytes from model 0's copy of a tensor to this block's model's (wave-uniform)
+template <bool GROUP>
+__device__ __forceinline__ long chain_moff(long model_stride) {
+    if constexpr (GROUP) return (long)blockIdx.y * model_stride;
+    else return 0;
+}
+template <bool GROUP>
+__device__ __forceinline__ uint32_t chain_model_index() {
+    if constexpr (GROUP) return blockIdx.y;
+    else return 0u;
+}
+// this model's copy of a per-model tensor that the launcher guarantees (W, bias, a, the masks of dX, the head's tensors) ...
+template <typename P>
+__device__ __forceinline__ P* chain_model(P* p, long moff) { return (P*)((char*)p + moff); }
+template <typename P>
+__device__ __forceinline__ const P* chain_model(const P* p, long moff) { return (const P*)((const char*)p + moff); }
+// ... and of an optional one (out, a forward mask, cs, the loss scalars): null stays null
+template <typename P>
+__device__ __forceinline__ P* chain_model_opt(P* p, long moff) { return p ? (P*)((char*)p + moff) : p; }
 
 // LDS writes of every wave visible to every wave; VMEM left in flight
 __device__ __forceinline__ void lds_barrier() {

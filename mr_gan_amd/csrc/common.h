@@ -212,6 +212,9 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 static inline long round_up(long a, long b) { return (a + b - 1) / b * b; }
+// m with (i * m) >> 16 == i / d for every i * m < 2^32 the grouped launches form (model = index / segments, without a
+// division on the device): ceil(65536 / d), + 1 where d divides 65536; exact for i < 1024 at d <= 64
+static inline uint32_t div_mul16(int d) { return (65536u + (uint32_t)d - 1) / (uint32_t)d + ((65536u % (uint32_t)d) == 0 ? 1u : 0u); }
 
 // one fp8 tensor's scaling state.  Delayed scaling: a pass stores with `scale` (from the amax of the previous pass) and
 // records its own max |v| (before scaling); fp8_update_scales_kernel (gemm_fp8.hip) turns that into the next pass's scale.

@@ -314,6 +314,7 @@ int gen_fwd_tail(mrgan_handle* h, int nb, int fake_seg_slot, uint32_t fake_seg_i
     else { b.cs1 = h->cs_bn1; b.cs2 = h->cs_bn2; b.npart = h->tiles_m; b.cs_seg_stride = (long)h->tiles_m * n; }
     b.ldcs = n; b.count = h->stat_count; b.eps = h->cfg.bn_eps;
     b.gamma = h->gt[2].p; b.beta = h->gt[3].p; b.mu = h->bn_mu; b.rstd = h->bn_rstd;
+    b.models = h->grouped; b.model_stride = (long)h->W;
     PROF("bn_apply_kernel", launch_bn_apply(h->bf16, b, s));
     // fp8: BN(h1) is quantised with its transpose (the weight gradient of the G sub-step reads it, also after a paired pass)
     CHK(dense_fwd(h, h->g[1], KIND_D, h->hbn, h->B, nb, h->h2, ACT_SOFTPLUS, NO_NOISE, NO_MASK, NO_SUMS, s, Fp8Use{nullptr, true, true}));
@@ -371,7 +372,7 @@ int chain_block_rows(const mrgan_handle* h, int nseg) {
 double chain_flops(const mrgan_handle* h, const ChainArgs& c, bool with_head) {
     double f = 0.0;
     for (int l = 2; l < 5; ++l) f += 2.0 * h->B * c.nseg * h->d[l].K * h->d[l].N;     // each product appears once per direction
-    return f * (with_head ? 2.0 : 1.0);
+    return f * (with_head ? 2.0 : 1.0) * std::max(1, c.models);       // (a model group: every model's products)
 }
 int run_chain(mrgan_handle* h, const ChainArgs& c0, double flops, hipStream_t s) {
     ChainArgs c = c0;
@@ -398,12 +399,12 @@ int run_chain(mrgan_handle* h, const ChainArgs& c0, double flops, hipStream_t s)
 #endif
     // algorithmic bytes (logical widths, bf16): the first A image, every product's weights and stored output
     double bytes = 0.0;
-    const double nrows = (double)c.rows * c.nseg;
+    const double nrows = (double)c.rows * c.nseg * std::max(1, c.models);
     const bool has_fwd = c.variant != CH_V_GBWD, has_dx = c.variant != CH_V_GFWD;
     if (has_fwd) bytes += nrows * h->d[2].K * 2.0;
     else bytes += nrows * h->F * 2.0;                                  // the stored features whose sign is the relu mask
     for (int l = 2; l < 5; ++l) {
-        const double w = (double)h->d[l].K * h->d[l].N * 2.0;
+        const double w = (double)h->d[l].K * h->d[l].N * 2.0 * std::max(1, c.models);
         if (has_fwd) bytes += w + nrows * h->d[l].N * 2.0;
         if (has_dx) bytes += w + nrows * h->d[l].K * 2.0;
     }
@@ -419,6 +420,7 @@ int stage_common(StageArgs& st, mrgan_handle* h, const float* z, int stream_mode
         memset(&zs, 0, sizeof zs);
         zs.src = z; zs.ld = h->cfg.noise_size; zs.rows = h->B; zs.cols = h->cfg.noise_size; zs.cols_pad = h->nzp;
         zs.out = h->zbuf; zs.ldo = h->nzp; zs.sigma = 0.f; zs.site = SITE_Z; zs.seg = 0; zs.gen = z ? 0 : 1; zs.stream = z ? stream_mode : 0;
+        if (h->grouped > 1) { zs.models = h->grouped; zs.src_ms = h->gs.z; zs.out_ms = (long)h->W; }      // (a grouped sub-step: every model its own z)
         st.nseg = slot + 1;
         if (paired_z) {                                 // the following G sub-step's z (drawn on device at iteration + 1)
             StageSeg& z2 = st.s[slot + 1];
@@ -431,8 +433,11 @@ int stage_common(StageArgs& st, mrgan_handle* h, const float* z, int stream_mode
     st.cur = h->state + h->cur;
     return 0;
 }
-void data_seg(StageSeg& sg, mrgan_handle* h, const float* x, const int32_t* idx, long ld, int slot, uint32_t seg_id, int stream_mode) {
+// (src_ms / idx_ms: elements between the models' rows and index vectors in a grouped step)
+void data_seg(StageSeg& sg, mrgan_handle* h, const float* x, const int32_t* idx, long ld, int slot, uint32_t seg_id, int stream_mode,
+              long src_ms = 0, long idx_ms = 0) {
     memset(&sg, 0, sizeof sg);
+    if (h->grouped > 1) { sg.models = h->grouped; sg.src_ms = src_ms; sg.idx_ms = idx_ms; sg.out_ms = (long)h->W; }
     sg.src = x; sg.idx = idx; sg.ld = ld; sg.rows = h->B; sg.cols = h->cfg.d_in; sg.cols_pad = h->Dp;
     sg.out = rowptr(h, h->xin[0], (long)slot * h->S, h->Dp); sg.ldo = h->Dp;
     sg.sigma = h->cfg.sigma[0]; sg.site = 0; sg.seg = seg_id; sg.gen = 0; sg.stream = stream_mode;
@@ -458,6 +463,7 @@ HeadArgs head_args(mrgan_handle* h, std::initializer_list<int> kinds, int rows, 
     hd.dpre = h->dpre[4]; hd.dpre_bs = (long)h->S * h->Fp; hd.ldd = h->Fp;
     hd.part = h->head_part; hd.part_stride = h->head_stride; hd.off_db = h->Fp * h->KP; hd.off_dbf = h->Fp * h->KP + h->KP;
     hd.loss_part = h->loss_part;
+    if (h->grouped > 1) { hd.models = h->grouped; hd.model_stride = (long)h->W; }      // (labels_ms: the caller's)
     return hd;
 }
 
@@ -469,6 +475,7 @@ ChainArgs chain_args(mrgan_handle* h, int variant, int nseg, int block_rows) {
     c.rows = h->B; c.nseg = nseg; c.seg0 = 0;
     c.seed = h->cfg.seed; c.row0 = (uint32_t)(h->cfg.rank * h->B); c.st = h->state + h->cur; c.gauss = h->gauss;
     c.ablate = h->ablate;
+    c.models = h->grouped; c.model_stride = (long)h->W;
     if (variant != CH_V_GBWD) { c.a = (const __bf16*)h->xin[2]; c.a_bs = (long)h->S * h->d[2].Kp; c.lda = h->d[2].Kp; c.a_cols = h->d[2].Kp; }
     return c;
 }
@@ -480,7 +487,7 @@ ChainArgs chain_args(mrgan_handle* h, int variant, int nseg, int block_rows) {
 // before the head and their dX after it (8-class pitch only: at the 32-class pitch D3 .. D5 run per layer and the head alone).  Records how many partial rows of head_part / loss_part it wrote.
 int disc_head(mrgan_handle* h, const mrgan_disc_args* a, hipStream_t s) {
     HeadArgs hd = head_args(h, {HEAD_LAB, HEAD_UNL, HEAD_FAKE}, h->B, true);
-    hd.labels = a->labels_dev; hd.labels_stream = a->stream_mode;
+    hd.labels = a->labels_dev; hd.labels_stream = a->stream_mode; hd.labels_ms = h->gs.labels;
     hd.inv_count = 1.0f / (float)h->Bg; hd.unl_weight = h->cfg.unlabeled_weight;
     if (h->fp8) {                 // the head writes the e5m2 copies of dpre itself (no bf16 dpre, no quantiser pass)
         hd.dpre = nullptr;
@@ -500,7 +507,7 @@ int disc_head(mrgan_handle* h, const mrgan_disc_args* a, hipStream_t s) {
         h->head_nblk = 3 * ceil_div(h->B, CH_ROWS);
         return run_chain(h, c, chain_flops(h, c, true), s);
     }
-    if (h->head_wide) {
+    if (h->head_wide && h->grouped <= 1) {       // (head_wide_kernel / w6_split_kernel carry no model index: a group takes head_kernel)
         HeadWideArgs hw;
         memset(&hw, 0, sizeof hw);
         hw.h = hd; hw.mask = h->mask[4]; hw.mask_bs = mask_pitch(h->S, h->ldm[4]); hw.ldm = h->ldm[4];
@@ -534,8 +541,8 @@ int disc_phase(mrgan_handle* h, const mrgan_disc_args* a, int phase, hipStream_t
         prof_backlog(h, s);
         StageArgs st;
         memset(&st, 0, sizeof st);
-        data_seg(st.s[0], h, a->x_lab_dev, a->idx_lab_dev, a->ld_x_lab, 0, 0, a->stream_mode);
-        data_seg(st.s[1], h, a->x_unl_dev, a->idx_unl_dev, a->ld_x_unl, 1, 1, a->stream_mode);
+        data_seg(st.s[0], h, a->x_lab_dev, a->idx_lab_dev, a->ld_x_lab, 0, 0, a->stream_mode, h->gs.x_lab, h->gs.idx_lab);
+        data_seg(st.s[1], h, a->x_unl_dev, a->idx_unl_dev, a->ld_x_unl, 1, 1, a->stream_mode, h->gs.x_unl, h->gs.idx_unl);
         set_gen_view(h, 0);
         stage_common(st, h, a->z_dev, a->stream_mode, 2, h->pair_gen != 0);
         h->real_staged = 0;
@@ -590,6 +597,7 @@ int fm_grad(mrgan_handle* h, hipStream_t s) {
     f.mask = h->mask[4]; f.ldm = h->ldm[4]; f.dpre = h->dpre[4]; f.ldd = h->Fp; f.rows = h->B;
     f.loss_out = h->step_out + 3; f.accum = h->accum + 3;
     f.lscratch = h->fm_scratch; f.lcount = h->fm_count;
+    f.models = h->grouped; f.model_stride = (long)h->W;
     if (h->fp8) { f.dpre = nullptr; f.q8 = h->d[4].q.g8; f.ldq8 = h->Fp; f.q8_slot = h->slots + h->d[4].q.sg[KIND_G]; }
     if (!h->use_chain) {
         PROF("fm_kernel", launch_fm(h->bf16, f, s));
@@ -626,7 +634,7 @@ int gen_phase(mrgan_handle* h, const mrgan_gen_args* a, int phase, hipStream_t s
         const bool staged = ready && h->real_staged;           // the D sub-step's stage launch already placed the real rows in slot 4
         h->real_staged = 0;
         if (!staged) {
-            data_seg(st.s[0], h, a->x_unl_dev, a->idx_unl_dev, a->ld_x_unl, h->xbase + 1, 1, a->stream_mode);   // real rows
+            data_seg(st.s[0], h, a->x_unl_dev, a->idx_unl_dev, a->ld_x_unl, h->xbase + 1, 1, a->stream_mode, h->gs.x_unl, h->gs.idx_unl);   // real rows
             st.nseg = 1;
             stage_common(st, h, a->z_dev, a->stream_mode, ready ? -1 : 1);
             PROF("stage_kernel", launch_stage(h->bf16, st, s));
@@ -660,6 +668,7 @@ int gen_phase(mrgan_handle* h, const mrgan_gen_args* a, int phase, hipStream_t s
         else { b.cs1 = h->cs_dbeta; b.cs2 = h->cs_dgamma; b.npart = tm; }
         b.ldcs = N1p; b.count = h->stat_count; b.gamma = h->gt[2].p; b.mu = h->bn_mu; b.rstd = h->bn_rstd;
         b.db_part = h->db1g_part;
+        b.models = h->grouped; b.model_stride = (long)h->W;
         PROF("bn_bwd_kernel", launch_bn_bwd(h->bf16, b, s));
         // the generator's weight gradients; in fp8 the wide one (G2) is a product of its own, after the grouped launch
         const DwJob jobs[3] = {{&h->g[2], h->h2, h->dxfake}, {&h->g[0], h->zbuf, h->dpre1g}, {&h->g[1], h->hbn, h->dpre2g}};
@@ -728,10 +737,105 @@ int sup_step_group(mrgan_handle* h, const mrgan_sup_group_args* a, hipStream_t s
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// the GAN sub-steps of a group handle: disc_phase / gen_phase with every launch covering all models
+// ---------------------------------------------------------------------------------------------------
+// For the scope of one grouped sub-step the handle describes all models: h->grouped (every argument builder adds the model
+// count and the stride W) and h->gs (the strides of the caller's inputs).  Every return path leaves the handle single.
+struct GroupScope {
+    mrgan_handle* h;
+    GroupScope(mrgan_handle* h_, const mrgan_handle::GroupStrides& gs) : h(h_) { h->grouped = h->models; h->gs = gs; h->pair_gen = 0; h->pair_g = nullptr; }
+    ~GroupScope() { h->grouped = 1; memset(&h->gs, 0, sizeof h->gs); }
+};
+mrgan_disc_args single_args(const mrgan_disc_group_args* a) {
+    mrgan_disc_args d;
+    memset(&d, 0, sizeof d);
+    d.x_lab_dev = a->x_lab_dev; d.idx_lab_dev = a->idx_lab_dev; d.labels_dev = a->labels_dev;
+    d.x_unl_dev = a->x_unl_dev; d.idx_unl_dev = a->idx_unl_dev; d.z_dev = a->z_dev;
+    d.ld_x_lab = a->ld_x_lab; d.ld_x_unl = a->ld_x_unl; d.stream_mode = a->stream_mode;
+    return d;
+}
+mrgan_gen_args single_args(const mrgan_gen_group_args* a) {
+    mrgan_gen_args g;
+    memset(&g, 0, sizeof g);
+    g.x_unl_dev = a->x_unl_dev; g.idx_unl_dev = a->idx_unl_dev; g.z_dev = a->z_dev; g.ld_x_unl = a->ld_x_unl; g.stream_mode = a->stream_mode;
+    return g;
+}
+int disc_step_group(mrgan_handle* h, const mrgan_disc_group_args* a, hipStream_t s) {
+    GroupScope scope(h, {(long)a->x_lab_model_stride, (long)a->idx_lab_model_stride, (long)a->labels_model_stride,
+                         (long)a->x_unl_model_stride, (long)a->idx_unl_model_stride, (long)a->z_model_stride});
+    const mrgan_disc_args d = single_args(a);
+    for (int p = 0; p < MRGAN_D_NPHASES; ++p) { const int r = disc_phase(h, &d, p, s); if (r) return r; }
+    return 0;
+}
+int gen_step_group(mrgan_handle* h, const mrgan_gen_group_args* a, hipStream_t s) {
+    GroupScope scope(h, {0, 0, 0, (long)a->x_unl_model_stride, (long)a->idx_unl_model_stride, (long)a->z_model_stride});
+    const mrgan_gen_args g = single_args(a);
+    h->gen_ready = 0;                                  // (a group's G sub-step always runs its own generator forward)
+    for (int p = 0; p < MRGAN_G_NPHASES; ++p) { const int r = gen_phase(h, &g, p, s); if (r) return r; }
+    return 0;
+}
+int check_disc_args(const mrgan_handle* h, const mrgan_disc_args* a);
+int check_gen_args(const mrgan_handle* h, const mrgan_gen_args* a);
+int check_group_handle(const mrgan_handle* h, const char* entry) {
+    if (h->models > 1) return 0;
+    return fail(-3, "%s: not a group handle (mrgan_config.models = %d); a single model steps through mrgan_disc_step / mrgan_gen_step / mrgan_train_pair",
+                entry, (int)h->cfg.models);
+}
+int check_disc_group_args(const mrgan_handle* h, const mrgan_disc_group_args* a) {
+    if (!a) return fail(-2, "disc_step_group: null arguments");
+    const mrgan_disc_args d = single_args(a);
+    const int r = check_disc_args(h, &d);
+    if (r) return r;
+    if (a->x_lab_model_stride < 0 || a->idx_lab_model_stride < 0 || a->labels_model_stride < 0 || a->x_unl_model_stride < 0 ||
+        a->idx_unl_model_stride < 0 || a->z_model_stride < 0)
+        return fail(-2, "disc_step_group: negative model stride");
+    return 0;
+}
+int check_gen_group_args(const mrgan_handle* h, const mrgan_gen_group_args* a) {
+    if (!a) return fail(-2, "gen_step_group: null arguments");
+    const mrgan_gen_args g = single_args(a);
+    const int r = check_gen_args(h, &g);
+    if (r) return r;
+    if (a->x_unl_model_stride < 0 || a->idx_unl_model_stride < 0 || a->z_model_stride < 0) return fail(-2, "gen_step_group: negative model stride");
+    return 0;
+}
+
+// One (D sub-step, G sub-step) pair, `both`, launched eagerly or -- want_graph -- as the replay of a captured graph.
+// A pair flips the state slot twice, so every kernel argument is identical on every replay as long as the slot parity and the
+// caller's argument blocks (dargs / gargs: the single or the group ones, compared byte by byte) are those of the capture.
+template <typename Both>
+int run_pair(mrgan_handle* h, bool want_graph, const void* dargs, size_t dn, const void* gargs, size_t gn, hipStream_t s, Both both) {
+    if (!want_graph) return both();
+    if (dn + gn > sizeof h->graph_key) return fail(-1, "run_pair: argument blocks larger than the graph key");
+    if (h->graph_ready && (h->graph_cur != h->cur || h->graph_key_d != dn || h->graph_key_g != gn || memcmp(h->graph_key, dargs, dn) != 0 ||
+                           memcmp(h->graph_key + dn, gargs, gn) != 0)) {
+        hipGraphExecDestroy(h->graph_exec);
+        h->graph_exec = nullptr; h->graph_ready = false;
+    }
+    if (!h->graph_ready) {
+        hipGraph_t graph;
+        const int cur0 = h->cur;
+        HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        const int r = both();
+        graph = nullptr;
+        hipError_t e = hipStreamEndCapture(s, &graph);
+        if (r) { if (graph) hipGraphDestroy(graph); return r; }       // a launch failed during capture: drop the partial graph
+        if (e != hipSuccess) return fail(-10, "hipStreamEndCapture: %s", hipGetErrorString(e));
+        e = hipGraphInstantiate(&h->graph_exec, graph, nullptr, nullptr, 0);
+        hipGraphDestroy(graph);
+        if (e != hipSuccess) return fail(-10, "hipGraphInstantiate: %s", hipGetErrorString(e));
+        memcpy(h->graph_key, dargs, dn); memcpy(h->graph_key + dn, gargs, gn);
+        h->graph_key_d = dn; h->graph_key_g = gn; h->graph_cur = cur0; h->graph_ready = true;
+    }
+    HIPCHK(hipGraphLaunch(h->graph_exec, s));
+    return 0;
+}
+
 // what a group handle does not do (status -3)
 int refuse_group(const mrgan_handle* h, const char* entry) {
     if (h->models <= 1) return 0;
-    return fail(-3, "%s: a group handle (models = %d) trains through mrgan_sup_step_group only; the grouped GAN step (generator, BatchNorm, feature matching, chains) is not built", entry, h->models);
+    return fail(-3, "%s: a group handle (models = %d) trains through the _group entries (mrgan_sup_step_group, mrgan_disc_step_group, mrgan_gen_step_group, mrgan_train_pair_group)", entry, h->models);
 }
 
 int check_disc_args(const mrgan_handle* h, const mrgan_disc_args* a) {
@@ -951,29 +1055,57 @@ int mrgan_train_pair(mrgan_handle* h, const mrgan_disc_args* d, const mrgan_gen_
         h->gen_ready = 0;
         return rr;
     };
-    if (!want_graph || (h->fp8 && !(h->fp8_cal[0] == 1 && h->fp8_cal[1] == 1))) return both();     // (the calibrating first pair runs eagerly)
-    // A pair flips the state slot twice, so every kernel argument is identical on every replay as long as
-    // the slot parity and the caller's pointers are those of the capture.
-    if (h->graph_ready && (h->graph_cur != h->cur || memcmp(&h->graph_d, d, sizeof *d) != 0 || memcmp(&h->graph_g, g, sizeof *g) != 0)) {
-        hipGraphExecDestroy(h->graph_exec);
-        h->graph_exec = nullptr; h->graph_ready = false;
+    // (the calibrating first pair of an fp8 handle runs eagerly)
+    return run_pair(h, want_graph && !(h->fp8 && !(h->fp8_cal[0] == 1 && h->fp8_cal[1] == 1)), d, sizeof *d, g, sizeof *g, s, both);
+}
+
+int mrgan_disc_step_group(mrgan_handle* h, const mrgan_disc_group_args* a, float* out3, mrgan_stream stream) {
+    if (!h) return fail(-1, "null handle");
+    int r = check_group_handle(h, "disc_step_group");
+    if (!r) r = check_disc_group_args(h, a);
+    if (r) return r;
+    hipStream_t s = (hipStream_t)stream;
+    r = disc_step_group(h, a, s);
+    if (r) return r;
+    if (out3) {
+        for (int m = 0; m < h->models; ++m)
+            HIPCHK(hipMemcpyAsync(out3 + 3 * m, model_at(h, h->step_out, m), 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
     }
-    if (!h->graph_ready) {
-        hipGraph_t graph;
-        const int cur0 = h->cur;
-        HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        r = both();
-        graph = nullptr;
-        hipError_t e = hipStreamEndCapture(s, &graph);
-        if (r) { if (graph) hipGraphDestroy(graph); return r; }       // a launch failed during capture: drop the partial graph
-        if (e != hipSuccess) return fail(-10, "hipStreamEndCapture: %s", hipGetErrorString(e));
-        e = hipGraphInstantiate(&h->graph_exec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (e != hipSuccess) return fail(-10, "hipGraphInstantiate: %s", hipGetErrorString(e));
-        h->graph_d = *d; h->graph_g = *g; h->graph_cur = cur0; h->graph_ready = true;
-    }
-    HIPCHK(hipGraphLaunch(h->graph_exec, s));
     return 0;
+}
+
+int mrgan_gen_step_group(mrgan_handle* h, const mrgan_gen_group_args* a, float* out1, mrgan_stream stream) {
+    if (!h) return fail(-1, "null handle");
+    int r = check_group_handle(h, "gen_step_group");
+    if (!r) r = check_gen_group_args(h, a);
+    if (r) return r;
+    hipStream_t s = (hipStream_t)stream;
+    r = gen_step_group(h, a, s);
+    if (r) return r;
+    if (out1) {
+        for (int m = 0; m < h->models; ++m)
+            HIPCHK(hipMemcpyAsync(out1 + m, model_at(h, h->step_out, m) + 3, sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
+int mrgan_train_pair_group(mrgan_handle* h, const mrgan_disc_group_args* d, const mrgan_gen_group_args* g, mrgan_stream stream) {
+    if (!h) return fail(-1, "null handle");
+    int r = check_group_handle(h, "train_pair_group");
+    if (!r) r = check_disc_group_args(h, d);
+    if (!r) r = check_gen_group_args(h, g);
+    if (r) return r;
+    hipStream_t s = (hipStream_t)stream;
+    const bool want_graph = !h->prof && (h->cfg.flags & MRGAN_FLAG_GRAPH) && d->stream_mode && g->stream_mode;
+    // the two generator forwards run separately: bit-identical to the paired two-segment pass of mrgan_train_pair
+    auto both = [&]() {
+        int rr = disc_step_group(h, d, s);
+        if (!rr) rr = gen_step_group(h, g, s);
+        return rr;
+    };
+    return run_pair(h, want_graph, d, sizeof *d, g, sizeof *g, s, both);
 }
 
 int mrgan_eval_error(mrgan_handle* h, const float* x, const int32_t* idx, int64_t ld, const int32_t* labels, int64_t n,

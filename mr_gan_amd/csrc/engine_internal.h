@@ -95,6 +95,9 @@ struct mrgan_handle {
     size_t W;                             // model stride in bytes
     int sel;                              // mrgan_select_model: the model the per-model entries address
     int grouped;                          // models while a grouped step builds its launches (every launch covers all models), else 1
+    // element strides between the models' inputs of the grouped GAN sub-step being built (mrgan_disc_group_args /
+    // mrgan_gen_group_args); all zero outside one
+    struct GroupStrides { long x_lab, idx_lab, labels, x_unl, idx_unl, z; } gs;
 
     std::vector<Tensor> gt, dt;           // Keras order
     Dense g[3], d[6];
@@ -141,7 +144,9 @@ struct mrgan_handle {
     bool prof; std::vector<ProfRec> prof_recs; std::vector<std::string> prof_names;
 
     // graph replay of (D step, G step)
-    hipGraphExec_t graph_exec; bool graph_ready; int graph_cur; mrgan_disc_args graph_d; mrgan_gen_args graph_g;
+    // (graph_key: the bytes of the two argument blocks the graph was captured with -- the single or the group ones)
+    hipGraphExec_t graph_exec; bool graph_ready; int graph_cur;
+    unsigned char graph_key[sizeof(mrgan_disc_group_args) + sizeof(mrgan_gen_group_args)]; size_t graph_key_d, graph_key_g;
 };
 
 namespace mrgan {

@@ -96,7 +96,7 @@ int validate(const mrgan_config& c) {
     if (c.models > 1) {
         // a group trains through mrgan_sup_step_group: fp32 / bf16, fused Adam, one device
         if (c.world != 1) return fail(-3, "a model group (models = %d) needs world = 1: data-parallel groups are not built", c.models);
-        if (c.dtype == MRGAN_FP8) return fail(-3, "a model group (models = %d) cannot be an fp8 handle: the grouped step is the supervised one", c.models);
+        if (c.dtype == MRGAN_FP8) return fail(-3, "a model group (models = %d) cannot be an fp8 handle: fp8 images and scaling slots per model are not built", c.models);
         if (c.flags & (MRGAN_FLAG_FLAT_GRADS | MRGAN_FLAG_SYNC_STATS))
             return fail(-3, "a model group (models = %d) cannot have MRGAN_FLAG_FLAT_GRADS or MRGAN_FLAG_SYNC_STATS: data-parallel groups are not built", c.models);
     }

@@ -131,7 +131,7 @@ __device__ __forceinline__ void epilogue_prefetch(EpiPrefetch<MR, NR>& pf, const
             if (e.cs_mode == CS_SUM_XHAT) {
                 const bool cok = col < e.n_valid && col < g.N;
                 const int cc = cok ? col : 0;
-                const float m = e.bn_mu[cc], r = e.bn_rstd[cc];
+                const float m = model_ptr(e.bn_mu, e, model)[cc], r = model_ptr(e.bn_rstd, e, model)[cc];
                 pf.mu[ni] = cok ? m : 0.f; pf.rstd[ni] = cok ? r : 0.f;
             }
         }
@@ -381,7 +381,8 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[MR][NR], const GemmArgs& 
                         const int rsub = row_blk + (wm * MR + mi) * 32 + 4 * lh;
                         if (e.cs_mode == CS_SUM_XHAT) {
                             const bool cok = col < e.n_valid && col < g.N;
-                            const float mu = pf ? pf->mu[ni] : (cok ? e.bn_mu[col] : 0.f), rstd = pf ? pf->rstd[ni] : (cok ? e.bn_rstd[col] : 0.f);
+                            const float mu = pf ? pf->mu[ni] : (cok ? model_ptr(e.bn_mu, e, model)[col] : 0.f);
+                            const float rstd = pf ? pf->rstd[ni] : (cok ? model_ptr(e.bn_rstd, e, model)[col] : 0.f);
 #pragma unroll
                             for (int r = 0; r < 16; ++r) {
                                 const int row = rsub + (r & 3) + 8 * (r >> 2);
@@ -545,7 +546,7 @@ inline GemmArgs gemm_dw_args(int K, int N, int vrows, int splits, int kchunk, in
 inline GemmArgs gemm_group(GemmArgs g, int models, long model_stride) {
     if (models <= 1) return g;
     g.e.segs = g.nbatch; g.e.model_stride = model_stride;
-    g.e.model_mul = (65536u + (uint32_t)g.nbatch - 1) / (uint32_t)g.nbatch + ((65536u % (uint32_t)g.nbatch) == 0 ? 1u : 0u);
+    g.e.model_mul = div_mul16(g.nbatch);
     g.nbatch *= models;
     return g;
 }

@@ -37,7 +37,7 @@ __device__ __forceinline__ void wait_vm(int n) {
 struct Stamps {
     unsigned long long acc[8], prev;
     __device__ void start() { for (int i = 0; i < 8; ++i) acc[i] = 0; prev = __builtin_amdgcn_s_memtime(); }
-    __device__ void store(unsigned long long* out) const { if (out) for (int i = 0; i < 8; ++i) out[(long)blockIdx.x * 8 + i] = acc[i]; }
+    __device__ void store(unsigned long long* out) const { if (out) for (int i = 0; i < 8; ++i) out[((long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + i] = acc[i]; }
 };
 #define CH_STAMP(i) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); st.acc[i] += n_ - st.prev; st.prev = n_; } while (0)
 #else
@@ -109,22 +109,27 @@ __device__ __forceinline__ void flush_copy(Stream& sm, int rows_valid, int t) {
 // what the head reads from global memory, fetched in the kernel's prologue: inside the head each of these would be an exposed
 // L2 / HBM round trip with the whole block waiting at the next barrier (the labels even two dependent ones)
 struct HeadInputs { f32x4 w0, w1, bw0, bw1, b0, b1; int label; };
+template <bool GROUP>
 __device__ __forceinline__ void head_prefetch(const ChainArgs& a, HeadInputs& hi, int seg, int row_blk, int rows_valid, int t) {
     const HeadArgs& h = a.head;
     const int lane = t & 63, lc = lane & 31, wave = t >> 6;
     const int k = min(t & (CH_PW - 1), h.feat_valid - 1), j = min(wave * 32 + lc, h.feat_valid - 1);
-    hi.w0 = *(const f32x4*)(h.w + (long)k * h.ldw); hi.w1 = *(const f32x4*)(h.w + (long)k * h.ldw + 4);
-    hi.bw0 = *(const f32x4*)(h.w + (long)j * h.ldw); hi.bw1 = *(const f32x4*)(h.w + (long)j * h.ldw + 4);
+    const long hoff = chain_moff<GROUP>(h.model_stride);      // model groups: this model's W6 / b6 (bytes) and labels (elements)
+    const float* const w6 = chain_model(h.w, hoff);
+    const float* const b6 = chain_model(h.b, hoff);
+    hi.w0 = *(const f32x4*)(w6 + (long)k * h.ldw); hi.w1 = *(const f32x4*)(w6 + (long)k * h.ldw + 4);
+    hi.bw0 = *(const f32x4*)(w6 + (long)j * h.ldw); hi.bw1 = *(const f32x4*)(w6 + (long)j * h.ldw + 4);
     hi.b0 = (f32x4){0.f, 0.f, 0.f, 0.f}; hi.b1 = hi.b0;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) { hi.b0[c] = h.b[min(c, h.classes - 1)]; hi.b1[c] = h.b[min(4 + c, h.classes - 1)]; }
+    for (int c = 0; c < 4; ++c) { hi.b0[c] = b6[min(c, h.classes - 1)]; hi.b1[c] = b6[min(4 + c, h.classes - 1)]; }
     hi.label = 0;
     if (h.seg_kind[seg] == HEAD_LAB) {
-        const long lo = h.labels_stream ? (long)h.st->batch * h.rows : 0;
+        const long lo = (h.labels_stream ? (long)h.st->batch * h.rows : 0) + chain_moff<GROUP>(h.labels_ms);
         hi.label = h.labels[lo + row_blk + min(lane, rows_valid - 1)];
     }
 }
 
+template <bool GROUP>
 __device__ __forceinline__ void chain_head(const ChainArgs& a, char* lds, Stream& sm, const HeadInputs& hi, const uint32_t (&mw)[2][2], int seg,
                                            int rb, int nrb, int row_blk, int rows_valid, int t) {
     const HeadArgs& h = a.head;
@@ -192,7 +197,8 @@ __device__ __forceinline__ void chain_head(const ChainArgs& a, char* lds, Stream
     lds_barrier();
 
     // ---- 3. per row (wave 0: lane <-> row): losses, error, dlogits ----
-    float* part_row = h.part + (long)blk * h.part_stride;
+    const long hoff = chain_moff<GROUP>(h.model_stride);      // model groups: this model's partial rows, loss partials and dpre
+    float* part_row = chain_model(h.part, hoff) + (long)blk * h.part_stride;
     if (wave == 0) {
         const int r = lane;
         float l[KMAX];
@@ -230,20 +236,23 @@ __device__ __forceinline__ void chain_head(const ChainArgs& a, char* lds, Stream
         const int j = wave * 32 + lc;                         // registers 0 .. 3 = classes 4 lh .. 4 lh + 3 of feature j
         if (j < h.feat) *(f32x4*)(part_row + (long)j * KMAX + 4 * lh) = (f32x4){acc[0], acc[1], acc[2], acc[3]};
     }
-    head_block_sums(red, h, blk, part_row, wave, lane);
+    head_block_sums(red, h, blk, part_row, wave, lane, hoff);
     lds_barrier();
     // dL/d(pre5): the next product's A image is complete; its copy for the weight-gradient launch leaves at the end of that
     // product's k-loop
-    sm.cp_img = oimg; sm.cp_out = (__bf16*)h.dpre + (long)seg * h.dpre_bs + (long)row_blk * h.ldd;
+    sm.cp_img = oimg; sm.cp_out = (__bf16*)chain_model_opt(h.dpre, hoff) + (long)seg * h.dpre_bs + (long)row_blk * h.ldd;
     sm.cp_ldo = h.ldd; sm.cp_col0 = 0; sm.cp_ncols = h.feat;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
 // feature-matching gradient as the first A image (mr_gan.py:152-154): dL/d(pre5) = relu-mask ? 2/(J B) (m_gen - m_real) : 0
 // ------------------------------------------------------------------------------------------------------------------
-template <int ROWS>
+template <int ROWS, bool GROUP>
 __device__ __forceinline__ void chain_fmgrad(const ChainArgs& a, char* lds, int rb, int row_blk, int rows_valid, int t, Stamps& st) {
     const FmArgs& f = a.fm;
+    const long moff = chain_moff<GROUP>(a.model_stride);      // model groups: this model's features, moments and loss scalars
+    const __bf16* const fm_feat = chain_model(a.fm_feat, moff);
+    const float* const cs = chain_model(f.cs, moff);
     // the stored features of this block's rows (their sign is relu'(pre5), used at the end): requested first, so that their round
     // trip runs beside the fold of the partial sums instead of behind it
     constexpr int NCH = ROWS * CH_PW / 8 / CH_THREADS;
@@ -252,11 +261,11 @@ __device__ __forceinline__ void chain_fmgrad(const ChainArgs& a, char* lds, int 
     for (int u = 0; u < NCH; ++u) {
         const int q = t + CH_THREADS * u, r = q >> 5, c0 = (q & 31) * 8;
         const bool ok = r < rows_valid && c0 < f.feat;
-        fv[u] = *(const bf16x8*)(a.fm_feat + (long)(row_blk + (ok ? r : 0)) * a.fm_ldf + (ok ? c0 : 0));
+        fv[u] = *(const bf16x8*)(fm_feat + (long)(row_blk + (ok ? r : 0)) * a.fm_ldf + (ok ? c0 : 0));
     }
     float* gj = (float*)(lds + chain_img(ROWS, 1));          // 9 KiB in the first product's output image: idle until its epilogue (both ring stages are in flight)
     float* scr = gj + CH_PW;                                  // [8][256]
-    const float* cs_real = f.cs + (long)f.npart_fake * f.ldcs;
+    const float* cs_real = cs + (long)f.npart_fake * f.ldcs;
     // fold the per-row-block partial sums: thread <-> (4 columns, every 8th partial row), 64 partial rows of both streams per
     // round trip (16 loads of 16 bytes in flight per thread), then an 8-way combine through LDS
     {
@@ -271,7 +280,7 @@ __device__ __forceinline__ void chain_fmgrad(const ChainArgs& a, char* lds, int 
             for (int base = 0; base < nmax; base += 64) {
                 f32x4 vf[8], vr[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) vf[i] = *(const f32x4*)(f.cs + (long)min(base + pg + 8 * i, f.npart_fake - 1) * f.ldcs + cq);
+                for (int i = 0; i < 8; ++i) vf[i] = *(const f32x4*)(cs + (long)min(base + pg + 8 * i, f.npart_fake - 1) * f.ldcs + cq);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) vr[i] = *(const f32x4*)(cs_real + (long)min(base + pg + 8 * i, f.npart_real - 1) * f.ldcs + cq);
 #pragma unroll
@@ -294,15 +303,15 @@ __device__ __forceinline__ void chain_fmgrad(const ChainArgs& a, char* lds, int 
         gj[c] = f.grad_scale * 2.0f / ((float)f.feat_valid * f.count) * diff;
         sq = diff * diff;
     }
-    if (rb == 0 && blockIdx.x == 0) {                         // the loss scalar, once
+    if (rb == 0 && blockIdx.x == 0) {                         // the loss scalar, once (per model)
         sq = wave_sum(sq);
         __syncthreads();
         if ((t & 63) == 0) scr[t >> 6] = sq;
         __syncthreads();
         if (t == 0) {
             const float loss = (scr[0] + scr[1] + scr[2] + scr[3]) / (float)f.feat_valid;
-            if (f.loss_out) *f.loss_out = loss;
-            if (f.accum) *f.accum += loss;
+            if (f.loss_out) *chain_model(f.loss_out, moff) = loss;      // (tested non-null: the plain offset)
+            if (f.accum) *chain_model(f.accum, moff) += loss;
         }
     }
     __syncthreads();
@@ -330,7 +339,7 @@ __device__ __forceinline__ void chain_fmgrad(const ChainArgs& a, char* lds, int 
 // images: chain.h), are compile-time; `bias` (forward) and `mw` (the relu-mask words
 // of the output tile: read by dX, returned by forward) live in registers, loaded or produced before this call.
 // GAUSS: forward noise from the true-Gaussian generator (common.h: gauss_block; rowhash[] then holds row-pair hashes)
-template <int MODE, int J, int MI, bool GAUSS>
+template <int MODE, int J, int MI, bool GAUSS, bool GROUP>
 __device__ __forceinline__ void chain_gemm(const ChainArgs& a, const ChainOp& op, const __bf16* nextW, const int nextK, const int nextN,
                                            char* lds, Stream& sm, const float bias,
                                            uint32_t (&mw)[2][MI], const int seg, const int nrb, const int rb, const int row_blk,
@@ -346,7 +355,7 @@ __device__ __forceinline__ void chain_gemm(const ChainArgs& a, const ChainOp& op
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) rowhash[mi] = 0u;
     if (noisy) {
-        const uint32_t nkey = noise_key(a.seed, op.site * 256u + (uint32_t)(a.seg0 + seg), iter);
+        const uint32_t nkey = noise_key(a.seed + (uint64_t)chain_model_index<GROUP>(), op.site * 256u + (uint32_t)(a.seg0 + seg), iter);      // (model m: seed + m)
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
             if constexpr (GAUSS) rowhash[mi] = gauss_pairhash(nkey, a.row0 + (uint32_t)(row_blk + mi * 32), lane);
@@ -529,9 +538,9 @@ __device__ __forceinline__ void chain_gemm(const ChainArgs& a, const ChainOp& op
 }
 
 // relu-mask words of a dX product's output tile, from HBM (written by an earlier launch)
-template <int MI>
+template <int MI, bool GROUP>
 __device__ __forceinline__ void load_mask_words(const ChainArgs& a, const ChainOp& op, uint32_t (&mw)[2][MI], int seg, int row_blk, int wave, int lc, int lh) {
-    const uint16_t* mask = op.mask + (long)seg * op.mask_bs;
+    const uint16_t* mask = chain_model(op.mask, chain_moff<GROUP>(a.model_stride)) + (long)seg * op.mask_bs;
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
         const int col = pass * CH_PW + wave * 32 + lc;
@@ -551,7 +560,8 @@ __device__ __forceinline__ void load_mask_words(const ChainArgs& a, const ChainO
 // reload sits between two products.
 // MI: 32-row groups per block (2: 64 rows, the D sub-step's launch; 1: 32 rows, for launches that would leave most CUs idle)
 // GAUSS: the forward products draw their layer noise from the true-Gaussian generator (ChainArgs::gauss; never with CH_V_GBWD)
-template <int VARIANT, int MI, bool GAUSS = false>
+// GROUP: the launch covers the models of a group handle, grid.y = models (chain.h: chain_moff); false: the single handle's kernel
+template <int VARIANT, int MI, bool GAUSS = false, bool GROUP = false>
 __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
     constexpr int ROWS = 32 * MI;
     static_assert(VARIANT != CH_V_DTAIL || MI == 2, "the loss head works on 64-row blocks");
@@ -561,6 +571,7 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
     const int nrb = (a.rows + ROWS - 1) / ROWS;
     const int seg = blockIdx.x / nrb, rb = blockIdx.x - seg * nrb;
     const int row_blk = rb * ROWS, rows_valid = min(ROWS, a.rows - row_blk);
+    const long moff = chain_moff<GROUP>(a.model_stride);      // model groups (ChainArgs::models): bytes to this model's tensors
 
     Stamps st;
     st.start();
@@ -578,21 +589,21 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
         for (int mi = 0; mi < MI; ++mi) { mwA[p_][mi] = 0u; mwB[p_][mi] = 0u; mwC[p_][mi] = 0u; }
     if constexpr (VARIANT != CH_V_GBWD) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) { const float bv = a.fwd[i].bias[min(col0, a.fwd[i].n_valid - 1)]; bias[i] = col0 < a.fwd[i].n_valid ? bv : 0.f; }
+        for (int i = 0; i < 3; ++i) { const float bv = chain_model(a.fwd[i].bias, moff)[min(col0, a.fwd[i].n_valid - 1)]; bias[i] = col0 < a.fwd[i].n_valid ? bv : 0.f; }
     }
-    if constexpr (VARIANT == CH_V_DTAIL) load_mask_words<MI>(a, a.dx[2], mwC, seg, row_blk, wave, lc, lh);      // dX through D3 needs D2's mask
+    if constexpr (VARIANT == CH_V_DTAIL) load_mask_words<MI, GROUP>(a, a.dx[2], mwC, seg, row_blk, wave, lc, lh);      // dX through D3 needs D2's mask
     HeadInputs hin;
-    if constexpr (VARIANT == CH_V_DTAIL) head_prefetch(a, hin, seg, row_blk, rows_valid, t);
+    if constexpr (VARIANT == CH_V_DTAIL) head_prefetch<GROUP>(a, hin, seg, row_blk, rows_valid, t);
     if constexpr (VARIANT == CH_V_GBWD) {
-        load_mask_words<MI>(a, a.dx[0], mwA, seg, row_blk, wave, lc, lh);
-        load_mask_words<MI>(a, a.dx[1], mwB, seg, row_blk, wave, lc, lh);
-        load_mask_words<MI>(a, a.dx[2], mwC, seg, row_blk, wave, lc, lh);
+        load_mask_words<MI, GROUP>(a, a.dx[0], mwA, seg, row_blk, wave, lc, lh);
+        load_mask_words<MI, GROUP>(a, a.dx[1], mwB, seg, row_blk, wave, lc, lh);
+        load_mask_words<MI, GROUP>(a, a.dx[2], mwC, seg, row_blk, wave, lc, lh);
     }
 
     // ---- first A image ----
     constexpr int a0_off = chain_img(ROWS, 0);
     if constexpr (VARIANT != CH_V_GBWD) {
-        const __bf16* src = a.a + (long)seg * a.a_bs;
+        const __bf16* src = chain_model(a.a, moff) + (long)seg * a.a_bs;
         const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, (int)((long)a.rows * a.lda * 2), 0x00020000);
         const int lrow = lane >> 3, lp = lane & 7, nkt = a.a_cols / 64;
         // ROWS / 8 pieces of [8 rows][128 B] per k-tile, spread over the waves: rows >= a.rows arrive as zeros
@@ -610,7 +621,7 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
     {
         const ChainOp& first = VARIANT == CH_V_GBWD ? a.dx[0] : a.fwd[0];
         BTile b0;
-        btile_setup(b0, first.W, first.K, first.N, wave, lane);
+        btile_setup(b0, chain_model(first.W, moff), first.K, first.N, wave, lane);
 #pragma unroll
         for (int i = 0; i < AHEAD; ++i) issue_btile(b0, 0, i, lds + chain_ring(ROWS) + i * CH_STAGE_BYTES, wave);
     }
@@ -619,8 +630,8 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
         __builtin_amdgcn_s_barrier();      // ... everyone's: the k-loops below run without workgroup barriers
         asm volatile("" ::: "memory");
     } else {
-        chain_fmgrad<ROWS>(a, lds, rb, row_blk, rows_valid, t, st);      // (ends with a workgroup barrier)
-        sm.cp_img = lds + a0_off; sm.cp_out = (__bf16*)a.fm.dpre + (long)row_blk * a.fm.ldd;
+        chain_fmgrad<ROWS, GROUP>(a, lds, rb, row_blk, rows_valid, t, st);      // (ends with a workgroup barrier)
+        sm.cp_img = lds + a0_off; sm.cp_out = (__bf16*)chain_model_opt(a.fm.dpre, moff) + (long)row_blk * a.fm.ldd;
         sm.cp_ldo = a.fm.ldd; sm.cp_col0 = 0; sm.cp_ncols = a.fm.feat;
     }
     CH_STAMP(0);                   // prologue (epilogue inputs, first tile issue, A image)
@@ -633,9 +644,12 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
     // ... and the descriptor is copied as a whole (wide scalar loads, one wait) instead of field by field at the points of use
     // OPS[J]: the product (fwd or dx: its direction); NOPS[NEXT]: the product that follows (NEXT = -1: none) -- its first weight
     // tile is issued during this product's last k-tile
-#define CH_GEMM(OPS, J, NOPS, NEXT, BIAS, MW) do { const ChainOp op_ = a.OPS[opq(J)];                                                    \
+    // (model groups: the copy's pointers move to this model's tensors -- scalar adds on the descriptor, null stays null)
+#define CH_GEMM(OPS, J, NOPS, NEXT, BIAS, MW) do { ChainOp op_ = a.OPS[opq(J)];                                                          \
+        op_.W = chain_model(op_.W, moff); op_.out = chain_model_opt(op_.out, moff);                                                        \
+        op_.mask = chain_model_opt(op_.mask, moff); op_.cs = chain_model_opt(op_.cs, moff);                                                    \
         const int nx_ = opq(NEXT < 0 ? 0 : NEXT);                                                                                      \
-        chain_gemm<CH_GEMM_MODE_##OPS, J, MI, GAUSS>(a, op_, NEXT < 0 ? nullptr : a.NOPS[nx_].W, a.NOPS[nx_].K, a.NOPS[nx_].N, lds, sm, BIAS, MW,   \
+        chain_gemm<CH_GEMM_MODE_##OPS, J, MI, GAUSS, GROUP>(a, op_, NEXT < 0 ? nullptr : chain_model(a.NOPS[nx_].W, moff), a.NOPS[nx_].K, a.NOPS[nx_].N, lds, sm, BIAS, MW,   \
                          seg, nrb, rb, row_blk, rows_valid, iter, hfrag, t, st); } while (0)
     constexpr int CH_GEMM_MODE_fwd = CH_FWD_RELU, CH_GEMM_MODE_dx = CH_DX_RELU;
     if constexpr (VARIANT == CH_V_DTAIL) {
@@ -646,7 +660,7 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
         CH_GEMM(fwd, 2, dx, 0, bias[2], mw4);
         CH_STAMP(1);               // (the feature image is complete: chain_gemm ended with the image barrier; the weight tile in
                                    //  flight lands in the ring, which the head does not touch)
-        if constexpr (MI == 2) { if (!(a.ablate & CH_ABL_HEAD)) chain_head(a, lds, sm, hin, mw4, seg, rb, nrb, row_blk, rows_valid, t); }
+        if constexpr (MI == 2) { if (!(a.ablate & CH_ABL_HEAD)) chain_head<GROUP>(a, lds, sm, hin, mw4, seg, rb, nrb, row_blk, rows_valid, t); }
         CH_STAMP(2);               // loss head
         CH_GEMM(dx, 0, dx, 1, 0.f, mwA);       // dX through D5 * relu'(D4)
         CH_GEMM(dx, 1, dx, 2, 0.f, mwB);       // dX through D4 * relu'(D3)
@@ -669,12 +683,13 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(const ChainArgs a) {
 }  // namespace
 
 // every instantiation of chain_kernel: launch_chain picks its kernel here, chain_init_attributes raises the LDS limit of each
-struct ChainKernel { int variant, block_rows, gauss; void (*kernel)(const ChainArgs); };
+struct ChainKernel { int variant, block_rows, gauss, group; void (*kernel)(const ChainArgs); };
+#define CH_K(V, MI, G) {V, 32 * MI, G, 0, chain_kernel<V, MI, G != 0, false>}, {V, 32 * MI, G, 1, chain_kernel<V, MI, G != 0, true>}
 static const ChainKernel chain_kernels[] = {
-    {CH_V_DTAIL, 64, 0, chain_kernel<CH_V_DTAIL, 2>},      {CH_V_GFWD, 64, 0, chain_kernel<CH_V_GFWD, 2>},       {CH_V_GBWD, 64, 0, chain_kernel<CH_V_GBWD, 2>},
-    {CH_V_GFWD, 32, 0, chain_kernel<CH_V_GFWD, 1>},        {CH_V_GBWD, 32, 0, chain_kernel<CH_V_GBWD, 1>},
-    {CH_V_DTAIL, 64, 1, chain_kernel<CH_V_DTAIL, 2, true>}, {CH_V_GFWD, 64, 1, chain_kernel<CH_V_GFWD, 2, true>}, {CH_V_GFWD, 32, 1, chain_kernel<CH_V_GFWD, 1, true>},
+    CH_K(CH_V_DTAIL, 2, 0), CH_K(CH_V_GFWD, 2, 0), CH_K(CH_V_GBWD, 2, 0), CH_K(CH_V_GFWD, 1, 0), CH_K(CH_V_GBWD, 1, 0),
+    CH_K(CH_V_DTAIL, 2, 1), CH_K(CH_V_GFWD, 2, 1), CH_K(CH_V_GFWD, 1, 1),
 };
+#undef CH_K
 
 int chain_init_attributes() {
     for (const ChainKernel& k : chain_kernels)
@@ -692,10 +707,10 @@ static bool chain_op_ok(const ChainOp& op, bool fwd) {
 int launch_chain(const ChainArgs& a, hipStream_t s) {
     const bool has_fwd = a.variant != CH_V_GBWD, has_dx = a.variant != CH_V_GFWD;
     // (the 32-row blocks have no D-tail kernel; the dX products draw no noise, so CH_V_GBWD has one kernel for both generators)
-    const int gauss = has_fwd && a.gauss;
+    const int gauss = has_fwd && a.gauss, group = a.models > 1;
     const ChainKernel* k = nullptr;
     for (const ChainKernel& c : chain_kernels)
-        if (c.variant == a.variant && c.block_rows == a.block_rows && c.gauss == gauss) k = &c;
+        if (c.variant == a.variant && c.block_rows == a.block_rows && c.gauss == gauss && c.group == group) k = &c;
     if (!k) return -3;
     // the head inside the D-tail chain is an 8-class kernel (its scratch is half of image 0)
     if (a.variant == CH_V_DTAIL && (a.head.classes > KMAX || a.head.ldw != KMAX)) return -3;
@@ -703,7 +718,7 @@ int launch_chain(const ChainArgs& a, hipStream_t s) {
         if ((has_fwd && !chain_op_ok(a.fwd[i], true)) || (has_dx && !chain_op_ok(a.dx[i], false))) return -3;
     if (has_fwd && ((a.a_cols % 64) || a.a_cols > CH_KMAX || a.a_cols != a.fwd[0].K || (long)a.rows * a.lda * 2 >= (1L << 31))) return -3;
     const int nrb = (a.rows + a.block_rows - 1) / a.block_rows;
-    MRGAN_LAUNCH(k->kernel, dim3(nrb * a.nseg), dim3(CH_THREADS), chain_lds_bytes(a.block_rows), s, a);
+    MRGAN_LAUNCH(k->kernel, dim3(nrb * a.nseg, std::max(1, a.models)), dim3(CH_THREADS), chain_lds_bytes(a.block_rows), s, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -168,8 +168,10 @@ __device__ __forceinline__ void head_rows_to_lds(const float (&dl)[KP], float lo
 }
 // ... and the 3 + KP sums (behind a barrier): loss terms -> loss_part[blk], db6 -> the block's partial-gradient row
 template <int KP = KMAX>
-__device__ __forceinline__ void head_block_sums(const float* red, const HeadArgs& h, int blk, float* part_row, int wave, int lane) {
+__device__ __forceinline__ void head_block_sums(const float* red, const HeadArgs& h, int blk, float* part_row, int wave, int lane,
+                                                long moff = 0 /* model groups: bytes to this model's loss_part */) {
     if (wave == CH_THREADS / 64 - 1 && lane < 3 + KP) {
+        float* const loss_part = (float*)((char*)h.loss_part + moff);
         float s4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < CH_ROWS / 4; ++i) {
@@ -177,9 +179,9 @@ __device__ __forceinline__ void head_block_sums(const float* red, const HeadArgs
             s4[i & 3] += (v[0] + v[1]) + (v[2] + v[3]);
         }
         const float tot = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-        if (lane < 3) h.loss_part[blk * 4 + lane] = tot;
+        if (lane < 3) loss_part[blk * 4 + lane] = tot;
         else part_row[h.off_db + lane - 3] = tot;
-        if (lane == 0) h.loss_part[blk * 4 + 3] = 0.f;
+        if (lane == 0) loss_part[blk * 4 + 3] = 0.f;
     }
 }
 

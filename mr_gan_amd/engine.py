@@ -33,6 +33,7 @@ EXPORTS = [
     "mrgan_debug_stage", "mrgan_debug_reduce_partials","mrgan_debug_colsum_finalize", "mrgan_debug_bn_apply", "mrgan_debug_bn_bwd", "mrgan_debug_head", "mrgan_debug_head_wide",
     "mrgan_debug_fm", "mrgan_debug_adam",
     "mrgan_select_model", "mrgan_sup_step_group",
+    "mrgan_disc_step_group", "mrgan_gen_step_group", "mrgan_train_pair_group",
 ]
 MAX_MODELS = 16
 PROF_NAME_LEN = 96
@@ -83,6 +84,28 @@ class SupGroupArgs(C.Structure):
         ("ld_x", C.c_int64),
         ("x_model_stride", C.c_int64), ("idx_model_stride", C.c_int64), ("labels_model_stride", C.c_int64),
         ("stream_mode", C.c_int32), ("rows_valid", C.c_int32),
+    ]
+
+
+class DiscGroupArgs(C.Structure):
+    """mrgan_disc_group_args: mrgan_disc_args + element strides between models"""
+    _fields_ = [
+        ("x_lab", C.c_void_p), ("idx_lab", C.c_void_p), ("labels", C.c_void_p),
+        ("x_unl", C.c_void_p), ("idx_unl", C.c_void_p), ("z", C.c_void_p),
+        ("ld_x_lab", C.c_int64), ("ld_x_unl", C.c_int64),
+        ("x_lab_model_stride", C.c_int64), ("idx_lab_model_stride", C.c_int64), ("labels_model_stride", C.c_int64),
+        ("x_unl_model_stride", C.c_int64), ("idx_unl_model_stride", C.c_int64), ("z_model_stride", C.c_int64),
+        ("stream_mode", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class GenGroupArgs(C.Structure):
+    """mrgan_gen_group_args: mrgan_gen_args + element strides between models"""
+    _fields_ = [
+        ("x_unl", C.c_void_p), ("idx_unl", C.c_void_p), ("z", C.c_void_p),
+        ("ld_x_unl", C.c_int64),
+        ("x_unl_model_stride", C.c_int64), ("idx_unl_model_stride", C.c_int64), ("z_model_stride", C.c_int64),
+        ("stream_mode", C.c_int32), ("reserved", C.c_int32),
     ]
 
 
@@ -326,6 +349,52 @@ class Engine(object):
         out = (C.c_float * (2 * MAX_MODELS))()
         _check(self.lib.mrgan_sup_step_group(self.handle, C.byref(args), out if want_outputs else None, _stream()))
         return [(out[2 * m], out[2 * m + 1]) for m in range(self.models)] if want_outputs else None
+
+    # the GAN sub-steps of a group handle: stacked [models, ...] tensors, strides derived as in sup_group_args
+    @staticmethod
+    def _model_stride(t, stacked_dim):
+        return t.stride(0) if t is not None and t.dim() == stacked_dim else 0
+
+    @staticmethod
+    def disc_group_args(x_lab, labels, x_unl, z=None, idx_lab=None, idx_unl=None, stream_mode=0):
+        """x_lab / x_unl [models, rows, D] (or [rows, D]: one matrix every model gathers from through its idx_* [models, n]);
+        labels [models, n]; z [models, n, noise] or None (model m draws z on the device with seed + m)"""
+        a = DiscGroupArgs()
+        a.x_lab, a.idx_lab, a.labels = _ptr(x_lab), _ptr(idx_lab), _ptr(labels)
+        a.x_unl, a.idx_unl, a.z = _ptr(x_unl), _ptr(idx_unl), _ptr(z)
+        a.ld_x_lab, a.ld_x_unl = x_lab.stride(-2), x_unl.stride(-2)
+        ms = Engine._model_stride
+        a.x_lab_model_stride, a.idx_lab_model_stride, a.labels_model_stride = ms(x_lab, 3), ms(idx_lab, 2), ms(labels, 2)
+        a.x_unl_model_stride, a.idx_unl_model_stride, a.z_model_stride = ms(x_unl, 3), ms(idx_unl, 2), ms(z, 3)
+        a.stream_mode = stream_mode
+        a._refs = (x_lab, labels, x_unl, z, idx_lab, idx_unl)
+        return a
+
+    @staticmethod
+    def gen_group_args(x_unl, z=None, idx_unl=None, stream_mode=0):
+        a = GenGroupArgs()
+        a.x_unl, a.idx_unl, a.z = _ptr(x_unl), _ptr(idx_unl), _ptr(z)
+        a.ld_x_unl = x_unl.stride(-2)
+        ms = Engine._model_stride
+        a.x_unl_model_stride, a.idx_unl_model_stride, a.z_model_stride = ms(x_unl, 3), ms(idx_unl, 2), ms(z, 3)
+        a.stream_mode = stream_mode
+        a._refs = (x_unl, z, idx_unl)
+        return a
+
+    def disc_step_group(self, args, want_outputs=True):
+        """disc_step once per model of a group handle, as one launch set -> [(loss_lab, loss_unl, train_err)] per model"""
+        out = (C.c_float * (3 * MAX_MODELS))()
+        _check(self.lib.mrgan_disc_step_group(self.handle, C.byref(args), out if want_outputs else None, _stream()))
+        return [tuple(out[3 * m:3 * m + 3]) for m in range(self.models)] if want_outputs else None
+
+    def gen_step_group(self, args, want_outputs=True):
+        """gen_step once per model of a group handle, as one launch set -> [loss_gen] per model"""
+        out = (C.c_float * MAX_MODELS)()
+        _check(self.lib.mrgan_gen_step_group(self.handle, C.byref(args), out if want_outputs else None, _stream()))
+        return [out[m] for m in range(self.models)] if want_outputs else None
+
+    def train_pair_group(self, dargs, gargs):
+        _check(self.lib.mrgan_train_pair_group(self.handle, C.byref(dargs), C.byref(gargs), _stream()))
 
     FP8_DRY_PASSES = 5
     FP8_CAL_QUERY, FP8_CAL_BEGIN, FP8_CAL_END_PASS, FP8_CAL_DONE = 0, 1, 2, 3

@@ -14,6 +14,10 @@ from mr_gan_amd import engine as E
 from mr_gan_amd.data import tiled_permutation
 
 
+# the per-epoch line of mr_gan.py:227
+EPOCH_LINE = 'Epoch %d, time = %ds, loss labeled = %.4f, loss unlabeled = %.4f, train error = %.4f, test error = %.4f'
+
+
 def glorot_uniform(rng, fan_in, fan_out):
     lim = np.sqrt(6.0 / (fan_in + fan_out))
     return rng.uniform(-lim, lim, size=(fan_in, fan_out)).astype(np.float32)
@@ -189,10 +193,132 @@ class MRGAN(object):
             self.history.append(rec)
             if verbose:
                 # mr_gan.py:227
-                print('Epoch %d, time = %ds, loss labeled = %.4f, loss unlabeled = %.4f, train error = %.4f, test error = %.4f'
-                      % (epoch, rec['time'], loss_lab, loss_unl, train_err, test_err))
+                print(EPOCH_LINE % (epoch, rec['time'], loss_lab, loss_unl, train_err, test_err))
                 sys.stdout.flush()
         return self.history
 
     def predict(self, X):
         return np.argmax(self.predict_logits(X), axis=1)
+
+
+class MRGANGroup(object):
+    """`models` MRGAN trainings of one shape on one group handle (mrgan_config.models): model m is MRGAN(seed=seed + m) -- the
+    same glorot streams for G and D, engine seed seed + m -- and every (D, G) pair of all models is one train_pair_group (one
+    launch set per sub-step).  The results are those of the `models` single MRGAN runs bit for bit."""
+
+    def __init__(self, input_dim, models, batch_size=50, dtype='float32', seed=None, device='cuda:0', num_classes=6,
+                 noise_size=100, g_hidden=(500, 500), d_hidden=(1000, 500, 250, 250, 250), lr=0.0006, beta_1=0.5,
+                 unlabeled_weight=1.0, use_graph=True, flags=0, init_weights=True, noise='irwin-hall'):
+        self.input_dim, self.batch_size, self.models = int(input_dim), int(batch_size), int(models)
+        if not 2 <= self.models <= E.MAX_MODELS:
+            raise ValueError("a model group has 2 .. %d models, got %d (one model: MRGAN)" % (E.MAX_MODELS, self.models))
+        if dtype in ('fp8', 'float8'):
+            raise ValueError("a model group cannot be an fp8 handle")
+        self.seed = int(np.random.randint(1 << 31)) if seed is None else int(seed)
+        cfg = E.default_config(self.input_dim, self.batch_size)
+        cfg.dtype = {'float32': E.F32, 'fp32': E.F32, 'bfloat16': E.BF16, 'bf16': E.BF16}[dtype]
+        cfg.num_classes, cfg.noise_size = num_classes, noise_size
+        cfg.g_hidden[0], cfg.g_hidden[1] = g_hidden
+        for i, w in enumerate(d_hidden):
+            cfg.d_hidden[i] = w
+        cfg.lr, cfg.beta1, cfg.unlabeled_weight = lr, beta_1, unlabeled_weight
+        cfg.seed = self.seed                                       # model m draws what a handle with seed + m draws
+        cfg.models = self.models
+        cfg.flags = flags | (E.FLAG_GRAPH if use_graph else 0) | E.noise_flags(noise)
+        self.cfg = cfg
+        self.engine = E.Engine(cfg, device)
+        self.device = self.engine.device
+        self.stream = torch.cuda.Stream(self.device)               # (graph capture is not permitted on the legacy default stream)
+        self.iterations = 0
+        self.history = []
+        if init_weights:
+            for m in range(self.models):
+                self.engine.select_model(m)
+                MRGAN.initialize(self, self.seed + m)
+            self.engine.select_model(0)
+
+    _dev = MRGAN._dev
+    _on_stream = MRGAN._on_stream
+
+    def fit(self, x_labeled, y_labeled, x_unlabeled, epochs=100, verbose=0, validation_data=None, x_unlabeled_pools=None, rngs=None):
+        """MRGAN.fit (z drawn on the device) of every model at once.  x_labeled / y_labeled / x_unlabeled: `models` arrays each,
+        of equal length across the models; validation_data: `models` (X, y) pairs, or None; x_unlabeled_pools: `models` table-6
+        pools of equal length, or None.  Model m's permutation streams come from rngs[m] (default: MRGAN.fit's default for
+        seed + m).  The matrices stay resident as [models][n][D]; one train_pair_group per batch, metrics per model once per epoch."""
+        with self._on_stream():
+            return self._fit(x_labeled, y_labeled, x_unlabeled, epochs, verbose, validation_data, x_unlabeled_pools, rngs)
+
+    def _fit(self, x_labeled, y_labeled, x_unlabeled, epochs, verbose, validation_data, pools, rngs):
+        G, B = self.models, self.batch_size
+        groups = [x_labeled, y_labeled, x_unlabeled] + ([pools] if pools is not None else [])
+        if any(len(g) != G for g in groups) or any(len({len(a) for a in g}) != 1 for g in groups) or len(x_labeled[0]) != len(y_labeled[0]):
+            raise ValueError("fit: a group trains %d sets of equal length" % G)
+        if validation_data is not None and len(validation_data) != G:
+            raise ValueError("fit: validation_data is one (X, y) pair per model")
+        rngs = rngs or [np.random.RandomState((self.seed + m) ^ 0x5bd1e995) for m in range(G)]
+        xl = torch.stack([self._dev(x) for x in x_labeled])
+        xu = torch.stack([self._dev(x) for x in x_unlabeled])
+        yl = [np.asarray(y).astype(np.int32) for y in y_labeled]
+        pool = torch.stack([self._dev(p) for p in pools]) if pools is not None else None
+        n_train, n_lab = xu.shape[1], xl.shape[1]
+        nb = n_train // B                                          # mr_gan.py:173 (remainder rows dropped)
+        if nb < 1:
+            raise ValueError("fewer training rows (%d) than one batch (%d)" % (n_train, B))
+        val = None
+        if validation_data is not None:
+            val = [(self._dev(v[0]), self._dev(v[1], torch.int32)) for v in validation_data]
+        unl_src = xu if pool is None else pool
+        for epoch in range(1, epochs + 1):
+            begin = time.time()
+            inds, unl = [], []
+            for m in range(G):                                     # model m: the draws of MRGAN._fit, in its order, from rngs[m]
+                inds.append(tiled_permutation(rngs[m], n_lab, n_train))
+                if pool is None:
+                    unl.append([rngs[m].permutation(n_train).astype(np.int32) for _ in range(3)])
+                else:
+                    unl.append([tiled_permutation(rngs[m], pool.shape[1], n_train) for _ in range(3)])
+            idx_lab = self._dev(np.stack(inds), torch.int32)
+            lab_stream = self._dev(np.stack([yl[m][inds[m]] for m in range(G)]), torch.int32)
+            idx_unl = self._dev(np.stack([u[0] for u in unl]), torch.int32)
+            idx_unl2 = self._dev(np.stack([u[1] for u in unl]), torch.int32)
+            dargs = E.Engine.disc_group_args(xl, lab_stream, unl_src, None, idx_lab, idx_unl, stream_mode=1)
+            gargs = E.Engine.gen_group_args(unl_src, None, idx_unl2, stream_mode=1)
+            self.engine.set_iterations(self.iterations, 0)
+            for _ in range(nb):                                    # mr_gan.py:204-213
+                self.engine.train_pair_group(dargs, gargs)
+            self.iterations += 2 * nb
+            rec = dict(epoch=epoch, loss_lab=[], loss_unl=[], train_err=[], loss_gen=[], test_err=[])
+            for m in range(G):                                     # metrics and evaluation: model by model
+                self.engine.select_model(m)
+                met = self.engine.read_metrics(reset=True)
+                for k, v in zip(('loss_lab', 'loss_unl', 'train_err', 'loss_gen'), met[:4]):
+                    rec[k].append(v / nb)
+                test_err = float('nan')
+                if val is not None:
+                    nte = (val[m][0].shape[0] // B) * B            # mr_gan.py:221-223: mean over whole test batches
+                    if nte > 0:
+                        test_err = self.engine.eval_error(val[m][0][:nte], val[m][1][:nte])
+                rec['test_err'].append(test_err)
+            self.engine.select_model(0)
+            rec['time'] = time.time() - begin
+            self.history.append(rec)
+            if verbose:
+                for m in range(G):                                 # mr_gan.py:227, once per model
+                    print(('Model %d: ' % m) + EPOCH_LINE % (epoch, rec['time'], rec['loss_lab'][m], rec['loss_unl'][m], rec['train_err'][m],
+                                                             rec['test_err'][m]))
+                sys.stdout.flush()
+        return self.history
+
+    def predict_logits(self, m, X):
+        with self._on_stream():
+            self.engine.select_model(m)
+            return self.engine.predict_logits(self._dev(X)).cpu().numpy()
+
+    def evaluate(self, Xs, ys):
+        """[test error of model m over (Xs[m], ys[m])], model by model"""
+        errs = []
+        with self._on_stream():
+            for m in range(self.models):
+                self.engine.select_model(m)
+                errs.append(self.engine.eval_error(self._dev(Xs[m]), self._dev(ys[m], torch.int32)))
+        return errs

@@ -6,6 +6,7 @@
         same signature as mr_gan.py:23
     python -m mr_gan_amd.mr_gan --tables 1 3 5 6 [-v]        (mr_gan.py:236-341)
     python -m mr_gan_amd.mr_gan --tables 1 3 5 6 --gpus 8 --jobs-per-gpu 2     run-level scheduling of the tables (scheduler.py)
+    python -m mr_gan_amd.mr_gan --tables 1 5 6 --group-folds   the six folds of every cell as one model group (mr_gan_folds)
 
 Extra keyword arguments (batch_size, dtype, seed, device, noise) default to the reference's literals; noise='gaussian'
 (--noise gaussian) draws the layer noise and z as true normals instead of the engine's default Irwin-Hall variates.
@@ -69,6 +70,60 @@ def mr_gan(X, y, percentlabeled=50, percentunlabeled=None, epochs=100, trainTest
         sys.stdout.flush()
     model.engine.close()
     return testerror
+
+
+class UnequalFolds(ValueError):
+    """the folds of a cell cannot train as one group: their training, labelled or unlabelled sets differ in length"""
+
+
+def mr_gan_folds(sets, percentlabeled=50, percentunlabeled=None, epochs=100, verbose=False, batch_size=50, dtype='float32',
+                 seed=None, device='cuda:0', noise='irwin-hall', num_classes=None):
+    """mr_gan() of every [X_train, X_test, y_train, y_test] of `sets` (the folds of one cell: equal shapes) as one model group
+    -> their test errors.  Fold f runs mr_gan()'s prologue and its index streams from RandomState(seed + f); its model is
+    MRGAN(seed=s + f) with s drawn from RandomState(seed).  Raises UnequalFolds where the sets differ in length.
+    verbose: the folds train together, so mr_gan()'s lines are printed after the training, fold by fold and in mr_gan()'s order
+    (prologue, sizes, one line per epoch from the recorded history, test error): the lines of six verbose mr_gan() calls."""
+    from sklearn.utils import shuffle
+
+    from mr_gan_amd.engine import noise_flags
+    from mr_gan_amd.model import EPOCH_LINE, MRGANGroup
+    noise_flags(noise)
+    base = int(seed if seed is not None else np.random.randint(1 << 30))
+    num_classes = resolve_num_classes(num_classes)
+    num_labeled_examples = int(10 * percentlabeled)
+    num_unlabeled_examples = int(10 * percentunlabeled) if percentunlabeled is not None else None
+    rss = [np.random.RandomState(base + f) for f in range(len(sets))]
+    folds, lines = [], []                                          # lines[f]: what a verbose mr_gan() of fold f prints, as print() arguments
+    for (X_train, X_test, y_train, y_test), rs in zip(sets, rss):  # mr_gan()'s prologue, fold by fold
+        out = [('Num of class examples in test set:', [int(np.sum(y_test == i)) for i in range(num_classes)]),
+               ('X_train:', np.shape(X_train), 'y_train:', np.shape(y_train), 'X_test:', np.shape(X_test), 'y_test:', np.shape(y_test))]
+        X_train, X_test = standard_scale(X_train, X_test)
+        X_train, y_train = shuffle(X_train, y_train, random_state=rs)
+        x_labeled, y_labeled, x_unlabeled = select_labeled(X_train, y_train, num_labeled_examples, num_unlabeled_examples, num_classes=num_classes)
+        out.append(('x_labeled:', np.shape(x_labeled), 'y_labeled:', np.shape(y_labeled)))
+        out += [('Epochs:', epochs), ('Batch size:', batch_size), ('Training batches per epoch:', X_train.shape[0] // batch_size),
+                ('Testing batches per epoch:', X_test.shape[0] // batch_size)]
+        lines.append(out)
+        folds.append((x_labeled, y_labeled, X_train, x_unlabeled, X_test, y_test))
+    pooled = [f[3] is not None for f in folds]
+    if (len({len(f[0]) for f in folds}) != 1 or len({len(f[2]) for f in folds}) != 1 or len(set(pooled)) != 1 or
+            (pooled[0] and len({len(f[3]) for f in folds}) != 1)):
+        raise UnequalFolds("mr_gan_folds: the folds' training, labelled or unlabelled sets differ in length")
+    model = MRGANGroup(folds[0][2].shape[1], len(sets), batch_size=batch_size, dtype=dtype,
+                       seed=int(np.random.RandomState(base).randint(1 << 30)), device=device, noise=noise, num_classes=num_classes)
+    hist = model.fit([f[0] for f in folds], [f[1] for f in folds], [f[2] for f in folds], epochs=epochs, verbose=0,
+                     validation_data=[(f[4], f[5]) for f in folds], x_unlabeled_pools=[f[3] for f in folds] if pooled[0] else None, rngs=rss)
+    errors = model.evaluate([f[4] for f in folds], [f[5] for f in folds])          # mr_gan.py:230 -- whole test sets
+    if verbose:
+        for f, out in enumerate(lines):
+            for args in out:
+                print(*args)
+            for rec in hist:
+                print(EPOCH_LINE % (rec['epoch'], rec['time'], rec['loss_lab'][f], rec['loss_unl'][f], rec['train_err'][f], rec['test_err'][f]))
+            print('Test error:', errors[f], hist[-1]['test_err'][f] if hist else float('nan'))
+        sys.stdout.flush()
+    model.engine.close()
+    return errors
 
 
 def _logmel_all(contacts, sr=48000, n_mels=128):
@@ -151,6 +206,38 @@ class InProcessRuns(object):
             X, y = self.datasets[job['dataset']]
             tr, te = job['train_idx'], job['test_idx']
             out.append(self.fn(None, None, trainTestSets=[X[tr], X[te], y[tr], y[te]], **kw))
+        return out
+
+
+class GroupedRuns(InProcessRuns):
+    """--group-folds: InProcessRuns whose run() trains every run of consecutive jobs that differ in their row indices only -- the
+    six folds of a cell -- as ONE model group (folds_fn = mr_gan_folds), in the jobs' order.  A cell whose folds differ in the
+    length of their training, labelled or unlabelled sets (UnequalFolds), and a run of one job, take the ungrouped path."""
+
+    def __init__(self, mr_gan_fn, folds_fn, max_models=16):
+        InProcessRuns.__init__(self, mr_gan_fn)
+        self.folds_fn, self.max_models = folds_fn, max_models
+
+    @staticmethod
+    def _cell(job):
+        return sorted((k, repr(v)) for k, v in job.items() if k not in ('train_idx', 'test_idx'))
+
+    def run(self, jobs):
+        out, i = [], 0
+        while i < len(jobs):
+            j = i + 1
+            while j < len(jobs) and j - i < self.max_models and self._cell(jobs[j]) == self._cell(jobs[i]):
+                j += 1
+            cell, errors = jobs[i:j], None
+            if len(cell) > 1 and len({len(job['train_idx']) for job in cell}) == 1:
+                X, y = self.datasets[cell[0]['dataset']]
+                kw = {k: v for k, v in cell[0].items() if k not in ('dataset', 'train_idx', 'test_idx')}
+                try:
+                    errors = list(self.folds_fn([[X[job['train_idx']], X[job['test_idx']], y[job['train_idx']], y[job['test_idx']]] for job in cell], **kw))
+                except UnequalFolds:
+                    errors = None
+            out += errors if errors is not None else InProcessRuns.run(self, cell)
+            i = j
         return out
 
 
@@ -255,7 +342,7 @@ def _table6_scheduled(sched, dataset_fn, kw):
                 _print_kfold(errors[6 * i:6 * i + 6])
 
 
-def main(argv=None, dataset_fn=dataset, mr_gan_fn=mr_gan, scheduler_factory=None):
+def main(argv=None, dataset_fn=dataset, mr_gan_fn=mr_gan, scheduler_factory=None, folds_fn=None):
     parser = argparse.ArgumentParser(description='Semi-supervised learning with GANs for material recognition on haptic data.')
     parser.add_argument('-t', '--tables', nargs='+', help='[Required] Tables to recompute', required=True)
     parser.add_argument('-v', '--verbose', help='Verbose', action='store_true')
@@ -266,7 +353,12 @@ def main(argv=None, dataset_fn=dataset, mr_gan_fn=mr_gan, scheduler_factory=None
     parser.add_argument('--gpus', type=int, default=0,
                         help='run-level scheduling: dispatch the independent trainings of tables 1 / 3 / 5 / 6 over this many GPUs (0 = in-process, sequential)')
     parser.add_argument('--jobs-per-gpu', type=int, default=1, help='concurrent trainings per GPU with --gpus')
+    parser.add_argument('--group-folds', action='store_true',
+                        help='tables 1, 5 and 6, in-process mode: train the six folds of each cell as one model group (one launch set)')
     args = parser.parse_args(argv)
+    if args.group_folds and args.gpus > 0:
+        parser.error('--group-folds trains the folds of a cell as one model group in this process; scheduling groups over GPUs '
+                     '(--gpus > 0) is not part of it')
     kw = dict(epochs=args.epochs, dtype=args.dtype)
     if args.noise != 'irwin-hall':                                 # travels in every job dict (scheduler.train_job -> mr_gan())
         kw['noise'] = args.noise
@@ -274,13 +366,13 @@ def main(argv=None, dataset_fn=dataset, mr_gan_fn=mr_gan, scheduler_factory=None
         from mr_gan_amd.scheduler import RunScheduler
         runs = (scheduler_factory or RunScheduler)(gpus=args.gpus, jobs_per_gpu=args.jobs_per_gpu)
     else:                                                          # the reference's behaviour: one after the other, here
-        runs = InProcessRuns(mr_gan_fn)
+        runs = GroupedRuns(mr_gan_fn, folds_fn or mr_gan_folds) if args.group_folds else InProcessRuns(mr_gan_fn)
         kw['verbose'] = args.verbose
     with runs as sched:
         if '1' in args.tables:                                     # mr_gan.py:244-261
             _table1_scheduled(sched, dataset_fn, kw)
-        if '3' in args.tables:                                     # mr_gan.py:263-283
-            _table3_scheduled(sched, dataset_fn, kw)
+        if '3' in args.tables:                                     # mr_gan.py:263-283 (leave-one-object-out: never grouped)
+            _table3_scheduled(InProcessRuns(mr_gan_fn) if args.group_folds else sched, dataset_fn, kw)
         if '5' in args.tables:                                     # mr_gan.py:285-318
             _table5_scheduled(sched, dataset_fn, kw)
         if '6' in args.tables:                                     # mr_gan.py:320-341

@@ -9,6 +9,12 @@ around work that ends in a device synchronise, each under a time limit of its ow
 of a side, in ms per step of ALL G models (the sequential side: G single steps).  With --profile-g G a second, separate pass
 takes the per-kernel profile (mrgan_profile_begin / _end) of one grouped and one single step at that G.
 
+    python scripts/group_bench.py --gan [--out profiles/group_gan_bench.json] [--groups 2 4 6 8 16] [--profile-g 6]
+
+--gan: the same method applied to the GAN hot loop at the reference's size (D = 1200, batch 50, N = 6000 rows resident, stream
+mode, graph replay): one group handle stepped through train_pair_group against G single handles stepped one after the other
+through train_pair; a step is one (D, G) pair of ALL G models.
+
 Every (dtype, G) runs in a child process of its own under a time limit; the first failure ends the run."""
 import argparse
 import json
@@ -116,25 +122,128 @@ def worker(dtype, G, blocks, steps, profile):
     print("RESULT " + json.dumps(res))
 
 
+GAN_B, GAN_N = 50, 6000      # mr_gan.py's batch; a fold's training rows
+
+
+def gan_worker(dtype, G, blocks, steps, profile):
+    import numpy as np
+    import torch
+    from mr_gan_amd import engine as E
+    from mr_gan_amd.model import MRGAN
+    dev = "cuda:0"
+    rng = np.random.RandomState(1)
+    if steps > GAN_N // GAN_B:
+        raise SystemExit("--steps: a block is at most one epoch of the index streams (%d batches)" % (GAN_N // GAN_B))
+
+    class Shell(object):          # (MRGAN.initialize: Keras' default initialisation from a seed, through the selected model)
+        pass
+
+    def make(models, seed):
+        cfg = E.default_config(D, GAN_B)
+        cfg.dtype = E.BF16 if dtype == 'bf16' else E.F32
+        cfg.seed, cfg.models, cfg.flags = seed, models, E.FLAG_GRAPH
+        sh = Shell()
+        sh.engine = E.Engine(cfg, dev)
+        for m in range(max(1, models)):
+            if models > 1:
+                sh.engine.select_model(m)
+            MRGAN.initialize(sh, seed + m)
+        return sh.engine
+
+    stream = torch.cuda.Stream(dev)      # (graph capture is not permitted on the legacy default stream)
+    with torch.cuda.stream(stream):
+        t = lambda a, dt=torch.float32: torch.from_numpy(np.ascontiguousarray(a)).to(dev, dt)
+        X = t(rng.standard_normal((GAN_N, D)).astype(np.float32))
+        XL = t(rng.standard_normal((600, D)).astype(np.float32))
+        idx_lab = rng.randint(0, 600, (G, GAN_N)).astype(np.int32)
+        lab = t(rng.randint(0, 6, 600).astype(np.int32)[idx_lab], torch.int32)
+        idx_lab = t(idx_lab, torch.int32)
+        idx_u1 = t(np.stack([rng.permutation(GAN_N) for _ in range(G)]), torch.int32)
+        idx_u2 = t(np.stack([rng.permutation(GAN_N) for _ in range(G)]), torch.int32)
+        singles = [make(0, 100 + m) for m in range(G)]
+        sargs = [(E.Engine.disc_args(XL, lab[m], X, None, idx_lab[m], idx_u1[m], stream_mode=1),
+                  E.Engine.gen_args(X, None, idx_u2[m], stream_mode=1)) for m in range(G)]
+        group = make(G, 100)
+        gd = E.Engine.disc_group_args(XL, lab, X, None, idx_lab, idx_u1, stream_mode=1)
+        gg = E.Engine.gen_group_args(X, None, idx_u2, stream_mode=1)
+
+        def seq_block(n):
+            for eng in singles:
+                eng.set_iterations(0, 0)          # (rewinds the batch counter of the index streams)
+            for _ in range(n):
+                for eng, (da, ga) in zip(singles, sargs):
+                    eng.train_pair(da, ga)
+
+        def grp_block(n):
+            group.set_iterations(0, 0)
+            for _ in range(n):
+                group.train_pair_group(gd, gg)
+
+        signal.signal(signal.SIGALRM, _alarm)
+
+        def timed(fn):
+            signal.alarm(BLOCK_LIMIT_S)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(steps)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            signal.alarm(0)
+            return (t1 - t0) * 1e3 / steps
+
+        for fn in (seq_block, grp_block):           # warm up both sides: code objects, graph capture, caches, clocks
+            fn(30)
+        torch.cuda.synchronize()
+        seq, grp = [], []
+        for _ in range(blocks):
+            seq.append(timed(seq_block))
+            grp.append(timed(grp_block))
+        res = dict(dtype=dtype, G=G, steps_per_block=steps, blocks=blocks, seq_ms=seq, grp_ms=grp,
+                   seq_median_ms=float(np.median(seq)), grp_median_ms=float(np.median(grp)))
+        res['speedup'] = res['seq_median_ms'] / res['grp_median_ms']
+        res['spread_pct'] = dict(seq=100.0 * (max(seq) - min(seq)) / res['seq_median_ms'], grp=100.0 * (max(grp) - min(grp)) / res['grp_median_ms'])
+        if profile:
+            def prof(eng, step):
+                eng.set_iterations(0, 0)
+                step()
+                torch.cuda.synchronize()
+                eng.profile_begin()
+                for _ in range(10):
+                    step()
+                return {k: dict(us=1e2 * v[0], launches=v[1] // 10) for k, v in eng.profile_end().items()}
+            res['profile_group_us_per_pair'] = prof(group, lambda: group.train_pair_group(gd, gg))
+            res['profile_single_us_per_pair'] = prof(singles[0], lambda: singles[0].train_pair(*sargs[0]))
+        for e in singles + [group]:
+            e.close()
+    print("RESULT " + json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'group_sup_bench.json'))
-    ap.add_argument('--groups', type=int, nargs='+', default=[1, 2, 4, 6, 8, 16])
+    ap.add_argument('--gan', action='store_true', help='the GAN hot loop (train_pair_group against G x train_pair) instead of the supervised step')
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--groups', type=int, nargs='+', default=None)
     ap.add_argument('--dtypes', nargs='+', default=['float32', 'bf16'])
     ap.add_argument('--blocks', type=int, default=9)
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--profile-g', type=int, nargs='*', default=[])
     ap.add_argument('--worker', nargs=2, metavar=('DTYPE', 'G'))
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'group_gan_bench.json' if args.gan else 'group_sup_bench.json')
+    if args.groups is None:
+        args.groups = [2, 4, 6, 8, 16] if args.gan else [1, 2, 4, 6, 8, 16]
+    if args.gan and min(args.groups) < 2:
+        ap.error("--gan: a group has at least 2 models")
     if args.blocks < 5:
         ap.error("--blocks: the median needs at least 5 blocks per side")
     if args.worker:
-        return worker(args.worker[0], int(args.worker[1]), args.blocks, args.steps, int(args.worker[1]) in args.profile_g)
+        return (gan_worker if args.gan else worker)(args.worker[0], int(args.worker[1]), args.blocks, args.steps, int(args.worker[1]) in args.profile_g)
     results = []
     for dtype in args.dtypes:
         for G in args.groups:
-            cmd = [sys.executable, os.path.abspath(__file__), '--worker', dtype, str(G), '--blocks', str(args.blocks), '--steps', str(args.steps),
-                   '--profile-g'] + [str(g) for g in args.profile_g]
+            cmd = [sys.executable, os.path.abspath(__file__), '--worker', dtype, str(G), '--blocks', str(args.blocks), '--steps', str(args.steps)]
+            cmd += (['--gan'] if args.gan else []) + ['--profile-g'] + [str(g) for g in args.profile_g]
             try:
                 out = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=240, check=True).stdout.decode()
             except (subprocess.TimeoutExpired, subprocess.CalledProcessError) as e:
@@ -148,7 +257,8 @@ def main():
         else:
             continue
         break
-    doc = dict(command="python scripts/group_bench.py " + " ".join(sys.argv[1:]), shape=dict(D=D, batch=B), results=results)
+    shape = dict(D=D, batch=GAN_B, rows=GAN_N, step="one (D, G) pair of all G models, stream mode, graph replay") if args.gan else dict(D=D, batch=B)
+    doc = dict(command="python scripts/group_bench.py " + " ".join(sys.argv[1:]), shape=shape, results=results)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, 'w') as f:
         json.dump(doc, f, indent=1)
