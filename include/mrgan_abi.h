@@ -274,6 +274,35 @@ int mrgan_eval_error(mrgan_handle* h, const float* x_dev, const int32_t* idx_dev
 int mrgan_predict_logits(mrgan_handle* h, const float* x_dev, const int32_t* idx_dev, int64_t ld_x, int64_t n,
                          float* logits_dev, mrgan_stream stream);
 
+/* Input-gradient saliency of a trained discriminator (the reference's others/mr_nn_activation_map.py): per row, the gradient
+ * of an objective of the noise-free forward (learning phase 0) with respect to the input row, from the engine's own forward and
+ * dX products.  Objectives, with t the row's target class (targets_dev[i], or the predicted class -- argmax of the logits,
+ * ties to the first class -- when targets_dev is NULL):
+ *   MRGAN_SAL_LOGIT  the class score l_t
+ *   MRGAN_SAL_XENT   -log softmax(l)_t, the labelled loss term of mr_gan.py:146 for one row
+ *   MRGAN_SAL_MSE    mean_c (l_c - onehot(t)_c)^2, the loss of the linear-output baseline (mr_nn.py:112) for one row
+ * post MRGAN_SAL_RAW writes the gradient; MRGAN_SAL_HEATMAP the reference's map: g / (rms(g) + 1e-5), absolute value, min-max
+ * scaled to [0, 1] over the d_in columns of the row.  A row whose map is constant (an all-dead row has a zero gradient) is
+ * written as zeros; the reference would print NaN there.  out_dev: fp32 [n][ld_out], columns >= d_in are left untouched.
+ * classes_out_dev (optional) receives the t each row used.  A target outside [0, num_classes) is a caller error: the gradient
+ * of that row is then the objective's without the onehot term (it is not checked).
+ * x_dev / idx_dev / ld_x: as mrgan_predict_logits.  The call uses the training activations as scratch, S = batch rounded up
+ * to 128 rows at a time, and leaves the weights, the Adam slots, the iteration and batch counters, the metrics and a captured
+ * mrgan_train_pair graph untouched; two calls give identical bits.  A group handle serves the model of mrgan_select_model.
+ * Status -2: null x / out, n < 0, a pitch smaller than d_in, unknown objective or post.  Status -3: an fp8 handle (use an fp32
+ * or bf16 engine with the same weights). */
+enum { MRGAN_SAL_LOGIT = 0, MRGAN_SAL_XENT = 1, MRGAN_SAL_MSE = 2 };
+enum { MRGAN_SAL_RAW = 0, MRGAN_SAL_HEATMAP = 1 };
+typedef struct mrgan_saliency_args {
+    const float* x_dev; const int32_t* idx_dev; int64_t ld_x; int64_t n;
+    const int32_t* targets_dev;      /* [n] or NULL: the predicted class */
+    int32_t objective;               /* MRGAN_SAL_LOGIT | MRGAN_SAL_XENT | MRGAN_SAL_MSE */
+    int32_t post;                    /* MRGAN_SAL_RAW | MRGAN_SAL_HEATMAP */
+    float* out_dev; int64_t ld_out;  /* [n][ld_out], ld_out >= d_in */
+    int32_t* classes_out_dev;        /* optional [n]: the target class used */
+} mrgan_saliency_args;
+int mrgan_input_gradient(mrgan_handle* h, const mrgan_saliency_args* a, mrgan_stream stream);
+
 /* epoch metrics accumulated on the device (mr_gan.py:208-210 accumulate on the host and force a sync per step):
  * out8_host = sum loss_lab, sum loss_unl, sum train_err, sum loss_gen, last loss_lab, last loss_unl, last err,
  * last loss_gen.  reset != 0 zeroes the sums afterwards. */

@@ -154,7 +154,8 @@ int mrgan_debug_bn_bwd(const mrgan_debug_bn_bwd_desc* d, mrgan_stream stream);
  * segment: logits[row][0 .. KP) (KP = ldw; zeros in columns >= classes), dpre[row][0 .. feat), and per 32-row block blk =
  * seg * ceil(rows / 32) + b: loss_part[blk][0 .. 4), part[blk][0 .. feat * KP) = dW6, [off_db .. + KP) = db6,
  * [off_dbf .. + feat) = the feature layer's bias gradient.  HEAD_EVAL adds to *err_count and writes nothing else but logits;
- * HEAD_LOGITS writes logits only.  q8 / q8t (fp8 mode): e5m2 bytes [row][0 .. feat) and [col][0 .. round_up(rows, 32)) (rows
+ * HEAD_LOGITS writes logits only.  The saliency kinds (6 .. 8, one segment, labels = targets or null) write dpre, logits where
+ * given and, through the err_count field, the target class of every row (int32 [rows], or null).  q8 / q8t (fp8 mode): e5m2 bytes [row][0 .. feat) and [col][0 .. round_up(rows, 32)) (rows
  * beyond `rows` zero), max |dpre| into q8_slot. */
 typedef struct mrgan_debug_head_desc {
     int32_t dtype;

@@ -65,7 +65,12 @@ int stat_row_blocks(int rows);                                 // row blocks of 
 
 // ---- loss head (mr_gan.py:128, :146-149, :161-162): last dense + losses + their gradients ----
 enum { HEAD_LAB = 0, HEAD_UNL = 1, HEAD_FAKE = 2, HEAD_EVAL = 3, HEAD_LOGITS = 4,
-       HEAD_MSE = 5 };   // supervised baseline (mr_nn.py:112): mean squared error against the one-hot label
+       HEAD_MSE = 5,     // supervised baseline (mr_nn.py:112): mean squared error against the one-hot label
+       // Saliency row kinds (head_kernel only; every segment of a launch, or none): dpre = the PER-ROW gradient of the class
+       // score / the cross-entropy / the squared error of the target class (head.h: head_row), no 1 / batch.  labels = the
+       // targets, or null: the row's argmax.  Such a launch writes dpre and classes_out (and logits where given), nothing else:
+       // no loss_part, no part, no err_count.
+       HEAD_SAL_LOGIT = 6, HEAD_SAL_XENT = 7, HEAD_SAL_MSE = 8 };
 struct HeadArgs {
     const void* f; long f_bs; int ldf;         // features [seg][rows][ldf]
     int rows, nseg, seg_kind[3];
@@ -82,7 +87,10 @@ struct HeadArgs {
     // Model groups: grid.z = models (0 or 1: one model).  Model m's f, w, b, logits, dpre, part and loss_part lie model_stride
     // BYTES behind model 0's, its labels labels_ms elements behind; st is shared.  Training heads without fp8 copies only.
     int models; long model_stride, labels_ms;
-    int* err_count;                            // HEAD_EVAL: integer count of argmax != label
+    union {                                    // (one pointer: the kinds that use them never share a launch)
+        int* err_count;                        // HEAD_EVAL: integer count of argmax != label
+        int32_t* classes_out;                  // HEAD_SAL_*: optional [rows], the target class each row used
+    };
     // fp8 mode: dpre leaves as e5m2 copies scaled by q8_slot->scale (row-major [seg][rows][ldq8] and transposed [feat][ldq8t] with
     // segment s at row offset s * q8t_bs), max |dpre| -> q8_slot; dpre itself may then be null
     unsigned char* q8; long q8_bs; int ldq8;
@@ -95,6 +103,19 @@ int launch_head(int bf16, const HeadArgs& a, hipStream_t s);
 int launch_reduce_partials(const float* src, int nsrc, long stride, int n, int ngroups, float* dst, hipStream_t s, int models = 1,
                            long model_stride = 0);
 int init_kernel_attributes();
+
+// ---- saliency map of a trained discriminator: rows of d objective / d input (the layer-0 dX) -> the caller's fp32 rows ----
+// SAL_RAW: the gradient, widened.  SAL_HEATMAP (others/mr_nn_activation_map.py:170-178 of the reference): g_hat = g / (rms(g) +
+// 1e-5), a = |g_hat|, out = (a - min a) / (max a - min a), mean and extrema over the row's `cols` columns.  A row with max a ==
+// min a (an all-dead row: zero gradient) is written as zeros, where the reference divides 0 by 0.
+enum { SAL_RAW = 0, SAL_HEATMAP = 1 };
+struct SaliencyFinishArgs {
+    const void* g; int ldg;                    // T [rows][ldg]
+    int rows, cols;
+    float* out; long ldo;                      // [rows][ldo], columns >= cols are left alone
+    int mode;
+};
+int launch_saliency_finish(int bf16, const SaliencyFinishArgs& a, hipStream_t s);
 
 // ---- feature matching (mr_gan.py:152-154) ----
 struct FmArgs {

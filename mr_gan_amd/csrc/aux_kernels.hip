@@ -300,7 +300,10 @@ __device__ __forceinline__ float head_fma(float a, float b, float c) { return fm
 __device__ __forceinline__ double head_fma(float a, float b, double c) { return fma((double)a, (double)b, c); }
 // Q8 (fp8 mode): dpre leaves as e5m2 copies (row-major + transposed) packed from the fp32 values; a separate instantiation,
 // so the bf16 / fp32 kernels keep their rolled row loop and register count
-template <typename T, bool Q8 = false, int KP = KMAX>
+// SAL: the saliency row kinds HEAD_SAL_* (aux_kernels.h), again an instantiation of its own: the per-row dlogits go on through
+// W6 and the feature layer's relu mask into dpre as in a training launch, and nothing else leaves the kernel -- no loss
+// partials, no partial gradients, no error count -- beside the optional target classes (and logits)
+template <typename T, bool Q8 = false, int KP = KMAX, bool SAL = false>
 __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
     constexpr int KG = KP / 4;                 // f32x4 groups of classes
     typedef typename HeadAcc<(KP > KMAX && sizeof(T) == 2)>::type acc_t;
@@ -382,14 +385,15 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
     float b[KP];
 #pragma unroll
     for (int c = 0; c < KP; ++c) b[c] = (c < a.classes) ? ((const float*)((const char*)a.b + moff))[c] : 0.f;
-    int y = 0;
-    if (rowvalid && head_kind_has_label(kind)) {
+    int y = SAL ? -1 : 0, target = 0;              // (SAL without targets: y < 0, the row's argmax)
+    if (rowvalid && (SAL ? a.labels != nullptr : head_kind_has_label(kind))) {
         const long lo = a.labels_stream ? (long)a.st->batch * a.rows : 0;
         y = a.labels[(long)blockIdx.z * a.labels_ms + lo + row];
     }
     float loss0, loss1, err, dl[KP];
-    head_row<true>(l, b, kind, y, a.classes, a.inv_count, a.unl_weight, rowvalid, loss0, loss1, err, dl);
+    head_row<true, KP, SAL>(l, b, kind, y, a.classes, a.inv_count, a.unl_weight, rowvalid, loss0, loss1, err, dl, &target);
     if (part == 0) {
+        if constexpr (SAL) { if (a.classes_out && rowvalid) a.classes_out[row] = target; }
 #pragma unroll
         for (int g = 0; g < KG; ++g) *(f32x4*)(dl_lds + r * KP + 4 * g) = (f32x4){dl[4 * g], dl[4 * g + 1], dl[4 * g + 2], dl[4 * g + 3]};
         if (a.logits && rowvalid) {
@@ -398,10 +402,12 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
             for (int c = 0; c < KP; ++c) lp[c] = (c < a.classes) ? l[c] : 0.f;
         }
     } else { loss0 = 0.f; loss1 = 0.f; err = 0.f; }
-    loss0 = wave_sum(loss0); loss1 = wave_sum(loss1); err = wave_sum(err);
-    if (lane == 0) { red[wave * 4 + 0] = loss0; red[wave * 4 + 1] = loss1; red[wave * 4 + 2] = err; }
-    __syncthreads();
-    if (t == 0) {
+    if constexpr (!SAL) {
+        loss0 = wave_sum(loss0); loss1 = wave_sum(loss1); err = wave_sum(err);
+        if (lane == 0) { red[wave * 4 + 0] = loss0; red[wave * 4 + 1] = loss1; red[wave * 4 + 2] = err; }
+    }
+    __syncthreads();                               // (also: dl_lds is complete)
+    if (!SAL && t == 0) {
         float s0 = 0.f, s1 = 0.f, s2 = 0.f;
         for (int w = 0; w < 4; ++w) { s0 += red[w * 4 + 0]; s1 += red[w * 4 + 1]; s2 += red[w * 4 + 2]; }
         if (kind == HEAD_EVAL) { if (a.err_count) atomicAdd(a.err_count, (int)(s2 + 0.5f)); }
@@ -414,8 +420,8 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
     if (kind == HEAD_EVAL || kind == HEAD_LOGITS) return;
 
     // ---- backward of the last dense: thread <-> feature column j ----
-    float* part_row = (float*)((char*)a.part + moff) + (long)blk * a.part_stride;
-    if (t < KP) {
+    float* part_row = SAL ? nullptr : (float*)((char*)a.part + moff) + (long)blk * a.part_stride;
+    if (!SAL && t < KP) {
         float s = 0.f;
         for (int rr = 0; rr < HR; ++rr) s += dl_lds[rr * KP + t];
         part_row[a.off_db + t] = s;
@@ -484,13 +490,68 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
             } else {
                 for (int rr = 0; rr < HR; ++rr) row_step(rr);
             }
+            if constexpr (!SAL) {
 #pragma unroll
-            for (int g = 0; g < KG; ++g)
-                *(f32x4*)(part_row + (long)(c0 + j) * KP + 4 * g) = (f32x4){dw[4 * g], dw[4 * g + 1], dw[4 * g + 2], dw[4 * g + 3]};
-            part_row[a.off_dbf + c0 + j] = dbf;
+                for (int g = 0; g < KG; ++g)
+                    *(f32x4*)(part_row + (long)(c0 + j) * KP + 4 * g) = (f32x4){dw[4 * g], dw[4 * g + 1], dw[4 * g + 2], dw[4 * g + 3]};
+                part_row[a.off_dbf + c0 + j] = dbf;
+            }
         }
     }
     if constexpr (Q8) fp8_amax_commit(a.q8_slot, q8_amax);
+}
+
+// =========================================================================================
+// saliency finish: one block = one row of the layer-0 dX (T, pitch ldg) -> one fp32 row of the caller (SaliencyFinishArgs).
+// thread <-> 8 consecutive columns, every 2048th column group; the row is read twice (second time from cache).  SAL_HEATMAP:
+// sum g^2, max |g| and min |g| of the row by wave shuffles, then over the four waves through LDS in wave order -- no
+// atomics: the same bits on every call.  |g| / denom is monotone in |g|, so min a and max a are the quotients of min |g| and
+// max |g|, and the elements that attain them come out as exactly 0 and 1.
+// =========================================================================================
+template <typename T>
+__global__ __launch_bounds__(256) void saliency_finish_kernel(const SaliencyFinishArgs a) {
+    __shared__ float red[3][4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, row = blockIdx.x;
+    const T* g = (const T*)a.g + (long)row * a.ldg;
+    float* out = a.out + (long)row * a.ldo;
+    float denom = 1.f, amin = 0.f, range = 0.f;
+    if (a.mode == SAL_HEATMAP) {
+        float ss = 0.f, mx = 0.f, mn = 3.0e38f;
+        for (int c = t * 8; c < a.cols; c += 2048) {       // (ldg is a multiple of 8: the group lies inside the padded row)
+            float v[8];
+            load8<T>(g + c, v);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if (c + i < a.cols) { ss = fmaf(v[i], v[i], ss); mx = fmaxf(mx, fabsf(v[i])); mn = fminf(mn, fabsf(v[i])); }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            ss += __shfl_xor(ss, o, 64); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); mn = fminf(mn, __shfl_xor(mn, o, 64));
+        }
+        if (lane == 0) { red[0][wave] = ss; red[1][wave] = mx; red[2][wave] = mn; }
+        __syncthreads();
+        ss = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        mx = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+        mn = fminf(fminf(red[2][0], red[2][1]), fminf(red[2][2], red[2][3]));
+        denom = sqrtf(ss / (float)a.cols) + 1e-5f;
+        amin = mn / denom;
+        range = mx / denom - amin;
+    }
+    const bool vec = (((uintptr_t)out) & 15) == 0;
+    for (int c = t * 8; c < a.cols; c += 2048) {
+        float v[8];
+        load8<T>(g + c, v);
+        if (a.mode == SAL_HEATMAP) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = range > 0.f ? (fabsf(v[i]) / denom - amin) / range : 0.f;
+        }
+        if (vec && c + 7 < a.cols) store8<float>(out + c, v);
+        else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) if (c + i < a.cols) out[c + i] = v[i];
+        }
+    }
 }
 
 // dst[g][i] = sum of src[p][i] over the partial rows p of group g (p = g, g + ngroups, ...)
@@ -896,6 +957,15 @@ int init_kernel_attributes() {
         e = hipFuncSetAttribute((const void*)head_kernel<float, false, KWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)head_kernel<__bf16, false, KWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    // ... and its saliency instantiations
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)head_kernel<float, false, KMAX, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)head_kernel<__bf16, false, KMAX, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)head_kernel<float, false, KWIDE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)head_kernel<__bf16, false, KWIDE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     return e == hipSuccess ? 0 : -2;
 }
 
@@ -906,6 +976,19 @@ int launch_head(int bf16, const HeadArgs& a, hipStream_t s) {
     const size_t smem = sizeof(float) * ((size_t)HR * (ch + 8) + (size_t)ch * kp + HR * kp + 16);
     dim3 grid(ceil_div(a.rows, HR), a.nseg, std::max(1, a.models));
     if (a.models > 1 && (a.q8_slot || a.err_count)) return -3;      // model groups: training heads without fp8 copies
+    int nsal = 0;
+    for (int i = 0; i < a.nseg; ++i) nsal += a.seg_kind[i] >= HEAD_SAL_LOGIT && a.seg_kind[i] <= HEAD_SAL_MSE;
+    if (nsal) {                                // the saliency kinds: every segment, one model, no fp8 copies, dpre required
+        if (nsal != a.nseg || a.models > 1 || a.q8_slot || !a.dpre) return -3;
+        if (kp == KWIDE) {
+            if (bf16) MRGAN_LAUNCH((head_kernel<__bf16, false, KWIDE, true>), grid, dim3(256), smem, s, a);
+            else MRGAN_LAUNCH((head_kernel<float, false, KWIDE, true>), grid, dim3(256), smem, s, a);
+        } else {
+            if (bf16) MRGAN_LAUNCH((head_kernel<__bf16, false, KMAX, true>), grid, dim3(256), smem, s, a);
+            else MRGAN_LAUNCH((head_kernel<float, false, KMAX, true>), grid, dim3(256), smem, s, a);
+        }
+        RET_LAUNCH;
+    }
     if (kp == KWIDE) {
         if (a.q8_slot) return -3;              // the e5m2 packing epilogue exists at the 8-class pitch only
         if (bf16) MRGAN_LAUNCH((head_kernel<__bf16, false, KWIDE>), grid, dim3(256), smem, s, a);
@@ -921,6 +1004,13 @@ int launch_head(int bf16, const HeadArgs& a, hipStream_t s) {
     } else {
         LAUNCH_T(head_kernel, grid, dim3(256), smem, s, a);
     }
+    RET_LAUNCH;
+}
+
+int launch_saliency_finish(int bf16, const SaliencyFinishArgs& a, hipStream_t s) {
+    if (a.rows <= 0) return 0;
+    if ((a.mode != SAL_RAW && a.mode != SAL_HEATMAP) || a.cols <= 0 || a.cols > a.ldg || (a.ldg % 8) != 0 || a.ldo < a.cols) return -3;
+    LAUNCH_T(saliency_finish_kernel, dim3(a.rows), dim3(256), 0, s, a);
     RET_LAUNCH;
 }
 

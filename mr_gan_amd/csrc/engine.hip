@@ -189,6 +189,7 @@ int dense_dx(mrgan_handle* h, const Dense& L, int kind, const void* dy, int rows
                                                     h->bf16 ? (const void*)L.W->w16 : (const void*)L.W->p, L.Np));
     Epi& e = g.e;
     e.act = act; e.n_valid = n_valid;
+    if (kind == KIND_EVAL) g.B = selected(h, g.B);      // (model by model, as dense_fwd: dy, out and the mask are the caller's)
     e.out = out; e.out_bs = (long)h->S * L.Kp; e.ldo = L.Kp;
     epi_mask(h, e, m);
     e.h = hprev; e.h_bs = (long)h->S * L.Kp; e.ldh = L.Kp;
@@ -891,6 +892,59 @@ int eval_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, cons
     return 0;
 }
 
+// Input-gradient saliency of n rows (mrgan_input_gradient): per chunk the evaluation forward WITH its relu masks, the per-row
+// saliency head into dpre[4], the masked dX chain down to layer 1, the linear layer-0 dX into dxfake and the finishing kernel
+// into the caller's rows.  Everything lives in segment 0 of the training activations (xin[l], mask[l], dpre[l], feat) as one
+// run of contiguous rows; dxfake holds S rows, which is what bounds the chunk.  No noise, no state slot, no column sums, no
+// weight gradients: cur, the counters and the cached graph are not touched.
+int saliency_rows(mrgan_handle* h, const mrgan_saliency_args* a, hipStream_t s) {
+    static const int kinds[3] = {HEAD_SAL_LOGIT, HEAD_SAL_XENT, HEAD_SAL_MSE};
+    const long cap = h->S, n = a->n;
+    auto mask_of = [&](int l) { return ReluMask{selected(h, h->mask[l]), h->ldm[l]}; };
+    for (long r0 = 0; r0 < n; r0 += cap) {
+        const int rows = (int)std::min(cap, n - r0);
+        StageArgs st;
+        memset(&st, 0, sizeof st);
+        StageSeg& sg = st.s[0];
+        sg.src = a->idx_dev ? a->x_dev : a->x_dev + r0 * a->ld_x; sg.idx = a->idx_dev ? a->idx_dev + r0 : nullptr; sg.ld = a->ld_x; sg.rows = rows;
+        sg.cols = h->cfg.d_in; sg.cols_pad = h->Dp; sg.out = selected(h, h->xin[0]); sg.ldo = h->Dp;
+        st.nseg = 1; st.seed = h->cfg.seed; st.cur = h->state + h->cur;
+        PROF("stage_kernel", launch_stage(h->bf16, st, s));
+        for (int l = 0; l < 5; ++l)
+            CHK(dense_fwd(h, h->d[l], KIND_EVAL, selected(h, h->xin[l]), rows, 1, selected(h, l < 4 ? h->xin[l + 1] : h->feat), ACT_RELU, NO_NOISE,
+                          mask_of(l), NO_SUMS, s));
+        HeadArgs hd = head_args(h, {kinds[a->objective]}, rows, false);
+        hd.f = selected(h, hd.f); hd.w = selected(h, hd.w); hd.b = selected(h, hd.b); hd.logits = nullptr;
+        hd.labels = a->targets_dev ? a->targets_dev + r0 : nullptr;
+        hd.classes_out = a->classes_out_dev ? a->classes_out_dev + r0 : nullptr;
+        hd.dpre = selected(h, h->dpre[4]); hd.ldd = h->Fp;
+        PROF("head_kernel", launch_head(h->bf16, hd, s));
+        for (int l = 4; l >= 1; --l)
+            CHK(dense_dx(h, h->d[l], KIND_EVAL, selected(h, h->dpre[l]), rows, 1, selected(h, h->dpre[l - 1]), ACT_RELU, h->d[l - 1].N, mask_of(l - 1),
+                         nullptr, NO_SUMS, s));
+        CHK(dense_dx(h, h->d[0], KIND_EVAL, selected(h, h->dpre[0]), rows, 1, selected(h, h->dxfake), ACT_LINEAR, h->cfg.d_in, NO_MASK, nullptr,
+                     NO_SUMS, s));
+        SaliencyFinishArgs f;
+        memset(&f, 0, sizeof f);
+        f.g = selected(h, h->dxfake); f.ldg = h->Dp; f.rows = rows; f.cols = h->cfg.d_in;
+        f.out = a->out_dev + r0 * a->ld_out; f.ldo = a->ld_out; f.mode = a->post == MRGAN_SAL_HEATMAP ? SAL_HEATMAP : SAL_RAW;
+        PROFB("saliency_finish_kernel", launch_saliency_finish(h->bf16, f, s), (double)rows * h->cfg.d_in * (2.0 * h->es + 4.0));
+    }
+    // Ragged batches: the chunks filled rows B .. S of segment 0, the padding rows of a training segment.  The bf16 weight
+    // gradients reduce over all S rows and need zero dY -- dpre[l], and dxfake, the dY of the generator's last layer -- and
+    // finite xin there (see eval_rows): re-zero them.  (feat and the masks: every training forward rewrites what its sub-step
+    // reads, and the padding rows of feat meet zero dlogits only.)
+    if (h->B < h->S && n > h->B) {
+        const size_t pad = (size_t)(h->S - h->B);
+        HIPCHK(hipMemsetAsync((char*)selected(h, h->dxfake) + (size_t)h->B * h->Dp * h->es, 0, pad * h->Dp * h->es, s));
+        for (int l = 0; l < 5; ++l) {
+            HIPCHK(hipMemsetAsync((char*)selected(h, h->xin[l]) + (size_t)h->B * h->d[l].Kp * h->es, 0, pad * h->d[l].Kp * h->es, s));
+            HIPCHK(hipMemsetAsync((char*)selected(h, h->dpre[l]) + (size_t)h->B * h->d[l].Np * h->es, 0, pad * h->d[l].Np * h->es, s));
+        }
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // fp8 calibration of a sub-step kind (0 = D, 1 = G): dry passes (forward + backward phases, no update) between begin and
 // done, each followed by end_pass, settle the delayed scales, one layer of the gradient chain per pass.  Whole sub-steps run
@@ -1128,6 +1182,18 @@ int mrgan_predict_logits(mrgan_handle* h, const float* x, const int32_t* idx, in
     if (!h || !x || !logits || n < 1) return fail(-1, "predict_logits: bad argument");
     if (ld < h->cfg.d_in) return fail(-2, "predict_logits: row pitch smaller than d_in");
     return eval_rows(h, x, idx, ld, nullptr, n, logits, (hipStream_t)stream);
+}
+
+int mrgan_input_gradient(mrgan_handle* h, const mrgan_saliency_args* a, mrgan_stream stream) {
+    if (!h) return fail(-1, "null handle");
+    if (h->fp8) return fail(-3, "input_gradient: not on an fp8 handle (its dX products read fp8-scaled images and would disturb the calibration); use an fp32 or a bf16 engine");
+    if (!a || !a->x_dev || !a->out_dev) return fail(-2, "input_gradient: x and out are required");
+    if (a->n < 0) return fail(-2, "input_gradient: negative row count");
+    if (a->ld_x < h->cfg.d_in || a->ld_out < h->cfg.d_in) return fail(-2, "input_gradient: row pitch smaller than d_in");
+    if (a->objective != MRGAN_SAL_LOGIT && a->objective != MRGAN_SAL_XENT && a->objective != MRGAN_SAL_MSE)
+        return fail(-2, "input_gradient: unknown objective %d", (int)a->objective);
+    if (a->post != MRGAN_SAL_RAW && a->post != MRGAN_SAL_HEATMAP) return fail(-2, "input_gradient: unknown post mode %d", (int)a->post);
+    return saliency_rows(h, a, (hipStream_t)stream);
 }
 
 int mrgan_profile_begin(mrgan_handle* h) {

@@ -30,9 +30,16 @@ __device__ __forceinline__ void split3(float v, __bf16& hi, __bf16& mid, __bf16&
 // segment gives zeros.
 // ALL_KINDS: head_kernel also serves HEAD_MSE, HEAD_EVAL and HEAD_LOGITS; the matrix-core heads are launched with the three
 // training kinds only (their launchers check it) and compile those branches out.
-template <bool ALL_KINDS, int KP = KMAX>
+// SAL (head_kernel's saliency instantiation only): the row kinds HEAD_SAL_* and nothing else.  dl is the PER-ROW d objective /
+// d logits of target class t -- no 1 / batch, no loss terms -- with t = y, or the row's argmax (ties -> first index, as
+// HEAD_EVAL decides it) where y < 0; *target receives t.
+//   HEAD_SAL_LOGIT  onehot(t)                                   the class score
+//   HEAD_SAL_XENT   softmax over the real logits - onehot(t)    HEAD_LAB without the batch mean (mr_gan.py:146)
+//   HEAD_SAL_MSE    2 (l - onehot(t)) / classes                 HEAD_MSE without the batch mean
+template <bool ALL_KINDS, int KP = KMAX, bool SAL = false>
 __device__ __forceinline__ void head_row(float (&l)[KP], const float (&b)[KP], int kind, int y, int classes, float inv_count, float unl_weight,
-                                         bool rowvalid, float& loss0, float& loss1, float& err, float (&dl)[KP]) {
+                                         bool rowvalid, float& loss0, float& loss1, float& err, float (&dl)[KP], int* target = nullptr) {
+    static_assert(ALL_KINDS || !SAL, "the saliency kinds belong to head_kernel");
     float mx = -3.0e38f;
 #pragma unroll
     for (int c = 0; c < KP; ++c) {
@@ -52,6 +59,19 @@ __device__ __forceinline__ void head_row(float (&l)[KP], const float (&b)[KP], i
 #pragma unroll
     for (int c = 0; c < KP; ++c) dl[c] = 0.f;
     if (!rowvalid) return;
+    if constexpr (SAL) {
+        const int t = y >= 0 ? y : am;
+        if (target) *target = t;
+        const float invc = 1.0f / (float)classes;
+#pragma unroll
+        for (int c = 0; c < KP; ++c) {
+            if (c < classes) {
+                const float oh = c == t ? 1.f : 0.f;
+                dl[c] = kind == HEAD_SAL_LOGIT ? oh : kind == HEAD_SAL_XENT ? p[c] * inv_se - oh : 2.0f * (l[c] - oh) * invc;
+            }
+        }
+        return;
+    }
     if (ALL_KINDS && kind == HEAD_MSE) {
         // Keras 'mse' on one-hot targets (mr_nn.py:99, :112): mean over the classes, then over the batch
         err = (y >= 0 && am != y) ? 1.f : 0.f;

@@ -34,7 +34,11 @@ EXPORTS = [
     "mrgan_debug_fm", "mrgan_debug_adam",
     "mrgan_select_model", "mrgan_sup_step_group",
     "mrgan_disc_step_group", "mrgan_gen_step_group", "mrgan_train_pair_group",
+    "mrgan_input_gradient",
 ]
+SAL_LOGIT, SAL_XENT, SAL_MSE = 0, 1, 2
+SAL_RAW, SAL_HEATMAP = 0, 1
+SAL_OBJECTIVES = {'logit': SAL_LOGIT, 'xent': SAL_XENT, 'mse': SAL_MSE}
 MAX_MODELS = 16
 PROF_NAME_LEN = 96
 
@@ -107,6 +111,24 @@ class GenGroupArgs(C.Structure):
         ("x_unl_model_stride", C.c_int64), ("idx_unl_model_stride", C.c_int64), ("z_model_stride", C.c_int64),
         ("stream_mode", C.c_int32), ("reserved", C.c_int32),
     ]
+
+
+class SaliencyArgs(C.Structure):
+    """mrgan_saliency_args"""
+    _fields_ = [
+        ("x", C.c_void_p), ("idx", C.c_void_p), ("ld_x", C.c_int64), ("n", C.c_int64),
+        ("targets", C.c_void_p),
+        ("objective", C.c_int32), ("post", C.c_int32),
+        ("out", C.c_void_p), ("ld_out", C.c_int64),
+        ("classes_out", C.c_void_p),
+    ]
+
+
+def saliency_objective(objective):
+    """'logit' | 'xent' | 'mse' -> MRGAN_SAL_*"""
+    if objective not in SAL_OBJECTIVES:
+        raise ValueError("objective must be one of %s, got %r" % (sorted(SAL_OBJECTIVES), objective))
+    return SAL_OBJECTIVES[objective]
 
 
 _lib = None
@@ -430,6 +452,23 @@ class Engine(object):
         _check(self.lib.mrgan_predict_logits(self.handle, _ptr(x), _ptr(idx), C.c_int64(x.stride(0)), C.c_int64(n), _ptr(out),
                                              _stream()))
         return out
+
+    def input_gradient(self, x, targets=None, objective=SAL_XENT, post=SAL_RAW, idx=None, out=None, classes_out=None):
+        """mrgan_input_gradient -> (maps fp32 [n, >= d_in], classes int32 [n]): per row the gradient of `objective` (SAL_*) at
+        its target class -- targets[i], or the predicted class -- with respect to the input row, raw or as the reference's
+        heat-map (post = SAL_HEATMAP).  out / classes_out: buffers to write into (out may have a row pitch above d_in; its
+        further columns are left alone)."""
+        n = x.shape[0] if idx is None else idx.numel()
+        if out is None:
+            out = torch.empty((n, self.cfg.d_in), dtype=torch.float32, device=self.device)
+        if classes_out is None:
+            classes_out = torch.empty((n,), dtype=torch.int32, device=self.device)
+        a = SaliencyArgs()
+        a.x, a.idx, a.ld_x, a.n = _ptr(x), _ptr(idx), x.stride(0), n
+        a.targets, a.objective, a.post = _ptr(targets), int(objective), int(post)
+        a.out, a.ld_out, a.classes_out = _ptr(out), out.stride(0), _ptr(classes_out)
+        _check(self.lib.mrgan_input_gradient(self.handle, C.byref(a), _stream()))
+        return out, classes_out
 
     def read_metrics(self, reset=True):
         out = (C.c_float * 8)()

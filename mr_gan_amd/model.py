@@ -110,6 +110,17 @@ class MRGAN(object):
         with self._on_stream():
             return self.engine.predict_logits(self._dev(X)).cpu().numpy()
 
+    def saliency(self, X, y=None, objective='xent', heatmap=True):
+        """Input-gradient saliency of the discriminator (the reference's others/mr_nn_activation_map.py): per row of X the
+        gradient of `objective` -- 'xent' (the labelled loss term), 'logit' (the class score) or 'mse' -- at class y[i], or at
+        the predicted class when y is None, with respect to the input; heatmap: |g / (rms(g) + 1e-5)| min-max scaled to [0, 1]
+        per row (a zero gradient gives a zero row), else the raw gradient.  -> (maps [n, D] float32, classes [n] int32)"""
+        code = E.saliency_objective(objective)
+        with self._on_stream():
+            maps, cls = self.engine.input_gradient(self._dev(X), None if y is None else self._dev(y, torch.int32), code,
+                                                   E.SAL_HEATMAP if heatmap else E.SAL_RAW)
+            return maps.cpu().numpy(), cls.cpu().numpy()
+
     def evaluate(self, X, y):
         """test_batch([0, X, y]) over the whole set (mr_gan.py:230) -> error rate."""
         with self._on_stream():
@@ -313,6 +324,15 @@ class MRGANGroup(object):
         with self._on_stream():
             self.engine.select_model(m)
             return self.engine.predict_logits(self._dev(X)).cpu().numpy()
+
+    def saliency(self, m, X, y=None, objective='xent', heatmap=True):
+        """MRGAN.saliency of model m"""
+        code = E.saliency_objective(objective)
+        with self._on_stream():
+            self.engine.select_model(m)
+            maps, cls = self.engine.input_gradient(self._dev(X), None if y is None else self._dev(y, torch.int32), code,
+                                                   E.SAL_HEATMAP if heatmap else E.SAL_RAW)
+            return maps.cpu().numpy(), cls.cpu().numpy()
 
     def evaluate(self, Xs, ys):
         """[test error of model m over (Xs[m], ys[m])], model by model"""

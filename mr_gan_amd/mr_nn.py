@@ -101,6 +101,15 @@ class MRNN(object):
         with torch.cuda.stream(self.stream):
             return self.engine.eval_error(self._dev(X), self._dev(y, torch.int32))
 
+    def saliency(self, X, y=None, objective='mse', heatmap=True):
+        """MRGAN.saliency for the baseline; the default objective is its training loss, as in the reference's
+        others/mr_nn_activation_map.py -> (maps [n, D] float32, classes [n] int32)"""
+        code = E.saliency_objective(objective)
+        with torch.cuda.stream(self.stream):
+            maps, cls = self.engine.input_gradient(self._dev(X), None if y is None else self._dev(y, torch.int32), code,
+                                                   E.SAL_HEATMAP if heatmap else E.SAL_RAW)
+            return maps.cpu().numpy(), cls.cpu().numpy()
+
 
 class MRNNGroup(object):
     """`models` MRNN trainings of one shape on one group handle (mrgan_config.models): model m is initialised and seeded exactly
