@@ -436,7 +436,7 @@ int stage_common(StageArgs& st, mrgan_handle* h, const float* z, int stream_mode
 }
 // (src_ms / idx_ms: elements between the models' rows and index vectors in a grouped step)
 void data_seg(StageSeg& sg, mrgan_handle* h, const float* x, const int32_t* idx, long ld, int slot, uint32_t seg_id, int stream_mode,
-              long src_ms = 0, long idx_ms = 0) {
+              long src_ms, long idx_ms) {
     memset(&sg, 0, sizeof sg);
     if (h->grouped > 1) { sg.models = h->grouped; sg.src_ms = src_ms; sg.idx_ms = idx_ms; sg.out_ms = (long)h->W; }
     sg.src = x; sg.idx = idx; sg.ld = ld; sg.rows = h->B; sg.cols = h->cfg.d_in; sg.cols_pad = h->Dp;
@@ -464,7 +464,8 @@ HeadArgs head_args(mrgan_handle* h, std::initializer_list<int> kinds, int rows, 
     hd.dpre = h->dpre[4]; hd.dpre_bs = (long)h->S * h->Fp; hd.ldd = h->Fp;
     hd.part = h->head_part; hd.part_stride = h->head_stride; hd.off_db = h->Fp * h->KP; hd.off_dbf = h->Fp * h->KP + h->KP;
     hd.loss_part = h->loss_part;
-    if (h->grouped > 1) { hd.models = h->grouped; hd.model_stride = (long)h->W; }      // (labels_ms: the caller's)
+    if (h->grouped > 1) { hd.models = h->grouped; hd.model_stride = (long)h->W; }
+    hd.labels_ms = h->gs.labels;
     return hd;
 }
 
@@ -488,7 +489,7 @@ ChainArgs chain_args(mrgan_handle* h, int variant, int nseg, int block_rows) {
 // before the head and their dX after it (8-class pitch only: at the 32-class pitch D3 .. D5 run per layer and the head alone).  Records how many partial rows of head_part / loss_part it wrote.
 int disc_head(mrgan_handle* h, const mrgan_disc_args* a, hipStream_t s) {
     HeadArgs hd = head_args(h, {HEAD_LAB, HEAD_UNL, HEAD_FAKE}, h->B, true);
-    hd.labels = a->labels_dev; hd.labels_stream = a->stream_mode; hd.labels_ms = h->gs.labels;
+    hd.labels = a->labels_dev; hd.labels_stream = a->stream_mode;
     hd.inv_count = 1.0f / (float)h->Bg; hd.unl_weight = h->cfg.unlabeled_weight;
     if (h->fp8) {                 // the head writes the e5m2 copies of dpre itself (no bf16 dpre, no quantiser pass)
         hd.dpre = nullptr;
@@ -551,7 +552,7 @@ int disc_phase(mrgan_handle* h, const mrgan_disc_args* a, int phase, hipStream_t
             // mrgan_train_pair: the G sub-step's real rows (its x_unl batch, drawn at iteration + 1) ride in this launch too
             const mrgan_gen_args* g = h->pair_g;
             StageSeg& rs = st.s[st.nseg];
-            data_seg(rs, h, g->x_unl_dev, g->idx_unl_dev, g->ld_x_unl, 4, 1, g->stream_mode);
+            data_seg(rs, h, g->x_unl_dev, g->idx_unl_dev, g->ld_x_unl, 4, 1, g->stream_mode, 0, 0);      // (single handles only)
             rs.iter_off = 1;
             st.nseg += 1;
             h->real_staged = 1;
@@ -691,7 +692,7 @@ int sup_step(mrgan_handle* h, const mrgan_sup_args* a, hipStream_t s) {
     prof_backlog(h, s);
     StageArgs st;
     memset(&st, 0, sizeof st);
-    data_seg(st.s[0], h, a->x_dev, a->idx_dev, a->ld_x, 0, 0, a->stream_mode);
+    data_seg(st.s[0], h, a->x_dev, a->idx_dev, a->ld_x, 0, 0, a->stream_mode, h->gs.x_lab, h->gs.idx_lab);
     st.nseg = 1;
     stage_common(st, h, nullptr, 0, -1);
     PROF("stage_kernel", launch_stage(h->bf16, st, s));
@@ -709,40 +710,38 @@ int sup_step(mrgan_handle* h, const mrgan_sup_args* a, hipStream_t s) {
     return 0;
 }
 
-// The same step for every model of a group handle, as ONE launch set: each launch below is the launch of sup_step with the
-// model as a further grid index (h->grouped: with_handle / gemm_group for the products, the model fields of StageSeg, HeadArgs,
-// FoldJob and AdamArgs for the rest).  Model m stages its own rows, draws its noise with seed + m and updates its own copy of
-// the weights; the iteration counter is shared.
-int sup_step_group(mrgan_handle* h, const mrgan_sup_group_args* a, hipStream_t s) {
-    const int B = h->B;
-    struct Grouped { mrgan_handle* h; ~Grouped() { h->grouped = 1; } } scope{h};      // (every return path leaves the handle single)
-    h->grouped = h->models;
-    prof_backlog(h, s);
-    StageArgs st;
-    memset(&st, 0, sizeof st);
-    data_seg(st.s[0], h, a->x_dev, a->idx_dev, a->ld_x, 0, 0, a->stream_mode);
-    st.s[0].models = h->models; st.s[0].src_ms = a->x_model_stride; st.s[0].idx_ms = a->idx_model_stride; st.s[0].out_ms = (long)h->W;
-    st.nseg = 1;
-    stage_common(st, h, nullptr, 0, -1);
-    PROF("stage_kernel", launch_stage(h->bf16, st, s));
-    CHK(disc_fwd_train(h, 0, 1, false, 0, s, 5));
-    HeadArgs hd = head_args(h, {HEAD_MSE}, B, true);
-    hd.labels = a->labels_dev; hd.labels_stream = a->stream_mode;
-    hd.inv_count = 1.0f / (float)(a->rows_valid > 0 ? a->rows_valid : B); hd.unl_weight = 0.f;
-    hd.models = h->models; hd.model_stride = (long)h->W; hd.labels_ms = a->labels_model_stride;
-    PROF("head_kernel", launch_head(h->bf16, hd, s));
-    h->head_nblk = 3 * ceil_div(B, HEAD_ROWS);           // (as sup_step: the partial rows of the two other segments stay zero)
-    CHK(disc_bwd(h, 1, 4, ceil_div(B, HEAD_ROWS), s));
-    CHK(run_adam(h, MRGAN_NET_D, ADAM_FUSED, true, s, a->stream_mode ? 1 : 0));
-    h->cur ^= 1;
+// ---------------------------------------------------------------------------------------------------
+// what the step entries ask of their arguments
+// ---------------------------------------------------------------------------------------------------
+int check_disc_args(const mrgan_handle* h, const mrgan_disc_args* a) {
+    if (!a || !a->x_lab_dev || !a->x_unl_dev || !a->labels_dev) return fail(-2, "disc_step: x_lab, x_unl and labels are required");
+    if (a->ld_x_lab < h->cfg.d_in || a->ld_x_unl < h->cfg.d_in) return fail(-2, "disc_step: row pitch smaller than d_in");
+    return 0;
+}
+int check_gen_args(const mrgan_handle* h, const mrgan_gen_args* a) {
+    if (!a || !a->x_unl_dev) return fail(-2, "gen_step: x_unl is required");
+    if (a->ld_x_unl < h->cfg.d_in) return fail(-2, "gen_step: row pitch smaller than d_in");
+    return 0;
+}
+// entry: "sup_step" or "sup_step_group" (a group handle is never data-parallel or fp8: mrgan_create refuses those)
+int check_sup_args(const mrgan_handle* h, const mrgan_sup_args& a, const char* entry) {
+    if (a.ld_x < h->cfg.d_in) return fail(-2, "%s: row pitch smaller than d_in", entry);
+    if (h->flat_grads || h->cfg.world != 1) return fail(-3, "%s: single-GPU handles only", entry);
+    if (h->fp8) return fail(-3, "%s: the fp8 mode covers the GAN step only", entry);
+    if (a.rows_valid < 0 || a.rows_valid > h->B) return fail(-2, "%s: rows_valid outside [0, batch]", entry);
+    if (a.rows_valid && a.stream_mode) return fail(-2, "%s: a short batch cannot be combined with stream mode", entry);
     return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------
-// the GAN sub-steps of a group handle: disc_phase / gen_phase with every launch covering all models
+// the steps of a group handle: sup_step / disc_phase / gen_phase with every launch covering all models
 // ---------------------------------------------------------------------------------------------------
-// For the scope of one grouped sub-step the handle describes all models: h->grouped (every argument builder adds the model
+// For the scope of one grouped step the handle describes all models: h->grouped (every argument builder adds the model
 // count and the stride W) and h->gs (the strides of the caller's inputs).  Every return path leaves the handle single.
+// Each launch is then the single handle's launch with the model as a further grid index: model m stages its own rows, draws
+// its noise with seed + m and updates its own copy of the weights; the iteration counter is shared.
+// (pair_gen / pair_g: a group never shares a generator pass.  Only disc_phase / gen_phase read them, so clearing them is
+// nothing to the supervised step, and a hint left by mrgan_pair_hint was cleared by the next grouped D sub-step anyway.)
 struct GroupScope {
     mrgan_handle* h;
     GroupScope(mrgan_handle* h_, const mrgan_handle::GroupStrides& gs) : h(h_) { h->grouped = h->models; h->gs = gs; h->pair_gen = 0; h->pair_g = nullptr; }
@@ -762,6 +761,19 @@ mrgan_gen_args single_args(const mrgan_gen_group_args* a) {
     g.x_unl_dev = a->x_unl_dev; g.idx_unl_dev = a->idx_unl_dev; g.z_dev = a->z_dev; g.ld_x_unl = a->ld_x_unl; g.stream_mode = a->stream_mode;
     return g;
 }
+mrgan_sup_args single_args(const mrgan_sup_group_args* a) {
+    mrgan_sup_args u;
+    memset(&u, 0, sizeof u);
+    u.x_dev = a->x_dev; u.idx_dev = a->idx_dev; u.labels_dev = a->labels_dev; u.ld_x = a->ld_x;
+    u.stream_mode = a->stream_mode; u.rows_valid = a->rows_valid;
+    return u;
+}
+int sup_step_group(mrgan_handle* h, const mrgan_sup_group_args* a, hipStream_t s) {
+    // (the one data segment and the labels of the supervised step travel in the labelled slots)
+    GroupScope scope(h, {(long)a->x_model_stride, (long)a->idx_model_stride, (long)a->labels_model_stride, 0, 0, 0});
+    const mrgan_sup_args u = single_args(a);
+    return sup_step(h, &u, s);
+}
 int disc_step_group(mrgan_handle* h, const mrgan_disc_group_args* a, hipStream_t s) {
     GroupScope scope(h, {(long)a->x_lab_model_stride, (long)a->idx_lab_model_stride, (long)a->labels_model_stride,
                          (long)a->x_unl_model_stride, (long)a->idx_unl_model_stride, (long)a->z_model_stride});
@@ -776,8 +788,6 @@ int gen_step_group(mrgan_handle* h, const mrgan_gen_group_args* a, hipStream_t s
     for (int p = 0; p < MRGAN_G_NPHASES; ++p) { const int r = gen_phase(h, &g, p, s); if (r) return r; }
     return 0;
 }
-int check_disc_args(const mrgan_handle* h, const mrgan_disc_args* a);
-int check_gen_args(const mrgan_handle* h, const mrgan_gen_args* a);
 int check_group_handle(const mrgan_handle* h, const char* entry) {
     if (h->models > 1) return 0;
     return fail(-3, "%s: not a group handle (mrgan_config.models = %d); a single model steps through mrgan_disc_step / mrgan_gen_step / mrgan_train_pair",
@@ -839,14 +849,46 @@ int refuse_group(const mrgan_handle* h, const char* entry) {
     return fail(-3, "%s: a group handle (models = %d) trains through the _group entries (mrgan_sup_step_group, mrgan_disc_step_group, mrgan_gen_step_group, mrgan_train_pair_group)", entry, h->models);
 }
 
-int check_disc_args(const mrgan_handle* h, const mrgan_disc_args* a) {
-    if (!a || !a->x_lab_dev || !a->x_unl_dev || !a->labels_dev) return fail(-2, "disc_step: x_lab, x_unl and labels are required");
-    if (a->ld_x_lab < h->cfg.d_in || a->ld_x_unl < h->cfg.d_in) return fail(-2, "disc_step: row pitch smaller than d_in");
+// ---------------------------------------------------------------------------------------------------
+// evaluation and saliency: forward-only passes (learning phase 0) that use the training activations as scratch
+// ---------------------------------------------------------------------------------------------------
+ReluMask eval_mask(const mrgan_handle* h, int l) { return ReluMask{selected(h, h->mask[l]), h->ldm[l]}; }
+
+// One chunk: `rows` rows from r0 of the caller's matrix (gathered through idx when given) -> xin[0], then dense 1..5 -> feat,
+// as one run of contiguous rows from row 0 (nb = 1: the batch stride is irrelevant).  keep_masks: the relu masks are
+// written for a dX chain that follows.  A group handle evaluates the selected model: its activations here, its weights in dense_fwd.
+int eval_forward(mrgan_handle* h, const float* x, const int32_t* idx, long ld, long r0, int rows, bool keep_masks, hipStream_t s) {
+    StageArgs st;
+    memset(&st, 0, sizeof st);
+    StageSeg& sg = st.s[0];
+    sg.src = idx ? x : x + r0 * ld; sg.idx = idx ? idx + r0 : nullptr; sg.ld = ld; sg.rows = rows;
+    sg.cols = h->cfg.d_in; sg.cols_pad = h->Dp; sg.out = selected(h, h->xin[0]); sg.ldo = h->Dp;
+    st.nseg = 1; st.seed = h->cfg.seed; st.cur = h->state + h->cur;
+    PROF("stage_kernel", launch_stage(h->bf16, st, s));
+    for (int l = 0; l < 5; ++l)
+        CHK(dense_fwd(h, h->d[l], KIND_EVAL, selected(h, h->xin[l]), rows, 1, selected(h, l < 4 ? h->xin[l + 1] : h->feat), ACT_RELU, NO_NOISE,
+                      keep_masks ? eval_mask(h, l) : NO_MASK, NO_SUMS, s));
     return 0;
 }
-int check_gen_args(const mrgan_handle* h, const mrgan_gen_args* a) {
-    if (!a || !a->x_unl_dev) return fail(-2, "gen_step: x_unl is required");
-    if (a->ld_x_unl < h->cfg.d_in) return fail(-2, "gen_step: row pitch smaller than d_in");
+
+// The chunks above fill rows from row 0 of every layer input, i.e. also the padding rows B .. S of the training segments they
+// reach.  The bf16 weight gradients reduce over all S rows of a segment, zero dY padding rows x FINITE X padding rows (dw_args):
+// a non-finite value left there by an evaluation input would turn into NaN gradients from then on (0 * NaN), and a nonzero dY
+// would add to them.  Ragged batches only: re-zero the padding rows of the first nseg_x0 segments of xin[0] and the first nseg
+// of xin[1..4]; grads: also those of segment 0 of the dY tensors a dX chain wrote, dpre[l] and dxfake (the dY of the generator's
+// last layer).  (feat and the masks: every training forward rewrites what its sub-step reads, and the padding rows of feat meet
+// zero dlogits only.)
+int rezero_padding(mrgan_handle* h, int nseg_x0, int nseg, bool grads, hipStream_t s) {
+    if (h->B >= h->S) return 0;
+    const size_t pad = (size_t)(h->S - h->B);
+    auto clear = [&](void* t, int seg, int ld) {
+        return hipMemsetAsync((char*)selected(h, t) + ((size_t)seg * h->S + h->B) * ld * h->es, 0, pad * ld * h->es, s);
+    };
+    for (int l = 0; l < 5; ++l) {
+        for (int seg = 0; seg < (l == 0 ? nseg_x0 : nseg); ++seg) HIPCHK(clear(h->xin[l], seg, h->d[l].Kp));
+        if (grads) HIPCHK(clear(h->dpre[l], 0, h->d[l].Np));
+    }
+    if (grads) HIPCHK(clear(h->dxfake, 0, h->Dp));
     return 0;
 }
 
@@ -856,19 +898,8 @@ int eval_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, cons
     const long cap = 3L * h->S;
     for (long r0 = 0; r0 < n; r0 += cap) {
         const int rows = (int)std::min(cap, n - r0);
-        StageArgs st;
-        memset(&st, 0, sizeof st);
-        StageSeg& sg = st.s[0];
-        sg.src = idx ? x : x + r0 * ld; sg.idx = idx ? idx + r0 : nullptr; sg.ld = ld; sg.rows = rows;
-        sg.cols = h->cfg.d_in; sg.cols_pad = h->Dp; sg.out = selected(h, h->xin[0]); sg.ldo = h->Dp;
-        st.nseg = 1; st.seed = h->cfg.seed; st.cur = h->state + h->cur;
-        PROF("stage_kernel", launch_stage(h->bf16, st, s));
-        for (int l = 0; l < 5; ++l) {
-            // one "segment" of `rows` contiguous rows: batch stride is irrelevant with nb = 1
-            // (a group handle evaluates the selected model: its activations here, its weights in dense_fwd)
-            CHK(dense_fwd(h, h->d[l], KIND_EVAL, selected(h, h->xin[l]), rows, 1, selected(h, l < 4 ? h->xin[l + 1] : h->feat), ACT_RELU, NO_NOISE,
-                          NO_MASK, NO_SUMS, s));
-        }
+        const int r = eval_forward(h, x, idx, ld, r0, rows, false, s);
+        if (r) return r;
         HeadArgs hd = head_args(h, {labels ? HEAD_EVAL : HEAD_LOGITS}, rows, false);
         hd.f = selected(h, hd.f); hd.w = selected(h, hd.w); hd.b = selected(h, hd.b); hd.logits = selected(h, hd.logits);
         hd.labels = labels ? labels + r0 : nullptr;
@@ -878,18 +909,7 @@ int eval_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, cons
             HIPCHK(hipMemcpy2DAsync(logits_out + r0 * h->cfg.num_classes, sizeof(float) * h->cfg.num_classes, selected(h, h->logits),
                                     sizeof(float) * h->KP, sizeof(float) * h->cfg.num_classes, rows, hipMemcpyDeviceToDevice, s));
     }
-    // The evaluation used the training activations as scratch and filled rows [0, 3S) of every layer input, i.e. also the
-    // padding rows B..S of each training segment.  The bf16 weight gradients reduce over all S rows of a segment (zero dY
-    // padding rows x FINITE X padding rows): a non-finite value left there by an evaluation input would turn into NaN
-    // gradients from then on (0 * NaN).  Ragged batches only: re-zero those rows.
-    if (h->B < h->S) {
-        for (int l = 0; l < 5; ++l)
-            for (int sg = 0; sg < (l == 0 ? 5 : 3); ++sg) {
-                char* p = (char*)selected(h, h->xin[l]) + ((size_t)sg * h->S + h->B) * h->d[l].Kp * h->es;
-                HIPCHK(hipMemsetAsync(p, 0, (size_t)(h->S - h->B) * h->d[l].Kp * h->es, s));
-            }
-    }
-    return 0;
+    return rezero_padding(h, 5, 3, false, s);      // the chunks reach rows [0, 3S); xin[0]: all five segments, whatever n
 }
 
 // Input-gradient saliency of n rows (mrgan_input_gradient): per chunk the evaluation forward WITH its relu masks, the per-row
@@ -900,19 +920,10 @@ int eval_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, cons
 int saliency_rows(mrgan_handle* h, const mrgan_saliency_args* a, hipStream_t s) {
     static const int kinds[3] = {HEAD_SAL_LOGIT, HEAD_SAL_XENT, HEAD_SAL_MSE};
     const long cap = h->S, n = a->n;
-    auto mask_of = [&](int l) { return ReluMask{selected(h, h->mask[l]), h->ldm[l]}; };
     for (long r0 = 0; r0 < n; r0 += cap) {
         const int rows = (int)std::min(cap, n - r0);
-        StageArgs st;
-        memset(&st, 0, sizeof st);
-        StageSeg& sg = st.s[0];
-        sg.src = a->idx_dev ? a->x_dev : a->x_dev + r0 * a->ld_x; sg.idx = a->idx_dev ? a->idx_dev + r0 : nullptr; sg.ld = a->ld_x; sg.rows = rows;
-        sg.cols = h->cfg.d_in; sg.cols_pad = h->Dp; sg.out = selected(h, h->xin[0]); sg.ldo = h->Dp;
-        st.nseg = 1; st.seed = h->cfg.seed; st.cur = h->state + h->cur;
-        PROF("stage_kernel", launch_stage(h->bf16, st, s));
-        for (int l = 0; l < 5; ++l)
-            CHK(dense_fwd(h, h->d[l], KIND_EVAL, selected(h, h->xin[l]), rows, 1, selected(h, l < 4 ? h->xin[l + 1] : h->feat), ACT_RELU, NO_NOISE,
-                          mask_of(l), NO_SUMS, s));
+        const int r = eval_forward(h, a->x_dev, a->idx_dev, a->ld_x, r0, rows, true, s);
+        if (r) return r;
         HeadArgs hd = head_args(h, {kinds[a->objective]}, rows, false);
         hd.f = selected(h, hd.f); hd.w = selected(h, hd.w); hd.b = selected(h, hd.b); hd.logits = nullptr;
         hd.labels = a->targets_dev ? a->targets_dev + r0 : nullptr;
@@ -920,7 +931,7 @@ int saliency_rows(mrgan_handle* h, const mrgan_saliency_args* a, hipStream_t s) 
         hd.dpre = selected(h, h->dpre[4]); hd.ldd = h->Fp;
         PROF("head_kernel", launch_head(h->bf16, hd, s));
         for (int l = 4; l >= 1; --l)
-            CHK(dense_dx(h, h->d[l], KIND_EVAL, selected(h, h->dpre[l]), rows, 1, selected(h, h->dpre[l - 1]), ACT_RELU, h->d[l - 1].N, mask_of(l - 1),
+            CHK(dense_dx(h, h->d[l], KIND_EVAL, selected(h, h->dpre[l]), rows, 1, selected(h, h->dpre[l - 1]), ACT_RELU, h->d[l - 1].N, eval_mask(h, l - 1),
                          nullptr, NO_SUMS, s));
         CHK(dense_dx(h, h->d[0], KIND_EVAL, selected(h, h->dpre[0]), rows, 1, selected(h, h->dxfake), ACT_LINEAR, h->cfg.d_in, NO_MASK, nullptr,
                      NO_SUMS, s));
@@ -930,19 +941,7 @@ int saliency_rows(mrgan_handle* h, const mrgan_saliency_args* a, hipStream_t s) 
         f.out = a->out_dev + r0 * a->ld_out; f.ldo = a->ld_out; f.mode = a->post == MRGAN_SAL_HEATMAP ? SAL_HEATMAP : SAL_RAW;
         PROFB("saliency_finish_kernel", launch_saliency_finish(h->bf16, f, s), (double)rows * h->cfg.d_in * (2.0 * h->es + 4.0));
     }
-    // Ragged batches: the chunks filled rows B .. S of segment 0, the padding rows of a training segment.  The bf16 weight
-    // gradients reduce over all S rows and need zero dY -- dpre[l], and dxfake, the dY of the generator's last layer -- and
-    // finite xin there (see eval_rows): re-zero them.  (feat and the masks: every training forward rewrites what its sub-step
-    // reads, and the padding rows of feat meet zero dlogits only.)
-    if (h->B < h->S && n > h->B) {
-        const size_t pad = (size_t)(h->S - h->B);
-        HIPCHK(hipMemsetAsync((char*)selected(h, h->dxfake) + (size_t)h->B * h->Dp * h->es, 0, pad * h->Dp * h->es, s));
-        for (int l = 0; l < 5; ++l) {
-            HIPCHK(hipMemsetAsync((char*)selected(h, h->xin[l]) + (size_t)h->B * h->d[l].Kp * h->es, 0, pad * h->d[l].Kp * h->es, s));
-            HIPCHK(hipMemsetAsync((char*)selected(h, h->dpre[l]) + (size_t)h->B * h->d[l].Np * h->es, 0, pad * h->d[l].Np * h->es, s));
-        }
-    }
-    return 0;
+    return n > h->B ? rezero_padding(h, 1, 1, true, s) : 0;      // (no chunk reached the padding rows of segment 0 otherwise)
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -965,6 +964,41 @@ int fp8_cal_done(mrgan_handle* h, int kind, hipStream_t s) {
     h->fp8_cal[kind] = 1;
     return 0;
 }
+// The first whole sub-step of `kind` on an fp8 handle (phases p0 .. p1 of nphases, starting at 0) calibrates by itself: dry
+// passes over the phases 0 .. dry_last of `phase` (disc_phase / gen_phase; each kind has its own slots: the feature-matching
+// gradient has another scale than the D loss's).
+template <typename Args>
+int fp8_calibrate(mrgan_handle* h, int kind, int p0, int p1, int nphases, int dry_last, int (*phase)(mrgan_handle*, const Args*, int, hipStream_t),
+                  const Args* a, hipStream_t s) {
+    if (!h->fp8 || p0 != 0 || h->fp8_cal[kind]) return 0;
+    if (p1 < nphases - 1 && h->sync_stats)
+        return fail(-3, "fp8 with synchronised statistics: a phase-wise host runs the calibration passes itself (mrgan_fp8_calibration)");
+    CHK(fp8_cal_begin(h, kind, s));
+    for (int i = 0; i < FP8_DRY_PASSES; ++i) {
+        for (int p = 0; p <= dry_last; ++p) { const int r = phase(h, a, p, s); if (r) return r; }
+        CHK(fp8_cal_end_pass(h, kind, s));
+    }
+    CHK(fp8_cal_done(h, kind, s));
+    return 0;
+}
+
+// `count` floats from `offset` of the step_out of each of the first `models` models -> out [models][count], and wait for them
+int read_step_out(mrgan_handle* h, int models, int offset, int count, float* out, hipStream_t s) {
+    for (int m = 0; m < models; ++m)
+        HIPCHK(hipMemcpyAsync(out + (size_t)m * count, model_at(h, h->step_out, m) + offset, count * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+// the supervised step's outputs of `models` models -> out2 [models][2] = loss, training error.  The metrics pass divides by
+// the batch: a short batch (rows_valid) is rescaled here.
+int read_sup_out(mrgan_handle* h, int models, int rows_valid, float* out2, hipStream_t s) {
+    float o[MRGAN_MAX_MODELS][3];
+    const int r = read_step_out(h, models, 0, 3, &o[0][0], s);
+    if (r) return r;
+    const float k = rows_valid > 0 ? (float)h->B / (float)rows_valid : 1.f;
+    for (int m = 0; m < models; ++m) { out2[2 * m] = o[m][0] * k; out2[2 * m + 1] = o[m][2] * k; }
+    return 0;
+}
 
 }  // namespace
 
@@ -977,23 +1011,10 @@ int mrgan_disc_step(mrgan_handle* h, const mrgan_disc_args* a, int p0, int p1, f
     if (r) return r;
     hipStream_t s = (hipStream_t)stream;
     if (p1 < 0) p1 = MRGAN_D_NPHASES - 1;
-    if (h->fp8 && p0 == 0 && !h->fp8_cal[0] && p1 < MRGAN_D_NPHASES - 1 && h->sync_stats)
-        return fail(-3, "fp8 with synchronised statistics: a phase-wise host runs the calibration passes itself (mrgan_fp8_calibration)");
-    if (h->fp8 && p0 == 0 && !h->fp8_cal[0]) {
-        // first D sub-step of an fp8 handle: calibrate with dry passes
-        CHK(fp8_cal_begin(h, 0, s));
-        for (int i = 0; i < FP8_DRY_PASSES; ++i) {
-            for (int p = MRGAN_D_GEN; p <= MRGAN_D_MAIN; ++p) { r = disc_phase(h, a, p, s); if (r) return r; }
-            CHK(fp8_cal_end_pass(h, 0, s));
-        }
-        CHK(fp8_cal_done(h, 0, s));
-    }
+    r = fp8_calibrate(h, 0, p0, p1, MRGAN_D_NPHASES, MRGAN_D_MAIN, disc_phase, a, s);
+    if (r) return r;
     for (int p = p0; p <= p1; ++p) { r = disc_phase(h, a, p, s); if (r) return r; }
-    if (out3) {
-        HIPCHK(hipMemcpyAsync(out3, h->step_out, 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return 0;
+    return out3 ? read_step_out(h, 1, 0, 3, out3, s) : 0;
 }
 
 int mrgan_gen_step(mrgan_handle* h, const mrgan_gen_args* a, int p0, int p1, float* out1, mrgan_stream stream) {
@@ -1003,23 +1024,10 @@ int mrgan_gen_step(mrgan_handle* h, const mrgan_gen_args* a, int p0, int p1, flo
     if (r) return r;
     hipStream_t s = (hipStream_t)stream;
     if (p1 < 0) p1 = MRGAN_G_NPHASES - 1;
-    if (h->fp8 && p0 == 0 && !h->fp8_cal[1] && p1 < MRGAN_G_NPHASES - 1 && h->sync_stats)
-        return fail(-3, "fp8 with synchronised statistics: a phase-wise host runs the calibration passes itself (mrgan_fp8_calibration)");
-    if (h->fp8 && p0 == 0 && !h->fp8_cal[1]) {
-        // same for the G sub-step's tensors (its own slots: the feature-matching gradient has another scale than the D loss's)
-        CHK(fp8_cal_begin(h, 1, s));
-        for (int i = 0; i < FP8_DRY_PASSES; ++i) {
-            for (int p = MRGAN_G_GEN; p <= MRGAN_G_BWD; ++p) { r = gen_phase(h, a, p, s); if (r) return r; }
-            CHK(fp8_cal_end_pass(h, 1, s));
-        }
-        CHK(fp8_cal_done(h, 1, s));
-    }
+    r = fp8_calibrate(h, 1, p0, p1, MRGAN_G_NPHASES, MRGAN_G_BWD, gen_phase, a, s);
+    if (r) return r;
     for (int p = p0; p <= p1; ++p) { r = gen_phase(h, a, p, s); if (r) return r; }
-    if (out1) {
-        HIPCHK(hipMemcpyAsync(out1, h->step_out + 3, sizeof(float), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return 0;
+    return out1 ? read_step_out(h, 1, 3, 1, out1, s) : 0;
 }
 
 int mrgan_fp8_calibration(mrgan_handle* h, int kind, int action, mrgan_stream stream) {
@@ -1049,43 +1057,24 @@ int mrgan_logmel(const float* y_dev, int64_t n_trials, int64_t n_samples, int64_
 int mrgan_sup_step(mrgan_handle* h, const mrgan_sup_args* a, float* out2, mrgan_stream stream) {
     if (!h || !a || !a->x_dev || !a->labels_dev) return fail(-1, "sup_step: x and labels are required");
     if (refuse_group(h, "sup_step")) return -3;
-    if (a->ld_x < h->cfg.d_in) return fail(-2, "sup_step: row pitch smaller than d_in");
-    if (h->flat_grads || h->cfg.world != 1) return fail(-3, "sup_step: single-GPU handles only");
-    if (h->fp8) return fail(-3, "sup_step: the fp8 mode covers the GAN step only");
-    if (a->rows_valid < 0 || a->rows_valid > h->B) return fail(-2, "sup_step: rows_valid outside [0, batch]");
-    if (a->rows_valid && a->stream_mode) return fail(-2, "sup_step: a short batch cannot be combined with stream mode");
-    hipStream_t s = (hipStream_t)stream;
-    int r = sup_step(h, a, s);
+    int r = check_sup_args(h, *a, "sup_step");
     if (r) return r;
-    if (out2) {
-        float o[3];
-        HIPCHK(hipMemcpyAsync(o, h->step_out, 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        const float k = a->rows_valid > 0 ? (float)h->B / (float)a->rows_valid : 1.f;     // the metrics pass divides by the batch
-        out2[0] = o[0] * k; out2[1] = o[2] * k;
-    }
-    return 0;
+    hipStream_t s = (hipStream_t)stream;
+    r = sup_step(h, a, s);
+    if (r) return r;
+    return out2 ? read_sup_out(h, 1, a->rows_valid, out2, s) : 0;
 }
 
 int mrgan_sup_step_group(mrgan_handle* h, const mrgan_sup_group_args* a, float* out2, mrgan_stream stream) {
     if (!h || !a || !a->x_dev || !a->labels_dev) return fail(-1, "sup_step_group: x and labels are required");
     if (h->models <= 1) return fail(-3, "sup_step_group: not a group handle (mrgan_config.models = %d); a single model steps through mrgan_sup_step", (int)h->cfg.models);
-    if (a->ld_x < h->cfg.d_in) return fail(-2, "sup_step_group: row pitch smaller than d_in");
-    if (a->rows_valid < 0 || a->rows_valid > h->B) return fail(-2, "sup_step_group: rows_valid outside [0, batch]");
-    if (a->rows_valid && a->stream_mode) return fail(-2, "sup_step_group: a short batch cannot be combined with stream mode");
+    int r = check_sup_args(h, single_args(a), "sup_step_group");
+    if (r) return r;
     if (a->x_model_stride < 0 || a->idx_model_stride < 0 || a->labels_model_stride < 0) return fail(-2, "sup_step_group: negative model stride");
     hipStream_t s = (hipStream_t)stream;
-    int r = sup_step_group(h, a, s);
+    r = sup_step_group(h, a, s);
     if (r) return r;
-    if (out2) {
-        float o[MRGAN_MAX_MODELS][3];
-        for (int m = 0; m < h->models; ++m)
-            HIPCHK(hipMemcpyAsync(o[m], model_at(h, h->step_out, m), 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        const float k = a->rows_valid > 0 ? (float)h->B / (float)a->rows_valid : 1.f;     // the metrics pass divides by the batch
-        for (int m = 0; m < h->models; ++m) { out2[2 * m] = o[m][0] * k; out2[2 * m + 1] = o[m][2] * k; }
-    }
-    return 0;
+    return out2 ? read_sup_out(h, h->models, a->rows_valid, out2, s) : 0;
 }
 
 int mrgan_train_pair(mrgan_handle* h, const mrgan_disc_args* d, const mrgan_gen_args* g, mrgan_stream stream) {
@@ -1121,12 +1110,7 @@ int mrgan_disc_step_group(mrgan_handle* h, const mrgan_disc_group_args* a, float
     hipStream_t s = (hipStream_t)stream;
     r = disc_step_group(h, a, s);
     if (r) return r;
-    if (out3) {
-        for (int m = 0; m < h->models; ++m)
-            HIPCHK(hipMemcpyAsync(out3 + 3 * m, model_at(h, h->step_out, m), 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return 0;
+    return out3 ? read_step_out(h, h->models, 0, 3, out3, s) : 0;
 }
 
 int mrgan_gen_step_group(mrgan_handle* h, const mrgan_gen_group_args* a, float* out1, mrgan_stream stream) {
@@ -1137,12 +1121,7 @@ int mrgan_gen_step_group(mrgan_handle* h, const mrgan_gen_group_args* a, float* 
     hipStream_t s = (hipStream_t)stream;
     r = gen_step_group(h, a, s);
     if (r) return r;
-    if (out1) {
-        for (int m = 0; m < h->models; ++m)
-            HIPCHK(hipMemcpyAsync(out1 + m, model_at(h, h->step_out, m) + 3, sizeof(float), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return 0;
+    return out1 ? read_step_out(h, h->models, 3, 1, out1, s) : 0;
 }
 
 int mrgan_train_pair_group(mrgan_handle* h, const mrgan_disc_group_args* d, const mrgan_gen_group_args* g, mrgan_stream stream) {

@@ -95,8 +95,8 @@ struct mrgan_handle {
     size_t W;                             // model stride in bytes
     int sel;                              // mrgan_select_model: the model the per-model entries address
     int grouped;                          // models while a grouped step builds its launches (every launch covers all models), else 1
-    // element strides between the models' inputs of the grouped GAN sub-step being built (mrgan_disc_group_args /
-    // mrgan_gen_group_args); all zero outside one
+    // element strides between the models' inputs of the grouped step being built (mrgan_disc_group_args / mrgan_gen_group_args;
+    // mrgan_sup_group_args: its x, idx and labels in the labelled slots); all zero outside one
     struct GroupStrides { long x_lab, idx_lab, labels, x_unl, idx_unl, z; } gs;
 
     std::vector<Tensor> gt, dt;           // Keras order

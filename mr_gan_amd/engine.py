@@ -202,6 +202,38 @@ def exchange_regions(region, grad_dtype, which):
     return (region(which),)
 
 
+# What a single handle's argument struct and its group twin share.  The row pitch is that of the matrix itself, whether it
+# is stacked [models, rows, D] or not; the structs hold raw pointers, so _refs keeps the tensors alive.
+def _fill_disc(a, x_lab, labels, x_unl, z, idx_lab, idx_unl, stream_mode):
+    a.x_lab, a.idx_lab, a.labels = _ptr(x_lab), _ptr(idx_lab), _ptr(labels)
+    a.x_unl, a.idx_unl, a.z = _ptr(x_unl), _ptr(idx_unl), _ptr(z)
+    a.ld_x_lab, a.ld_x_unl = x_lab.stride(-2), x_unl.stride(-2)
+    a.stream_mode = stream_mode
+    a._refs = (x_lab, labels, x_unl, z, idx_lab, idx_unl)
+    return a
+
+
+def _fill_gen(a, x_unl, z, idx_unl, stream_mode):
+    a.x_unl, a.idx_unl, a.z = _ptr(x_unl), _ptr(idx_unl), _ptr(z)
+    a.ld_x_unl = x_unl.stride(-2)
+    a.stream_mode = stream_mode
+    a._refs = (x_unl, z, idx_unl)
+    return a
+
+
+def _fill_sup(a, x, labels, idx, stream_mode, rows_valid):
+    a.x, a.idx, a.labels = _ptr(x), _ptr(idx), _ptr(labels)
+    a.ld_x = x.stride(-2)
+    a.stream_mode, a.rows_valid = stream_mode, rows_valid
+    a._refs = (x, labels, idx)
+    return a
+
+
+def _model_stride(t, stacked_dim):
+    """elements between the models' parts of a tensor stacked [models, ...] (stacked_dim dimensions); 0: one tensor for all"""
+    return t.stride(0) if t is not None and t.dim() == stacked_dim else 0
+
+
 class Engine(object):
     """One handle = the Keras shared state of one mr_gan() call (weights, Adam slots, iteration counter)
     plus the three compiled functions of mr_gan.py:169-171."""
@@ -297,22 +329,11 @@ class Engine(object):
     # ---- the compiled functions -------------------------------------------------------------------------
     @staticmethod
     def disc_args(x_lab, labels, x_unl, z=None, idx_lab=None, idx_unl=None, stream_mode=0):
-        a = DiscArgs()
-        a.x_lab, a.idx_lab, a.labels = _ptr(x_lab), _ptr(idx_lab), _ptr(labels)
-        a.x_unl, a.idx_unl, a.z = _ptr(x_unl), _ptr(idx_unl), _ptr(z)
-        a.ld_x_lab, a.ld_x_unl = x_lab.stride(0), x_unl.stride(0)
-        a.stream_mode = stream_mode
-        a._refs = (x_lab, labels, x_unl, z, idx_lab, idx_unl)    # the struct holds raw pointers: keep the tensors alive
-        return a
+        return _fill_disc(DiscArgs(), x_lab, labels, x_unl, z, idx_lab, idx_unl, stream_mode)
 
     @staticmethod
     def gen_args(x_unl, z=None, idx_unl=None, stream_mode=0):
-        a = GenArgs()
-        a.x_unl, a.idx_unl, a.z = _ptr(x_unl), _ptr(idx_unl), _ptr(z)
-        a.ld_x_unl = x_unl.stride(0)
-        a.stream_mode = stream_mode
-        a._refs = (x_unl, z, idx_unl)
-        return a
+        return _fill_gen(GenArgs(), x_unl, z, idx_unl, stream_mode)
 
     def disc_step(self, args, first=0, last=-1, want_outputs=True):
         """train_batch_disc -> (loss_lab, loss_unl, train_err)"""
@@ -328,13 +349,7 @@ class Engine(object):
 
     @staticmethod
     def sup_args(x, labels, idx=None, stream_mode=0, rows_valid=0):
-        a = SupArgs()
-        a.x, a.idx, a.labels = _ptr(x), _ptr(idx), _ptr(labels)
-        a.ld_x = x.stride(0)
-        a.stream_mode = stream_mode
-        a.rows_valid = rows_valid
-        a._refs = (x, labels, idx)
-        return a
+        return _fill_sup(SupArgs(), x, labels, idx, stream_mode, rows_valid)
 
     def sup_step(self, args, want_outputs=True):
         """one supervised train_on_batch of the NN baseline (mr_nn.py:117) -> (mse loss, training error of the batch)"""
@@ -356,14 +371,10 @@ class Engine(object):
                        labels_model_stride=None):
         """x [models, rows, D] (or [rows, D] with x_model_stride = 0: one matrix, gathered through idx [models, n]); labels
         [models, n].  The strides default to those of the tensors' first dimension."""
-        a = SupGroupArgs()
-        a.x, a.idx, a.labels = _ptr(x), _ptr(idx), _ptr(labels)
-        a.ld_x = x.stride(-2)
-        a.x_model_stride = (x.stride(0) if x.dim() == 3 else 0) if x_model_stride is None else x_model_stride
-        a.idx_model_stride = (idx.stride(0) if idx is not None and idx.dim() == 2 else 0) if idx_model_stride is None else idx_model_stride
-        a.labels_model_stride = (labels.stride(0) if labels.dim() == 2 else 0) if labels_model_stride is None else labels_model_stride
-        a.stream_mode, a.rows_valid = stream_mode, rows_valid
-        a._refs = (x, labels, idx)
+        a = _fill_sup(SupGroupArgs(), x, labels, idx, stream_mode, rows_valid)
+        a.x_model_stride = _model_stride(x, 3) if x_model_stride is None else x_model_stride
+        a.idx_model_stride = _model_stride(idx, 2) if idx_model_stride is None else idx_model_stride
+        a.labels_model_stride = _model_stride(labels, 2) if labels_model_stride is None else labels_model_stride
         return a
 
     def sup_step_group(self, args, want_outputs=True):
@@ -374,33 +385,19 @@ class Engine(object):
 
     # the GAN sub-steps of a group handle: stacked [models, ...] tensors, strides derived as in sup_group_args
     @staticmethod
-    def _model_stride(t, stacked_dim):
-        return t.stride(0) if t is not None and t.dim() == stacked_dim else 0
-
-    @staticmethod
     def disc_group_args(x_lab, labels, x_unl, z=None, idx_lab=None, idx_unl=None, stream_mode=0):
         """x_lab / x_unl [models, rows, D] (or [rows, D]: one matrix every model gathers from through its idx_* [models, n]);
         labels [models, n]; z [models, n, noise] or None (model m draws z on the device with seed + m)"""
-        a = DiscGroupArgs()
-        a.x_lab, a.idx_lab, a.labels = _ptr(x_lab), _ptr(idx_lab), _ptr(labels)
-        a.x_unl, a.idx_unl, a.z = _ptr(x_unl), _ptr(idx_unl), _ptr(z)
-        a.ld_x_lab, a.ld_x_unl = x_lab.stride(-2), x_unl.stride(-2)
-        ms = Engine._model_stride
+        a = _fill_disc(DiscGroupArgs(), x_lab, labels, x_unl, z, idx_lab, idx_unl, stream_mode)
+        ms = _model_stride
         a.x_lab_model_stride, a.idx_lab_model_stride, a.labels_model_stride = ms(x_lab, 3), ms(idx_lab, 2), ms(labels, 2)
         a.x_unl_model_stride, a.idx_unl_model_stride, a.z_model_stride = ms(x_unl, 3), ms(idx_unl, 2), ms(z, 3)
-        a.stream_mode = stream_mode
-        a._refs = (x_lab, labels, x_unl, z, idx_lab, idx_unl)
         return a
 
     @staticmethod
     def gen_group_args(x_unl, z=None, idx_unl=None, stream_mode=0):
-        a = GenGroupArgs()
-        a.x_unl, a.idx_unl, a.z = _ptr(x_unl), _ptr(idx_unl), _ptr(z)
-        a.ld_x_unl = x_unl.stride(-2)
-        ms = Engine._model_stride
-        a.x_unl_model_stride, a.idx_unl_model_stride, a.z_model_stride = ms(x_unl, 3), ms(idx_unl, 2), ms(z, 3)
-        a.stream_mode = stream_mode
-        a._refs = (x_unl, z, idx_unl)
+        a = _fill_gen(GenGroupArgs(), x_unl, z, idx_unl, stream_mode)
+        a.x_unl_model_stride, a.idx_unl_model_stride, a.z_model_stride = _model_stride(x_unl, 3), _model_stride(idx_unl, 2), _model_stride(z, 3)
         return a
 
     def disc_step_group(self, args, want_outputs=True):

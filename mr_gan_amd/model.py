@@ -23,6 +23,37 @@ def glorot_uniform(rng, fan_in, fan_out):
     return rng.uniform(-lim, lim, size=(fan_in, fan_out)).astype(np.float32)
 
 
+DTYPES = {'float32': E.F32, 'fp32': E.F32, 'bfloat16': E.BF16, 'bf16': E.BF16, 'fp8': E.FP8, 'float8': E.FP8}
+
+
+def gan_config(input_dim, batch_size, dtype, seed, num_classes, noise_size, g_hidden, d_hidden, lr, beta_1, unlabeled_weight,
+               use_graph, flags, noise, models=0, rank=0, world=1):
+    """the mrgan_config of MRGAN (models = 0) and MRGANGroup (model m draws what a handle with seed + m draws)"""
+    cfg = E.default_config(input_dim, batch_size)
+    cfg.dtype = DTYPES[dtype]
+    cfg.num_classes, cfg.noise_size = num_classes, noise_size
+    cfg.g_hidden[0], cfg.g_hidden[1] = g_hidden
+    for i, w in enumerate(d_hidden):
+        cfg.d_hidden[i] = w
+    cfg.lr, cfg.beta1, cfg.unlabeled_weight = lr, beta_1, unlabeled_weight
+    cfg.seed = seed
+    cfg.rank, cfg.world = rank, world
+    if models:
+        cfg.models = models
+    cfg.flags = flags | (E.FLAG_GRAPH if use_graph else 0) | E.noise_flags(noise)
+    return cfg
+
+
+def epoch_streams(rng, n_lab, n_train, n_pool=None):
+    """One epoch's index streams, drawn from rng in the reference's order (the draws and their order are part of the results):
+    the labelled tiling (mr_gan.py:189), then three unlabelled permutations (:193-195; the third is unused) or, with a table-6
+    pool of n_pool rows, three tilings of it (:197-202) -> (inds, [unl, unl2, unused])"""
+    inds = tiled_permutation(rng, n_lab, n_train)
+    if n_pool is None:
+        return inds, [rng.permutation(n_train).astype(np.int32) for _ in range(3)]
+    return inds, [tiled_permutation(rng, n_pool, n_train) for _ in range(3)]
+
+
 class MRGAN(object):
     """Feature-matching semi-supervised GAN of mr_gan.py on one MI355X.
 
@@ -38,18 +69,9 @@ class MRGAN(object):
         self.input_dim = int(input_dim)
         self.batch_size = int(batch_size)
         self.seed = int(np.random.randint(1 << 31)) if seed is None else int(seed)   # mr_gan.py:75 is unseeded
-        cfg = E.default_config(self.input_dim, self.batch_size)
-        cfg.dtype = {'float32': E.F32, 'fp32': E.F32, 'bfloat16': E.BF16, 'bf16': E.BF16, 'fp8': E.FP8, 'float8': E.FP8}[dtype]
-        cfg.num_classes, cfg.noise_size = num_classes, noise_size
-        cfg.g_hidden[0], cfg.g_hidden[1] = g_hidden
-        for i, w in enumerate(d_hidden):
-            cfg.d_hidden[i] = w
-        cfg.lr, cfg.beta1, cfg.unlabeled_weight = lr, beta_1, unlabeled_weight
-        cfg.seed = self.seed
-        cfg.rank, cfg.world = rank, world
-        cfg.flags = flags | (E.FLAG_GRAPH if use_graph else 0) | E.noise_flags(noise)
-        self.cfg = cfg
-        self.engine = E.Engine(cfg, device)
+        self.cfg = gan_config(self.input_dim, self.batch_size, dtype, self.seed, num_classes, noise_size, g_hidden, d_hidden, lr, beta_1,
+                              unlabeled_weight, use_graph, flags, noise, rank=rank, world=world)
+        self.engine = E.Engine(self.cfg, device)
         self.device = self.engine.device
         # a private HIP stream: graph capture is not permitted on the legacy default stream
         self.stream = torch.cuda.Stream(self.device)
@@ -115,7 +137,7 @@ class MRGAN(object):
         gradient of `objective` -- 'xent' (the labelled loss term), 'logit' (the class score) or 'mse' -- at class y[i], or at
         the predicted class when y is None, with respect to the input; heatmap: |g / (rms(g) + 1e-5)| min-max scaled to [0, 1]
         per row (a zero gradient gives a zero row), else the raw gradient.  -> (maps [n, D] float32, classes [n] int32)"""
-        code = E.saliency_objective(objective)
+        code = E.saliency_objective(objective)                     # (checked before anything touches the device)
         with self._on_stream():
             maps, cls = self.engine.input_gradient(self._dev(X), None if y is None else self._dev(y, torch.int32), code,
                                                    E.SAL_HEATMAP if heatmap else E.SAL_RAW)
@@ -169,13 +191,8 @@ class MRGAN(object):
             xt, yt = self._dev(validation_data[0]), self._dev(validation_data[1], torch.int32)
         for epoch in range(1, epochs + 1):
             begin = time.time()
-            inds = tiled_permutation(rng, n_lab, n_train)          # mr_gan.py:189
-            if pool is None:
-                unl = [rng.permutation(n_train).astype(np.int32) for _ in range(3)]      # :193-195 (third is unused)
-                unl_src = xu
-            else:
-                unl = [tiled_permutation(rng, pool.shape[0], n_train) for _ in range(3)]  # :197-202
-                unl_src = pool
+            inds, unl = epoch_streams(rng, n_lab, n_train, None if pool is None else pool.shape[0])
+            unl_src = xu if pool is None else pool
             idx_lab = self._dev(inds, torch.int32)
             lab_stream = self._dev(yl[inds], torch.int32)
             idx_unl = self._dev(unl[0], torch.int32)
@@ -226,18 +243,9 @@ class MRGANGroup(object):
         if dtype in ('fp8', 'float8'):
             raise ValueError("a model group cannot be an fp8 handle")
         self.seed = int(np.random.randint(1 << 31)) if seed is None else int(seed)
-        cfg = E.default_config(self.input_dim, self.batch_size)
-        cfg.dtype = {'float32': E.F32, 'fp32': E.F32, 'bfloat16': E.BF16, 'bf16': E.BF16}[dtype]
-        cfg.num_classes, cfg.noise_size = num_classes, noise_size
-        cfg.g_hidden[0], cfg.g_hidden[1] = g_hidden
-        for i, w in enumerate(d_hidden):
-            cfg.d_hidden[i] = w
-        cfg.lr, cfg.beta1, cfg.unlabeled_weight = lr, beta_1, unlabeled_weight
-        cfg.seed = self.seed                                       # model m draws what a handle with seed + m draws
-        cfg.models = self.models
-        cfg.flags = flags | (E.FLAG_GRAPH if use_graph else 0) | E.noise_flags(noise)
-        self.cfg = cfg
-        self.engine = E.Engine(cfg, device)
+        self.cfg = gan_config(self.input_dim, self.batch_size, dtype, self.seed, num_classes, noise_size, g_hidden, d_hidden, lr, beta_1,
+                              unlabeled_weight, use_graph, flags, noise, models=self.models)
+        self.engine = E.Engine(self.cfg, device)
         self.device = self.engine.device
         self.stream = torch.cuda.Stream(self.device)               # (graph capture is not permitted on the legacy default stream)
         self.iterations = 0
@@ -281,13 +289,8 @@ class MRGANGroup(object):
         unl_src = xu if pool is None else pool
         for epoch in range(1, epochs + 1):
             begin = time.time()
-            inds, unl = [], []
-            for m in range(G):                                     # model m: the draws of MRGAN._fit, in its order, from rngs[m]
-                inds.append(tiled_permutation(rngs[m], n_lab, n_train))
-                if pool is None:
-                    unl.append([rngs[m].permutation(n_train).astype(np.int32) for _ in range(3)])
-                else:
-                    unl.append([tiled_permutation(rngs[m], pool.shape[1], n_train) for _ in range(3)])
+            # model m: the draws of MRGAN._fit, from rngs[m]
+            inds, unl = zip(*[epoch_streams(rngs[m], n_lab, n_train, None if pool is None else pool.shape[1]) for m in range(G)])
             idx_lab = self._dev(np.stack(inds), torch.int32)
             lab_stream = self._dev(np.stack([yl[m][inds[m]] for m in range(G)]), torch.int32)
             idx_unl = self._dev(np.stack([u[0] for u in unl]), torch.int32)
@@ -327,12 +330,9 @@ class MRGANGroup(object):
 
     def saliency(self, m, X, y=None, objective='xent', heatmap=True):
         """MRGAN.saliency of model m"""
-        code = E.saliency_objective(objective)
-        with self._on_stream():
-            self.engine.select_model(m)
-            maps, cls = self.engine.input_gradient(self._dev(X), None if y is None else self._dev(y, torch.int32), code,
-                                                   E.SAL_HEATMAP if heatmap else E.SAL_RAW)
-            return maps.cpu().numpy(), cls.cpu().numpy()
+        E.saliency_objective(objective)                            # (an unknown one is refused before the selection moves)
+        self.engine.select_model(m)
+        return MRGAN.saliency(self, X, y, objective, heatmap)
 
     def evaluate(self, Xs, ys):
         """[test error of model m over (Xs[m], ys[m])], model by model"""

@@ -17,11 +17,36 @@ import torch
 
 from mr_gan_amd import engine as E
 from mr_gan_amd.data import resolve_num_classes, select_labeled, standard_scale
-from mr_gan_amd.model import glorot_uniform
+from mr_gan_amd.model import MRGAN, glorot_uniform
 from mr_gan_amd.mr_gan import dataset
 from mr_gan_amd.mr_svm import baseline_tables
 
 NN_LR, NN_BETA_1 = 0.001, 0.9              # Keras-2.0.9 Adam defaults (mr_nn.py:112 optimizer='adam')
+
+
+def nn_config(input_dim, batch_size, dtype, seed, num_classes, d_hidden, lr, beta_1, noise, models=0):
+    """the mrgan_config of MRNN (models = 0) and MRNNGroup (model m draws what a handle with seed + m draws)"""
+    cfg = E.default_config(input_dim, batch_size)
+    cfg.dtype = {'float32': E.F32, 'fp32': E.F32, 'bfloat16': E.BF16, 'bf16': E.BF16}[dtype]      # (fp8 covers the GAN step only)
+    cfg.num_classes = num_classes
+    for i, w in enumerate(d_hidden):
+        cfg.d_hidden[i] = w
+    cfg.lr, cfg.beta1 = lr, beta_1
+    cfg.seed = seed
+    if models:
+        cfg.models = models
+    cfg.flags |= E.noise_flags(noise)                              # the GaussianNoise layers' generator (engine.noise_flags)
+    return cfg
+
+
+def init_discriminator(engine, seed):
+    """Keras defaults for the (selected model's) discriminator stack: kernels glorot_uniform from RandomState(seed), biases zero"""
+    rng = np.random.RandomState(seed)
+    ws = []
+    for i in range(engine.num_tensors(E.NET_D)):
+        shp = engine.full_shape(E.NET_D, i)
+        ws.append(glorot_uniform(rng, shp[0], shp[1]) if len(shp) == 2 else np.zeros(shp, np.float32))
+    engine.set_weights(E.NET_D, ws)
 
 
 class MRNN(object):
@@ -31,29 +56,19 @@ class MRNN(object):
                  d_hidden=(1000, 500, 250, 250, 250), lr=NN_LR, beta_1=NN_BETA_1, init_weights=True, noise='irwin-hall'):
         self.input_dim, self.batch_size = int(input_dim), int(batch_size)
         self.seed = int(np.random.randint(1 << 31)) if seed is None else int(seed)      # mr_nn.py:71 is unseeded
-        cfg = E.default_config(self.input_dim, self.batch_size)
-        cfg.dtype = {'float32': E.F32, 'fp32': E.F32, 'bfloat16': E.BF16, 'bf16': E.BF16}[dtype]
-        cfg.num_classes = num_classes
-        for i, w in enumerate(d_hidden):
-            cfg.d_hidden[i] = w
-        cfg.lr, cfg.beta1 = lr, beta_1
-        cfg.seed = self.seed
-        cfg.flags |= E.noise_flags(noise)                          # the GaussianNoise layers' generator (engine.noise_flags)
-        self.engine = E.Engine(cfg, device)
+        self.engine = E.Engine(nn_config(self.input_dim, self.batch_size, dtype, self.seed, num_classes, d_hidden, lr, beta_1, noise), device)
         self.device = self.engine.device
         self.stream = torch.cuda.Stream(self.device)
         if init_weights:
-            rng = np.random.RandomState(self.seed)
-            ws = []
-            for i in range(self.engine.num_tensors(E.NET_D)):
-                shp = self.engine.full_shape(E.NET_D, i)
-                ws.append(glorot_uniform(rng, shp[0], shp[1]) if len(shp) == 2 else np.zeros(shp, np.float32))
-            self.engine.set_weights(E.NET_D, ws)
+            init_discriminator(self.engine, self.seed)
 
     def _dev(self, a, dtype=torch.float32):
         if isinstance(a, torch.Tensor):
             return a.to(device=self.device, dtype=dtype).contiguous()
         return torch.from_numpy(np.ascontiguousarray(a)).to(device=self.device, dtype=dtype).contiguous()
+
+    def _on_stream(self):
+        return torch.cuda.stream(self.stream)
 
     def train_on_batch(self, x, labels):
         """one batch of at most batch_size rows -> (mse, training error)"""
@@ -104,11 +119,7 @@ class MRNN(object):
     def saliency(self, X, y=None, objective='mse', heatmap=True):
         """MRGAN.saliency for the baseline; the default objective is its training loss, as in the reference's
         others/mr_nn_activation_map.py -> (maps [n, D] float32, classes [n] int32)"""
-        code = E.saliency_objective(objective)
-        with torch.cuda.stream(self.stream):
-            maps, cls = self.engine.input_gradient(self._dev(X), None if y is None else self._dev(y, torch.int32), code,
-                                                   E.SAL_HEATMAP if heatmap else E.SAL_RAW)
-            return maps.cpu().numpy(), cls.cpu().numpy()
+        return MRGAN.saliency(self, X, y, objective, heatmap)
 
 
 class MRNNGroup(object):
@@ -122,27 +133,14 @@ class MRNNGroup(object):
         if not 2 <= self.models <= E.MAX_MODELS:
             raise ValueError("a model group has 2 .. %d models, got %d (one model: MRNN)" % (E.MAX_MODELS, self.models))
         self.seed = int(np.random.randint(1 << 31)) if seed is None else int(seed)
-        cfg = E.default_config(self.input_dim, self.batch_size)
-        cfg.dtype = {'float32': E.F32, 'fp32': E.F32, 'bfloat16': E.BF16, 'bf16': E.BF16}[dtype]
-        cfg.num_classes = num_classes
-        for i, w in enumerate(d_hidden):
-            cfg.d_hidden[i] = w
-        cfg.lr, cfg.beta1 = lr, beta_1
-        cfg.seed = self.seed                                       # model m draws what a handle with seed + m draws
-        cfg.models = self.models
-        cfg.flags |= E.noise_flags(noise)
-        self.engine = E.Engine(cfg, device)
+        self.engine = E.Engine(nn_config(self.input_dim, self.batch_size, dtype, self.seed, num_classes, d_hidden, lr, beta_1, noise,
+                                         models=self.models), device)
         self.device = self.engine.device
         self.stream = torch.cuda.Stream(self.device)
         if init_weights:
             for m in range(self.models):
-                rng = np.random.RandomState(self.seed + m)
-                ws = []
-                for i in range(self.engine.num_tensors(E.NET_D)):
-                    shp = self.engine.full_shape(E.NET_D, i)
-                    ws.append(glorot_uniform(rng, shp[0], shp[1]) if len(shp) == 2 else np.zeros(shp, np.float32))
                 self.engine.select_model(m)
-                self.engine.set_weights(E.NET_D, ws)
+                init_discriminator(self.engine, self.seed + m)
             self.engine.select_model(0)
 
     _dev = MRNN._dev

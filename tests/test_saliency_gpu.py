@@ -210,6 +210,73 @@ def test_training_is_undisturbed_by_saliency_calls():
     _assert_same_state(*states)
 
 
+def _assert_finite_state(a):
+    assert all(np.isfinite(x).all() for x in a[0]) and np.isfinite(np.asarray(a[2], np.float32)).all()
+
+
+def test_training_is_undisturbed_by_evaluation_calls():
+    """predict_logits / eval_error use the training activations as scratch.  A ragged batch (B = 50, S = 128) of a bf16 handle
+    reduces its weight gradients over all S rows of a segment, zero dY x the padding rows of X: NaN rows (3 S + 7 of them: two
+    chunks, every padding row of every segment) in front of every step must leave no trace.  Only a non-finite value shows a
+    missing re-zero (0 x NaN); a large finite one meets exact zeros."""
+    D = 16
+    case = Case(D=D, B=B, steps=2, device_z=True)
+    n = 3 * 128 + 7
+    nan = torch.full((n, D), float("nan"), device=P.DEV)
+    labels = P.to_dev(np.arange(n) % 6, torch.int32)
+    states = []
+    for disturb in (False, True):
+        eng = P.engine(D, B, E.BF16)
+        P.load(eng, case)
+        for t in range(case.steps):
+            if disturb:
+                assert eng.predict_logits(nan).shape == (n, 6)
+                eng.eval_error(nan, labels)
+            eng.disc_step(P.disc_args(case, t, True))
+            eng.gen_step(P.gen_args(case, t, True))
+        states.append(_state(eng))
+        eng.close()
+    assert states[0][1] == 2 * case.steps
+    _assert_finite_state(states[0])
+    _assert_same_state(*states)
+
+
+def test_group_training_is_undisturbed_by_evaluation_calls():
+    """the same on a group handle of two models: NaN rows evaluated on model 1 between two grouped (D, G) steps; both models'
+    states equal the undisturbed group's"""
+    D, G = 16, 2
+    cases = [Case(D=D, B=B, steps=2, seed=7 + m, device_z=True) for m in range(G)]
+    n = 3 * 128 + 7
+    nan = torch.full((n, D), float("nan"), device=P.DEV)
+    labels = P.to_dev(np.arange(n) % 6, torch.int32)
+    states = []
+    for disturb in (False, True):
+        eng = P.engine(D, B, E.BF16, models=G)
+        for m, case in enumerate(cases):
+            eng.select_model(m)
+            P.load(eng, case)
+        for t in range(cases[0].steps):
+            if disturb and t == 1:
+                eng.select_model(1)
+                assert eng.predict_logits(nan).shape == (n, 6)
+                eng.eval_error(nan, labels)
+            eng.disc_step_group(E.Engine.disc_group_args(P.to_dev(np.stack([c.x_lab[t] for c in cases])),
+                                                         P.to_dev(np.stack([c.labels[t] for c in cases]), torch.int32),
+                                                         P.to_dev(np.stack([c.x_unl[t] for c in cases]))))
+            eng.gen_step_group(E.Engine.gen_group_args(P.to_dev(np.stack([c.x_unl2[t] for c in cases]))))
+        per_model = []
+        for m in range(G):
+            eng.select_model(m)
+            per_model.append(_state(eng))
+        states.append(per_model)
+        eng.close()
+    for m in range(G):
+        assert states[0][m][1] == 2 * cases[0].steps
+        _assert_finite_state(states[0][m])
+        _assert_same_state(states[0][m], states[1][m])
+    assert not np.array_equal(states[0][0][0][0], states[0][1][0][0])      # (the models differ from each other)
+
+
 def test_graph_replay_is_undisturbed_by_saliency_calls():
     from mr_gan_amd import MRGAN
     D, n = 400, 4 * B
