@@ -207,6 +207,50 @@ typedef struct mrgan_debug_fm_desc {
 } mrgan_debug_fm_desc;
 int mrgan_debug_fm(const mrgan_debug_fm_desc* d, mrgan_stream stream);
 
+/* ---- one launch of the row-block chain kernel (csrc/chain.h: ChainArgs / ChainOp, which document the fields) through
+ * launch_chain.  variant: 0 = D tail [F F F H X X X], 1 = G forward [F F F], 2 = G backward [fm X X X]; the products a variant
+ * does not run are ignored.  Every data buffer is the caller's device memory (bf16 activations and weights, fp32 bias / cs /
+ * head and fm tensors, uint16 mask words); nothing is converted or cleared, the entry allocates only the DevState that carries
+ * iter / batch, and it synchronises the stream.  W is [N][K] with pitch K exactly (rows beyond N read as zeros); rows [n_valid, N)
+ * of a forward W are the caller's zeros.  head.dtype / f / logits / q8* and fm.dtype / mask / rows / q8* / lscratch / lcount are
+ * not read.  Model m's tensors lie model_stride bytes behind model 0's (head: head.model_stride, labels head.labels_ms elements).
+ * Written, per model (nrb = ceil(rows / block_rows), npass = ceil(N / 256)) -- and nothing else:
+ *   out of a product    out[seg][r][0 .. N) for r < rows (16 bytes at a time); forward columns >= n_valid are zeros
+ *   mask of a FORWARD product   words [seg][0 .. ceil(rows / 32))[0 .. N)[2]; the bits of rows >= `rows` in a ragged 32-row
+ *                       group are unspecified (those rows carry relu(bias) + noise inside the block).  A dX mask is only read
+ *                       (D tail: dx[2].mask alone; dx[0] / dx[1] follow the words fwd[1] / fwd[0] keep in registers)
+ *   cs of a product     cs[seg * nrb + rb][0 .. min(256 npass, ldcs)): the column sums of the kept, unrounded values over the
+ *                       block's valid rows (forward: before the noise), zeros from column N on
+ *   head (D tail)       dpre[seg][r][0 .. feat) for r < rows (zeros from feat_valid on); per block blk = seg * nrb + rb:
+ *                       loss_part[blk][0 .. 4), part[blk][0 .. feat * 8) = dW6, [off_db .. + 8) = db6, [off_dbf .. + feat) = the
+ *                       feature layer's bias gradient
+ *   fm (G backward)     fm.dpre[r][0 .. feat) for r < rows (every segment the same rows), *loss_out, *accum += loss
+ * Returns launch_chain's -3 unchanged -- chain_args_ok runs before any device call, so a refused descriptor touches no device
+ * -- and -1 for what the launcher takes on trust about memory: a, W, out, fm_feat, fm.dpre, head.dpre / w / part, fm.cs and
+ * model_stride not 16-byte aligned; lda / ldo / ldd / fm_ldf / a_bs / out_bs / dpre_bs not a multiple of 8 or a pitch below its
+ * width; fm.ldcs not a multiple of 4 or below feat; ldm / ldcs of a product below N; the head's part row layout; an odd row0
+ * with gauss.  kname (optional, kname_len bytes) receives "chain_kernel<V, MI, GAUSS, GROUP>" of the instantiation that ran. */
+typedef struct mrgan_debug_chain_op {
+    int32_t K, N, n_valid;
+    const void* W; const float* bias;
+    float sigma; uint32_t site;
+    void* out; int64_t out_bs; int32_t ldo;
+    uint16_t* mask; int64_t mask_bs; int32_t ldm;
+    float* cs; int32_t ldcs;
+} mrgan_debug_chain_op;
+typedef struct mrgan_debug_chain_desc {
+    int32_t variant;
+    mrgan_debug_chain_op fwd[3], dx[3];
+    int32_t rows, nseg, block_rows;
+    int32_t models; int64_t model_stride;
+    const void* a; int64_t a_bs; int32_t lda, a_cols;
+    int32_t seg0; uint64_t seed; uint32_t row0; int32_t gauss;
+    uint32_t iter, batch;                /* the DevState of the launch */
+    mrgan_debug_head_desc head;
+    mrgan_debug_fm_desc fm; const void* fm_feat; int32_t fm_ldf;
+} mrgan_debug_chain_desc;
+int mrgan_debug_chain(const mrgan_debug_chain_desc* d, char* kname, int kname_len, mrgan_stream stream);
+
 /* multi-tensor Adam (AdamArgs).  `tiles` is a HOST array of ntiles tile descriptors (copied to the device by the entry); every
  * pointer inside is device memory.  iter / batch / lr_t: the DevState the launch reads.  publish_next != 0: the launch gets a
  * `next` slot, pre-filled with 0xA5 bytes, whose four words are returned in next_out (an updating launch writes

@@ -76,7 +76,16 @@ struct ChainArgs {
     int ablate;                        // timing experiments only (mrgan_debug_ablate): CH_ABL_* bits
 };
 
+// What launch_chain accepts (it returns -3 otherwise); a pure host function, no HIP call.  Per product: K in 128 .. 512 and N in
+// 64 .. 256 (dX: .. 512) in steps of 64, W (+ bias and 1 <= n_valid <= N forward, + mask dX).  Across products: fwd[i].N ==
+// fwd[i + 1].K and dx[i].N == dx[i + 1].K (a product's output image is the next one's A image), dx[0].N and dx[1].N <= CH_PW (only
+// the product that ends a chain may take two passes), a_cols == fwd[0].K.  D tail: 64-row blocks, nseg <= 3 training segments,
+// classes <= KMAX at pitch KMAX, head.feat == fwd[2].N == dx[0].K <= CH_PW.  G backward: fm.feat == dx[0].K <= CH_PW.
+// 1 <= feat_valid <= feat; rows, nseg >= 1; block_rows 32 or 64; no null W6 / b6 / part / loss_part / dpre / cs / fm_feat.
+bool chain_args_ok(const ChainArgs& a);
 int launch_chain(const ChainArgs& a, hipStream_t s);
+// "chain_kernel<V, MI, GAUSS, GROUP>" of the instantiation launch_chain selects for `a` (false: there is none)
+bool chain_kernel_name(const ChainArgs& a, char* name, int len);
 int chain_init_attributes();           // the dynamic-LDS limit of every chain kernel: once per handle, outside any stream capture
 
 // ---- device side: the activation image [K/64 k-tiles][ROWS rows][64 k] bf16, 16-byte chunks XOR-swizzled per row (kc_off) ----

@@ -554,6 +554,77 @@ int mrgan_debug_fm(const mrgan_debug_fm_desc* d, mrgan_stream stream) {
     return debug_finish("debug_fm", launch_fm(d->dtype == MRGAN_BF16, a, s), s);
 }
 
+// one product's descriptor -> ChainOp; the checks are what chain_gemm / copy_out / load_mask_words take on trust
+static int debug_chain_op(const mrgan_debug_chain_op& d, ChainOp& o, const char* what, int i) {
+    memset(&o, 0, sizeof o);
+    o.K = d.K; o.N = d.N; o.n_valid = d.n_valid; o.W = (const __bf16*)d.W; o.bias = d.bias; o.sigma = d.sigma; o.site = d.site;
+    o.out = (__bf16*)d.out; o.out_bs = d.out_bs; o.ldo = d.ldo; o.mask = d.mask; o.mask_bs = d.mask_bs; o.ldm = d.ldm;
+    o.cs = d.cs; o.ldcs = d.ldcs;
+    if (!al(d.W, 16)) return fail(-1, "debug_chain: %s[%d]: W is read 16 bytes at a time", what, i);
+    if (d.out && (!al(d.out, 16) || (d.ldo % 8) || (d.out_bs % 8) || d.ldo < d.N)) return fail(-1, "debug_chain: %s[%d]: out is stored 16 bytes at a time, ldo >= N", what, i);
+    if (d.mask && d.ldm < d.N) return fail(-1, "debug_chain: %s[%d]: ldm >= N", what, i);
+    // (the partial rows are what chain_fmgrad and the folds read back four floats at a time)
+    if (d.cs && (!al(d.cs, 16) || (d.ldcs % 4) || d.ldcs < d.N)) return fail(-1, "debug_chain: %s[%d]: cs rows are 16-byte aligned, ldcs >= N", what, i);
+    return 0;
+}
+
+int mrgan_debug_chain(const mrgan_debug_chain_desc* d, char* kname, int kname_len, mrgan_stream stream) {
+    if (!d) return fail(-1, "null argument");
+    if (kname && kname_len > 0) kname[0] = 0;
+    if (d->variant < CH_V_DTAIL || d->variant > CH_V_GBWD) return fail(-1, "debug_chain: variant must be 0, 1 or 2");
+    const bool has_fwd = d->variant != CH_V_GBWD, has_dx = d->variant != CH_V_GFWD;
+    ChainArgs a;
+    memset(&a, 0, sizeof a);
+    a.variant = d->variant; a.rows = d->rows; a.nseg = d->nseg; a.block_rows = d->block_rows;
+    a.models = d->models; a.model_stride = d->model_stride;
+    a.a = (const __bf16*)d->a; a.a_bs = d->a_bs; a.lda = d->lda; a.a_cols = d->a_cols;
+    a.seg0 = d->seg0; a.seed = d->seed; a.row0 = d->row0; a.gauss = d->gauss;
+    int rop = 0;                               // (the launcher's refusals come first: a pitch is only judged on a shape it accepts)
+    for (int i = 0; i < 3; ++i) {
+        if (has_fwd) { if (int r = debug_chain_op(d->fwd[i], a.fwd[i], "fwd", i)) rop = rop ? rop : r; }
+        if (has_dx) { if (int r = debug_chain_op(d->dx[i], a.dx[i], "dx", i)) rop = rop ? rop : r; }
+    }
+    if (d->variant == CH_V_DTAIL) debug_head_args(&d->head, nullptr, a.head);
+    if (d->variant == CH_V_GBWD) {
+        const mrgan_debug_fm_desc& f = d->fm;
+        a.fm.cs = f.cs; a.fm.npart_fake = f.npart_fake; a.fm.npart_real = f.npart_real; a.fm.ldcs = f.ldcs;
+        a.fm.count = f.count; a.fm.grad_scale = f.grad_scale; a.fm.feat = f.feat; a.fm.feat_valid = f.feat_valid;
+        a.fm.dpre = f.dpre; a.fm.ldd = f.ldd; a.fm.rows = d->rows; a.fm.loss_out = f.loss_out; a.fm.accum = f.accum;
+        a.fm_feat = (const __bf16*)d->fm_feat; a.fm_ldf = d->fm_ldf;
+    }
+    // before anything touches the device: a refused descriptor never reaches a launch
+    if (!chain_args_ok(a)) return fail(-3, "debug_chain: launch refused (-3)");
+    if (rop) return rop;
+    if (d->models > 1 && (d->model_stride % 16)) return fail(-1, "debug_chain: model_stride must keep the 16-byte alignments");
+    if (has_fwd && (!al(d->a, 16) || (d->lda % 8) || (d->a_bs % 8) || d->lda < d->a_cols)) return fail(-1, "debug_chain: the first A image is read 16 bytes at a time (a, a_bs, lda %% 8), lda >= a_cols");
+    if (has_fwd && d->gauss && (d->row0 & 1u)) return fail(-1, "debug_chain: the true-Gaussian generator draws row pairs, row0 must be even");
+    if (d->variant == CH_V_DTAIL) {
+        const mrgan_debug_head_desc& h = d->head;
+        if (!al(h.w, 16) || !al(h.part, 16) || (h.part_stride % 4) || (h.off_db % 4) || h.off_db < (int64_t)h.feat * KMAX || h.off_dbf < h.off_db + KMAX ||
+            h.part_stride < (int64_t)h.off_dbf + h.feat)
+            return fail(-1, "debug_chain: w and part are accessed 16 bytes at a time; part rows hold dW6 [feat * 8), db6 at off_db, the bias gradient at off_dbf");
+        if (!al(h.dpre, 16) || (h.ldd % 8) || (h.dpre_bs % 8) || h.ldd < h.feat) return fail(-1, "debug_chain: head.dpre is stored 16 bytes at a time, ldd >= feat");
+        if (d->models > 1 && (h.model_stride % 16)) return fail(-1, "debug_chain: head.model_stride must keep the 16-byte alignments");
+    }
+    if (d->variant == CH_V_GBWD) {
+        const mrgan_debug_fm_desc& f = d->fm;
+        if (!al(f.cs, 16) || (f.ldcs % 4) || f.ldcs < f.feat) return fail(-1, "debug_chain: fm.cs is read 16 bytes at a time, ldcs >= feat");
+        if (!al(d->fm_feat, 16) || (d->fm_ldf % 8) || d->fm_ldf < f.feat) return fail(-1, "debug_chain: fm_feat is read 16 bytes at a time, fm_ldf >= feat");
+        if (!al(f.dpre, 16) || (f.ldd % 8) || f.ldd < f.feat) return fail(-1, "debug_chain: fm.dpre is stored 16 bytes at a time, ldd >= feat");
+    }
+    DevState* st = nullptr;
+    if (int r = debug_devstate(d->iter, d->batch, 0.f, &st)) return r;
+    a.st = st; a.head.st = st;
+    hipStream_t s = (hipStream_t)stream;
+    static int attr = chain_init_attributes();              // as in debug_head: once per process
+    int r = attr;
+    if (!r) r = launch_chain(a, s);
+    r = debug_finish("debug_chain", r, s);
+    hipFree(st);
+    if (!r && kname && kname_len > 0) chain_kernel_name(a, kname, kname_len);
+    return r;
+}
+
 int mrgan_debug_adam(const mrgan_debug_adam_desc* d, uint32_t next_out[4], mrgan_stream stream) {
     if (!d || !d->tiles || d->ntiles < 1 || d->ntiles > 4096) return fail(-1, "debug_adam: null argument");
     if (d->mode < ADAM_FUSED || d->mode > ADAM_FROM_FLAT) return fail(-1, "debug_adam: unknown mode %d", d->mode);

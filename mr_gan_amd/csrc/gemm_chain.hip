@@ -699,24 +699,75 @@ int chain_init_attributes() {
 
 // one product's shape limits; fwd: a forward product (its output is the next product's A image), else a dX product
 static bool chain_op_ok(const ChainOp& op, bool fwd) {
-    if ((op.K % 64) || (op.N % 64) || op.K > CH_KMAX || op.K < 128 || op.N > 2 * CH_PW || !op.W) return false;
-    if (fwd ? (op.N > CH_PW || !op.bias) : !op.mask) return false;
+    if ((op.K % 64) || (op.N % 64) || op.K > CH_KMAX || op.K < 128 || op.N < 64 || op.N > 2 * CH_PW || !op.W) return false;
+    // (the bias of a forward product is read at min(column, n_valid - 1): the kernel's prologue)
+    if (fwd ? (op.N > CH_PW || !op.bias || op.n_valid < 1 || op.n_valid > op.N) : !op.mask) return false;
     return (long)op.N * op.K * 2 < (1L << 31);
 }
 
-int launch_chain(const ChainArgs& a, hipStream_t s) {
-    const bool has_fwd = a.variant != CH_V_GBWD, has_dx = a.variant != CH_V_GFWD;
-    // (the 32-row blocks have no D-tail kernel; the dX products draw no noise, so CH_V_GBWD has one kernel for both generators)
-    const int gauss = has_fwd && a.gauss, group = a.models > 1;
-    const ChainKernel* k = nullptr;
+// the instantiation a launch runs: (the 32-row blocks have no D-tail kernel; the dX products draw no noise, so CH_V_GBWD has one
+// kernel for both generators)
+static const ChainKernel* chain_pick(const ChainArgs& a) {
+    const int gauss = a.variant != CH_V_GBWD && a.gauss, group = a.models > 1;
     for (const ChainKernel& c : chain_kernels)
-        if (c.variant == a.variant && c.block_rows == a.block_rows && c.gauss == gauss && c.group == group) k = &c;
-    if (!k) return -3;
-    // the head inside the D-tail chain is an 8-class kernel (its scratch is half of image 0)
-    if (a.variant == CH_V_DTAIL && (a.head.classes > KMAX || a.head.ldw != KMAX)) return -3;
+        if (c.variant == a.variant && c.block_rows == a.block_rows && c.gauss == gauss && c.group == group) return &c;
+    return nullptr;
+}
+
+bool chain_kernel_name(const ChainArgs& a, char* name, int len) {
+    const ChainKernel* k = chain_pick(a);
+    if (k && name && len > 0) snprintf(name, (size_t)len, "chain_kernel<%d, %d, %d, %d>", k->variant, k->block_rows / 32, k->gauss, k->group);
+    return k != nullptr;
+}
+
+// Everything launch_chain refuses (-3), as a pure host function: no HIP call, so a refused descriptor never reaches the device.
+// Beside each product's own limits (chain_op_ok) the products of a run must fit each other, because the kernel compiles in
+// which LDS image holds what (chain.h) and takes every width from the descriptors:
+bool chain_args_ok(const ChainArgs& a) {
+    const bool has_fwd = a.variant != CH_V_GBWD, has_dx = a.variant != CH_V_GFWD;
+    // block_rows is 32 or 64, and 64 for the D tail: the table holds nothing else
+    if (!chain_pick(a)) return false;
+    if (a.rows < 1 || a.nseg < 1) return false;
     for (int i = 0; i < 3; ++i)
-        if ((has_fwd && !chain_op_ok(a.fwd[i], true)) || (has_dx && !chain_op_ok(a.dx[i], false))) return -3;
-    if (has_fwd && ((a.a_cols % 64) || a.a_cols > CH_KMAX || a.a_cols != a.fwd[0].K || (long)a.rows * a.lda * 2 >= (1L << 31))) return -3;
+        if ((has_fwd && !chain_op_ok(a.fwd[i], true)) || (has_dx && !chain_op_ok(a.dx[i], false))) return false;
+    if (has_fwd) {
+        if (!a.a || (a.a_cols % 64) || a.a_cols > CH_KMAX || a.a_cols != a.fwd[0].K || (long)a.rows * a.lda * 2 >= (1L << 31)) return false;
+        // chain_gemm reads nk = K / 64 k-tiles of the image the previous epilogue wrote N columns of (`As = lds + a_off + kt * ...`)
+        if (a.fwd[0].N != a.fwd[1].K || a.fwd[1].N != a.fwd[2].K) return false;
+    }
+    if (has_dx) {
+        if (a.dx[0].N != a.dx[1].K || a.dx[1].N != a.dx[2].K) return false;      // the same hand-over, on the way back
+        // every pass of a product lands in columns 0 .. 255 of ONE image (chain_gemm: `cip`, not `col`, addresses oimg): the
+        // product after a two-pass one would read the second pass only, and image 1 holds CH_PW columns
+        if (a.dx[0].N > CH_PW || a.dx[1].N > CH_PW) return false;
+    }
+    if (a.variant == CH_V_DTAIL) {
+        const HeadArgs& h = a.head;
+        // the head inside the D-tail chain is an 8-class kernel (its scratch is half of image 0) ...
+        if (h.classes < 1 || h.classes > KMAX || h.ldw != KMAX) return false;
+        if (a.nseg > 3) return false;                                             // HeadArgs::seg_kind[3], indexed by the block's segment
+        // ... that reads `feat` columns of the feature image fwd[2] wrote (chain_head 2.) and writes dL/d(pre5) into the lower
+        // 256 columns of image 0, whose upper half is its scratch (chain_head_scratch): dx[0] may read no k-tile beyond them
+        if (h.feat != a.fwd[2].N || a.dx[0].K != h.feat || h.feat > CH_PW || h.feat_valid < 1 || h.feat_valid > h.feat) return false;
+        // (every one of these is dereferenced or stored through without a test: head_prefetch, chain_head 3. .. 5., head_block_sums)
+        if (!h.w || !h.b || !h.part || !h.loss_part || !h.dpre) return false;
+        for (int i = 0; i < a.nseg; ++i) {
+            if (h.seg_kind[i] < HEAD_LAB || h.seg_kind[i] > HEAD_FAKE) return false;      // head_row<false>: the training kinds
+            if (h.seg_kind[i] == HEAD_LAB && !h.labels) return false;
+        }
+    }
+    if (a.variant == CH_V_GBWD) {
+        const FmArgs& f = a.fm;
+        // chain_fmgrad builds 256 columns of image 0 (zeros from column `feat` on) and folds `feat` <= 256 columns of moments
+        if (f.feat != a.dx[0].K || f.feat > CH_PW || f.feat_valid < 1 || f.feat_valid > f.feat) return false;
+        if (!f.cs || !a.fm_feat || !f.dpre || f.npart_fake < 1 || f.npart_real < 1) return false;      // (the copy of image 0 goes to dpre untested)
+    }
+    return true;
+}
+
+int launch_chain(const ChainArgs& a, hipStream_t s) {
+    if (!chain_args_ok(a)) return -3;
+    const ChainKernel* k = chain_pick(a);
     const int nrb = (a.rows + a.block_rows - 1) / a.block_rows;
     MRGAN_LAUNCH(k->kernel, dim3(nrb * a.nseg, std::max(1, a.models)), dim3(CH_THREADS), chain_lds_bytes(a.block_rows), s, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;

@@ -31,7 +31,7 @@ EXPORTS = [
     "mrgan_pair_hint", "mrgan_set_tuning", "mrgan_debug_noise", "mrgan_debug_tr_probe", "mrgan_debug_gemm_launch", "mrgan_profile_begin", "mrgan_profile_end", "mrgan_debug_ablate", "mrgan_debug_gemm_time", "mrgan_debug_buffer", "mrgan_debug_gemm_fp8",
     "mrgan_debug_quant8", "mrgan_debug_fp8_update_scales",
     "mrgan_debug_stage", "mrgan_debug_reduce_partials","mrgan_debug_colsum_finalize", "mrgan_debug_bn_apply", "mrgan_debug_bn_bwd", "mrgan_debug_head", "mrgan_debug_head_wide",
-    "mrgan_debug_fm", "mrgan_debug_adam",
+    "mrgan_debug_fm", "mrgan_debug_adam", "mrgan_debug_chain",
     "mrgan_select_model", "mrgan_sup_step_group",
     "mrgan_disc_step_group", "mrgan_gen_step_group", "mrgan_train_pair_group",
     "mrgan_input_gradient",
@@ -666,6 +666,31 @@ class DebugFmDesc(C.Structure):
     ]
 
 
+class DebugChainOp(C.Structure):
+    """mrgan_debug_chain_op"""
+    _fields_ = [
+        ("K", C.c_int32), ("N", C.c_int32), ("n_valid", C.c_int32),
+        ("W", C.c_void_p), ("bias", C.c_void_p), ("sigma", C.c_float), ("site", C.c_uint32),
+        ("out", C.c_void_p), ("out_bs", C.c_int64), ("ldo", C.c_int32),
+        ("mask", C.c_void_p), ("mask_bs", C.c_int64), ("ldm", C.c_int32),
+        ("cs", C.c_void_p), ("ldcs", C.c_int32),
+    ]
+
+
+class DebugChainDesc(C.Structure):
+    """mrgan_debug_chain_desc"""
+    _fields_ = [
+        ("variant", C.c_int32), ("fwd", DebugChainOp * 3), ("dx", DebugChainOp * 3),
+        ("rows", C.c_int32), ("nseg", C.c_int32), ("block_rows", C.c_int32),
+        ("models", C.c_int32), ("model_stride", C.c_int64),
+        ("a", C.c_void_p), ("a_bs", C.c_int64), ("lda", C.c_int32), ("a_cols", C.c_int32),
+        ("seg0", C.c_int32), ("seed", C.c_uint64), ("row0", C.c_uint32), ("gauss", C.c_int32),
+        ("iter", C.c_uint32), ("batch", C.c_uint32),
+        ("head", DebugHeadDesc),
+        ("fm", DebugFmDesc), ("fm_feat", C.c_void_p), ("fm_ldf", C.c_int32),
+    ]
+
+
 class DebugAdamTile(C.Structure):
     """mrgan_debug_adam_tile"""
     _fields_ = [
@@ -752,6 +777,35 @@ def debug_head_wide(mask=None, mask_bs=0, ldm=0, w6c=None, w6r=None, **kw):
 
 def debug_fm(**kw):
     return _debug_rc(load_library().mrgan_debug_fm(C.byref(_debug_fill(DebugFmDesc(), kw)), _stream()))
+
+
+CH_V_DTAIL, CH_V_GFWD, CH_V_GBWD = range(3)
+
+
+def debug_chain(fwd=(), dx=(), head=None, fm=None, **kw):
+    """One launch of the row-block chain kernel through mrgan_debug_chain -> (return code, kernel name).  fwd / dx: up to three
+    dicts of DebugChainOp fields each, head / fm: dicts of DebugHeadDesc / DebugFmDesc fields, kw: the launch's own fields.
+    Pointers may be tensors or plain integers (a refused descriptor is never dereferenced, so the refusals need no device)."""
+    d = _debug_fill(DebugChainDesc(), kw)
+    keep = [d._refs]
+    for name, ops in (("fwd", fwd), ("dx", dx)):
+        for i, o in enumerate(list(ops)[:3]):
+            op = _debug_fill(DebugChainOp(), o)
+            keep.append(op._refs)
+            getattr(d, name)[i] = op
+    if head is not None:
+        h = _debug_fill(DebugHeadDesc(), head)
+        keep.append(h._refs)
+        d.head = h
+    if fm is not None:
+        f = _debug_fill(DebugFmDesc(), fm)
+        keep.append(f._refs)
+        d.fm = f
+    name = C.create_string_buffer(PROF_NAME_LEN)
+    stream = _stream() if torch.cuda.is_available() else None
+    rc = _debug_rc(load_library().mrgan_debug_chain(C.byref(d), name, PROF_NAME_LEN, stream))
+    del keep
+    return rc, name.value.decode()
 
 
 def debug_adam(tiles, **kw):

@@ -422,6 +422,21 @@ def _e5m2_neighbour(byte_vals, y):
     return np.abs(byte_vals - y) <= 0.5 * step
 
 
+def _fm_bounds(tf, tr, af, ar, npf, npr, count, gs):
+    """the valid columns' fp64 totals tf / tr of npf fake and npr real partial rows (af / ar: the sums of their magnitudes) ->
+    (loss, gj, e_gj, e_gj_mixed, e_loss).  e_gj: the gradient from two folds, one per stream; e_gj_mixed: from ONE fold that takes
+    the rows of both streams in any order (what the loss of every kernel and the gradient inside the chain kernel do)"""
+    fvn = tf.size
+    loss, gj = R.fm(tf, tr, count, gs)
+    diff = (tf - tr) / count
+    e_diff = (npf * U * af + npr * U * ar + U * np.abs(tf - tr)) / count + U * np.abs(diff)
+    scale = np.abs(gs * 2.0 / (fvn * count))
+    # the loss: the mixed fold of fake and real rows (any order), the square, the sum over the features (any order)
+    e_d2 = ((npf + npr) * U * (af + ar) / count + U * np.abs(diff))
+    e_loss = (np.sum(2 * np.abs(diff) * e_d2 + e_d2 ** 2 + 3 * U * diff * diff) + fvn * U * np.sum(diff * diff)) / fvn + U * loss
+    return loss, gj, scale * e_diff + 4 * U * np.abs(gj), scale * e_d2 + 4 * U * np.abs(gj), e_loss
+
+
 def _run_fm(dtype, feat, feat_valid, rows, npf, npr, q8=False, dist=False, launches=1, key=0):
     E = _E()
     rng = _rng(15, dtype, feat, feat_valid, rows, npf, npr, key)
@@ -458,10 +473,7 @@ def _run_fm(dtype, feat, feat_valid, rows, npf, npr, q8=False, dist=False, launc
     for _ in range(launches):
         _ok(E.debug_fm(**kw))
     fv = slice(0, feat_valid)
-    loss, gj = R.fm(tf[fv], tr[fv], count, gs)
-    diff = (tf[fv] - tr[fv]) / count
-    e_diff = (npf * U * af[fv] + npr * U * ar[fv] + U * np.abs(tf[fv] - tr[fv])) / count + U * np.abs(diff)
-    e_gj = np.abs(gs * 2.0 / (feat_valid * count)) * e_diff + 4 * U * np.abs(gj)
+    loss, gj, e_gj, _, e_loss = _fm_bounds(tf[fv], tr[fv], af[fv], ar[fv], npf, npr, count, gs)
     ref = np.zeros((rows, feat))
     ref[:, fv] = np.where(bits[:, fv], gj[None, :], 0.0)
     bound = np.zeros((rows, feat))
@@ -472,9 +484,6 @@ def _run_fm(dtype, feat, feat_valid, rows, npf, npr, q8=False, dist=False, launc
     inside = torch.zeros_like(dpre, dtype=torch.bool)
     inside[:rows, :feat] = True
     _assert_sentinel(label + " dpre", dpre.float(), inside)
-    # the loss: the mixed fold of fake and real rows (any order), the square, the sum over the features (any order)
-    e_d2 = ((npf + npr) * U * (af[fv] + ar[fv]) / count + U * np.abs(diff))
-    e_loss = (np.sum(2 * np.abs(diff) * e_d2 + e_d2 ** 2 + 3 * U * diff * diff) + feat_valid * U * np.sum(diff * diff)) / feat_valid + U * loss
     got = scal.cpu().double().numpy()
     _close(label + " loss", got[0:1], [loss], [e_loss])
     _close(label + " accum", got[1:2], [3.25 + launches * loss], [launches * (e_loss + U * (3.25 + launches * loss))])
@@ -888,6 +897,26 @@ def _head_undecided(l, delta, c2):
     return top[:, -1] - top[:, -2] < 2 * delta.max(axis=1)
 
 
+def _head_grad_bounds(fs, Wv, dl, e_dl, dp, bits, dtype, KP, HB, nblk, wide):
+    """bounds of the head's gradients around the reference dlogits dl (bound e_dl) and dL/d(pre5) dp of one segment (formulas in
+    the comment above; shared with tests/test_chain_kernel.py, whose head is the matrix-core one at KP = 8) ->
+    e_dp (dpre before the store), dpre (as stored), dw_ref / dw (dW6 per HB-row block), db6, dbf (per block)"""
+    aW = np.abs(Wv)
+    fp64_acc = KP == 32 and dtype == BF16 and not wide
+    # wide: six addend pairs x 16-deep k-steps of exact products in fp32 accumulators, the dropped pairs below 4 U
+    acc_df = (2 * 6 * 16 * (1 if KP == 8 else 2) + 4) * U if wide else 2 * U if fp64_acc else 2 * KP * U
+    e_df = e_dl @ aW.T + acc_df * (np.abs(dl) @ aW.T) + KP * UF
+    e_dp = e_df * bits
+    ndw = 2 * 3 * 64 if wide else 32                   # wide: 64 rows x three addends of dlogits in fp32 MFMA accumulators
+    blk = lambda x, i: x[i * HB:(i + 1) * HB]
+    return dict(
+        e_dp=e_dp, dpre=e_dp + BF16_RND * (np.abs(dp) + e_dp) if dtype == BF16 else e_dp,
+        dw_ref=np.stack([blk(fs, i).T @ blk(dl, i) for i in range(nblk)]),
+        dw=np.stack([np.abs(blk(fs, i)).T @ (blk(e_dl, i) + ndw * U * np.abs(blk(dl, i))) for i in range(nblk)]) + HB * UF,
+        db6=_blocks(e_dl, nblk, HB) + HB * U * _blocks(np.abs(dl), nblk, HB) + HB * UF,
+        dbf=_blocks(e_dp, nblk, HB) + HB * U * _blocks(np.abs(dp), nblk, HB) + HB * UF)
+
+
 def _head_inputs(dtype, kinds, classes, feat, feat_valid, rows, models=1, stream=False, hot=False, key=0, wide=False, **_):
     """The draws of one head case (numpy only, so the CPU suite can hold the seeds: tests/test_aux_refs_cpu.py) ->
     (rng, f, W6, b, labels, batch, (undecided rows, rows with a label, tie rows)).  The labels of the rows on which the two identical
@@ -939,7 +968,6 @@ def _run_head(dtype, kinds, classes, feat, feat_valid, rows, models=1, stream=Fa
     nseg, nblk = len(kinds), -(-rows // HB)
     label = "%s %s kinds %s K %d feat %d/%d rows %d%s%s" % ("head_wide" if wide else "head", "bf16" if dtype else "f32", list(kinds), classes, feat, feat_valid, rows,
                                                               " models %d" % models if models > 1 else "", " q8" if q8 else "")
-    fp64_acc = KP == 32 and dtype == BF16
     inv, w_unl = 1.0 / rows, 0.75
     ldf, ldd, srows = feat + 8, feat + 16, rows + GAP
     off_db = feat * KP + 4
@@ -1066,27 +1094,20 @@ def _run_head(dtype, kinds, classes, feat, feat_valid, rows, models=1, stream=Fa
             else:
                 assert (lp[:, 2] == 0).all()
             dw6, db6, dp, dbf = R.head_backward(fs, Wv, dl, live=bits[m, s])
-            aW = np.abs(Wv)
-            # wide: six addend pairs x 16-deep k-steps of exact products in fp32 accumulators, the dropped pairs below 4 U
-            acc_df = (2 * 6 * 16 * (1 if KP == 8 else 2) + 4) * U if wide else 2 * U if fp64_acc else 2 * KP * U
-            e_df = e_dl @ aW.T + acc_df * (np.abs(dl) @ aW.T) + KP * UF
-            e_dp = e_df * bits[m, s]
-            bound = e_dp + BF16_RND * (np.abs(dp) + e_dp) if dtype == BF16 else e_dp
+            gb = _head_grad_bounds(fs, Wv, dl, e_dl, dp, bits[m, s], dtype, KP, HB, nblk, wide)
+            e_dp, bound = gb["e_dp"], gb["dpre"]
             if wide and q8:
                 assert (got_dpre == SENT).all(), tag + ": the fp8 form writes no dpre"
             else:
                 worst = max(worst, _close(tag + " dpre", got_dpre[s, :rows, :feat], dp, bound))
                 assert (got_dpre[s, rows:] == SENT).all() and (got_dpre[s, :rows, feat:] == SENT).all()
             pr = got_part[blk0:blk0 + nblk]
-            ndw = 2 * 3 * 64 if wide else 32               # wide: 64 rows x three addends of dlogits in fp32 MFMA accumulators
-            dw_ref = np.stack([fs[i * HB:(i + 1) * HB].T @ dl[i * HB:(i + 1) * HB] for i in range(nblk)])
-            dw_b = np.stack([np.abs(fs[i * HB:(i + 1) * HB]).T @ (e_dl[i * HB:(i + 1) * HB] + ndw * U * np.abs(dl[i * HB:(i + 1) * HB])) for i in range(nblk)]) + HB * UF
             gw = pr[:, :feat * KP].reshape(nblk, feat, KP)
-            worst = max(worst, _close(tag + " dW6", gw[:, :, :classes], dw_ref, dw_b))
+            worst = max(worst, _close(tag + " dW6", gw[:, :, :classes], gb["dw_ref"], gb["dw"]))
             assert (gw[:, :, classes:] == 0).all(), tag + ": dW6 columns >= classes must be exact zeros"
-            worst = max(worst, _close(tag + " db6", pr[:, off_db:off_db + classes], _blocks(dl, nblk, HB), _blocks(e_dl, nblk, HB) + HB * U * _blocks(np.abs(dl), nblk, HB) + HB * UF))
+            worst = max(worst, _close(tag + " db6", pr[:, off_db:off_db + classes], _blocks(dl, nblk, HB), gb["db6"]))
             assert (pr[:, off_db + classes:off_db + KP] == 0).all()
-            worst = max(worst, _close(tag + " dbf", pr[:, off_dbf:off_dbf + feat], _blocks(dp, nblk, HB), _blocks(e_dp, nblk, HB) + HB * U * _blocks(np.abs(dp), nblk, HB) + HB * UF))
+            worst = max(worst, _close(tag + " dbf", pr[:, off_dbf:off_dbf + feat], _blocks(dp, nblk, HB), gb["dbf"]))
             for a0, a1 in ((feat * KP, off_db), (off_db + KP, off_dbf), (off_dbf + feat, pstride)):
                 assert (pr[:, a0:a1] == SENT).all(), tag + ": part row written outside dW6 / db6 / dbf"
             if q8:

@@ -104,7 +104,7 @@ def test_library_exports_every_declared_symbol():
     from mr_gan_amd import engine as E
     lib = E.load_library()
     names = _declared_symbols()
-    assert len(names) >= 20
+    assert len(names) >= 20 and "mrgan_debug_chain" in names
     for n in names:
         assert hasattr(lib, n), n
     assert sorted(E.EXPORTS) == names
@@ -168,6 +168,9 @@ def test_debug_aux_desc_layouts_match_header():
             ("mrgan_debug_head_desc", E.DebugHeadDesc, ("seg_kind", "labels", "batch", "part_stride", "model_stride", "err_count", "q8_slot")),
             ("mrgan_debug_head_wide_desc", E.DebugHeadWideDesc, ("mask", "ldm", "w6r")),
             ("mrgan_debug_fm_desc", E.DebugFmDesc, ("mask", "loss_out", "ldq8", "lcount")),
+            ("mrgan_debug_chain_op", E.DebugChainOp, ("W", "sigma", "out_bs", "mask", "ldm", "ldcs")),
+            ("mrgan_debug_chain_desc", E.DebugChainDesc, ("dx", "rows", "model_stride", "a_cols", "seed", "gauss", "batch", "head", "fm", "fm_feat",
+                                                          "fm_ldf")),
             ("mrgan_debug_adam_tile", E.DebugAdamTile, ("slab_stride", "w8_slot", "cols")),
             ("mrgan_debug_adam_desc", E.DebugAdamDesc, ("lr_t", "loss_part", "flat_tail", "lr", "model_stride"))]
     body = "".join('  printf("%%zu", sizeof(%s));%s  printf("\\n");\n'
@@ -182,6 +185,106 @@ def test_debug_aux_desc_layouts_match_header():
     for line, (cname, S, fields) in zip(lines, pins):
         assert [int(v) for v in line.split()] == [ctypes.sizeof(S)] + [getattr(S, f).offset for f in fields], cname
         assert S._fields_[-1][0] == fields[-1], cname
+
+
+# ---- the chain launcher's refusals: chain_args_ok (csrc/gemm_chain.hip) is pure host code and runs before any device call ------
+CHAIN_P = 0x70000000         # a non-null, 16-byte aligned stand-in for every device pointer: a refused descriptor is never dereferenced
+
+
+def _chain_stock(variant):
+    """the engine's tail 512(500) -> 256(250) -> 256(250) -> 256(250), 130 rows per segment, as keywords of engine.debug_chain"""
+    P, rows, srows = CHAIN_P, 130, 133
+    w, v = [512, 256, 256, 256], [500, 250, 250, 250]
+    nseg = {0: 3, 1: 2, 2: 1}[variant]
+    op = lambda K, N, nv, **kw: dict(K=K, N=N, n_valid=nv, W=P, out=P, out_bs=srows * (N + 8), ldo=N + 8, mask=P, mask_bs=6 * (N + 8) * 2, ldm=N + 8, **kw)
+    fwd = [op(w[i], w[i + 1], v[i + 1], bias=P, sigma=0.5, site=i + 3) for i in range(3)]
+    dx = [op(w[3 - i], w[2 - i], v[2 - i], cs=P, ldcs=w[2 - i] + 8) for i in range(3)]
+    head = dict(rows=rows, nseg=3, seg_kind=[0, 1, 2], feat=256, feat_valid=250, classes=6, w=P, ldw=8, b=P, labels=P, inv_count=1.0 / rows,
+                unl_weight=1.0, dpre=P, dpre_bs=srows * 264, ldd=264, part=P, part_stride=2320, off_db=2048, off_dbf=2056, loss_part=P)
+    fm = dict(cs=P, npart_fake=3, npart_real=3, ldcs=264, count=float(rows), grad_scale=1.0, feat=256, feat_valid=250, dpre=P, ldd=264,
+              loss_out=P, accum=P)
+    return dict(variant=variant, fwd=fwd, dx=dx, head=head, fm=fm, rows=rows, nseg=nseg, block_rows=64, models=1, a=P, a_bs=srows * 520, lda=520,
+                a_cols=512, seed=1, row0=0, gauss=0, iter=3, fm_feat=P, fm_ldf=264)
+
+
+def _chain_rc(variant, **changes):
+    """the entry's return code for the stock descriptor with `changes`: 'fwd_1_K' = field K of fwd[1], 'head_feat', 'fm_ldcs', or a
+    field of the launch itself"""
+    import copy
+    from mr_gan_amd import engine as E
+    kw = copy.deepcopy(_chain_stock(variant))
+    for path, val in changes.items():
+        head, _, rest = path.partition("_")
+        if head in ("fwd", "dx") and rest[:1].isdigit():
+            kw[head][int(rest[0])][rest[2:]] = val
+        elif head == "head" or (head == "fm" and rest not in ("feat", "ldf")):      # (fm_feat / fm_ldf are the launch's own)
+            kw[head][rest] = val
+        else:
+            kw[path] = val
+    rc, name = E.debug_chain(**kw)
+    assert name == ""
+    return rc
+
+
+def test_chain_launcher_refusals_without_a_device():
+    """Every descriptor below differs from a valid one in the named field(s) only and is refused before the entry allocates or
+    launches anything, so the test needs no GPU (and launches nothing where there is one).  -3: launch_chain's own refusals
+    (chain_args_ok); -1: what the launcher takes on trust about memory, which the entry judges only on a shape chain_args_ok
+    accepted -- so every -1 below also shows that the stock descriptor of its variant passes chain_args_ok."""
+    D, GF, GB = 0, 1, 2
+    P = CHAIN_P
+    refused = [
+        # ---- the refusals launch_chain always made ----
+        (D, dict(fwd_1_K=200)), (GF, dict(fwd_0_K=448)),                     # K not a multiple of 64
+        (D, dict(dx_2_K=64)), (GF, dict(fwd_1_K=64)),                        # K < 128
+        (GF, dict(fwd_0_K=576)), (GB, dict(dx_0_K=576)),                     # K > 512
+        (GF, dict(fwd_2_N=320)), (D, dict(fwd_0_N=512)),                     # forward N > 256
+        (GB, dict(dx_2_N=576)),                                              # dX N > 512
+        (D, dict(fwd_1_bias=0)), (GB, dict(dx_1_mask=0)), (D, dict(dx_0_mask=0)), (GF, dict(fwd_0_W=0)), (GB, dict(dx_2_W=0)),
+        (GF, dict(a_cols=448)), (D, dict(a_cols=256)),                       # a_cols != fwd[0].K
+        (D, dict(block_rows=32)),                                            # no D tail at 32-row blocks
+        (D, dict(head_classes=9)), (D, dict(head_ldw=32)),
+        # ---- consistency between the products ----
+        (GF, dict(fwd_0_N=192)), (D, dict(fwd_1_N=192)), (GF, dict(fwd_1_K=192)), (D, dict(fwd_2_K=128)),
+        (GB, dict(dx_0_N=192)), (D, dict(dx_1_N=192)), (GB, dict(dx_1_K=128)), (D, dict(dx_2_K=128)),
+        (GB, dict(dx_0_N=512)), (D, dict(dx_1_N=512)),                       # a two-pass product that does not end the chain ...
+        (GB, dict(dx_0_N=512, dx_1_K=512)), (D, dict(dx_1_N=512, dx_2_K=512)),      # ... refused for that alone: the widths agree
+        (D, dict(dx_0_K=128)), (D, dict(head_feat=192)), (D, dict(head_feat=128, dx_0_K=128)),      # dx[0].K == fwd[2].N == head.feat
+        (D, dict(head_feat_valid=257)), (D, dict(head_feat_valid=0)),
+        (GB, dict(dx_0_K=512)),                                              # fm.feat == dx[0].K (more below)
+        (GB, dict(fm_feat_valid=300)), (GB, dict(fm_feat_valid=0)),
+        (D, dict(rows=0)), (GF, dict(rows=-5)), (GB, dict(nseg=0)), (D, dict(nseg=4)),
+        (GF, dict(block_rows=48)), (GB, dict(block_rows=128)), (GF, dict(block_rows=0)),
+        # ---- what the kernel would dereference untested ----
+        (GF, dict(fwd_2_n_valid=0)), (GF, dict(fwd_0_n_valid=300)), (D, dict(head_dpre=0)), (D, dict(head_part=0)), (D, dict(head_loss_part=0)),
+        (D, dict(head_seg_kind=[0, 3, 2])), (D, dict(head_labels=0)), (GB, dict(fm_dpre=0)), (GB, dict(fm_cs=0)), (GB, dict(fm_feat=0)),
+        (GF, dict(a=0)),
+    ]
+    for variant, ch in refused:
+        assert _chain_rc(variant, **ch) == -3, (variant, ch)
+    # fm.feat against dx[0].K and the image: the field is fm's `feat` (the launch's fm_feat is the pointer)
+    from mr_gan_amd import engine as E
+    for feat, k0 in ((192, 256), (512, 512)):
+        kw = _chain_stock(GB)
+        kw["fm"]["feat"] = feat
+        kw["dx"][0]["K"] = k0
+        assert E.debug_chain(**kw)[0] == -3, (feat, k0)
+    trusted = [
+        (GF, dict(a=P + 8)), (GF, dict(lda=516)), (GF, dict(lda=504)), (D, dict(a_bs=133 * 520 + 4)),
+        (GF, dict(fwd_0_W=P + 8)), (GB, dict(dx_1_W=P + 2)),
+        (GF, dict(fwd_1_out=P + 8)), (GF, dict(fwd_1_ldo=248)), (GB, dict(dx_2_ldo=516)), (D, dict(dx_0_out_bs=133 * 264 + 4)),
+        (GF, dict(fwd_0_ldm=200)), (GB, dict(dx_2_ldm=500)),
+        (D, dict(dx_2_ldcs=504)), (D, dict(dx_1_cs=P + 8)), (D, dict(dx_0_ldcs=266)),
+        (GF, dict(gauss=1, row0=3)), (D, dict(gauss=1, row0=1)),
+        (GF, dict(models=2, model_stride=1 << 20 | 8)),
+        (GB, dict(fm_feat=P + 8)), (GB, dict(fm_ldf=248)), (GB, dict(fm_ldf=260)), (GB, dict(fm_ldcs=248)), (GB, dict(fm_ldcs=262)),
+        (GB, dict(fm_cs=P + 4)), (GB, dict(fm_ldd=260)), (GB, dict(fm_ldd=248)), (GB, dict(fm_dpre=P + 8)),
+        (D, dict(head_ldd=248)), (D, dict(head_ldd=260)), (D, dict(head_dpre=P + 8)), (D, dict(head_part=P + 8)), (D, dict(head_w=P + 4)),
+        (D, dict(head_off_db=2044)), (D, dict(head_off_dbf=2052)), (D, dict(head_part_stride=2300)),
+    ]
+    for variant, ch in trusted:
+        assert _chain_rc(variant, **ch) == -1, (variant, ch)
+    assert b"debug_chain" in E.load_library().mrgan_last_error()
 
 
 def test_fp8_round_equals_torch_casts_on_every_bf16_value():
