@@ -303,6 +303,55 @@ typedef struct mrgan_saliency_args {
 } mrgan_saliency_args;
 int mrgan_input_gradient(mrgan_handle* h, const mrgan_saliency_args* a, mrgan_stream stream);
 
+/* Attribution maps averaged over `draws` forwards, accumulated on the device: the mean over d = 0 .. draws - 1 of the input
+ * gradient g_d of mrgan_input_gradient's objective, taken at a forward that differs per draw.  x_dev .. classes_out_dev mean what
+ * they mean in mrgan_saliency_args.
+ *   method MRGAN_ATTR_NOISE (SmoothGrad): draw d is the learning-phase-1 forward at x with fresh GaussianNoise.  Site 0 is the
+ *     staged input, sites 1 .. 4 the outputs of dense 1 .. 4; draw d of site s adds sigma * N(0, 1) with sigma = sigma_input at
+ *     site 0 and sigma_hidden at sites 1 .. 4.  A sigma of exactly 0 leaves that site noise-free (the kernels the evaluation
+ *     runs); mrgan_config.sigma[0] and sigma[1] (0.3 and 0.5) give the training forward; (s, 0) is the classic input-only
+ *     SmoothGrad.  The gradient is taken with respect to the noisy input, which is the gradient with respect to x.
+ *   method MRGAN_ATTR_PATH: draw d is the noise-free forward at the point
+ *         v = fmaf(alpha_d, x - b, b),   alpha_d = (d + 0.5f) / (float)draws      (all fp32; the midpoint rule on [0, 1])
+ *     of the straight path from the baseline b (baseline_dev: fp32 [d_in], or NULL for zeros -- the training mean of
+ *     standard-scaled data) to the row x.
+ *   multiply = 1 multiplies the mean gradient elementwise by (x - b), x the caller's fp32 row and b the baseline (zeros when
+ *     NULL): gradient x input for MRGAN_ATTR_NOISE, integrated gradients for MRGAN_ATTR_PATH (they sum to l_t(x) - l_t(b) under
+ *     MRGAN_SAL_LOGIT as draws grows).  multiply = 0 leaves the mean gradient.
+ * The sum over draws is fp32, in draw order, without atomics; the last draw divides by draws, applies multiply and then post
+ * (MRGAN_SAL_HEATMAP: the map of mrgan_input_gradient, constant-row rule included, of that final quantity).  draws = 1, both
+ * sigmas 0, MRGAN_ATTR_NOISE, multiply = 0 gives the bits of mrgan_input_gradient.
+ * Noise keys: site s, draw d of the call draws its normals at (seed + selected model, s * 256 + MRGAN_ATTR_NOISE_SEG, step d,
+ * row = the row's index in the call), from the generator of the handle (MRGAN_FLAG_GAUSS_NOISE: the true-Gaussian one).  Segment
+ * id MRGAN_ATTR_NOISE_SEG is used by no training or evaluation draw, and the step is the draw index, not the handle's iteration:
+ * a map is a function of (weights, seed, rows, arguments) alone -- training further or mrgan_set_iterations do not move it, nor
+ * does the chunking of the call.
+ * Target class: targets_dev[i], or with targets_dev NULL the predicted class of the noise-free forward at x (what
+ * mrgan_input_gradient reports), computed once per chunk of S rows by one extra clean forward, written to classes_out_dev and
+ * used for every draw; classes_out_dev is required in that case.
+ * Leaves untouched what mrgan_input_gradient leaves untouched; two calls give identical bits; a group handle serves the model
+ * of mrgan_select_model.
+ * Status -2: what mrgan_input_gradient refuses; an unknown method; draws outside [1, MRGAN_ATTR_MAX_DRAWS]; multiply not 0 or 1;
+ * a negative or non-finite sigma; a nonzero sigma with MRGAN_ATTR_PATH or a baseline with MRGAN_ATTR_NOISE; targets_dev and
+ * classes_out_dev both NULL.  Status -3: an fp8 handle. */
+enum { MRGAN_ATTR_NOISE = 0, MRGAN_ATTR_PATH = 1 };
+enum { MRGAN_ATTR_MAX_DRAWS = 4096, MRGAN_ATTR_NOISE_SEG = 255 };
+typedef struct mrgan_attribution_args {
+    const float* x_dev; const int32_t* idx_dev; int64_t ld_x; int64_t n;
+    const int32_t* targets_dev;      /* [n] or NULL: the predicted class of the noise-free forward at x */
+    int32_t objective;               /* MRGAN_SAL_LOGIT | MRGAN_SAL_XENT | MRGAN_SAL_MSE */
+    int32_t post;                    /* MRGAN_SAL_RAW | MRGAN_SAL_HEATMAP */
+    float* out_dev; int64_t ld_out;  /* [n][ld_out], ld_out >= d_in */
+    int32_t* classes_out_dev;        /* [n]: the target class used; optional when targets_dev is given */
+    int32_t method;                  /* MRGAN_ATTR_NOISE | MRGAN_ATTR_PATH */
+    int32_t draws;                   /* 1 .. MRGAN_ATTR_MAX_DRAWS */
+    float sigma_input, sigma_hidden; /* MRGAN_ATTR_NOISE: sigma of site 0 / of sites 1 .. 4; 0 with MRGAN_ATTR_PATH */
+    const float* baseline_dev;       /* MRGAN_ATTR_PATH: [d_in] or NULL (zeros); NULL with MRGAN_ATTR_NOISE */
+    int32_t multiply;                /* 1: times (x - baseline) */
+    int32_t reserved;
+} mrgan_attribution_args;
+int mrgan_attribution(mrgan_handle* h, const mrgan_attribution_args* a, mrgan_stream stream);
+
 /* epoch metrics accumulated on the device (mr_gan.py:208-210 accumulate on the host and force a sync per step):
  * out8_host = sum loss_lab, sum loss_unl, sum train_err, sum loss_gen, last loss_lab, last loss_unl, last err,
  * last loss_gen.  reset != 0 zeroes the sums afterwards. */

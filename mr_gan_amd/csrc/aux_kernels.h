@@ -117,6 +117,32 @@ struct SaliencyFinishArgs {
 };
 int launch_saliency_finish(int bf16, const SaliencyFinishArgs& a, hipStream_t s);
 
+// ---- attribution over draws (mrgan_attribution): a path point as the discriminator's input, and the accumulator ----
+// out[r][c] = T(fmaf(alpha, x[r][c] - b[c], b[c])) for c < cols, 0 for cols <= c < cols_pad; row r of x is
+// src[(idx ? idx[r] : r) * ld + c], b = baseline[c] or 0.  The gather of the stage kernel without its noise.
+struct PathStageArgs {
+    const float* src; const int32_t* idx; long ld;
+    const float* baseline;                     // [cols] or null: zeros
+    float alpha;
+    int rows, cols, cols_pad;
+    void* out; int ldo;                        // T [rows][ldo], ldo a multiple of 8 and >= cols_pad
+};
+int launch_path_stage(int bf16, const PathStageArgs& a, hipStream_t s);
+// Draw `draw` of `draws`: out = g (draw 0) or out += g (fp32, in draw order); the last draw then divides by draws, multiplies
+// by (x - baseline) where asked (x gathered as in PathStageArgs) and stores that, or its SAL_HEATMAP map.  draws = 1 never reads
+// out.  Columns >= cols of out are never touched.
+struct AttrAccumArgs {
+    const void* g; int ldg;                    // T [rows][ldg]: this draw's layer-0 dX
+    int rows, cols;
+    float* out; long ldo;
+    int mode;                                  // SAL_RAW | SAL_HEATMAP, applied by the last draw
+    int draw, draws;
+    int multiply;
+    const float* x; const int32_t* idx; long ld_x;      // multiply: the caller's rows (idx already offset to the chunk)
+    const float* baseline;
+};
+int launch_attr_accum(int bf16, const AttrAccumArgs& a, hipStream_t s);
+
 // ---- feature matching (mr_gan.py:152-154) ----
 struct FmArgs {
     const float* cs; int npart_fake, npart_real, ldcs;   // column partial sums of f: fake rows first, then real

@@ -508,45 +508,150 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
 // atomics: the same bits on every call.  |g| / denom is monotone in |g|, so min a and max a are the quotients of min |g| and
 // max |g|, and the elements that attain them come out as exactly 0 and 1.
 // =========================================================================================
+// the heat-map's row statistics (one block = one row, every thread calls): a thread's sum g^2, max |g| and min |g| over its
+// columns -> the row's denominator rms + 1e-5, min a and max a - min a
+struct HeatRow { float denom, amin, range; };
+__device__ __forceinline__ void heat_accum(const float v[8], int c, int cols, float& ss, float& mx, float& mn) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if (c + i < cols) { ss = fmaf(v[i], v[i], ss); mx = fmaxf(mx, fabsf(v[i])); mn = fminf(mn, fabsf(v[i])); }
+    }
+}
+__device__ __forceinline__ HeatRow heat_row(float ss, float mx, float mn, int cols, float (*red)[4]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ss += __shfl_xor(ss, o, 64); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); mn = fminf(mn, __shfl_xor(mn, o, 64));
+    }
+    if (lane == 0) { red[0][wave] = ss; red[1][wave] = mx; red[2][wave] = mn; }
+    __syncthreads();
+    ss = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    mx = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+    mn = fminf(fminf(red[2][0], red[2][1]), fminf(red[2][2], red[2][3]));
+    HeatRow h;
+    h.denom = sqrtf(ss / (float)cols) + 1e-5f;
+    h.amin = mn / h.denom;
+    h.range = mx / h.denom - h.amin;
+    return h;
+}
+__device__ __forceinline__ void heat_map8(float v[8], const HeatRow& h) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = h.range > 0.f ? (fabsf(v[i]) / h.denom - h.amin) / h.range : 0.f;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void saliency_finish_kernel(const SaliencyFinishArgs a) {
     __shared__ float red[3][4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, row = blockIdx.x;
+    const int t = threadIdx.x, row = blockIdx.x;
     const T* g = (const T*)a.g + (long)row * a.ldg;
     float* out = a.out + (long)row * a.ldo;
-    float denom = 1.f, amin = 0.f, range = 0.f;
+    HeatRow hr = {1.f, 0.f, 0.f};
     if (a.mode == SAL_HEATMAP) {
         float ss = 0.f, mx = 0.f, mn = 3.0e38f;
         for (int c = t * 8; c < a.cols; c += 2048) {       // (ldg is a multiple of 8: the group lies inside the padded row)
             float v[8];
             load8<T>(g + c, v);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                if (c + i < a.cols) { ss = fmaf(v[i], v[i], ss); mx = fmaxf(mx, fabsf(v[i])); mn = fminf(mn, fabsf(v[i])); }
-            }
+            heat_accum(v, c, a.cols, ss, mx, mn);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            ss += __shfl_xor(ss, o, 64); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); mn = fminf(mn, __shfl_xor(mn, o, 64));
-        }
-        if (lane == 0) { red[0][wave] = ss; red[1][wave] = mx; red[2][wave] = mn; }
-        __syncthreads();
-        ss = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        mx = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
-        mn = fminf(fminf(red[2][0], red[2][1]), fminf(red[2][2], red[2][3]));
-        denom = sqrtf(ss / (float)a.cols) + 1e-5f;
-        amin = mn / denom;
-        range = mx / denom - amin;
+        hr = heat_row(ss, mx, mn, a.cols, red);
     }
     const bool vec = (((uintptr_t)out) & 15) == 0;
     for (int c = t * 8; c < a.cols; c += 2048) {
         float v[8];
         load8<T>(g + c, v);
-        if (a.mode == SAL_HEATMAP) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = range > 0.f ? (fabsf(v[i]) / denom - amin) / range : 0.f;
-        }
+        if (a.mode == SAL_HEATMAP) heat_map8(v, hr);
         if (vec && c + 7 < a.cols) store8<float>(out + c, v);
+        else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) if (c + i < a.cols) out[c + i] = v[i];
+        }
+    }
+}
+
+// =========================================================================================
+// attribution over draws (mrgan_attribution)
+// =========================================================================================
+// path stage: block = 256 threads x 8 consecutive columns of one row (grid.y = rows); AttrAccumArgs / PathStageArgs, aux_kernels.h
+template <typename T>
+__global__ __launch_bounds__(256) void path_stage_kernel(const PathStageArgs a) {
+    const int row = blockIdx.y, c = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 8;
+    if (c >= a.cols_pad) return;                                   // (cols_pad is a multiple of 8: the group lies inside it)
+    const float* src = a.src + (a.idx ? (long)a.idx[row] : (long)row) * a.ld + c;
+    float v[8], b[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { v[i] = 0.f; b[i] = 0.f; }
+    if (c + 7 < a.cols && (a.ld & 3) == 0 && ((uintptr_t)a.src & 15) == 0) load8<float>(src, v);
+    else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) if (c + i < a.cols) v[i] = src[i];
+    }
+    if (a.baseline) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) if (c + i < a.cols) b[i] = a.baseline[c + i];
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = c + i < a.cols ? fmaf(a.alpha, v[i] - b[i], b[i]) : 0.f;
+    store8<T>((T*)a.out + (long)row * a.ldo + c, v);
+}
+
+// accumulate: one block = one row, thread <-> 8 consecutive columns, every 2048th group (saliency_finish_kernel's pattern).
+// Each thread reads and writes only its own columns of out, so the second pass of the heat-map reads back what the same
+// thread stored; the reductions are heat_row's: draws = 1 without multiply gives saliency_finish_kernel's bits.
+template <typename T>
+__global__ __launch_bounds__(256) void attribution_accum_kernel(const AttrAccumArgs a) {
+    __shared__ float red[3][4];
+    const int t = threadIdx.x, row = blockIdx.x;
+    const T* g = (const T*)a.g + (long)row * a.ldg;
+    float* out = a.out + (long)row * a.ldo;
+    const bool last = a.draw == a.draws - 1, heat = last && a.mode == SAL_HEATMAP;
+    const bool vec = (((uintptr_t)out) & 15) == 0;
+    const float* xr = (last && a.multiply) ? a.x + (a.idx ? (long)a.idx[row] : (long)row) * a.ld_x : nullptr;
+    const float ndraws = (float)a.draws;
+    float ss = 0.f, mx = 0.f, mn = 3.0e38f;
+    for (int c = t * 8; c < a.cols; c += 2048) {           // (ldg is a multiple of 8: the group lies inside the padded row)
+        float v[8];
+        load8<T>(g + c, v);
+        const bool full = vec && c + 7 < a.cols;
+        if (a.draw > 0) {
+            float o[8];
+            if (full) load8<float>(out + c, o);
+            else {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) o[i] = c + i < a.cols ? out[c + i] : 0.f;
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = o[i] + v[i];
+        }
+        if (last) {
+            if (a.draws > 1) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = v[i] / ndraws;
+            }
+            if (xr) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    if (c + i < a.cols) v[i] *= xr[c + i] - (a.baseline ? a.baseline[c + i] : 0.f);
+            }
+            if (heat) heat_accum(v, c, a.cols, ss, mx, mn);
+        }
+        if (full) store8<float>(out + c, v);
+        else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) if (c + i < a.cols) out[c + i] = v[i];
+        }
+    }
+    if (!heat) return;                                     // (block-uniform)
+    const HeatRow hr = heat_row(ss, mx, mn, a.cols, red);
+    for (int c = t * 8; c < a.cols; c += 2048) {
+        float v[8];
+        const bool full = vec && c + 7 < a.cols;
+        if (full) load8<float>(out + c, v);
+        else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = c + i < a.cols ? out[c + i] : 0.f;
+        }
+        heat_map8(v, hr);
+        if (full) store8<float>(out + c, v);
         else {
 #pragma unroll
             for (int i = 0; i < 8; ++i) if (c + i < a.cols) out[c + i] = v[i];
@@ -1011,6 +1116,23 @@ int launch_saliency_finish(int bf16, const SaliencyFinishArgs& a, hipStream_t s)
     if (a.rows <= 0) return 0;
     if ((a.mode != SAL_RAW && a.mode != SAL_HEATMAP) || a.cols <= 0 || a.cols > a.ldg || (a.ldg % 8) != 0 || a.ldo < a.cols) return -3;
     LAUNCH_T(saliency_finish_kernel, dim3(a.rows), dim3(256), 0, s, a);
+    RET_LAUNCH;
+}
+
+int launch_path_stage(int bf16, const PathStageArgs& a, hipStream_t s) {
+    if (a.rows <= 0) return 0;
+    if (!a.src || !a.out || a.cols <= 0 || a.cols > a.cols_pad || (a.cols_pad % 8) != 0 || a.ldo < a.cols_pad || (a.ldo % 8) != 0 || a.ld < a.cols)
+        return -3;
+    LAUNCH_T(path_stage_kernel, dim3(ceil_div(a.cols_pad, 2048), a.rows), dim3(256), 0, s, a);
+    RET_LAUNCH;
+}
+
+int launch_attr_accum(int bf16, const AttrAccumArgs& a, hipStream_t s) {
+    if (a.rows <= 0) return 0;
+    if ((a.mode != SAL_RAW && a.mode != SAL_HEATMAP) || a.cols <= 0 || a.cols > a.ldg || (a.ldg % 8) != 0 || a.ldo < a.cols) return -3;
+    if (a.draws < 1 || a.draw < 0 || a.draw >= a.draws || !a.g || !a.out) return -3;
+    if (a.multiply && (!a.x || a.ld_x < a.cols)) return -3;
+    LAUNCH_T(attribution_accum_kernel, dim3(a.rows), dim3(256), 0, s, a);
     RET_LAUNCH;
 }
 

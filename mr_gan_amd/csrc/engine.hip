@@ -116,6 +116,9 @@ const ColSums NO_SUMS = {CS_NONE, nullptr, nullptr};
 //             layer's own images first
 struct Fp8Use { const Dense* to; bool wgrad, quant_in; };
 const Fp8Use NO_FP8 = {nullptr, false, false};
+// mrgan_attribution: what keys the noise of draw d of an evaluation forward -- a constant state slot whose iter is d
+// (mrgan_handle::draw_state), the selected model's seed and the chunk's first row
+struct DrawKey { const DevState* st; uint64_t seed; uint32_t row0; };
 
 ReluMask relu_mask(const mrgan_handle* h, int l) { return ReluMask{h->mask[l], h->ldm[l]}; }
 void epi_mask(mrgan_handle* h, Epi& e, const ReluMask& m) {
@@ -151,7 +154,7 @@ int fp8_quant_images(mrgan_handle* h, const void* src, int width, int nb, unsign
 
 // Y = act(X W + b): X [nb][S][Kp] -> out [nb][S][Np]
 int dense_fwd(mrgan_handle* h, const Dense& L, int kind, const void* x, int rows, int nb, void* out, int act, const NoiseSite& nz,
-              const ReluMask& m, const ColSums& cs, hipStream_t s, const Fp8Use& f8 = NO_FP8) {
+              const ReluMask& m, const ColSums& cs, hipStream_t s, const Fp8Use& f8 = NO_FP8, const DrawKey* dk = nullptr) {
     const Fp8Images& q = L.q;
     const bool fp8 = q.on && kind != KIND_EVAL;
     const long a_bs = (long)h->S * L.Kp;
@@ -164,6 +167,7 @@ int dense_fwd(mrgan_handle* h, const Dense& L, int kind, const void* x, int rows
     e.act = act; e.n_valid = L.N; e.bias = L.b->p;
     if (kind == KIND_EVAL) {        // evaluation runs model by model: the selected model's weights (x and out are the caller's)
         e.st = nullptr;
+        if (dk) { e.st = dk->st; e.seed = dk->seed; e.row0 = dk->row0; }      // (noise of an attribution draw)
         g.B = selected(h, g.B); e.bias = selected(h, e.bias);
     }
     e.out = out; e.out_bs = (long)h->S * L.Np; e.ldo = L.Np;
@@ -912,29 +916,36 @@ int eval_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, cons
     return rezero_padding(h, 5, 3, false, s);      // the chunks reach rows [0, 3S); xin[0]: all five segments, whatever n
 }
 
+// the backward half of a chunk: the per-row saliency head of `objective` (targets, or null: the row's argmax; classes_out optional)
+// into dpre[4], the masked dX chain down to layer 1 and the linear layer-0 dX into dxfake
+int saliency_backward(mrgan_handle* h, int objective, const int32_t* targets, int32_t* classes_out, int rows, hipStream_t s) {
+    static const int kinds[3] = {HEAD_SAL_LOGIT, HEAD_SAL_XENT, HEAD_SAL_MSE};
+    HeadArgs hd = head_args(h, {kinds[objective]}, rows, false);
+    hd.f = selected(h, hd.f); hd.w = selected(h, hd.w); hd.b = selected(h, hd.b); hd.logits = nullptr;
+    hd.labels = targets;
+    hd.classes_out = classes_out;
+    hd.dpre = selected(h, h->dpre[4]); hd.ldd = h->Fp;
+    PROF("head_kernel", launch_head(h->bf16, hd, s));
+    for (int l = 4; l >= 1; --l)
+        CHK(dense_dx(h, h->d[l], KIND_EVAL, selected(h, h->dpre[l]), rows, 1, selected(h, h->dpre[l - 1]), ACT_RELU, h->d[l - 1].N, eval_mask(h, l - 1),
+                     nullptr, NO_SUMS, s));
+    CHK(dense_dx(h, h->d[0], KIND_EVAL, selected(h, h->dpre[0]), rows, 1, selected(h, h->dxfake), ACT_LINEAR, h->cfg.d_in, NO_MASK, nullptr,
+                 NO_SUMS, s));
+    return 0;
+}
 // Input-gradient saliency of n rows (mrgan_input_gradient): per chunk the evaluation forward WITH its relu masks, the per-row
 // saliency head into dpre[4], the masked dX chain down to layer 1, the linear layer-0 dX into dxfake and the finishing kernel
 // into the caller's rows.  Everything lives in segment 0 of the training activations (xin[l], mask[l], dpre[l], feat) as one
 // run of contiguous rows; dxfake holds S rows, which is what bounds the chunk.  No noise, no state slot, no column sums, no
 // weight gradients: cur, the counters and the cached graph are not touched.
 int saliency_rows(mrgan_handle* h, const mrgan_saliency_args* a, hipStream_t s) {
-    static const int kinds[3] = {HEAD_SAL_LOGIT, HEAD_SAL_XENT, HEAD_SAL_MSE};
     const long cap = h->S, n = a->n;
     for (long r0 = 0; r0 < n; r0 += cap) {
         const int rows = (int)std::min(cap, n - r0);
         const int r = eval_forward(h, a->x_dev, a->idx_dev, a->ld_x, r0, rows, true, s);
         if (r) return r;
-        HeadArgs hd = head_args(h, {kinds[a->objective]}, rows, false);
-        hd.f = selected(h, hd.f); hd.w = selected(h, hd.w); hd.b = selected(h, hd.b); hd.logits = nullptr;
-        hd.labels = a->targets_dev ? a->targets_dev + r0 : nullptr;
-        hd.classes_out = a->classes_out_dev ? a->classes_out_dev + r0 : nullptr;
-        hd.dpre = selected(h, h->dpre[4]); hd.ldd = h->Fp;
-        PROF("head_kernel", launch_head(h->bf16, hd, s));
-        for (int l = 4; l >= 1; --l)
-            CHK(dense_dx(h, h->d[l], KIND_EVAL, selected(h, h->dpre[l]), rows, 1, selected(h, h->dpre[l - 1]), ACT_RELU, h->d[l - 1].N, eval_mask(h, l - 1),
-                         nullptr, NO_SUMS, s));
-        CHK(dense_dx(h, h->d[0], KIND_EVAL, selected(h, h->dpre[0]), rows, 1, selected(h, h->dxfake), ACT_LINEAR, h->cfg.d_in, NO_MASK, nullptr,
-                     NO_SUMS, s));
+        CHK(saliency_backward(h, a->objective, a->targets_dev ? a->targets_dev + r0 : nullptr,
+                              a->classes_out_dev ? a->classes_out_dev + r0 : nullptr, rows, s));
         SaliencyFinishArgs f;
         memset(&f, 0, sizeof f);
         f.g = selected(h, h->dxfake); f.ldg = h->Dp; f.rows = rows; f.cols = h->cfg.d_in;
@@ -942,6 +953,77 @@ int saliency_rows(mrgan_handle* h, const mrgan_saliency_args* a, hipStream_t s) 
         PROFB("saliency_finish_kernel", launch_saliency_finish(h->bf16, f, s), (double)rows * h->cfg.d_in * (2.0 * h->es + 4.0));
     }
     return n > h->B ? rezero_padding(h, 1, 1, true, s) : 0;      // (no chunk reached the padding rows of segment 0 otherwise)
+}
+
+// Attribution over draws (mrgan_attribution).  Per chunk of at most S rows: the target classes (given, or one clean forward +
+// head when the draws themselves are not that forward), then per draw d the chunk of saliency_rows with a forward of its own
+// -- MRGAN_ATTR_NOISE: the stage and the epilogues of dense 1 .. 4 add the site's noise, keyed by slot d of draw_state (step
+// d), seed + selected model, segment id MRGAN_ATTR_NOISE_SEG and the chunk's first row; MRGAN_ATTR_PATH: the path stage at
+// alpha_d -- and the accumulate launch into the caller's rows.  Draws are the inner loop: a chunk's out rows stay in L2.
+int attribution_rows(mrgan_handle* h, const mrgan_attribution_args* a, hipStream_t s) {
+    const long cap = h->S, n = a->n;
+    const bool path = a->method == MRGAN_ATTR_PATH;
+    const float sig[2] = {path ? 0.f : a->sigma_input, path ? 0.f : a->sigma_hidden};
+    // NOISE with both sigmas 0: every draw is the clean forward at x, its head finds the predicted class itself
+    const bool clean_pass = !a->targets_dev && (path || sig[0] > 0.f || sig[1] > 0.f);
+    const uint64_t seed = h->cfg.seed + (uint64_t)h->sel;
+    for (long r0 = 0; r0 < n; r0 += cap) {
+        const int rows = (int)std::min(cap, n - r0);
+        const float* xsrc = a->idx_dev ? a->x_dev : a->x_dev + r0 * a->ld_x;
+        const int32_t* xidx = a->idx_dev ? a->idx_dev + r0 : nullptr;
+        int32_t* classes = a->classes_out_dev ? a->classes_out_dev + r0 : nullptr;
+        const int32_t* targets = a->targets_dev ? a->targets_dev + r0 : nullptr;
+        if (clean_pass) {
+            const int r = eval_forward(h, a->x_dev, a->idx_dev, a->ld_x, r0, rows, false, s);
+            if (r) return r;
+            HeadArgs hd = head_args(h, {HEAD_SAL_LOGIT}, rows, false);      // (for its argmax: dpre[4] is rewritten by every draw)
+            hd.f = selected(h, hd.f); hd.w = selected(h, hd.w); hd.b = selected(h, hd.b); hd.logits = nullptr;
+            hd.labels = nullptr; hd.classes_out = classes;
+            hd.dpre = selected(h, h->dpre[4]); hd.ldd = h->Fp;
+            PROF("head_kernel", launch_head(h->bf16, hd, s));
+            targets = classes;
+        }
+        for (int d = 0; d < a->draws; ++d) {
+            const DrawKey dk = {h->draw_state + d, seed, (uint32_t)r0};
+            if (path) {
+                PathStageArgs ps;
+                memset(&ps, 0, sizeof ps);
+                ps.src = xsrc; ps.idx = xidx; ps.ld = a->ld_x; ps.baseline = a->baseline_dev;
+                ps.alpha = ((float)d + 0.5f) / (float)a->draws;
+                ps.rows = rows; ps.cols = h->cfg.d_in; ps.cols_pad = h->Dp; ps.out = selected(h, h->xin[0]); ps.ldo = h->Dp;
+                PROFB("path_stage_kernel", launch_path_stage(h->bf16, ps, s), (double)rows * h->cfg.d_in * (4.0 + h->es));
+            } else {
+                StageArgs st;
+                memset(&st, 0, sizeof st);
+                StageSeg& sg = st.s[0];
+                sg.src = xsrc; sg.idx = xidx; sg.ld = a->ld_x; sg.rows = rows;
+                sg.cols = h->cfg.d_in; sg.cols_pad = h->Dp; sg.out = selected(h, h->xin[0]); sg.ldo = h->Dp;
+                sg.sigma = sig[0]; sg.site = 0; sg.seg = MRGAN_ATTR_NOISE_SEG;
+                st.nseg = 1; st.seed = seed; st.row0 = (uint32_t)r0; st.cur = h->draw_state + d;
+                st.gauss = sig[0] > 0.f ? h->gauss : 0;      // (sigma 0: the instantiation eval_forward launches)
+                PROF("stage_kernel", launch_stage(h->bf16, st, s));
+            }
+            for (int l = 0; l < 5; ++l) {
+                const bool noisy = l < 4 && sig[1] > 0.f;
+                const NoiseSite nz = {sig[1], (uint32_t)(l + 1), (uint32_t)MRGAN_ATTR_NOISE_SEG, 1, 0};
+                CHK(dense_fwd(h, h->d[l], KIND_EVAL, selected(h, h->xin[l]), rows, 1, selected(h, l < 4 ? h->xin[l + 1] : h->feat), ACT_RELU,
+                              noisy ? nz : NO_NOISE, eval_mask(h, l), NO_SUMS, s, NO_FP8, noisy ? &dk : nullptr));
+            }
+            // draw 0 reports the classes unless the clean pass has; without targets (the noise-free call) its head finds them, and
+            // the later draws read them back
+            CHK(saliency_backward(h, a->objective, targets, (d == 0 && targets != classes) ? classes : nullptr, rows, s));
+            if (!targets) targets = classes;
+            AttrAccumArgs f;
+            memset(&f, 0, sizeof f);
+            f.g = selected(h, h->dxfake); f.ldg = h->Dp; f.rows = rows; f.cols = h->cfg.d_in;
+            f.out = a->out_dev + r0 * a->ld_out; f.ldo = a->ld_out; f.mode = a->post == MRGAN_SAL_HEATMAP ? SAL_HEATMAP : SAL_RAW;
+            f.draw = d; f.draws = a->draws; f.multiply = a->multiply;
+            f.x = xsrc; f.idx = xidx; f.ld_x = a->ld_x; f.baseline = a->baseline_dev;
+            PROFB("attribution_accum_kernel", launch_attr_accum(h->bf16, f, s),
+                  (double)rows * h->cfg.d_in * (h->es + (d > 0 ? 8.0 : 4.0) + (a->multiply && d == a->draws - 1 ? 4.0 : 0.0)));
+        }
+    }
+    return n > h->B ? rezero_padding(h, 1, 1, true, s) : 0;      // (as saliency_rows)
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1173,6 +1255,31 @@ int mrgan_input_gradient(mrgan_handle* h, const mrgan_saliency_args* a, mrgan_st
         return fail(-2, "input_gradient: unknown objective %d", (int)a->objective);
     if (a->post != MRGAN_SAL_RAW && a->post != MRGAN_SAL_HEATMAP) return fail(-2, "input_gradient: unknown post mode %d", (int)a->post);
     return saliency_rows(h, a, (hipStream_t)stream);
+}
+
+int mrgan_attribution(mrgan_handle* h, const mrgan_attribution_args* a, mrgan_stream stream) {
+    if (!h) return fail(-1, "null handle");
+    if (h->fp8) return fail(-3, "attribution: not on an fp8 handle (its dX products read fp8-scaled images and would disturb the calibration); use an fp32 or a bf16 engine");
+    if (!a || !a->x_dev || !a->out_dev) return fail(-2, "attribution: x and out are required");
+    if (a->n < 0) return fail(-2, "attribution: negative row count n");
+    if (a->ld_x < h->cfg.d_in) return fail(-2, "attribution: row pitch ld_x smaller than d_in");
+    if (a->ld_out < h->cfg.d_in) return fail(-2, "attribution: row pitch ld_out smaller than d_in");
+    if (a->objective != MRGAN_SAL_LOGIT && a->objective != MRGAN_SAL_XENT && a->objective != MRGAN_SAL_MSE)
+        return fail(-2, "attribution: unknown objective %d", (int)a->objective);
+    if (a->post != MRGAN_SAL_RAW && a->post != MRGAN_SAL_HEATMAP) return fail(-2, "attribution: unknown post mode %d", (int)a->post);
+    if (a->method != MRGAN_ATTR_NOISE && a->method != MRGAN_ATTR_PATH) return fail(-2, "attribution: unknown method %d", (int)a->method);
+    if (a->draws < 1 || a->draws > MRGAN_ATTR_MAX_DRAWS)
+        return fail(-2, "attribution: draws = %d outside [1, %d]", (int)a->draws, (int)MRGAN_ATTR_MAX_DRAWS);
+    if (a->multiply != 0 && a->multiply != 1) return fail(-2, "attribution: multiply must be 0 or 1, got %d", (int)a->multiply);
+    if (!(a->sigma_input >= 0.f) || !std::isfinite(a->sigma_input)) return fail(-2, "attribution: sigma_input must be finite and >= 0");
+    if (!(a->sigma_hidden >= 0.f) || !std::isfinite(a->sigma_hidden)) return fail(-2, "attribution: sigma_hidden must be finite and >= 0");
+    if (a->method == MRGAN_ATTR_PATH && (a->sigma_input != 0.f || a->sigma_hidden != 0.f))
+        return fail(-2, "attribution: sigma_input / sigma_hidden belong to MRGAN_ATTR_NOISE; MRGAN_ATTR_PATH is noise-free");
+    if (a->method == MRGAN_ATTR_NOISE && a->baseline_dev) return fail(-2, "attribution: baseline_dev belongs to MRGAN_ATTR_PATH");
+    if (!a->targets_dev && !a->classes_out_dev)
+        return fail(-2, "attribution: classes_out_dev is required when targets_dev is null (the predicted classes are kept there between draws)");
+    if (!h->draw_state) return fail(-1, "attribution: the handle has no draw slots");
+    return attribution_rows(h, a, (hipStream_t)stream);
 }
 
 int mrgan_profile_begin(mrgan_handle* h) {

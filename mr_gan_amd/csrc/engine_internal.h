@@ -103,6 +103,10 @@ struct mrgan_handle {
     Dense g[3], d[6];
 
     DevState* state;                      // [2]
+    // mrgan_attribution: [MRGAN_ATTR_MAX_DRAWS] constant slots, slot d with iter = d and batch = 0 -- the kernels of draw d read
+    // their noise step from slot d, so no training kernel learns about draws.  An allocation of its own (64 KB), not workspace.
+    DevState* draw_state = nullptr;
+    ~mrgan_handle() { if (draw_state) hipFree(draw_state); }
     int cur;                              // host mirror of the live slot
     float* step_out;                      // [4]
     float* accum;                         // [4]

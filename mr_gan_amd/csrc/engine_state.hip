@@ -57,6 +57,14 @@ __global__ void init_state_kernel(DevState* st, uint32_t iter, uint32_t batch, f
     s.lr_t = (float)((double)lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
     st[0] = s; st[1] = s;
 }
+// the constant slots of mrgan_attribution: slot d carries the draw index as its noise step (engine_internal.h: draw_state)
+__global__ void init_draw_state_kernel(DevState* st, int n) {
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= n) return;
+    DevState s;
+    s.iter = (uint32_t)d; s.batch = 0; s.lr_t = 0.f; s.pad = 0;
+    st[d] = s;
+}
 
 // ------------------------------------------------------------------------------------------------
 // layout
@@ -416,6 +424,10 @@ int mrgan_create(const mrgan_config* cfg, void* workspace, size_t bytes, mrgan_s
     // zero everything: padding of weights/activations must be exactly zero and stays so
     CREATE_CHK(hipMemsetAsync(h->ws, 0, h->ws_bytes, s));
     hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(1), 0, s, h->state, 0u, 0u, cfg->lr, cfg->beta1, cfg->beta2);
+    if (!h->fp8) {      // (mrgan_attribution refuses an fp8 handle)
+        CREATE_CHK(hipMalloc((void**)&h->draw_state, sizeof(DevState) * MRGAN_ATTR_MAX_DRAWS));
+        hipLaunchKernelGGL(init_draw_state_kernel, dim3(ceil_div(MRGAN_ATTR_MAX_DRAWS, 256)), dim3(256), 0, s, h->draw_state, (int)MRGAN_ATTR_MAX_DRAWS);
+    }
     r = upload_tiles(h, h->gt, h->tiles_g_dev, h->ntiles_g, s);
     if (!r) r = upload_tiles(h, h->dt, h->tiles_d_dev, h->ntiles_d, s);
     if (r) { if (h->own_ws) hipFree(h->ws); delete h; return r; }

@@ -34,11 +34,15 @@ EXPORTS = [
     "mrgan_debug_fm", "mrgan_debug_adam", "mrgan_debug_chain",
     "mrgan_select_model", "mrgan_sup_step_group",
     "mrgan_disc_step_group", "mrgan_gen_step_group", "mrgan_train_pair_group",
-    "mrgan_input_gradient",
+    "mrgan_input_gradient", "mrgan_attribution",
 ]
 SAL_LOGIT, SAL_XENT, SAL_MSE = 0, 1, 2
 SAL_RAW, SAL_HEATMAP = 0, 1
 SAL_OBJECTIVES = {'logit': SAL_LOGIT, 'xent': SAL_XENT, 'mse': SAL_MSE}
+ATTR_NOISE, ATTR_PATH = 0, 1
+ATTR_MAX_DRAWS = 4096
+ATTR_NOISE_SEG = 255          # MRGAN_ATTR_NOISE_SEG: the noise segment id of the attribution draws (no training draw uses it)
+ATTR_METHODS = ('gradient', 'smoothgrad', 'integrated')
 MAX_MODELS = 16
 PROF_NAME_LEN = 96
 
@@ -122,6 +126,67 @@ class SaliencyArgs(C.Structure):
         ("out", C.c_void_p), ("ld_out", C.c_int64),
         ("classes_out", C.c_void_p),
     ]
+
+
+class AttributionArgs(C.Structure):
+    """mrgan_attribution_args"""
+    _fields_ = SaliencyArgs._fields_ + [
+        ("method", C.c_int32), ("draws", C.c_int32),
+        ("sigma_input", C.c_float), ("sigma_hidden", C.c_float),
+        ("baseline", C.c_void_p),
+        ("multiply", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+def attribution_plan(method, draws=None, sigma=None, baseline=None, times_input=False, d_in=None, own_sigmas=(0.3, 0.5)):
+    """The keywords of MRGAN.saliency -> None for the plain gradient call (mrgan_input_gradient), else the dict of
+    Engine.attribution's keywords (method, draws, sigma_input, sigma_hidden, baseline, multiply).  Everything is checked here,
+    before any device call:
+      'gradient'    one gradient of the noise-free forward; draws, sigma and baseline do not apply; times_input: x input
+      'smoothgrad'  the mean over draws (default 16) forwards with GaussianNoise: sigma None = the network's own sigmas
+                    (own_sigmas: input, hidden), a float = input-only noise, (input, hidden) = both; times_input: x input
+      'integrated'  integrated gradients over draws (default 16) points of the path from baseline (None: zeros; else [d_in])
+                    to the row; always x (input - baseline)"""
+    if method not in ATTR_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (ATTR_METHODS, method))
+    if method == 'gradient':
+        for name, v in (('draws', draws), ('sigma', sigma), ('baseline', baseline)):
+            if v is not None:
+                raise ValueError("%s does not apply to method 'gradient' (use 'smoothgrad' or 'integrated')" % name)
+        if not times_input:
+            return None
+        return dict(method=ATTR_NOISE, draws=1, sigma_input=0.0, sigma_hidden=0.0, baseline=None, multiply=1)
+    if draws is None:
+        draws = 16
+    if isinstance(draws, bool) or not isinstance(draws, (int, np.integer)) or not 1 <= int(draws) <= ATTR_MAX_DRAWS:
+        raise ValueError("draws must be an integer in [1, %d], got %r" % (ATTR_MAX_DRAWS, draws))
+    if method == 'smoothgrad':
+        if baseline is not None:
+            raise ValueError("baseline belongs to method 'integrated', not 'smoothgrad'")
+        if sigma is None:
+            sig = tuple(own_sigmas)
+        elif isinstance(sigma, (tuple, list)):
+            if len(sigma) != 2:
+                raise ValueError("sigma must be a float (input only) or a pair (input, hidden), got %r" % (sigma,))
+            sig = tuple(sigma)
+        else:
+            sig = (sigma, 0.0)
+        try:
+            sig = (float(sig[0]), float(sig[1]))
+        except (TypeError, ValueError):
+            raise ValueError("sigma must be a float (input only) or a pair (input, hidden), got %r" % (sigma,))
+        if not all(np.isfinite(v) and v >= 0.0 for v in sig):
+            raise ValueError("sigma must be finite and >= 0, got %r" % (sigma,))
+        return dict(method=ATTR_NOISE, draws=int(draws), sigma_input=sig[0], sigma_hidden=sig[1], baseline=None,
+                    multiply=1 if times_input else 0)
+    if sigma is not None:
+        raise ValueError("sigma belongs to method 'smoothgrad'; 'integrated' is noise-free")
+    if baseline is not None:
+        baseline = np.asarray(baseline, dtype=np.float32)
+        if baseline.ndim != 1 or (d_in is not None and baseline.shape[0] != d_in) or not np.isfinite(baseline).all():
+            raise ValueError("baseline must be a finite vector of d_in%s values, got shape %s"
+                             % ("" if d_in is None else " = %d" % d_in, baseline.shape))
+    return dict(method=ATTR_PATH, draws=int(draws), sigma_input=0.0, sigma_hidden=0.0, baseline=baseline, multiply=1)
 
 
 def saliency_objective(objective):
@@ -465,6 +530,26 @@ class Engine(object):
         a.targets, a.objective, a.post = _ptr(targets), int(objective), int(post)
         a.out, a.ld_out, a.classes_out = _ptr(out), out.stride(0), _ptr(classes_out)
         _check(self.lib.mrgan_input_gradient(self.handle, C.byref(a), _stream()))
+        return out, classes_out
+
+    def attribution(self, x, targets=None, objective=SAL_XENT, post=SAL_RAW, idx=None, out=None, classes_out=None,
+                    method=ATTR_NOISE, draws=1, sigma_input=0.0, sigma_hidden=0.0, baseline=None, multiply=0):
+        """mrgan_attribution -> (maps fp32 [n, >= d_in], classes int32 [n]): input_gradient averaged over `draws` forwards on
+        the device -- ATTR_NOISE: with GaussianNoise of sigma_input at the input and sigma_hidden behind dense 1 .. 4
+        (SmoothGrad); ATTR_PATH: at the midpoints of `draws` pieces of the path from baseline (device fp32 [d_in], or None:
+        zeros) to the row -- times (x - baseline) when multiply is 1."""
+        n = x.shape[0] if idx is None else idx.numel()
+        if out is None:
+            out = torch.empty((n, self.cfg.d_in), dtype=torch.float32, device=self.device)
+        if classes_out is None:
+            classes_out = torch.empty((n,), dtype=torch.int32, device=self.device)
+        a = AttributionArgs()
+        a.x, a.idx, a.ld_x, a.n = _ptr(x), _ptr(idx), x.stride(0), n
+        a.targets, a.objective, a.post = _ptr(targets), int(objective), int(post)
+        a.out, a.ld_out, a.classes_out = _ptr(out), out.stride(0), _ptr(classes_out)
+        a.method, a.draws, a.sigma_input, a.sigma_hidden = int(method), int(draws), float(sigma_input), float(sigma_hidden)
+        a.baseline, a.multiply = _ptr(baseline), int(multiply)
+        _check(self.lib.mrgan_attribution(self.handle, C.byref(a), _stream()))
         return out, classes_out
 
     def read_metrics(self, reset=True):

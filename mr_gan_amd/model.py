@@ -132,15 +132,32 @@ class MRGAN(object):
         with self._on_stream():
             return self.engine.predict_logits(self._dev(X)).cpu().numpy()
 
-    def saliency(self, X, y=None, objective='xent', heatmap=True):
-        """Input-gradient saliency of the discriminator (the reference's others/mr_nn_activation_map.py): per row of X the
-        gradient of `objective` -- 'xent' (the labelled loss term), 'logit' (the class score) or 'mse' -- at class y[i], or at
-        the predicted class when y is None, with respect to the input; heatmap: |g / (rms(g) + 1e-5)| min-max scaled to [0, 1]
-        per row (a zero gradient gives a zero row), else the raw gradient.  -> (maps [n, D] float32, classes [n] int32)"""
+    def saliency(self, X, y=None, objective='xent', heatmap=True, method='gradient', draws=None, sigma=None, baseline=None,
+                 times_input=False):
+        """Saliency maps of the discriminator (the reference's others/mr_nn_activation_map.py): per row of X the gradient of
+        `objective` -- 'xent' (the labelled loss term), 'logit' (the class score) or 'mse' -- at class y[i], or at the
+        predicted class when y is None, with respect to the input; heatmap: |g / (rms(g) + 1e-5)| min-max scaled to [0, 1]
+        per row (a zero gradient gives a zero row), else the raw values.  method (engine.attribution_plan):
+          'gradient'    one gradient of the noise-free forward
+          'smoothgrad'  the mean over `draws` (16) forwards with GaussianNoise, accumulated on the device; sigma None: the
+                        network's own sigmas (the training forward), a float: input-only noise, (input, hidden): both
+          'integrated'  integrated gradients over `draws` (16) points of the path from `baseline` (None: zeros, the training
+                        mean of scaled data) to the row, times (x - baseline)
+        times_input multiplies the 'gradient' / 'smoothgrad' map by the input.  The noise of a 'smoothgrad' map depends on
+        the seed, the rows and the arguments only, not on how far the model has trained.
+        -> (maps [n, D] float32, classes [n] int32)"""
         code = E.saliency_objective(objective)                     # (checked before anything touches the device)
+        plan = E.attribution_plan(method, draws, sigma, baseline, times_input, d_in=self.input_dim,
+                                  own_sigmas=(float(self.engine.cfg.sigma[0]), float(self.engine.cfg.sigma[1])))
+        post = E.SAL_HEATMAP if heatmap else E.SAL_RAW
         with self._on_stream():
-            maps, cls = self.engine.input_gradient(self._dev(X), None if y is None else self._dev(y, torch.int32), code,
-                                                   E.SAL_HEATMAP if heatmap else E.SAL_RAW)
+            x, t = self._dev(X), None if y is None else self._dev(y, torch.int32)
+            if plan is None:
+                maps, cls = self.engine.input_gradient(x, t, code, post)
+            else:
+                if plan['baseline'] is not None:
+                    plan['baseline'] = self._dev(plan['baseline'])
+                maps, cls = self.engine.attribution(x, t, code, post, **plan)
             return maps.cpu().numpy(), cls.cpu().numpy()
 
     def evaluate(self, X, y):
@@ -328,11 +345,13 @@ class MRGANGroup(object):
             self.engine.select_model(m)
             return self.engine.predict_logits(self._dev(X)).cpu().numpy()
 
-    def saliency(self, m, X, y=None, objective='xent', heatmap=True):
-        """MRGAN.saliency of model m"""
-        E.saliency_objective(objective)                            # (an unknown one is refused before the selection moves)
+    def saliency(self, m, X, y=None, objective='xent', heatmap=True, **kw):
+        """MRGAN.saliency of model m (kw: method, draws, sigma, baseline, times_input)"""
+        E.saliency_objective(objective)                            # (unknown ones are refused before the selection moves)
+        E.attribution_plan(kw.get('method', 'gradient'), kw.get('draws'), kw.get('sigma'), kw.get('baseline'),
+                           kw.get('times_input', False), d_in=self.input_dim)
         self.engine.select_model(m)
-        return MRGAN.saliency(self, X, y, objective, heatmap)
+        return MRGAN.saliency(self, X, y, objective, heatmap, **kw)
 
     def evaluate(self, Xs, ys):
         """[test error of model m over (Xs[m], ys[m])], model by model"""

@@ -116,10 +116,10 @@ class MRNN(object):
         with torch.cuda.stream(self.stream):
             return self.engine.eval_error(self._dev(X), self._dev(y, torch.int32))
 
-    def saliency(self, X, y=None, objective='mse', heatmap=True):
-        """MRGAN.saliency for the baseline; the default objective is its training loss, as in the reference's
-        others/mr_nn_activation_map.py -> (maps [n, D] float32, classes [n] int32)"""
-        return MRGAN.saliency(self, X, y, objective, heatmap)
+    def saliency(self, X, y=None, objective='mse', heatmap=True, **kw):
+        """MRGAN.saliency for the baseline (kw: method, draws, sigma, baseline, times_input); the default objective is its
+        training loss, as in the reference's others/mr_nn_activation_map.py -> (maps [n, D] float32, classes [n] int32)"""
+        return MRGAN.saliency(self, X, y, objective, heatmap, **kw)
 
 
 class MRNNGroup(object):

@@ -3,6 +3,9 @@
 mrgan_profile_end) for the per-kernel split.
 
     python scripts/saliency_bench.py [--d 1200 --rows 1200 --batches 50 4096 --dtype bf16 --reps 20]
+    python scripts/saliency_bench.py --method smoothgrad --draws 16      (or --method integrated)
+With --method the line also carries one mrgan_attribution call of `draws` draws (smoothgrad: the network's own sigmas;
+integrated: zero baseline, times the input) beside `draws` plain calls timed in the same run, and its per-kernel split.
 Prints one JSON line per batch size."""
 import argparse
 import json
@@ -42,6 +45,8 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[50, 4096])
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--method", default=None, choices=["smoothgrad", "integrated"])
+    ap.add_argument("--draws", type=int, default=16)
     args = ap.parse_args()
     rs = np.random.RandomState(3)
     X = rs.randn(args.rows, args.d).astype(np.float32)
@@ -59,6 +64,15 @@ def main():
             res["predict_logits_ms"] = round(timed(lambda: eng.predict_logits(x), args.reps, m.stream), 4)
             res["input_gradient_kernels"] = profiled(eng, lambda: eng.input_gradient(x, None, E.SAL_XENT, E.SAL_HEATMAP, out=out, classes_out=cls))
             res["predict_logits_kernels"] = profiled(eng, lambda: eng.predict_logits(x))
+            if args.method:
+                kw = dict(E.attribution_plan(args.method, args.draws, own_sigmas=(float(eng.cfg.sigma[0]), float(eng.cfg.sigma[1]))))
+                attr = lambda: eng.attribution(x, None, E.SAL_XENT, E.SAL_HEATMAP, out=out, classes_out=cls, **kw)
+                plain = lambda: eng.input_gradient(x, None, E.SAL_XENT, E.SAL_HEATMAP, out=out, classes_out=cls)
+                reps = max(2, args.reps // 4)
+                res.update(method=args.method, draws=args.draws)
+                res["attribution_ms"] = round(timed(attr, reps, m.stream), 4)
+                res["plain_calls_ms"] = round(timed(lambda: [plain() for _ in range(args.draws)], reps, m.stream), 4)      # draws x the plain call
+                res["attribution_kernels"] = profiled(eng, attr)
         eng.close()
         print(json.dumps(res))
         sys.stdout.flush()
