@@ -109,15 +109,8 @@ int init_kernel_attributes();
 // 1e-5), a = |g_hat|, out = (a - min a) / (max a - min a), mean and extrema over the row's `cols` columns.  A row with max a ==
 // min a (an all-dead row: zero gradient) is written as zeros, where the reference divides 0 by 0.
 enum { SAL_RAW = 0, SAL_HEATMAP = 1 };
-struct SaliencyFinishArgs {
-    const void* g; int ldg;                    // T [rows][ldg]
-    int rows, cols;
-    float* out; long ldo;                      // [rows][ldo], columns >= cols are left alone
-    int mode;
-};
-int launch_saliency_finish(int bf16, const SaliencyFinishArgs& a, hipStream_t s);
 
-// ---- attribution over draws (mrgan_attribution): a path point as the discriminator's input, and the accumulator ----
+// ---- maps over draws (mrgan_attribution; mrgan_input_gradient is one draw): a path point as the input, and the accumulator ----
 // out[r][c] = T(fmaf(alpha, x[r][c] - b[c], b[c])) for c < cols, 0 for cols <= c < cols_pad; row r of x is
 // src[(idx ? idx[r] : r) * ld + c], b = baseline[c] or 0.  The gather of the stage kernel without its noise.
 struct PathStageArgs {

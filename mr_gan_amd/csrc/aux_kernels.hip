@@ -502,11 +502,7 @@ __global__ __launch_bounds__(256) void head_kernel(const HeadArgs a) {
 }
 
 // =========================================================================================
-// saliency finish: one block = one row of the layer-0 dX (T, pitch ldg) -> one fp32 row of the caller (SaliencyFinishArgs).
-// thread <-> 8 consecutive columns, every 2048th column group; the row is read twice (second time from cache).  SAL_HEATMAP:
-// sum g^2, max |g| and min |g| of the row by wave shuffles, then over the four waves through LDS in wave order -- no
-// atomics: the same bits on every call.  |g| / denom is monotone in |g|, so min a and max a are the quotients of min |g| and
-// max |g|, and the elements that attain them come out as exactly 0 and 1.
+// saliency maps (mrgan_input_gradient, mrgan_attribution): the layer-0 dX of a draw -> the caller's fp32 rows
 // =========================================================================================
 // the heat-map's row statistics (one block = one row, every thread calls): a thread's sum g^2, max |g| and min |g| over its
 // columns -> the row's denominator rms + 1e-5, min a and max a - min a
@@ -539,38 +535,6 @@ __device__ __forceinline__ void heat_map8(float v[8], const HeatRow& h) {
     for (int i = 0; i < 8; ++i) v[i] = h.range > 0.f ? (fabsf(v[i]) / h.denom - h.amin) / h.range : 0.f;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void saliency_finish_kernel(const SaliencyFinishArgs a) {
-    __shared__ float red[3][4];
-    const int t = threadIdx.x, row = blockIdx.x;
-    const T* g = (const T*)a.g + (long)row * a.ldg;
-    float* out = a.out + (long)row * a.ldo;
-    HeatRow hr = {1.f, 0.f, 0.f};
-    if (a.mode == SAL_HEATMAP) {
-        float ss = 0.f, mx = 0.f, mn = 3.0e38f;
-        for (int c = t * 8; c < a.cols; c += 2048) {       // (ldg is a multiple of 8: the group lies inside the padded row)
-            float v[8];
-            load8<T>(g + c, v);
-            heat_accum(v, c, a.cols, ss, mx, mn);
-        }
-        hr = heat_row(ss, mx, mn, a.cols, red);
-    }
-    const bool vec = (((uintptr_t)out) & 15) == 0;
-    for (int c = t * 8; c < a.cols; c += 2048) {
-        float v[8];
-        load8<T>(g + c, v);
-        if (a.mode == SAL_HEATMAP) heat_map8(v, hr);
-        if (vec && c + 7 < a.cols) store8<float>(out + c, v);
-        else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) if (c + i < a.cols) out[c + i] = v[i];
-        }
-    }
-}
-
-// =========================================================================================
-// attribution over draws (mrgan_attribution)
-// =========================================================================================
 // path stage: block = 256 threads x 8 consecutive columns of one row (grid.y = rows); AttrAccumArgs / PathStageArgs, aux_kernels.h
 template <typename T>
 __global__ __launch_bounds__(256) void path_stage_kernel(const PathStageArgs a) {
@@ -594,9 +558,13 @@ __global__ __launch_bounds__(256) void path_stage_kernel(const PathStageArgs a) 
     store8<T>((T*)a.out + (long)row * a.ldo + c, v);
 }
 
-// accumulate: one block = one row, thread <-> 8 consecutive columns, every 2048th group (saliency_finish_kernel's pattern).
-// Each thread reads and writes only its own columns of out, so the second pass of the heat-map reads back what the same
-// thread stored; the reductions are heat_row's: draws = 1 without multiply gives saliency_finish_kernel's bits.
+// accumulate (the only kernel that writes a map): one block = one row of the layer-0 dX (T, pitch ldg) -> one fp32 row of the
+// caller (AttrAccumArgs), thread <-> 8 consecutive columns, every 2048th column group.  Each thread reads and writes only its
+// own columns of out, so the second pass of the heat-map reads back what the same thread stored (or, for the one-draw map
+// without multiply, the same values from g again: measured, profiles/README.md).  SAL_HEATMAP: sum g^2, max |g|
+// and min |g| of the row by wave shuffles, then over the four waves through LDS in wave order -- no atomics: the same bits on
+// every call.  |g| / denom is monotone in |g|, so min a and max a are the quotients of min |g| and max |g|, and the elements
+// that attain them come out as exactly 0 and 1.
 template <typename T>
 __global__ __launch_bounds__(256) void attribution_accum_kernel(const AttrAccumArgs a) {
     __shared__ float red[3][4];
@@ -604,6 +572,7 @@ __global__ __launch_bounds__(256) void attribution_accum_kernel(const AttrAccumA
     const T* g = (const T*)a.g + (long)row * a.ldg;
     float* out = a.out + (long)row * a.ldo;
     const bool last = a.draw == a.draws - 1, heat = last && a.mode == SAL_HEATMAP;
+    const bool once = heat && a.draws == 1 && !a.multiply;     // the map of g itself: g is read twice, out written once (block-uniform)
     const bool vec = (((uintptr_t)out) & 15) == 0;
     const float* xr = (last && a.multiply) ? a.x + (a.idx ? (long)a.idx[row] : (long)row) * a.ld_x : nullptr;
     const float ndraws = (float)a.draws;
@@ -634,6 +603,7 @@ __global__ __launch_bounds__(256) void attribution_accum_kernel(const AttrAccumA
             }
             if (heat) heat_accum(v, c, a.cols, ss, mx, mn);
         }
+        if (once) continue;
         if (full) store8<float>(out + c, v);
         else {
 #pragma unroll
@@ -645,7 +615,8 @@ __global__ __launch_bounds__(256) void attribution_accum_kernel(const AttrAccumA
     for (int c = t * 8; c < a.cols; c += 2048) {
         float v[8];
         const bool full = vec && c + 7 < a.cols;
-        if (full) load8<float>(out + c, v);
+        if (once) load8<T>(g + c, v);
+        else if (full) load8<float>(out + c, v);
         else {
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] = c + i < a.cols ? out[c + i] : 0.f;
@@ -1109,13 +1080,6 @@ int launch_head(int bf16, const HeadArgs& a, hipStream_t s) {
     } else {
         LAUNCH_T(head_kernel, grid, dim3(256), smem, s, a);
     }
-    RET_LAUNCH;
-}
-
-int launch_saliency_finish(int bf16, const SaliencyFinishArgs& a, hipStream_t s) {
-    if (a.rows <= 0) return 0;
-    if ((a.mode != SAL_RAW && a.mode != SAL_HEATMAP) || a.cols <= 0 || a.cols > a.ldg || (a.ldg % 8) != 0 || a.ldo < a.cols) return -3;
-    LAUNCH_T(saliency_finish_kernel, dim3(a.rows), dim3(256), 0, s, a);
     RET_LAUNCH;
 }
 

@@ -858,21 +858,59 @@ int refuse_group(const mrgan_handle* h, const char* entry) {
 // ---------------------------------------------------------------------------------------------------
 ReluMask eval_mask(const mrgan_handle* h, int l) { return ReluMask{selected(h, h->mask[l]), h->ldm[l]}; }
 
+// what makes an evaluation forward draw d of mrgan_attribution.  MRGAN_ATTR_NOISE: the stage and the epilogues of dense 1 .. 4
+// add the site's noise (sigma_in at site 0, sigma_hid at sites 1 .. 4) under `key`, segment id MRGAN_ATTR_NOISE_SEG;
+// MRGAN_ATTR_PATH (path): the noise-free forward at the point alpha of the way from the baseline (null: zeros) to the row
+struct Draw { DrawKey key; float sigma_in, sigma_hid; bool path; float alpha; const float* baseline; };
+
 // One chunk: `rows` rows from r0 of the caller's matrix (gathered through idx when given) -> xin[0], then dense 1..5 -> feat,
 // as one run of contiguous rows from row 0 (nb = 1: the batch stride is irrelevant).  keep_masks: the relu masks are
-// written for a dX chain that follows.  A group handle evaluates the selected model: its activations here, its weights in dense_fwd.
-int eval_forward(mrgan_handle* h, const float* x, const int32_t* idx, long ld, long r0, int rows, bool keep_masks, hipStream_t s) {
-    StageArgs st;
-    memset(&st, 0, sizeof st);
-    StageSeg& sg = st.s[0];
-    sg.src = idx ? x : x + r0 * ld; sg.idx = idx ? idx + r0 : nullptr; sg.ld = ld; sg.rows = rows;
-    sg.cols = h->cfg.d_in; sg.cols_pad = h->Dp; sg.out = selected(h, h->xin[0]); sg.ldo = h->Dp;
-    st.nseg = 1; st.seed = h->cfg.seed; st.cur = h->state + h->cur;
-    PROF("stage_kernel", launch_stage(h->bf16, st, s));
-    for (int l = 0; l < 5; ++l)
-        CHK(dense_fwd(h, h->d[l], KIND_EVAL, selected(h, h->xin[l]), rows, 1, selected(h, l < 4 ? h->xin[l + 1] : h->feat), ACT_RELU, NO_NOISE,
-                      keep_masks ? eval_mask(h, l) : NO_MASK, NO_SUMS, s));
+// written for a dX chain that follows.  draw: null for the noise-free forward at the rows themselves (no state slot beside the
+// current one, the plain stage instantiation).  A group handle evaluates the selected model: its activations here, its weights
+// in dense_fwd.
+int eval_forward(mrgan_handle* h, const float* x, const int32_t* idx, long ld, long r0, int rows, bool keep_masks, hipStream_t s,
+                 const Draw* draw = nullptr) {
+    const float* src = idx ? x : x + r0 * ld;
+    const int32_t* ridx = idx ? idx + r0 : nullptr;
+    if (draw && draw->path) {
+        PathStageArgs ps;
+        memset(&ps, 0, sizeof ps);
+        ps.src = src; ps.idx = ridx; ps.ld = ld; ps.baseline = draw->baseline; ps.alpha = draw->alpha;
+        ps.rows = rows; ps.cols = h->cfg.d_in; ps.cols_pad = h->Dp; ps.out = selected(h, h->xin[0]); ps.ldo = h->Dp;
+        PROFB("path_stage_kernel", launch_path_stage(h->bf16, ps, s), (double)rows * h->cfg.d_in * (4.0 + h->es));
+    } else {
+        StageArgs st;
+        memset(&st, 0, sizeof st);
+        StageSeg& sg = st.s[0];
+        sg.src = src; sg.idx = ridx; sg.ld = ld; sg.rows = rows;
+        sg.cols = h->cfg.d_in; sg.cols_pad = h->Dp; sg.out = selected(h, h->xin[0]); sg.ldo = h->Dp;
+        st.nseg = 1; st.seed = h->cfg.seed; st.cur = h->state + h->cur;
+        if (draw) {
+            sg.sigma = draw->sigma_in; sg.site = 0; sg.seg = MRGAN_ATTR_NOISE_SEG;
+            st.seed = draw->key.seed; st.row0 = draw->key.row0; st.cur = draw->key.st;
+            st.gauss = draw->sigma_in > 0.f ? h->gauss : 0;      // (sigma 0: the instantiation of the noise-free forward)
+        }
+        PROF("stage_kernel", launch_stage(h->bf16, st, s));
+    }
+    for (int l = 0; l < 5; ++l) {
+        const bool noisy = draw && l < 4 && draw->sigma_hid > 0.f;
+        const NoiseSite nz = {noisy ? draw->sigma_hid : 0.f, (uint32_t)(l + 1), (uint32_t)MRGAN_ATTR_NOISE_SEG, 1, 0};
+        CHK(dense_fwd(h, h->d[l], KIND_EVAL, selected(h, h->xin[l]), rows, 1, selected(h, l < 4 ? h->xin[l + 1] : h->feat), ACT_RELU,
+                      noisy ? nz : NO_NOISE, keep_masks ? eval_mask(h, l) : NO_MASK, NO_SUMS, s, NO_FP8, noisy ? &draw->key : nullptr));
+    }
     return 0;
+}
+
+// the head of such a chunk on the selected model: `kind` over `rows` rows of feat with `labels` (null where the kind takes
+// none).  HEAD_EVAL / HEAD_LOGITS keep the logits; the saliency kinds (want_dpre) write the per-row dpre[4] instead -- at
+// labels, or null: at the row's argmax -- and report the class each row used to classes_out where given
+HeadArgs eval_head(mrgan_handle* h, int kind, const int32_t* labels, int32_t* classes_out, bool want_dpre, int rows) {
+    HeadArgs hd = head_args(h, {kind}, rows, false);
+    hd.f = selected(h, hd.f); hd.w = selected(h, hd.w); hd.b = selected(h, hd.b);
+    hd.logits = want_dpre ? nullptr : selected(h, hd.logits);
+    hd.labels = labels; hd.classes_out = classes_out;
+    if (want_dpre) { hd.dpre = selected(h, h->dpre[4]); hd.ldd = h->Fp; }
+    return hd;
 }
 
 // The chunks above fill rows from row 0 of every layer input, i.e. also the padding rows B .. S of the training segments they
@@ -904,9 +942,7 @@ int eval_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, cons
         const int rows = (int)std::min(cap, n - r0);
         const int r = eval_forward(h, x, idx, ld, r0, rows, false, s);
         if (r) return r;
-        HeadArgs hd = head_args(h, {labels ? HEAD_EVAL : HEAD_LOGITS}, rows, false);
-        hd.f = selected(h, hd.f); hd.w = selected(h, hd.w); hd.b = selected(h, hd.b); hd.logits = selected(h, hd.logits);
-        hd.labels = labels ? labels + r0 : nullptr;
+        HeadArgs hd = eval_head(h, labels ? HEAD_EVAL : HEAD_LOGITS, labels ? labels + r0 : nullptr, nullptr, false, rows);
         hd.err_count = labels ? h->err_count : nullptr;
         PROF("head_kernel", launch_head(h->bf16, hd, s));
         if (logits_out)
@@ -920,12 +956,7 @@ int eval_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, cons
 // into dpre[4], the masked dX chain down to layer 1 and the linear layer-0 dX into dxfake
 int saliency_backward(mrgan_handle* h, int objective, const int32_t* targets, int32_t* classes_out, int rows, hipStream_t s) {
     static const int kinds[3] = {HEAD_SAL_LOGIT, HEAD_SAL_XENT, HEAD_SAL_MSE};
-    HeadArgs hd = head_args(h, {kinds[objective]}, rows, false);
-    hd.f = selected(h, hd.f); hd.w = selected(h, hd.w); hd.b = selected(h, hd.b); hd.logits = nullptr;
-    hd.labels = targets;
-    hd.classes_out = classes_out;
-    hd.dpre = selected(h, h->dpre[4]); hd.ldd = h->Fp;
-    PROF("head_kernel", launch_head(h->bf16, hd, s));
+    PROF("head_kernel", launch_head(h->bf16, eval_head(h, kinds[objective], targets, classes_out, true, rows), s));
     for (int l = 4; l >= 1; --l)
         CHK(dense_dx(h, h->d[l], KIND_EVAL, selected(h, h->dpre[l]), rows, 1, selected(h, h->dpre[l - 1]), ACT_RELU, h->d[l - 1].N, eval_mask(h, l - 1),
                      nullptr, NO_SUMS, s));
@@ -933,82 +964,35 @@ int saliency_backward(mrgan_handle* h, int objective, const int32_t* targets, in
                  NO_SUMS, s));
     return 0;
 }
-// Input-gradient saliency of n rows (mrgan_input_gradient): per chunk the evaluation forward WITH its relu masks, the per-row
-// saliency head into dpre[4], the masked dX chain down to layer 1, the linear layer-0 dX into dxfake and the finishing kernel
-// into the caller's rows.  Everything lives in segment 0 of the training activations (xin[l], mask[l], dpre[l], feat) as one
-// run of contiguous rows; dxfake holds S rows, which is what bounds the chunk.  No noise, no state slot, no column sums, no
-// weight gradients: cur, the counters and the cached graph are not touched.
-int saliency_rows(mrgan_handle* h, const mrgan_saliency_args* a, hipStream_t s) {
-    const long cap = h->S, n = a->n;
-    for (long r0 = 0; r0 < n; r0 += cap) {
-        const int rows = (int)std::min(cap, n - r0);
-        const int r = eval_forward(h, a->x_dev, a->idx_dev, a->ld_x, r0, rows, true, s);
-        if (r) return r;
-        CHK(saliency_backward(h, a->objective, a->targets_dev ? a->targets_dev + r0 : nullptr,
-                              a->classes_out_dev ? a->classes_out_dev + r0 : nullptr, rows, s));
-        SaliencyFinishArgs f;
-        memset(&f, 0, sizeof f);
-        f.g = selected(h, h->dxfake); f.ldg = h->Dp; f.rows = rows; f.cols = h->cfg.d_in;
-        f.out = a->out_dev + r0 * a->ld_out; f.ldo = a->ld_out; f.mode = a->post == MRGAN_SAL_HEATMAP ? SAL_HEATMAP : SAL_RAW;
-        PROFB("saliency_finish_kernel", launch_saliency_finish(h->bf16, f, s), (double)rows * h->cfg.d_in * (2.0 * h->es + 4.0));
-    }
-    return n > h->B ? rezero_padding(h, 1, 1, true, s) : 0;      // (no chunk reached the padding rows of segment 0 otherwise)
-}
-
-// Attribution over draws (mrgan_attribution).  Per chunk of at most S rows: the target classes (given, or one clean forward +
-// head when the draws themselves are not that forward), then per draw d the chunk of saliency_rows with a forward of its own
-// -- MRGAN_ATTR_NOISE: the stage and the epilogues of dense 1 .. 4 add the site's noise, keyed by slot d of draw_state (step
-// d), seed + selected model, segment id MRGAN_ATTR_NOISE_SEG and the chunk's first row; MRGAN_ATTR_PATH: the path stage at
-// alpha_d -- and the accumulate launch into the caller's rows.  Draws are the inner loop: a chunk's out rows stay in L2.
+// Saliency maps of n rows (mrgan_attribution; mrgan_input_gradient is its call of one noise-free draw).  Per chunk of at most
+// S rows: the target classes (given, or one clean forward + head when the draws themselves are not that forward), then per
+// draw d the evaluation forward WITH its relu masks -- at the rows themselves, or (Draw) with the noise keyed by slot d of
+// draw_state (step d), seed + selected model and the chunk's first row, or at the path point alpha_d -- the per-row saliency
+// head into dpre[4], the masked dX chain down to layer 1, the linear layer-0 dX into dxfake and the accumulate launch into the
+// caller's rows.  Everything lives in segment 0 of the training activations (xin[l], mask[l], dpre[l], feat) as one run of
+// contiguous rows; dxfake holds S rows, which is what bounds the chunk.  No column sums, no weight gradients: cur, the
+// counters and the cached graph are not touched.  Draws are the inner loop: a chunk's out rows stay in L2.
 int attribution_rows(mrgan_handle* h, const mrgan_attribution_args* a, hipStream_t s) {
     const long cap = h->S, n = a->n;
     const bool path = a->method == MRGAN_ATTR_PATH;
-    const float sig[2] = {path ? 0.f : a->sigma_input, path ? 0.f : a->sigma_hidden};
-    // NOISE with both sigmas 0: every draw is the clean forward at x, its head finds the predicted class itself
-    const bool clean_pass = !a->targets_dev && (path || sig[0] > 0.f || sig[1] > 0.f);
-    const uint64_t seed = h->cfg.seed + (uint64_t)h->sel;
+    const bool noise_free = !path && a->sigma_input == 0.f && a->sigma_hidden == 0.f;      // every draw is the clean forward at x
+    const bool clean_pass = !a->targets_dev && !noise_free;      // (noise-free: the draw's own head finds the predicted class)
     for (long r0 = 0; r0 < n; r0 += cap) {
         const int rows = (int)std::min(cap, n - r0);
-        const float* xsrc = a->idx_dev ? a->x_dev : a->x_dev + r0 * a->ld_x;
-        const int32_t* xidx = a->idx_dev ? a->idx_dev + r0 : nullptr;
         int32_t* classes = a->classes_out_dev ? a->classes_out_dev + r0 : nullptr;
         const int32_t* targets = a->targets_dev ? a->targets_dev + r0 : nullptr;
         if (clean_pass) {
             const int r = eval_forward(h, a->x_dev, a->idx_dev, a->ld_x, r0, rows, false, s);
             if (r) return r;
-            HeadArgs hd = head_args(h, {HEAD_SAL_LOGIT}, rows, false);      // (for its argmax: dpre[4] is rewritten by every draw)
-            hd.f = selected(h, hd.f); hd.w = selected(h, hd.w); hd.b = selected(h, hd.b); hd.logits = nullptr;
-            hd.labels = nullptr; hd.classes_out = classes;
-            hd.dpre = selected(h, h->dpre[4]); hd.ldd = h->Fp;
-            PROF("head_kernel", launch_head(h->bf16, hd, s));
+            // (for its argmax: dpre[4] is rewritten by every draw)
+            PROF("head_kernel", launch_head(h->bf16, eval_head(h, HEAD_SAL_LOGIT, nullptr, classes, true, rows), s));
             targets = classes;
         }
         for (int d = 0; d < a->draws; ++d) {
-            const DrawKey dk = {h->draw_state + d, seed, (uint32_t)r0};
-            if (path) {
-                PathStageArgs ps;
-                memset(&ps, 0, sizeof ps);
-                ps.src = xsrc; ps.idx = xidx; ps.ld = a->ld_x; ps.baseline = a->baseline_dev;
-                ps.alpha = ((float)d + 0.5f) / (float)a->draws;
-                ps.rows = rows; ps.cols = h->cfg.d_in; ps.cols_pad = h->Dp; ps.out = selected(h, h->xin[0]); ps.ldo = h->Dp;
-                PROFB("path_stage_kernel", launch_path_stage(h->bf16, ps, s), (double)rows * h->cfg.d_in * (4.0 + h->es));
-            } else {
-                StageArgs st;
-                memset(&st, 0, sizeof st);
-                StageSeg& sg = st.s[0];
-                sg.src = xsrc; sg.idx = xidx; sg.ld = a->ld_x; sg.rows = rows;
-                sg.cols = h->cfg.d_in; sg.cols_pad = h->Dp; sg.out = selected(h, h->xin[0]); sg.ldo = h->Dp;
-                sg.sigma = sig[0]; sg.site = 0; sg.seg = MRGAN_ATTR_NOISE_SEG;
-                st.nseg = 1; st.seed = seed; st.row0 = (uint32_t)r0; st.cur = h->draw_state + d;
-                st.gauss = sig[0] > 0.f ? h->gauss : 0;      // (sigma 0: the instantiation eval_forward launches)
-                PROF("stage_kernel", launch_stage(h->bf16, st, s));
-            }
-            for (int l = 0; l < 5; ++l) {
-                const bool noisy = l < 4 && sig[1] > 0.f;
-                const NoiseSite nz = {sig[1], (uint32_t)(l + 1), (uint32_t)MRGAN_ATTR_NOISE_SEG, 1, 0};
-                CHK(dense_fwd(h, h->d[l], KIND_EVAL, selected(h, h->xin[l]), rows, 1, selected(h, l < 4 ? h->xin[l + 1] : h->feat), ACT_RELU,
-                              noisy ? nz : NO_NOISE, eval_mask(h, l), NO_SUMS, s, NO_FP8, noisy ? &dk : nullptr));
-            }
+            const Draw draw = {{h->draw_state + d, h->cfg.seed + (uint64_t)h->sel, (uint32_t)r0}, a->sigma_input, a->sigma_hidden, path,
+                               ((float)d + 0.5f) / (float)a->draws, a->baseline_dev};
+            const int r = eval_forward(h, a->x_dev, a->idx_dev, a->ld_x, r0, rows, true, s, noise_free ? nullptr : &draw);
+            if (r) return r;
             // draw 0 reports the classes unless the clean pass has; without targets (the noise-free call) its head finds them, and
             // the later draws read them back
             CHK(saliency_backward(h, a->objective, targets, (d == 0 && targets != classes) ? classes : nullptr, rows, s));
@@ -1018,12 +1002,36 @@ int attribution_rows(mrgan_handle* h, const mrgan_attribution_args* a, hipStream
             f.g = selected(h, h->dxfake); f.ldg = h->Dp; f.rows = rows; f.cols = h->cfg.d_in;
             f.out = a->out_dev + r0 * a->ld_out; f.ldo = a->ld_out; f.mode = a->post == MRGAN_SAL_HEATMAP ? SAL_HEATMAP : SAL_RAW;
             f.draw = d; f.draws = a->draws; f.multiply = a->multiply;
-            f.x = xsrc; f.idx = xidx; f.ld_x = a->ld_x; f.baseline = a->baseline_dev;
+            f.x = a->idx_dev ? a->x_dev : a->x_dev + r0 * a->ld_x; f.idx = a->idx_dev ? a->idx_dev + r0 : nullptr; f.ld_x = a->ld_x;
+            f.baseline = a->baseline_dev;
             PROFB("attribution_accum_kernel", launch_attr_accum(h->bf16, f, s),
                   (double)rows * h->cfg.d_in * (h->es + (d > 0 ? 8.0 : 4.0) + (a->multiply && d == a->draws - 1 ? 4.0 : 0.0)));
         }
     }
-    return n > h->B ? rezero_padding(h, 1, 1, true, s) : 0;      // (as saliency_rows)
+    return n > h->B ? rezero_padding(h, 1, 1, true, s) : 0;      // (no chunk reached the padding rows of segment 0 otherwise)
+}
+
+// what mrgan_input_gradient and mrgan_attribution refuse alike, under the entry's name (a: null, or the call as an attribution)
+int check_attribution(const mrgan_handle* h, const char* entry, const mrgan_attribution_args* a) {
+    if (!h) return fail(-1, "null handle");
+    if (h->fp8) return fail(-3, "%s: not on an fp8 handle (its dX products read fp8-scaled images and would disturb the calibration); use an fp32 or a bf16 engine", entry);
+    if (!a || !a->x_dev || !a->out_dev) return fail(-2, "%s: x and out are required", entry);
+    if (a->n < 0) return fail(-2, "%s: negative row count n", entry);
+    if (a->ld_x < h->cfg.d_in) return fail(-2, "%s: row pitch ld_x smaller than d_in", entry);
+    if (a->ld_out < h->cfg.d_in) return fail(-2, "%s: row pitch ld_out smaller than d_in", entry);
+    if (a->objective != MRGAN_SAL_LOGIT && a->objective != MRGAN_SAL_XENT && a->objective != MRGAN_SAL_MSE)
+        return fail(-2, "%s: unknown objective %d", entry, (int)a->objective);
+    if (a->post != MRGAN_SAL_RAW && a->post != MRGAN_SAL_HEATMAP) return fail(-2, "%s: unknown post mode %d", entry, (int)a->post);
+    if (a->method != MRGAN_ATTR_NOISE && a->method != MRGAN_ATTR_PATH) return fail(-2, "%s: unknown method %d", entry, (int)a->method);
+    if (a->draws < 1 || a->draws > MRGAN_ATTR_MAX_DRAWS)
+        return fail(-2, "%s: draws = %d outside [1, %d]", entry, (int)a->draws, (int)MRGAN_ATTR_MAX_DRAWS);
+    if (a->multiply != 0 && a->multiply != 1) return fail(-2, "%s: multiply must be 0 or 1, got %d", entry, (int)a->multiply);
+    if (!(a->sigma_input >= 0.f) || !std::isfinite(a->sigma_input)) return fail(-2, "%s: sigma_input must be finite and >= 0", entry);
+    if (!(a->sigma_hidden >= 0.f) || !std::isfinite(a->sigma_hidden)) return fail(-2, "%s: sigma_hidden must be finite and >= 0", entry);
+    if (a->method == MRGAN_ATTR_PATH && (a->sigma_input != 0.f || a->sigma_hidden != 0.f))
+        return fail(-2, "%s: sigma_input / sigma_hidden belong to MRGAN_ATTR_NOISE; MRGAN_ATTR_PATH is noise-free", entry);
+    if (a->method == MRGAN_ATTR_NOISE && a->baseline_dev) return fail(-2, "%s: baseline_dev belongs to MRGAN_ATTR_PATH", entry);
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1245,37 +1253,23 @@ int mrgan_predict_logits(mrgan_handle* h, const float* x, const int32_t* idx, in
     return eval_rows(h, x, idx, ld, nullptr, n, logits, (hipStream_t)stream);
 }
 
+// the attribution of one noise-free draw: nothing reads the classes back, so classes_out_dev may be null, and no draw slot is read
 int mrgan_input_gradient(mrgan_handle* h, const mrgan_saliency_args* a, mrgan_stream stream) {
-    if (!h) return fail(-1, "null handle");
-    if (h->fp8) return fail(-3, "input_gradient: not on an fp8 handle (its dX products read fp8-scaled images and would disturb the calibration); use an fp32 or a bf16 engine");
-    if (!a || !a->x_dev || !a->out_dev) return fail(-2, "input_gradient: x and out are required");
-    if (a->n < 0) return fail(-2, "input_gradient: negative row count");
-    if (a->ld_x < h->cfg.d_in || a->ld_out < h->cfg.d_in) return fail(-2, "input_gradient: row pitch smaller than d_in");
-    if (a->objective != MRGAN_SAL_LOGIT && a->objective != MRGAN_SAL_XENT && a->objective != MRGAN_SAL_MSE)
-        return fail(-2, "input_gradient: unknown objective %d", (int)a->objective);
-    if (a->post != MRGAN_SAL_RAW && a->post != MRGAN_SAL_HEATMAP) return fail(-2, "input_gradient: unknown post mode %d", (int)a->post);
-    return saliency_rows(h, a, (hipStream_t)stream);
+    mrgan_attribution_args f;
+    memset(&f, 0, sizeof f);
+    if (a) {
+        f.x_dev = a->x_dev; f.idx_dev = a->idx_dev; f.ld_x = a->ld_x; f.n = a->n;
+        f.targets_dev = a->targets_dev; f.objective = a->objective; f.post = a->post;
+        f.out_dev = a->out_dev; f.ld_out = a->ld_out; f.classes_out_dev = a->classes_out_dev;
+        f.method = MRGAN_ATTR_NOISE; f.draws = 1;
+    }
+    const int r = check_attribution(h, "input_gradient", a ? &f : nullptr);
+    return r ? r : attribution_rows(h, &f, (hipStream_t)stream);
 }
 
 int mrgan_attribution(mrgan_handle* h, const mrgan_attribution_args* a, mrgan_stream stream) {
-    if (!h) return fail(-1, "null handle");
-    if (h->fp8) return fail(-3, "attribution: not on an fp8 handle (its dX products read fp8-scaled images and would disturb the calibration); use an fp32 or a bf16 engine");
-    if (!a || !a->x_dev || !a->out_dev) return fail(-2, "attribution: x and out are required");
-    if (a->n < 0) return fail(-2, "attribution: negative row count n");
-    if (a->ld_x < h->cfg.d_in) return fail(-2, "attribution: row pitch ld_x smaller than d_in");
-    if (a->ld_out < h->cfg.d_in) return fail(-2, "attribution: row pitch ld_out smaller than d_in");
-    if (a->objective != MRGAN_SAL_LOGIT && a->objective != MRGAN_SAL_XENT && a->objective != MRGAN_SAL_MSE)
-        return fail(-2, "attribution: unknown objective %d", (int)a->objective);
-    if (a->post != MRGAN_SAL_RAW && a->post != MRGAN_SAL_HEATMAP) return fail(-2, "attribution: unknown post mode %d", (int)a->post);
-    if (a->method != MRGAN_ATTR_NOISE && a->method != MRGAN_ATTR_PATH) return fail(-2, "attribution: unknown method %d", (int)a->method);
-    if (a->draws < 1 || a->draws > MRGAN_ATTR_MAX_DRAWS)
-        return fail(-2, "attribution: draws = %d outside [1, %d]", (int)a->draws, (int)MRGAN_ATTR_MAX_DRAWS);
-    if (a->multiply != 0 && a->multiply != 1) return fail(-2, "attribution: multiply must be 0 or 1, got %d", (int)a->multiply);
-    if (!(a->sigma_input >= 0.f) || !std::isfinite(a->sigma_input)) return fail(-2, "attribution: sigma_input must be finite and >= 0");
-    if (!(a->sigma_hidden >= 0.f) || !std::isfinite(a->sigma_hidden)) return fail(-2, "attribution: sigma_hidden must be finite and >= 0");
-    if (a->method == MRGAN_ATTR_PATH && (a->sigma_input != 0.f || a->sigma_hidden != 0.f))
-        return fail(-2, "attribution: sigma_input / sigma_hidden belong to MRGAN_ATTR_NOISE; MRGAN_ATTR_PATH is noise-free");
-    if (a->method == MRGAN_ATTR_NOISE && a->baseline_dev) return fail(-2, "attribution: baseline_dev belongs to MRGAN_ATTR_PATH");
+    const int r = check_attribution(h, "attribution", a);
+    if (r) return r;
     if (!a->targets_dev && !a->classes_out_dev)
         return fail(-2, "attribution: classes_out_dev is required when targets_dev is null (the predicted classes are kept there between draws)");
     if (!h->draw_state) return fail(-1, "attribution: the handle has no draw slots");

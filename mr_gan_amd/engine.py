@@ -139,9 +139,8 @@ class AttributionArgs(C.Structure):
 
 
 def attribution_plan(method, draws=None, sigma=None, baseline=None, times_input=False, d_in=None, own_sigmas=(0.3, 0.5)):
-    """The keywords of MRGAN.saliency -> None for the plain gradient call (mrgan_input_gradient), else the dict of
-    Engine.attribution's keywords (method, draws, sigma_input, sigma_hidden, baseline, multiply).  Everything is checked here,
-    before any device call:
+    """The keywords of MRGAN.saliency -> the dict of Engine.attribution's keywords (method, draws, sigma_input, sigma_hidden,
+    baseline, multiply).  Everything is checked here, before any device call:
       'gradient'    one gradient of the noise-free forward; draws, sigma and baseline do not apply; times_input: x input
       'smoothgrad'  the mean over draws (default 16) forwards with GaussianNoise: sigma None = the network's own sigmas
                     (own_sigmas: input, hidden), a float = input-only noise, (input, hidden) = both; times_input: x input
@@ -153,9 +152,7 @@ def attribution_plan(method, draws=None, sigma=None, baseline=None, times_input=
         for name, v in (('draws', draws), ('sigma', sigma), ('baseline', baseline)):
             if v is not None:
                 raise ValueError("%s does not apply to method 'gradient' (use 'smoothgrad' or 'integrated')" % name)
-        if not times_input:
-            return None
-        return dict(method=ATTR_NOISE, draws=1, sigma_input=0.0, sigma_hidden=0.0, baseline=None, multiply=1)
+        return dict(method=ATTR_NOISE, draws=1, sigma_input=0.0, sigma_hidden=0.0, baseline=None, multiply=1 if times_input else 0)
     if draws is None:
         draws = 16
     if isinstance(draws, bool) or not isinstance(draws, (int, np.integer)) or not 1 <= int(draws) <= ATTR_MAX_DRAWS:
@@ -515,42 +512,40 @@ class Engine(object):
                                              _stream()))
         return out
 
-    def input_gradient(self, x, targets=None, objective=SAL_XENT, post=SAL_RAW, idx=None, out=None, classes_out=None):
-        """mrgan_input_gradient -> (maps fp32 [n, >= d_in], classes int32 [n]): per row the gradient of `objective` (SAL_*) at
-        its target class -- targets[i], or the predicted class -- with respect to the input row, raw or as the reference's
-        heat-map (post = SAL_HEATMAP).  out / classes_out: buffers to write into (out may have a row pitch above d_in; its
-        further columns are left alone)."""
+    def _map_args(self, a, x, targets, objective, post, idx, out, classes_out):
+        """the fields mrgan_saliency_args and mrgan_attribution_args share, the buffers allocated where not given -> (out, classes_out)"""
         n = x.shape[0] if idx is None else idx.numel()
         if out is None:
             out = torch.empty((n, self.cfg.d_in), dtype=torch.float32, device=self.device)
         if classes_out is None:
             classes_out = torch.empty((n,), dtype=torch.int32, device=self.device)
-        a = SaliencyArgs()
         a.x, a.idx, a.ld_x, a.n = _ptr(x), _ptr(idx), x.stride(0), n
         a.targets, a.objective, a.post = _ptr(targets), int(objective), int(post)
         a.out, a.ld_out, a.classes_out = _ptr(out), out.stride(0), _ptr(classes_out)
-        _check(self.lib.mrgan_input_gradient(self.handle, C.byref(a), _stream()))
         return out, classes_out
+
+    def input_gradient(self, x, targets=None, objective=SAL_XENT, post=SAL_RAW, idx=None, out=None, classes_out=None):
+        """mrgan_input_gradient -> (maps fp32 [n, >= d_in], classes int32 [n]): per row the gradient of `objective` (SAL_*) at
+        its target class -- targets[i], or the predicted class -- with respect to the input row, raw or as the reference's
+        heat-map (post = SAL_HEATMAP).  out / classes_out: buffers to write into (out may have a row pitch above d_in; its
+        further columns are left alone)."""
+        a = SaliencyArgs()
+        res = self._map_args(a, x, targets, objective, post, idx, out, classes_out)
+        _check(self.lib.mrgan_input_gradient(self.handle, C.byref(a), _stream()))
+        return res
 
     def attribution(self, x, targets=None, objective=SAL_XENT, post=SAL_RAW, idx=None, out=None, classes_out=None,
                     method=ATTR_NOISE, draws=1, sigma_input=0.0, sigma_hidden=0.0, baseline=None, multiply=0):
         """mrgan_attribution -> (maps fp32 [n, >= d_in], classes int32 [n]): input_gradient averaged over `draws` forwards on
         the device -- ATTR_NOISE: with GaussianNoise of sigma_input at the input and sigma_hidden behind dense 1 .. 4
         (SmoothGrad); ATTR_PATH: at the midpoints of `draws` pieces of the path from baseline (device fp32 [d_in], or None:
-        zeros) to the row -- times (x - baseline) when multiply is 1."""
-        n = x.shape[0] if idx is None else idx.numel()
-        if out is None:
-            out = torch.empty((n, self.cfg.d_in), dtype=torch.float32, device=self.device)
-        if classes_out is None:
-            classes_out = torch.empty((n,), dtype=torch.int32, device=self.device)
+        zeros) to the row -- times (x - baseline) when multiply is 1.  The defaults are input_gradient itself."""
         a = AttributionArgs()
-        a.x, a.idx, a.ld_x, a.n = _ptr(x), _ptr(idx), x.stride(0), n
-        a.targets, a.objective, a.post = _ptr(targets), int(objective), int(post)
-        a.out, a.ld_out, a.classes_out = _ptr(out), out.stride(0), _ptr(classes_out)
+        res = self._map_args(a, x, targets, objective, post, idx, out, classes_out)
         a.method, a.draws, a.sigma_input, a.sigma_hidden = int(method), int(draws), float(sigma_input), float(sigma_hidden)
         a.baseline, a.multiply = _ptr(baseline), int(multiply)
         _check(self.lib.mrgan_attribution(self.handle, C.byref(a), _stream()))
-        return out, classes_out
+        return res
 
     def read_metrics(self, reset=True):
         out = (C.c_float * 8)()

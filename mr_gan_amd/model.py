@@ -152,12 +152,9 @@ class MRGAN(object):
         post = E.SAL_HEATMAP if heatmap else E.SAL_RAW
         with self._on_stream():
             x, t = self._dev(X), None if y is None else self._dev(y, torch.int32)
-            if plan is None:
-                maps, cls = self.engine.input_gradient(x, t, code, post)
-            else:
-                if plan['baseline'] is not None:
-                    plan['baseline'] = self._dev(plan['baseline'])
-                maps, cls = self.engine.attribution(x, t, code, post, **plan)
+            if plan['baseline'] is not None:
+                plan['baseline'] = self._dev(plan['baseline'])
+            maps, cls = self.engine.attribution(x, t, code, post, **plan)
             return maps.cpu().numpy(), cls.cpu().numpy()
 
     def evaluate(self, X, y):

@@ -10,12 +10,12 @@ import numpy as np
 
 from oracle import mrgan_oracle as O
 from tests import saliency_ref as R
-from tests.helpers import SEED, Case
+from tests.helpers import SEED
 
 NOISE_SEG = 255                       # MRGAN_ATTR_NOISE_SEG
-DECIDED = 1e-5                        # a row is decided when every fp64 pre-activation of every draw is at least this far from zero
-B, N, DRAWS = 50, 130, 3              # S = 128: two chunks of 128 + 2 rows
-WIDE_HEAD = (256, 256, 256, 256, 512)
+DECIDED = R.DECIDED                   # a row is decided when every fp64 pre-activation of every draw is at least this far from zero
+B, N, DRAWS = R.B, 130, 3             # S = 128: two chunks of 128 + 2 rows
+WIDE_HEAD = R.WIDE_HEAD
 SHAPES = [(6, 72, None), (10, 400, None), (6, 96, WIDE_HEAD)]                      # (K, D, d_hidden) of the fp32 tests
 BF16_SHAPES = [(6, 400, None), (10, 96, None), (6, 96, WIDE_HEAD)]                 # those of the bf16 saliency tests
 OWN = (0.3, 0.5)                      # mrgan_config.sigma: input, hidden
@@ -69,12 +69,8 @@ def attribution(d, x32, targets, objective, method, draws, sigmas=(0.0, 0.0), ba
 
 
 # ---- the shared problems of the CPU and GPU tests (never modified) ---------------------------------------------------
-@functools.lru_cache(maxsize=None)
 def problem(K, D, d_hidden=None, n=N):
-    kw = dict(d_hidden=d_hidden) if d_hidden else {}
-    case = Case(K=K, D=D, B=B, steps=1, **kw)
-    x32 = np.random.default_rng(3).standard_normal((n, D)).astype(np.float32)
-    return case, x32
+    return R.problem(K, D, d_hidden, n)
 
 
 def random_baseline(D):

@@ -95,7 +95,7 @@ def test_at_most_a_quarter_of_the_rows_of_a_gpu_case_is_undecided(K, D, dh):
 def test_saliency_keywords_are_validated_without_a_device():
     from mr_gan_amd import engine as E
     plan = E.attribution_plan
-    assert plan('gradient') is None
+    assert plan('gradient') == dict(method=E.ATTR_NOISE, draws=1, sigma_input=0.0, sigma_hidden=0.0, baseline=None, multiply=0)
     assert plan('gradient', times_input=True) == dict(method=E.ATTR_NOISE, draws=1, sigma_input=0.0, sigma_hidden=0.0, baseline=None,
                                                       multiply=1)
     p = plan('smoothgrad')

@@ -8,26 +8,18 @@ import pytest
 import torch
 
 from mr_gan_amd import engine as E
-from oracle import mrgan_oracle as O
 from tests import attribution_ref as A
 from tests import parity as P
+from tests import saliency_gpu as G
 from tests import saliency_ref as R
-from tests.helpers import SEED, Case, cosine, frob_rel_err, rel_err
+from tests.helpers import Case, cosine, frob_rel_err, rel_err
 
 pytestmark = pytest.mark.gpu
 
 B, N, DRAWS = A.B, A.N, A.DRAWS
-FP32_TOL = 2e-4                       # the saliency tests' bound; a mean over draws cannot exceed the worst draw's error
-SENT = -768.0
+FP32_TOL, SENT = G.FP32_TOL, G.SENT   # the saliency tests' bound; a mean over draws cannot exceed the worst draw's error
 METHOD = {'noise': E.ATTR_NOISE, 'path': E.ATTR_PATH}
-
-
-def _engine(case, D, dtype, **kw):
-    if case.d_hidden != tuple(O.D_HIDDEN):
-        kw['d_hidden'] = case.d_hidden
-    eng = P.engine(D, B, dtype, num_classes=case.K, **kw)
-    P.load(eng, case)
-    return eng
+_engine, _bits = G.engine, G.bits
 
 
 def _mode_kw(mode, D):
@@ -42,10 +34,6 @@ def _attr(eng, x, targets=None, objective='xent', post=E.SAL_RAW, draws=DRAWS, *
     return out.cpu().numpy(), cls.cpu().numpy()
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 # ---- 1. the degenerate call ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", [E.F32, E.BF16])
 @pytest.mark.parametrize("post", [E.SAL_RAW, E.SAL_HEATMAP])
@@ -55,13 +43,10 @@ def test_one_noise_free_draw_gives_the_bits_of_input_gradient(dtype, post):
     eng = _engine(case, D, dtype)
     rng = np.random.default_rng(11)
     idx = P.to_dev(np.concatenate([rng.permutation(N), rng.integers(0, N, 23)]).astype(np.int32), torch.int32)
-    wide = torch.full((N, D + 9), float("nan"), device=P.DEV)
-    wide[:, :D] = P.to_dev(x32)
-    n = idx.numel()
+    wide = G.wide_rows(x32)
     outs = []
     for call in (eng.input_gradient, eng.attribution):
-        out = torch.full((n, D + 5), SENT, device=P.DEV)
-        cls = torch.full((n,), -1, dtype=torch.int32, device=P.DEV)
+        out, cls = G.sentinel_buffers(idx.numel(), D)
         call(wide, None, E.SAL_XENT, post, idx=idx, out=out, classes_out=cls)      # (attribution's defaults: NOISE, 1 draw, sigmas 0)
         outs.append((out.cpu().numpy(), cls.cpu().numpy()))
     eng.close()
@@ -184,14 +169,8 @@ def test_heatmap_is_the_reference_map_of_the_raw_result(dtype, mode):
 
 @pytest.mark.parametrize("dtype", [E.F32, E.BF16])
 def test_heatmap_of_an_all_dead_row_is_zero(dtype):
-    K, D, dh = A.SHAPES[0]
-    case, x32 = A.problem(K, D, dh)
-    eng = P.engine(D, B, dtype, num_classes=K)
-    d = [p.astype(np.float32) for p in case.d0]
-    d[1] = -np.abs(d[1]) - 0.5                          # first-layer biases negative: a zero row has every unit of layer 1 dead
-    eng.set_weights(E.NET_D, d)
-    x = x32[:5].copy()
-    x[2] = 0.0
+    K, D, _ = A.SHAPES[0]
+    eng, x = G.dead_row_engine(dtype, K, D, N)
     # hidden noise only (the input stays zero) and the path from zero (every point of it is zero)
     for kw in (dict(method=E.ATTR_NOISE, sigma_hidden=0.5), dict(method=E.ATTR_PATH, multiply=1)):
         raw, _ = _attr(eng, x, **kw)
@@ -241,36 +220,10 @@ def _one_draw(case, D, dtype, xd, kw):
 
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
 def test_group_handle_serves_the_selected_model(dtype):
-    from mr_gan_amd import MRGAN, MRGANGroup
-    D, seed = 40, 123
-    X = np.random.default_rng(3).standard_normal((N, D)).astype(np.float32)
-    grp = MRGANGroup(D, 3, batch_size=B, dtype=dtype, seed=seed)
-    got = [grp.saliency(m, X, method='smoothgrad', draws=DRAWS, heatmap=False) for m in (2, 0, 1)]
-    grp.engine.close()
-    for (maps, cls), m in zip(got, (2, 0, 1)):
-        one = MRGAN(D, batch_size=B, dtype=dtype, seed=seed + m)
-        want, wcls = one.saliency(X, method='smoothgrad', draws=DRAWS, heatmap=False)
-        one.engine.close()
-        assert maps.shape == (N, D) and maps.dtype == np.float32
-        assert np.array_equal(_bits(maps), _bits(want)) and np.array_equal(cls, wcls)
-    assert not np.array_equal(got[0][0], got[1][0])
+    G.group_handle_serves_the_selected_model(dtype, N, method='smoothgrad', draws=DRAWS, heatmap=False)
 
 
 # ---- 8. training is undisturbed ------------------------------------------------------------------------------------
-def _state(eng):
-    out = []
-    for net in (E.NET_G, E.NET_D):
-        out += eng.get_weights(net) + eng.get_slot(net, 0) + eng.get_slot(net, 1)
-    return out, eng.get_iterations(), eng.read_metrics(reset=False)
-
-
-def _assert_same_state(a, b):
-    for x, y in zip(a[0], b[0]):
-        assert np.array_equal(x.view(np.uint32), y.view(np.uint32))
-    assert a[1] == b[1]
-    assert np.array_equal(np.asarray(a[2], np.float32).view(np.uint32), np.asarray(b[2], np.float32).view(np.uint32))
-
-
 def _disturb(eng, big, t):
     """one NOISE call and one PATH call of 199 large rows: two chunks, every padding row of segment 0"""
     out, _ = eng.attribution(big, None, E.SAL_XENT, E.SAL_HEATMAP if t == 1 else E.SAL_RAW, method=E.ATTR_NOISE, draws=2,
@@ -281,64 +234,16 @@ def _disturb(eng, big, t):
 
 
 def test_training_is_undisturbed_by_attribution_calls():
-    D = 400
-    case = Case(D=D, B=B, steps=3, device_z=True)
-    big = P.to_dev(1e3 * np.random.default_rng(9).standard_normal((3 * 64 + 7, D)).astype(np.float32))
-    states = []
-    for disturb in (False, True):
-        eng = P.engine(D, B, E.BF16)
-        P.load(eng, case)
-        for t in range(case.steps):
-            if disturb:
-                _disturb(eng, big, t)
-            eng.disc_step(P.disc_args(case, t, True))
-            eng.gen_step(P.gen_args(case, t, True))
-        states.append(_state(eng))
-        eng.close()
-    assert states[0][1] == 2 * case.steps
-    _assert_same_state(*states)
+    G.training_is_undisturbed_by(_disturb)
 
 
 def test_graph_replay_is_undisturbed_by_attribution_calls():
-    from mr_gan_amd import MRGAN
-    D, n = 400, 4 * B
-    case = Case(D=D, B=B, steps=1, device_z=True)
-    rs = np.random.RandomState(3)
-    X, xl = rs.randn(n, D).astype(np.float32), rs.randn(2 * B, D).astype(np.float32)
-    yl = rs.randint(0, 6, size=2 * B).astype(np.int32)
-    big = 1e3 * rs.randn(3 * 64 + 7, D).astype(np.float32)
-    states = []
-    for disturb in (False, True):
-        m = MRGAN(D, batch_size=B, dtype='bfloat16', seed=77, use_graph=True, init_weights=False)
-        P.load(m.engine, case)
-        with m._on_stream():
-            xu, xlab, bigd = m._dev(X), m._dev(xl), m._dev(big)
-            idx_lab = m._dev(np.arange(n, dtype=np.int32) % (2 * B), torch.int32)
-            labs = m._dev(yl[np.arange(n) % (2 * B)], torch.int32)
-            idx_u1 = m._dev(np.arange(n, dtype=np.int32)[::-1].copy(), torch.int32)
-            idx_u2 = m._dev(np.roll(np.arange(n, dtype=np.int32), 7), torch.int32)
-            dargs = E.Engine.disc_args(xlab, labs, xu, None, idx_lab, idx_u1, stream_mode=1)
-            gargs = E.Engine.gen_args(xu, None, idx_u2, stream_mode=1)
-            m.engine.set_iterations(0, 0)
-            for t in range(n // B):
-                if disturb:
-                    _disturb(m.engine, bigd, t)
-                m.engine.train_pair(dargs, gargs)
-            torch.cuda.synchronize()
-            states.append(_state(m.engine))
-        m.engine.close()
-    assert states[0][1] == 2 * (n // B)
-    _assert_same_state(*states)
+    G.graph_replay_is_undisturbed_by(_disturb)
 
 
 # ---- 9. refusals ---------------------------------------------------------------------------------------------------
 def test_fp8_handle_is_refused():
-    eng = P.engine(64, 128, E.FP8)
-    with pytest.raises(E.MrganError) as ei:
-        eng.attribution(torch.zeros((4, 64), device=P.DEV), draws=2, sigma_input=0.3)
-    eng.close()
-    msg = str(ei.value)
-    assert "error -3" in msg and "fp32" in msg and "bf16" in msg
+    G.fp8_handle_is_refused(lambda eng, x: eng.attribution(x, draws=2, sigma_input=0.3))
 
 
 def test_bad_arguments_are_refused():
@@ -380,12 +285,8 @@ def test_bad_arguments_are_refused():
 @pytest.mark.parametrize("dtype,dh", [(E.F32, None), (E.BF16, None), (E.BF16, A.WIDE_HEAD)])
 def test_kernels_of_one_call(dtype, dh):
     """a 3-draw call of one chunk: per draw one stage, five forward and five dX products, the scalar head and the accumulate
-    launch, plus one clean forward and head when the targets are not given; no finishing kernel, nothing of a training step"""
-    D = 96
-    kw = dict(d_hidden=dh) if dh else {}
-    eng = P.engine(D, B, dtype, **kw)
-    P.load(eng, Case(D=D, B=B, steps=1, **kw))
-    x = P.to_dev(np.random.default_rng(3).standard_normal((100, D)).astype(np.float32))
+    launch, plus one clean forward and head when the targets are not given; nothing of a training step"""
+    eng, x = G.profiled_engine(dtype, dh, 100)
     profs = []
     for call in (dict(method=E.ATTR_NOISE, sigma_input=0.3, sigma_hidden=0.5), dict(method=E.ATTR_PATH, multiply=1),
                  dict(method=E.ATTR_NOISE, targets=torch.zeros(100, dtype=torch.int32, device=P.DEV))):
@@ -399,11 +300,8 @@ def test_kernels_of_one_call(dtype, dh):
     for prof, (stage, pstage, head, gemms) in zip(profs, ((4, 0, 4, 35), (1, 3, 4, 35), (3, 0, 3, 30))):
         print(sorted((k, v[1]) for k, v in prof.items()))
         assert count(prof, "stage_kernel") == stage and count(prof, "path_stage_kernel") == pstage and count(prof, "head_kernel") == head
-        assert count(prof, "attribution_accum_kernel") == 3 and "saliency_finish_kernel" not in prof
-        for name in prof:
-            assert not any(s in name for s in ("head_wide", "chain_kernel", "adam", "_ks_", "w6_split", "reduce_partials", "fm_kernel")), name
-            assert not name.startswith(("gemm_f32_kernel<2", "gemm_bf16_kc_kernel<2")), name
-        assert sum(v[1] for k, v in prof.items() if k.startswith("gemm")) == gemms
+        assert count(prof, "attribution_accum_kernel") == 3
+        G.assert_no_training_kernels(prof, gemms)
 
 
 # ---- 11. the front ends --------------------------------------------------------------------------------------------

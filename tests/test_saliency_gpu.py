@@ -2,54 +2,21 @@
 arithmetic of tests/saliency_ref.py (fp64 for the fp32 engine, the bf16 mirror for the bf16 engine), and what the call must
 leave alone."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 import torch
 
 from mr_gan_amd import engine as E
-from oracle import mrgan_oracle as O
 from tests import parity as P
+from tests import saliency_gpu as G
 from tests import saliency_ref as R
 from tests.helpers import Case, cosine, frob_rel_err, rel_err
 
 pytestmark = pytest.mark.gpu
 
-B = 50                                # local batch of every handle here: S = 128, so padding rows exist and 200 rows are two chunks
-WIDE_HEAD = (256, 256, 256, 256, 512)  # a feature layer of two HEAD_CHUNKs
-DECIDED = 1e-5                        # a row is decided when every fp64 pre-activation is at least this far from zero
-FP32_TOL = 2e-4                       # parity.fp32_gradients_match_oracle's bound on gradients behind the same dX chain
-
-
-@functools.lru_cache(maxsize=None)
-def _problem(K, D, n, d_hidden=None):
-    """(case, rows as the engine gets them, the same rows in fp64, decided rows); shared, never modified"""
-    kw = dict(d_hidden=d_hidden) if d_hidden else {}
-    case = Case(K=K, D=D, B=B, steps=1, **kw)
-    x32 = np.random.default_rng(3).standard_normal((n, D)).astype(np.float32)
-    x = x32.astype(np.float64)
-    decided = np.all([np.abs(p).min(axis=1) >= DECIDED for p in R.preactivations(case.d0, x)], axis=0)
-    return case, x32, x, decided
-
-
-@functools.lru_cache(maxsize=None)
-def _reference(K, D, n, objective, planted, quantize=None, d_hidden=None):
-    """fp64 (or mirror) gradient at the fp64 argmax, or at planted targets (argmax + 1); shared, never modified"""
-    case, _, x, _ = _problem(K, D, n, d_hidden)
-    t = R.input_gradient(case.d0, x, None, objective)[2]
-    if planted:
-        t = ((t + 1) % K).astype(np.int32)
-    g, _, t, _ = R.input_gradient(case.d0, x, t, objective, quantize=quantize)
-    return g, t
-
-
-def _engine(case, D, dtype, **kw):
-    if case.d_hidden != tuple(O.D_HIDDEN):
-        kw['d_hidden'] = case.d_hidden
-    eng = P.engine(D, B, dtype, num_classes=case.K, **kw)
-    P.load(eng, case)
-    return eng
+B, WIDE_HEAD, FP32_TOL = G.B, G.WIDE_HEAD, G.FP32_TOL      # B = 50: S = 128, so 200 rows are two chunks
+_problem, _reference, _engine = R.decided_problem, R.reference, G.engine
 
 
 def _grad(eng, x, targets=None, objective='xent', post=E.SAL_RAW, **kw):
@@ -106,16 +73,12 @@ def test_gather_and_pitches_reproduce_the_plain_call(dtype):
     rng = np.random.default_rng(11)
     idx = np.concatenate([rng.permutation(n), rng.integers(0, n, 37)]).astype(np.int32)      # permuted, then repeated
     plain, cls = _grad(eng, x32[idx])
-    wide = torch.full((n, D + 9), float("nan"), device=P.DEV)
-    wide[:, :D] = P.to_dev(x32)
-    SENT = -768.0
-    out = torch.full((len(idx), D + 5), SENT, device=P.DEV)
-    cls_out = torch.full((len(idx),), -1, dtype=torch.int32, device=P.DEV)
-    eng.input_gradient(wide, None, E.SAL_XENT, E.SAL_RAW, idx=P.to_dev(idx, torch.int32), out=out, classes_out=cls_out)
+    out, cls_out = G.sentinel_buffers(len(idx), D)
+    eng.input_gradient(G.wide_rows(x32), None, E.SAL_XENT, E.SAL_RAW, idx=P.to_dev(idx, torch.int32), out=out, classes_out=cls_out)
     got = out.cpu().numpy()
     eng.close()
     assert np.array_equal(got[:, :D].view(np.uint32), plain.view(np.uint32))
-    assert (got[:, D:] == SENT).all()
+    assert (got[:, D:] == G.SENT).all()
     assert np.array_equal(cls_out.cpu().numpy(), cls)
 
 
@@ -160,14 +123,7 @@ def test_heatmap_is_the_reference_map_of_the_raw_gradient(dtype):
 
 @pytest.mark.parametrize("dtype", [E.F32, E.BF16])
 def test_heatmap_of_an_all_dead_row_is_zero(dtype):
-    K, D, n = 6, 72, 200
-    case, x32, _, _ = _problem(K, D, n)
-    eng = P.engine(D, B, dtype, num_classes=K)
-    d = [p.astype(np.float32) for p in case.d0]
-    d[1] = -np.abs(d[1]) - 0.5                          # first-layer biases negative: a zero row has every unit of layer 1 dead
-    eng.set_weights(E.NET_D, d)
-    x = x32[:5].copy()
-    x[2] = 0.0
+    eng, x = G.dead_row_engine(dtype, 6, 72, 200)
     raw, _ = _grad(eng, x)
     hm, _ = _grad(eng, x, post=E.SAL_HEATMAP)
     eng.close()
@@ -176,42 +132,14 @@ def test_heatmap_of_an_all_dead_row_is_zero(dtype):
 
 
 # ---- 6. training is undisturbed ------------------------------------------------------------------------------------
-def _state(eng):
-    out = []
-    for net in (E.NET_G, E.NET_D):
-        out += eng.get_weights(net) + eng.get_slot(net, 0) + eng.get_slot(net, 1)
-    return out, eng.get_iterations(), eng.read_metrics(reset=False)
-
-
-def _assert_same_state(a, b):
-    for x, y in zip(a[0], b[0]):
-        assert np.array_equal(x.view(np.uint32), y.view(np.uint32))
-    assert a[1] == b[1]
-    assert np.array_equal(np.asarray(a[2], np.float32).view(np.uint32), np.asarray(b[2], np.float32).view(np.uint32))
+_state, _assert_same_state, _assert_finite_state = G.state, G.assert_same_state, G.assert_finite_state
 
 
 def test_training_is_undisturbed_by_saliency_calls():
-    D = 400
-    case = Case(D=D, B=B, steps=3, device_z=True)
-    big = P.to_dev(1e3 * np.random.default_rng(9).standard_normal((3 * 64 + 7, D)).astype(np.float32))
-    states = []
-    for disturb in (False, True):
-        eng = P.engine(D, B, E.BF16)
-        P.load(eng, case)
-        for t in range(case.steps):
-            if disturb:
-                out, _ = eng.input_gradient(big, None, E.SAL_XENT, E.SAL_HEATMAP if t == 1 else E.SAL_RAW)
-                assert bool(torch.isfinite(out).all())
-            eng.disc_step(P.disc_args(case, t, True))
-            eng.gen_step(P.gen_args(case, t, True))
-        states.append(_state(eng))
-        eng.close()
-    assert states[0][1] == 2 * case.steps
-    _assert_same_state(*states)
-
-
-def _assert_finite_state(a):
-    assert all(np.isfinite(x).all() for x in a[0]) and np.isfinite(np.asarray(a[2], np.float32)).all()
+    def disturb(eng, big, t):
+        out, _ = eng.input_gradient(big, None, E.SAL_XENT, E.SAL_HEATMAP if t == 1 else E.SAL_RAW)
+        assert bool(torch.isfinite(out).all())
+    G.training_is_undisturbed_by(disturb)
 
 
 def test_training_is_undisturbed_by_evaluation_calls():
@@ -278,35 +206,7 @@ def test_group_training_is_undisturbed_by_evaluation_calls():
 
 
 def test_graph_replay_is_undisturbed_by_saliency_calls():
-    from mr_gan_amd import MRGAN
-    D, n = 400, 4 * B
-    case = Case(D=D, B=B, steps=1, device_z=True)
-    rs = np.random.RandomState(3)
-    X, xl = rs.randn(n, D).astype(np.float32), rs.randn(2 * B, D).astype(np.float32)
-    yl = rs.randint(0, 6, size=2 * B).astype(np.int32)
-    big = 1e3 * rs.randn(3 * 64 + 7, D).astype(np.float32)
-    states = []
-    for disturb in (False, True):
-        m = MRGAN(D, batch_size=B, dtype='bfloat16', seed=77, use_graph=True, init_weights=False)
-        P.load(m.engine, case)
-        with m._on_stream():
-            xu, xlab, bigd = m._dev(X), m._dev(xl), m._dev(big)
-            idx_lab = m._dev(np.arange(n, dtype=np.int32) % (2 * B), torch.int32)
-            labs = m._dev(yl[np.arange(n) % (2 * B)], torch.int32)
-            idx_u1 = m._dev(np.arange(n, dtype=np.int32)[::-1].copy(), torch.int32)
-            idx_u2 = m._dev(np.roll(np.arange(n, dtype=np.int32), 7), torch.int32)
-            dargs = E.Engine.disc_args(xlab, labs, xu, None, idx_lab, idx_u1, stream_mode=1)
-            gargs = E.Engine.gen_args(xu, None, idx_u2, stream_mode=1)
-            m.engine.set_iterations(0, 0)
-            for _ in range(n // B):
-                if disturb:
-                    m.engine.input_gradient(bigd, None, E.SAL_XENT, E.SAL_RAW)
-                m.engine.train_pair(dargs, gargs)
-            torch.cuda.synchronize()
-            states.append(_state(m.engine))
-        m.engine.close()
-    assert states[0][1] == 2 * (n // B)
-    _assert_same_state(*states)
+    G.graph_replay_is_undisturbed_by(lambda eng, big, t: eng.input_gradient(big, None, E.SAL_XENT, E.SAL_RAW))
 
 
 # ---- 7. determinism ------------------------------------------------------------------------------------------------
@@ -326,19 +226,8 @@ def test_two_calls_give_identical_bits(dtype):
 # ---- 8. group handle -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
 def test_group_handle_serves_the_selected_model(dtype):
-    from mr_gan_amd import MRGAN, MRGANGroup
-    D, seed = 40, 123
-    X = np.random.default_rng(3).standard_normal((77, D)).astype(np.float32)
-    grp = MRGANGroup(D, 3, batch_size=B, dtype=dtype, seed=seed)
-    got = [grp.saliency(m, X) for m in (2, 0, 1)]
-    grp.engine.close()
-    for (maps, cls), m in zip(got, (2, 0, 1)):
-        one = MRGAN(D, batch_size=B, dtype=dtype, seed=seed + m)
-        want, wcls = one.saliency(X)
-        one.engine.close()
-        assert maps.shape == (77, D) and maps.dtype == np.float32 and maps.max() == 1.0
-        assert np.array_equal(maps.view(np.uint32), want.view(np.uint32)) and np.array_equal(cls, wcls)
-    assert not np.array_equal(got[0][0], got[1][0])
+    for maps, _ in G.group_handle_serves_the_selected_model(dtype, 77):
+        assert maps.max() == 1.0
 
 
 # ---- 9. the baseline's front end -----------------------------------------------------------------------------------
@@ -362,12 +251,7 @@ def test_mrnn_saliency():
 
 # ---- 10. refusals --------------------------------------------------------------------------------------------------
 def test_fp8_handle_is_refused():
-    eng = P.engine(64, 128, E.FP8)
-    with pytest.raises(E.MrganError) as ei:
-        eng.input_gradient(torch.zeros((4, 64), device=P.DEV))
-    eng.close()
-    msg = str(ei.value)
-    assert "error -3" in msg and "fp32" in msg and "bf16" in msg
+    G.fp8_handle_is_refused(lambda eng, x: eng.input_gradient(x))
 
 
 def test_bad_arguments_are_refused():
@@ -395,19 +279,12 @@ def test_bad_arguments_are_refused():
 # ---- 11. kernel names ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype,d_hidden", [(E.F32, None), (E.BF16, None), (E.BF16, WIDE_HEAD)])
 def test_kernels_of_one_call(dtype, d_hidden):
-    """the scalar head and the finishing kernel; no matrix-core head, no chain launch, no weight gradient, no update"""
-    D = 96
-    kw = dict(d_hidden=d_hidden) if d_hidden else {}
-    eng = P.engine(D, B, dtype, **kw)
-    P.load(eng, Case(D=D, B=B, steps=1, **kw))
-    x = P.to_dev(np.random.default_rng(3).standard_normal((130, D)).astype(np.float32))
+    """the scalar head and the one kernel that writes a map; no matrix-core head, no chain launch, no weight gradient, no update"""
+    eng, x = G.profiled_engine(dtype, d_hidden, 130)
     eng.profile_begin()
     eng.input_gradient(x, None, E.SAL_XENT, E.SAL_HEATMAP)
     prof = eng.profile_end()
     eng.close()
     print(sorted((k, v[1]) for k, v in prof.items()))
-    assert prof["saliency_finish_kernel"][1] == 2 and prof["head_kernel"][1] == 2 and prof["stage_kernel"][1] == 2
-    for name in prof:
-        assert not any(s in name for s in ("head_wide", "chain_kernel", "adam", "_ks_", "w6_split", "reduce_partials", "fm_kernel")), name
-        assert not name.startswith(("gemm_f32_kernel<2", "gemm_bf16_kc_kernel<2")), name
-    assert sum(v[1] for k, v in prof.items() if k.startswith("gemm")) == 20
+    assert prof["attribution_accum_kernel"][1] == 2 and prof["head_kernel"][1] == 2 and prof["stage_kernel"][1] == 2
+    G.assert_no_training_kernels(prof, 20)
