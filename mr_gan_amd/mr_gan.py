@@ -19,56 +19,49 @@ import sys
 
 import numpy as np
 
-from mr_gan_amd.data import MATERIALS, resolve_num_classes, select_labeled, standard_scale
+from mr_gan_amd.data import MATERIALS, prologue, resolve_num_classes, train_test_sets
 
 MODALITIES = ['Force', 'Temperature', 'Force and Temperature', 'Contact mic', 'Temperature and Contact Mic',
               'Force, Temperature, and Contact Mic', 'Force and Contact Mic']          # mr_gan.py:237
 
 
+def print_lines(lines, verbose=True):
+    """the lines of a run, each a tuple of print() arguments (data.prologue), when verbose"""
+    if verbose:
+        for args in lines:
+            print(*args)
+        sys.stdout.flush()
+
+
+def _run_lines(prologue_lines, epochs, batch_size, X_train, X_test):
+    """what a verbose mr_gan() prints before its first epoch (mr_gan.py:92-94, :108, :175-178)"""
+    return prologue_lines + [('Epochs:', epochs), ('Batch size:', batch_size), ('Training batches per epoch:', X_train.shape[0] // batch_size),
+                             ('Testing batches per epoch:', X_test.shape[0] // batch_size)]
+
+
+def _test_error_line(error, last_epoch_errors):
+    """mr_gan.py:231: the whole test set in one call, and the last epoch's mean over whole test batches"""
+    return [('Test error:', error, last_epoch_errors[-1] if last_epoch_errors else float('nan'))]
+
+
 def mr_gan(X, y, percentlabeled=50, percentunlabeled=None, epochs=100, trainTestSets=None, verbose=False,
            batch_size=50, dtype='float32', seed=None, device='cuda:0', noise='irwin-hall', num_classes=None):
-    from sklearn.model_selection import train_test_split
-    from sklearn.utils import shuffle
-
     from mr_gan_amd.engine import noise_flags
     from mr_gan_amd.model import MRGAN
     noise_flags(noise)                                             # an unknown value fails before any data is touched
 
     rs = np.random.RandomState(seed if seed is not None else np.random.randint(1 << 31))   # mr_gan.py:75 (unseeded there)
     num_classes = resolve_num_classes(num_classes)                 # None: the reference's six materials
-    test_ratio = 200 * num_classes                                 # mr_gan.py:81
-    num_labeled_examples = int(10 * percentlabeled)                # mr_gan.py:82
-    num_unlabeled_examples = int(10 * percentunlabeled) if percentunlabeled is not None else None
-
-    if trainTestSets is None:                                      # mr_gan.py:87-90
-        X_train, X_test, y_train, y_test = train_test_split(X, y, test_size=test_ratio, stratify=y, random_state=rs)
-    else:
-        X_train, X_test, y_train, y_test = trainTestSets
-    if verbose:
-        print('Num of class examples in test set:', [int(np.sum(y_test == i)) for i in range(num_classes)])
-        print('X_train:', np.shape(X_train), 'y_train:', np.shape(y_train), 'X_test:', np.shape(X_test), 'y_test:',
-              np.shape(y_test))
-
-    X_train, X_test = standard_scale(X_train, X_test)              # mr_gan.py:96-98
-    X_train, y_train = shuffle(X_train, y_train, random_state=rs)  # mr_gan.py:101
-    x_labeled, y_labeled, x_unlabeled = select_labeled(X_train, y_train, num_labeled_examples, num_unlabeled_examples, num_classes=num_classes)
-    if verbose:
-        print('x_labeled:', np.shape(x_labeled), 'y_labeled:', np.shape(y_labeled))
-
+    sets = train_test_sets(X, y, trainTestSets, rs, num_classes)
+    x_labeled, y_labeled, x_unlabeled, X_train, X_test, y_test, lines = prologue(sets, percentlabeled, percentunlabeled, rs, num_classes)
+    print_lines(_run_lines(lines, epochs, batch_size, X_train, X_test), verbose)
     model = MRGAN(X_train.shape[1], batch_size=batch_size, dtype=dtype, seed=int(rs.randint(1 << 31)), device=device, noise=noise,
                   num_classes=num_classes)
-    if verbose:
-        print('Epochs:', epochs)
-        print('Batch size:', batch_size)
-        print('Training batches per epoch:', X_train.shape[0] // batch_size)
-        print('Testing batches per epoch:', X_test.shape[0] // batch_size)
     hist = model.fit(x_labeled, y_labeled, X_train, epochs=epochs, verbose=1 if verbose else 0,
                      validation_data=(X_test, y_test), x_unlabeled_pool=x_unlabeled, rng=rs)
     testerror = model.evaluate(X_test, y_test)                     # mr_gan.py:230 -- whole test set in one call
-    if verbose:
-        print('Test error:', testerror, hist[-1]['test_err'] if hist else float('nan'))
-        sys.stdout.flush()
-    model.engine.close()
+    print_lines(_test_error_line(testerror, [rec['test_err'] for rec in hist]), verbose)
+    model.close()
     return testerror
 
 
@@ -83,46 +76,25 @@ def mr_gan_folds(sets, percentlabeled=50, percentunlabeled=None, epochs=100, ver
     MRGAN(seed=s + f) with s drawn from RandomState(seed).  Raises UnequalFolds where the sets differ in length.
     verbose: the folds train together, so mr_gan()'s lines are printed after the training, fold by fold and in mr_gan()'s order
     (prologue, sizes, one line per epoch from the recorded history, test error): the lines of six verbose mr_gan() calls."""
-    from sklearn.utils import shuffle
-
     from mr_gan_amd.engine import noise_flags
-    from mr_gan_amd.model import EPOCH_LINE, MRGANGroup
+    from mr_gan_amd.model import MRGANGroup, epoch_line
     noise_flags(noise)
     base = int(seed if seed is not None else np.random.randint(1 << 30))
     num_classes = resolve_num_classes(num_classes)
-    num_labeled_examples = int(10 * percentlabeled)
-    num_unlabeled_examples = int(10 * percentunlabeled) if percentunlabeled is not None else None
     rss = [np.random.RandomState(base + f) for f in range(len(sets))]
-    folds, lines = [], []                                          # lines[f]: what a verbose mr_gan() of fold f prints, as print() arguments
-    for (X_train, X_test, y_train, y_test), rs in zip(sets, rss):  # mr_gan()'s prologue, fold by fold
-        out = [('Num of class examples in test set:', [int(np.sum(y_test == i)) for i in range(num_classes)]),
-               ('X_train:', np.shape(X_train), 'y_train:', np.shape(y_train), 'X_test:', np.shape(X_test), 'y_test:', np.shape(y_test))]
-        X_train, X_test = standard_scale(X_train, X_test)
-        X_train, y_train = shuffle(X_train, y_train, random_state=rs)
-        x_labeled, y_labeled, x_unlabeled = select_labeled(X_train, y_train, num_labeled_examples, num_unlabeled_examples, num_classes=num_classes)
-        out.append(('x_labeled:', np.shape(x_labeled), 'y_labeled:', np.shape(y_labeled)))
-        out += [('Epochs:', epochs), ('Batch size:', batch_size), ('Training batches per epoch:', X_train.shape[0] // batch_size),
-                ('Testing batches per epoch:', X_test.shape[0] // batch_size)]
-        lines.append(out)
-        folds.append((x_labeled, y_labeled, X_train, x_unlabeled, X_test, y_test))
-    pooled = [f[3] is not None for f in folds]
-    if (len({len(f[0]) for f in folds}) != 1 or len({len(f[2]) for f in folds}) != 1 or len(set(pooled)) != 1 or
-            (pooled[0] and len({len(f[3]) for f in folds}) != 1)):
+    x_labeled, y_labeled, pools, X_train, X_test, y_test, lines = zip(*[prologue(s, percentlabeled, percentunlabeled, rs, num_classes)
+                                                                        for s, rs in zip(sets, rss)])
+    if any(len({None if a is None else len(a) for a in group}) != 1 for group in (x_labeled, X_train, pools)):
         raise UnequalFolds("mr_gan_folds: the folds' training, labelled or unlabelled sets differ in length")
-    model = MRGANGroup(folds[0][2].shape[1], len(sets), batch_size=batch_size, dtype=dtype,
+    model = MRGANGroup(X_train[0].shape[1], len(sets), batch_size=batch_size, dtype=dtype,
                        seed=int(np.random.RandomState(base).randint(1 << 30)), device=device, noise=noise, num_classes=num_classes)
-    hist = model.fit([f[0] for f in folds], [f[1] for f in folds], [f[2] for f in folds], epochs=epochs, verbose=0,
-                     validation_data=[(f[4], f[5]) for f in folds], x_unlabeled_pools=[f[3] for f in folds] if pooled[0] else None, rngs=rss)
-    errors = model.evaluate([f[4] for f in folds], [f[5] for f in folds])          # mr_gan.py:230 -- whole test sets
-    if verbose:
-        for f, out in enumerate(lines):
-            for args in out:
-                print(*args)
-            for rec in hist:
-                print(EPOCH_LINE % (rec['epoch'], rec['time'], rec['loss_lab'][f], rec['loss_unl'][f], rec['train_err'][f], rec['test_err'][f]))
-            print('Test error:', errors[f], hist[-1]['test_err'][f] if hist else float('nan'))
-        sys.stdout.flush()
-    model.engine.close()
+    hist = model.fit(x_labeled, y_labeled, X_train, epochs=epochs, verbose=0, validation_data=list(zip(X_test, y_test)),
+                     x_unlabeled_pools=None if pools[0] is None else pools, rngs=rss)
+    errors = model.evaluate(X_test, y_test)                        # mr_gan.py:230 -- whole test sets
+    for f in range(len(sets)):
+        print_lines(_run_lines(lines[f], epochs, batch_size, X_train[f], X_test[f]) + [(epoch_line(rec, f),) for rec in hist] +
+                    _test_error_line(errors[f], [rec['test_err'][f] for rec in hist]), verbose)
+    model.close()
     return errors
 
 

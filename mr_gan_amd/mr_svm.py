@@ -11,32 +11,20 @@ import sys
 
 import numpy as np
 
-from mr_gan_amd.data import MATERIALS, select_labeled, standard_scale
-from mr_gan_amd.mr_gan import MODALITIES, dataset
+from mr_gan_amd.data import prologue, resolve_num_classes, train_test_sets
+from mr_gan_amd.mr_gan import MODALITIES, dataset, print_lines
 
 
 SVC_GAMMA = 'auto'
 
 
 def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None):
-    from sklearn.model_selection import train_test_split
     from sklearn.svm import SVC
-    from sklearn.utils import shuffle
     rs = np.random.RandomState(seed if seed is not None else np.random.randint(1 << 31))     # mr_svm.py:79 is unseeded
-    test_ratio = 200 * len(MATERIALS)                              # mr_svm.py:82
-    num_labeled_examples = int(10 * percentlabeled)                # mr_svm.py:83
-    if trainTestSets is None:                                      # mr_svm.py:86-89
-        X_train, X_test, y_train, y_test = train_test_split(X, y, test_size=test_ratio, stratify=y, random_state=rs)
-    else:
-        X_train, X_test, y_train, y_test = trainTestSets
-    if verbose:
-        print('Num of class examples in test set:', [int(np.sum(y_test == i)) for i in range(len(MATERIALS))])
-        print('X_train:', np.shape(X_train), 'y_train:', np.shape(y_train), 'X_test:', np.shape(X_test), 'y_test:', np.shape(y_test))
-    X_train, X_test = standard_scale(X_train, X_test)              # mr_svm.py:95-97
-    X_train, y_train = shuffle(X_train, y_train, random_state=rs)  # mr_svm.py:100
-    x_labeled, y_labeled, _ = select_labeled(X_train, y_train, num_labeled_examples)
-    if verbose:
-        print('x_labeled:', np.shape(x_labeled), 'y_labeled:', np.shape(y_labeled))
+    num_classes = resolve_num_classes(None)
+    sets = train_test_sets(X, y, trainTestSets, rs, num_classes)   # mr_svm.py:82-89
+    x_labeled, y_labeled, _, _, X_test, y_test, lines = prologue(sets, percentlabeled, None, rs, num_classes)
+    print_lines(lines, verbose)
     # mr_svm.py:106 is SVC(kernel='rbf', C=1.0) under the scikit-learn of 2017 (Keras 2.0.9 era, README.md:43-48), whose default
     # kernel width was gamma='auto' = 1 / n_features.  scikit-learn >= 0.22 defaults to 'scale' (1 / (n_features * X.var())),
     # which differs on the small standardised labeled subset: pass the reference's value explicitly.
@@ -44,8 +32,7 @@ def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None
     svm.fit(x_labeled, y_labeled)
     testerror = 1.0 - svm.score(X_test, y_test)                    # mr_svm.py:110
     if verbose:
-        print('Test error:', testerror, 1.0 - np.mean(svm.predict(X_test) == y_test))
-        sys.stdout.flush()
+        print_lines([('Test error:', testerror, 1.0 - np.mean(svm.predict(X_test) == y_test))])
     return testerror
 
 

@@ -12,6 +12,14 @@ from oracle import mrgan_oracle as O
 SEED = 0x5EED5EED
 
 
+def planted(n, d, seed):
+    """n rows of six planted classes (y = arange(n) % 6): class centres 2 N(0, 1), unit noise -> (X float32 [n, d], y int32)"""
+    rng = np.random.default_rng(seed)
+    y = (np.arange(n) % 6).astype(np.int32)
+    centres = 2.0 * rng.standard_normal((6, d)).astype(np.float32)
+    return centres[y] + rng.standard_normal((n, d)).astype(np.float32), y
+
+
 def layer_dims(D, d_hidden=O.D_HIDDEN):
     return (D,) + tuple(d_hidden)
 

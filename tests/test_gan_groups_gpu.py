@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from tests import parity as P
-from tests.helpers import SEED, Case
+from tests.helpers import SEED, Case, planted as _planted
 
 pytestmark = pytest.mark.gpu
 
@@ -317,13 +317,6 @@ def test_refusals():
 # ---------------------------------------------------------------------------------------------------------
 # 6. host level
 # ---------------------------------------------------------------------------------------------------------
-def _planted(n, d, seed):
-    rng = np.random.default_rng(seed)
-    y = (np.arange(n) % 6).astype(np.int32)
-    centres = 2.0 * rng.standard_normal((6, d)).astype(np.float32)
-    return centres[y] + rng.standard_normal((n, d)).astype(np.float32), y
-
-
 def test_mrgan_group_fit_equals_single_fits():
     """MRGANGroup.fit for 2 epochs, G 3, D 40, B 32, n 128 against three MRGAN(seed + m).fit runs with the same rngs: weights,
     history and evaluate"""

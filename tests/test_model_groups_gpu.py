@@ -11,7 +11,7 @@ import torch
 
 from oracle import mrgan_oracle as O
 from tests import parity as P
-from tests.helpers import SEED, Case
+from tests.helpers import SEED, Case, planted as _planted
 
 pytestmark = pytest.mark.gpu
 
@@ -348,13 +348,6 @@ def test_default_path_is_untouched():
 # ---------------------------------------------------------------------------------------------------------
 # 8. host level
 # ---------------------------------------------------------------------------------------------------------
-def _planted(n, d, seed):
-    rng = np.random.default_rng(seed)
-    y = (np.arange(n) % 6).astype(np.int32)
-    centres = 2.0 * rng.standard_normal((6, d)).astype(np.float32)
-    return centres[y] + rng.standard_normal((n, d)).astype(np.float32), y
-
-
 def test_mrnn_group_equals_single_mrnn_runs():
     """three planted 90-row sets, batch 20 (a short last batch), two epochs"""
     from mr_gan_amd import engine as E
