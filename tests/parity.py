@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from mr_gan_amd import engine as E
+from mr_gan_amd.dist import DataParallel, EngineBackend, PhaseBackend, dp_flags
 from oracle import mrgan_oracle as O
 from tests.gaussian_noise import gaussian_normal
 from tests.helpers import SEED, Case, cosine, frob_rel_err, noise_set, rel_err, update_rel_err
@@ -370,18 +371,34 @@ def rank_args(case, t, world=2):
     return [disc_args(case, t, True, s) for s in shards], [gen_args(case, t, True, s) for s in shards]
 
 
+D_EXCHANGES = ((E.D_GEN, E.REGION_BN_STATS, True), (E.D_MAIN, E.REGION_GRAD_D, False))      # (phase, what it produced, a batch statistic?)
+G_EXCHANGES = ((E.G_GEN, E.REGION_BN_STATS, True), (E.G_FEAT, E.REGION_FM_MOMENTS, True), (E.G_BWD, E.REGION_BN_BWD, True),
+               (E.G_TAIL, E.REGION_GRAD_G, False))
+
+
+def _walk(step, exchanges, ranks, args, allreduce, exact):
+    for ph, reg, statistic in exchanges:
+        for e, a in zip(ranks, args):
+            getattr(e, step)(a, ph, ph, want_outputs=False)
+        if exact or not statistic:                 # per-shard statistics (exact=False): only the gradients travel
+            allreduce(reg)
+
+
+def disc_walk(ranks, da, allreduce, exact=True):
+    """the D sub-step up to its all-reduced flat gradients (get_slot(NET_D, 2) reads them); D_ADAM is left to the caller"""
+    _walk("disc_step", D_EXCHANGES, ranks, da, allreduce, exact)
+
+
+def gen_walk(ranks, ga, allreduce, exact=True):
+    _walk("gen_step", G_EXCHANGES, ranks, ga, allreduce, exact)
+
+
 def phase_walk(ranks, da, ga, allreduce):
     """One (D, G) pair through the data-parallel phases (mr_gan_amd/dist.py): every phase on every rank, then the all-reduce
     of the region it produced, then the Adam phase.  -> (the D outputs per rank, the G loss per rank)"""
-    for ph, reg in ((E.D_GEN, E.REGION_BN_STATS), (E.D_MAIN, E.REGION_GRAD_D)):
-        for e, a in zip(ranks, da):
-            e.disc_step(a, ph, ph, want_outputs=False)
-        allreduce(reg)
+    disc_walk(ranks, da, allreduce)
     d_out = [e.disc_step(a, E.D_ADAM, E.D_ADAM) for e, a in zip(ranks, da)]
-    for ph, reg in ((E.G_GEN, E.REGION_BN_STATS), (E.G_FEAT, E.REGION_FM_MOMENTS), (E.G_BWD, E.REGION_BN_BWD), (E.G_TAIL, E.REGION_GRAD_G)):
-        for e, a in zip(ranks, ga):
-            e.gen_step(a, ph, ph, want_outputs=False)
-        allreduce(reg)
+    gen_walk(ranks, ga, allreduce)
     return d_out, [e.gen_step(a, E.G_ADAM, E.G_ADAM) for e, a in zip(ranks, ga)]
 
 
@@ -412,3 +429,362 @@ def two_rank_emulation_equals_full_batch(variant):
         assert update_rel_err(w, wr, wi) < 0.05, ("D", i)
     for e in ranks:
         e.close()
+
+
+# ---------------------------------------------------------------------------------------------------------
+# W rank handles in lock step on one GPU (tests/test_data_parallel_gpu.py): the all-reduce is a device-side add over the
+# ranks' exchange regions, the control flow is dist.DataParallel's own
+# ---------------------------------------------------------------------------------------------------------
+def sum_exchange(backends, on_exchange=None):
+    """-> allreduce(which): the sum over the backends' exchange_regions(which), in rank order, written back to every one of
+    them.  fp32 regions add in fp32; a bfloat16 payload adds in fp32 and rounds once, like a bf16 all-reduce
+    (test_two_rank_emulation_with_bf16_gradient_payload).  on_exchange(which) is called behind each exchange."""
+    def allreduce(which):
+        for views in zip(*(b.exchange_regions(which) for b in backends)):
+            acc = torch.float32 if views[0].dtype == torch.bfloat16 else views[0].dtype
+            tot = views[0].to(acc)
+            for v in views[1:]:
+                tot = tot + v.to(acc)
+            tot = tot.to(views[0].dtype)
+            for v in views:
+                v.copy_(tot)
+        if on_exchange is not None:
+            on_exchange(which)
+    return allreduce
+
+
+class LockstepBackend(PhaseBackend):
+    """W PhaseBackends (one per rank: EngineBackend, or the oracle stand-in of the CPU tests) as the one backend DataParallel
+    drives: each call goes to every rank in turn, the step arguments are a list with one entry per rank (its row shard).
+    pair_hint and fp8_calibration exist when every rank has them, as DataParallel asks (getattr)."""
+
+    def __init__(self, backends):
+        self.backends = list(backends)
+        dtypes = {getattr(b, "grad_dtype", None) for b in self.backends}
+        assert len(dtypes) == 1, dtypes
+        self.grad_dtype = dtypes.pop()
+        if all(hasattr(b, "pair_hint") for b in self.backends):
+            self.pair_hint = self._pair_hint
+        if all(hasattr(b, "fp8_calibration") for b in self.backends):
+            self.fp8_calibration = self._fp8_calibration
+
+    def disc_phase(self, args, phase):
+        for b, a in zip(self.backends, args):
+            b.disc_phase(a, phase)
+
+    def gen_phase(self, args, phase):
+        for b, a in zip(self.backends, args):
+            b.gen_phase(a, phase)
+
+    def region(self, which):
+        raise NotImplementedError("a lock-step backend has one region per rank: LockstepDataParallel sums them")
+
+    def _pair_hint(self, on=True):
+        for b in self.backends:
+            b.pair_hint(on)
+
+    def _fp8_calibration(self, kind, action):
+        rcs = {b.fp8_calibration(kind, action) for b in self.backends}
+        assert len(rcs) == 1, ("the replicas disagree about their calibration state", kind, action, rcs)
+        return rcs.pop()
+
+
+class LockstepDataParallel(DataParallel):
+    """dist.DataParallel over W ranks in one process: train_pair / disc_step / gen_step run unchanged (pair hint, fp8
+    calibration order, which exchanges a sub-step skips); only the all-reduce is replaced, by sum_exchange."""
+
+    def __init__(self, backends, exact=True, on_exchange=None):
+        super().__init__(LockstepBackend(backends), exact=exact)
+        self.world = len(backends)
+        self._sum = sum_exchange(self.backend.backends, on_exchange)
+
+    def _allreduce(self, which):
+        self._sum(which)
+
+
+def lockstep(ranks, exact=True, on_exchange=None):
+    """LockstepDataParallel over engine handles"""
+    return LockstepDataParallel([EngineBackend(e) for e in ranks], exact=exact, on_exchange=on_exchange)
+
+
+def _equal_on_all_ranks(per_rank, what):
+    for r, other in enumerate(per_rank[1:], 1):
+        for i, (a, b) in enumerate(zip(per_rank[0], other)):
+            np.testing.assert_array_equal(b, a, err_msg="%s %d: rank %d differs from rank 0" % (what, i, r))
+
+
+def shard_mean_reference(case, make, shards, d_after=None):
+    """One D and one G sub-step of `shards` independent references make() -> MRGANOracle | MRGANMirror, reference r on the rows
+    [r h, (r + 1) h) of the batch with the noise and z of those GLOBAL rows: the mean over the references of their gradients and
+    D outputs, and each one's generator loss.  shards = 1 is the full-batch step.  With per-shard statistics every rank scales its
+    sums by 1 / B_global and its feature-matching gradient by 1 / world, so the all-reduced sum is this mean of shard means.
+    The G sub-step runs on d_after (default: the D weights after Adam on the mean D gradients, as every replica applies them)."""
+    h = case.B // shards
+    models = [make() for _ in range(shards)]
+    mean = lambda parts: [sum(ts) / shards for ts in zip(*parts)]
+    outs, grads = zip(*[m.disc_grads(**case.disc_inputs(0, 0, rows=h, row0=r * h))[:2] for r, m in enumerate(models)])
+    res = dict(d_out=np.mean(np.array(outs, np.float64), axis=0), gd=mean(grads))
+    if d_after is None:
+        models[0].adam.apply(models[0].d, res['gd'], 'd')
+        d_after = models[0].d
+    res['d_after'] = [np.array(p) for p in d_after]
+    for m in models:
+        m.d = [p.copy() for p in res['d_after']]
+        m.adam.iterations = 1
+    losses, grads = zip(*[m.gen_grads(**case.gen_inputs(0, 1, rows=h, row0=r * h))[:2] for r, m in enumerate(models)])
+    res.update(g_loss=[float(l) for l in losses], gg=mean(grads))
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def _dp_problem(variant, D, B, d_hidden, shards, quantize):
+    """(case, the tight reference, the fp64 reference on the tight one's updated D weights); shared, never modified"""
+    case = variant.case(D=D, B=B, steps=1, device_z=True, **({'d_hidden': d_hidden} if d_hidden else {}))
+    o64 = lambda: O.MRGANOracle(case.g0, case.d0)
+    if not quantize:
+        ref = shard_mean_reference(case, o64, shards)
+        return case, ref, ref
+    mir = shard_mean_reference(case, lambda: O.MRGANMirror(case.g0, case.d0, quantize=quantize), shards)
+    return case, mir, shard_mean_reference(case, o64, shards, d_after=mir['d_after'])
+
+
+@functools.lru_cache(maxsize=None)
+def _full_batch_handle_grads(variant, D, B, d_hidden, dtype, quantize):
+    """(D gradients, G gradients) of ONE full-batch FLAT_GRADS | SYNC_STATS handle on the problem above: what W ranks should
+    reproduce up to summation order.  Reported beside the references, not asserted."""
+    case, ref, _ = _dp_problem(variant, D, B, d_hidden, 1, quantize)
+    eng = variant.engine(D, B, dtype, flags=E.FLAG_FLAT_GRADS | E.FLAG_SYNC_STATS, **({'d_hidden': d_hidden} if d_hidden else {}))
+    try:
+        load(eng, case)
+        none = lambda which: None
+        da, ga = [disc_args(case, 0, True)], [gen_args(case, 0, True)]
+        disc_walk([eng], da, none)
+        gd = eng.get_slot(E.NET_D, 2)
+        eng.disc_step(da[0], E.D_ADAM, E.D_ADAM)
+        eng.set_weights(E.NET_D, [p.astype(np.float32) for p in ref['d_after']])
+        gen_walk([eng], ga, none)
+        return gd, eng.get_slot(E.NET_G, 2)
+    finally:
+        eng.close()
+
+
+FP32_GRAD_TOL = dict(dD=2e-5, dG=2e-4)        # the rel_err bounds of fp32_gradients_match_oracle
+
+
+def dp_grad_parity(variant, D, B, world, dtype, tol=None, tol_loss=None, d_hidden=None, frac=0.6, loose=(0.995, 0.98, 0.25), exact=True):
+    """The data-parallel twin of grad_parity: W rank handles at B / W rows (rank r: global rows [r h, (r + 1) h)), one D and one
+    G sub-step through the phases with the all-reduces of the protocol in between; the all-reduced flat gradients and the
+    outputs of the Adam phases against references of the FULL batch.
+    exact (FLAT_GRADS | SYNC_STATS): the references are the full-batch MRGANMirror(quantize='bf16') and the fp64 oracle under
+    the rule of grad_parity -- err(engine, mirror) < max(tol, frac * err(mirror, fp64)), and the loose direction bound.
+    not exact (FLAT_GRADS, per-shard statistics): the mean over ranks of W shard-sized references (shard_mean_reference).
+    dtype 0: the fp64 oracle alone, at the bounds of fp32_gradients_match_oracle.
+    Every rank must hold the same all-reduced gradients and Adam outputs bit for bit.  The G sub-step starts from the same
+    updated D weights on the engine, the mirror and the oracle, as in grad_parity."""
+    quantize = 'bf16' if dtype else None
+    kw = {'d_hidden': d_hidden} if d_hidden else {}
+    case, ref_m, ref_o = _dp_problem(variant, D, B, d_hidden, 1 if exact else world, quantize)
+    full = _full_batch_handle_grads(variant, D, B, d_hidden, dtype, quantize) if exact else None
+    flags = E.FLAG_FLAT_GRADS | (E.FLAG_SYNC_STATS if exact else 0)
+    ranks = [variant.engine(D, B // world, dtype, flags=flags, rank=r, world=world, **kw) for r in range(world)]
+    allreduce = sum_exchange(ranks)
+    report = []
+
+    def check(name, k, want_m, want_o, cos_min):
+        per_rank = [e.get_slot(E.NET_D if name == "dD" else E.NET_G, 2) for e in ranks]
+        for i, (a, m, o) in enumerate(zip(per_rank[0], want_m, want_o)):
+            em, eo, emo = frob_rel_err(a, m), frob_rel_err(a, o), frob_rel_err(m, o)
+            report.append("%s%-2d %.1e %.1e %.1e" % (name, i, em, eo, emo) + (" %.1e" % frob_rel_err(a, full[k][i]) if full else ""))
+        _equal_on_all_ranks(per_rank, name)
+        for i, (a, m, o) in enumerate(zip(per_rank[0], want_m, want_o)):
+            if quantize:
+                em, emo = frob_rel_err(a, m), frob_rel_err(m, o)
+                assert em < max(tol, frac * emo), (name + " vs mirror", i, em, emo)
+                assert cosine(a, o) > cos_min and frob_rel_err(a, o) < loose[2], (name + " vs fp64", i, cosine(a, o), frob_rel_err(a, o))
+            else:
+                assert rel_err(a, o) < FP32_GRAD_TOL[name], (name, i, rel_err(a, o))
+
+    try:
+        for e in ranks:
+            load(e, case)
+        da, ga = rank_args(case, 0, world)
+        disc_walk(ranks, da, allreduce, exact)
+        check("dD", 0, ref_m['gd'], ref_o['gd'], loose[0])
+        outs = [e.disc_step(a, E.D_ADAM, E.D_ADAM) for e, a in zip(ranks, da)]
+        print("\nD outputs %s, reference %s" % (outs[0], tuple(ref_m['d_out'])))
+        for out in outs[1:]:
+            assert out == outs[0], outs                                 # the loss sums travel behind the gradients
+        if quantize:             # the loss rule of grad_parity
+            for got_l, m_l, o_l in zip(outs[0][:2], ref_m['d_out'][:2], ref_o['d_out'][:2]):
+                np.testing.assert_allclose(got_l, m_l, rtol=max(tol_loss, frac * abs(m_l - o_l) / max(abs(o_l), 1e-12)), atol=tol_loss * 0.1)
+            assert abs(outs[0][2] - ref_m['d_out'][2]) <= 1.01 / B      # an argmax may flip
+        else:                    # fp32_gradients_match_oracle's
+            np.testing.assert_allclose(outs[0], ref_o['d_out'], rtol=2e-4, atol=2e-5)
+        for e in ranks:
+            e.set_weights(E.NET_D, [p.astype(np.float32) for p in ref_m['d_after']])
+        gen_walk(ranks, ga, allreduce, exact)
+        check("dG", 1, ref_m['gg'], ref_o['gg'], loose[1])
+        lgs = [e.gen_step(a, E.G_ADAM, E.G_ADAM) for e, a in zip(ranks, ga)]
+        print("G loss per rank %s, reference %s" % (lgs, ref_m['g_loss']))
+        # synchronised statistics: one loss, of the all-reduced moments; per-shard statistics: every rank its own shard's
+        want = ref_m['g_loss'] * world if exact else ref_m['g_loss']
+        assert not exact or all(lg == lgs[0] for lg in lgs), lgs
+        for lg, loss in zip(lgs, want):
+            assert abs(lg - loss) < ((5 * tol_loss) if quantize else 2e-3) * abs(loss) + (1e-12 if quantize else 1e-9), (lgs, want)
+    finally:
+        for e in ranks:
+            e.close()
+        print("(D=%d, B=%d, W=%d%s) tensor: err vs %s | vs fp64 | reference vs fp64%s\n  " % (
+            D, B, world, "" if exact else ", per-shard statistics", "mirror" if quantize else "fp64", " | vs one full-batch handle" if full else "") + "\n  ".join(report))
+
+
+def shards_stage_the_rows_of_the_full_batch(variant, dtype, D, B, world):
+    """D_GEN + D_MAIN on W rank handles and on one full-batch handle with the same flags, every handle forced to one product tile
+    (TUNE_KC_CFG 0): rows [0, h) of the two real-row segments on rank r against rows [r h, (r + 1) h) of the full batch's.
+    * xin[0], the staged rows with their noise: a function of (seed, site, segment, iteration, GLOBAL row, column) alone.
+    * xin[1], the first discriminator product with its noise epilogue: a row's reduction order does not depend on how many
+      rows the launch has."""
+    flags = E.FLAG_FLAT_GRADS | E.FLAG_SYNC_STATS
+    case = variant.case(D=D, B=B, steps=1, device_z=True)
+    h = B // world
+    full = variant.engine(D, B, dtype, flags=flags)
+    ranks = [variant.engine(D, h, dtype, flags=flags, rank=r, world=world) for r in range(world)]
+    try:
+        for e in [full] + ranks:
+            e.set_tuning(E.TUNE_KC_CFG, 0)
+            load(e, case)
+        disc_walk([full], [disc_args(case, 0, True)], lambda which: None)
+        disc_walk(ranks, rank_args(case, 0, world)[0], sum_exchange(ranks))
+        for l, what in ((0, "staged rows"), (1, "first product")):
+            want = full.debug_buffer(0, l).cpu().numpy()
+            assert np.abs(want[:2, :B]).max() > 0.1, what
+            for r, e in enumerate(ranks):
+                got = e.debug_buffer(0, l).cpu().numpy()
+                for seg in (0, 1):
+                    np.testing.assert_array_equal(got[seg, :h], want[seg, r * h:(r + 1) * h], err_msg="%s, segment %d, rank %d" % (what, seg, r))
+    finally:
+        for e in [full] + ranks:
+            e.close()
+
+
+def fp8_replicas_calibrate_in_lock_step(D, B, world):
+    """One D and one G sub-step of W fp8 replicas through the lock-step DataParallel with synchronised statistics: the HOST runs
+    the calibration passes, with real exchanges between the replicas.  -> nothing; asserts inside."""
+    case = Case(D=D, B=B, steps=1, device_z=True)
+    ranks = [engine(D, B // world, E.FP8, flags=dp_flags(exact=True), rank=r, world=world) for r in range(world)]
+    seen = {}
+
+    def tap(which):            # the all-reduced gradients, before the Adam phase
+        if which in (E.REGION_GRAD_D, E.REGION_GRAD_G):
+            seen.setdefault(which, []).append([e.get_slot(E.NET_D if which == E.REGION_GRAD_D else E.NET_G, 2) for e in ranks])
+
+    try:
+        for e in ranks:
+            load(e, case)
+        dp = lockstep(ranks, exact=True, on_exchange=tap)
+        da, ga = rank_args(case, 0, world)
+        orc = O.MRGANOracle(case.g0, case.d0)
+        _, gd_o, _ = orc.disc_grads(**case.disc_inputs(0, 0))
+        dp.disc_step(da)
+        wd = [e.get_weights(E.NET_D) for e in ranks]
+        orc.d = [p.astype(np.float64) for p in wd[0]]
+        orc.adam.iterations = 1
+        _, gg_o, _ = orc.gen_grads(**case.gen_inputs(0, 1))
+        dp.gen_step(ga)
+        assert len(seen[E.REGION_GRAD_D]) == 1 and len(seen[E.REGION_GRAD_G]) == 1       # the dry passes exchange no gradients
+        for name, which, want, cos_min in (("dD", E.REGION_GRAD_D, gd_o, 0.9), ("dG", E.REGION_GRAD_G, gg_o, 0.8)):
+            per_rank = seen[which][0]
+            print("\n%s: cosine / err vs fp64 %s" % (name, " ".join("%.3f/%.2f" % (cosine(a, o), frob_rel_err(a, o)) for a, o in zip(per_rank[0], want))))
+            _equal_on_all_ranks(per_rank, name)
+            for i, (a, o) in enumerate(zip(per_rank[0], want)):
+                assert cosine(a, o) > cos_min and frob_rel_err(a, o) < 0.6, (name + " vs fp64", i, cosine(a, o), frob_rel_err(a, o))
+        _equal_on_all_ranks(wd, "D weight")
+        _equal_on_all_ranks([e.get_weights(E.NET_G) for e in ranks], "G weight")
+        for e in ranks:
+            assert e.fp8_calibration(0, E.Engine.FP8_CAL_QUERY) == 1 and e.fp8_calibration(1, E.Engine.FP8_CAL_QUERY) == 1
+    finally:
+        for e in ranks:
+            e.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _pairs_problem(D, B, d_hidden, steps):
+    """(case, its fp64 trajectory, the bf16 mirror's) of `steps` full-batch (D, G) pairs; shared, never modified"""
+    case = Case(D=D, B=B, steps=steps, device_z=True, **({'d_hidden': d_hidden} if d_hidden else {}))
+    return case, case.run_oracle(), case.run_oracle(mirror=True, quantize='bf16')
+
+
+@functools.lru_cache(maxsize=None)
+def lockstep_pairs(D, B, world, d_hidden=None, grad_dtype=None, paired=True, steps=2):
+    """`steps` (D, G) pairs of W bf16 replicas with synchronised statistics through the lock-step DataParallel -- paired: train_pair
+    (the pair hint: both generator segments in the D sub-step's one BN_STATS all-reduce), else disc_step + gen_step with no
+    hint.  -> per rank (D weights, G weights, read_metrics); the replicas' weights are asserted bit-identical.  Shared, never modified."""
+    case = _pairs_problem(D, B, d_hidden, steps)[0]
+    kw = {'d_hidden': d_hidden} if d_hidden else {}
+    ranks = [engine(D, B // world, E.BF16, flags=dp_flags(exact=True, grad_dtype=grad_dtype), rank=r, world=world, **kw) for r in range(world)]
+    try:
+        for e in ranks:
+            load(e, case)
+        dp = lockstep(ranks, exact=True)
+        for t in range(steps):
+            da, ga = rank_args(case, t, world)
+            if paired:
+                dp.train_pair(da, ga)
+            else:
+                dp.disc_step(da)
+                dp.gen_step(ga)
+        torch.cuda.synchronize()
+        res = [(e.get_weights(E.NET_D), e.get_weights(E.NET_G), e.read_metrics(reset=False)) for e in ranks]
+        assert all(e.get_iterations() == 2 * steps for e in ranks)
+    finally:
+        for e in ranks:
+            e.close()
+    _equal_on_all_ranks([d + g for d, g, _ in res], "weight")
+    return res
+
+
+def lockstep_pairs_match_mirror(D, B, world, d_hidden=None, steps=2):
+    """(i) .. (iii) of the train_pair test: see tests/test_data_parallel_gpu.py"""
+    case, ref, mir = _pairs_problem(D, B, d_hidden, steps)
+    paired = lockstep_pairs(D, B, world, d_hidden, None, True, steps)           # (i) inside
+    apart = lockstep_pairs(D, B, world, d_hidden, None, False, steps)
+    # (ii) the paired generator pass is what the G sub-step would compute on its own
+    for (d1, g1, m1), (d0, g0, m0) in zip(paired, apart):
+        for i, (a, b) in enumerate(zip(d1 + g1, d0 + g0)):
+            np.testing.assert_array_equal(a, b, err_msg="tensor %d: train_pair differs from disc_step + gen_step" % i)
+        np.testing.assert_array_equal(np.asarray(m1), np.asarray(m0))
+    # (iii) the rule of test_bf16_steps_match_bf16_mirror
+    report = []
+    for name, ws, wm, wr_, w0 in (("D", paired[0][0], mir['d'], ref['d'], case.d0), ("G", paired[0][1], mir['g'], ref['g'], case.g0)):
+        for i, (w, wm_i, wr, wi) in enumerate(zip(ws, wm, wr_, w0)):
+            report.append((name, i, update_rel_err(w, wm_i, wi), update_rel_err(w, wr, wi), update_rel_err(wm_i, wr, wi)))
+    print("\nweights after %d pairs on %d ranks, error / update size: vs mirror | vs fp64 | mirror vs fp64\n  " % (steps, world) +
+          "\n  ".join("%s%-2d %.3f %.3f %.3f" % r for r in report))
+    for name, i, em, eo, emo in report:
+        assert em < max(0.05, 0.9 * emo), (name, i, em, emo)
+        assert eo < 0.5, (name, i, eo)
+
+
+def phases_equal_whole_steps(D, B, exact, steps=2):
+    """one bf16 rank: a FLAT_GRADS handle stepping through whole sub-steps against a dp_flags(exact) handle driven by
+    dist.DataParallel -> per net, per tensor: update_rel_err of the phased weights against the whole-step ones, and whether
+    they are bit-identical"""
+    case = Case(D=D, B=B, steps=steps, device_z=True)
+    plain = engine(D, B, E.BF16, flags=E.FLAG_FLAT_GRADS)
+    phased = engine(D, B, E.BF16, flags=dp_flags(exact=exact))
+    try:
+        for e in (plain, phased):
+            load(e, case)
+        dp = DataParallel(EngineBackend(phased), exact=exact)
+        for t in range(steps):
+            da, ga = disc_args(case, t, device_z=True), gen_args(case, t, device_z=True)
+            plain.disc_step(da, want_outputs=False)
+            plain.gen_step(ga, want_outputs=False)
+            dp.disc_step(da)
+            dp.gen_step(ga)
+        return [(net, i, update_rel_err(b, a, w0), bool(np.array_equal(a, b)))
+                for net, w0s in ((E.NET_D, case.d0), (E.NET_G, case.g0))
+                for i, (a, b, w0) in enumerate(zip(plain.get_weights(net), phased.get_weights(net), w0s))]
+    finally:
+        plain.close()
+        phased.close()

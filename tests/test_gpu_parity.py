@@ -264,6 +264,14 @@ def test_bf16_gradients_match_bf16_mirror(D, B):
     P.grad_parity(P.DEFAULT, D, B, 1, 'bf16', tol=3e-3, tol_loss=5e-4)
 
 
+def test_wide_head_bf16_gradients_match_bf16_mirror():
+    """six classes behind a 512-column feature layer (two chunks of the stand-alone matrix-core head; per-layer D tail) at the
+    bounds of the reference widths, as test_many_classes_gpu.py holds the same widths to at ten classes.  (96, 256) is also the
+    full batch of the data-parallel wide-head case (tests/test_data_parallel_gpu.py), which takes its bounds from here."""
+    from tests.saliency_ref import WIDE_HEAD
+    P.grad_parity(P.DEFAULT, 96, 256, 1, 'bf16', tol=3e-3, tol_loss=5e-4, d_hidden=WIDE_HEAD)
+
+
 @pytest.mark.parametrize("D,B", [(400, 256), (96, 50), (512, 1024),
                                  (64, 8200)])     # 129 row blocks per segment: the 64-row blocks of both G sub-step chains, last block 8 rows
 def test_chain_launches_equal_per_layer_launches(D, B):
