@@ -47,7 +47,7 @@ enum {
                                   * (MRGAN_REGION_TAIL_*) still travel in fp32, and mrgan_region refuses
                                   * MRGAN_REGION_GRAD_D / _G, whose fp32 bodies no phase reads.  A labelled, different
                                   * numerical path.                                                                       */
-    MRGAN_FLAG_GAUSS_NOISE = 16  /* the five GaussianNoise sites and the device-drawn z are true N(0, 1) variates (Box-Muller
+    MRGAN_FLAG_GAUSS_NOISE = 16, /* the five GaussianNoise sites and the device-drawn z are true N(0, 1) variates (Box-Muller
                                   * on the same counter keys, support +-5.77 sigma) instead of the default Irwin-Hall(32)
                                   * sums: what the reference's K.random_normal draws, for comparisons against it.  A
                                   * DIFFERENT random stream (results are not comparable draw by draw with a default handle)
@@ -55,6 +55,9 @@ enum {
                                   * entry honours it: mrgan_disc_step / mrgan_gen_step and their phases, mrgan_train_pair
                                   * with and without graph replay, data-parallel shards (rows stay global: the shards of a
                                   * batch draw what the full batch would), mrgan_sup_step, the _group entries.  Host-supplied z is untouched.  */
+    MRGAN_FLAG_AUTOENCODER = 32  /* a handle of another kind: MRGAN_NET_D is a dense autoencoder (mrgan_ae_step and the text
+                                  * above it); it trains through mrgan_ae_step and is read through mrgan_ae_encode /
+                                  * mrgan_ae_reconstruct only                                                             */
 };
 
 #define MRGAN_MAX_CLASSES 32   /* largest mrgan_config.num_classes */
@@ -180,6 +183,44 @@ typedef struct mrgan_sup_group_args {
     int32_t stream_mode, rows_valid;
 } mrgan_sup_group_args;
 int mrgan_sup_step_group(mrgan_handle* h, const mrgan_sup_group_args* a, float* out2_host, mrgan_stream stream);
+
+/* Autoencoder pre-stage (others/mr_gan_autoencoder.py:109-140 of the reference): the dimensionality reduction of the raw
+ * contact-microphone vector whose codes the unchanged GAN then trains on.  A handle created with MRGAN_FLAG_AUTOENCODER holds, as
+ * MRGAN_NET_D, the six dense layers d_in -> d_hidden[0] -> ... -> d_hidden[4] -> d_in (relu after the first five, linear last;
+ * the reference's three encoderNodes n0 n1 n2 are d_hidden = n0 n1 n2 n1 n0).  Tensor 10 is [d_hidden[4], d_in] and tensor 11
+ * [d_in], padded like a hidden layer, the last weight with the bf16 copies of the other five.  num_classes is validated and
+ * unused; the generator tensors exist and nothing reads them.  mrgan_config adds no field.
+ * mrgan_create refuses such a handle with a nonzero sigma[i] (status -1: no denoising variant), and (status -3) with
+ * MRGAN_FP8, models > 1, world != 1, MRGAN_FLAG_FLAT_GRADS, MRGAN_FLAG_SYNC_STATS or MRGAN_FLAG_GRAD_BF16.  On such a handle
+ * every GAN, supervised, group, fp8-calibration, evaluation (mrgan_eval_error, mrgan_predict_logits), saliency and attribution
+ * entry returns -3; on any other handle the three entries below do.
+ *
+ * mrgan_ae_step: one Keras train_on_batch(x, x) with loss = 'mse' and Adam (the handle's lr / beta_1 / beta_2 / eps; Keras'
+ * defaults are 0.001 / 0.9 / 0.999 / 1e-8).  x_dev / idx_dev / ld_x / stream_mode / rows_valid mean what they mean in
+ * mrgan_sup_args: gather, whole-epoch index stream with the device batch counter, Keras' short last batch; a short batch in
+ * stream mode is refused.  loss = mean over rows_valid x d_in of (y - x)^2 with y the stored output of the last layer (the
+ * engine's activation type) and x the caller's fp32 row, read again through the same gather; dY = 2 (y - x) / (rows_valid d_in).
+ * Every reduction folds per-block partials in a fixed order: a step is bit-reproducible.  One iteration-counter step.
+ * out1_host (optional): the loss.  mrgan_read_metrics: out8[0] accumulates the loss, out8[4] is the last one.
+ *
+ * mrgan_ae_encode: the learning-phase-0 forward through dense 3; the relu output of dense 3 (the code, d_hidden[2] wide) is
+ * written as fp32 [n][ld_code], ld_code >= d_hidden[2]; further columns of the caller's rows are left untouched.
+ * mrgan_ae_reconstruct: the full forward; y as fp32 [n][ld_out] (ld_out >= d_in, further columns untouched) where out_dev is
+ * given, the mse over all n x d_in elements where mse_host is given (fp32 sums per chunk in a fixed order, the chunks folded in
+ * order; the call synchronises then); both NULL is status -2.
+ * Both run in chunks of 3 S rows (S = batch rounded up to 128) through the training activations, leave weights, Adam slots,
+ * counters and metrics untouched and re-zero the padding rows they reached, so that a following step is unchanged bit for
+ * bit; two calls give identical bits.  Status -2: null x / output, n < 1, a pitch smaller than the row it holds. */
+typedef struct mrgan_ae_args {
+    const float* x_dev; const int32_t* idx_dev;
+    int64_t ld_x;
+    int32_t stream_mode, rows_valid;
+} mrgan_ae_args;
+int mrgan_ae_step(mrgan_handle* h, const mrgan_ae_args* a, float* out1_host, mrgan_stream stream);
+int mrgan_ae_encode(mrgan_handle* h, const float* x_dev, const int32_t* idx_dev, int64_t ld_x, int64_t n,
+                    float* code_dev, int64_t ld_code, mrgan_stream stream);
+int mrgan_ae_reconstruct(mrgan_handle* h, const float* x_dev, const int32_t* idx_dev, int64_t ld_x, int64_t n,
+                         float* out_dev, int64_t ld_out, float* mse_host, mrgan_stream stream);
 
 /* Log-mel front end of the contact-microphone modality (mr_gan.py:42-47: librosa.feature.melspectrogram(y, sr, n_mels=128)
  * followed by librosa.logamplitude(S, ref_power=np.max); n_fft 2048, hop 512, Slaney mel basis, -80 dB floor).  No handle:

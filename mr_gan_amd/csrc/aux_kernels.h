@@ -136,6 +136,32 @@ struct AttrAccumArgs {
 };
 int launch_attr_accum(int bf16, const AttrAccumArgs& a, hipStream_t s);
 
+// ---- autoencoder (MRGAN_FLAG_AUTOENCODER): the reconstruction head and the copy-out of the read-only entries ----
+// The mse head over the stored output y of the last layer against the caller's own fp32 rows x (row r of the batch is
+// src[(idx ? idx[o + r] : o + r) * ld_x + c], o = batch counter * batch_rows in stream mode): for r < rows_valid, c < cols
+//     dY[r][c] = T(scale * (y - x)),   loss partial += (y - x)^2
+// and exact zeros in every other element of the rows x cols_pad the grid covers (rows and cols_pad multiples of 64).  One block
+// = 64 rows x 64 columns: cs[row block][c] = the column sums of the STORED dY (what the weight-gradient product reads),
+// loss_part[(row block * column blocks + column block) * 4] = the block's sum of squares (the three further floats zero: the
+// layout the Adam launch's metrics pass folds).  Thread, wave and block sums in a fixed order, no atomics.  dy = cs = null:
+// the loss partials alone (mrgan_ae_reconstruct).
+struct ReconHeadArgs {
+    const void* y; int ldy;                    // T [rows][ldy]
+    const float* x; const int32_t* idx; long ld_x;
+    const DevState* st; int stream, batch_rows;
+    int rows, rows_valid, cols, cols_pad;
+    float scale;                               // 2 / (rows_valid * cols)
+    void* dy; int ldd;                         // T [rows][ldd] or null
+    float* cs; int ldcs;                       // [rows / 64][ldcs] or null
+    float* loss_part;                          // [rows / 64][cols_pad / 64][4]
+};
+int launch_recon_head(int bf16, const ReconHeadArgs& a, hipStream_t s);
+// acc[0] = (first ? 0 : acc[0]) + the sum of part[4 i], i < n, in a fixed order (one block)
+int launch_fold_loss(const float* part, int n, float* acc, int first, hipStream_t s);
+// dst[r][c] = (float)src[r][c] for c < cols: rows of a padded activation T [rows][lds] -> the caller's fp32 rows [rows][ldd];
+// columns >= cols of dst are never touched
+int launch_cast_rows(int bf16, const void* src, int lds, int rows, int cols, float* dst, long ldd, hipStream_t s);
+
 // ---- feature matching (mr_gan.py:152-154) ----
 struct FmArgs {
     const float* cs; int npart_fake, npart_real, ldcs;   // column partial sums of f: fake rows first, then real

@@ -630,6 +630,94 @@ __global__ __launch_bounds__(256) void attribution_accum_kernel(const AttrAccumA
     }
 }
 
+// =========================================================================================
+// autoencoder: the reconstruction (mse) head, the fold of its loss partials across the chunks of mrgan_ae_reconstruct, and the
+// copy of stored activation rows to the caller's fp32 rows (ReconHeadArgs, aux_kernels.h)
+// block = 64 rows x 64 columns; thread <-> 8 consecutive columns x rows (t >> 3) and (t >> 3) + 32
+// =========================================================================================
+template <typename T>
+__global__ __launch_bounds__(256) void recon_head_kernel(const ReconHeadArgs a) {
+    __shared__ float red[32][CB + 1];
+    __shared__ float wsum[4];
+    const int t = threadIdx.x, cg = (t & 7) * 8, rl = t >> 3;
+    const int col = (int)blockIdx.x * CB + cg, row0 = (int)blockIdx.y * RB;
+    const long o = a.stream ? (long)a.st->batch * a.batch_rows : 0;
+    const bool xvec = (a.ld_x & 3) == 0 && ((uintptr_t)a.x & 15) == 0 && col + 7 < a.cols;
+    float csum[8], sq = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) csum[c] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = row0 + rl + 32 * i;
+        float g[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) g[c] = 0.f;
+        if (row < a.rows_valid && col < a.cols) {
+            float y[8], x[8];
+            load8<T>((const T*)a.y + (long)row * a.ldy + col, y);
+            const float* xr = a.x + (a.idx ? (long)a.idx[o + row] : o + row) * a.ld_x + col;
+            if (xvec) load8<float>(xr, x);
+            else {
+#pragma unroll
+                for (int c = 0; c < 8; ++c) x[c] = col + c < a.cols ? xr[c] : 0.f;
+            }
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const float d = col + c < a.cols ? y[c] - x[c] : 0.f;
+                sq = fmaf(d, d, sq);
+                g[c] = Elem<T>::to_f32(Elem<T>::from_f32(a.scale * d));      // the stored value: what the dW product reads
+                csum[c] += g[c];
+            }
+        }
+        if (a.dy && row < a.rows) store8<T>((T*)a.dy + (long)row * a.ldd + col, g);
+    }
+    if (a.cs) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) red[rl][cg + c] = csum[c];
+    }
+    sq = wave_sum(sq);
+    if ((t & 63) == 0) wsum[t >> 6] = sq;
+    __syncthreads();
+    if (a.cs && t < CB) {
+        float s = 0.f;
+        for (int k = 0; k < 32; ++k) s += red[k][t];                          // fixed order: reproducible
+        a.cs[(long)blockIdx.y * a.ldcs + (int)blockIdx.x * CB + t] = s;
+    }
+    if (t == 0) {
+        float* lp = a.loss_part + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 4;
+        lp[0] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]); lp[1] = 0.f; lp[2] = 0.f; lp[3] = 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void fold_loss_kernel(const float* part, int n, float* acc, int first) {
+    __shared__ float ms[256];
+    const int t = threadIdx.x;
+    float s = 0.f;
+    for (int i = t; i < n; i += 256) s += part[(long)i * 4];
+    ms[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        float tot = 0.f;
+        for (int k = 0; k < 256; ++k) tot += ms[k];                           // fixed order: reproducible
+        acc[0] = (first ? 0.f : acc[0]) + tot;
+    }
+}
+
+// block = 256 threads x 8 consecutive columns of one row (grid.y = rows), as path_stage_kernel
+template <typename T>
+__global__ __launch_bounds__(256) void cast_rows_kernel(const T* src, int lds, int cols, float* dst, long ldd) {
+    const int row = blockIdx.y, c = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 8;
+    if (c >= cols) return;                                     // (lds is a multiple of 8 and >= cols: the group lies inside the padded row)
+    float v[8];
+    load8<T>(src + (long)row * lds + c, v);
+    float* out = dst + (long)row * ldd + c;
+    if (c + 7 < cols && (ldd & 3) == 0 && ((uintptr_t)dst & 15) == 0) store8<float>(out, v);
+    else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) if (c + i < cols) out[i] = v[i];
+    }
+}
+
 // dst[g][i] = sum of src[p][i] over the partial rows p of group g (p = g, g + ngroups, ...)
 __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* src, int nsrc, long stride, int n, int ngroups, float* dst,
                                                               long model_stride) {
@@ -1097,6 +1185,35 @@ int launch_attr_accum(int bf16, const AttrAccumArgs& a, hipStream_t s) {
     if (a.draws < 1 || a.draw < 0 || a.draw >= a.draws || !a.g || !a.out) return -3;
     if (a.multiply && (!a.x || a.ld_x < a.cols)) return -3;
     LAUNCH_T(attribution_accum_kernel, dim3(a.rows), dim3(256), 0, s, a);
+    RET_LAUNCH;
+}
+
+int launch_recon_head(int bf16, const ReconHeadArgs& a, hipStream_t s) {
+    if (a.rows <= 0) return 0;
+    if (!a.y || !a.x || !a.loss_part || a.cols <= 0 || a.cols > a.cols_pad || (a.cols_pad % CB) != 0 || a.ldy < a.cols_pad || (a.ldy % 8) != 0 ||
+        a.ld_x < a.cols || a.rows_valid < 0 || a.rows_valid > a.rows || (a.stream && !a.st))
+        return -3;
+    // the training form writes whole blocks of dY and one column-sum row per block
+    if (a.dy && ((a.rows % RB) != 0 || a.ldd < a.cols_pad || (a.ldd % 8) != 0)) return -3;
+    if (a.cs && (!a.dy || a.ldcs < a.cols_pad)) return -3;
+    LAUNCH_T(recon_head_kernel, dim3(a.cols_pad / CB, ceil_div(a.rows, RB)), dim3(256), 0, s, a);
+    RET_LAUNCH;
+}
+
+int launch_fold_loss(const float* part, int n, float* acc, int first, hipStream_t s) {
+    if (!part || !acc || n < 0) return -3;
+    MRGAN_LAUNCH(fold_loss_kernel, dim3(1), dim3(256), 0, s, part, n, acc, first);
+    RET_LAUNCH;
+}
+
+int launch_cast_rows(int bf16, const void* src, int lds, int rows, int cols, float* dst, long ldd, hipStream_t s) {
+    if (rows <= 0) return 0;
+    if (!src || !dst || cols <= 0 || cols > lds || (lds % 8) != 0 || ldd < cols) return -3;
+    for (int r0 = 0; r0 < rows; r0 += 32768) {             // (grid.y stays below its limit of 65535)
+        const dim3 grid(ceil_div(cols, 2048), std::min(32768, rows - r0));
+        if (bf16) MRGAN_LAUNCH(cast_rows_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)src + (long)r0 * lds, lds, cols, dst + (long)r0 * ldd, ldd);
+        else MRGAN_LAUNCH(cast_rows_kernel<float>, grid, dim3(256), 0, s, (const float*)src + (long)r0 * lds, lds, cols, dst + (long)r0 * ldd, ldd);
+    }
     RET_LAUNCH;
 }
 

@@ -272,7 +272,9 @@ int mrgan::fp8_refresh_weights(mrgan_handle* h, int net, hipStream_t s) {
 }
 namespace {
 
-int run_adam(mrgan_handle* h, int net, int mode, bool with_metrics, hipStream_t s, int advance_batch = 0) {
+// lp (optional): the loss partials [nlp][4] and their scale instead of the loss head's (the autoencoder step)
+int run_adam(mrgan_handle* h, int net, int mode, bool with_metrics, hipStream_t s, int advance_batch = 0, const float* lp = nullptr,
+             int nlp = 0, float lp_scale = 0.f) {
     AdamArgs a;
     memset(&a, 0, sizeof a);
     if (mode != ADAM_REDUCE_ONLY) { a.next = h->state + (h->cur ^ 1); a.advance_batch = advance_batch; a.lr = h->cfg.lr; }
@@ -284,6 +286,7 @@ int run_adam(mrgan_handle* h, int net, int mode, bool with_metrics, hipStream_t 
         a.loss_part = h->loss_part; a.nloss_part = h->head_nblk; a.inv_rows = 1.0f / (float)h->Bg;
         a.step_out = h->step_out; a.accum = h->accum;
         a.flat_tail = h->flat_d + h->flat_d_n;
+        if (lp) { a.loss_part = lp; a.nloss_part = nlp; a.inv_rows = lp_scale; }
     }
     a.models = h->grouped; a.model_stride = (long)h->W;
     {
@@ -535,8 +538,12 @@ int disc_bwd(mrgan_handle* h, int nseg, int l_top, int fold_rows, hipStream_t s)
     for (int l = l_top; l >= 1; --l)
         CHK(dense_dx(h, h->d[l], KIND_D, h->dpre[l], h->B, nseg, h->dpre[l - 1], ACT_RELU, h->d[l - 1].N, relu_mask(h, l - 1), nullptr,
                      ColSums{CS_SUM, h->cs_db[l - 1], nullptr}, s, Fp8Use{&h->d[l - 1], true, false}));
-    DwJob jobs[5];
+    DwJob jobs[6];
     for (int l = 0; l < 5; ++l) jobs[l] = DwJob{&h->d[l], h->xin[l], h->dpre[l]};
+    if (h->ae) {        // the last layer is a product like the others (features x dY), and no loss head left partials to fold
+        jobs[5] = DwJob{&h->d[5], h->feat, h->ae_dy};
+        return dense_dw_all(h, KIND_D, jobs, 6, h->B, nseg, s);
+    }
     const FoldJob fold = {h->head_part, h->head_red, (long)h->head_stride, fold_rows, h->head_stride, h->head_groups, 0,
                           h->grouped > 1 ? (long)h->W : 0};
     return dense_dw_all(h, KIND_D, jobs, 5, h->B, nseg, s, &fold);
@@ -715,8 +722,60 @@ int sup_step(mrgan_handle* h, const mrgan_sup_args* a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// autoencoder step (others/mr_gan_autoencoder.py:109-127): the supervised step's stack with a full-width last layer whose
+// target is the input row itself -- stage, dense 1..5 (relu, masks), dense 6 (linear) -> y, the reconstruction head -> dY, its
+// column sums and the loss partials, dX through dense 6 (relu mask of dense 5) and on down, six weight gradients, fused Adam
+// ---------------------------------------------------------------------------------------------------
+ReconHeadArgs recon_head_args(mrgan_handle* h, const float* x, const int32_t* idx, long ld, int rows, int rows_valid) {
+    ReconHeadArgs r;
+    memset(&r, 0, sizeof r);
+    r.y = h->ae_y; r.ldy = h->Dp;
+    r.x = x; r.idx = idx; r.ld_x = ld;
+    r.st = h->state + h->cur; r.batch_rows = h->B;
+    r.rows = rows; r.rows_valid = rows_valid; r.cols = h->cfg.d_in; r.cols_pad = h->Dp;
+    r.loss_part = h->ae_loss_part;
+    return r;
+}
+int ae_step(mrgan_handle* h, const mrgan_ae_args* a, hipStream_t s) {
+    const int B = h->B, rows_valid = a->rows_valid > 0 ? a->rows_valid : B;
+    prof_backlog(h, s);
+    StageArgs st;
+    memset(&st, 0, sizeof st);
+    data_seg(st.s[0], h, a->x_dev, a->idx_dev, a->ld_x, 0, 0, a->stream_mode, 0, 0);
+    st.nseg = 1;
+    stage_common(st, h, nullptr, 0, -1);
+    PROF("stage_kernel", launch_stage(h->bf16, st, s));
+    CHK(disc_fwd_train(h, KIND_D, 1, false, 0, s, 5));
+    const Dense& L6 = h->d[5];
+    CHK(dense_fwd(h, L6, KIND_D, h->feat, B, 1, h->ae_y, ACT_LINEAR, NO_NOISE, NO_MASK, NO_SUMS, s));
+    // dY over whole 64-row blocks: rows >= rows_valid are zeros there, and the rows behind them keep the zeros of mrgan_create
+    ReconHeadArgs r = recon_head_args(h, a->x_dev, a->idx_dev, a->ld_x, h->tiles_m * 64, rows_valid);
+    r.stream = a->stream_mode;
+    r.scale = 2.0f / ((float)rows_valid * (float)h->cfg.d_in);
+    r.dy = h->ae_dy; r.ldd = h->Dp; r.cs = h->ae_cs; r.ldcs = h->Dp;
+    PROFB("recon_head_kernel", launch_recon_head(h->bf16, r, s), (double)rows_valid * h->cfg.d_in * (4.0 + 2.0 * h->es));
+    CHK(dense_dx(h, L6, KIND_D, h->ae_dy, B, 1, h->dpre[4], ACT_RELU, h->d[4].N, relu_mask(h, 4), nullptr,
+                 ColSums{CS_SUM, h->cs_db[4], nullptr}, s));
+    CHK(disc_bwd(h, 1, 4, 0, s));
+    CHK(run_adam(h, MRGAN_NET_D, ADAM_FUSED, true, s, a->stream_mode ? 1 : 0, h->ae_loss_part, h->tiles_m * (h->Dp / 64),
+                 1.0f / ((float)rows_valid * (float)h->cfg.d_in)));
+    h->cur ^= 1;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // what the step entries ask of their arguments
 // ---------------------------------------------------------------------------------------------------
+// an autoencoder handle (MRGAN_FLAG_AUTOENCODER) serves mrgan_ae_step / mrgan_ae_encode / mrgan_ae_reconstruct and no other
+// step, evaluation or saliency entry; every other handle refuses those three (status -3)
+int refuse_ae(const mrgan_handle* h, const char* entry) {
+    if (!h->ae) return 0;
+    return fail(-3, "%s: not on an autoencoder handle (MRGAN_FLAG_AUTOENCODER): its last layer is no class layer; it trains through mrgan_ae_step and is read through mrgan_ae_encode / mrgan_ae_reconstruct", entry);
+}
+int require_ae(const mrgan_handle* h, const char* entry) {
+    if (h->ae) return 0;
+    return fail(-3, "%s: not an autoencoder handle (create it with MRGAN_FLAG_AUTOENCODER)", entry);
+}
 int check_disc_args(const mrgan_handle* h, const mrgan_disc_args* a) {
     if (!a || !a->x_lab_dev || !a->x_unl_dev || !a->labels_dev) return fail(-2, "disc_step: x_lab, x_unl and labels are required");
     if (a->ld_x_lab < h->cfg.d_in || a->ld_x_unl < h->cfg.d_in) return fail(-2, "disc_step: row pitch smaller than d_in");
@@ -869,7 +928,7 @@ struct Draw { DrawKey key; float sigma_in, sigma_hid; bool path; float alpha; co
 // current one, the plain stage instantiation).  A group handle evaluates the selected model: its activations here, its weights
 // in dense_fwd.
 int eval_forward(mrgan_handle* h, const float* x, const int32_t* idx, long ld, long r0, int rows, bool keep_masks, hipStream_t s,
-                 const Draw* draw = nullptr) {
+                 const Draw* draw = nullptr, int l_end = 5 /* dense 1 .. l_end only (mrgan_ae_encode) */) {
     const float* src = idx ? x : x + r0 * ld;
     const int32_t* ridx = idx ? idx + r0 : nullptr;
     if (draw && draw->path) {
@@ -892,7 +951,7 @@ int eval_forward(mrgan_handle* h, const float* x, const int32_t* idx, long ld, l
         }
         PROF("stage_kernel", launch_stage(h->bf16, st, s));
     }
-    for (int l = 0; l < 5; ++l) {
+    for (int l = 0; l < l_end; ++l) {
         const bool noisy = draw && l < 4 && draw->sigma_hid > 0.f;
         const NoiseSite nz = {noisy ? draw->sigma_hid : 0.f, (uint32_t)(l + 1), (uint32_t)MRGAN_ATTR_NOISE_SEG, 1, 0};
         CHK(dense_fwd(h, h->d[l], KIND_EVAL, selected(h, h->xin[l]), rows, 1, selected(h, l < 4 ? h->xin[l + 1] : h->feat), ACT_RELU,
@@ -950,6 +1009,43 @@ int eval_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, cons
                                     sizeof(float) * h->KP, sizeof(float) * h->cfg.num_classes, rows, hipMemcpyDeviceToDevice, s));
     }
     return rezero_padding(h, 5, 3, false, s);      // the chunks reach rows [0, 3S); xin[0]: all five segments, whatever n
+}
+
+// The read-only entries of an autoencoder handle, chunked like eval_rows.  through = 3: the code, the stored relu output of
+// dense 3 (the input of dense 4) -> out; through = 6: the whole forward, y -> out where given, and where mse is wanted the
+// reconstruction head without its dY over the chunk, its partials folded into ae_mse chunk after chunk.  The chunks reach what
+// eval_rows' reach, and the features: their padding rows are the X operand of the last weight gradient (dw_args).
+int ae_rows(mrgan_handle* h, const float* x, const int32_t* idx, long ld, long n, int through, float* out, long ld_out, bool mse,
+            hipStream_t s) {
+    const long cap = 3L * h->S;
+    for (long r0 = 0; r0 < n; r0 += cap) {
+        const int rows = (int)std::min(cap, n - r0);
+        const int r = eval_forward(h, x, idx, ld, r0, rows, false, s, nullptr, through == 3 ? 3 : 5);
+        if (r) return r;
+        if (through == 3) {
+            PROFB("cast_rows_kernel", launch_cast_rows(h->bf16, h->xin[3], h->d[3].Kp, rows, h->d[3].K, out + r0 * ld_out, ld_out, s),
+                  (double)rows * h->d[3].K * (4.0 + h->es));
+            continue;
+        }
+        CHK(dense_fwd(h, h->d[5], KIND_EVAL, h->feat, rows, 1, h->ae_y, ACT_LINEAR, NO_NOISE, NO_MASK, NO_SUMS, s));
+        if (out)
+            PROFB("cast_rows_kernel", launch_cast_rows(h->bf16, h->ae_y, h->Dp, rows, h->cfg.d_in, out + r0 * ld_out, ld_out, s),
+                  (double)rows * h->cfg.d_in * (4.0 + h->es));
+        if (mse) {
+            const ReconHeadArgs rh = recon_head_args(h, idx ? x : x + r0 * ld, idx ? idx + r0 : nullptr, ld, rows, rows);
+            PROFB("recon_head_kernel", launch_recon_head(h->bf16, rh, s), (double)rows * h->cfg.d_in * (4.0 + h->es));
+            PROF("fold_loss_kernel", launch_fold_loss(h->ae_loss_part, ceil_div(rows, 64) * (h->Dp / 64), h->ae_mse, r0 == 0 ? 1 : 0, s));
+        }
+    }
+    CHK(rezero_padding(h, 5, 3, false, s));
+    if (h->B < h->S) HIPCHK(hipMemsetAsync((char*)h->feat + (size_t)h->B * h->Fp * h->es, 0, (size_t)(h->S - h->B) * h->Fp * h->es, s));
+    return 0;
+}
+int check_ae_rows(const mrgan_handle* h, const char* entry, const float* x, int64_t ld, int64_t n) {
+    if (!x) return fail(-2, "%s: x is required", entry);
+    if (n < 1) return fail(-2, "%s: row count n must be positive", entry);
+    if (ld < h->cfg.d_in) return fail(-2, "%s: row pitch ld_x smaller than d_in", entry);
+    return 0;
 }
 
 // the backward half of a chunk: the per-row saliency head of `objective` (targets, or null: the row's argmax; classes_out optional)
@@ -1014,6 +1110,7 @@ int attribution_rows(mrgan_handle* h, const mrgan_attribution_args* a, hipStream
 // what mrgan_input_gradient and mrgan_attribution refuse alike, under the entry's name (a: null, or the call as an attribution)
 int check_attribution(const mrgan_handle* h, const char* entry, const mrgan_attribution_args* a) {
     if (!h) return fail(-1, "null handle");
+    if (refuse_ae(h, entry)) return -3;
     if (h->fp8) return fail(-3, "%s: not on an fp8 handle (its dX products read fp8-scaled images and would disturb the calibration); use an fp32 or a bf16 engine", entry);
     if (!a || !a->x_dev || !a->out_dev) return fail(-2, "%s: x and out are required", entry);
     if (a->n < 0) return fail(-2, "%s: negative row count n", entry);
@@ -1096,7 +1193,8 @@ extern "C" {
 
 int mrgan_disc_step(mrgan_handle* h, const mrgan_disc_args* a, int p0, int p1, float* out3, mrgan_stream stream) {
     if (!h) return fail(-1, "null handle");
-    int r = refuse_group(h, "disc_step");
+    int r = refuse_ae(h, "disc_step");
+    if (!r) r = refuse_group(h, "disc_step");
     if (!r) r = check_disc_args(h, a);
     if (r) return r;
     hipStream_t s = (hipStream_t)stream;
@@ -1109,7 +1207,8 @@ int mrgan_disc_step(mrgan_handle* h, const mrgan_disc_args* a, int p0, int p1, f
 
 int mrgan_gen_step(mrgan_handle* h, const mrgan_gen_args* a, int p0, int p1, float* out1, mrgan_stream stream) {
     if (!h) return fail(-1, "null handle");
-    int r = refuse_group(h, "gen_step");
+    int r = refuse_ae(h, "gen_step");
+    if (!r) r = refuse_group(h, "gen_step");
     if (!r) r = check_gen_args(h, a);
     if (r) return r;
     hipStream_t s = (hipStream_t)stream;
@@ -1122,7 +1221,7 @@ int mrgan_gen_step(mrgan_handle* h, const mrgan_gen_args* a, int p0, int p1, flo
 
 int mrgan_fp8_calibration(mrgan_handle* h, int kind, int action, mrgan_stream stream) {
     if (!h || kind < 0 || kind > 1) return fail(-1, "fp8_calibration: bad handle or kind");
-    if (refuse_group(h, "fp8_calibration")) return -3;
+    if (refuse_ae(h, "fp8_calibration") || refuse_group(h, "fp8_calibration")) return -3;
     hipStream_t s = (hipStream_t)stream;
     if (action == MRGAN_FP8_CAL_QUERY) return (!h->fp8 || h->fp8_cal[kind] == 1) ? 1 : 0;
     if (!h->fp8) return 0;
@@ -1146,7 +1245,7 @@ int mrgan_logmel(const float* y_dev, int64_t n_trials, int64_t n_samples, int64_
 
 int mrgan_sup_step(mrgan_handle* h, const mrgan_sup_args* a, float* out2, mrgan_stream stream) {
     if (!h || !a || !a->x_dev || !a->labels_dev) return fail(-1, "sup_step: x and labels are required");
-    if (refuse_group(h, "sup_step")) return -3;
+    if (refuse_ae(h, "sup_step") || refuse_group(h, "sup_step")) return -3;
     int r = check_sup_args(h, *a, "sup_step");
     if (r) return r;
     hipStream_t s = (hipStream_t)stream;
@@ -1157,6 +1256,7 @@ int mrgan_sup_step(mrgan_handle* h, const mrgan_sup_args* a, float* out2, mrgan_
 
 int mrgan_sup_step_group(mrgan_handle* h, const mrgan_sup_group_args* a, float* out2, mrgan_stream stream) {
     if (!h || !a || !a->x_dev || !a->labels_dev) return fail(-1, "sup_step_group: x and labels are required");
+    if (refuse_ae(h, "sup_step_group")) return -3;
     if (h->models <= 1) return fail(-3, "sup_step_group: not a group handle (mrgan_config.models = %d); a single model steps through mrgan_sup_step", (int)h->cfg.models);
     int r = check_sup_args(h, single_args(a), "sup_step_group");
     if (r) return r;
@@ -1167,9 +1267,54 @@ int mrgan_sup_step_group(mrgan_handle* h, const mrgan_sup_group_args* a, float* 
     return out2 ? read_sup_out(h, h->models, a->rows_valid, out2, s) : 0;
 }
 
+int mrgan_ae_step(mrgan_handle* h, const mrgan_ae_args* a, float* out1, mrgan_stream stream) {
+    if (!h) return fail(-1, "null handle");
+    if (require_ae(h, "ae_step")) return -3;
+    if (!a || !a->x_dev) return fail(-2, "ae_step: x is required");
+    mrgan_sup_args u;       // (the fields mean what they mean in the supervised step)
+    memset(&u, 0, sizeof u);
+    u.ld_x = a->ld_x; u.stream_mode = a->stream_mode; u.rows_valid = a->rows_valid;
+    int r = check_sup_args(h, u, "ae_step");
+    if (r) return r;
+    hipStream_t s = (hipStream_t)stream;
+    r = ae_step(h, a, s);
+    if (r) return r;
+    return out1 ? read_step_out(h, 1, 0, 1, out1, s) : 0;
+}
+
+int mrgan_ae_encode(mrgan_handle* h, const float* x, const int32_t* idx, int64_t ld, int64_t n, float* code, int64_t ld_code,
+                    mrgan_stream stream) {
+    if (!h) return fail(-1, "null handle");
+    if (require_ae(h, "ae_encode")) return -3;
+    const int r = check_ae_rows(h, "ae_encode", x, ld, n);
+    if (r) return r;
+    if (!code) return fail(-2, "ae_encode: code_dev is required");
+    if (ld_code < h->cfg.d_hidden[2]) return fail(-2, "ae_encode: row pitch ld_code smaller than d_hidden[2]");
+    return ae_rows(h, x, idx, (long)ld, (long)n, 3, code, (long)ld_code, false, (hipStream_t)stream);
+}
+
+int mrgan_ae_reconstruct(mrgan_handle* h, const float* x, const int32_t* idx, int64_t ld, int64_t n, float* out, int64_t ld_out,
+                         float* mse_host, mrgan_stream stream) {
+    if (!h) return fail(-1, "null handle");
+    if (require_ae(h, "ae_reconstruct")) return -3;
+    int r = check_ae_rows(h, "ae_reconstruct", x, ld, n);
+    if (r) return r;
+    if (!out && !mse_host) return fail(-2, "ae_reconstruct: out_dev and mse_host are both null");
+    if (out && ld_out < h->cfg.d_in) return fail(-2, "ae_reconstruct: row pitch ld_out smaller than d_in");
+    hipStream_t s = (hipStream_t)stream;
+    r = ae_rows(h, x, idx, (long)ld, (long)n, 6, out, (long)ld_out, mse_host != nullptr, s);
+    if (r || !mse_host) return r;
+    float sum = 0.f;
+    HIPCHK(hipMemcpyAsync(&sum, h->ae_mse, sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *mse_host = (float)((double)sum / ((double)n * (double)h->cfg.d_in));
+    return 0;
+}
+
 int mrgan_train_pair(mrgan_handle* h, const mrgan_disc_args* d, const mrgan_gen_args* g, mrgan_stream stream) {
     if (!h) return fail(-1, "null handle");
-    int r = refuse_group(h, "train_pair");
+    int r = refuse_ae(h, "train_pair");
+    if (!r) r = refuse_group(h, "train_pair");
     if (!r) r = check_disc_args(h, d);
     if (!r) r = check_gen_args(h, g);
     if (r) return r;
@@ -1194,7 +1339,8 @@ int mrgan_train_pair(mrgan_handle* h, const mrgan_disc_args* d, const mrgan_gen_
 
 int mrgan_disc_step_group(mrgan_handle* h, const mrgan_disc_group_args* a, float* out3, mrgan_stream stream) {
     if (!h) return fail(-1, "null handle");
-    int r = check_group_handle(h, "disc_step_group");
+    int r = refuse_ae(h, "disc_step_group");
+    if (!r) r = check_group_handle(h, "disc_step_group");
     if (!r) r = check_disc_group_args(h, a);
     if (r) return r;
     hipStream_t s = (hipStream_t)stream;
@@ -1205,7 +1351,8 @@ int mrgan_disc_step_group(mrgan_handle* h, const mrgan_disc_group_args* a, float
 
 int mrgan_gen_step_group(mrgan_handle* h, const mrgan_gen_group_args* a, float* out1, mrgan_stream stream) {
     if (!h) return fail(-1, "null handle");
-    int r = check_group_handle(h, "gen_step_group");
+    int r = refuse_ae(h, "gen_step_group");
+    if (!r) r = check_group_handle(h, "gen_step_group");
     if (!r) r = check_gen_group_args(h, a);
     if (r) return r;
     hipStream_t s = (hipStream_t)stream;
@@ -1216,7 +1363,8 @@ int mrgan_gen_step_group(mrgan_handle* h, const mrgan_gen_group_args* a, float* 
 
 int mrgan_train_pair_group(mrgan_handle* h, const mrgan_disc_group_args* d, const mrgan_gen_group_args* g, mrgan_stream stream) {
     if (!h) return fail(-1, "null handle");
-    int r = check_group_handle(h, "train_pair_group");
+    int r = refuse_ae(h, "train_pair_group");
+    if (!r) r = check_group_handle(h, "train_pair_group");
     if (!r) r = check_disc_group_args(h, d);
     if (!r) r = check_gen_group_args(h, g);
     if (r) return r;
@@ -1234,6 +1382,7 @@ int mrgan_train_pair_group(mrgan_handle* h, const mrgan_disc_group_args* d, cons
 int mrgan_eval_error(mrgan_handle* h, const float* x, const int32_t* idx, int64_t ld, const int32_t* labels, int64_t n,
                      float* err_host, mrgan_stream stream) {
     if (!h || !x || !labels || !err_host || n < 1) return fail(-1, "eval_error: bad argument");
+    if (refuse_ae(h, "eval_error")) return -3;
     if (ld < h->cfg.d_in) return fail(-2, "eval_error: row pitch smaller than d_in");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(h->err_count, 0, sizeof(int), s));
@@ -1249,6 +1398,7 @@ int mrgan_eval_error(mrgan_handle* h, const float* x, const int32_t* idx, int64_
 int mrgan_predict_logits(mrgan_handle* h, const float* x, const int32_t* idx, int64_t ld, int64_t n, float* logits,
                          mrgan_stream stream) {
     if (!h || !x || !logits || n < 1) return fail(-1, "predict_logits: bad argument");
+    if (refuse_ae(h, "predict_logits")) return -3;
     if (ld < h->cfg.d_in) return fail(-2, "predict_logits: row pitch smaller than d_in");
     return eval_rows(h, x, idx, ld, nullptr, n, logits, (hipStream_t)stream);
 }

@@ -128,10 +128,15 @@ struct mrgan_handle {
     float* logits;
     float *bn_mu, *bn_rstd, *bn_mu_all, *bn_rstd_all;
     // partial sums
-    float *cs_bn1, *cs_bn2, *cs_db[4], *cs_f, *cs_db3g, *cs_db2g, *cs_dbeta, *cs_dgamma, *db1g_part;
+    float *cs_bn1, *cs_bn2, *cs_db[5], *cs_f, *cs_db3g, *cs_db2g, *cs_dbeta, *cs_dgamma, *db1g_part;
     float *head_part, *head_red, *loss_part; int head_stride, head_groups;
     int head_nblk;                        // partial rows of head_part / loss_part behind the last loss head (set where it is launched)
     int bnb_blocks;
+    // MRGAN_FLAG_AUTOENCODER: d[5] is a full-width layer d_hidden[4] x d_in.  y = its stored output [3 S][Dp], dY [S][Dp] (rows >=
+    // batch keep the zeros of mrgan_create), the per-64-row column sums of dY [tiles_m][Dp] (the last bias gradient; cs_db[4] is
+    // that of the layer below), the loss partials [row block][column block][4] of the reconstruction head and the mse
+    // accumulator of mrgan_ae_reconstruct.  All null / zero on every other handle, whose layout they leave alone.
+    bool ae; void *ae_y, *ae_dy; float *ae_cs, *ae_loss_part, *ae_mse;
     // fp8 mode (gemm_fp8.hip): the layers' Fp8Images and their scaling slots
     bool fp8; int fp8_cal[2];
     Fp8Slot* slots; float* slot_targets; float* accum_save;

@@ -92,6 +92,16 @@ int validate(const mrgan_config& c) {
     if (c.d_in < 1 || c.batch < 1) return fail(-1, "d_in and batch must be positive");
     if (c.num_classes < 2 || c.num_classes > MRGAN_MAX_CLASSES) return fail(-1, "num_classes must be in [2,%d]", MRGAN_MAX_CLASSES);
     if (c.dtype != MRGAN_F32 && c.dtype != MRGAN_BF16 && c.dtype != MRGAN_FP8) return fail(-1, "unknown dtype");
+    if (c.flags & MRGAN_FLAG_AUTOENCODER) {
+        // an autoencoder trains through mrgan_ae_step: fp32 / bf16, one model, fused Adam, one device, no GaussianNoise
+        if (c.dtype == MRGAN_FP8) return fail(-3, "an autoencoder handle cannot be an fp8 handle: its last layer has no fp8 images");
+        if (c.models > 1) return fail(-3, "an autoencoder handle cannot be a model group (models = %d)", c.models);
+        if (c.world != 1) return fail(-3, "an autoencoder handle needs world = 1: the data-parallel step is not built");
+        if (c.flags & (MRGAN_FLAG_FLAT_GRADS | MRGAN_FLAG_SYNC_STATS | MRGAN_FLAG_GRAD_BF16))
+            return fail(-3, "an autoencoder handle cannot have MRGAN_FLAG_FLAT_GRADS, MRGAN_FLAG_SYNC_STATS or MRGAN_FLAG_GRAD_BF16: the data-parallel step is not built");
+        for (int i = 0; i < 5; ++i)
+            if (c.sigma[i] != 0.f) return fail(-1, "an autoencoder handle needs sigma[%d] = 0 (got %g): the denoising variant is not built", i, (double)c.sigma[i]);
+    }
     if (c.dtype == MRGAN_FP8 && c.num_classes > KMAX)
         return fail(-1, "the fp8 engine supports at most %d classes (num_classes = %d): its loss head packs e5m2 at the 8-class pitch only", KMAX, c.num_classes);
     if (c.world < 1 || c.rank < 0 || c.rank >= c.world) return fail(-1, "bad rank/world");
@@ -137,6 +147,7 @@ int layout_model(mrgan_handle* h, char* base, size_t* bytes_out) {
     h->sync_stats = (c.flags & MRGAN_FLAG_SYNC_STATS) != 0;
     h->gauss = (c.flags & MRGAN_FLAG_GAUSS_NOISE) ? 1 : 0;
     h->flat_grads = (c.flags & MRGAN_FLAG_FLAT_GRADS) != 0;
+    h->ae = (c.flags & MRGAN_FLAG_AUTOENCODER) != 0;
     h->B = c.batch; h->S = (int)round_up(c.batch, SEG_ALIGN); h->tiles_m = ceil_div(c.batch, 64);   // 64-row column-sum partials
     h->Bg = c.batch * c.world;
     h->stat_count = (float)(h->sync_stats ? h->Bg : h->B);
@@ -155,7 +166,8 @@ int layout_model(mrgan_handle* h, char* base, size_t* bytes_out) {
 
     // ---- tensors -----------------------------------------------------------------------------
     const int gdim[4] = {c.noise_size, c.g_hidden[0], c.g_hidden[1], c.d_in};
-    const int ddim[7] = {c.d_in, c.d_hidden[0], c.d_hidden[1], c.d_hidden[2], c.d_hidden[3], c.d_hidden[4], c.num_classes};
+    // (an autoencoder handle: the last dense is the full-width layer d_hidden[4] x d_in, stored like a hidden one)
+    const int ddim[7] = {c.d_in, c.d_hidden[0], c.d_hidden[1], c.d_hidden[2], c.d_hidden[3], c.d_hidden[4], h->ae ? c.d_in : c.num_classes};
     h->gt.assign(8, Tensor());
     h->dt.assign(12, Tensor());
     auto mk = [&](Tensor& t, int rows, int cols, int prow, int pcol, bool copies) {
@@ -178,8 +190,8 @@ int layout_model(mrgan_handle* h, char* base, size_t* bytes_out) {
     mk(h->gt[2], 1, gdim[1], 1, padded(gdim[1]), false);
     mk(h->gt[3], 1, gdim[1], 1, padded(gdim[1]), false);
     for (int l = 0; l < 6; ++l) {
-        const int K = ddim[l], N = ddim[l + 1], Kp = padded(K), Np = (l == 5) ? KP : padded(N);
-        mk(h->dt[2 * l], K, N, Kp, Np, l < 5);
+        const int K = ddim[l], N = ddim[l + 1], Kp = padded(K), Np = (l == 5 && !h->ae) ? KP : padded(N);
+        mk(h->dt[2 * l], K, N, Kp, Np, l < 5 || h->ae);
         mk(h->dt[2 * l + 1], 1, N, 1, Np, false);
         h->d[l] = Dense{K, N, Kp, Np, l < 5 ? ACT_RELU : ACT_LINEAR, &h->dt[2 * l], &h->dt[2 * l + 1], nullptr, 1, Fp8Images()};
         h->dt[2 * l].layer = &h->d[l];
@@ -265,15 +277,24 @@ int layout_model(mrgan_handle* h, char* base, size_t* bytes_out) {
     h->head_part = a.take<float>((size_t)head_cap * h->head_stride);
     h->head_red = a.take<float>((size_t)h->head_groups * h->head_stride);
     h->loss_part = a.take<float>((size_t)head_cap * 4);
+    h->cs_db[4] = nullptr; h->ae_y = h->ae_dy = nullptr; h->ae_cs = h->ae_loss_part = h->ae_mse = nullptr;
+    if (h->ae) {
+        h->ae_y = act(3 * (size_t)S, h->Dp); h->ae_dy = act(S, h->Dp);
+        h->cs_db[4] = a.take<float>((size_t)tm * h->Fp); h->ae_cs = a.take<float>((size_t)tm * h->Dp);
+        h->ae_loss_part = a.take<float>((size_t)(3 * S / 64) * (h->Dp / 64) * 4);      // (a chunk of mrgan_ae_reconstruct: 3 S rows)
+        h->ae_mse = a.take<float>(4);
+    }
 
     // ---- weight-gradient slabs ---------------------------------------------------------------------
     int tiles_d = 0, tiles_g = 0;
-    for (int l = 0; l < 5; ++l) tiles_d += dw_tiles(h->d[l]);
+    const int nl_d = h->ae ? 6 : 5;                  // discriminator layers whose weight gradient is a product of its own
+    for (int l = 0; l < nl_d; ++l) tiles_d += dw_tiles(h->d[l]);
     for (int l = 0; l < 3; ++l) tiles_g += dw_tiles(h->g[l]);
     // (256 x 128 output tiles with one 8-wave block per CU were tried for the discriminator's launch in round 3: 25 % fewer staged
     //  bytes per flop, but 54.5 us against 47.5 us with two- and three-stage rings -- 200 blocks leave a fifth of the CUs idle)
-    const int splits_d = choose_splits(tiles_d, 2 * S + B), splits_g = choose_splits(tiles_g, B);
-    for (int l = 0; l < 5; ++l) {
+    // (the autoencoder step has one segment)
+    const int splits_d = choose_splits(tiles_d, h->ae ? S : 2 * S + B), splits_g = choose_splits(tiles_g, B);
+    for (int l = 0; l < nl_d; ++l) {
         Dense& L = h->d[l];
         // fp8: one product per layer over all 3 S rows; only a layer with too few 128 x 128 output tiles to fill the chip
         // (the first layer of a wide stack) splits its reduction
@@ -287,11 +308,17 @@ int layout_model(mrgan_handle* h, char* base, size_t* bytes_out) {
     }
     // ---- fused-mode gradient sources ----------------------------------------------------------------
     auto src = [&](Tensor& t, const float* g, int nslab, long stride) { t.g = g; t.nslab = nslab; t.slab_stride = stride; };
-    for (int l = 0; l < 5; ++l) src(*h->d[l].W, h->d[l].slabs, h->d[l].splits, (long)h->d[l].Kp * h->d[l].Np);
+    for (int l = 0; l < nl_d; ++l) src(*h->d[l].W, h->d[l].slabs, h->d[l].splits, (long)h->d[l].Kp * h->d[l].Np);
     for (int l = 0; l < 4; ++l) src(*h->d[l].b, h->cs_db[l], 3 * tm, h->d[l].Np);
-    src(*h->d[4].b, h->head_red + h->Fp * KP + KP, h->head_groups, h->head_stride);
-    src(*h->d[5].W, h->head_red, h->head_groups, h->head_stride);
-    src(*h->d[5].b, h->head_red + h->Fp * KP, h->head_groups, h->head_stride);
+    if (h->ae) {
+        // the dX product through the last layer leaves the column sums behind b5, the reconstruction head those behind b6
+        src(*h->d[4].b, h->cs_db[4], tm, h->Fp);
+        src(*h->d[5].b, h->ae_cs, tm, h->Dp);
+    } else {
+        src(*h->d[4].b, h->head_red + h->Fp * KP + KP, h->head_groups, h->head_stride);
+        src(*h->d[5].W, h->head_red, h->head_groups, h->head_stride);
+        src(*h->d[5].b, h->head_red + h->Fp * KP, h->head_groups, h->head_stride);
+    }
     for (int l = 0; l < 3; ++l) src(*h->g[l].W, h->g[l].slabs, h->g[l].splits, (long)h->g[l].Kp * h->g[l].Np);
     src(*h->g[0].b, h->db1g_part, h->bnb_blocks, N1p);
     src(h->gt[2], h->cs_dgamma, tm, N1p);

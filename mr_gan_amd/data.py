@@ -42,17 +42,20 @@ def train_test_sets(X, y, trainTestSets, rs, num_classes):
     return train_test_split(X, y, test_size=200 * num_classes, stratify=y, random_state=rs)
 
 
-def prologue(sets, percentlabeled, percentunlabeled, rs, num_classes):
+def prologue(sets, percentlabeled, percentunlabeled, rs, num_classes, transform=None):
     """The data prologue the reference's three scripts share (mr_gan.py:91-107, mr_nn.py:82-93, mr_svm.py:90-102) for
     sets = [X_train, X_test, y_train, y_test]: scale, shuffle -- the one draw from rs -- and the labelled subset of
     10 * percentlabeled rows per class, with percentunlabeled also the table-6 pool
     -> (x_labeled, y_labeled, pool or None, X_train, X_test, y_test, lines); lines: what the reference prints when verbose, in
-    its order, each as a tuple of print() arguments"""
+    its order, each as a tuple of print() arguments.  transform(X_train, X_test) -> (X_train, X_test), where given, replaces the
+    scaled sets before the shuffle (others/mr_gan_autoencoder.py:125-140: the autoencoder's codes)"""
     from sklearn.utils import shuffle
     X_train, X_test, y_train, y_test = sets
     lines = [('Num of class examples in test set:', [int(np.sum(y_test == i)) for i in range(num_classes)]),
              ('X_train:', np.shape(X_train), 'y_train:', np.shape(y_train), 'X_test:', np.shape(X_test), 'y_test:', np.shape(y_test))]
     X_train, X_test = standard_scale(X_train, X_test)
+    if transform is not None:
+        X_train, X_test = transform(X_train, X_test)
     X_train, y_train = shuffle(X_train, y_train, random_state=rs)
     x_labeled, y_labeled, pool = select_labeled(X_train, y_train, int(10 * percentlabeled),
                                                 None if percentunlabeled is None else int(10 * percentunlabeled), num_classes=num_classes)

@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libmrgan_hip.so")
 F32, BF16, FP8 = 0, 1, 2
 NET_G, NET_D = 0, 1
 FLAG_SYNC_STATS, FLAG_FLAT_GRADS, FLAG_GRAPH, FLAG_GRAD_BF16, FLAG_GAUSS_NOISE = 1, 2, 4, 8, 16
+FLAG_AUTOENCODER = 32         # MRGAN_FLAG_AUTOENCODER: NET_D is a dense autoencoder (ae_step / ae_encode / ae_reconstruct)
 NOISE_MODES = ('irwin-hall', 'gaussian')
 D_GEN, D_MAIN, D_ADAM = 0, 1, 2
 G_GEN, G_FEAT, G_BWD, G_TAIL, G_ADAM = 0, 1, 2, 3, 4
@@ -35,6 +36,7 @@ EXPORTS = [
     "mrgan_select_model", "mrgan_sup_step_group",
     "mrgan_disc_step_group", "mrgan_gen_step_group", "mrgan_train_pair_group",
     "mrgan_input_gradient", "mrgan_attribution",
+    "mrgan_ae_step", "mrgan_ae_encode", "mrgan_ae_reconstruct",
 ]
 SAL_LOGIT, SAL_XENT, SAL_MSE = 0, 1, 2
 SAL_RAW, SAL_HEATMAP = 0, 1
@@ -80,6 +82,15 @@ class GenArgs(C.Structure):
 class SupArgs(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("idx", C.c_void_p), ("labels", C.c_void_p),
+        ("ld_x", C.c_int64),
+        ("stream_mode", C.c_int32), ("rows_valid", C.c_int32),
+    ]
+
+
+class AeArgs(C.Structure):
+    """mrgan_ae_args"""
+    _fields_ = [
+        ("x", C.c_void_p), ("idx", C.c_void_p),
         ("ld_x", C.c_int64),
         ("stream_mode", C.c_int32), ("rows_valid", C.c_int32),
     ]
@@ -418,6 +429,41 @@ class Engine(object):
         out = (C.c_float * 2)()
         _check(self.lib.mrgan_sup_step(self.handle, C.byref(args), out if want_outputs else None, _stream()))
         return tuple(out) if want_outputs else None
+
+    # ---- autoencoder handles (FLAG_AUTOENCODER) ----------------------------------------------------------------------
+    @staticmethod
+    def ae_args(x, idx=None, stream_mode=0, rows_valid=0):
+        a = AeArgs()
+        a.x, a.idx, a.ld_x = _ptr(x), _ptr(idx), x.stride(-2)
+        a.stream_mode, a.rows_valid = stream_mode, rows_valid
+        a._refs = (x, idx)
+        return a
+
+    def ae_step(self, args, want_outputs=True):
+        """one train_on_batch(x, x) of the autoencoder (loss 'mse', Adam) -> the loss of the batch"""
+        out = (C.c_float * 1)()
+        _check(self.lib.mrgan_ae_step(self.handle, C.byref(args), out if want_outputs else None, _stream()))
+        return out[0] if want_outputs else None
+
+    def ae_encode(self, x, idx=None, out=None):
+        """mrgan_ae_encode -> codes fp32 [n, >= d_hidden[2]] (out: a buffer to write into; its further columns are left alone)"""
+        n = x.shape[0] if idx is None else idx.numel()
+        if out is None:
+            out = torch.empty((n, self.cfg.d_hidden[2]), dtype=torch.float32, device=self.device)
+        _check(self.lib.mrgan_ae_encode(self.handle, _ptr(x), _ptr(idx), C.c_int64(x.stride(0)), C.c_int64(n), _ptr(out),
+                                        C.c_int64(out.stride(0)), _stream()))
+        return out
+
+    def ae_reconstruct(self, x, idx=None, out=None, want_out=True, want_mse=True):
+        """mrgan_ae_reconstruct -> (y fp32 [n, >= d_in] or None, mse over all n x d_in elements or None)"""
+        n = x.shape[0] if idx is None else idx.numel()
+        if out is None and want_out:
+            out = torch.empty((n, self.cfg.d_in), dtype=torch.float32, device=self.device)
+        mse = C.c_float()
+        _check(self.lib.mrgan_ae_reconstruct(self.handle, _ptr(x), _ptr(idx), C.c_int64(x.stride(0)), C.c_int64(n), _ptr(out),
+                                             C.c_int64(out.stride(0) if out is not None else 0), C.byref(mse) if want_mse else None,
+                                             _stream()))
+        return out, (mse.value if want_mse else None)
 
     # ---- model groups (cfg.models > 1): G equal-shape trainings in one launch set ----------------------------------
     @property

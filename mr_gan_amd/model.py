@@ -5,7 +5,8 @@ The reference script exposes no class -- its model lives in local variables of m
 models elsewhere in the repository (mr_nn.py:117-118, others/mr_gan_autoencoder.py:125-139).
 
 Front is what the four public classes share (MRGAN and MRGANGroup here, MRNN and MRNNGroup in mr_nn.py); gan_epochs and
-sup_epochs are the two epoch loops, each for the G >= 1 models of a handle.
+sup_epochs are the two epoch loops, each for the G >= 1 models of a handle; ae_epochs (autoencoder.py) shares the shuffled
+batches of sup_epochs.
 """
 import contextlib
 import sys
@@ -155,43 +156,80 @@ def gan_epochs(engine, dev, x_labeled, y_labeled, x_unlabeled, pools, validation
     return iterations
 
 
-def sup_epochs(engine, dev, xs, ys, rngs, epochs, verbose=0):
-    """Keras fit(batch_size, epochs, shuffle=True) of mr_nn.py:117 for the G = len(rngs) models of `engine` (G > 1: a group
-    handle): per epoch a fresh permutation per model, drawn model by model from rngs[m]; batches in order, the last one short
-    (rows_valid; its padding carries label -1); every batch is one step call for all models.  The loss and training error
-    of an epoch's last batch are read on the last epoch (verbose: on every epoch) -> [records of those epochs]"""
+def shuffled_epochs(engine, dev, xs, ys, rngs, epochs, make, step):
+    """The batches of Keras fit(batch_size, epochs, shuffle=True) for the G = len(rngs) models of `engine`, as a generator: per
+    epoch a fresh permutation per model, drawn model by model from rngs[m], fills the resident rows ([G, nb * B, D], and the
+    labels where ys is given; their padding -- zeros, label -1 -- stays), then (epoch, batches, run) is yielded: run(read)
+    launches the batches in order, the last one short (rows_valid), as step(args, want_outputs=b == read) and returns the
+    outputs of batch `read` (-1: none are read).  make(x[, labels], rows_valid=...) builds a batch's argument struct, once: every
+    epoch reuses them."""
     G, B, n = len(rngs), engine.cfg.batch, len(xs[0])
     group = engine.models > 1                                      # the one choice between a single handle's entries and a group's
     nb = (n + B - 1) // B
-    xd, yd = [dev(x) for x in xs], [dev(y, torch.int32) for y in ys]
+    xd = [dev(x) for x in xs]
+    yd = None if ys is None else [dev(y, torch.int32) for y in ys]
     device = xd[0].device
     xb = torch.zeros((G, nb * B, engine.cfg.d_in), device=device)
-    yb = torch.full((G, nb * B), -1, dtype=torch.int32, device=device)
-    rows = [(xb[m, :n], yb[m, :n]) for m in range(G)]              # what an epoch's permutation fills; the padding stays
-    xv, yv = (xb, yb) if group else (xb[0], yb[0])
-    make, step = (E.Engine.sup_group_args, engine.sup_step_group) if group else (E.Engine.sup_args, engine.sup_step)
+    yb = None if ys is None else torch.full((G, nb * B), -1, dtype=torch.int32, device=device)
+    xv = xb if group else xb[0]
+    yv = None if yb is None else (yb if group else yb[0])
     args = []                                                      # one struct per batch, reused by every epoch
 
     def first_epoch():                                             # (builds them between its launches, not ahead of the first one)
         for b in range(nb):
-            args.append(make(xv.narrow(-2, b * B, B), yv.narrow(-1, b * B, B), rows_valid=n - b * B if (b + 1) * B > n else 0))
+            cols = (xv.narrow(-2, b * B, B),) + (() if yv is None else (yv.narrow(-1, b * B, B),))
+            args.append(make(*cols, rows_valid=n - b * B if (b + 1) * B > n else 0))
             yield args[-1]
-    hist = []
     for ep in range(epochs):
-        for rng, x, y, (xr, yr) in zip(rngs, xd, yd, rows):
+        for m, rng in enumerate(rngs):
             perm = torch.from_numpy(rng.permutation(n)).to(device)
-            torch.index_select(x, 0, perm, out=xr)
-            torch.index_select(y, 0, perm, out=yr)
-        read = nb - 1 if ep == epochs - 1 or verbose else -1       # the batch whose outputs are read, if any
-        out = None
-        for b, a in enumerate(args if ep else first_epoch()):
-            out = step(a, want_outputs=b == read)
+            torch.index_select(xd[m], 0, perm, out=xb[m, :n])      # what an epoch's permutation fills; the padding stays
+            if yd is not None:
+                torch.index_select(yd[m], 0, perm, out=yb[m, :n])
+
+        def run(read, ep=ep):
+            out = None
+            for b, a in enumerate(args if ep else first_epoch()):
+                out = step(a, want_outputs=b == read)
+            return out if read == nb - 1 else None
+        yield ep, nb, run
+
+
+def sup_epochs(engine, dev, xs, ys, rngs, epochs, verbose=0):
+    """shuffled_epochs of mr_nn.py:117 for the G = len(rngs) models of `engine` (G > 1: a group handle): every batch is one
+    supervised step call for all models, the padding of the short last batch carries label -1.  The loss and training error
+    of an epoch's last batch are read on the last epoch (verbose: on every epoch) -> [records of those epochs]"""
+    group = engine.models > 1
+    make, step = (E.Engine.sup_group_args, engine.sup_step_group) if group else (E.Engine.sup_args, engine.sup_step)
+    hist = []
+    for ep, nb, run in shuffled_epochs(engine, dev, xs, ys, rngs, epochs, make, step):
+        out = run(nb - 1 if ep == epochs - 1 or verbose else -1)   # the batch whose outputs are read, if any
         if out is not None:
             loss, err = zip(*(out if group else [out]))
             hist.append(dict(epoch=ep, loss=list(loss), train_err=list(err)) if group else dict(epoch=ep, loss=loss[0], train_err=err[0]))
             if verbose:
                 print('Epoch %d: loss %s, train err %s' % (ep + 1, ' '.join('%.5f' % v for v in loss), ' '.join('%.4f' % v for v in err)))
     return hist
+
+
+def ae_epochs(engine, dev, x, rng, epochs, history, validation=None, verbose=0):
+    """shuffled_epochs of others/mr_gan_autoencoder.py:127, autoencoder.fit(X, X, batch_size, shuffle=True), appending one record
+    per epoch to `history`: loss = the mean of the batch losses weighted by their rows, as Keras reports it -- from the epoch
+    metrics accumulated on the device (their sum and the last batch's loss, one read per epoch) -- and val_loss = the mse over
+    `validation` (nan without)."""
+    n, B = len(x), engine.cfg.batch
+    xv = None if validation is None else dev(validation)
+    for ep, nb, run in shuffled_epochs(engine, dev, [x], None, [rng], epochs, E.Engine.ae_args, engine.ae_step):
+        run(-1)
+        m = engine.read_metrics(reset=True)
+        total, last = m[0], m[4]                                   # sum over the epoch's batches, the (short) last batch
+        loss = ((total - last) * B + last * (n - (nb - 1) * B)) / n
+        val = float('nan') if xv is None else engine.ae_reconstruct(xv, want_out=False)[1]
+        history.append(dict(epoch=ep + 1, loss=loss, val_loss=val))
+        if verbose:
+            print('Epoch %d/%d - loss: %.4f - val_loss: %.4f' % (ep + 1, epochs, loss, val))
+            sys.stdout.flush()
+    return history
 
 
 class Front(object):
