@@ -231,6 +231,31 @@ int32_t mrgan_logmel_frames(int64_t n_samples);
 int mrgan_logmel(const float* y_dev, int64_t n_trials, int64_t n_samples, int64_t ld_y, int32_t sr, int32_t n_mels,
                  float* out_dev, int64_t ld_out, mrgan_stream stream);
 
+/* RBF-kernel C-SVC of the SVM baseline (mr_svm.py:106: SVC(kernel='rbf', C=1)) on the device.  No handle and no state: three
+ * launches the host chains on one stream.  Rows are SORTED BY CLASS: class c owns rows class_start_host[c] ..
+ * class_start_host[c + 1] - 1 (num_classes + 1 host values, from 0 to n), and the one-vs-one pairs are numbered (0,1), (0,2), ..,
+ * (1,2), .. as libsvm and scikit-learn's decision_function_shape='ovo' number them.  2 <= num_classes <= 32, no class is empty,
+ * and the two largest classes together have at most MRGAN_SVM_MAX_PAIR rows (a larger pair is an error, never another path).
+ *   mrgan_svm_gram    out[a, b] = exp(-gamma * max(0, |A_a|^2 + |B_b|^2 - 2 A_a . B_b)) for the m rows of a_dev and the n rows
+ *                     of b_dev (d float32 features each; row pitches ld_a, ld_b, ld_out in elements).  With a_dev == b_dev the
+ *                     result is symmetric bit for bit and its diagonal is exactly 1.  Nothing outside the m x n window is written.
+ *   mrgan_svm_solve   libsvm's C-SVC solver (SMO, second-order working-set selection, no shrinking) on a precomputed n x n
+ *                     kernel matrix, one workgroup per pair; stops at max(-y G over I_up) - min(-y G over I_low) < tol or after
+ *                     max_iter updates.  coef_dev: [num_classes - 1][n] float64, alpha_t y_t in libsvm's sv_coef /
+ *                     scikit-learn's dual_coef_ row convention (a row of class c holds its coefficients against the other
+ *                     classes in class order); rho_dev: [pairs] float64; iters_dev: [pairs] int32, == max_iter where a pair
+ *                     did not converge.  Results are bit-identical from run to run.
+ *   mrgan_svm_decide  kt_dev: m x n kernel values between test rows and the training rows.  dec = sum_t coef_t K(x, x_t) - rho
+ *                     per pair (float64), vote i where dec > 0 else j, labels_dev[row] = the first class with the most votes
+ *                     (int32 class index).  dec_dev (optional): [m][pairs] float64. */
+#define MRGAN_SVM_MAX_PAIR 2048
+int mrgan_svm_gram(const float* a_dev, int64_t ld_a, int64_t m, const float* b_dev, int64_t ld_b, int64_t n, int64_t d, float gamma,
+                   float* out_dev, int64_t ld_out, mrgan_stream stream);
+int mrgan_svm_solve(const float* k_dev, int64_t ld_k, int64_t n, int32_t num_classes, const int64_t* class_start_host, double C,
+                    double tol, int32_t max_iter, double* coef_dev, double* rho_dev, int32_t* iters_dev, mrgan_stream stream);
+int mrgan_svm_decide(const float* kt_dev, int64_t ld_kt, int64_t m, int64_t n, int32_t num_classes, const int64_t* class_start_host,
+                     const double* coef_dev, const double* rho_dev, double* dec_dev, int32_t* labels_dev, mrgan_stream stream);
+
 /* one iteration of the hot loop (mr_gan.py:204-213): D step then G step */
 int mrgan_train_pair(mrgan_handle* h, const mrgan_disc_args* d, const mrgan_gen_args* g, mrgan_stream stream);
 /* For hosts that drive the phases themselves (data parallel) and know that the next mrgan_disc_step is followed by a

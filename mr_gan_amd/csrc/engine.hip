@@ -1243,6 +1243,30 @@ int mrgan_logmel(const float* y_dev, int64_t n_trials, int64_t n_samples, int64_
     return r ? fail(r, "%s", msg) : 0;
 }
 
+int mrgan_svm_gram(const float* a_dev, int64_t ld_a, int64_t m, const float* b_dev, int64_t ld_b, int64_t n, int64_t d, float gamma,
+                   float* out_dev, int64_t ld_out, mrgan_stream stream) {
+    const char* msg = "";
+    const int r = launch_svm_gram(a_dev, (long)ld_a, (long)m, b_dev, (long)ld_b, (long)n, (long)d, gamma, out_dev, (long)ld_out, 0,
+                                  (hipStream_t)stream, &msg);
+    return r ? fail(r, "%s", msg) : 0;
+}
+
+int mrgan_svm_solve(const float* k_dev, int64_t ld_k, int64_t n, int32_t num_classes, const int64_t* class_start_host, double C,
+                    double tol, int32_t max_iter, double* coef_dev, double* rho_dev, int32_t* iters_dev, mrgan_stream stream) {
+    const char* msg = "";
+    const int r = launch_svm_solve(k_dev, (long)ld_k, (long)n, num_classes, class_start_host, C, tol, max_iter, coef_dev, rho_dev,
+                                   iters_dev, (hipStream_t)stream, &msg);
+    return r ? fail(r, "%s", msg) : 0;
+}
+
+int mrgan_svm_decide(const float* kt_dev, int64_t ld_kt, int64_t m, int64_t n, int32_t num_classes, const int64_t* class_start_host,
+                     const double* coef_dev, const double* rho_dev, double* dec_dev, int32_t* labels_dev, mrgan_stream stream) {
+    const char* msg = "";
+    const int r = launch_svm_decide(kt_dev, (long)ld_kt, (long)m, (long)n, num_classes, class_start_host, coef_dev, rho_dev, dec_dev,
+                                    labels_dev, (hipStream_t)stream, &msg);
+    return r ? fail(r, "%s", msg) : 0;
+}
+
 int mrgan_sup_step(mrgan_handle* h, const mrgan_sup_args* a, float* out2, mrgan_stream stream) {
     if (!h || !a || !a->x_dev || !a->labels_dev) return fail(-1, "sup_step: x and labels are required");
     if (refuse_ae(h, "sup_step") || refuse_group(h, "sup_step")) return -3;

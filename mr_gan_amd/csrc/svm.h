@@ -1,0 +1,24 @@
+// RBF-kernel C-SVC of the SVM baseline (mr_svm.py:106) on the device (svm.hip): Gram matrix, SMO solver, one-vs-one vote.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace mrgan {
+
+constexpr int SVM_MAX_PAIR = 2048;         // rows of one one-vs-one problem (MRGAN_SVM_MAX_PAIR): two per thread of the solver's block
+constexpr int SVM_MAX_CLASSES = 32;
+constexpr int SVM_MAX_PAIRS = SVM_MAX_CLASSES * (SVM_MAX_CLASSES - 1) / 2;
+
+// first row of every class in the class-sorted row order, start[num_classes] = n (passed to the kernels by value)
+struct SvmClasses { int start[SVM_MAX_CLASSES + 1]; };
+
+// All three: 0 on success, -1 bad argument, -10 HIP failure (message in *err, static storage).
+// out[a, b] = exp(-gamma * max(0, |A_a|^2 + |B_b|^2 - 2 A_a . B_b)); tile: 0 = chosen from the shape, 64 or 128 = forced
+int launch_svm_gram(const float* a, long ld_a, long m, const float* b, long ld_b, long n, long d, float gamma, float* out, long ld_out,
+                    int tile, hipStream_t s, const char** err);
+int launch_svm_solve(const float* k, long ld_k, long n, int num_classes, const int64_t* class_start, double C, double tol, int max_iter,
+                     double* coef, double* rho, int* iters, hipStream_t s, const char** err);
+int launch_svm_decide(const float* kt, long ld_kt, long m, long n, int num_classes, const int64_t* class_start, const double* coef,
+                      const double* rho, double* dec, int* labels, hipStream_t s, const char** err);
+
+}  // namespace mrgan

@@ -1,0 +1,420 @@
+// RBF-kernel C-SVC on the device: what SVC(kernel='rbf', C=1) of the reference's SVM baseline (mr_svm.py:106) computes.
+//
+//   svm_gram_kernel    K[a, b] = exp(-gamma * max(0, |A_a|^2 + |B_b|^2 - 2 A_a . B_b)), fp32.  The dot product is the k-ordered
+//                      v_mfma_f32_32x32x2_f32 chain of gemm_f32.hip (same fragments, same k-major LDS image); the row norms are
+//                      the same chain written with fmaf over the staged tile, so with A == B the diagonal's distance is exactly
+//                      0 and K_ii exactly 1.0f, and K[a, b] == K[b, a] bit for bit (products and the norm sum commute).
+//   svm_smo_kernel     libsvm's C-SVC Solver without shrinking, one 1024-thread workgroup per one-vs-one pair: alpha and G
+//                      (fp64) stay in LDS for the whole solve, an iteration is two block reductions (working-set selection
+//                      WSS2) and two coalesced fp32 Gram rows.  No grid barrier, nothing polls memory, every loop ends at max_iter.
+//   svm_decide_kernel  per test row: the pairs' decision values (fp64 sums) and the one-vs-one vote.
+//
+// Rows are sorted by class: pair (i, j), i < j, is the two contiguous row ranges of classes i and j, y = +1 on class i.
+#include <math.h>
+
+#include "common.h"
+#include "svm.h"
+
+namespace mrgan {
+
+namespace {
+constexpr int BK = 16;
+
+template <int TS>
+__global__ __launch_bounds__(256) void svm_gram_kernel(const float* __restrict__ A, long ld_a, int M, const float* __restrict__ B, long ld_b,
+                                                       int N, int D, float gamma, float* __restrict__ out, long ld_out) {
+    constexpr int LDT = TS, MR = TS / 64, KPT = TS / 16;      // KPT: k values staged per thread
+    __shared__ __attribute__((aligned(16))) float lds[2 * BK * TS + 2 * TS];
+    float* As = lds;
+    float* Bs = lds + BK * LDT;
+    float* nrm = lds + 2 * BK * LDT;                         // [0, TS): |A_row|^2, [TS, 2 TS): |B_row|^2
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int row_blk = blockIdx.y * TS, col_blk = blockIdx.x * TS;
+
+    // staging map: thread -> (row t % TS of the tile, KPT consecutive k starting at (t / TS) * KPT)
+    const int si = t % TS, sk = (t / TS) * KPT;
+    const bool a_row_ok = (row_blk + si) < M;
+    const bool b_row_ok = (col_blk + si) < N;
+    const float* a_ptr = A + (long)(row_blk + si) * ld_a;
+    const float* b_ptr = B + (long)(col_blk + si) * ld_b;
+
+    f32x16 acc[MR][MR];
+#pragma unroll
+    for (int i = 0; i < MR; ++i)
+#pragma unroll
+        for (int j = 0; j < MR; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    float ra[KPT], rb[KPT];
+    auto load_tile = [&](int k0) {
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            const int k = k0 + sk + j;
+            ra[j] = (a_row_ok && k < D) ? a_ptr[k] : 0.f;
+            rb[j] = (b_row_ok && k < D) ? b_ptr[k] : 0.f;
+        }
+    };
+    // the norm of tile row t (A) or t - TS (B): the dot product's own chain, fmaf(v_k, v_k, .) in k order; a padded k adds 0
+    const float* nsrc = t < TS ? As + t : Bs + (t - TS);
+    float nacc = 0.f;
+
+    load_tile(0);
+    for (int k0 = 0; k0 < D; k0 += BK) {
+        __syncthreads();                 // previous tile's fragment reads done
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            As[(sk + j) * LDT + si] = ra[j];
+            Bs[(sk + j) * LDT + si] = rb[j];
+        }
+        __syncthreads();
+        if (k0 + BK < D) load_tile(k0 + BK);      // in flight under the MFMAs below
+        if (t < 2 * TS) {
+#pragma unroll
+            for (int kk = 0; kk < BK; ++kk) {
+                const float v = nsrc[kk * LDT];
+                nacc = fmaf(v, v, nacc);
+            }
+        }
+        const int lr = lane & 31, lh = lane >> 5;
+#pragma unroll
+        for (int kk = 0; kk < BK / 2; ++kk) {
+            float a[MR], b[MR];
+#pragma unroll
+            for (int mi = 0; mi < MR; ++mi) a[mi] = As[(2 * kk + lh) * LDT + (wm * MR + mi) * 32 + lr];
+#pragma unroll
+            for (int ni = 0; ni < MR; ++ni) b[ni] = Bs[(2 * kk + lh) * LDT + (wn * MR + ni) * 32 + lr];
+#pragma unroll
+            for (int mi = 0; mi < MR; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < MR; ++ni)
+                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+        }
+    }
+    if (t < 2 * TS) nrm[t] = nacc;
+    __syncthreads();
+
+    const int lr = lane & 31, lh = lane >> 5;
+#pragma unroll
+    for (int mi = 0; mi < MR; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < MR; ++ni) {
+            const int lc = (wn * MR + ni) * 32 + lr, col = col_blk + lc;
+            if (col >= N) continue;
+            const float nb = nrm[TS + lc];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int lrow = (wm * MR + mi) * 32 + acc_row(r, lh), row = row_blk + lrow;
+                if (row >= M) continue;
+                const float d2 = fmaxf(0.f, fmaf(-2.f, acc[mi][ni][r], nrm[lrow] + nb));
+                out[(long)row * ld_out + col] = expf(-gamma * d2);
+            }
+        }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// SMO
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int SMO_THREADS = 1024, SMO_WAVES = SMO_THREADS / 64, SMO_PER = SVM_MAX_PAIR / SMO_THREADS;
+constexpr double SMO_TAU = 1e-12;
+
+// pair index p -> classes (ci < cj), in the order (0,1), (0,2), .., (1,2), ..  (libsvm's, scikit-learn's 'ovo' columns)
+__device__ __forceinline__ void pair_classes(int p, int num_classes, int& ci, int& cj) {
+    ci = 0;
+    while (p >= num_classes - 1 - ci) { p -= num_classes - 1 - ci; ++ci; }
+    cj = ci + 1 + p;
+}
+
+// (value, index) candidates: larger value wins, equal values go to the higher index -- what libsvm's ascending `>=` scan keeps
+__device__ __forceinline__ void take_max(double& v, int& i, double ov, int oi) {
+    if (ov > v || (ov == v && oi > i)) { v = ov; i = oi; }
+}
+
+__global__ __launch_bounds__(SMO_THREADS) void svm_smo_kernel(const float* __restrict__ K, long ld_k, int n, int num_classes,
+                                                              const SvmClasses cls, double C, double tol, int max_iter,
+                                                              double* __restrict__ coef, double* __restrict__ rho, int* __restrict__ iters) {
+    __shared__ double s_alpha[SVM_MAX_PAIR], s_G[SVM_MAX_PAIR];
+    __shared__ float s_diag[SVM_MAX_PAIR], s_Ki[SVM_MAX_PAIR];
+    __shared__ double r1_v[SMO_WAVES], r2_v[SMO_WAVES], r2_m[SMO_WAVES];
+    __shared__ int r1_i[SMO_WAVES], r2_i[SMO_WAVES];
+    __shared__ double f_ub[SMO_WAVES], f_lb[SMO_WAVES], f_sum[SMO_WAVES];
+    __shared__ int f_cnt[SMO_WAVES];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int ci, cj;
+    pair_classes(blockIdx.x, num_classes, ci, cj);
+    const int s1 = cls.start[ci], n1 = cls.start[ci + 1] - s1, s2 = cls.start[cj], n2 = cls.start[cj + 1] - s2;
+    const int l = n1 + n2;                                   // <= SVM_MAX_PAIR (checked by the launcher)
+    auto grow = [&](int t) { return t < n1 ? s1 + t : s2 + (t - n1); };     // row of the Gram matrix behind local index t
+
+    int own[SMO_PER], gown[SMO_PER];
+    double yown[SMO_PER];
+#pragma unroll
+    for (int e = 0; e < SMO_PER; ++e) {
+        const int t = tid + e * SMO_THREADS;
+        own[e] = t;
+        gown[e] = t < l ? grow(t) : 0;
+        yown[e] = t < n1 ? 1.0 : -1.0;
+        if (t < l) {
+            s_alpha[t] = 0.0;
+            s_G[t] = -1.0;
+            s_diag[t] = K[(long)gown[e] * ld_k + gown[e]];
+        }
+    }
+    __syncthreads();
+
+    int it = 0;
+    while (it < max_iter) {
+        // ---- i = argmax over I_up of -y G ----
+        double bv = -INFINITY;
+        int bi = -1;
+#pragma unroll
+        for (int e = 0; e < SMO_PER; ++e) {
+            const int t = own[e];
+            if (t < l) {
+                const double a = s_alpha[t];
+                const bool up = yown[e] > 0 ? a < C : a > 0.0;
+                if (up) take_max(bv, bi, -yown[e] * s_G[t], t);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) take_max(bv, bi, __shfl_xor(bv, o, 64), __shfl_xor(bi, o, 64));
+        if (lane == 0) { r1_v[wave] = bv; r1_i[wave] = bi; }
+        __syncthreads();                                                           // (1)
+        bv = r1_v[0]; bi = r1_i[0];
+#pragma unroll
+        for (int w = 1; w < SMO_WAVES; ++w) take_max(bv, bi, r1_v[w], r1_i[w]);
+        const int i = bi;
+        const double Gmax = bv;
+        if (i < 0) break;                                                          // block-uniform: every thread reduced the same values
+
+        const long gi = grow(i);
+        float ki[SMO_PER];
+#pragma unroll
+        for (int e = 0; e < SMO_PER; ++e) ki[e] = own[e] < l ? K[gi * ld_k + gown[e]] : 0.f;
+        const double a_i = s_alpha[i], G_i = s_G[i], QD_i = (double)s_diag[i], y_i = i < n1 ? 1.0 : -1.0;
+
+        // ---- j = argmin over I_low, b_t > 0, of -b_t^2 / a_t;  Gmax2 = max over I_low of y G ----
+        double ov = -INFINITY, gm2 = -INFINITY;                                    // ov holds +b^2/a: the largest is libsvm's smallest
+        int oj = -1;
+#pragma unroll
+        for (int e = 0; e < SMO_PER; ++e) {
+            const int t = own[e];
+            if (t < l) {
+                s_Ki[t] = ki[e];
+                const double a = s_alpha[t];
+                const bool low = yown[e] > 0 ? a > 0.0 : a < C;
+                if (low) {
+                    const double yG = yown[e] * s_G[t];
+                    gm2 = fmax(gm2, yG);
+                    const double gd = Gmax + yG;
+                    if (gd > 0.0) {
+                        double q = QD_i + (double)s_diag[t] - 2.0 * (double)ki[e];
+                        if (!(q > 0.0)) q = SMO_TAU;
+                        take_max(ov, oj, (gd * gd) / q, t);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            take_max(ov, oj, __shfl_xor(ov, o, 64), __shfl_xor(oj, o, 64));
+            gm2 = fmax(gm2, __shfl_xor(gm2, o, 64));
+        }
+        if (lane == 0) { r2_v[wave] = ov; r2_i[wave] = oj; r2_m[wave] = gm2; }
+        __syncthreads();                                                           // (2)
+        ov = r2_v[0]; oj = r2_i[0]; gm2 = r2_m[0];
+#pragma unroll
+        for (int w = 1; w < SMO_WAVES; ++w) { take_max(ov, oj, r2_v[w], r2_i[w]); gm2 = fmax(gm2, r2_m[w]); }
+        if (Gmax + gm2 < tol || oj < 0) break;                                     // block-uniform
+        const int j = oj;
+
+        const long gj = grow(j);
+        float kj[SMO_PER];
+#pragma unroll
+        for (int e = 0; e < SMO_PER; ++e) kj[e] = own[e] < l ? K[gj * ld_k + gown[e]] : 0.f;
+        const double a_j = s_alpha[j], G_j = s_G[j], QD_j = (double)s_diag[j], y_j = j < n1 ? 1.0 : -1.0;
+
+        // ---- the two-variable update, libsvm's clipping order (every thread computes the same values) ----
+        double q = QD_i + QD_j - 2.0 * (double)s_Ki[j];
+        if (!(q > 0.0)) q = SMO_TAU;
+        double na_i = a_i, na_j = a_j;
+        if (y_i != y_j) {
+            const double delta = (-G_i - G_j) / q, diff = a_i - a_j;
+            na_i += delta; na_j += delta;
+            if (diff > 0.0) { if (na_j < 0.0) { na_j = 0.0; na_i = diff; } }
+            else { if (na_i < 0.0) { na_i = 0.0; na_j = -diff; } }
+            if (diff > 0.0) { if (na_i > C) { na_i = C; na_j = C - diff; } }
+            else { if (na_j > C) { na_j = C; na_i = C + diff; } }
+        } else {
+            const double delta = (G_i - G_j) / q, sum = a_i + a_j;
+            na_i -= delta; na_j += delta;
+            if (sum > C) { if (na_i > C) { na_i = C; na_j = sum - C; } }
+            else { if (na_j < 0.0) { na_j = 0.0; na_i = sum; } }
+            if (sum > C) { if (na_j > C) { na_j = C; na_i = sum - C; } }
+            else { if (na_i < 0.0) { na_i = 0.0; na_j = sum; } }
+        }
+        const double da_i = na_i - a_i, da_j = na_j - a_j;
+        __syncthreads();                                                           // (3) alpha, G, Ki of i and j are read everywhere
+#pragma unroll
+        for (int e = 0; e < SMO_PER; ++e) {
+            const int t = own[e];
+            if (t < l) {
+                if (t == i) s_alpha[t] = na_i;
+                if (t == j) s_alpha[t] = na_j;
+                // Q_i[t] = y_i y_t K_it is a float in libsvm as well; the products and the sum are fp64
+                s_G[t] += (double)ki[e] * (y_i * yown[e]) * da_i + (double)kj[e] * (y_j * yown[e]) * da_j;
+            }
+        }
+        ++it;
+        // the next reads of another thread's alpha / G come after barrier (1) of the next iteration
+    }
+    __syncthreads();
+
+    // ---- rho = calculate_rho: mean of y G over the free variables, else the midpoint of the bounds ----
+    double ub = INFINITY, lb = -INFINITY, sum_free = 0.0;
+    int nr_free = 0;
+#pragma unroll
+    for (int e = 0; e < SMO_PER; ++e) {
+        const int t = own[e];
+        if (t < l) {
+            const double a = s_alpha[t], yG = yown[e] * s_G[t];
+            if (a >= C) { if (yown[e] < 0) ub = fmin(ub, yG); else lb = fmax(lb, yG); }
+            else if (a <= 0.0) { if (yown[e] > 0) ub = fmin(ub, yG); else lb = fmax(lb, yG); }
+            else { ++nr_free; sum_free += yG; }
+            const double c = a * yown[e];
+            if (t < n1) coef[(long)(cj - 1) * n + gown[e]] = c;             // libsvm's sv_coef rows: class i's rows against class j
+            else coef[(long)ci * n + gown[e]] = c;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ub = fmin(ub, __shfl_xor(ub, o, 64));
+        lb = fmax(lb, __shfl_xor(lb, o, 64));
+        sum_free += __shfl_xor(sum_free, o, 64);
+        nr_free += __shfl_xor(nr_free, o, 64);
+    }
+    if (lane == 0) { f_ub[wave] = ub; f_lb[wave] = lb; f_sum[wave] = sum_free; f_cnt[wave] = nr_free; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < SMO_WAVES; ++w) {
+            ub = fmin(ub, f_ub[w]); lb = fmax(lb, f_lb[w]); sum_free += f_sum[w]; nr_free += f_cnt[w];
+        }
+        rho[blockIdx.x] = nr_free > 0 ? sum_free / nr_free : (ub + lb) / 2;
+        iters[blockIdx.x] = it;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// decision values and the vote: one block per test row, a wave per pair (round robin)
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void svm_decide_kernel(const float* __restrict__ Kt, long ld_kt, int n, int num_classes, const SvmClasses cls,
+                                                         const double* __restrict__ coef, const double* __restrict__ rho,
+                                                         double* __restrict__ dec, int* __restrict__ labels) {
+    __shared__ double s_dec[SVM_MAX_PAIRS];
+    __shared__ int s_votes[SVM_MAX_CLASSES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int pairs = num_classes * (num_classes - 1) / 2;
+    const long row = blockIdx.x;
+    const float* kr = Kt + row * ld_kt;
+    for (int p = wave; p < pairs; p += 4) {
+        int ci, cj;
+        pair_classes(p, num_classes, ci, cj);
+        const double* c1 = coef + (long)(cj - 1) * n;      // class i's rows against class j
+        const double* c2 = coef + (long)ci * n;            // class j's rows against class i
+        double s = 0.0;
+        for (int t = cls.start[ci] + lane; t < cls.start[ci + 1]; t += 64) s = fma(c1[t], (double)kr[t], s);
+        for (int t = cls.start[cj] + lane; t < cls.start[cj + 1]; t += 64) s = fma(c2[t], (double)kr[t], s);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) s_dec[p] = s - rho[p];
+    }
+    if (tid < SVM_MAX_CLASSES) s_votes[tid] = 0;
+    __syncthreads();
+    if (dec)
+        for (int p = tid; p < pairs; p += 256) dec[row * pairs + p] = s_dec[p];
+    if (tid == 0) {
+        int p = 0;
+        for (int ci = 0; ci < num_classes; ++ci)
+            for (int cj = ci + 1; cj < num_classes; ++cj, ++p) s_votes[s_dec[p] > 0.0 ? ci : cj] += 1;
+        int best = 0;
+        for (int c = 1; c < num_classes; ++c)
+            if (s_votes[c] > s_votes[best]) best = c;       // the first class with the most votes
+        labels[row] = best;
+    }
+}
+
+int fill_classes(long n, int num_classes, const int64_t* class_start, SvmClasses& cls, const char** err) {
+    if (num_classes < 2 || num_classes > SVM_MAX_CLASSES) { *err = "svm: num_classes outside [2, 32]"; return -1; }
+    if (!class_start) { *err = "svm: class_start is required"; return -1; }
+    if (n < 2 || n > (1 << 24)) { *err = "svm: n outside [2, 2^24]"; return -1; }
+    if (class_start[0] != 0 || class_start[num_classes] != n) { *err = "svm: class_start must run from 0 to n"; return -1; }
+    for (int c = 0; c < num_classes; ++c) {
+        if (class_start[c + 1] <= class_start[c]) { *err = "svm: every class needs at least one row (class_start must increase)"; return -1; }
+        cls.start[c] = (int)class_start[c];
+    }
+    cls.start[num_classes] = (int)n;
+    for (int c = num_classes + 1; c <= SVM_MAX_CLASSES; ++c) cls.start[c] = (int)n;
+    return 0;
+}
+}  // namespace
+
+int launch_svm_gram(const float* a, long ld_a, long m, const float* b, long ld_b, long n, long d, float gamma, float* out, long ld_out,
+                    int tile, hipStream_t s, const char** err) {
+    if (!a || !b || !out) { *err = "svm_gram: null buffer"; return -1; }
+    if (m < 1 || n < 1 || d < 1 || m > (1 << 21) || n > (1 << 21) || d > (1 << 24)) { *err = "svm_gram: m, n in [1, 2^21] and d in [1, 2^24]"; return -1; }
+    if (ld_a < d || ld_b < d || ld_out < n) { *err = "svm_gram: row pitch smaller than the row"; return -1; }
+    if (!(gamma > 0.f) || !isfinite(gamma)) { *err = "svm_gram: gamma must be positive and finite"; return -1; }
+    if (tile != 0 && tile != 64 && tile != 128) { *err = "svm_gram: tile must be 0, 64 or 128"; return -1; }
+    // 64x64 blocks while 128x128 ones would leave most CUs without work, as launch_gemm_f32 chooses; every output element is
+    // the same k-ordered chain in both
+    const bool small = tile ? tile == 64 : (long)ceil_div(n, 128) * ceil_div(m, 128) < 128;
+    const dim3 block(256);
+    if (small) {
+        const dim3 grid(ceil_div(n, 64), ceil_div(m, 64));
+        MRGAN_LAUNCH((svm_gram_kernel<64>), grid, block, 0, s, a, ld_a, (int)m, b, ld_b, (int)n, (int)d, gamma, out, ld_out);
+    } else {
+        const dim3 grid(ceil_div(n, 128), ceil_div(m, 128));
+        MRGAN_LAUNCH((svm_gram_kernel<128>), grid, block, 0, s, a, ld_a, (int)m, b, ld_b, (int)n, (int)d, gamma, out, ld_out);
+    }
+    if (hipGetLastError() != hipSuccess) { *err = "svm_gram: launch failed"; return -10; }
+    return 0;
+}
+
+int launch_svm_solve(const float* k, long ld_k, long n, int num_classes, const int64_t* class_start, double C, double tol, int max_iter,
+                     double* coef, double* rho, int* iters, hipStream_t s, const char** err) {
+    if (!k || !coef || !rho || !iters) { *err = "svm_solve: null buffer"; return -1; }
+    SvmClasses cls;
+    const int r = fill_classes(n, num_classes, class_start, cls, err);
+    if (r) return r;
+    if (ld_k < n) { *err = "svm_solve: row pitch smaller than the row"; return -1; }
+    if (!(C > 0.0) || !isfinite(C) || !(tol > 0.0) || !isfinite(tol) || max_iter < 1) { *err = "svm_solve: C, tol and max_iter must be positive"; return -1; }
+    // the two largest classes make the largest pair
+    int big1 = 0, big2 = 0;
+    for (int c = 0; c < num_classes; ++c) {
+        const int sz = cls.start[c + 1] - cls.start[c];
+        if (sz > big1) { big2 = big1; big1 = sz; } else if (sz > big2) big2 = sz;
+    }
+    if (big1 + big2 > SVM_MAX_PAIR) { *err = "svm_solve: a one-vs-one pair has more than MRGAN_SVM_MAX_PAIR = 2048 rows"; return -1; }
+    const int pairs = num_classes * (num_classes - 1) / 2;
+    MRGAN_LAUNCH(svm_smo_kernel, dim3(pairs), dim3(SMO_THREADS), 0, s, k, ld_k, (int)n, num_classes, cls, C, tol, max_iter, coef, rho, iters);
+    if (hipGetLastError() != hipSuccess) { *err = "svm_solve: launch failed"; return -10; }
+    return 0;
+}
+
+int launch_svm_decide(const float* kt, long ld_kt, long m, long n, int num_classes, const int64_t* class_start, const double* coef,
+                      const double* rho, double* dec, int* labels, hipStream_t s, const char** err) {
+    if (!kt || !coef || !rho || !labels) { *err = "svm_decide: null buffer"; return -1; }
+    SvmClasses cls;
+    const int r = fill_classes(n, num_classes, class_start, cls, err);
+    if (r) return r;
+    if (m < 1 || m > (1 << 24)) { *err = "svm_decide: m outside [1, 2^24]"; return -1; }
+    if (ld_kt < n) { *err = "svm_decide: row pitch smaller than the row"; return -1; }
+    MRGAN_LAUNCH(svm_decide_kernel, dim3((unsigned)m), dim3(256), 0, s, kt, ld_kt, (int)n, num_classes, cls, coef, rho, dec, labels);
+    if (hipGetLastError() != hipSuccess) { *err = "svm_decide: launch failed"; return -10; }
+    return 0;
+}
+
+}  // namespace mrgan

@@ -37,7 +37,10 @@ EXPORTS = [
     "mrgan_disc_step_group", "mrgan_gen_step_group", "mrgan_train_pair_group",
     "mrgan_input_gradient", "mrgan_attribution",
     "mrgan_ae_step", "mrgan_ae_encode", "mrgan_ae_reconstruct",
+    "mrgan_svm_gram", "mrgan_svm_solve", "mrgan_svm_decide", "mrgan_debug_svm_gram",
 ]
+SVM_MAX_PAIR = 2048           # MRGAN_SVM_MAX_PAIR: rows of one one-vs-one problem
+SVM_MAX_CLASSES = 32
 SAL_LOGIT, SAL_XENT, SAL_MSE = 0, 1, 2
 SAL_RAW, SAL_HEATMAP = 0, 1
 SAL_OBJECTIVES = {'logit': SAL_LOGIT, 'xent': SAL_XENT, 'mse': SAL_MSE}
@@ -224,6 +227,14 @@ def load_library(path=None):
     for name in EXPORTS:
         if name != "mrgan_last_error":
             getattr(lib, name).restype = C.c_int
+    # the handle-free SVM entries mix float, double and 64-bit arguments: declared, so ctypes converts plain Python numbers
+    gram = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_int64]
+    lib.mrgan_svm_gram.argtypes = gram + [C.c_void_p]
+    lib.mrgan_debug_svm_gram.argtypes = gram + [C.c_int32, C.c_void_p]
+    lib.mrgan_svm_solve.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_double, C.c_double, C.c_int32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mrgan_svm_decide.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 

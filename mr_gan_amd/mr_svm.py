@@ -1,11 +1,13 @@
 """SVM baseline of the reference on the same harness (mr_svm.py:77-116 and its --tables 2 4 loops, :119-166):
-RBF-kernel SVC (C = 1) trained on the labeled subset only, stays on scikit-learn / CPU as in the reference.
+RBF-kernel SVC (C = 1) trained on the labeled subset only.  By default on scikit-learn / CPU as in the reference;
+--backend hip fits and scores with mr_gan_amd.svm.RBFSVM (csrc/svm.hip: Gram matrix, SMO solver and vote on the GPU).
 
-    python -m mr_gan_amd.mr_svm --tables 2 4 [-v]
+    python -m mr_gan_amd.mr_svm --tables 2 4 [-v] [--backend {sklearn,hip}]
 
 Shares dataset(), the data prologue and the modality names with mr_gan_amd.mr_gan; prints the reference's lines
 (mr_svm.py prints only the averages for table 2 and one line per object for table 4)."""
 import argparse
+import functools
 import itertools
 import sys
 
@@ -13,13 +15,16 @@ import numpy as np
 
 from mr_gan_amd.data import prologue, resolve_num_classes, train_test_sets
 from mr_gan_amd.mr_gan import MODALITIES, dataset, print_lines
+from mr_gan_amd.svm import RBFSVM
 
 
 SVC_GAMMA = 'auto'
+BACKENDS = ('sklearn', 'hip')
 
 
-def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None):
-    from sklearn.svm import SVC
+def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None, backend='sklearn'):
+    if backend not in BACKENDS:
+        raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
     rs = np.random.RandomState(seed if seed is not None else np.random.randint(1 << 31))     # mr_svm.py:79 is unseeded
     num_classes = resolve_num_classes(None)
     sets = train_test_sets(X, y, trainTestSets, rs, num_classes)   # mr_svm.py:82-89
@@ -28,7 +33,11 @@ def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None
     # mr_svm.py:106 is SVC(kernel='rbf', C=1.0) under the scikit-learn of 2017 (Keras 2.0.9 era, README.md:43-48), whose default
     # kernel width was gamma='auto' = 1 / n_features.  scikit-learn >= 0.22 defaults to 'scale' (1 / (n_features * X.var())),
     # which differs on the small standardised labeled subset: pass the reference's value explicitly.
-    svm = SVC(kernel='rbf', C=1.0, gamma=SVC_GAMMA)
+    if backend == 'hip':
+        svm = RBFSVM(C=1.0, gamma=SVC_GAMMA)         # the same C and kernel width; no CPU fallback behind it
+    else:
+        from sklearn.svm import SVC
+        svm = SVC(kernel='rbf', C=1.0, gamma=SVC_GAMMA)
     svm.fit(x_labeled, y_labeled)
     testerror = 1.0 - svm.score(X_test, y_test)                    # mr_svm.py:110
     if verbose:
@@ -84,7 +93,11 @@ def main(argv=None, dataset_fn=dataset, fn=mr_svm):
     parser = argparse.ArgumentParser(description='RBF-SVM baseline for material recognition on haptic data.')
     parser.add_argument('-t', '--tables', nargs='+', help='[Required] Tables to recompute', required=True)
     parser.add_argument('-v', '--verbose', help='Verbose', action='store_true')
+    parser.add_argument('--backend', choices=BACKENDS, default='sklearn',
+                        help="'sklearn': scikit-learn on the CPU, as in the reference (default); 'hip': RBFSVM on the GPU")
     args = parser.parse_args(argv)
+    if args.backend != 'sklearn':
+        fn = functools.partial(fn, backend=args.backend)
     baseline_tables(args.tables, fn, dataset_fn, args.verbose)
 
 

@@ -1,0 +1,170 @@
+"""RBF-kernel C-SVC on the GPU: the SVM baseline of the reference (mr_svm.py:106, SVC(kernel='rbf', C=1.0)) without scikit-learn.
+
+    clf = RBFSVM(C=1.0, gamma='auto').fit(x_labeled, y_labeled); err = 1.0 - clf.score(X_test, y_test)
+
+Three launches of csrc/svm.hip behind include/mrgan_abi.h: mrgan_svm_gram (fp32 Gram matrix on the matrix cores),
+mrgan_svm_solve (libsvm's SMO, one workgroup per one-vs-one pair, fp64 state on chip) and mrgan_svm_decide (decision values
+and the vote).  There is no CPU path: without the library or a GPU every entry raises.  The numpy restatement the tests
+compare against lives in tests/svm_ref.py.
+
+Conventions are libsvm's: pairs (i, j), i < j, in the order of scikit-learn's decision_function_shape='ovo'; a positive
+decision value votes for classes_[i]; intercept_ = -rho.  Two classes give ONE column with that same sign (scikit-learn flips
+the sign of its binary decision_function; this class does not).
+Out of scope: shrinking, probability estimates, kernels other than RBF."""
+import ctypes as C
+import warnings
+
+import numpy as np
+import torch
+
+from mr_gan_amd import engine as E
+
+
+class SVMConvergenceWarning(UserWarning):
+    """a one-vs-one problem stopped at max_iter (the role of sklearn.exceptions.ConvergenceWarning)"""
+
+
+def class_sort(y):
+    """labels -> (classes, order, class_start): classes = sorted distinct labels; order = the STABLE permutation that sorts the
+    rows by class (row order[k] of the caller is row k on the device); class_start[c] = first sorted row of class c, [-1] = n"""
+    y = np.asarray(y)
+    if y.ndim != 1 or y.shape[0] == 0:
+        raise ValueError("y must be a non-empty vector of labels, got shape %s" % (y.shape,))
+    classes, codes = np.unique(y, return_inverse=True)
+    order = np.argsort(codes, kind='stable')
+    class_start = np.concatenate([[0], np.cumsum(np.bincount(codes, minlength=len(classes)))]).astype(np.int64)
+    return classes, order, class_start
+
+
+def unsort_coef(coef_sorted, order):
+    """[(K-1), n] coefficients in device (class-sorted) row order -> the caller's row order"""
+    out = np.empty_like(coef_sorted)
+    out[:, order] = coef_sorted
+    return out
+
+
+def _finite_matrix(X, name, d=None):
+    X = np.asarray(X)
+    if X.ndim != 2 or X.shape[0] == 0 or X.shape[1] == 0:
+        raise ValueError("%s must be a non-empty matrix [rows, features], got shape %s" % (name, X.shape))
+    if d is not None and X.shape[1] != d:
+        raise ValueError("%s has %d features, the model was fitted on %d" % (name, X.shape[1], d))
+    X32 = np.ascontiguousarray(X, dtype=np.float32)
+    if not np.isfinite(X32).all():
+        raise ValueError("%s holds non-finite values (or values beyond float32)" % name)
+    return X32
+
+
+class RBFSVM:
+    def __init__(self, C=1.0, gamma='auto', tol=1e-3, max_iter=10_000_000, device='cuda:0'):
+        if not (isinstance(gamma, str) and gamma == 'auto') and not (np.isreal(gamma) and np.isfinite(gamma) and gamma > 0):
+            raise ValueError("gamma must be 'auto' (1 / n_features, the reference's kernel width) or a positive number, got %r" % (gamma,))
+        if not (np.isfinite(C) and C > 0 and np.isfinite(tol) and tol > 0):
+            raise ValueError("C and tol must be positive, got C=%r tol=%r" % (C, tol))
+        if int(max_iter) != max_iter or not 1 <= max_iter < 2 ** 31:
+            raise ValueError("max_iter must be an integer in [1, 2^31), got %r" % (max_iter,))
+        self.C, self.gamma, self.tol, self.max_iter, self.device = float(C), gamma, float(tol), int(max_iter), torch.device(device)
+        self.classes_ = None
+        self.times_ = {}                 # seconds of the last fit / predict per stage, filled only while time_stages is set
+        self.time_stages = False
+
+    # ---- device plumbing ----
+    def _call(self, name, *args):
+        lib = E.load_library()
+        with torch.cuda.device(self.device):
+            rc = getattr(lib, name)(*args, torch.cuda.current_stream(self.device).cuda_stream)
+        if rc != 0:
+            raise E.MrganError("%s failed (%d): %s" % (name, rc, lib.mrgan_last_error().decode()))
+
+    def _timed(self, key, fn):
+        if not self.time_stages:
+            return fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(torch.cuda.current_stream(self.device))
+        out = fn()
+        b.record(torch.cuda.current_stream(self.device))
+        b.synchronize()
+        self.times_[key] = self.times_.get(key, 0.0) + a.elapsed_time(b) * 1e-3
+        return out
+
+    def _require_gpu(self):
+        E.load_library()
+        if not torch.cuda.is_available():
+            raise RuntimeError("RBFSVM runs on the GPU only (mrgan_svm_*); no HIP device is visible and there is no CPU fallback")
+
+    def _gram(self, a, b):
+        out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=self.device)
+        self._call("mrgan_svm_gram", a.data_ptr(), a.stride(0), a.shape[0], b.data_ptr(), b.stride(0), b.shape[0], a.shape[1],
+                   self._gamma, out.data_ptr(), out.stride(0))
+        return out
+
+    # ---- the estimator ----
+    def fit(self, X, y):
+        X32 = _finite_matrix(X, "X")
+        classes, order, class_start = class_sort(y)
+        if len(y) != X32.shape[0]:
+            raise ValueError("X has %d rows, y has %d labels" % (X32.shape[0], len(y)))
+        K = len(classes)
+        if not 2 <= K <= E.SVM_MAX_CLASSES:
+            raise ValueError("RBFSVM needs 2 to %d classes, got %d" % (E.SVM_MAX_CLASSES, K))
+        sizes = np.sort(np.diff(class_start))
+        if sizes[-1] + sizes[-2] > E.SVM_MAX_PAIR:
+            raise ValueError("the two largest classes have %d rows together; one one-vs-one problem holds at most %d "
+                             "(MRGAN_SVM_MAX_PAIR)" % (sizes[-1] + sizes[-2], E.SVM_MAX_PAIR))
+        self._require_gpu()
+        n, d = X32.shape
+        self._gamma = 1.0 / d if isinstance(self.gamma, str) else float(self.gamma)
+        self.times_ = {}
+        self._cs = (C.c_int64 * (K + 1))(*[int(v) for v in class_start])
+        self._x = torch.from_numpy(X32[order]).to(self.device)
+        self._coef = torch.empty((K - 1, n), dtype=torch.float64, device=self.device)
+        self._rho = torch.empty(K * (K - 1) // 2, dtype=torch.float64, device=self.device)
+        iters = torch.empty(K * (K - 1) // 2, dtype=torch.int32, device=self.device)
+        gram = self._timed('gram', lambda: self._gram(self._x, self._x))
+        self._timed('solve', lambda: self._call("mrgan_svm_solve", gram.data_ptr(), gram.stride(0), n, K, self._cs, self.C, self.tol,
+                                                self.max_iter, self._coef.data_ptr(), self._rho.data_ptr(), iters.data_ptr()))
+        self.n_iter_ = iters.cpu().numpy()
+        del gram
+        self.classes_, self._order, self.n_features_in_ = classes, order, d
+        self.dual_coef_dense_ = unsort_coef(self._coef.cpu().numpy(), order)
+        self.intercept_ = -self._rho.cpu().numpy()
+        if (self.n_iter_ >= self.max_iter).any():
+            warnings.warn("RBFSVM: %d of %d one-vs-one problems stopped at max_iter = %d before reaching tol = %g"
+                          % (int((self.n_iter_ >= self.max_iter).sum()), len(self.n_iter_), self.max_iter, self.tol),
+                          SVMConvergenceWarning, stacklevel=2)
+        return self
+
+    def _decide(self, X, chunk, want_dec):
+        if self.classes_ is None:
+            raise RuntimeError("RBFSVM: fit() first")
+        X32 = _finite_matrix(X, "X", self.n_features_in_)
+        if chunk is None:
+            chunk = 4096
+        if int(chunk) != chunk or chunk < 1:
+            raise ValueError("chunk must be a positive integer, got %r" % (chunk,))
+        self._require_gpu()
+        m, K, n = X32.shape[0], len(self.classes_), self._x.shape[0]
+        pairs = K * (K - 1) // 2
+        labels = torch.empty(m, dtype=torch.int32, device=self.device)
+        dec = torch.empty((m, pairs), dtype=torch.float64, device=self.device) if want_dec else None
+
+        def run():
+            # the cross-Gram buffer holds one chunk of rows; every row's values depend on that row alone
+            for r0 in range(0, m, int(chunk)):
+                xt = torch.from_numpy(X32[r0:r0 + int(chunk)]).to(self.device)
+                kt = self._gram(xt, self._x)
+                self._call("mrgan_svm_decide", kt.data_ptr(), kt.stride(0), xt.shape[0], n, K, self._cs, self._coef.data_ptr(),
+                           self._rho.data_ptr(), dec[r0:].data_ptr() if want_dec else None, labels[r0:].data_ptr())
+        self._timed('predict', run)
+        return labels.cpu().numpy(), (dec.cpu().numpy() if want_dec else None)
+
+    def decision_function(self, X, chunk=None):
+        """[rows, K (K - 1) / 2] one-vs-one decision values, columns in scikit-learn's 'ovo' order"""
+        return self._decide(X, chunk, True)[1]
+
+    def predict(self, X, chunk=None):
+        """labels of the rows of X, worked in chunks of `chunk` rows (default 4096); chunk edges change no value"""
+        return self.classes_[self._decide(X, chunk, False)[0]]
+
+    def score(self, X, y, chunk=None):
+        return float(np.mean(self.predict(X, chunk) == np.asarray(y)))

@@ -1,0 +1,94 @@
+"""Seconds per fit and per score of the SVM baseline at the surrogate's shape -- synthetic_mreo(): d = 1200, 7200 rows, 6000 of
+them the training fold, 1200 the test fold -- with 60, 960 and 6000 labeled rows (1 %, 16 % and 100 % of table 2), on the GPU
+through mr_gan_amd.svm.RBFSVM and on this machine's CPU through scikit-learn's SVC (libsvm, one thread), side by side.
+
+The RBFSVM time is split into its three stages with device events around each (gram / solve inside fit, predict = the chunked
+cross-Gram + decide launches of score, host-to-device copies of the chunks included); fit and score are also timed as a whole with
+the host clock around calls that end in a device-to-host copy (they include the host sort, the upload and the download).  Every
+size is warmed up once, then repeated; the medians are reported, with the per-pair SMO iteration counts of both sides and the
+test error of both.
+
+    python scripts/svm_bench.py [--labeled 60 960 6000] [--repeats 5] [--sklearn-repeats 3]
+Prints one JSON line per size."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from mr_gan_amd import RBFSVM, synthetic_mreo  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--labeled", type=int, nargs="+", default=[60, 960, 6000])
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--sklearn-repeats", type=int, default=3, help="repeats of the CPU side (1 at 6000 rows: one fit is tens of seconds)")
+    ap.add_argument("--d", type=int, default=1200)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("svm_bench needs a GPU: nothing is measured without one")
+    from sklearn import preprocessing
+    from sklearn.svm import SVC
+    X, y, _ = synthetic_mreo(d=args.d)
+    tr = np.arange(len(y)) % 6 != 0
+    sc = preprocessing.StandardScaler()
+    a, xt = sc.fit_transform(X[tr]), sc.transform(X[~tr])
+    ya, yt = y[tr], y[~tr]
+    for n in args.labeled:
+        per = n // 6
+        xl = np.concatenate([a[ya == c][:per] for c in range(6)])
+        yl = np.repeat(np.arange(6), per)
+        print(json.dumps(measure(args, SVC, xl, yl, xt, yt)))
+        sys.stdout.flush()
+
+
+def measure(args, SVC, xl, yl, xt, yt):
+    n, d = xl.shape
+    clf = RBFSVM(C=1.0, gamma='auto')
+    clf.fit(xl, yl).score(xt, yt)                       # warm-up: code objects, allocator
+    fit_s, score_s, stages = [], [], dict(gram=[], solve=[], predict=[])
+    for rep in range(args.repeats):
+        clf.time_stages = False
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        clf.fit(xl, yl)
+        t1 = time.perf_counter()
+        acc = clf.score(xt, yt)
+        t2 = time.perf_counter()
+        fit_s.append(t1 - t0)
+        score_s.append(t2 - t1)
+        clf.time_stages = True                          # a pass of its own: the events synchronise between the stages
+        clf.fit(xl, yl)
+        clf.score(xt, yt)
+        for k in stages:
+            stages[k].append(clf.times_[k])
+    reps = 1 if n > 2000 else args.sklearn_repeats
+    sk_fit, sk_score = [], []
+    for rep in range(reps):
+        svc = SVC(kernel='rbf', C=1.0, gamma='auto')
+        t0 = time.perf_counter()
+        svc.fit(xl, yl)
+        t1 = time.perf_counter()
+        sk_acc = svc.score(xt, yt)
+        t2 = time.perf_counter()
+        sk_fit.append(t1 - t0)
+        sk_score.append(t2 - t1)
+    med = lambda v: round(float(np.median(v)), 6)
+    return dict(labeled=n, d=d, test_rows=len(yt), repeats=args.repeats, sklearn_repeats=reps,
+                hip_fit_s=med(fit_s), hip_score_s=med(score_s), hip_fit_all=[round(v, 6) for v in fit_s],
+                hip_gram_s=med(stages['gram']), hip_solve_s=med(stages['solve']), hip_predict_s=med(stages['predict']),
+                sklearn_fit_s=med(sk_fit), sklearn_score_s=med(sk_score),
+                fit_ratio_sklearn_over_hip=round(float(np.median(sk_fit) / np.median(fit_s)), 2),
+                score_ratio_sklearn_over_hip=round(float(np.median(sk_score) / np.median(score_s)), 2),
+                hip_iterations=clf.n_iter_.tolist(), sklearn_iterations=np.asarray(svc.n_iter_).tolist(),
+                hip_test_error=round(1.0 - acc, 6), sklearn_test_error=round(1.0 - sk_acc, 6),
+                gram_gflop=round(2e-9 * n * n * d, 2))
+
+
+if __name__ == "__main__":
+    main()
