@@ -256,6 +256,35 @@ int mrgan_svm_solve(const float* k_dev, int64_t ld_k, int64_t n, int32_t num_cla
 int mrgan_svm_decide(const float* kt_dev, int64_t ld_kt, int64_t m, int64_t n, int32_t num_classes, const int64_t* class_start_host,
                      const double* coef_dev, const double* rho_dev, double* dec_dev, int32_t* labels_dev, mrgan_stream stream);
 
+/* The same three entries for a GROUP of 1 .. MRGAN_SVM_MAX_GROUP independent problems (the folds of a table cell) in ONE launch
+ * each.  The problems are ragged -- every item has its own row counts, class sizes, pitches and buffers -- and share d, gamma,
+ * num_classes, C, tol and max_iter.  items_host is a host array of `count` descriptors, read during the call only; the calls
+ * allocate nothing, do not synchronise and keep no state.  Every item gets exactly the checks of its single entry, before any
+ * launch; a message about an item ends in "(item i)".  Each item's outputs are bit-identical to the single entry called on
+ * that item.  The items of one call must not overlap in what they write. */
+#define MRGAN_SVM_MAX_GROUP 16
+typedef struct {
+    const float* a_dev; int64_t ld_a, m;
+    const float* b_dev; int64_t ld_b, n;
+    float* out_dev; int64_t ld_out;
+} mrgan_svm_gram_item;
+typedef struct {
+    const float* k_dev; int64_t ld_k, n;
+    const int64_t* class_start_host;      /* num_classes + 1 host values */
+    double* coef_dev; double* rho_dev; int32_t* iters_dev;
+} mrgan_svm_solve_item;
+typedef struct {
+    const float* kt_dev; int64_t ld_kt, m, n;
+    const int64_t* class_start_host;
+    const double* coef_dev; const double* rho_dev;
+    double* dec_dev;                      /* optional */
+    int32_t* labels_dev;
+} mrgan_svm_decide_item;
+int mrgan_svm_gram_group(const mrgan_svm_gram_item* items_host, int32_t count, int64_t d, float gamma, mrgan_stream stream);
+int mrgan_svm_solve_group(const mrgan_svm_solve_item* items_host, int32_t count, int32_t num_classes, double C, double tol,
+                          int32_t max_iter, mrgan_stream stream);
+int mrgan_svm_decide_group(const mrgan_svm_decide_item* items_host, int32_t count, int32_t num_classes, mrgan_stream stream);
+
 /* one iteration of the hot loop (mr_gan.py:204-213): D step then G step */
 int mrgan_train_pair(mrgan_handle* h, const mrgan_disc_args* d, const mrgan_gen_args* g, mrgan_stream stream);
 /* For hosts that drive the phases themselves (data parallel) and know that the next mrgan_disc_step is followed by a

@@ -1267,6 +1267,28 @@ int mrgan_svm_decide(const float* kt_dev, int64_t ld_kt, int64_t m, int64_t n, i
     return r ? fail(r, "%s", msg) : 0;
 }
 
+int mrgan_svm_gram_group(const mrgan_svm_gram_item* items_host, int32_t count, int64_t d, float gamma, mrgan_stream stream) {
+    const char* msg = "";
+    int item = -1;
+    const int r = launch_svm_gram_group(items_host, count, (long)d, gamma, 0, (hipStream_t)stream, &msg, &item);
+    return r ? svm_group_fail(r, msg, item) : 0;
+}
+
+int mrgan_svm_solve_group(const mrgan_svm_solve_item* items_host, int32_t count, int32_t num_classes, double C, double tol,
+                          int32_t max_iter, mrgan_stream stream) {
+    const char* msg = "";
+    int item = -1;
+    const int r = launch_svm_solve_group(items_host, count, num_classes, C, tol, max_iter, (hipStream_t)stream, &msg, &item);
+    return r ? svm_group_fail(r, msg, item) : 0;
+}
+
+int mrgan_svm_decide_group(const mrgan_svm_decide_item* items_host, int32_t count, int32_t num_classes, mrgan_stream stream) {
+    const char* msg = "";
+    int item = -1;
+    const int r = launch_svm_decide_group(items_host, count, num_classes, (hipStream_t)stream, &msg, &item);
+    return r ? svm_group_fail(r, msg, item) : 0;
+}
+
 int mrgan_sup_step(mrgan_handle* h, const mrgan_sup_args* a, float* out2, mrgan_stream stream) {
     if (!h || !a || !a->x_dev || !a->labels_dev) return fail(-1, "sup_step: x and labels are required");
     if (refuse_ae(h, "sup_step") || refuse_group(h, "sup_step")) return -3;

@@ -691,4 +691,11 @@ int mrgan_debug_svm_gram(const float* a_dev, int64_t ld_a, int64_t m, const floa
     return r ? fail(r, "%s", msg) : 0;
 }
 
+int mrgan_debug_svm_gram_group(const mrgan_svm_gram_item* items_host, int32_t count, int64_t d, float gamma, int32_t tile, mrgan_stream stream) {
+    const char* msg = "";
+    int item = -1;
+    const int r = launch_svm_gram_group(items_host, count, (long)d, gamma, tile, (hipStream_t)stream, &msg, &item);
+    return r ? svm_group_fail(r, msg, item) : 0;
+}
+
 }  // extern "C"

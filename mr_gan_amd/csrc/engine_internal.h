@@ -23,6 +23,10 @@
 namespace mrgan {
 
 int fail(int code, const char* fmt, ...);      // records the message behind mrgan_last_error (per thread), returns code
+// a grouped SVM launcher's message, naming the item it is about (item < 0: about the group itself)
+inline int svm_group_fail(int code, const char* msg, int item) {
+    return item < 0 ? fail(code, "%s", msg) : fail(code, "%s (item %d)", msg, item);
+}
 #define HIPCHK(x)                                                                               \
     do {                                                                                        \
         hipError_t e_ = (x);                                                                    \

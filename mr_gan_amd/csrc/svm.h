@@ -3,8 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/mrgan_abi.h"
+
 namespace mrgan {
 
+constexpr int SVM_MAX_GROUP = MRGAN_SVM_MAX_GROUP;     // problems of one grouped launch
 constexpr int SVM_MAX_PAIR = 2048;         // rows of one one-vs-one problem (MRGAN_SVM_MAX_PAIR): two per thread of the solver's block
 constexpr int SVM_MAX_CLASSES = 32;
 constexpr int SVM_MAX_PAIRS = SVM_MAX_CLASSES * (SVM_MAX_CLASSES - 1) / 2;
@@ -20,5 +23,14 @@ int launch_svm_solve(const float* k, long ld_k, long n, int num_classes, const i
                      double* coef, double* rho, int* iters, hipStream_t s, const char** err);
 int launch_svm_decide(const float* kt, long ld_kt, long m, long n, int num_classes, const int64_t* class_start, const double* coef,
                       const double* rho, double* dec, int* labels, hipStream_t s, const char** err);
+
+// The same three for up to SVM_MAX_GROUP ragged problems in one launch each (items: host arrays of the ABI's descriptors,
+// copied into the kernel arguments).  Every item gets its single entry's checks before any launch; *bad_item = the item a
+// message is about, -1 where it is about the group.  Each item's outputs are the single launch's bit for bit.
+int launch_svm_gram_group(const mrgan_svm_gram_item* items, int count, long d, float gamma, int tile, hipStream_t s, const char** err,
+                          int* bad_item);
+int launch_svm_solve_group(const mrgan_svm_solve_item* items, int count, int num_classes, double C, double tol, int max_iter, hipStream_t s,
+                           const char** err, int* bad_item);
+int launch_svm_decide_group(const mrgan_svm_decide_item* items, int count, int num_classes, hipStream_t s, const char** err, int* bad_item);
 
 }  // namespace mrgan

@@ -9,6 +9,9 @@
 //                      WSS2) and two coalesced fp32 Gram rows.  No grid barrier, nothing polls memory, every loop ends at max_iter.
 //   svm_decide_kernel  per test row: the pairs' decision values (fp64 sums) and the one-vs-one vote.
 //
+// Each has a grouped twin (svm_*_group_kernel) for up to SVM_MAX_GROUP ragged problems in one launch: the same __device__ body
+// (gram_tile, smo_pair, decide_row), a block finding its problem from blockIdx through the descriptors in the kernel arguments.
+//
 // Rows are sorted by class: pair (i, j), i < j, is the two contiguous row ranges of classes i and j, y = +1 on class i.
 #include <math.h>
 
@@ -20,9 +23,10 @@ namespace mrgan {
 namespace {
 constexpr int BK = 16;
 
+// one TS x TS tile of the window, rows from row_blk and columns from col_blk: the body of the single and of the grouped kernel
 template <int TS>
-__global__ __launch_bounds__(256) void svm_gram_kernel(const float* __restrict__ A, long ld_a, int M, const float* __restrict__ B, long ld_b,
-                                                       int N, int D, float gamma, float* __restrict__ out, long ld_out) {
+__device__ __forceinline__ void gram_tile(const float* __restrict__ A, long ld_a, int M, const float* __restrict__ B, long ld_b, int N, int D,
+                                          float gamma, float* __restrict__ out, long ld_out, int row_blk, int col_blk) {
     constexpr int LDT = TS, MR = TS / 64, KPT = TS / 16;      // KPT: k values staged per thread
     __shared__ __attribute__((aligned(16))) float lds[2 * BK * TS + 2 * TS];
     float* As = lds;
@@ -31,7 +35,6 @@ __global__ __launch_bounds__(256) void svm_gram_kernel(const float* __restrict__
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int row_blk = blockIdx.y * TS, col_blk = blockIdx.x * TS;
 
     // staging map: thread -> (row t % TS of the tile, KPT consecutive k starting at (t / TS) * KPT)
     const int si = t % TS, sk = (t / TS) * KPT;
@@ -114,6 +117,33 @@ __global__ __launch_bounds__(256) void svm_gram_kernel(const float* __restrict__
         }
 }
 
+template <int TS>
+__global__ __launch_bounds__(256) void svm_gram_kernel(const float* __restrict__ A, long ld_a, int M, const float* __restrict__ B, long ld_b,
+                                                       int N, int D, float gamma, float* __restrict__ out, long ld_out) {
+    gram_tile<TS>(A, ld_a, M, B, ld_b, N, D, gamma, out, ld_out, blockIdx.y * TS, blockIdx.x * TS);
+}
+
+// The descriptors of a group reach the kernels BY VALUE in the kernel arguments (no device table: the entries neither
+// allocate nor copy).  A block indexes them with blockIdx alone, so the item's fields are scalar loads from the
+// argument segment into SGPRs.  The HIP programming guide gives 4 KB as the size of a kernel's arguments.
+constexpr int KERNARG_LIMIT = 4096;
+
+struct GramItem { const float* a; const float* b; float* out; long ld_a, ld_b, ld_out; int m, n; };
+// the grid is the concatenation of the items' tile lists: item i owns blocks tile_start[i] .. tile_start[i + 1] - 1, row-major
+// over its tiles (tiles_x[i] per tile row), as blockIdx.x / .y order them in the single launch
+struct GramGroup { GramItem item[SVM_MAX_GROUP]; int tile_start[SVM_MAX_GROUP + 1]; int tiles_x[SVM_MAX_GROUP]; };
+static_assert(sizeof(GramGroup) + 16 <= KERNARG_LIMIT, "svm_gram_group_kernel: descriptors beyond the kernel argument limit");
+
+template <int TS>
+__global__ __launch_bounds__(256) void svm_gram_group_kernel(const GramGroup g, int count, int D, float gamma) {
+    const int bid = blockIdx.x;
+    int it = 0;
+    while (it + 1 < count && bid >= g.tile_start[it + 1]) ++it;       // wave-uniform: blockIdx and arguments only
+    const GramItem& d = g.item[it];
+    const int local = bid - g.tile_start[it], tx = g.tiles_x[it], ty = local / tx;
+    gram_tile<TS>(d.a, d.ld_a, d.m, d.b, d.ld_b, d.n, D, gamma, d.out, d.ld_out, ty * TS, (local - ty * tx) * TS);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // SMO
 // ---------------------------------------------------------------------------------------------------------------------
@@ -132,9 +162,11 @@ __device__ __forceinline__ void take_max(double& v, int& i, double ov, int oi) {
     if (ov > v || (ov == v && oi > i)) { v = ov; i = oi; }
 }
 
-__global__ __launch_bounds__(SMO_THREADS) void svm_smo_kernel(const float* __restrict__ K, long ld_k, int n, int num_classes,
-                                                              const SvmClasses cls, double C, double tol, int max_iter,
-                                                              double* __restrict__ coef, double* __restrict__ rho, int* __restrict__ iters) {
+// The whole solve of pair `pair` = classes (ci, cj) of one problem by one workgroup: the body of the single and of the grouped
+// kernel (one copy of the solver).  s1, n1 / s2, n2: first row and size of the two classes; rho and iters are the problem's.
+__device__ __forceinline__ void smo_pair(const float* __restrict__ K, long ld_k, int n, int pair, int ci, int cj, int s1, int n1, int s2, int n2,
+                                         double C, double tol, int max_iter, double* __restrict__ coef, double* __restrict__ rho,
+                                         int* __restrict__ iters) {
     __shared__ double s_alpha[SVM_MAX_PAIR], s_G[SVM_MAX_PAIR];
     __shared__ float s_diag[SVM_MAX_PAIR], s_Ki[SVM_MAX_PAIR];
     __shared__ double r1_v[SMO_WAVES], r2_v[SMO_WAVES], r2_m[SMO_WAVES];
@@ -143,9 +175,6 @@ __global__ __launch_bounds__(SMO_THREADS) void svm_smo_kernel(const float* __res
     __shared__ int f_cnt[SMO_WAVES];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int ci, cj;
-    pair_classes(blockIdx.x, num_classes, ci, cj);
-    const int s1 = cls.start[ci], n1 = cls.start[ci + 1] - s1, s2 = cls.start[cj], n2 = cls.start[cj + 1] - s2;
     const int l = n1 + n2;                                   // <= SVM_MAX_PAIR (checked by the launcher)
     auto grow = [&](int t) { return t < n1 ? s1 + t : s2 + (t - n1); };     // row of the Gram matrix behind local index t
 
@@ -302,22 +331,45 @@ __global__ __launch_bounds__(SMO_THREADS) void svm_smo_kernel(const float* __res
         for (int w = 1; w < SMO_WAVES; ++w) {
             ub = fmin(ub, f_ub[w]); lb = fmax(lb, f_lb[w]); sum_free += f_sum[w]; nr_free += f_cnt[w];
         }
-        rho[blockIdx.x] = nr_free > 0 ? sum_free / nr_free : (ub + lb) / 2;
-        iters[blockIdx.x] = it;
+        rho[pair] = nr_free > 0 ? sum_free / nr_free : (ub + lb) / 2;
+        iters[pair] = it;
     }
+}
+
+__global__ __launch_bounds__(SMO_THREADS) void svm_smo_kernel(const float* __restrict__ K, long ld_k, int n, int num_classes,
+                                                              const SvmClasses cls, double C, double tol, int max_iter,
+                                                              double* __restrict__ coef, double* __restrict__ rho, int* __restrict__ iters) {
+    int ci, cj;
+    pair_classes(blockIdx.x, num_classes, ci, cj);
+    const int s1 = cls.start[ci], n1 = cls.start[ci + 1] - s1, s2 = cls.start[cj], n2 = cls.start[cj + 1] - s2;
+    smo_pair(K, ld_k, n, blockIdx.x, ci, cj, s1, n1, s2, n2, C, tol, max_iter, coef, rho, iters);
+}
+
+struct SmoItem { const float* k; long ld_k; double* coef; double* rho; int* iters; int n; SvmClasses cls; };
+struct SmoGroup { SmoItem item[SVM_MAX_GROUP]; };
+static_assert(sizeof(SmoGroup) + 32 <= KERNARG_LIMIT, "svm_smo_group_kernel: descriptors beyond the kernel argument limit");
+
+// grid (pairs, count): blockIdx.y is the problem, blockIdx.x its pair.  No block waits for another: a group is count x pairs
+// independent solves, each ending at max_iter.
+__global__ __launch_bounds__(SMO_THREADS) void svm_smo_group_kernel(const SmoGroup g, int num_classes, double C, double tol, int max_iter) {
+    const SmoItem& d = g.item[blockIdx.y];
+    int ci, cj;
+    pair_classes(blockIdx.x, num_classes, ci, cj);
+    const int s1 = d.cls.start[ci], n1 = d.cls.start[ci + 1] - s1, s2 = d.cls.start[cj], n2 = d.cls.start[cj + 1] - s2;
+    smo_pair(d.k, d.ld_k, d.n, blockIdx.x, ci, cj, s1, n1, s2, n2, C, tol, max_iter, d.coef, d.rho, d.iters);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // decision values and the vote: one block per test row, a wave per pair (round robin)
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void svm_decide_kernel(const float* __restrict__ Kt, long ld_kt, int n, int num_classes, const SvmClasses cls,
-                                                         const double* __restrict__ coef, const double* __restrict__ rho,
-                                                         double* __restrict__ dec, int* __restrict__ labels) {
+// test row `row` of one problem by one block: the body of the single and of the grouped kernel
+__device__ __forceinline__ void decide_row(const float* __restrict__ Kt, long ld_kt, int n, int num_classes, const SvmClasses& cls,
+                                           const double* __restrict__ coef, const double* __restrict__ rho, double* __restrict__ dec,
+                                           int* __restrict__ labels, long row) {
     __shared__ double s_dec[SVM_MAX_PAIRS];
     __shared__ int s_votes[SVM_MAX_CLASSES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int pairs = num_classes * (num_classes - 1) / 2;
-    const long row = blockIdx.x;
     const float* kr = Kt + row * ld_kt;
     for (int p = wave; p < pairs; p += 4) {
         int ci, cj;
@@ -346,6 +398,25 @@ __global__ __launch_bounds__(256) void svm_decide_kernel(const float* __restrict
     }
 }
 
+__global__ __launch_bounds__(256) void svm_decide_kernel(const float* __restrict__ Kt, long ld_kt, int n, int num_classes, const SvmClasses cls,
+                                                         const double* __restrict__ coef, const double* __restrict__ rho,
+                                                         double* __restrict__ dec, int* __restrict__ labels) {
+    decide_row(Kt, ld_kt, n, num_classes, cls, coef, rho, dec, labels, blockIdx.x);
+}
+
+struct DecideItem { const float* kt; long ld_kt; const double* coef; const double* rho; double* dec; int* labels; int n; SvmClasses cls; };
+// the grid is the concatenation of the items' test rows: item i owns blocks row_start[i] .. row_start[i + 1] - 1
+struct DecideGroup { DecideItem item[SVM_MAX_GROUP]; int row_start[SVM_MAX_GROUP + 1]; };
+static_assert(sizeof(DecideGroup) + 8 <= KERNARG_LIMIT, "svm_decide_group_kernel: descriptors beyond the kernel argument limit");
+
+__global__ __launch_bounds__(256) void svm_decide_group_kernel(const DecideGroup g, int count, int num_classes) {
+    const int bid = blockIdx.x;
+    int it = 0;
+    while (it + 1 < count && bid >= g.row_start[it + 1]) ++it;        // wave-uniform: blockIdx and arguments only
+    const DecideItem& d = g.item[it];
+    decide_row(d.kt, d.ld_kt, d.n, num_classes, d.cls, d.coef, d.rho, d.dec, d.labels, bid - g.row_start[it]);
+}
+
 int fill_classes(long n, int num_classes, const int64_t* class_start, SvmClasses& cls, const char** err) {
     if (num_classes < 2 || num_classes > SVM_MAX_CLASSES) { *err = "svm: num_classes outside [2, 32]"; return -1; }
     if (!class_start) { *err = "svm: class_start is required"; return -1; }
@@ -359,15 +430,59 @@ int fill_classes(long n, int num_classes, const int64_t* class_start, SvmClasses
     for (int c = num_classes + 1; c <= SVM_MAX_CLASSES; ++c) cls.start[c] = (int)n;
     return 0;
 }
-}  // namespace
 
-int launch_svm_gram(const float* a, long ld_a, long m, const float* b, long ld_b, long n, long d, float gamma, float* out, long ld_out,
-                    int tile, hipStream_t s, const char** err) {
+// The argument checks of the three entries: a single call makes them on its one problem, a grouped call on every item, before
+// any launch.
+int check_gram(const float* a, long ld_a, long m, const float* b, long ld_b, long n, long d, float gamma, const float* out, long ld_out,
+               int tile, const char** err) {
     if (!a || !b || !out) { *err = "svm_gram: null buffer"; return -1; }
     if (m < 1 || n < 1 || d < 1 || m > (1 << 21) || n > (1 << 21) || d > (1 << 24)) { *err = "svm_gram: m, n in [1, 2^21] and d in [1, 2^24]"; return -1; }
     if (ld_a < d || ld_b < d || ld_out < n) { *err = "svm_gram: row pitch smaller than the row"; return -1; }
     if (!(gamma > 0.f) || !isfinite(gamma)) { *err = "svm_gram: gamma must be positive and finite"; return -1; }
     if (tile != 0 && tile != 64 && tile != 128) { *err = "svm_gram: tile must be 0, 64 or 128"; return -1; }
+    return 0;
+}
+
+int check_solve(const float* k, long ld_k, long n, int num_classes, const int64_t* class_start, double C, double tol, int max_iter,
+                const double* coef, const double* rho, const int* iters, SvmClasses& cls, const char** err) {
+    if (!k || !coef || !rho || !iters) { *err = "svm_solve: null buffer"; return -1; }
+    const int r = fill_classes(n, num_classes, class_start, cls, err);
+    if (r) return r;
+    if (ld_k < n) { *err = "svm_solve: row pitch smaller than the row"; return -1; }
+    if (!(C > 0.0) || !isfinite(C) || !(tol > 0.0) || !isfinite(tol) || max_iter < 1) { *err = "svm_solve: C, tol and max_iter must be positive"; return -1; }
+    // the two largest classes make the largest pair
+    int big1 = 0, big2 = 0;
+    for (int c = 0; c < num_classes; ++c) {
+        const int sz = cls.start[c + 1] - cls.start[c];
+        if (sz > big1) { big2 = big1; big1 = sz; } else if (sz > big2) big2 = sz;
+    }
+    if (big1 + big2 > SVM_MAX_PAIR) { *err = "svm_solve: a one-vs-one pair has more than MRGAN_SVM_MAX_PAIR = 2048 rows"; return -1; }
+    return 0;
+}
+
+int check_decide(const float* kt, long ld_kt, long m, long n, int num_classes, const int64_t* class_start, const double* coef,
+                 const double* rho, const int* labels, SvmClasses& cls, const char** err) {
+    if (!kt || !coef || !rho || !labels) { *err = "svm_decide: null buffer"; return -1; }
+    const int r = fill_classes(n, num_classes, class_start, cls, err);
+    if (r) return r;
+    if (m < 1 || m > (1 << 24)) { *err = "svm_decide: m outside [1, 2^24]"; return -1; }
+    if (ld_kt < n) { *err = "svm_decide: row pitch smaller than the row"; return -1; }
+    return 0;
+}
+
+// items == null or count outside [1, SVM_MAX_GROUP]: the group's own check (*bad_item stays -1)
+int check_group(const void* items, int count, const char* null_msg, const char* count_msg, int* bad_item, const char** err) {
+    *bad_item = -1;
+    if (!items) { *err = null_msg; return -1; }
+    if (count < 1 || count > SVM_MAX_GROUP) { *err = count_msg; return -1; }
+    return 0;
+}
+}  // namespace
+
+int launch_svm_gram(const float* a, long ld_a, long m, const float* b, long ld_b, long n, long d, float gamma, float* out, long ld_out,
+                    int tile, hipStream_t s, const char** err) {
+    const int r = check_gram(a, ld_a, m, b, ld_b, n, d, gamma, out, ld_out, tile, err);
+    if (r) return r;
     // 64x64 blocks while 128x128 ones would leave most CUs without work, as launch_gemm_f32 chooses; every output element is
     // the same k-ordered chain in both
     const bool small = tile ? tile == 64 : (long)ceil_div(n, 128) * ceil_div(m, 128) < 128;
@@ -385,19 +500,9 @@ int launch_svm_gram(const float* a, long ld_a, long m, const float* b, long ld_b
 
 int launch_svm_solve(const float* k, long ld_k, long n, int num_classes, const int64_t* class_start, double C, double tol, int max_iter,
                      double* coef, double* rho, int* iters, hipStream_t s, const char** err) {
-    if (!k || !coef || !rho || !iters) { *err = "svm_solve: null buffer"; return -1; }
     SvmClasses cls;
-    const int r = fill_classes(n, num_classes, class_start, cls, err);
+    const int r = check_solve(k, ld_k, n, num_classes, class_start, C, tol, max_iter, coef, rho, iters, cls, err);
     if (r) return r;
-    if (ld_k < n) { *err = "svm_solve: row pitch smaller than the row"; return -1; }
-    if (!(C > 0.0) || !isfinite(C) || !(tol > 0.0) || !isfinite(tol) || max_iter < 1) { *err = "svm_solve: C, tol and max_iter must be positive"; return -1; }
-    // the two largest classes make the largest pair
-    int big1 = 0, big2 = 0;
-    for (int c = 0; c < num_classes; ++c) {
-        const int sz = cls.start[c + 1] - cls.start[c];
-        if (sz > big1) { big2 = big1; big1 = sz; } else if (sz > big2) big2 = sz;
-    }
-    if (big1 + big2 > SVM_MAX_PAIR) { *err = "svm_solve: a one-vs-one pair has more than MRGAN_SVM_MAX_PAIR = 2048 rows"; return -1; }
     const int pairs = num_classes * (num_classes - 1) / 2;
     MRGAN_LAUNCH(svm_smo_kernel, dim3(pairs), dim3(SMO_THREADS), 0, s, k, ld_k, (int)n, num_classes, cls, C, tol, max_iter, coef, rho, iters);
     if (hipGetLastError() != hipSuccess) { *err = "svm_solve: launch failed"; return -10; }
@@ -406,14 +511,83 @@ int launch_svm_solve(const float* k, long ld_k, long n, int num_classes, const i
 
 int launch_svm_decide(const float* kt, long ld_kt, long m, long n, int num_classes, const int64_t* class_start, const double* coef,
                       const double* rho, double* dec, int* labels, hipStream_t s, const char** err) {
-    if (!kt || !coef || !rho || !labels) { *err = "svm_decide: null buffer"; return -1; }
     SvmClasses cls;
-    const int r = fill_classes(n, num_classes, class_start, cls, err);
+    const int r = check_decide(kt, ld_kt, m, n, num_classes, class_start, coef, rho, labels, cls, err);
     if (r) return r;
-    if (m < 1 || m > (1 << 24)) { *err = "svm_decide: m outside [1, 2^24]"; return -1; }
-    if (ld_kt < n) { *err = "svm_decide: row pitch smaller than the row"; return -1; }
     MRGAN_LAUNCH(svm_decide_kernel, dim3((unsigned)m), dim3(256), 0, s, kt, ld_kt, (int)n, num_classes, cls, coef, rho, dec, labels);
     if (hipGetLastError() != hipSuccess) { *err = "svm_decide: launch failed"; return -10; }
+    return 0;
+}
+
+int launch_svm_gram_group(const mrgan_svm_gram_item* items, int count, long d, float gamma, int tile, hipStream_t s, const char** err,
+                          int* bad_item) {
+    int r = check_group(items, count, "svm_gram: null item list", "svm_gram: count outside [1, MRGAN_SVM_MAX_GROUP = 16]", bad_item, err);
+    if (r) return r;
+    long tiles128 = 0;
+    for (int i = 0; i < count; ++i) {
+        const mrgan_svm_gram_item& it = items[i];
+        r = check_gram(it.a_dev, (long)it.ld_a, (long)it.m, it.b_dev, (long)it.ld_b, (long)it.n, d, gamma, it.out_dev, (long)it.ld_out, tile, err);
+        if (r) { *bad_item = i; return r; }
+        tiles128 += (long)ceil_div(it.n, 128) * ceil_div(it.m, 128);
+    }
+    // launch_svm_gram's rule on the group's total: one tile size per launch
+    const int ts = tile ? tile : (tiles128 < 128 ? 64 : 128);
+    GramGroup g = {};
+    long total = 0;
+    for (int i = 0; i < count; ++i) {
+        const mrgan_svm_gram_item& it = items[i];
+        g.item[i] = {it.a_dev, it.b_dev, it.out_dev, (long)it.ld_a, (long)it.ld_b, (long)it.ld_out, (int)it.m, (int)it.n};
+        g.tile_start[i] = (int)total;
+        g.tiles_x[i] = ceil_div(it.n, ts);
+        total += (long)g.tiles_x[i] * ceil_div(it.m, ts);
+        if (total > 0x7fffffffL) { *bad_item = i; *err = "svm_gram: the group has more than 2^31 - 1 tiles"; return -1; }
+    }
+    for (int i = count; i <= SVM_MAX_GROUP; ++i) g.tile_start[i] = (int)total;
+    for (int i = count; i < SVM_MAX_GROUP; ++i) g.tiles_x[i] = 1;
+    const dim3 grid((unsigned)total), block(256);
+    if (ts == 64) MRGAN_LAUNCH((svm_gram_group_kernel<64>), grid, block, 0, s, g, count, (int)d, gamma);
+    else MRGAN_LAUNCH((svm_gram_group_kernel<128>), grid, block, 0, s, g, count, (int)d, gamma);
+    if (hipGetLastError() != hipSuccess) { *err = "svm_gram: group launch failed"; return -10; }
+    return 0;
+}
+
+int launch_svm_solve_group(const mrgan_svm_solve_item* items, int count, int num_classes, double C, double tol, int max_iter, hipStream_t s,
+                           const char** err, int* bad_item) {
+    int r = check_group(items, count, "svm_solve: null item list", "svm_solve: count outside [1, MRGAN_SVM_MAX_GROUP = 16]", bad_item, err);
+    if (r) return r;
+    SmoGroup g = {};
+    for (int i = 0; i < count; ++i) {
+        const mrgan_svm_solve_item& it = items[i];
+        r = check_solve(it.k_dev, (long)it.ld_k, (long)it.n, num_classes, it.class_start_host, C, tol, max_iter, it.coef_dev, it.rho_dev,
+                        it.iters_dev, g.item[i].cls, err);
+        if (r) { *bad_item = i; return r; }
+        g.item[i].k = it.k_dev; g.item[i].ld_k = (long)it.ld_k; g.item[i].coef = it.coef_dev; g.item[i].rho = it.rho_dev;
+        g.item[i].iters = it.iters_dev; g.item[i].n = (int)it.n;
+    }
+    const int pairs = num_classes * (num_classes - 1) / 2;
+    MRGAN_LAUNCH(svm_smo_group_kernel, dim3(pairs, count), dim3(SMO_THREADS), 0, s, g, num_classes, C, tol, max_iter);
+    if (hipGetLastError() != hipSuccess) { *err = "svm_solve: group launch failed"; return -10; }
+    return 0;
+}
+
+int launch_svm_decide_group(const mrgan_svm_decide_item* items, int count, int num_classes, hipStream_t s, const char** err, int* bad_item) {
+    int r = check_group(items, count, "svm_decide: null item list", "svm_decide: count outside [1, MRGAN_SVM_MAX_GROUP = 16]", bad_item, err);
+    if (r) return r;
+    DecideGroup g = {};
+    long total = 0;
+    for (int i = 0; i < count; ++i) {
+        const mrgan_svm_decide_item& it = items[i];
+        r = check_decide(it.kt_dev, (long)it.ld_kt, (long)it.m, (long)it.n, num_classes, it.class_start_host, it.coef_dev, it.rho_dev,
+                         it.labels_dev, g.item[i].cls, err);
+        if (r) { *bad_item = i; return r; }
+        g.item[i].kt = it.kt_dev; g.item[i].ld_kt = (long)it.ld_kt; g.item[i].coef = it.coef_dev; g.item[i].rho = it.rho_dev;
+        g.item[i].dec = it.dec_dev; g.item[i].labels = it.labels_dev; g.item[i].n = (int)it.n;
+        g.row_start[i] = (int)total;
+        total += (long)it.m;                                 // <= 16 * 2^24
+    }
+    for (int i = count; i <= SVM_MAX_GROUP; ++i) g.row_start[i] = (int)total;
+    MRGAN_LAUNCH(svm_decide_group_kernel, dim3((unsigned)total), dim3(256), 0, s, g, count, num_classes);
+    if (hipGetLastError() != hipSuccess) { *err = "svm_decide: group launch failed"; return -10; }
     return 0;
 }
 

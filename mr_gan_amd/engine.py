@@ -38,9 +38,11 @@ EXPORTS = [
     "mrgan_input_gradient", "mrgan_attribution",
     "mrgan_ae_step", "mrgan_ae_encode", "mrgan_ae_reconstruct",
     "mrgan_svm_gram", "mrgan_svm_solve", "mrgan_svm_decide", "mrgan_debug_svm_gram",
+    "mrgan_svm_gram_group", "mrgan_svm_solve_group", "mrgan_svm_decide_group", "mrgan_debug_svm_gram_group",
 ]
 SVM_MAX_PAIR = 2048           # MRGAN_SVM_MAX_PAIR: rows of one one-vs-one problem
 SVM_MAX_CLASSES = 32
+SVM_MAX_GROUP = 16            # MRGAN_SVM_MAX_GROUP: problems of one grouped launch
 SAL_LOGIT, SAL_XENT, SAL_MSE = 0, 1, 2
 SAL_RAW, SAL_HEATMAP = 0, 1
 SAL_OBJECTIVES = {'logit': SAL_LOGIT, 'xent': SAL_XENT, 'mse': SAL_MSE}
@@ -128,6 +130,33 @@ class GenGroupArgs(C.Structure):
         ("ld_x_unl", C.c_int64),
         ("x_unl_model_stride", C.c_int64), ("idx_unl_model_stride", C.c_int64), ("z_model_stride", C.c_int64),
         ("stream_mode", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class SvmGramItem(C.Structure):
+    """mrgan_svm_gram_item"""
+    _fields_ = [
+        ("a", C.c_void_p), ("ld_a", C.c_int64), ("m", C.c_int64),
+        ("b", C.c_void_p), ("ld_b", C.c_int64), ("n", C.c_int64),
+        ("out", C.c_void_p), ("ld_out", C.c_int64),
+    ]
+
+
+class SvmSolveItem(C.Structure):
+    """mrgan_svm_solve_item"""
+    _fields_ = [
+        ("k", C.c_void_p), ("ld_k", C.c_int64), ("n", C.c_int64),
+        ("class_start", C.POINTER(C.c_int64)),
+        ("coef", C.c_void_p), ("rho", C.c_void_p), ("iters", C.c_void_p),
+    ]
+
+
+class SvmDecideItem(C.Structure):
+    """mrgan_svm_decide_item"""
+    _fields_ = [
+        ("kt", C.c_void_p), ("ld_kt", C.c_int64), ("m", C.c_int64), ("n", C.c_int64),
+        ("class_start", C.POINTER(C.c_int64)),
+        ("coef", C.c_void_p), ("rho", C.c_void_p), ("dec", C.c_void_p), ("labels", C.c_void_p),
     ]
 
 
@@ -235,6 +264,10 @@ def load_library(path=None):
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mrgan_svm_decide.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mrgan_svm_gram_group.argtypes = [C.POINTER(SvmGramItem), C.c_int32, C.c_int64, C.c_float, C.c_void_p]
+    lib.mrgan_debug_svm_gram_group.argtypes = [C.POINTER(SvmGramItem), C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_void_p]
+    lib.mrgan_svm_solve_group.argtypes = [C.POINTER(SvmSolveItem), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p]
+    lib.mrgan_svm_decide_group.argtypes = [C.POINTER(SvmDecideItem), C.c_int32, C.c_int32, C.c_void_p]
     _lib = lib
     return lib
 

@@ -2,7 +2,10 @@
 RBF-kernel SVC (C = 1) trained on the labeled subset only.  By default on scikit-learn / CPU as in the reference;
 --backend hip fits and scores with mr_gan_amd.svm.RBFSVM (csrc/svm.hip: Gram matrix, SMO solver and vote on the GPU).
 
-    python -m mr_gan_amd.mr_svm --tables 2 4 [-v] [--backend {sklearn,hip}]
+    python -m mr_gan_amd.mr_svm --tables 2 4 [-v] [--backend {sklearn,hip}] [--group-folds]
+
+--group-folds (with --backend hip) fits and scores the six folds of each table-2 cell, and consecutive runs of twelve objects of
+each table-4 cell, as ONE RBFSVMGroup (grouped launches over ragged problems) and prints the same lines.
 
 Shares dataset(), the data prologue and the modality names with mr_gan_amd.mr_gan; prints the reference's lines
 (mr_svm.py prints only the averages for table 2 and one line per object for table 4)."""
@@ -15,7 +18,7 @@ import numpy as np
 
 from mr_gan_amd.data import prologue, resolve_num_classes, train_test_sets
 from mr_gan_amd.mr_gan import MODALITIES, dataset, print_lines
-from mr_gan_amd.svm import RBFSVM
+from mr_gan_amd.svm import RBFSVM, RBFSVMGroup
 
 
 SVC_GAMMA = 'auto'
@@ -45,10 +48,34 @@ def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None
     return testerror
 
 
-def baseline_tables(tables, fn, dataset_fn, verbose=False, folds_fn=None):
+def mr_svm_folds(sets, percentlabeled=50, verbose=False, seed=None):
+    """mr_svm(backend='hip') of every [X_train, X_test, y_train, y_test] of `sets` (the folds of a table-2 cell, the objects of a
+    table-4 cell) as one RBFSVMGroup -> their test errors.  Fold f runs mr_svm()'s prologue from RandomState(seed + f), the rule
+    of mr_nn_folds: the errors are those of mr_svm(None, None, trainTestSets=sets[f], seed=seed + f, backend='hip')."""
+    base = int(seed if seed is not None else np.random.randint(1 << 30))
+    num_classes = resolve_num_classes(None)
+    folds = []
+    for f, s in enumerate(sets):
+        folds.append(prologue(s, percentlabeled, None, np.random.RandomState(base + f), num_classes))
+        print_lines(folds[-1][-1], verbose)
+    x_labeled, y_labeled, _, _, X_test, y_test, _ = zip(*folds)
+    group = RBFSVMGroup(C=1.0, gamma=SVC_GAMMA).fit(x_labeled, y_labeled)
+    errors = [1.0 - s for s in group.score(X_test, y_test)]
+    if verbose:
+        for e, lab, yt in zip(errors, group.predict(X_test), y_test):
+            print_lines([('Test error:', e, 1.0 - np.mean(lab == yt))])
+    return errors
+
+
+OBJECT_GROUP = 12              # table 4: consecutive runs of this many objects of a cell are one group
+
+
+def baseline_tables(tables, fn, dataset_fn, verbose=False, folds_fn=None, objects_fn=None):
     """The --tables 2 4 loops shared by mr_svm.py:126-166 and mr_nn.py:128-168 (identical up to the function called).
-    folds_fn (mr_nn --group-folds): table 2 hands the six folds of a (modality, percentage) to
-    folds_fn(sets, percentlabeled=, verbose=) -> their test errors in fold order, instead of calling fn once per fold."""
+    folds_fn (mr_nn / mr_svm --group-folds): table 2 hands the six folds of a (modality, percentage) to
+    folds_fn(sets, percentlabeled=, verbose=) -> their test errors in fold order, instead of calling fn once per fold.
+    objects_fn (mr_svm --group-folds), the same signature: table 4 hands it consecutive runs of OBJECT_GROUP leave-one-out sets
+    of a cell; the per-object lines keep their order and format."""
     from sklearn.model_selection import StratifiedKFold
     if '2' in tables:
         print('\n', '-' * 25, 'Testing various amounts of labeled training data', '-' * 25)
@@ -77,28 +104,45 @@ def baseline_tables(tables, fn, dataset_fn, verbose=False, folds_fn=None):
             objects = dataset_fn(modalities=modality, leaveObjectOut=True)
             for percent in [1, 4, 16, 50, 100]:
                 print('-' * 15, 'Percentage of training data labeled: %d%%' % percent, '-' * 15)
-                errors = []
-                for objName, objData in objects.items():
+                errors, names, pending = [], list(objects), []
+                for k, (objName, objData) in enumerate(objects.items()):
                     Xtest, ytest = np.array(objData['x']), np.array(objData['y'])
                     Xtrain = np.array(list(itertools.chain.from_iterable([d['x'] for n, d in objects.items() if n != objName])))
                     ytrain = np.array(list(itertools.chain.from_iterable([d['y'] for n, d in objects.items() if n != objName])))
-                    errors.append(fn(None, None, percentlabeled=percent, trainTestSets=[Xtrain, Xtest, ytrain, ytest], verbose=verbose))
-                    print(objName, 'Test error:', errors[-1], 'Test accuracy:', 1.0 - errors[-1])
+                    pending.append([Xtrain, Xtest, ytrain, ytest])
+                    if objects_fn is not None and len(pending) < OBJECT_GROUP and k + 1 < len(names):
+                        continue
+                    if objects_fn is not None:
+                        new = list(objects_fn(pending, percentlabeled=percent, verbose=verbose))
+                    else:
+                        new = [fn(None, None, percentlabeled=percent, trainTestSets=pending[0], verbose=verbose)]
+                    for name, e in zip(names[len(errors):], new):
+                        print(name, 'Test error:', e, 'Test accuracy:', 1.0 - e)
+                    errors += new
+                    pending = []
                     sys.stdout.flush()
                 print('Average leave-one-object-out error:', np.mean(errors), 'Average accuracy:', np.mean(1.0 - np.array(errors)))
                 sys.stdout.flush()
 
 
-def main(argv=None, dataset_fn=dataset, fn=mr_svm):
+def main(argv=None, dataset_fn=dataset, fn=mr_svm, folds_fn=None):
     parser = argparse.ArgumentParser(description='RBF-SVM baseline for material recognition on haptic data.')
     parser.add_argument('-t', '--tables', nargs='+', help='[Required] Tables to recompute', required=True)
     parser.add_argument('-v', '--verbose', help='Verbose', action='store_true')
     parser.add_argument('--backend', choices=BACKENDS, default='sklearn',
                         help="'sklearn': scikit-learn on the CPU, as in the reference (default); 'hip': RBFSVM on the GPU")
+    parser.add_argument('--group-folds', action='store_true',
+                        help='with --backend hip: fit and score the six folds of a table-2 cell, and runs of twelve objects of a '
+                             'table-4 cell, as one RBFSVMGroup (one launch set)')
     args = parser.parse_args(argv)
+    if args.group_folds and args.backend != 'hip':
+        parser.error('--group-folds needs --backend hip')
     if args.backend != 'sklearn':
         fn = functools.partial(fn, backend=args.backend)
-    baseline_tables(args.tables, fn, dataset_fn, args.verbose)
+    if args.group_folds and folds_fn is None:
+        folds_fn = mr_svm_folds
+    hook = folds_fn if args.group_folds else None
+    baseline_tables(args.tables, fn, dataset_fn, args.verbose, folds_fn=hook, objects_fn=hook)
 
 
 if __name__ == '__main__':

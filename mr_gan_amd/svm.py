@@ -5,7 +5,8 @@
 Three launches of csrc/svm.hip behind include/mrgan_abi.h: mrgan_svm_gram (fp32 Gram matrix on the matrix cores),
 mrgan_svm_solve (libsvm's SMO, one workgroup per one-vs-one pair, fp64 state on chip) and mrgan_svm_decide (decision values
 and the vote).  There is no CPU path: without the library or a GPU every entry raises.  The numpy restatement the tests
-compare against lives in tests/svm_ref.py.
+compare against lives in tests/svm_ref.py.  RBFSVMGroup fits and scores several independent problems (the folds of a table cell)
+through the grouped entries mrgan_svm_*_group, one launch set for up to 16 of them, with RBFSVM's bits per problem.
 
 Conventions are libsvm's: pairs (i, j), i < j, in the order of scikit-learn's decision_function_shape='ovo'; a positive
 decision value votes for classes_[i]; intercept_ = -rho.  Two classes give ONE column with that same sign (scikit-learn flips
@@ -55,8 +56,11 @@ def _finite_matrix(X, name, d=None):
     return X32
 
 
-class RBFSVM:
-    def __init__(self, C=1.0, gamma='auto', tol=1e-3, max_iter=10_000_000, device='cuda:0'):
+class _DeviceSVM:
+    """what RBFSVM and RBFSVMGroup share: the hyper-parameters and their checks, the library call on the current stream and
+    the per-stage device-event timer"""
+
+    def __init__(self, C, gamma, tol, max_iter, device):
         if not (isinstance(gamma, str) and gamma == 'auto') and not (np.isreal(gamma) and np.isfinite(gamma) and gamma > 0):
             raise ValueError("gamma must be 'auto' (1 / n_features, the reference's kernel width) or a positive number, got %r" % (gamma,))
         if not (np.isfinite(C) and C > 0 and np.isfinite(tol) and tol > 0):
@@ -64,7 +68,6 @@ class RBFSVM:
         if int(max_iter) != max_iter or not 1 <= max_iter < 2 ** 31:
             raise ValueError("max_iter must be an integer in [1, 2^31), got %r" % (max_iter,))
         self.C, self.gamma, self.tol, self.max_iter, self.device = float(C), gamma, float(tol), int(max_iter), torch.device(device)
-        self.classes_ = None
         self.times_ = {}                 # seconds of the last fit / predict per stage, filled only while time_stages is set
         self.time_stages = False
 
@@ -91,6 +94,12 @@ class RBFSVM:
         E.load_library()
         if not torch.cuda.is_available():
             raise RuntimeError("RBFSVM runs on the GPU only (mrgan_svm_*); no HIP device is visible and there is no CPU fallback")
+
+
+class RBFSVM(_DeviceSVM):
+    def __init__(self, C=1.0, gamma='auto', tol=1e-3, max_iter=10_000_000, device='cuda:0'):
+        _DeviceSVM.__init__(self, C, gamma, tol, max_iter, device)
+        self.classes_ = None
 
     def _gram(self, a, b):
         out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=self.device)
@@ -168,3 +177,152 @@ class RBFSVM:
 
     def score(self, X, y, chunk=None):
         return float(np.mean(self.predict(X, chunk) == np.asarray(y)))
+
+
+def plan_subgroups(nbytes, budget, max_group=E.SVM_MAX_GROUP):
+    """consecutive sub-groups of the problems 0 .. len(nbytes) - 1, in order: at most max_group problems each and at most
+    `budget` bytes of nbytes together; a single problem above the budget is a sub-group of its own -> list of index lists"""
+    groups, cur, used = [], [], 0
+    for p, b in enumerate(nbytes):
+        if cur and (len(cur) == max_group or used + b > budget):
+            groups.append(cur)
+            cur, used = [], 0
+        cur.append(p)
+        used += b
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+class _Fitted:
+    """one problem of a fitted RBFSVMGroup: what a fitted RBFSVM exposes"""
+
+    def __init__(self, classes, dual_coef_dense, intercept, n_iter):
+        self.classes_, self.dual_coef_dense_, self.intercept_, self.n_iter_ = classes, dual_coef_dense, intercept, n_iter
+
+
+class RBFSVMGroup(_DeviceSVM):
+    """Independent RBFSVM problems of one feature count and one class count (the folds of a table cell), fitted and scored in
+    grouped launches: mrgan_svm_gram_group, mrgan_svm_solve_group, mrgan_svm_decide_group serve up to 16 ragged problems
+    each.  Problem p's results are those of RBFSVM(...).fit(Xs[p], ys[p]) bit for bit.
+
+        group = RBFSVMGroup().fit(Xs, ys); errors = [1.0 - s for s in group.score(X_tests, y_tests)]; group[p].n_iter_
+
+    More than 16 problems, or Gram matrices above gram_bytes together, are worked in consecutive sub-groups (plan_subgroups);
+    prediction takes the problems' rows in chunks, one cross-Gram launch and one decide launch per chunk step of a sub-group.
+    Neither changes a bit.  There is no CPU path."""
+
+    def __init__(self, C=1.0, gamma='auto', tol=1e-3, max_iter=10_000_000, device='cuda:0', gram_bytes=4 << 30):
+        _DeviceSVM.__init__(self, C, gamma, tol, max_iter, device)
+        if int(gram_bytes) != gram_bytes or gram_bytes < 1:
+            raise ValueError("gram_bytes must be a positive integer, got %r" % (gram_bytes,))
+        self.gram_bytes = int(gram_bytes)
+        self._fitted = None
+
+    def __len__(self):
+        return 0 if self._fitted is None else len(self._fitted)
+
+    def __getitem__(self, p):
+        if self._fitted is None:
+            raise RuntimeError("RBFSVMGroup: fit() first")
+        return self._fitted[p]
+
+    def fit(self, Xs, ys):
+        if len(Xs) != len(ys) or len(Xs) == 0:
+            raise ValueError("fit: %d row sets and %d label sets; a group needs as many of one as of the other, at least one" % (len(Xs), len(ys)))
+        probs = []
+        for p, (X, y) in enumerate(zip(Xs, ys)):
+            X32 = _finite_matrix(X, "Xs[%d]" % p)
+            classes, order, class_start = class_sort(y)
+            if len(y) != X32.shape[0]:
+                raise ValueError("Xs[%d] has %d rows, ys[%d] has %d labels" % (p, X32.shape[0], p, len(y)))
+            K = len(classes)
+            if not 2 <= K <= E.SVM_MAX_CLASSES:
+                raise ValueError("RBFSVMGroup needs 2 to %d classes, problem %d has %d" % (E.SVM_MAX_CLASSES, p, K))
+            sizes = np.sort(np.diff(class_start))
+            if sizes[-1] + sizes[-2] > E.SVM_MAX_PAIR:
+                raise ValueError("the two largest classes of problem %d have %d rows together; one one-vs-one problem holds at most %d "
+                                 "(MRGAN_SVM_MAX_PAIR)" % (p, sizes[-1] + sizes[-2], E.SVM_MAX_PAIR))
+            probs.append((X32, classes, order, class_start))
+        if len({q[0].shape[1] for q in probs}) != 1:
+            raise ValueError("a group shares one feature count, got %s" % sorted({q[0].shape[1] for q in probs}))
+        if len({len(q[1]) for q in probs}) != 1:
+            raise ValueError("a group shares one class count, got %s" % sorted({len(q[1]) for q in probs}))
+        self._require_gpu()
+        d, K = probs[0][0].shape[1], len(probs[0][1])
+        pairs = K * (K - 1) // 2
+        self._gamma = 1.0 / d if isinstance(self.gamma, str) else float(self.gamma)
+        self.times_ = {}
+        self.n_features_in_, self._K = d, K
+        self._cs = [(C.c_int64 * (K + 1))(*[int(v) for v in q[3]]) for q in probs]
+        self._x = [torch.from_numpy(q[0][q[2]]).to(self.device) for q in probs]
+        self._coef = [torch.empty((K - 1, len(x)), dtype=torch.float64, device=self.device) for x in self._x]
+        self._rho = [torch.empty(pairs, dtype=torch.float64, device=self.device) for _ in probs]
+        iters = [torch.empty(pairs, dtype=torch.int32, device=self.device) for _ in probs]
+        for sub in plan_subgroups([4 * len(x) * len(x) for x in self._x], self.gram_bytes):
+            grams = [torch.empty((len(self._x[p]), len(self._x[p])), dtype=torch.float32, device=self.device) for p in sub]
+            gi = (E.SvmGramItem * len(sub))(*[E.SvmGramItem(self._x[p].data_ptr(), self._x[p].stride(0), len(self._x[p]),
+                                                            self._x[p].data_ptr(), self._x[p].stride(0), len(self._x[p]),
+                                                            g.data_ptr(), g.stride(0)) for p, g in zip(sub, grams)])
+            si = (E.SvmSolveItem * len(sub))(*[E.SvmSolveItem(g.data_ptr(), g.stride(0), len(self._x[p]), self._cs[p], self._coef[p].data_ptr(),
+                                                              self._rho[p].data_ptr(), iters[p].data_ptr()) for p, g in zip(sub, grams)])
+            self._timed('gram', lambda: self._call("mrgan_svm_gram_group", gi, len(sub), d, self._gamma))
+            self._timed('solve', lambda: self._call("mrgan_svm_solve_group", si, len(sub), K, self.C, self.tol, self.max_iter))
+            del grams                # back to the stream-ordered allocator: the next sub-group's launches come after these
+        self._fitted = [_Fitted(q[1], unsort_coef(self._coef[p].cpu().numpy(), q[2]), -self._rho[p].cpu().numpy(), iters[p].cpu().numpy())
+                        for p, q in enumerate(probs)]
+        late = [p for p, f in enumerate(self._fitted) if (f.n_iter_ >= self.max_iter).any()]
+        if late:
+            warnings.warn("RBFSVMGroup: problems %s have one-vs-one pairs that stopped at max_iter = %d before reaching tol = %g"
+                          % (late, self.max_iter, self.tol), SVMConvergenceWarning, stacklevel=2)
+        return self
+
+    def _decide(self, Xs, chunk, want_dec):
+        if self._fitted is None:
+            raise RuntimeError("RBFSVMGroup: fit() first")
+        if len(Xs) != len(self._fitted):
+            raise ValueError("the group was fitted on %d problems, got %d row sets" % (len(self._fitted), len(Xs)))
+        X32 = [_finite_matrix(X, "Xs[%d]" % p, self.n_features_in_) for p, X in enumerate(Xs)]
+        if chunk is None:
+            chunk = 4096
+        if int(chunk) != chunk or chunk < 1:
+            raise ValueError("chunk must be a positive integer, got %r" % (chunk,))
+        chunk = int(chunk)
+        self._require_gpu()
+        K, d = self._K, self.n_features_in_
+        pairs = K * (K - 1) // 2
+        labels = [torch.empty(len(x), dtype=torch.int32, device=self.device) for x in X32]
+        dec = [torch.empty((len(x), pairs), dtype=torch.float64, device=self.device) if want_dec else None for x in X32]
+
+        def run():
+            # a chunk step takes rows r0 .. r0 + chunk - 1 of every problem of the sub-group that still has rows there; every
+            # row's values depend on that row and its problem alone
+            for sub in plan_subgroups([4 * min(chunk, len(X32[p])) * len(self._x[p]) for p in range(len(X32))], self.gram_bytes):
+                for r0 in range(0, max(len(X32[p]) for p in sub), chunk):
+                    live = [p for p in sub if r0 < len(X32[p])]
+                    xt = [torch.from_numpy(X32[p][r0:r0 + chunk]).to(self.device) for p in live]
+                    kt = [torch.empty((len(t), len(self._x[p])), dtype=torch.float32, device=self.device) for p, t in zip(live, xt)]
+                    gi = (E.SvmGramItem * len(live))(*[E.SvmGramItem(t.data_ptr(), t.stride(0), len(t), self._x[p].data_ptr(),
+                                                                     self._x[p].stride(0), len(self._x[p]), k.data_ptr(), k.stride(0))
+                                                       for p, t, k in zip(live, xt, kt)])
+                    di = (E.SvmDecideItem * len(live))(*[E.SvmDecideItem(k.data_ptr(), k.stride(0), len(t), len(self._x[p]), self._cs[p],
+                                                                         self._coef[p].data_ptr(), self._rho[p].data_ptr(),
+                                                                         dec[p][r0:].data_ptr() if want_dec else None, labels[p][r0:].data_ptr())
+                                                         for p, t, k in zip(live, xt, kt)])
+                    self._call("mrgan_svm_gram_group", gi, len(live), d, self._gamma)
+                    self._call("mrgan_svm_decide_group", di, len(live), K)
+        self._timed('predict', run)
+        return [l.cpu().numpy() for l in labels], [v.cpu().numpy() if want_dec else None for v in dec]
+
+    def decision_function(self, Xs, chunk=None):
+        """per problem [rows, K (K - 1) / 2] one-vs-one decision values, columns in scikit-learn's 'ovo' order"""
+        return self._decide(Xs, chunk, True)[1]
+
+    def predict(self, Xs, chunk=None):
+        """per problem the labels of the rows of Xs[p], worked in chunks of `chunk` rows (default 4096)"""
+        return [f.classes_[l] for f, l in zip(self._fitted, self._decide(Xs, chunk, False)[0])]
+
+    def score(self, Xs, ys, chunk=None):
+        if len(ys) != len(Xs):
+            raise ValueError("score: %d row sets and %d label sets" % (len(Xs), len(ys)))
+        return [float(np.mean(l == np.asarray(y))) for l, y in zip(self.predict(Xs, chunk), ys)]

@@ -9,7 +9,13 @@ size is warmed up once, then repeated; the medians are reported, with the per-pa
 test error of both.
 
     python scripts/svm_bench.py [--labeled 60 960 6000] [--repeats 5] [--sklearn-repeats 3]
-Prints one JSON line per size."""
+Prints one JSON line per size.
+
+    python scripts/svm_bench.py --group [G] [--labeled 60 960 6000] [--repeats 5]          (G = 6 where not given)
+times G fits and scores through one RBFSVMGroup (grouped launches) against the same G problems through G RBFSVM objects one
+after the other, in the same process and by the same scheme (warm-up, medians, stages in passes of their own; scikit-learn is not
+run).  Problem f takes its training fold from np.arange(len(y)) % 6 != f % 6, so the problems hold different rows.  One JSON
+line per size with both totals, the per-stage times and their ratios single / grouped (profiles/svm_group_bench.txt)."""
 import argparse
 import json
 import os
@@ -20,7 +26,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from mr_gan_amd import RBFSVM, synthetic_mreo  # noqa: E402
+from mr_gan_amd import RBFSVM, RBFSVMGroup, synthetic_mreo  # noqa: E402
 
 
 def main():
@@ -29,12 +35,28 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sklearn-repeats", type=int, default=3, help="repeats of the CPU side (1 at 6000 rows: one fit is tens of seconds)")
     ap.add_argument("--d", type=int, default=1200)
+    ap.add_argument("--group", type=int, nargs="?", const=6, default=None,
+                    help="time G problems through RBFSVMGroup against G RBFSVM objects instead (G = 6 where not given)")
     args = ap.parse_args()
+    if args.group is not None and args.group < 1:
+        ap.error("--group needs at least one problem")
     if not torch.cuda.is_available():
         raise SystemExit("svm_bench needs a GPU: nothing is measured without one")
     from sklearn import preprocessing
     from sklearn.svm import SVC
     X, y, _ = synthetic_mreo(d=args.d)
+    if args.group is not None:
+        folds = []
+        for f in range(args.group):
+            tr = np.arange(len(y)) % 6 != f % 6
+            sc = preprocessing.StandardScaler()
+            folds.append((sc.fit_transform(X[tr]), y[tr], sc.transform(X[~tr]), y[~tr]))
+        for n in args.labeled:
+            per = n // 6
+            probs = [(np.concatenate([a[ya == c][:per] for c in range(6)]), np.repeat(np.arange(6), per), xt, yt) for a, ya, xt, yt in folds]
+            print(json.dumps(measure_group(args, probs)))
+            sys.stdout.flush()
+        return
     tr = np.arange(len(y)) % 6 != 0
     sc = preprocessing.StandardScaler()
     a, xt = sc.fit_transform(X[tr]), sc.transform(X[~tr])
@@ -88,6 +110,71 @@ def measure(args, SVC, xl, yl, xt, yt):
                 hip_iterations=clf.n_iter_.tolist(), sklearn_iterations=np.asarray(svc.n_iter_).tolist(),
                 hip_test_error=round(1.0 - acc, 6), sklearn_test_error=round(1.0 - sk_acc, 6),
                 gram_gflop=round(2e-9 * n * n * d, 2))
+
+
+def measure_group(args, probs):
+    G = len(probs)
+    xs, ys, xts, yts = [list(v) for v in zip(*probs)]
+    group = RBFSVMGroup(C=1.0, gamma='auto')
+    singles = [RBFSVM(C=1.0, gamma='auto') for _ in range(G)]
+    group.fit(xs, ys).score(xts, yts)                   # warm-up of both sides: code objects, allocator
+    for clf, x, y_, xt, yt in zip(singles, xs, ys, xts, yts):
+        clf.fit(x, y_).score(xt, yt)
+    keys = ('gram', 'solve', 'predict')
+    t = dict(group_fit=[], group_score=[], single_fit=[], single_score=[])
+    st = {side + k: [] for side in ('group_', 'single_') for k in keys}
+    for rep in range(args.repeats):                     # the two sides alternate inside every repeat
+        group.time_stages = False
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        group.fit(xs, ys)
+        t1 = time.perf_counter()
+        g_acc = group.score(xts, yts)
+        t2 = time.perf_counter()
+        t['group_fit'].append(t1 - t0)
+        t['group_score'].append(t2 - t1)
+        fit_s = score_s = 0.0
+        s_acc = []
+        for clf, x, y_, xt, yt in zip(singles, xs, ys, xts, yts):
+            clf.time_stages = False
+            t0 = time.perf_counter()
+            clf.fit(x, y_)
+            t1 = time.perf_counter()
+            s_acc.append(clf.score(xt, yt))
+            t2 = time.perf_counter()
+            fit_s += t1 - t0
+            score_s += t2 - t1
+        t['single_fit'].append(fit_s)
+        t['single_score'].append(score_s)
+        group.time_stages = True                        # passes of their own: the events synchronise between the stages
+        group.fit(xs, ys)
+        group.score(xts, yts)
+        tot = dict.fromkeys(keys, 0.0)
+        for clf, x, y_, xt, yt in zip(singles, xs, ys, xts, yts):
+            clf.time_stages = True
+            clf.fit(x, y_)
+            clf.score(xt, yt)
+            for k in keys:
+                tot[k] += clf.times_[k]
+        for k in keys:
+            st['group_' + k].append(group.times_[k])
+            st['single_' + k].append(tot[k])
+    if g_acc != s_acc or any(group[p].n_iter_.tobytes() != singles[p].n_iter_.tobytes() for p in range(G)):
+        raise SystemExit("svm_bench: the grouped and the single results differ")
+    med = lambda v: round(float(np.median(v)), 6)
+    out = dict(labeled=len(ys[0]), d=xs[0].shape[1], group=G, test_rows=[len(v) for v in yts], repeats=args.repeats)
+    for k, v in list(t.items()) + list(st.items()):
+        out[k + '_s'] = med(v)
+    for k in ('fit', 'score') + keys:
+        out[k + '_ratio_single_over_group'] = round(float(np.median((t if k in ('fit', 'score') else st)['single_' + k])
+                                                          / np.median((t if k in ('fit', 'score') else st)['group_' + k])), 2)
+    most = max(int(group[p].n_iter_.max()) for p in range(G))
+    out.update(iterations_max_per_problem=[int(group[p].n_iter_.max()) for p in range(G)],
+               group_solve_us_per_update_of_slowest_pair=round(1e6 * float(np.median(st['group_solve'])) / most, 3),
+               single_solve_us_per_update_of_slowest_pairs=round(1e6 * float(np.median(st['single_solve']))
+                                                                 / sum(int(c.n_iter_.max()) for c in singles), 3),
+               gram_mbytes_group=round(sum(4e-6 * len(v) ** 2 for v in ys), 1), test_error=[round(1.0 - a, 6) for a in g_acc])
+    return out
 
 
 if __name__ == "__main__":
