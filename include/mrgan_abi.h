@@ -256,6 +256,29 @@ int mrgan_svm_solve(const float* k_dev, int64_t ld_k, int64_t n, int32_t num_cla
 int mrgan_svm_decide(const float* kt_dev, int64_t ld_kt, int64_t m, int64_t n, int32_t num_classes, const int64_t* class_start_host,
                      const double* coef_dev, const double* rho_dev, double* dec_dev, int32_t* labels_dev, mrgan_stream stream);
 
+/* The other libsvm classifiers of the reference's SVM grid (others/wganlpctsemi.py:204-208: SVC and NuSVC, kernel 'rbf' or
+ * 'linear') through the same three stages.  Rows, classes, pairs and limits are those of the block above.
+ *   mrgan_svm_kernel_matrix  mrgan_svm_gram with a kernel kind.  MRGAN_SVM_KERNEL_RBF is mrgan_svm_gram bit for bit.
+ *                     MRGAN_SVM_KERNEL_LINEAR writes out[a, b] = A_a . B_b (the same k-ordered fp32 chain; gamma is ignored).
+ *                     With a_dev == b_dev the result is symmetric bit for bit; its diagonal is what the chain gives for |x|^2.
+ *                     Any other kind is an error.
+ *   mrgan_svm_solve_nu  libsvm's nu-SVC solver (Solver_NU: SMO inside each sign, second-order working-set selection, no
+ *                     shrinking) on a precomputed n x n kernel matrix, one workgroup per pair; 0 < nu <= 1.  Stops at
+ *                     max(Gmaxp + Gmaxp2, Gmaxn + Gmaxn2) < tol or after max_iter updates.  coef_dev: alpha_t y_t / r in
+ *                     mrgan_svm_solve's layout (0 <= alpha <= 1, each sign's alpha sum to nu l / 2 over the pair's l rows);
+ *                     rho_dev: [pairs] rho / r; r_dev (optional): [pairs] r, so coef * r gives alpha y back; iters_dev as in
+ *                     mrgan_svm_solve (0 where the start point is already optimal).  r <= 0 is not guarded, as in libsvm: the
+ *                     coefficients are then non-finite or negated.  nu is infeasible for a pair (i, j) when
+ *                     nu (n_i + n_j) / 2 > min(n_i, n_j): an error before any launch, its message names the pair.
+ *                     Results are bit-identical from run to run.
+ * mrgan_svm_decide serves all four classifiers unchanged: it sees kernel values, coefficients and rho only. */
+enum { MRGAN_SVM_KERNEL_RBF = 0, MRGAN_SVM_KERNEL_LINEAR = 1 };
+int mrgan_svm_kernel_matrix(int32_t kernel, const float* a_dev, int64_t ld_a, int64_t m, const float* b_dev, int64_t ld_b, int64_t n,
+                            int64_t d, float gamma, float* out_dev, int64_t ld_out, mrgan_stream stream);
+int mrgan_svm_solve_nu(const float* k_dev, int64_t ld_k, int64_t n, int32_t num_classes, const int64_t* class_start_host, double nu,
+                       double tol, int32_t max_iter, double* coef_dev, double* rho_dev, double* r_dev, int32_t* iters_dev,
+                       mrgan_stream stream);
+
 /* The same three entries for a GROUP of 1 .. MRGAN_SVM_MAX_GROUP independent problems (the folds of a table cell) in ONE launch
  * each.  The problems are ragged -- every item has its own row counts, class sizes, pitches and buffers -- and share d, gamma,
  * num_classes, C, tol and max_iter.  items_host is a host array of `count` descriptors, read during the call only; the calls

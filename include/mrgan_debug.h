@@ -280,6 +280,9 @@ int mrgan_debug_adam(const mrgan_debug_adam_desc* d, uint32_t next_out[4], mrgan
 /* mrgan_svm_gram with the block tile forced (tile = 64 or 128; 0 = the shape's own choice): both tiles give the same bits */
 int mrgan_debug_svm_gram(const float* a_dev, int64_t ld_a, int64_t m, const float* b_dev, int64_t ld_b, int64_t n, int64_t d, float gamma,
                          float* out_dev, int64_t ld_out, int32_t tile, mrgan_stream stream);
+/* mrgan_svm_kernel_matrix with the block tile forced in the same way */
+int mrgan_debug_svm_kernel_matrix(int32_t kernel, const float* a_dev, int64_t ld_a, int64_t m, const float* b_dev, int64_t ld_b, int64_t n,
+                                  int64_t d, float gamma, float* out_dev, int64_t ld_out, int32_t tile, mrgan_stream stream);
 /* mrgan_svm_gram_group with the launch's one tile forced in the same way */
 int mrgan_debug_svm_gram_group(const mrgan_svm_gram_item* items_host, int32_t count, int64_t d, float gamma, int32_t tile, mrgan_stream stream);
 

@@ -1267,6 +1267,25 @@ int mrgan_svm_decide(const float* kt_dev, int64_t ld_kt, int64_t m, int64_t n, i
     return r ? fail(r, "%s", msg) : 0;
 }
 
+int mrgan_svm_kernel_matrix(int32_t kernel, const float* a_dev, int64_t ld_a, int64_t m, const float* b_dev, int64_t ld_b, int64_t n,
+                            int64_t d, float gamma, float* out_dev, int64_t ld_out, mrgan_stream stream) {
+    const char* msg = "";
+    const int r = launch_svm_kernel_matrix(kernel, a_dev, (long)ld_a, (long)m, b_dev, (long)ld_b, (long)n, (long)d, gamma, out_dev,
+                                           (long)ld_out, 0, (hipStream_t)stream, &msg);
+    return r ? fail(r, "%s", msg) : 0;
+}
+
+int mrgan_svm_solve_nu(const float* k_dev, int64_t ld_k, int64_t n, int32_t num_classes, const int64_t* class_start_host, double nu,
+                       double tol, int32_t max_iter, double* coef_dev, double* rho_dev, double* r_dev, int32_t* iters_dev,
+                       mrgan_stream stream) {
+    const char* msg = "";
+    int bi = -1, bj = -1;
+    const int r = launch_svm_solve_nu(k_dev, (long)ld_k, (long)n, num_classes, class_start_host, nu, tol, max_iter, coef_dev, rho_dev,
+                                      r_dev, iters_dev, (hipStream_t)stream, &msg, &bi, &bj);
+    if (r && bi >= 0) return fail(r, "%s for the pair of classes %d and %d", msg, bi, bj);
+    return r ? fail(r, "%s", msg) : 0;
+}
+
 int mrgan_svm_gram_group(const mrgan_svm_gram_item* items_host, int32_t count, int64_t d, float gamma, mrgan_stream stream) {
     const char* msg = "";
     int item = -1;

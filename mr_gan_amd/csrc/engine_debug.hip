@@ -691,6 +691,14 @@ int mrgan_debug_svm_gram(const float* a_dev, int64_t ld_a, int64_t m, const floa
     return r ? fail(r, "%s", msg) : 0;
 }
 
+int mrgan_debug_svm_kernel_matrix(int32_t kernel, const float* a_dev, int64_t ld_a, int64_t m, const float* b_dev, int64_t ld_b, int64_t n,
+                                  int64_t d, float gamma, float* out_dev, int64_t ld_out, int32_t tile, mrgan_stream stream) {
+    const char* msg = "";
+    const int r = launch_svm_kernel_matrix(kernel, a_dev, (long)ld_a, (long)m, b_dev, (long)ld_b, (long)n, (long)d, gamma, out_dev,
+                                           (long)ld_out, tile, (hipStream_t)stream, &msg);
+    return r ? fail(r, "%s", msg) : 0;
+}
+
 int mrgan_debug_svm_gram_group(const mrgan_svm_gram_item* items_host, int32_t count, int64_t d, float gamma, int32_t tile, mrgan_stream stream) {
     const char* msg = "";
     int item = -1;

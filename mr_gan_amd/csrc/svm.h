@@ -1,4 +1,5 @@
-// RBF-kernel C-SVC of the SVM baseline (mr_svm.py:106) on the device (svm.hip): Gram matrix, SMO solver, one-vs-one vote.
+// The libsvm classifiers of the SVM baseline on the device (svm.hip): Gram matrix (RBF, mr_svm.py:106, or linear), SMO solver
+// (C-SVC or nu-SVC), one-vs-one vote.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,7 +16,7 @@ constexpr int SVM_MAX_PAIRS = SVM_MAX_CLASSES * (SVM_MAX_CLASSES - 1) / 2;
 // first row of every class in the class-sorted row order, start[num_classes] = n (passed to the kernels by value)
 struct SvmClasses { int start[SVM_MAX_CLASSES + 1]; };
 
-// All three: 0 on success, -1 bad argument, -10 HIP failure (message in *err, static storage).
+// All of them: 0 on success, -1 bad argument, -10 HIP failure (message in *err, static storage).
 // out[a, b] = exp(-gamma * max(0, |A_a|^2 + |B_b|^2 - 2 A_a . B_b)); tile: 0 = chosen from the shape, 64 or 128 = forced
 int launch_svm_gram(const float* a, long ld_a, long m, const float* b, long ld_b, long n, long d, float gamma, float* out, long ld_out,
                     int tile, hipStream_t s, const char** err);
@@ -23,6 +24,14 @@ int launch_svm_solve(const float* k, long ld_k, long n, int num_classes, const i
                      double* coef, double* rho, int* iters, hipStream_t s, const char** err);
 int launch_svm_decide(const float* kt, long ld_kt, long m, long n, int num_classes, const int64_t* class_start, const double* coef,
                       const double* rho, double* dec, int* labels, hipStream_t s, const char** err);
+// launch_svm_gram with a kernel kind: MRGAN_SVM_KERNEL_RBF is launch_svm_gram itself (the same kernel, the same bits);
+// MRGAN_SVM_KERNEL_LINEAR writes out[a, b] = A_a . B_b, the same k-ordered chain, and ignores gamma
+int launch_svm_kernel_matrix(int kind, const float* a, long ld_a, long m, const float* b, long ld_b, long n, long d, float gamma, float* out,
+                             long ld_out, int tile, hipStream_t s, const char** err);
+// libsvm's nu-SVC (Solver_NU) on a precomputed kernel matrix: coef = alpha y / r, rho / r, r itself (r_out optional), iterations.
+// An infeasible nu is an error before any launch: *bad_i, *bad_j = the classes of the first such pair (-1 otherwise).
+int launch_svm_solve_nu(const float* k, long ld_k, long n, int num_classes, const int64_t* class_start, double nu, double tol, int max_iter,
+                        double* coef, double* rho, double* r_out, int* iters, hipStream_t s, const char** err, int* bad_i, int* bad_j);
 
 // The same three for up to SVM_MAX_GROUP ragged problems in one launch each (items: host arrays of the ABI's descriptors,
 // copied into the kernel arguments).  Every item gets its single entry's checks before any launch; *bad_item = the item a

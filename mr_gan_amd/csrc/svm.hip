@@ -8,6 +8,9 @@
 //                      (fp64) stay in LDS for the whole solve, an iteration is two block reductions (working-set selection
 //                      WSS2) and two coalesced fp32 Gram rows.  No grid barrier, nothing polls memory, every loop ends at max_iter.
 //   svm_decide_kernel  per test row: the pairs' decision values (fp64 sums) and the one-vs-one vote.
+// The other libsvm classifiers of the reference's grid (others/wganlpctsemi.py:205-208) reuse the three stages:
+//   svm_gram_kernel<TS, LINEAR>  K[a, b] = A_a . B_b: the same chain, no norms, no expf (SVC / NuSVC(kernel='linear'))
+//   svm_smo_nu_kernel  libsvm's nu-SVC (solve_nu_svc, Solver_NU) without shrinking, under svm_smo_kernel's discipline
 //
 // Each has a grouped twin (svm_*_group_kernel) for up to SVM_MAX_GROUP ragged problems in one launch: the same __device__ body
 // (gram_tile, smo_pair, decide_row), a block finding its problem from blockIdx through the descriptors in the kernel arguments.
@@ -22,9 +25,11 @@ namespace mrgan {
 
 namespace {
 constexpr int BK = 16;
+constexpr int RBF = MRGAN_SVM_KERNEL_RBF, LINEAR = MRGAN_SVM_KERNEL_LINEAR;
 
-// one TS x TS tile of the window, rows from row_blk and columns from col_blk: the body of the single and of the grouped kernel
-template <int TS>
+// one TS x TS tile of the window, rows from row_blk and columns from col_blk: the body of the single and of the grouped kernel.
+// KIND == LINEAR writes the dot product's chain itself: no norms, no expf, gamma unused.
+template <int TS, int KIND = RBF>
 __device__ __forceinline__ void gram_tile(const float* __restrict__ A, long ld_a, int M, const float* __restrict__ B, long ld_b, int N, int D,
                                           float gamma, float* __restrict__ out, long ld_out, int row_blk, int col_blk) {
     constexpr int LDT = TS, MR = TS / 64, KPT = TS / 16;      // KPT: k values staged per thread
@@ -74,7 +79,7 @@ __device__ __forceinline__ void gram_tile(const float* __restrict__ A, long ld_a
         }
         __syncthreads();
         if (k0 + BK < D) load_tile(k0 + BK);      // in flight under the MFMAs below
-        if (t < 2 * TS) {
+        if (KIND == RBF && t < 2 * TS) {
 #pragma unroll
             for (int kk = 0; kk < BK; ++kk) {
                 const float v = nsrc[kk * LDT];
@@ -96,8 +101,10 @@ __device__ __forceinline__ void gram_tile(const float* __restrict__ A, long ld_a
                     acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
         }
     }
-    if (t < 2 * TS) nrm[t] = nacc;
-    __syncthreads();
+    if (KIND == RBF) {
+        if (t < 2 * TS) nrm[t] = nacc;
+        __syncthreads();
+    }
 
     const int lr = lane & 31, lh = lane >> 5;
 #pragma unroll
@@ -106,21 +113,25 @@ __device__ __forceinline__ void gram_tile(const float* __restrict__ A, long ld_a
         for (int ni = 0; ni < MR; ++ni) {
             const int lc = (wn * MR + ni) * 32 + lr, col = col_blk + lc;
             if (col >= N) continue;
-            const float nb = nrm[TS + lc];
+            const float nb = KIND == RBF ? nrm[TS + lc] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int lrow = (wm * MR + mi) * 32 + acc_row(r, lh), row = row_blk + lrow;
                 if (row >= M) continue;
-                const float d2 = fmaxf(0.f, fmaf(-2.f, acc[mi][ni][r], nrm[lrow] + nb));
-                out[(long)row * ld_out + col] = expf(-gamma * d2);
+                if (KIND == RBF) {
+                    const float d2 = fmaxf(0.f, fmaf(-2.f, acc[mi][ni][r], nrm[lrow] + nb));
+                    out[(long)row * ld_out + col] = expf(-gamma * d2);
+                } else {
+                    out[(long)row * ld_out + col] = acc[mi][ni][r];
+                }
             }
         }
 }
 
-template <int TS>
+template <int TS, int KIND = RBF>
 __global__ __launch_bounds__(256) void svm_gram_kernel(const float* __restrict__ A, long ld_a, int M, const float* __restrict__ B, long ld_b,
                                                        int N, int D, float gamma, float* __restrict__ out, long ld_out) {
-    gram_tile<TS>(A, ld_a, M, B, ld_b, N, D, gamma, out, ld_out, blockIdx.y * TS, blockIdx.x * TS);
+    gram_tile<TS, KIND>(A, ld_a, M, B, ld_b, N, D, gamma, out, ld_out, blockIdx.y * TS, blockIdx.x * TS);
 }
 
 // The descriptors of a group reach the kernels BY VALUE in the kernel arguments (no device table: the entries neither
@@ -360,6 +371,224 @@ __global__ __launch_bounds__(SMO_THREADS) void svm_smo_group_kernel(const SmoGro
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// nu-SVC: libsvm's solve_nu_svc / Solver_NU without shrinking, under smo_pair's discipline (one workgroup per pair, fp64 alpha
+// and G in LDS, two block reductions per iteration, every loop ends at max_iter).  It shares take_max and pair_classes with
+// smo_pair and nothing else.  The box is [0, 1], the linear term 0, and the two signs never mix: i and j of an update share
+// their sign, so an iteration needs row ip or row in of the Gram matrix per COLUMN (by the column's sign) for the selection,
+// and the chosen one of the two whole rows for the update.  Both rows are read up front in one round trip, row j in a second.
+// fp64 contraction is off: every product and sum rounds as libsvm's does, and the sums run in libsvm's order, so a pair
+// follows libsvm's pivots for as long as the two agree bit for bit.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void smo_nu_pair(const float* __restrict__ K, long ld_k, int n, int pair, int ci, int cj, int s1, int n1, int s2, int n2,
+                                            double nu, double tol, int max_iter, double* __restrict__ coef, double* __restrict__ rho,
+                                            double* __restrict__ r_out, int* __restrict__ iters) {
+#pragma clang fp contract(off)
+    __shared__ double s_alpha[SVM_MAX_PAIR], s_G[SVM_MAX_PAIR];
+    __shared__ float s_diag[SVM_MAX_PAIR], s_Km[SVM_MAX_PAIR];      // s_Km[t]: K[ip][t] on class i's columns, K[in][t] on class j's
+    __shared__ double r1_p[SMO_WAVES], r1_n[SMO_WAVES], r2_v[SMO_WAVES], r2_p[SMO_WAVES], r2_n[SMO_WAVES];
+    __shared__ int r1_ip[SMO_WAVES], r1_in[SMO_WAVES], r2_i[SMO_WAVES];
+    __shared__ double s_r;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l = n1 + n2;                                   // <= SVM_MAX_PAIR (checked by the launcher)
+    auto grow = [&](int t) { return t < n1 ? s1 + t : s2 + (t - n1); };     // row of the Gram matrix behind local index t
+
+    // ---- start point: per sign alpha = min(1, remaining), remaining from nu l / 2.  remaining after k rows is nu l / 2 - k
+    // exactly (a double minus a smaller integer is representable), so row k of its sign holds min(1, max(0, nu l / 2 - k)) ----
+    const double half = nu * (double)l / 2;
+    int own[SMO_PER], gown[SMO_PER];
+    bool pos[SMO_PER];
+#pragma unroll
+    for (int e = 0; e < SMO_PER; ++e) {
+        const int t = tid + e * SMO_THREADS;
+        own[e] = t;
+        gown[e] = t < l ? grow(t) : 0;
+        pos[e] = t < n1;
+        if (t < l) {
+            s_alpha[t] = fmin(1.0, fmax(0.0, half - (double)(t < n1 ? t : t - n1)));
+            s_diag[t] = K[(long)gown[e] * ld_k + gown[e]];
+        }
+    }
+    __syncthreads();
+    // ---- initial gradient: G_t = sum over alpha_s > 0, ascending s, of alpha_s * Q_st (Q a float, the sum fp64): a thread
+    // owns its t and walks the rows s; the reads K[row(s)][own t] are coalesced ----
+    {
+        double g[SMO_PER];
+#pragma unroll
+        for (int e = 0; e < SMO_PER; ++e) g[e] = 0.0;
+        for (int s = 0; s < l; ++s) {
+            const double a = s_alpha[s];                     // block-uniform
+            if (!(a > 0.0)) continue;
+            const long gs = grow(s);
+            const bool spos = s < n1;
+#pragma unroll
+            for (int e = 0; e < SMO_PER; ++e)
+                if (own[e] < l) {
+                    const float k = K[gs * ld_k + gown[e]];
+                    g[e] += a * (double)(spos == pos[e] ? k : -k);
+                }
+        }
+#pragma unroll
+        for (int e = 0; e < SMO_PER; ++e)
+            if (own[e] < l) s_G[own[e]] = g[e];
+    }
+    __syncthreads();
+
+    int it = 0;
+    while (it < max_iter) {
+        // ---- ip = argmax of -G over y = +1, alpha < 1;  in = argmax of G over y = -1, alpha > 0 ----
+        double vp = -INFINITY, vn = -INFINITY;
+        int ip = -1, in = -1;
+#pragma unroll
+        for (int e = 0; e < SMO_PER; ++e) {
+            const int t = own[e];
+            if (t < l) {
+                const double a = s_alpha[t], g = s_G[t];
+                if (pos[e]) { if (a < 1.0) take_max(vp, ip, -g, t); }
+                else { if (a > 0.0) take_max(vn, in, g, t); }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            take_max(vp, ip, __shfl_xor(vp, o, 64), __shfl_xor(ip, o, 64));
+            take_max(vn, in, __shfl_xor(vn, o, 64), __shfl_xor(in, o, 64));
+        }
+        if (lane == 0) { r1_p[wave] = vp; r1_ip[wave] = ip; r1_n[wave] = vn; r1_in[wave] = in; }
+        __syncthreads();                                                           // (1)
+        vp = r1_p[0]; ip = r1_ip[0]; vn = r1_n[0]; in = r1_in[0];
+#pragma unroll
+        for (int w = 1; w < SMO_WAVES; ++w) { take_max(vp, ip, r1_p[w], r1_ip[w]); take_max(vn, in, r1_n[w], r1_in[w]); }
+        const double Gmaxp = vp, Gmaxn = vn;                                       // -inf with index -1 where a sign has no candidate
+
+        // rows ip and in, whole: the selection reads each on its own sign's columns, the update the one that becomes i
+        const long gp = ip >= 0 ? grow(ip) : 0, gn = in >= 0 ? grow(in) : 0;
+        float kp[SMO_PER], kn[SMO_PER];
+#pragma unroll
+        for (int e = 0; e < SMO_PER; ++e) {
+            kp[e] = (ip >= 0 && own[e] < l) ? K[gp * ld_k + gown[e]] : 0.f;
+            kn[e] = (in >= 0 && own[e] < l) ? K[gn * ld_k + gown[e]] : 0.f;
+        }
+        const double QD_p = ip >= 0 ? (double)s_diag[ip] : 0.0, QD_n = in >= 0 ? (double)s_diag[in] : 0.0;
+
+        // ---- j = argmin of -b^2 / a inside its own sign, against Q_ip or Q_in;  Gmaxp2 = max G over y = +1, alpha > 0;
+        // Gmaxn2 = max -G over y = -1, alpha < 1 ----
+        double ov = -INFINITY, gp2 = -INFINITY, gn2 = -INFINITY;                   // ov holds +b^2/a: the largest is libsvm's smallest
+        int oj = -1;
+#pragma unroll
+        for (int e = 0; e < SMO_PER; ++e) {
+            const int t = own[e];
+            if (t < l) {
+                const float km = pos[e] ? kp[e] : kn[e];
+                s_Km[t] = km;
+                const double a = s_alpha[t], g = s_G[t];
+                if (pos[e] ? a > 0.0 : a < 1.0) {
+                    const double gd = pos[e] ? Gmaxp + g : Gmaxn - g;
+                    if (pos[e]) gp2 = fmax(gp2, g); else gn2 = fmax(gn2, -g);
+                    if (gd > 0.0) {                                                // never with Gmaxp / Gmaxn = -inf
+                        double q = (pos[e] ? QD_p : QD_n) + (double)s_diag[t] - 2.0 * (double)km;
+                        if (!(q > 0.0)) q = SMO_TAU;
+                        take_max(ov, oj, (gd * gd) / q, t);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            take_max(ov, oj, __shfl_xor(ov, o, 64), __shfl_xor(oj, o, 64));
+            gp2 = fmax(gp2, __shfl_xor(gp2, o, 64));
+            gn2 = fmax(gn2, __shfl_xor(gn2, o, 64));
+        }
+        if (lane == 0) { r2_v[wave] = ov; r2_i[wave] = oj; r2_p[wave] = gp2; r2_n[wave] = gn2; }
+        __syncthreads();                                                           // (2)
+        ov = r2_v[0]; oj = r2_i[0]; gp2 = r2_p[0]; gn2 = r2_n[0];
+#pragma unroll
+        for (int w = 1; w < SMO_WAVES; ++w) { take_max(ov, oj, r2_v[w], r2_i[w]); gp2 = fmax(gp2, r2_p[w]); gn2 = fmax(gn2, r2_n[w]); }
+        if (fmax(Gmaxp + gp2, Gmaxn + gn2) < tol || oj < 0) break;                 // block-uniform
+        const int j = oj;
+        const bool jpos = j < n1;
+        const int i = jpos ? ip : in;                                              // >= 0: j was a candidate of that sign
+
+        const long gj = grow(j);
+        float kj[SMO_PER];
+#pragma unroll
+        for (int e = 0; e < SMO_PER; ++e) kj[e] = own[e] < l ? K[gj * ld_k + gown[e]] : 0.f;
+        const double a_i = s_alpha[i], G_i = s_G[i], a_j = s_alpha[j], G_j = s_G[j];
+
+        // ---- libsvm's equal-sign update with bound 1 (every thread computes the same values) ----
+        double q = (jpos ? QD_p : QD_n) + (double)s_diag[j] - 2.0 * (double)s_Km[j];
+        if (!(q > 0.0)) q = SMO_TAU;
+        const double delta = (G_i - G_j) / q, sum = a_i + a_j;
+        double na_i = a_i - delta, na_j = a_j + delta;
+        if (sum > 1.0) { if (na_i > 1.0) { na_i = 1.0; na_j = sum - 1.0; } }
+        else { if (na_j < 0.0) { na_j = 0.0; na_i = sum; } }
+        if (sum > 1.0) { if (na_j > 1.0) { na_j = 1.0; na_i = sum - 1.0; } }
+        else { if (na_i < 0.0) { na_i = 0.0; na_j = sum; } }
+        const double da_i = na_i - a_i, da_j = na_j - a_j;
+        __syncthreads();                                                           // (3) alpha, G, Km of i and j are read everywhere
+#pragma unroll
+        for (int e = 0; e < SMO_PER; ++e) {
+            const int t = own[e];
+            if (t < l) {
+                if (t == i) s_alpha[t] = na_i;
+                if (t == j) s_alpha[t] = na_j;
+                const float ki = jpos ? kp[e] : kn[e];
+                const bool same = pos[e] == jpos;                                  // y_i = y_j: Q_i[t] = +-K_it, Q_j[t] = +-K_jt
+                s_G[t] += (double)(same ? ki : -ki) * da_i + (double)(same ? kj[e] : -kj[e]) * da_j;
+            }
+        }
+        ++it;
+        // the next reads of another thread's alpha / G come after barrier (1) of the next iteration
+    }
+    __syncthreads();
+
+    // ---- Solver_NU::calculate_rho by one thread in libsvm's order (the sums of the free G round as libsvm's), then
+    // coef = alpha y / r and rho / r ----
+    if (tid == 0) {
+        double ub1 = INFINITY, ub2 = INFINITY, lb1 = -INFINITY, lb2 = -INFINITY, sum1 = 0.0, sum2 = 0.0;
+        int nf1 = 0, nf2 = 0;
+        for (int t = 0; t < l; ++t) {
+            const double a = s_alpha[t], g = s_G[t];
+            if (t < n1) {
+                if (a >= 1.0) lb1 = fmax(lb1, g);
+                else if (a <= 0.0) ub1 = fmin(ub1, g);
+                else { ++nf1; sum1 += g; }
+            } else {
+                if (a >= 1.0) lb2 = fmax(lb2, g);
+                else if (a <= 0.0) ub2 = fmin(ub2, g);
+                else { ++nf2; sum2 += g; }
+            }
+        }
+        const double r1 = nf1 > 0 ? sum1 / nf1 : (ub1 + lb1) / 2, r2 = nf2 > 0 ? sum2 / nf2 : (ub2 + lb2) / 2;
+        const double r = (r1 + r2) / 2;
+        s_r = r;
+        rho[pair] = ((r1 - r2) / 2) / r;
+        if (r_out) r_out[pair] = r;
+        iters[pair] = it;
+    }
+    __syncthreads();
+    const double r = s_r;
+#pragma unroll
+    for (int e = 0; e < SMO_PER; ++e) {
+        const int t = own[e];
+        if (t < l) {
+            const double c = s_alpha[t] * ((pos[e] ? 1.0 : -1.0) / r);             // libsvm: alpha[i] *= y[i] / r
+            if (t < n1) coef[(long)(cj - 1) * n + gown[e]] = c;                    // libsvm's sv_coef rows: class i's rows against class j
+            else coef[(long)ci * n + gown[e]] = c;
+        }
+    }
+}
+
+__global__ __launch_bounds__(SMO_THREADS) void svm_smo_nu_kernel(const float* __restrict__ K, long ld_k, int n, int num_classes,
+                                                                 const SvmClasses cls, double nu, double tol, int max_iter,
+                                                                 double* __restrict__ coef, double* __restrict__ rho,
+                                                                 double* __restrict__ r_out, int* __restrict__ iters) {
+    int ci, cj;
+    pair_classes(blockIdx.x, num_classes, ci, cj);
+    const int s1 = cls.start[ci], n1 = cls.start[ci + 1] - s1, s2 = cls.start[cj], n2 = cls.start[cj + 1] - s2;
+    smo_nu_pair(K, ld_k, n, blockIdx.x, ci, cj, s1, n1, s2, n2, nu, tol, max_iter, coef, rho, r_out, iters);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // decision values and the vote: one block per test row, a wave per pair (round robin)
 // ---------------------------------------------------------------------------------------------------------------------
 // test row `row` of one problem by one block: the body of the single and of the grouped kernel
@@ -434,22 +663,27 @@ int fill_classes(long n, int num_classes, const int64_t* class_start, SvmClasses
 // The argument checks of the three entries: a single call makes them on its one problem, a grouped call on every item, before
 // any launch.
 int check_gram(const float* a, long ld_a, long m, const float* b, long ld_b, long n, long d, float gamma, const float* out, long ld_out,
-               int tile, const char** err) {
+               int tile, const char** err, int kind = RBF) {
+    if (kind != RBF && kind != LINEAR) { *err = "svm_gram: unknown kernel kind (MRGAN_SVM_KERNEL_RBF = 0 or MRGAN_SVM_KERNEL_LINEAR = 1)"; return -1; }
     if (!a || !b || !out) { *err = "svm_gram: null buffer"; return -1; }
     if (m < 1 || n < 1 || d < 1 || m > (1 << 21) || n > (1 << 21) || d > (1 << 24)) { *err = "svm_gram: m, n in [1, 2^21] and d in [1, 2^24]"; return -1; }
     if (ld_a < d || ld_b < d || ld_out < n) { *err = "svm_gram: row pitch smaller than the row"; return -1; }
-    if (!(gamma > 0.f) || !isfinite(gamma)) { *err = "svm_gram: gamma must be positive and finite"; return -1; }
+    if (kind == RBF && (!(gamma > 0.f) || !isfinite(gamma))) { *err = "svm_gram: gamma must be positive and finite"; return -1; }
     if (tile != 0 && tile != 64 && tile != 128) { *err = "svm_gram: tile must be 0, 64 or 128"; return -1; }
     return 0;
 }
 
-int check_solve(const float* k, long ld_k, long n, int num_classes, const int64_t* class_start, double C, double tol, int max_iter,
-                const double* coef, const double* rho, const int* iters, SvmClasses& cls, const char** err) {
+// what the C-SVC and the nu-SVC solver check alike, in two parts around their own parameter check
+int check_solve_buffers(const float* k, long ld_k, long n, int num_classes, const int64_t* class_start, const double* coef,
+                        const double* rho, const int* iters, SvmClasses& cls, const char** err) {
     if (!k || !coef || !rho || !iters) { *err = "svm_solve: null buffer"; return -1; }
     const int r = fill_classes(n, num_classes, class_start, cls, err);
     if (r) return r;
     if (ld_k < n) { *err = "svm_solve: row pitch smaller than the row"; return -1; }
-    if (!(C > 0.0) || !isfinite(C) || !(tol > 0.0) || !isfinite(tol) || max_iter < 1) { *err = "svm_solve: C, tol and max_iter must be positive"; return -1; }
+    return 0;
+}
+
+int check_solve_pair_size(int num_classes, const SvmClasses& cls, const char** err) {
     // the two largest classes make the largest pair
     int big1 = 0, big2 = 0;
     for (int c = 0; c < num_classes; ++c) {
@@ -457,6 +691,35 @@ int check_solve(const float* k, long ld_k, long n, int num_classes, const int64_
         if (sz > big1) { big2 = big1; big1 = sz; } else if (sz > big2) big2 = sz;
     }
     if (big1 + big2 > SVM_MAX_PAIR) { *err = "svm_solve: a one-vs-one pair has more than MRGAN_SVM_MAX_PAIR = 2048 rows"; return -1; }
+    return 0;
+}
+
+int check_solve(const float* k, long ld_k, long n, int num_classes, const int64_t* class_start, double C, double tol, int max_iter,
+                const double* coef, const double* rho, const int* iters, SvmClasses& cls, const char** err) {
+    const int r = check_solve_buffers(k, ld_k, n, num_classes, class_start, coef, rho, iters, cls, err);
+    if (r) return r;
+    if (!(C > 0.0) || !isfinite(C) || !(tol > 0.0) || !isfinite(tol) || max_iter < 1) { *err = "svm_solve: C, tol and max_iter must be positive"; return -1; }
+    return check_solve_pair_size(num_classes, cls, err);
+}
+
+// *bad_i, *bad_j: the classes of the first pair nu is infeasible for (libsvm's svm_check_parameter), else untouched
+int check_solve_nu(const float* k, long ld_k, long n, int num_classes, const int64_t* class_start, double nu, double tol, int max_iter,
+                   const double* coef, const double* rho, const int* iters, SvmClasses& cls, const char** err, int* bad_i, int* bad_j) {
+    int r = check_solve_buffers(k, ld_k, n, num_classes, class_start, coef, rho, iters, cls, err);
+    if (r) return r;
+    if (!(nu > 0.0) || !(nu <= 1.0)) { *err = "svm_solve_nu: nu must lie in (0, 1]"; return -1; }
+    if (!(tol > 0.0) || !isfinite(tol) || max_iter < 1) { *err = "svm_solve_nu: tol and max_iter must be positive"; return -1; }
+    r = check_solve_pair_size(num_classes, cls, err);
+    if (r) return r;
+    for (int i = 0; i < num_classes; ++i)
+        for (int j = i + 1; j < num_classes; ++j) {
+            const int ni = cls.start[i + 1] - cls.start[i], nj = cls.start[j + 1] - cls.start[j];
+            if (nu * (ni + nj) / 2 > (ni < nj ? ni : nj)) {
+                *bad_i = i; *bad_j = j;
+                *err = "svm_solve_nu: specified nu is infeasible";
+                return -1;
+            }
+        }
     return 0;
 }
 
@@ -479,9 +742,9 @@ int check_group(const void* items, int count, const char* null_msg, const char* 
 }
 }  // namespace
 
-int launch_svm_gram(const float* a, long ld_a, long m, const float* b, long ld_b, long n, long d, float gamma, float* out, long ld_out,
-                    int tile, hipStream_t s, const char** err) {
-    const int r = check_gram(a, ld_a, m, b, ld_b, n, d, gamma, out, ld_out, tile, err);
+int launch_svm_kernel_matrix(int kind, const float* a, long ld_a, long m, const float* b, long ld_b, long n, long d, float gamma, float* out,
+                             long ld_out, int tile, hipStream_t s, const char** err) {
+    const int r = check_gram(a, ld_a, m, b, ld_b, n, d, gamma, out, ld_out, tile, err, kind);
     if (r) return r;
     // 64x64 blocks while 128x128 ones would leave most CUs without work, as launch_gemm_f32 chooses; every output element is
     // the same k-ordered chain in both
@@ -489,13 +752,20 @@ int launch_svm_gram(const float* a, long ld_a, long m, const float* b, long ld_b
     const dim3 block(256);
     if (small) {
         const dim3 grid(ceil_div(n, 64), ceil_div(m, 64));
-        MRGAN_LAUNCH((svm_gram_kernel<64>), grid, block, 0, s, a, ld_a, (int)m, b, ld_b, (int)n, (int)d, gamma, out, ld_out);
+        if (kind == RBF) MRGAN_LAUNCH((svm_gram_kernel<64>), grid, block, 0, s, a, ld_a, (int)m, b, ld_b, (int)n, (int)d, gamma, out, ld_out);
+        else MRGAN_LAUNCH((svm_gram_kernel<64, LINEAR>), grid, block, 0, s, a, ld_a, (int)m, b, ld_b, (int)n, (int)d, 0.f, out, ld_out);
     } else {
         const dim3 grid(ceil_div(n, 128), ceil_div(m, 128));
-        MRGAN_LAUNCH((svm_gram_kernel<128>), grid, block, 0, s, a, ld_a, (int)m, b, ld_b, (int)n, (int)d, gamma, out, ld_out);
+        if (kind == RBF) MRGAN_LAUNCH((svm_gram_kernel<128>), grid, block, 0, s, a, ld_a, (int)m, b, ld_b, (int)n, (int)d, gamma, out, ld_out);
+        else MRGAN_LAUNCH((svm_gram_kernel<128, LINEAR>), grid, block, 0, s, a, ld_a, (int)m, b, ld_b, (int)n, (int)d, 0.f, out, ld_out);
     }
     if (hipGetLastError() != hipSuccess) { *err = "svm_gram: launch failed"; return -10; }
     return 0;
+}
+
+int launch_svm_gram(const float* a, long ld_a, long m, const float* b, long ld_b, long n, long d, float gamma, float* out, long ld_out,
+                    int tile, hipStream_t s, const char** err) {
+    return launch_svm_kernel_matrix(RBF, a, ld_a, m, b, ld_b, n, d, gamma, out, ld_out, tile, s, err);
 }
 
 int launch_svm_solve(const float* k, long ld_k, long n, int num_classes, const int64_t* class_start, double C, double tol, int max_iter,
@@ -506,6 +776,19 @@ int launch_svm_solve(const float* k, long ld_k, long n, int num_classes, const i
     const int pairs = num_classes * (num_classes - 1) / 2;
     MRGAN_LAUNCH(svm_smo_kernel, dim3(pairs), dim3(SMO_THREADS), 0, s, k, ld_k, (int)n, num_classes, cls, C, tol, max_iter, coef, rho, iters);
     if (hipGetLastError() != hipSuccess) { *err = "svm_solve: launch failed"; return -10; }
+    return 0;
+}
+
+int launch_svm_solve_nu(const float* k, long ld_k, long n, int num_classes, const int64_t* class_start, double nu, double tol, int max_iter,
+                        double* coef, double* rho, double* r_out, int* iters, hipStream_t s, const char** err, int* bad_i, int* bad_j) {
+    SvmClasses cls;
+    *bad_i = *bad_j = -1;
+    const int r = check_solve_nu(k, ld_k, n, num_classes, class_start, nu, tol, max_iter, coef, rho, iters, cls, err, bad_i, bad_j);
+    if (r) return r;
+    const int pairs = num_classes * (num_classes - 1) / 2;
+    MRGAN_LAUNCH(svm_smo_nu_kernel, dim3(pairs), dim3(SMO_THREADS), 0, s, k, ld_k, (int)n, num_classes, cls, nu, tol, max_iter, coef, rho,
+                 r_out, iters);
+    if (hipGetLastError() != hipSuccess) { *err = "svm_solve_nu: launch failed"; return -10; }
     return 0;
 }
 

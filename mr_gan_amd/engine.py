@@ -39,10 +39,13 @@ EXPORTS = [
     "mrgan_ae_step", "mrgan_ae_encode", "mrgan_ae_reconstruct",
     "mrgan_svm_gram", "mrgan_svm_solve", "mrgan_svm_decide", "mrgan_debug_svm_gram",
     "mrgan_svm_gram_group", "mrgan_svm_solve_group", "mrgan_svm_decide_group", "mrgan_debug_svm_gram_group",
+    "mrgan_svm_kernel_matrix", "mrgan_svm_solve_nu", "mrgan_debug_svm_kernel_matrix",
 ]
 SVM_MAX_PAIR = 2048           # MRGAN_SVM_MAX_PAIR: rows of one one-vs-one problem
 SVM_MAX_CLASSES = 32
 SVM_MAX_GROUP = 16            # MRGAN_SVM_MAX_GROUP: problems of one grouped launch
+SVM_KERNEL_RBF, SVM_KERNEL_LINEAR = 0, 1
+SVM_KERNELS = {'rbf': SVM_KERNEL_RBF, 'linear': SVM_KERNEL_LINEAR}
 SAL_LOGIT, SAL_XENT, SAL_MSE = 0, 1, 2
 SAL_RAW, SAL_HEATMAP = 0, 1
 SAL_OBJECTIVES = {'logit': SAL_LOGIT, 'xent': SAL_XENT, 'mse': SAL_MSE}
@@ -264,6 +267,10 @@ def load_library(path=None):
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mrgan_svm_decide.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mrgan_svm_kernel_matrix.argtypes = [C.c_int32] + gram + [C.c_void_p]
+    lib.mrgan_debug_svm_kernel_matrix.argtypes = [C.c_int32] + gram + [C.c_int32, C.c_void_p]
+    lib.mrgan_svm_solve_nu.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_double, C.c_double, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mrgan_svm_gram_group.argtypes = [C.POINTER(SvmGramItem), C.c_int32, C.c_int64, C.c_float, C.c_void_p]
     lib.mrgan_debug_svm_gram_group.argtypes = [C.POINTER(SvmGramItem), C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_void_p]
     lib.mrgan_svm_solve_group.argtypes = [C.POINTER(SvmSolveItem), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p]

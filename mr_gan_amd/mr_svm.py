@@ -3,6 +3,10 @@ RBF-kernel SVC (C = 1) trained on the labeled subset only.  By default on scikit
 --backend hip fits and scores with mr_gan_amd.svm.RBFSVM (csrc/svm.hip: Gram matrix, SMO solver and vote on the GPU).
 
     python -m mr_gan_amd.mr_svm --tables 2 4 [-v] [--backend {sklearn,hip}] [--group-folds]
+                                [--classifier {svc-rbf,svc-linear,nu-rbf,nu-linear}]
+
+--classifier picks another libsvm classifier of the reference's wider grid (others/wganlpctsemi.py:205-208): SVC or NuSVC
+(nu = 0.5) with the RBF or the linear kernel, on either backend (hip: mr_gan_amd.svm.KernelSVM).
 
 --group-folds (with --backend hip) fits and scores the six folds of each table-2 cell, and consecutive runs of twelve objects of
 each table-4 cell, as ONE RBFSVMGroup (grouped launches over ragged problems) and prints the same lines.
@@ -18,16 +22,22 @@ import numpy as np
 
 from mr_gan_amd.data import prologue, resolve_num_classes, train_test_sets
 from mr_gan_amd.mr_gan import MODALITIES, dataset, print_lines
-from mr_gan_amd.svm import RBFSVM, RBFSVMGroup
+from mr_gan_amd.svm import KernelSVM, RBFSVM, RBFSVMGroup
 
 
 SVC_GAMMA = 'auto'
 BACKENDS = ('sklearn', 'hip')
+# kernels 0 - 3 of the reference's wider SVM grid (others/wganlpctsemi.py:205-208) -> (kernel, nu); NuSVC's nu is scikit-learn's default
+NU = 0.5
+CLASSIFIERS = {'svc-rbf': ('rbf', None), 'svc-linear': ('linear', None), 'nu-rbf': ('rbf', NU), 'nu-linear': ('linear', NU)}
 
 
-def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None, backend='sklearn'):
+def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None, backend='sklearn', classifier='svc-rbf'):
     if backend not in BACKENDS:
         raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
+    if classifier not in CLASSIFIERS:
+        raise ValueError("classifier must be one of %s, got %r" % (sorted(CLASSIFIERS), classifier))
+    kernel, nu = CLASSIFIERS[classifier]
     rs = np.random.RandomState(seed if seed is not None else np.random.randint(1 << 31))     # mr_svm.py:79 is unseeded
     num_classes = resolve_num_classes(None)
     sets = train_test_sets(X, y, trainTestSets, rs, num_classes)   # mr_svm.py:82-89
@@ -36,11 +46,16 @@ def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None
     # mr_svm.py:106 is SVC(kernel='rbf', C=1.0) under the scikit-learn of 2017 (Keras 2.0.9 era, README.md:43-48), whose default
     # kernel width was gamma='auto' = 1 / n_features.  scikit-learn >= 0.22 defaults to 'scale' (1 / (n_features * X.var())),
     # which differs on the small standardised labeled subset: pass the reference's value explicitly.
-    if backend == 'hip':
+    if backend == 'hip' and classifier == 'svc-rbf':
         svm = RBFSVM(C=1.0, gamma=SVC_GAMMA)         # the same C and kernel width; no CPU fallback behind it
-    else:
+    elif backend == 'hip':
+        svm = KernelSVM(kernel=kernel, nu=nu, C=1.0, gamma=SVC_GAMMA)
+    elif nu is None:
         from sklearn.svm import SVC
-        svm = SVC(kernel='rbf', C=1.0, gamma=SVC_GAMMA)
+        svm = SVC(kernel=kernel, C=1.0, gamma=SVC_GAMMA)
+    else:
+        from sklearn.svm import NuSVC
+        svm = NuSVC(kernel=kernel, nu=nu, gamma=SVC_GAMMA)
     svm.fit(x_labeled, y_labeled)
     testerror = 1.0 - svm.score(X_test, y_test)                    # mr_svm.py:110
     if verbose:
@@ -134,11 +149,18 @@ def main(argv=None, dataset_fn=dataset, fn=mr_svm, folds_fn=None):
     parser.add_argument('--group-folds', action='store_true',
                         help='with --backend hip: fit and score the six folds of a table-2 cell, and runs of twelve objects of a '
                              'table-4 cell, as one RBFSVMGroup (one launch set)')
+    parser.add_argument('--classifier', choices=sorted(CLASSIFIERS), default='svc-rbf',
+                        help="the libsvm classifier of the reference's grid (others/wganlpctsemi.py:205-208): SVC (C = 1) or NuSVC "
+                             "(nu = 0.5) with the RBF or the linear kernel; default svc-rbf, the baseline of mr_svm.py")
     args = parser.parse_args(argv)
     if args.group_folds and args.backend != 'hip':
         parser.error('--group-folds needs --backend hip')
+    if args.group_folds and args.classifier != 'svc-rbf':
+        parser.error('--group-folds serves --classifier svc-rbf only (RBFSVMGroup)')
     if args.backend != 'sklearn':
         fn = functools.partial(fn, backend=args.backend)
+    if args.classifier != 'svc-rbf':
+        fn = functools.partial(fn, classifier=args.classifier)
     if args.group_folds and folds_fn is None:
         folds_fn = mr_svm_folds
     hook = folds_fn if args.group_folds else None

@@ -8,10 +8,17 @@ and the vote).  There is no CPU path: without the library or a GPU every entry r
 compare against lives in tests/svm_ref.py.  RBFSVMGroup fits and scores several independent problems (the folds of a table cell)
 through the grouped entries mrgan_svm_*_group, one launch set for up to 16 of them, with RBFSVM's bits per problem.
 
+KernelSVM covers the other libsvm classifiers of the reference's wider SVM grid (others/wganlpctsemi.py:205-208) with
+RBFSVM's surface and conventions: kernel='rbf' | 'linear' through mrgan_svm_kernel_matrix (the linear Gram matrix is the
+same matrix-core chain without norms and exp), and nu=None (C-SVC, mrgan_svm_solve) or a nu in (0, 1] (nu-SVC,
+mrgan_svm_solve_nu: libsvm's Solver_NU, coefficients alpha y / r, r in r_).  mrgan_svm_decide serves every kind.  The nu
+solver's restatement lives in tests/svm_kinds_ref.py.
+
 Conventions are libsvm's: pairs (i, j), i < j, in the order of scikit-learn's decision_function_shape='ovo'; a positive
 decision value votes for classes_[i]; intercept_ = -rho.  Two classes give ONE column with that same sign (scikit-learn flips
 the sign of its binary decision_function; this class does not).
-Out of scope: shrinking, probability estimates, kernels other than RBF."""
+Out of scope: shrinking, probability estimates, class weights, polynomial and sigmoid kernels, LinearSVC (liblinear, another
+algorithm), grouped launches for KernelSVM's kinds."""
 import ctypes as C
 import warnings
 
@@ -96,16 +103,17 @@ class _DeviceSVM:
             raise RuntimeError("RBFSVM runs on the GPU only (mrgan_svm_*); no HIP device is visible and there is no CPU fallback")
 
 
-class RBFSVM(_DeviceSVM):
-    def __init__(self, C=1.0, gamma='auto', tol=1e-3, max_iter=10_000_000, device='cuda:0'):
-        _DeviceSVM.__init__(self, C, gamma, tol, max_iter, device)
-        self.classes_ = None
+class _SingleSVM(_DeviceSVM):
+    """one problem on the device, what RBFSVM and KernelSVM share: fit = kernel matrix + solve, chunked decide, the estimator's
+    surface.  A subclass names itself (_name, for the messages) and supplies _gram(a, b) -> the kernel matrix between two
+    row sets on the device, _solve(gram, n, K, iters) -> the solver launch, and may refuse class counts in _check_classes."""
+    _name = None
 
-    def _gram(self, a, b):
-        out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=self.device)
-        self._call("mrgan_svm_gram", a.data_ptr(), a.stride(0), a.shape[0], b.data_ptr(), b.stride(0), b.shape[0], a.shape[1],
-                   self._gamma, out.data_ptr(), out.stride(0))
-        return out
+    def _check_classes(self, classes, class_start):
+        pass
+
+    def _after_solve(self):
+        pass
 
     # ---- the estimator ----
     def fit(self, X, y):
@@ -115,11 +123,12 @@ class RBFSVM(_DeviceSVM):
             raise ValueError("X has %d rows, y has %d labels" % (X32.shape[0], len(y)))
         K = len(classes)
         if not 2 <= K <= E.SVM_MAX_CLASSES:
-            raise ValueError("RBFSVM needs 2 to %d classes, got %d" % (E.SVM_MAX_CLASSES, K))
+            raise ValueError("%s needs 2 to %d classes, got %d" % (self._name, E.SVM_MAX_CLASSES, K))
         sizes = np.sort(np.diff(class_start))
         if sizes[-1] + sizes[-2] > E.SVM_MAX_PAIR:
             raise ValueError("the two largest classes have %d rows together; one one-vs-one problem holds at most %d "
                              "(MRGAN_SVM_MAX_PAIR)" % (sizes[-1] + sizes[-2], E.SVM_MAX_PAIR))
+        self._check_classes(classes, class_start)
         self._require_gpu()
         n, d = X32.shape
         self._gamma = 1.0 / d if isinstance(self.gamma, str) else float(self.gamma)
@@ -130,22 +139,22 @@ class RBFSVM(_DeviceSVM):
         self._rho = torch.empty(K * (K - 1) // 2, dtype=torch.float64, device=self.device)
         iters = torch.empty(K * (K - 1) // 2, dtype=torch.int32, device=self.device)
         gram = self._timed('gram', lambda: self._gram(self._x, self._x))
-        self._timed('solve', lambda: self._call("mrgan_svm_solve", gram.data_ptr(), gram.stride(0), n, K, self._cs, self.C, self.tol,
-                                                self.max_iter, self._coef.data_ptr(), self._rho.data_ptr(), iters.data_ptr()))
+        self._timed('solve', lambda: self._solve(gram, n, K, iters))
         self.n_iter_ = iters.cpu().numpy()
         del gram
-        self.classes_, self._order, self.n_features_in_ = classes, order, d
         self.dual_coef_dense_ = unsort_coef(self._coef.cpu().numpy(), order)
         self.intercept_ = -self._rho.cpu().numpy()
+        self._after_solve()
+        self.classes_, self._order, self.n_features_in_ = classes, order, d
         if (self.n_iter_ >= self.max_iter).any():
-            warnings.warn("RBFSVM: %d of %d one-vs-one problems stopped at max_iter = %d before reaching tol = %g"
-                          % (int((self.n_iter_ >= self.max_iter).sum()), len(self.n_iter_), self.max_iter, self.tol),
+            warnings.warn("%s: %d of %d one-vs-one problems stopped at max_iter = %d before reaching tol = %g"
+                          % (self._name, int((self.n_iter_ >= self.max_iter).sum()), len(self.n_iter_), self.max_iter, self.tol),
                           SVMConvergenceWarning, stacklevel=2)
         return self
 
     def _decide(self, X, chunk, want_dec):
         if self.classes_ is None:
-            raise RuntimeError("RBFSVM: fit() first")
+            raise RuntimeError("%s: fit() first" % self._name)
         X32 = _finite_matrix(X, "X", self.n_features_in_)
         if chunk is None:
             chunk = 4096
@@ -177,6 +186,83 @@ class RBFSVM(_DeviceSVM):
 
     def score(self, X, y, chunk=None):
         return float(np.mean(self.predict(X, chunk) == np.asarray(y)))
+
+
+class RBFSVM(_SingleSVM):
+    _name = 'RBFSVM'
+
+    def __init__(self, C=1.0, gamma='auto', tol=1e-3, max_iter=10_000_000, device='cuda:0'):
+        _DeviceSVM.__init__(self, C, gamma, tol, max_iter, device)
+        self.classes_ = None
+
+    def _gram(self, a, b):
+        out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=self.device)
+        self._call("mrgan_svm_gram", a.data_ptr(), a.stride(0), a.shape[0], b.data_ptr(), b.stride(0), b.shape[0], a.shape[1],
+                   self._gamma, out.data_ptr(), out.stride(0))
+        return out
+
+    def _solve(self, gram, n, K, iters):
+        self._call("mrgan_svm_solve", gram.data_ptr(), gram.stride(0), n, K, self._cs, self.C, self.tol, self.max_iter,
+                   self._coef.data_ptr(), self._rho.data_ptr(), iters.data_ptr())
+
+
+def nu_infeasible_pair(class_start, nu):
+    """libsvm's svm_check_parameter for NU_SVC: nu (n_i + n_j) / 2 > min(n_i, n_j) makes the pair's start point impossible
+    -> the first such pair of class indices (i, j), or None"""
+    sizes = np.diff(np.asarray(class_start))
+    for i in range(len(sizes)):
+        for j in range(i + 1, len(sizes)):
+            if nu * (sizes[i] + sizes[j]) / 2 > min(sizes[i], sizes[j]):
+                return i, j
+    return None
+
+
+class KernelSVM(_SingleSVM):
+    """The libsvm classifiers of the reference's SVM grid (others/wganlpctsemi.py:205-208) on the device, with RBFSVM's surface:
+
+        KernelSVM(kernel='rbf' | 'linear', nu=None | float in (0, 1], C=1.0, gamma='auto', tol=1e-3, max_iter=10_000_000)
+
+    nu=None is C-SVC (SVC(kernel=..., C=C)); a float is nu-SVC (NuSVC(kernel=..., nu=nu)) and C is unused.  gamma is the RBF
+    kernel's width and unused by the linear kernel.  KernelSVM(kernel='rbf') gives RBFSVM's bits.  A nu fit adds r_ (per pair:
+    dual_coef_dense_ * r_ is alpha y with alpha in [0, 1]) and raises ValueError where the solver returns non-finite
+    coefficients (libsvm divides by an r it does not guard)."""
+    _name = 'KernelSVM'
+
+    def __init__(self, kernel='rbf', nu=None, C=1.0, gamma='auto', tol=1e-3, max_iter=10_000_000, device='cuda:0'):
+        if kernel not in E.SVM_KERNELS:
+            raise ValueError("kernel must be one of %s, got %r" % (sorted(E.SVM_KERNELS), kernel))
+        if nu is not None and not (np.isreal(nu) and 0 < nu <= 1):
+            raise ValueError("nu must be None (C-SVC) or a number in (0, 1], got %r" % (nu,))
+        _DeviceSVM.__init__(self, C, gamma, tol, max_iter, device)
+        self.kernel, self.nu = kernel, None if nu is None else float(nu)
+        self.classes_, self.r_ = None, None
+
+    def _check_classes(self, classes, class_start):
+        bad = None if self.nu is None else nu_infeasible_pair(class_start, self.nu)
+        if bad is not None:
+            raise ValueError("specified nu is infeasible: nu = %g needs nu (n_i + n_j) / 2 <= min(n_i, n_j), which fails for classes %s and %s"
+                             % (self.nu, classes[bad[0]], classes[bad[1]]))
+
+    def _gram(self, a, b):
+        out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=self.device)
+        self._call("mrgan_svm_kernel_matrix", E.SVM_KERNELS[self.kernel], a.data_ptr(), a.stride(0), a.shape[0], b.data_ptr(), b.stride(0),
+                   b.shape[0], a.shape[1], self._gamma, out.data_ptr(), out.stride(0))
+        return out
+
+    def _solve(self, gram, n, K, iters):
+        if self.nu is None:
+            self._r = None
+            return RBFSVM._solve(self, gram, n, K, iters)
+        self._r = torch.empty(K * (K - 1) // 2, dtype=torch.float64, device=self.device)
+        self._call("mrgan_svm_solve_nu", gram.data_ptr(), gram.stride(0), n, K, self._cs, self.nu, self.tol, self.max_iter,
+                   self._coef.data_ptr(), self._rho.data_ptr(), self._r.data_ptr(), iters.data_ptr())
+
+    def _after_solve(self):
+        self.r_ = None if self._r is None else self._r.cpu().numpy()
+        if not (np.isfinite(self.dual_coef_dense_).all() and np.isfinite(self.intercept_).all()):
+            self.classes_ = None
+            raise ValueError("KernelSVM: the nu-SVC solver returned non-finite coefficients (r = %s): libsvm's r <= 0, nu = %g does "
+                             "not suit this problem" % (self.r_, self.nu))
 
 
 def plan_subgroups(nbytes, budget, max_group=E.SVM_MAX_GROUP):

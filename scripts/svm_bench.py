@@ -9,7 +9,9 @@ size is warmed up once, then repeated; the medians are reported, with the per-pa
 test error of both.
 
     python scripts/svm_bench.py [--labeled 60 960 6000] [--repeats 5] [--sklearn-repeats 3]
-Prints one JSON line per size.
+                                [--classifier {svc-rbf,svc-linear,nu-rbf,nu-linear}]
+Prints one JSON line per size.  --classifier takes another libsvm classifier of mr_svm's grid through mr_gan_amd.svm.KernelSVM, the
+same stages, against the matching SVC / NuSVC (profiles/svm_kinds_bench.txt); svc-rbf, the default, is RBFSVM as before.
 
     python scripts/svm_bench.py --group [G] [--labeled 60 960 6000] [--repeats 5]          (G = 6 where not given)
 times G fits and scores through one RBFSVMGroup (grouped launches) against the same G problems through G RBFSVM objects one
@@ -26,7 +28,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from mr_gan_amd import RBFSVM, RBFSVMGroup, synthetic_mreo  # noqa: E402
+from mr_gan_amd import KernelSVM, RBFSVM, RBFSVMGroup, synthetic_mreo  # noqa: E402
+from mr_gan_amd.mr_svm import CLASSIFIERS  # noqa: E402
 
 
 def main():
@@ -37,13 +40,17 @@ def main():
     ap.add_argument("--d", type=int, default=1200)
     ap.add_argument("--group", type=int, nargs="?", const=6, default=None,
                     help="time G problems through RBFSVMGroup against G RBFSVM objects instead (G = 6 where not given)")
+    ap.add_argument("--classifier", choices=sorted(CLASSIFIERS), default='svc-rbf')
     args = ap.parse_args()
     if args.group is not None and args.group < 1:
         ap.error("--group needs at least one problem")
+    if args.group is not None and args.classifier != 'svc-rbf':
+        ap.error("--group times RBFSVMGroup: --classifier svc-rbf only")
     if not torch.cuda.is_available():
         raise SystemExit("svm_bench needs a GPU: nothing is measured without one")
     from sklearn import preprocessing
-    from sklearn.svm import SVC
+    from sklearn.svm import SVC, NuSVC
+    kernel, nu = CLASSIFIERS[args.classifier]
     X, y, _ = synthetic_mreo(d=args.d)
     if args.group is not None:
         folds = []
@@ -65,13 +72,18 @@ def main():
         per = n // 6
         xl = np.concatenate([a[ya == c][:per] for c in range(6)])
         yl = np.repeat(np.arange(6), per)
-        print(json.dumps(measure(args, SVC, xl, yl, xt, yt)))
+        if args.classifier == 'svc-rbf':
+            print(json.dumps(measure(args, SVC, xl, yl, xt, yt)))
+        else:
+            make_hip = lambda: KernelSVM(kernel=kernel, nu=nu, C=1.0, gamma='auto')
+            make_sk = (lambda: SVC(kernel=kernel, C=1.0, gamma='auto')) if nu is None else (lambda: NuSVC(kernel=kernel, nu=nu, gamma='auto'))
+            print(json.dumps(dict(measure(args, SVC, xl, yl, xt, yt, make_hip, make_sk), classifier=args.classifier)))
         sys.stdout.flush()
 
 
-def measure(args, SVC, xl, yl, xt, yt):
+def measure(args, SVC, xl, yl, xt, yt, make_hip=None, make_sk=None):
     n, d = xl.shape
-    clf = RBFSVM(C=1.0, gamma='auto')
+    clf = RBFSVM(C=1.0, gamma='auto') if make_hip is None else make_hip()
     clf.fit(xl, yl).score(xt, yt)                       # warm-up: code objects, allocator
     fit_s, score_s, stages = [], [], dict(gram=[], solve=[], predict=[])
     for rep in range(args.repeats):
@@ -92,7 +104,7 @@ def measure(args, SVC, xl, yl, xt, yt):
     reps = 1 if n > 2000 else args.sklearn_repeats
     sk_fit, sk_score = [], []
     for rep in range(reps):
-        svc = SVC(kernel='rbf', C=1.0, gamma='auto')
+        svc = SVC(kernel='rbf', C=1.0, gamma='auto') if make_sk is None else make_sk()
         t0 = time.perf_counter()
         svc.fit(xl, yl)
         t1 = time.perf_counter()
