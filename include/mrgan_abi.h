@@ -308,6 +308,29 @@ int mrgan_svm_solve_group(const mrgan_svm_solve_item* items_host, int32_t count,
                           int32_t max_iter, mrgan_stream stream);
 int mrgan_svm_decide_group(const mrgan_svm_decide_item* items_host, int32_t count, int32_t num_classes, mrgan_stream stream);
 
+/* The grouped twins of mrgan_svm_kernel_matrix and mrgan_svm_solve_nu, under the rules of the block above: handle-free, no
+ * allocation, no copy, no synchronisation, descriptors read during the call only, every item's single-entry checks before any
+ * launch, "(item i)" at the end of a message about an item, each item's outputs bit-identical to the single entry on that item.
+ *   mrgan_svm_kernel_matrix_group  mrgan_svm_gram_group with a kernel kind.  MRGAN_SVM_KERNEL_RBF launches the very kernel of
+ *                     mrgan_svm_gram_group; MRGAN_SVM_KERNEL_LINEAR ignores gamma; any other kind is an error.
+ *   mrgan_svm_solve_nu_group  mrgan_svm_solve_nu per item.  nu belongs to the ITEM (tol and max_iter to the group), so one call
+ *                     can solve one kernel matrix at several nu: items may share k_dev, which they only read, while coef_dev,
+ *                     rho_dev, r_dev and iters_dev must not overlap.  r_dev is optional per item.  An infeasible nu names the
+ *                     pair of classes as the single entry does, then the item.
+ * mrgan_svm_decide_group serves all four kinds unchanged: it sees kernel values, coefficients and rho only. */
+typedef struct {
+    const float* k_dev; int64_t ld_k, n;
+    const int64_t* class_start_host;      /* num_classes + 1 host values */
+    double nu;                            /* this item's nu, 0 < nu <= 1 */
+    double* coef_dev; double* rho_dev;
+    double* r_dev;                        /* optional */
+    int32_t* iters_dev;
+} mrgan_svm_solve_nu_item;
+int mrgan_svm_kernel_matrix_group(int32_t kernel, const mrgan_svm_gram_item* items_host, int32_t count, int64_t d, float gamma,
+                                  mrgan_stream stream);
+int mrgan_svm_solve_nu_group(const mrgan_svm_solve_nu_item* items_host, int32_t count, int32_t num_classes, double tol,
+                             int32_t max_iter, mrgan_stream stream);
+
 /* one iteration of the hot loop (mr_gan.py:204-213): D step then G step */
 int mrgan_train_pair(mrgan_handle* h, const mrgan_disc_args* d, const mrgan_gen_args* g, mrgan_stream stream);
 /* For hosts that drive the phases themselves (data parallel) and know that the next mrgan_disc_step is followed by a

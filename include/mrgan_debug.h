@@ -285,6 +285,9 @@ int mrgan_debug_svm_kernel_matrix(int32_t kernel, const float* a_dev, int64_t ld
                                   int64_t d, float gamma, float* out_dev, int64_t ld_out, int32_t tile, mrgan_stream stream);
 /* mrgan_svm_gram_group with the launch's one tile forced in the same way */
 int mrgan_debug_svm_gram_group(const mrgan_svm_gram_item* items_host, int32_t count, int64_t d, float gamma, int32_t tile, mrgan_stream stream);
+/* mrgan_svm_kernel_matrix_group with the launch's one tile forced in the same way */
+int mrgan_debug_svm_kernel_matrix_group(int32_t kernel, const mrgan_svm_gram_item* items_host, int32_t count, int64_t d, float gamma,
+                                        int32_t tile, mrgan_stream stream);
 
 #ifdef __cplusplus
 }

@@ -1308,6 +1308,23 @@ int mrgan_svm_decide_group(const mrgan_svm_decide_item* items_host, int32_t coun
     return r ? svm_group_fail(r, msg, item) : 0;
 }
 
+int mrgan_svm_kernel_matrix_group(int32_t kernel, const mrgan_svm_gram_item* items_host, int32_t count, int64_t d, float gamma,
+                                  mrgan_stream stream) {
+    const char* msg = "";
+    int item = -1;
+    const int r = launch_svm_kernel_matrix_group(kernel, items_host, count, (long)d, gamma, 0, (hipStream_t)stream, &msg, &item);
+    return r ? svm_group_fail(r, msg, item) : 0;
+}
+
+int mrgan_svm_solve_nu_group(const mrgan_svm_solve_nu_item* items_host, int32_t count, int32_t num_classes, double tol,
+                             int32_t max_iter, mrgan_stream stream) {
+    const char* msg = "";
+    int item = -1, bi = -1, bj = -1;
+    const int r = launch_svm_solve_nu_group(items_host, count, num_classes, tol, max_iter, (hipStream_t)stream, &msg, &item, &bi, &bj);
+    if (r && bi >= 0) return fail(r, "%s for the pair of classes %d and %d (item %d)", msg, bi, bj, item);
+    return r ? svm_group_fail(r, msg, item) : 0;
+}
+
 int mrgan_sup_step(mrgan_handle* h, const mrgan_sup_args* a, float* out2, mrgan_stream stream) {
     if (!h || !a || !a->x_dev || !a->labels_dev) return fail(-1, "sup_step: x and labels are required");
     if (refuse_ae(h, "sup_step") || refuse_group(h, "sup_step")) return -3;

@@ -706,4 +706,12 @@ int mrgan_debug_svm_gram_group(const mrgan_svm_gram_item* items_host, int32_t co
     return r ? svm_group_fail(r, msg, item) : 0;
 }
 
+int mrgan_debug_svm_kernel_matrix_group(int32_t kernel, const mrgan_svm_gram_item* items_host, int32_t count, int64_t d, float gamma,
+                                        int32_t tile, mrgan_stream stream) {
+    const char* msg = "";
+    int item = -1;
+    const int r = launch_svm_kernel_matrix_group(kernel, items_host, count, (long)d, gamma, tile, (hipStream_t)stream, &msg, &item);
+    return r ? svm_group_fail(r, msg, item) : 0;
+}
+
 }  // extern "C"

@@ -41,5 +41,13 @@ int launch_svm_gram_group(const mrgan_svm_gram_item* items, int count, long d, f
 int launch_svm_solve_group(const mrgan_svm_solve_item* items, int count, int num_classes, double C, double tol, int max_iter, hipStream_t s,
                            const char** err, int* bad_item);
 int launch_svm_decide_group(const mrgan_svm_decide_item* items, int count, int num_classes, hipStream_t s, const char** err, int* bad_item);
+// launch_svm_gram_group with a kernel kind, as launch_svm_kernel_matrix is to launch_svm_gram: MRGAN_SVM_KERNEL_RBF is
+// launch_svm_gram_group itself (the same kernel); an unknown kind is refused
+int launch_svm_kernel_matrix_group(int kind, const mrgan_svm_gram_item* items, int count, long d, float gamma, int tile, hipStream_t s,
+                                   const char** err, int* bad_item);
+// launch_svm_solve_nu on every item with that item's nu (tol and max_iter are the group's).  *bad_i, *bad_j: the classes of the
+// pair the nu of item *bad_item is infeasible for (-1 otherwise)
+int launch_svm_solve_nu_group(const mrgan_svm_solve_nu_item* items, int count, int num_classes, double tol, int max_iter, hipStream_t s,
+                              const char** err, int* bad_item, int* bad_i, int* bad_j);
 
 }  // namespace mrgan

@@ -13,7 +13,9 @@
 //   svm_smo_nu_kernel  libsvm's nu-SVC (solve_nu_svc, Solver_NU) without shrinking, under svm_smo_kernel's discipline
 //
 // Each has a grouped twin (svm_*_group_kernel) for up to SVM_MAX_GROUP ragged problems in one launch: the same __device__ body
-// (gram_tile, smo_pair, decide_row), a block finding its problem from blockIdx through the descriptors in the kernel arguments.
+// (gram_tile, smo_pair, smo_nu_pair, decide_row), a block finding its problem from blockIdx through the descriptors in the
+// kernel arguments: svm_gram_group_kernel<TS, KIND> for both kernel kinds, svm_smo_group_kernel and svm_smo_nu_group_kernel (nu per
+// item) for the two solvers, svm_decide_group_kernel for every kind.
 //
 // Rows are sorted by class: pair (i, j), i < j, is the two contiguous row ranges of classes i and j, y = +1 on class i.
 #include <math.h>
@@ -145,14 +147,14 @@ struct GramItem { const float* a; const float* b; float* out; long ld_a, ld_b, l
 struct GramGroup { GramItem item[SVM_MAX_GROUP]; int tile_start[SVM_MAX_GROUP + 1]; int tiles_x[SVM_MAX_GROUP]; };
 static_assert(sizeof(GramGroup) + 16 <= KERNARG_LIMIT, "svm_gram_group_kernel: descriptors beyond the kernel argument limit");
 
-template <int TS>
+template <int TS, int KIND = RBF>
 __global__ __launch_bounds__(256) void svm_gram_group_kernel(const GramGroup g, int count, int D, float gamma) {
     const int bid = blockIdx.x;
     int it = 0;
     while (it + 1 < count && bid >= g.tile_start[it + 1]) ++it;       // wave-uniform: blockIdx and arguments only
     const GramItem& d = g.item[it];
     const int local = bid - g.tile_start[it], tx = g.tiles_x[it], ty = local / tx;
-    gram_tile<TS>(d.a, d.ld_a, d.m, d.b, d.ld_b, d.n, D, gamma, d.out, d.ld_out, ty * TS, (local - ty * tx) * TS);
+    gram_tile<TS, KIND>(d.a, d.ld_a, d.m, d.b, d.ld_b, d.n, D, gamma, d.out, d.ld_out, ty * TS, (local - ty * tx) * TS);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -588,6 +590,21 @@ __global__ __launch_bounds__(SMO_THREADS) void svm_smo_nu_kernel(const float* __
     smo_nu_pair(K, ld_k, n, blockIdx.x, ci, cj, s1, n1, s2, n2, nu, tol, max_iter, coef, rho, r_out, iters);
 }
 
+// nu differs from item to item (one Gram matrix at several nu is one launch: items may share k, which they only read); tol and
+// max_iter are the group's
+struct SmoNuItem { const float* k; long ld_k; double* coef; double* rho; double* r; int* iters; double nu; int n; SvmClasses cls; };
+struct SmoNuGroup { SmoNuItem item[SVM_MAX_GROUP]; };
+static_assert(sizeof(SmoNuGroup) + 32 <= KERNARG_LIMIT, "svm_smo_nu_group_kernel: descriptors beyond the kernel argument limit");
+
+// grid (pairs, count) as svm_smo_group_kernel: count x pairs independent solves, each ending at max_iter
+__global__ __launch_bounds__(SMO_THREADS) void svm_smo_nu_group_kernel(const SmoNuGroup g, int num_classes, double tol, int max_iter) {
+    const SmoNuItem& d = g.item[blockIdx.y];
+    int ci, cj;
+    pair_classes(blockIdx.x, num_classes, ci, cj);
+    const int s1 = d.cls.start[ci], n1 = d.cls.start[ci + 1] - s1, s2 = d.cls.start[cj], n2 = d.cls.start[cj + 1] - s2;
+    smo_nu_pair(d.k, d.ld_k, d.n, blockIdx.x, ci, cj, s1, n1, s2, n2, d.nu, tol, max_iter, d.coef, d.rho, d.r, d.iters);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // decision values and the vote: one block per test row, a wave per pair (round robin)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -802,14 +819,14 @@ int launch_svm_decide(const float* kt, long ld_kt, long m, long n, int num_class
     return 0;
 }
 
-int launch_svm_gram_group(const mrgan_svm_gram_item* items, int count, long d, float gamma, int tile, hipStream_t s, const char** err,
-                          int* bad_item) {
+int launch_svm_kernel_matrix_group(int kind, const mrgan_svm_gram_item* items, int count, long d, float gamma, int tile, hipStream_t s,
+                                   const char** err, int* bad_item) {
     int r = check_group(items, count, "svm_gram: null item list", "svm_gram: count outside [1, MRGAN_SVM_MAX_GROUP = 16]", bad_item, err);
     if (r) return r;
     long tiles128 = 0;
     for (int i = 0; i < count; ++i) {
         const mrgan_svm_gram_item& it = items[i];
-        r = check_gram(it.a_dev, (long)it.ld_a, (long)it.m, it.b_dev, (long)it.ld_b, (long)it.n, d, gamma, it.out_dev, (long)it.ld_out, tile, err);
+        r = check_gram(it.a_dev, (long)it.ld_a, (long)it.m, it.b_dev, (long)it.ld_b, (long)it.n, d, gamma, it.out_dev, (long)it.ld_out, tile, err, kind);
         if (r) { *bad_item = i; return r; }
         tiles128 += (long)ceil_div(it.n, 128) * ceil_div(it.m, 128);
     }
@@ -828,10 +845,20 @@ int launch_svm_gram_group(const mrgan_svm_gram_item* items, int count, long d, f
     for (int i = count; i <= SVM_MAX_GROUP; ++i) g.tile_start[i] = (int)total;
     for (int i = count; i < SVM_MAX_GROUP; ++i) g.tiles_x[i] = 1;
     const dim3 grid((unsigned)total), block(256);
-    if (ts == 64) MRGAN_LAUNCH((svm_gram_group_kernel<64>), grid, block, 0, s, g, count, (int)d, gamma);
-    else MRGAN_LAUNCH((svm_gram_group_kernel<128>), grid, block, 0, s, g, count, (int)d, gamma);
+    if (ts == 64) {
+        if (kind == RBF) MRGAN_LAUNCH((svm_gram_group_kernel<64>), grid, block, 0, s, g, count, (int)d, gamma);
+        else MRGAN_LAUNCH((svm_gram_group_kernel<64, LINEAR>), grid, block, 0, s, g, count, (int)d, 0.f);
+    } else {
+        if (kind == RBF) MRGAN_LAUNCH((svm_gram_group_kernel<128>), grid, block, 0, s, g, count, (int)d, gamma);
+        else MRGAN_LAUNCH((svm_gram_group_kernel<128, LINEAR>), grid, block, 0, s, g, count, (int)d, 0.f);
+    }
     if (hipGetLastError() != hipSuccess) { *err = "svm_gram: group launch failed"; return -10; }
     return 0;
+}
+
+int launch_svm_gram_group(const mrgan_svm_gram_item* items, int count, long d, float gamma, int tile, hipStream_t s, const char** err,
+                          int* bad_item) {
+    return launch_svm_kernel_matrix_group(RBF, items, count, d, gamma, tile, s, err, bad_item);
 }
 
 int launch_svm_solve_group(const mrgan_svm_solve_item* items, int count, int num_classes, double C, double tol, int max_iter, hipStream_t s,
@@ -850,6 +877,26 @@ int launch_svm_solve_group(const mrgan_svm_solve_item* items, int count, int num
     const int pairs = num_classes * (num_classes - 1) / 2;
     MRGAN_LAUNCH(svm_smo_group_kernel, dim3(pairs, count), dim3(SMO_THREADS), 0, s, g, num_classes, C, tol, max_iter);
     if (hipGetLastError() != hipSuccess) { *err = "svm_solve: group launch failed"; return -10; }
+    return 0;
+}
+
+int launch_svm_solve_nu_group(const mrgan_svm_solve_nu_item* items, int count, int num_classes, double tol, int max_iter, hipStream_t s,
+                              const char** err, int* bad_item, int* bad_i, int* bad_j) {
+    *bad_i = *bad_j = -1;
+    int r = check_group(items, count, "svm_solve_nu: null item list", "svm_solve_nu: count outside [1, MRGAN_SVM_MAX_GROUP = 16]", bad_item, err);
+    if (r) return r;
+    SmoNuGroup g = {};
+    for (int i = 0; i < count; ++i) {
+        const mrgan_svm_solve_nu_item& it = items[i];
+        r = check_solve_nu(it.k_dev, (long)it.ld_k, (long)it.n, num_classes, it.class_start_host, it.nu, tol, max_iter, it.coef_dev, it.rho_dev,
+                           it.iters_dev, g.item[i].cls, err, bad_i, bad_j);
+        if (r) { *bad_item = i; return r; }
+        g.item[i].k = it.k_dev; g.item[i].ld_k = (long)it.ld_k; g.item[i].coef = it.coef_dev; g.item[i].rho = it.rho_dev;
+        g.item[i].r = it.r_dev; g.item[i].iters = it.iters_dev; g.item[i].nu = it.nu; g.item[i].n = (int)it.n;
+    }
+    const int pairs = num_classes * (num_classes - 1) / 2;
+    MRGAN_LAUNCH(svm_smo_nu_group_kernel, dim3(pairs, count), dim3(SMO_THREADS), 0, s, g, num_classes, tol, max_iter);
+    if (hipGetLastError() != hipSuccess) { *err = "svm_solve_nu: group launch failed"; return -10; }
     return 0;
 }
 

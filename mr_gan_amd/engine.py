@@ -40,6 +40,7 @@ EXPORTS = [
     "mrgan_svm_gram", "mrgan_svm_solve", "mrgan_svm_decide", "mrgan_debug_svm_gram",
     "mrgan_svm_gram_group", "mrgan_svm_solve_group", "mrgan_svm_decide_group", "mrgan_debug_svm_gram_group",
     "mrgan_svm_kernel_matrix", "mrgan_svm_solve_nu", "mrgan_debug_svm_kernel_matrix",
+    "mrgan_svm_kernel_matrix_group", "mrgan_svm_solve_nu_group", "mrgan_debug_svm_kernel_matrix_group",
 ]
 SVM_MAX_PAIR = 2048           # MRGAN_SVM_MAX_PAIR: rows of one one-vs-one problem
 SVM_MAX_CLASSES = 32
@@ -151,6 +152,16 @@ class SvmSolveItem(C.Structure):
         ("k", C.c_void_p), ("ld_k", C.c_int64), ("n", C.c_int64),
         ("class_start", C.POINTER(C.c_int64)),
         ("coef", C.c_void_p), ("rho", C.c_void_p), ("iters", C.c_void_p),
+    ]
+
+
+class SvmSolveNuItem(C.Structure):
+    """mrgan_svm_solve_nu_item"""
+    _fields_ = [
+        ("k", C.c_void_p), ("ld_k", C.c_int64), ("n", C.c_int64),
+        ("class_start", C.POINTER(C.c_int64)),
+        ("nu", C.c_double),
+        ("coef", C.c_void_p), ("rho", C.c_void_p), ("r", C.c_void_p), ("iters", C.c_void_p),
     ]
 
 
@@ -275,6 +286,9 @@ def load_library(path=None):
     lib.mrgan_debug_svm_gram_group.argtypes = [C.POINTER(SvmGramItem), C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_void_p]
     lib.mrgan_svm_solve_group.argtypes = [C.POINTER(SvmSolveItem), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p]
     lib.mrgan_svm_decide_group.argtypes = [C.POINTER(SvmDecideItem), C.c_int32, C.c_int32, C.c_void_p]
+    lib.mrgan_svm_kernel_matrix_group.argtypes = [C.c_int32, C.POINTER(SvmGramItem), C.c_int32, C.c_int64, C.c_float, C.c_void_p]
+    lib.mrgan_debug_svm_kernel_matrix_group.argtypes = [C.c_int32, C.POINTER(SvmGramItem), C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_void_p]
+    lib.mrgan_svm_solve_nu_group.argtypes = [C.POINTER(SvmSolveNuItem), C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p]
     _lib = lib
     return lib
 

@@ -9,7 +9,9 @@ RBF-kernel SVC (C = 1) trained on the labeled subset only.  By default on scikit
 (nu = 0.5) with the RBF or the linear kernel, on either backend (hip: mr_gan_amd.svm.KernelSVM).
 
 --group-folds (with --backend hip) fits and scores the six folds of each table-2 cell, and consecutive runs of twelve objects of
-each table-4 cell, as ONE RBFSVMGroup (grouped launches over ragged problems) and prints the same lines.
+each table-4 cell, as ONE RBFSVMGroup (grouped launches over ragged problems) and prints the same lines.  The flag serves
+--classifier svc-rbf; the other classifiers are grouped through mr_svm_folds(..., classifier=) (one KernelSVMGroup), e.g.
+main(argv, folds_fn=functools.partial(mr_svm_folds, classifier='nu-linear')).
 
 Shares dataset(), the data prologue and the modality names with mr_gan_amd.mr_gan; prints the reference's lines
 (mr_svm.py prints only the averages for table 2 and one line per object for table 4)."""
@@ -22,7 +24,7 @@ import numpy as np
 
 from mr_gan_amd.data import prologue, resolve_num_classes, train_test_sets
 from mr_gan_amd.mr_gan import MODALITIES, dataset, print_lines
-from mr_gan_amd.svm import KernelSVM, RBFSVM, RBFSVMGroup
+from mr_gan_amd.svm import KernelSVM, KernelSVMGroup, RBFSVM, RBFSVMGroup
 
 
 SVC_GAMMA = 'auto'
@@ -63,10 +65,14 @@ def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None
     return testerror
 
 
-def mr_svm_folds(sets, percentlabeled=50, verbose=False, seed=None):
+def mr_svm_folds(sets, percentlabeled=50, verbose=False, seed=None, classifier='svc-rbf'):
     """mr_svm(backend='hip') of every [X_train, X_test, y_train, y_test] of `sets` (the folds of a table-2 cell, the objects of a
-    table-4 cell) as one RBFSVMGroup -> their test errors.  Fold f runs mr_svm()'s prologue from RandomState(seed + f), the rule
-    of mr_nn_folds: the errors are those of mr_svm(None, None, trainTestSets=sets[f], seed=seed + f, backend='hip')."""
+    table-4 cell) as one RBFSVMGroup -- for another classifier of CLASSIFIERS one KernelSVMGroup -> their test errors.  Fold f
+    runs mr_svm()'s prologue from RandomState(seed + f), the rule of mr_nn_folds: the errors are those of
+    mr_svm(None, None, trainTestSets=sets[f], seed=seed + f, backend='hip', classifier=classifier)."""
+    if classifier not in CLASSIFIERS:
+        raise ValueError("classifier must be one of %s, got %r" % (sorted(CLASSIFIERS), classifier))
+    kernel, nu = CLASSIFIERS[classifier]
     base = int(seed if seed is not None else np.random.randint(1 << 30))
     num_classes = resolve_num_classes(None)
     folds = []
@@ -74,7 +80,11 @@ def mr_svm_folds(sets, percentlabeled=50, verbose=False, seed=None):
         folds.append(prologue(s, percentlabeled, None, np.random.RandomState(base + f), num_classes))
         print_lines(folds[-1][-1], verbose)
     x_labeled, y_labeled, _, _, X_test, y_test, _ = zip(*folds)
-    group = RBFSVMGroup(C=1.0, gamma=SVC_GAMMA).fit(x_labeled, y_labeled)
+    if classifier == 'svc-rbf':
+        group = RBFSVMGroup(C=1.0, gamma=SVC_GAMMA)
+    else:
+        group = KernelSVMGroup(kernel=kernel, nu=nu, C=1.0, gamma=SVC_GAMMA)
+    group.fit(x_labeled, y_labeled)
     errors = [1.0 - s for s in group.score(X_test, y_test)]
     if verbose:
         for e, lab, yt in zip(errors, group.predict(X_test), y_test):
@@ -156,7 +166,7 @@ def main(argv=None, dataset_fn=dataset, fn=mr_svm, folds_fn=None):
     if args.group_folds and args.backend != 'hip':
         parser.error('--group-folds needs --backend hip')
     if args.group_folds and args.classifier != 'svc-rbf':
-        parser.error('--group-folds serves --classifier svc-rbf only (RBFSVMGroup)')
+        parser.error('--group-folds serves --classifier svc-rbf only; the other classifiers are grouped through mr_svm_folds(classifier=)')
     if args.backend != 'sklearn':
         fn = functools.partial(fn, backend=args.backend)
     if args.classifier != 'svc-rbf':

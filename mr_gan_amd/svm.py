@@ -12,13 +12,14 @@ KernelSVM covers the other libsvm classifiers of the reference's wider SVM grid 
 RBFSVM's surface and conventions: kernel='rbf' | 'linear' through mrgan_svm_kernel_matrix (the linear Gram matrix is the
 same matrix-core chain without norms and exp), and nu=None (C-SVC, mrgan_svm_solve) or a nu in (0, 1] (nu-SVC,
 mrgan_svm_solve_nu: libsvm's Solver_NU, coefficients alpha y / r, r in r_).  mrgan_svm_decide serves every kind.  The nu
-solver's restatement lives in tests/svm_kinds_ref.py.
+solver's restatement lives in tests/svm_kinds_ref.py.  KernelSVMGroup is to KernelSVM what RBFSVMGroup is to RBFSVM, through
+mrgan_svm_kernel_matrix_group and mrgan_svm_solve_nu_group (nu per problem); the two group classes share one body (_GroupSVM).
 
 Conventions are libsvm's: pairs (i, j), i < j, in the order of scikit-learn's decision_function_shape='ovo'; a positive
 decision value votes for classes_[i]; intercept_ = -rho.  Two classes give ONE column with that same sign (scikit-learn flips
 the sign of its binary decision_function; this class does not).
 Out of scope: shrinking, probability estimates, class weights, polynomial and sigmoid kernels, LinearSVC (liblinear, another
-algorithm), grouped launches for KernelSVM's kinds."""
+algorithm), groups with mixed feature or class counts, a C per problem."""
 import ctypes as C
 import warnings
 
@@ -281,36 +282,46 @@ def plan_subgroups(nbytes, budget, max_group=E.SVM_MAX_GROUP):
 
 
 class _Fitted:
-    """one problem of a fitted RBFSVMGroup: what a fitted RBFSVM exposes"""
+    """one problem of a fitted group: what a fitted RBFSVM / KernelSVM exposes (r_: the nu solver's r per pair, None for C-SVC)"""
 
-    def __init__(self, classes, dual_coef_dense, intercept, n_iter):
-        self.classes_, self.dual_coef_dense_, self.intercept_, self.n_iter_ = classes, dual_coef_dense, intercept, n_iter
+    def __init__(self, classes, dual_coef_dense, intercept, n_iter, r=None):
+        self.classes_, self.dual_coef_dense_, self.intercept_, self.n_iter_, self.r_ = classes, dual_coef_dense, intercept, n_iter, r
 
 
-class RBFSVMGroup(_DeviceSVM):
-    """Independent RBFSVM problems of one feature count and one class count (the folds of a table cell), fitted and scored in
-    grouped launches: mrgan_svm_gram_group, mrgan_svm_solve_group, mrgan_svm_decide_group serve up to 16 ragged problems
-    each.  Problem p's results are those of RBFSVM(...).fit(Xs[p], ys[p]) bit for bit.
+class _GroupSVM(_DeviceSVM):
+    """several problems of one feature count and one class count in grouped launches, what RBFSVMGroup and KernelSVMGroup share:
+    validation, sorting, uploads, the sub-group plan, chunked prediction through mrgan_svm_decide_group, the convergence
+    warning.  A subclass names itself (_name), supplies _gram_group(items, count, d) -> the grouped kernel-matrix launch and
+    _solve_group(sub, grams, K, iters) -> a callable that makes the grouped solver launch on the problems `sub`, and may
+    refuse problems from their class counts in _check_problems (before any device call), prepare per-problem buffers in
+    _before_solve and refuse results in _after_solve."""
+    _name = None
 
-        group = RBFSVMGroup().fit(Xs, ys); errors = [1.0 - s for s in group.score(X_tests, y_tests)]; group[p].n_iter_
-
-    More than 16 problems, or Gram matrices above gram_bytes together, are worked in consecutive sub-groups (plan_subgroups);
-    prediction takes the problems' rows in chunks, one cross-Gram launch and one decide launch per chunk step of a sub-group.
-    Neither changes a bit.  There is no CPU path."""
-
-    def __init__(self, C=1.0, gamma='auto', tol=1e-3, max_iter=10_000_000, device='cuda:0', gram_bytes=4 << 30):
+    def __init__(self, C, gamma, tol, max_iter, device, gram_bytes):
         _DeviceSVM.__init__(self, C, gamma, tol, max_iter, device)
         if int(gram_bytes) != gram_bytes or gram_bytes < 1:
             raise ValueError("gram_bytes must be a positive integer, got %r" % (gram_bytes,))
         self.gram_bytes = int(gram_bytes)
         self._fitted = None
 
+    def _check_problems(self, probs):
+        pass
+
+    def _before_solve(self, count, pairs):
+        pass
+
+    def _r_of(self, p):
+        return None
+
+    def _after_solve(self, fitted):
+        pass
+
     def __len__(self):
         return 0 if self._fitted is None else len(self._fitted)
 
     def __getitem__(self, p):
         if self._fitted is None:
-            raise RuntimeError("RBFSVMGroup: fit() first")
+            raise RuntimeError("%s: fit() first" % self._name)
         return self._fitted[p]
 
     def fit(self, Xs, ys):
@@ -324,7 +335,7 @@ class RBFSVMGroup(_DeviceSVM):
                 raise ValueError("Xs[%d] has %d rows, ys[%d] has %d labels" % (p, X32.shape[0], p, len(y)))
             K = len(classes)
             if not 2 <= K <= E.SVM_MAX_CLASSES:
-                raise ValueError("RBFSVMGroup needs 2 to %d classes, problem %d has %d" % (E.SVM_MAX_CLASSES, p, K))
+                raise ValueError("%s needs 2 to %d classes, problem %d has %d" % (self._name, E.SVM_MAX_CLASSES, p, K))
             sizes = np.sort(np.diff(class_start))
             if sizes[-1] + sizes[-2] > E.SVM_MAX_PAIR:
                 raise ValueError("the two largest classes of problem %d have %d rows together; one one-vs-one problem holds at most %d "
@@ -334,6 +345,7 @@ class RBFSVMGroup(_DeviceSVM):
             raise ValueError("a group shares one feature count, got %s" % sorted({q[0].shape[1] for q in probs}))
         if len({len(q[1]) for q in probs}) != 1:
             raise ValueError("a group shares one class count, got %s" % sorted({len(q[1]) for q in probs}))
+        self._check_problems(probs)
         self._require_gpu()
         d, K = probs[0][0].shape[1], len(probs[0][1])
         pairs = K * (K - 1) // 2
@@ -345,27 +357,30 @@ class RBFSVMGroup(_DeviceSVM):
         self._coef = [torch.empty((K - 1, len(x)), dtype=torch.float64, device=self.device) for x in self._x]
         self._rho = [torch.empty(pairs, dtype=torch.float64, device=self.device) for _ in probs]
         iters = [torch.empty(pairs, dtype=torch.int32, device=self.device) for _ in probs]
+        self._before_solve(len(probs), pairs)
         for sub in plan_subgroups([4 * len(x) * len(x) for x in self._x], self.gram_bytes):
             grams = [torch.empty((len(self._x[p]), len(self._x[p])), dtype=torch.float32, device=self.device) for p in sub]
             gi = (E.SvmGramItem * len(sub))(*[E.SvmGramItem(self._x[p].data_ptr(), self._x[p].stride(0), len(self._x[p]),
                                                             self._x[p].data_ptr(), self._x[p].stride(0), len(self._x[p]),
                                                             g.data_ptr(), g.stride(0)) for p, g in zip(sub, grams)])
-            si = (E.SvmSolveItem * len(sub))(*[E.SvmSolveItem(g.data_ptr(), g.stride(0), len(self._x[p]), self._cs[p], self._coef[p].data_ptr(),
-                                                              self._rho[p].data_ptr(), iters[p].data_ptr()) for p, g in zip(sub, grams)])
-            self._timed('gram', lambda: self._call("mrgan_svm_gram_group", gi, len(sub), d, self._gamma))
-            self._timed('solve', lambda: self._call("mrgan_svm_solve_group", si, len(sub), K, self.C, self.tol, self.max_iter))
+            solve = self._solve_group(sub, grams, K, iters)        # its descriptors are built outside the timed stage
+            self._timed('gram', lambda: self._gram_group(gi, len(sub), d))
+            self._timed('solve', solve)
             del grams                # back to the stream-ordered allocator: the next sub-group's launches come after these
-        self._fitted = [_Fitted(q[1], unsort_coef(self._coef[p].cpu().numpy(), q[2]), -self._rho[p].cpu().numpy(), iters[p].cpu().numpy())
-                        for p, q in enumerate(probs)]
+        self._fitted = None
+        fitted = [_Fitted(q[1], unsort_coef(self._coef[p].cpu().numpy(), q[2]), -self._rho[p].cpu().numpy(), iters[p].cpu().numpy(),
+                          self._r_of(p)) for p, q in enumerate(probs)]
+        self._after_solve(fitted)
+        self._fitted = fitted
         late = [p for p, f in enumerate(self._fitted) if (f.n_iter_ >= self.max_iter).any()]
         if late:
-            warnings.warn("RBFSVMGroup: problems %s have one-vs-one pairs that stopped at max_iter = %d before reaching tol = %g"
-                          % (late, self.max_iter, self.tol), SVMConvergenceWarning, stacklevel=2)
+            warnings.warn("%s: problems %s have one-vs-one pairs that stopped at max_iter = %d before reaching tol = %g"
+                          % (self._name, late, self.max_iter, self.tol), SVMConvergenceWarning, stacklevel=2)
         return self
 
     def _decide(self, Xs, chunk, want_dec):
         if self._fitted is None:
-            raise RuntimeError("RBFSVMGroup: fit() first")
+            raise RuntimeError("%s: fit() first" % self._name)
         if len(Xs) != len(self._fitted):
             raise ValueError("the group was fitted on %d problems, got %d row sets" % (len(self._fitted), len(Xs)))
         X32 = [_finite_matrix(X, "Xs[%d]" % p, self.n_features_in_) for p, X in enumerate(Xs)]
@@ -395,7 +410,7 @@ class RBFSVMGroup(_DeviceSVM):
                                                                          self._coef[p].data_ptr(), self._rho[p].data_ptr(),
                                                                          dec[p][r0:].data_ptr() if want_dec else None, labels[p][r0:].data_ptr())
                                                          for p, t, k in zip(live, xt, kt)])
-                    self._call("mrgan_svm_gram_group", gi, len(live), d, self._gamma)
+                    self._gram_group(gi, len(live), d)
                     self._call("mrgan_svm_decide_group", di, len(live), K)
         self._timed('predict', run)
         return [l.cpu().numpy() for l in labels], [v.cpu().numpy() if want_dec else None for v in dec]
@@ -412,3 +427,89 @@ class RBFSVMGroup(_DeviceSVM):
         if len(ys) != len(Xs):
             raise ValueError("score: %d row sets and %d label sets" % (len(Xs), len(ys)))
         return [float(np.mean(l == np.asarray(y))) for l, y in zip(self.predict(Xs, chunk), ys)]
+
+
+class RBFSVMGroup(_GroupSVM):
+    """Independent RBFSVM problems of one feature count and one class count (the folds of a table cell), fitted and scored in
+    grouped launches: mrgan_svm_gram_group, mrgan_svm_solve_group, mrgan_svm_decide_group serve up to 16 ragged problems
+    each.  Problem p's results are those of RBFSVM(...).fit(Xs[p], ys[p]) bit for bit.
+
+        group = RBFSVMGroup().fit(Xs, ys); errors = [1.0 - s for s in group.score(X_tests, y_tests)]; group[p].n_iter_
+
+    More than 16 problems, or Gram matrices above gram_bytes together, are worked in consecutive sub-groups (plan_subgroups);
+    prediction takes the problems' rows in chunks, one cross-Gram launch and one decide launch per chunk step of a sub-group.
+    Neither changes a bit.  There is no CPU path."""
+    _name = 'RBFSVMGroup'
+
+    def __init__(self, C=1.0, gamma='auto', tol=1e-3, max_iter=10_000_000, device='cuda:0', gram_bytes=4 << 30):
+        _GroupSVM.__init__(self, C, gamma, tol, max_iter, device, gram_bytes)
+
+    def _gram_group(self, items, count, d):
+        self._call("mrgan_svm_gram_group", items, count, d, self._gamma)
+
+    def _solve_group(self, sub, grams, K, iters):
+        si = (E.SvmSolveItem * len(sub))(*[E.SvmSolveItem(g.data_ptr(), g.stride(0), len(self._x[p]), self._cs[p], self._coef[p].data_ptr(),
+                                                          self._rho[p].data_ptr(), iters[p].data_ptr()) for p, g in zip(sub, grams)])
+        return lambda: self._call("mrgan_svm_solve_group", si, len(sub), K, self.C, self.tol, self.max_iter)
+
+
+class KernelSVMGroup(_GroupSVM):
+    """KernelSVM's kinds for a group of problems, with RBFSVMGroup's surface:
+
+        KernelSVMGroup(kernel='rbf' | 'linear', nu=None | float in (0, 1] | one such float per problem, C=1.0, gamma='auto', ...)
+
+    mrgan_svm_kernel_matrix_group makes the Gram and the cross-Gram matrices, mrgan_svm_solve_group (nu=None, C-SVC) or
+    mrgan_svm_solve_nu_group (nu-SVC; nu travels per item, so a sequence gives every problem its own) solves, and
+    mrgan_svm_decide_group votes.  Problem p's results are those of KernelSVM(kernel, nu_p, ...).fit(Xs[p], ys[p]) bit for bit,
+    r_ included; KernelSVMGroup(kernel='rbf') gives RBFSVMGroup's bits.  A nu that is infeasible for a problem is a ValueError
+    before any device call; non-finite coefficients in any problem are a ValueError that names the problems and leaves the
+    group unfitted."""
+    _name = 'KernelSVMGroup'
+
+    def __init__(self, kernel='rbf', nu=None, C=1.0, gamma='auto', tol=1e-3, max_iter=10_000_000, device='cuda:0', gram_bytes=4 << 30):
+        if kernel not in E.SVM_KERNELS:
+            raise ValueError("kernel must be one of %s, got %r" % (sorted(E.SVM_KERNELS), kernel))
+        if nu is not None and np.ndim(nu) == 0 and not (np.isreal(nu) and 0 < nu <= 1):
+            raise ValueError("nu must be None (C-SVC) or a number in (0, 1], got %r" % (nu,))
+        _GroupSVM.__init__(self, C, gamma, tol, max_iter, device, gram_bytes)
+        self.kernel = kernel
+        self.nu = None if nu is None else float(nu) if np.ndim(nu) == 0 else list(nu)        # a sequence is checked at fit
+
+    def _check_problems(self, probs):
+        self._nus = None
+        if self.nu is None:
+            return
+        nus = [self.nu] * len(probs) if isinstance(self.nu, float) else self.nu
+        if len(nus) != len(probs):
+            raise ValueError("nu holds %d values, the group %d problems; a sequence needs one nu per problem" % (len(nus), len(probs)))
+        for p, (nu, q) in enumerate(zip(nus, probs)):
+            if not (np.ndim(nu) == 0 and np.isreal(nu) and 0 < nu <= 1):
+                raise ValueError("nu must be None (C-SVC) or a number in (0, 1], got %r (problem %d)" % (nu, p))
+            bad = nu_infeasible_pair(q[3], float(nu))
+            if bad is not None:
+                raise ValueError("specified nu is infeasible: nu = %g needs nu (n_i + n_j) / 2 <= min(n_i, n_j), which fails for classes %s and %s "
+                                 "(problem %d)" % (nu, q[1][bad[0]], q[1][bad[1]], p))
+        self._nus = [float(nu) for nu in nus]
+
+    def _before_solve(self, count, pairs):
+        self._r = None if self._nus is None else [torch.empty(pairs, dtype=torch.float64, device=self.device) for _ in range(count)]
+
+    def _r_of(self, p):
+        return None if self._r is None else self._r[p].cpu().numpy()
+
+    def _gram_group(self, items, count, d):
+        self._call("mrgan_svm_kernel_matrix_group", E.SVM_KERNELS[self.kernel], items, count, d, self._gamma)
+
+    def _solve_group(self, sub, grams, K, iters):
+        if self._nus is None:
+            return RBFSVMGroup._solve_group(self, sub, grams, K, iters)
+        si = (E.SvmSolveNuItem * len(sub))(*[E.SvmSolveNuItem(g.data_ptr(), g.stride(0), len(self._x[p]), self._cs[p], self._nus[p],
+                                                              self._coef[p].data_ptr(), self._rho[p].data_ptr(), self._r[p].data_ptr(),
+                                                              iters[p].data_ptr()) for p, g in zip(sub, grams)])
+        return lambda: self._call("mrgan_svm_solve_nu_group", si, len(sub), K, self.tol, self.max_iter)
+
+    def _after_solve(self, fitted):
+        bad = [p for p, f in enumerate(fitted) if not (np.isfinite(f.dual_coef_dense_).all() and np.isfinite(f.intercept_).all())]
+        if bad:
+            raise ValueError("KernelSVMGroup: the nu-SVC solver returned non-finite coefficients in problems %s (libsvm's r <= 0: r = %s, "
+                             "nu = %s): nu does not suit them" % (bad, [fitted[p].r_ for p in bad], [self._nus[p] for p in bad] if self._nus else None))

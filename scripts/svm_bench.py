@@ -17,7 +17,8 @@ same stages, against the matching SVC / NuSVC (profiles/svm_kinds_bench.txt); sv
 times G fits and scores through one RBFSVMGroup (grouped launches) against the same G problems through G RBFSVM objects one
 after the other, in the same process and by the same scheme (warm-up, medians, stages in passes of their own; scikit-learn is not
 run).  Problem f takes its training fold from np.arange(len(y)) % 6 != f % 6, so the problems hold different rows.  One JSON
-line per size with both totals, the per-stage times and their ratios single / grouped (profiles/svm_group_bench.txt)."""
+line per size with both totals, the per-stage times and their ratios single / grouped (profiles/svm_group_bench.txt).  With
+--classifier KIND the two sides are one KernelSVMGroup and G KernelSVM objects of that kind (profiles/svm_kind_group_bench.txt)."""
 import argparse
 import json
 import os
@@ -28,7 +29,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from mr_gan_amd import KernelSVM, RBFSVM, RBFSVMGroup, synthetic_mreo  # noqa: E402
+from mr_gan_amd import KernelSVM, KernelSVMGroup, RBFSVM, RBFSVMGroup, synthetic_mreo  # noqa: E402
 from mr_gan_amd.mr_svm import CLASSIFIERS  # noqa: E402
 
 
@@ -39,13 +40,12 @@ def main():
     ap.add_argument("--sklearn-repeats", type=int, default=3, help="repeats of the CPU side (1 at 6000 rows: one fit is tens of seconds)")
     ap.add_argument("--d", type=int, default=1200)
     ap.add_argument("--group", type=int, nargs="?", const=6, default=None,
-                    help="time G problems through RBFSVMGroup against G RBFSVM objects instead (G = 6 where not given)")
+                    help="time G problems through RBFSVMGroup against G RBFSVM objects instead (G = 6 where not given); with "
+                         "--classifier, through KernelSVMGroup against G KernelSVM objects")
     ap.add_argument("--classifier", choices=sorted(CLASSIFIERS), default='svc-rbf')
     args = ap.parse_args()
     if args.group is not None and args.group < 1:
         ap.error("--group needs at least one problem")
-    if args.group is not None and args.classifier != 'svc-rbf':
-        ap.error("--group times RBFSVMGroup: --classifier svc-rbf only")
     if not torch.cuda.is_available():
         raise SystemExit("svm_bench needs a GPU: nothing is measured without one")
     from sklearn import preprocessing
@@ -61,7 +61,11 @@ def main():
         for n in args.labeled:
             per = n // 6
             probs = [(np.concatenate([a[ya == c][:per] for c in range(6)]), np.repeat(np.arange(6), per), xt, yt) for a, ya, xt, yt in folds]
-            print(json.dumps(measure_group(args, probs)))
+            if args.classifier == 'svc-rbf':
+                print(json.dumps(measure_group(args, probs)))
+            else:
+                print(json.dumps(dict(measure_group(args, probs, lambda: KernelSVMGroup(kernel=kernel, nu=nu, C=1.0, gamma='auto'),
+                                                    lambda: KernelSVM(kernel=kernel, nu=nu, C=1.0, gamma='auto')), classifier=args.classifier)))
             sys.stdout.flush()
         return
     tr = np.arange(len(y)) % 6 != 0
@@ -124,11 +128,11 @@ def measure(args, SVC, xl, yl, xt, yt, make_hip=None, make_sk=None):
                 gram_gflop=round(2e-9 * n * n * d, 2))
 
 
-def measure_group(args, probs):
+def measure_group(args, probs, make_group=None, make_single=None):
     G = len(probs)
     xs, ys, xts, yts = [list(v) for v in zip(*probs)]
-    group = RBFSVMGroup(C=1.0, gamma='auto')
-    singles = [RBFSVM(C=1.0, gamma='auto') for _ in range(G)]
+    group = RBFSVMGroup(C=1.0, gamma='auto') if make_group is None else make_group()
+    singles = [RBFSVM(C=1.0, gamma='auto') if make_single is None else make_single() for _ in range(G)]
     group.fit(xs, ys).score(xts, yts)                   # warm-up of both sides: code objects, allocator
     for clf, x, y_, xt, yt in zip(singles, xs, ys, xts, yts):
         clf.fit(x, y_).score(xt, yt)
@@ -180,11 +184,11 @@ def measure_group(args, probs):
     for k in ('fit', 'score') + keys:
         out[k + '_ratio_single_over_group'] = round(float(np.median((t if k in ('fit', 'score') else st)['single_' + k])
                                                           / np.median((t if k in ('fit', 'score') else st)['group_' + k])), 2)
-    most = max(int(group[p].n_iter_.max()) for p in range(G))
+    most = max(1, max(int(group[p].n_iter_.max()) for p in range(G)))      # a nu start point can be optimal: 0 updates
     out.update(iterations_max_per_problem=[int(group[p].n_iter_.max()) for p in range(G)],
                group_solve_us_per_update_of_slowest_pair=round(1e6 * float(np.median(st['group_solve'])) / most, 3),
                single_solve_us_per_update_of_slowest_pairs=round(1e6 * float(np.median(st['single_solve']))
-                                                                 / sum(int(c.n_iter_.max()) for c in singles), 3),
+                                                                 / max(1, sum(int(c.n_iter_.max()) for c in singles)), 3),
                gram_mbytes_group=round(sum(4e-6 * len(v) ** 2 for v in ys), 1), test_error=[round(1.0 - a, 6) for a in g_acc])
     return out
 
