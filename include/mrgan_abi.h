@@ -331,6 +331,49 @@ int mrgan_svm_kernel_matrix_group(int32_t kernel, const mrgan_svm_gram_item* ite
 int mrgan_svm_solve_nu_group(const mrgan_svm_solve_nu_item* items_host, int32_t count, int32_t num_classes, double tol,
                              int32_t max_iter, mrgan_stream stream);
 
+/* PCA pre-stage (others/wganlpctsemi.py:129-139, pcaScale: decomposition.PCA(n_components)) on the device.  No handle and no
+ * state; everything runs on the caller's stream; row pitches in elements; float32 rows unless stated.  Every entry's results
+ * are bit-identical from run to run (no float atomics).
+ *   mrgan_pca_mean        mean_dev[d]: the column means of the n rows of x_dev, summed in float64 in a fixed order and rounded
+ *                         once.
+ *   mrgan_pca_covariance  cov_dev[d x d] = (X - mean)^T (X - mean) / (n - 1), n >= 2, d <= MRGAN_PCA_MAX_FEATURES: the k-ordered
+ *                         fp32 matrix-core chain of mrgan_svm_kernel_matrix over the ROWS, the mean subtracted from the operands.
+ *                         The row range is split into slabs that are summed in a fixed order; cov[i, j] and cov[j, i] are written
+ *                         from one value.  work_dev: mrgan_pca_covariance_workspace_bytes(n, d) bytes (-1: n or d out of range).
+ *                         Nothing outside the d x d window is written.
+ *   mrgan_pca_eig         the k leading eigenpairs of the symmetric cov_dev by block (subspace) iteration, 1 <= k <=
+ *                         MRGAN_PCA_MAX_COMPONENTS, with a block of p = min(d, k + MRGAN_PCA_GUARD) rows started from q0_dev [p x d]
+ *                         (any full-rank rows).  One iteration: Y = Q C (mrgan_svm_kernel_matrix's linear kernel), the Rayleigh
+ *                         quotients theta_j = q_j . y_j and residuals |y_j - theta_j q_j|_2 in float64, then Q <- the orthonormal
+ *                         rows Lambda^-1/2 V^T Y from the eigen-decomposition Y Y^T = V Lambda V^T (cyclic Jacobi in one
+ *                         workgroup), sorted by descending Lambda; directions with Lambda_j <= 2^-40 Lambda_1 become zero rows.
+ *                         It stops when max_{j<k} residual_j <= tol * max_{j<k} theta_j, or after max_iter products (the outputs
+ *                         are written either way; the caller compares).  The call SYNCHRONISES the stream once per iteration to
+ *                         read 2 p + 1 doubles; nothing waits on the device.  components_dev [k x d]: rows by descending theta,
+ *                         each with its largest-magnitude entry positive (first index on ties); values_host, residuals_host [k]
+ *                         float64 and iters_host (products taken) are HOST memory.  work_dev: mrgan_pca_eig_workspace_bytes(d, k)
+ *                         bytes, 8-byte aligned.  Status MRGAN_PCA_RANK_DEFICIENT: fewer than k directions survived
+ *                         ("numerical rank below n_components").
+ *   mrgan_pca_transform   out_dev[m x k] = (X - mean) W^T for the k rows of components_dev; a row's values depend on that row
+ *                         alone, so working the rows in chunks changes no bit.
+ *   mrgan_pca_inverse_transform  out_dev[m x d] = Z W + mean. */
+#define MRGAN_PCA_MAX_COMPONENTS 64
+#define MRGAN_PCA_GUARD 16
+#define MRGAN_PCA_MAX_FEATURES 4096
+#define MRGAN_PCA_RANK_DEFICIENT (-4)
+int mrgan_pca_mean(const float* x_dev, int64_t ld_x, int64_t n, int64_t d, float* mean_dev, mrgan_stream stream);
+int64_t mrgan_pca_covariance_workspace_bytes(int64_t n, int64_t d);
+int mrgan_pca_covariance(const float* x_dev, int64_t ld_x, int64_t n, int64_t d, const float* mean_dev, float* cov_dev, int64_t ld_cov,
+                         void* work_dev, int64_t work_bytes, mrgan_stream stream);
+int64_t mrgan_pca_eig_workspace_bytes(int64_t d, int64_t k);
+int mrgan_pca_eig(const float* cov_dev, int64_t ld_cov, int64_t d, int64_t k, const float* q0_dev, int64_t ld_q0, int64_t p, double tol,
+                  int32_t max_iter, void* work_dev, int64_t work_bytes, float* components_dev, int64_t ld_w, double* values_host,
+                  double* residuals_host, int32_t* iters_host, mrgan_stream stream);
+int mrgan_pca_transform(const float* x_dev, int64_t ld_x, int64_t m, int64_t d, const float* mean_dev, const float* components_dev,
+                        int64_t ld_w, int64_t k, float* out_dev, int64_t ld_out, mrgan_stream stream);
+int mrgan_pca_inverse_transform(const float* z_dev, int64_t ld_z, int64_t m, int64_t k, const float* components_dev, int64_t ld_w,
+                                int64_t d, const float* mean_dev, float* out_dev, int64_t ld_out, mrgan_stream stream);
+
 /* one iteration of the hot loop (mr_gan.py:204-213): D step then G step */
 int mrgan_train_pair(mrgan_handle* h, const mrgan_disc_args* d, const mrgan_gen_args* g, mrgan_stream stream);
 /* For hosts that drive the phases themselves (data parallel) and know that the next mrgan_disc_step is followed by a

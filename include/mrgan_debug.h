@@ -289,6 +289,17 @@ int mrgan_debug_svm_gram_group(const mrgan_svm_gram_item* items_host, int32_t co
 int mrgan_debug_svm_kernel_matrix_group(int32_t kernel, const mrgan_svm_gram_item* items_host, int32_t count, int64_t d, float gamma,
                                         int32_t tile, mrgan_stream stream);
 
+/* mrgan_pca_covariance with the block tile (64 or 128; 0 = the shape's own choice) and the number of row ranges (0 = the shape's
+ * own choice; more than one per 16 rows is clamped) forced; the workspace query takes the same two */
+int64_t mrgan_debug_pca_covariance_workspace_bytes(int64_t n, int64_t d, int32_t tile, int32_t split);
+int mrgan_debug_pca_covariance(const float* x_dev, int64_t ld_x, int64_t n, int64_t d, const float* mean_dev, float* cov_dev, int64_t ld_cov,
+                               void* work_dev, int64_t work_bytes, int32_t tile, int32_t split, mrgan_stream stream);
+/* the orthonormalisation stage of mrgan_pca_eig alone: y_dev [p x d] -> q_dev [p x d], orthonormal rows spanning the rows of Y,
+ * sorted by descending lam_dev [p] (float64: the eigenvalues of Y Y^T); rows with lam_j <= 2^-40 lam_1 are zero.  p <= 80;
+ * work_dev: what mrgan_pca_eig needs for a block of p rows, 2 p p + 3 p + 2 doubles and 2 p d floats, 8-byte aligned */
+int mrgan_debug_pca_orthonormalize(const float* y_dev, int64_t ld_y, int64_t p, int64_t d, void* work_dev, int64_t work_bytes, float* q_dev,
+                                   int64_t ld_q, double* lam_dev, mrgan_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

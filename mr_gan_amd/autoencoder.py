@@ -82,26 +82,17 @@ class Autoencoder(Front):
             return self.engine.ae_reconstruct(self._dev(X), want_out=False)[1]
 
 
-def mr_gan_autoencoder(X, y, percentlabeled=50, percentunlabeled=None, epochs=100, trainTestSets=None, encoderNodes=(128, 64, 16),
-                       ae_epochs=100, verbose=False, batch_size=50, ae_batch_size=32, dtype='float32', seed=None, device='cuda:0',
-                       noise='irwin-hall', num_classes=None):
-    """mr_gan() of others/mr_gan_autoencoder.py: split and standard-scale (the scaler fitted on the training rows), fit the
-    autoencoder on X_train for ae_epochs epochs at batch ae_batch_size with X_test as validation data, replace both sets by
-    their codes (not rescaled: the reference does not), then the unchanged GAN training of mr_gan() on the codes.
-    Returns the test ACCURACY over the whole test set, as the reference's function does (others/mr_gan_autoencoder.py:212,
-    :285) -- mr_gan() returns the test error."""
-    E.noise_flags(noise)                                           # an unknown value fails before any data is touched
-    encoder_widths(encoderNodes)
+def gan_on_codes(make_codes, X, y, percentlabeled, percentunlabeled, epochs, trainTestSets, verbose, batch_size, dtype, seed, device, noise,
+                 num_classes):
+    """what mr_gan_autoencoder and mr_gan_pca (pca.py) share: split and standard-scale (the scaler fitted on the training rows),
+    replace both sets by make_codes(X_train, X_test, rs) -> (codes of X_train, codes of X_test), not rescaled, print their
+    shapes, then the unchanged GAN training of mr_gan() on the codes -> the test ACCURACY over the whole test set"""
     rs = np.random.RandomState(seed if seed is not None else np.random.randint(1 << 31))
     num_classes = resolve_num_classes(num_classes)
     sets = train_test_sets(X, y, trainTestSets, rs, num_classes)
 
-    def codes(X_train, X_test):                                    # others/mr_gan_autoencoder.py:109-140
-        ae = Autoencoder(X_train.shape[1], encoder_nodes=encoderNodes, batch_size=ae_batch_size, dtype=dtype,
-                         seed=int(rs.randint(1 << 31)), device=device)
-        ae.fit(X_train, epochs=ae_epochs, validation_data=X_test, verbose=1 if verbose else 0)
-        out = ae.encode(X_train), ae.encode(X_test)
-        ae.close()
+    def codes(X_train, X_test):
+        out = make_codes(X_train, X_test, rs)
         print_lines([(np.shape(out[0]), np.shape(out[1]))], verbose)
         return out
     x_labeled, y_labeled, x_unlabeled, X_train, X_test, y_test, lines = prologue(sets, percentlabeled, percentunlabeled, rs, num_classes,
@@ -115,3 +106,25 @@ def mr_gan_autoencoder(X, y, percentlabeled=50, percentunlabeled=None, epochs=10
     print_lines(_test_error_line(testerror, [rec['test_err'] for rec in hist]), verbose)
     model.close()
     return 1.0 - testerror
+
+
+def mr_gan_autoencoder(X, y, percentlabeled=50, percentunlabeled=None, epochs=100, trainTestSets=None, encoderNodes=(128, 64, 16),
+                       ae_epochs=100, verbose=False, batch_size=50, ae_batch_size=32, dtype='float32', seed=None, device='cuda:0',
+                       noise='irwin-hall', num_classes=None):
+    """mr_gan() of others/mr_gan_autoencoder.py: split and standard-scale (the scaler fitted on the training rows), fit the
+    autoencoder on X_train for ae_epochs epochs at batch ae_batch_size with X_test as validation data, replace both sets by
+    their codes (not rescaled: the reference does not), then the unchanged GAN training of mr_gan() on the codes.
+    Returns the test ACCURACY over the whole test set, as the reference's function does (others/mr_gan_autoencoder.py:212,
+    :285) -- mr_gan() returns the test error."""
+    E.noise_flags(noise)                                           # an unknown value fails before any data is touched
+    encoder_widths(encoderNodes)
+
+    def codes(X_train, X_test, rs):                                # others/mr_gan_autoencoder.py:109-140
+        ae = Autoencoder(X_train.shape[1], encoder_nodes=encoderNodes, batch_size=ae_batch_size, dtype=dtype,
+                         seed=int(rs.randint(1 << 31)), device=device)
+        ae.fit(X_train, epochs=ae_epochs, validation_data=X_test, verbose=1 if verbose else 0)
+        out = ae.encode(X_train), ae.encode(X_test)
+        ae.close()
+        return out
+    return gan_on_codes(codes, X, y, percentlabeled, percentunlabeled, epochs, trainTestSets, verbose, batch_size, dtype, seed, device, noise,
+                        num_classes)

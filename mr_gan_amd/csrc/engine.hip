@@ -1325,6 +1325,51 @@ int mrgan_svm_solve_nu_group(const mrgan_svm_solve_nu_item* items_host, int32_t 
     return r ? svm_group_fail(r, msg, item) : 0;
 }
 
+int mrgan_pca_mean(const float* x_dev, int64_t ld_x, int64_t n, int64_t d, float* mean_dev, mrgan_stream stream) {
+    const char* msg = "";
+    const int r = launch_pca_mean(x_dev, (long)ld_x, (long)n, (long)d, mean_dev, (hipStream_t)stream, &msg);
+    return r ? fail(r, "%s", msg) : 0;
+}
+
+int64_t mrgan_pca_covariance_workspace_bytes(int64_t n, int64_t d) { return pca_covariance_workspace_bytes((long)n, (long)d, 0, 0); }
+
+int mrgan_pca_covariance(const float* x_dev, int64_t ld_x, int64_t n, int64_t d, const float* mean_dev, float* cov_dev, int64_t ld_cov,
+                         void* work_dev, int64_t work_bytes, mrgan_stream stream) {
+    const char* msg = "";
+    const int r = launch_pca_covariance(x_dev, (long)ld_x, (long)n, (long)d, mean_dev, cov_dev, (long)ld_cov, work_dev, (long)work_bytes, 0, 0,
+                                        (hipStream_t)stream, &msg);
+    return r ? fail(r, "%s", msg) : 0;
+}
+
+int64_t mrgan_pca_eig_workspace_bytes(int64_t d, int64_t k) {
+    return k < 1 || k > PCA_MAX_COMPONENTS ? -1 : pca_eig_workspace_bytes((long)d, (long)std::min<int64_t>(d, k + PCA_GUARD));
+}
+
+int mrgan_pca_eig(const float* cov_dev, int64_t ld_cov, int64_t d, int64_t k, const float* q0_dev, int64_t ld_q0, int64_t p, double tol,
+                  int32_t max_iter, void* work_dev, int64_t work_bytes, float* components_dev, int64_t ld_w, double* values_host,
+                  double* residuals_host, int32_t* iters_host, mrgan_stream stream) {
+    const char* msg = "";
+    const int r = launch_pca_eig(cov_dev, (long)ld_cov, (long)d, (long)k, q0_dev, (long)ld_q0, (long)p, tol, max_iter, work_dev, (long)work_bytes,
+                                 components_dev, (long)ld_w, values_host, residuals_host, iters_host, (hipStream_t)stream, &msg);
+    return r ? fail(r, "%s", msg) : 0;
+}
+
+int mrgan_pca_transform(const float* x_dev, int64_t ld_x, int64_t m, int64_t d, const float* mean_dev, const float* components_dev,
+                        int64_t ld_w, int64_t k, float* out_dev, int64_t ld_out, mrgan_stream stream) {
+    const char* msg = "";
+    const int r = launch_pca_transform(x_dev, (long)ld_x, (long)m, (long)d, mean_dev, components_dev, (long)ld_w, (long)k, out_dev, (long)ld_out,
+                                       (hipStream_t)stream, &msg);
+    return r ? fail(r, "%s", msg) : 0;
+}
+
+int mrgan_pca_inverse_transform(const float* z_dev, int64_t ld_z, int64_t m, int64_t k, const float* components_dev, int64_t ld_w,
+                                int64_t d, const float* mean_dev, float* out_dev, int64_t ld_out, mrgan_stream stream) {
+    const char* msg = "";
+    const int r = launch_pca_inverse_transform(z_dev, (long)ld_z, (long)m, (long)k, components_dev, (long)ld_w, (long)d, mean_dev, out_dev,
+                                               (long)ld_out, (hipStream_t)stream, &msg);
+    return r ? fail(r, "%s", msg) : 0;
+}
+
 int mrgan_sup_step(mrgan_handle* h, const mrgan_sup_args* a, float* out2, mrgan_stream stream) {
     if (!h || !a || !a->x_dev || !a->labels_dev) return fail(-1, "sup_step: x and labels are required");
     if (refuse_ae(h, "sup_step") || refuse_group(h, "sup_step")) return -3;

@@ -714,4 +714,24 @@ int mrgan_debug_svm_kernel_matrix_group(int32_t kernel, const mrgan_svm_gram_ite
     return r ? svm_group_fail(r, msg, item) : 0;
 }
 
+int64_t mrgan_debug_pca_covariance_workspace_bytes(int64_t n, int64_t d, int32_t tile, int32_t split) {
+    return pca_covariance_workspace_bytes((long)n, (long)d, tile, split);
+}
+
+int mrgan_debug_pca_covariance(const float* x_dev, int64_t ld_x, int64_t n, int64_t d, const float* mean_dev, float* cov_dev, int64_t ld_cov,
+                               void* work_dev, int64_t work_bytes, int32_t tile, int32_t split, mrgan_stream stream) {
+    const char* msg = "";
+    const int r = launch_pca_covariance(x_dev, (long)ld_x, (long)n, (long)d, mean_dev, cov_dev, (long)ld_cov, work_dev, (long)work_bytes, tile,
+                                        split, (hipStream_t)stream, &msg);
+    return r ? fail(r, "%s", msg) : 0;
+}
+
+int mrgan_debug_pca_orthonormalize(const float* y_dev, int64_t ld_y, int64_t p, int64_t d, void* work_dev, int64_t work_bytes, float* q_dev,
+                                   int64_t ld_q, double* lam_dev, mrgan_stream stream) {
+    const char* msg = "";
+    const int r = launch_pca_orthonormalize(y_dev, (long)ld_y, (long)p, (long)d, work_dev, (long)work_bytes, q_dev, (long)ld_q, lam_dev,
+                                            (hipStream_t)stream, &msg);
+    return r ? fail(r, "%s", msg) : 0;
+}
+
 }  // extern "C"

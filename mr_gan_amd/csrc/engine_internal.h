@@ -17,6 +17,7 @@
 #include "chain.h"
 #include "head_wide.h"
 #include "logmel.h"
+#include "pca.h"
 #include "svm.h"
 #include "gemm.h"
 

@@ -41,7 +41,14 @@ EXPORTS = [
     "mrgan_svm_gram_group", "mrgan_svm_solve_group", "mrgan_svm_decide_group", "mrgan_debug_svm_gram_group",
     "mrgan_svm_kernel_matrix", "mrgan_svm_solve_nu", "mrgan_debug_svm_kernel_matrix",
     "mrgan_svm_kernel_matrix_group", "mrgan_svm_solve_nu_group", "mrgan_debug_svm_kernel_matrix_group",
+    "mrgan_pca_mean", "mrgan_pca_covariance_workspace_bytes", "mrgan_pca_covariance", "mrgan_pca_eig_workspace_bytes", "mrgan_pca_eig",
+    "mrgan_pca_transform", "mrgan_pca_inverse_transform",
+    "mrgan_debug_pca_covariance_workspace_bytes", "mrgan_debug_pca_covariance", "mrgan_debug_pca_orthonormalize",
 ]
+PCA_MAX_COMPONENTS = 64       # MRGAN_PCA_MAX_COMPONENTS
+PCA_GUARD = 16                # MRGAN_PCA_GUARD: extra rows of the iterated block
+PCA_MAX_FEATURES = 4096       # MRGAN_PCA_MAX_FEATURES: the covariance is one d x d buffer
+PCA_RANK_DEFICIENT = -4       # MRGAN_PCA_RANK_DEFICIENT: mrgan_pca_eig's "numerical rank below n_components"
 SVM_MAX_PAIR = 2048           # MRGAN_SVM_MAX_PAIR: rows of one one-vs-one problem
 SVM_MAX_CLASSES = 32
 SVM_MAX_GROUP = 16            # MRGAN_SVM_MAX_GROUP: problems of one grouped launch
@@ -289,12 +296,60 @@ def load_library(path=None):
     lib.mrgan_svm_kernel_matrix_group.argtypes = [C.c_int32, C.POINTER(SvmGramItem), C.c_int32, C.c_int64, C.c_float, C.c_void_p]
     lib.mrgan_debug_svm_kernel_matrix_group.argtypes = [C.c_int32, C.POINTER(SvmGramItem), C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_void_p]
     lib.mrgan_svm_solve_nu_group.argtypes = [C.POINTER(SvmSolveNuItem), C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p]
+    # the handle-free PCA entries, declared for the same reason; the workspace queries return a byte count
+    cov = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+    lib.mrgan_pca_mean.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.mrgan_pca_covariance_workspace_bytes.argtypes, lib.mrgan_pca_covariance_workspace_bytes.restype = [C.c_int64, C.c_int64], C.c_int64
+    lib.mrgan_debug_pca_covariance_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32]
+    lib.mrgan_debug_pca_covariance_workspace_bytes.restype = C.c_int64
+    lib.mrgan_pca_covariance.argtypes = cov + [C.c_void_p]
+    lib.mrgan_debug_pca_covariance.argtypes = cov + [C.c_int32, C.c_int32, C.c_void_p]
+    lib.mrgan_pca_eig_workspace_bytes.argtypes, lib.mrgan_pca_eig_workspace_bytes.restype = [C.c_int64, C.c_int64], C.c_int64
+    lib.mrgan_pca_eig.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_void_p,
+                                  C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mrgan_debug_pca_orthonormalize.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                   C.c_void_p, C.c_void_p]
+    lib.mrgan_pca_transform.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                        C.c_int64, C.c_void_p]
+    lib.mrgan_pca_inverse_transform.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                                C.c_void_p, C.c_int64, C.c_void_p]
     _lib = lib
     return lib
 
 
 class MrganError(RuntimeError):
-    pass
+    code = None              # the entry's status where a library call raised it
+
+
+class DeviceCalls:
+    """what the estimators over the handle-free entries share (svm.py, pca.py): the library call on the current stream of
+    self.device, the per-stage device-event timer (self.time_stages, self.times_) and the refusal to run without a GPU"""
+    _gpu_only = ('RBFSVM', 'mrgan_svm_*')                  # who refuses, and the entries it needs
+
+    def _call(self, name, *args):
+        lib = load_library()
+        with torch.cuda.device(self.device):
+            rc = getattr(lib, name)(*args, torch.cuda.current_stream(self.device).cuda_stream)
+        if rc != 0:
+            err = MrganError("%s failed (%d): %s" % (name, rc, lib.mrgan_last_error().decode()))
+            err.code = rc
+            raise err
+
+    def _timed(self, key, fn):
+        if not self.time_stages:
+            return fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(torch.cuda.current_stream(self.device))
+        out = fn()
+        b.record(torch.cuda.current_stream(self.device))
+        b.synchronize()
+        self.times_[key] = self.times_.get(key, 0.0) + a.elapsed_time(b) * 1e-3
+        return out
+
+    def _require_gpu(self):
+        load_library()
+        if not torch.cuda.is_available():
+            raise RuntimeError("%s runs on the GPU only (%s); no HIP device is visible and there is no CPU fallback" % self._gpu_only)
 
 
 def _check(rc):

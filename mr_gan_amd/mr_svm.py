@@ -3,7 +3,10 @@ RBF-kernel SVC (C = 1) trained on the labeled subset only.  By default on scikit
 --backend hip fits and scores with mr_gan_amd.svm.RBFSVM (csrc/svm.hip: Gram matrix, SMO solver and vote on the GPU).
 
     python -m mr_gan_amd.mr_svm --tables 2 4 [-v] [--backend {sklearn,hip}] [--group-folds]
-                                [--classifier {svc-rbf,svc-linear,nu-rbf,nu-linear}]
+                                [--classifier {svc-rbf,svc-linear,nu-rbf,nu-linear}] [--pca N]
+
+--pca N puts N principal components of the scaled sets in front of the classifier (others/wganlpctsemi.py:129-139 pcaScale), on
+either backend (hip: mr_gan_amd.pca.PCA, fitted on each fold's training rows).
 
 --classifier picks another libsvm classifier of the reference's wider grid (others/wganlpctsemi.py:205-208): SVC or NuSVC
 (nu = 0.5) with the RBF or the linear kernel, on either backend (hip: mr_gan_amd.svm.KernelSVM).
@@ -24,6 +27,7 @@ import numpy as np
 
 from mr_gan_amd.data import prologue, resolve_num_classes, train_test_sets
 from mr_gan_amd.mr_gan import MODALITIES, dataset, print_lines
+from mr_gan_amd.pca import pca_transform_hook
 from mr_gan_amd.svm import KernelSVM, KernelSVMGroup, RBFSVM, RBFSVMGroup
 
 
@@ -34,16 +38,19 @@ NU = 0.5
 CLASSIFIERS = {'svc-rbf': ('rbf', None), 'svc-linear': ('linear', None), 'nu-rbf': ('rbf', NU), 'nu-linear': ('linear', NU)}
 
 
-def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None, backend='sklearn', classifier='svc-rbf'):
+def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None, backend='sklearn', classifier='svc-rbf', pca=0):
+    """pca > 0: the classifier sees that many principal components of the standard-scaled sets, fitted on the training rows
+    (others/wganlpctsemi.py:129-139 pcaScale, whose SVM grid takes PCA in {0, 10}), computed by the chosen backend"""
     if backend not in BACKENDS:
         raise ValueError("backend must be one of %s, got %r" % (BACKENDS, backend))
     if classifier not in CLASSIFIERS:
         raise ValueError("classifier must be one of %s, got %r" % (sorted(CLASSIFIERS), classifier))
     kernel, nu = CLASSIFIERS[classifier]
+    transform = pca_transform_hook(pca, backend)
     rs = np.random.RandomState(seed if seed is not None else np.random.randint(1 << 31))     # mr_svm.py:79 is unseeded
     num_classes = resolve_num_classes(None)
     sets = train_test_sets(X, y, trainTestSets, rs, num_classes)   # mr_svm.py:82-89
-    x_labeled, y_labeled, _, _, X_test, y_test, lines = prologue(sets, percentlabeled, None, rs, num_classes)
+    x_labeled, y_labeled, _, _, X_test, y_test, lines = prologue(sets, percentlabeled, None, rs, num_classes, transform=transform)
     print_lines(lines, verbose)
     # mr_svm.py:106 is SVC(kernel='rbf', C=1.0) under the scikit-learn of 2017 (Keras 2.0.9 era, README.md:43-48), whose default
     # kernel width was gamma='auto' = 1 / n_features.  scikit-learn >= 0.22 defaults to 'scale' (1 / (n_features * X.var())),
@@ -65,19 +72,21 @@ def mr_svm(X, y, percentlabeled=50, trainTestSets=None, verbose=False, seed=None
     return testerror
 
 
-def mr_svm_folds(sets, percentlabeled=50, verbose=False, seed=None, classifier='svc-rbf'):
+def mr_svm_folds(sets, percentlabeled=50, verbose=False, seed=None, classifier='svc-rbf', pca=0):
     """mr_svm(backend='hip') of every [X_train, X_test, y_train, y_test] of `sets` (the folds of a table-2 cell, the objects of a
     table-4 cell) as one RBFSVMGroup -- for another classifier of CLASSIFIERS one KernelSVMGroup -> their test errors.  Fold f
     runs mr_svm()'s prologue from RandomState(seed + f), the rule of mr_nn_folds: the errors are those of
-    mr_svm(None, None, trainTestSets=sets[f], seed=seed + f, backend='hip', classifier=classifier)."""
+    mr_svm(None, None, trainTestSets=sets[f], seed=seed + f, backend='hip', classifier=classifier, pca=pca); pca > 0 is one device
+    PCA fit per fold, in turn, inside the fold's prologue."""
     if classifier not in CLASSIFIERS:
         raise ValueError("classifier must be one of %s, got %r" % (sorted(CLASSIFIERS), classifier))
     kernel, nu = CLASSIFIERS[classifier]
+    transform = pca_transform_hook(pca, 'hip')
     base = int(seed if seed is not None else np.random.randint(1 << 30))
     num_classes = resolve_num_classes(None)
     folds = []
     for f, s in enumerate(sets):
-        folds.append(prologue(s, percentlabeled, None, np.random.RandomState(base + f), num_classes))
+        folds.append(prologue(s, percentlabeled, None, np.random.RandomState(base + f), num_classes, transform=transform))
         print_lines(folds[-1][-1], verbose)
     x_labeled, y_labeled, _, _, X_test, y_test, _ = zip(*folds)
     if classifier == 'svc-rbf':
@@ -162,7 +171,12 @@ def main(argv=None, dataset_fn=dataset, fn=mr_svm, folds_fn=None):
     parser.add_argument('--classifier', choices=sorted(CLASSIFIERS), default='svc-rbf',
                         help="the libsvm classifier of the reference's grid (others/wganlpctsemi.py:205-208): SVC (C = 1) or NuSVC "
                              "(nu = 0.5) with the RBF or the linear kernel; default svc-rbf, the baseline of mr_svm.py")
+    parser.add_argument('--pca', type=int, default=0, metavar='N',
+                        help="fit the classifier on N principal components of the scaled sets (others/wganlpctsemi.py pcaScale; its grid "
+                             "takes 0 and 10), computed by the chosen backend; default 0: no PCA")
     args = parser.parse_args(argv)
+    if args.pca < 0:
+        parser.error('--pca takes a non-negative component count')
     if args.group_folds and args.backend != 'hip':
         parser.error('--group-folds needs --backend hip')
     if args.group_folds and args.classifier != 'svc-rbf':
@@ -173,6 +187,9 @@ def main(argv=None, dataset_fn=dataset, fn=mr_svm, folds_fn=None):
         fn = functools.partial(fn, classifier=args.classifier)
     if args.group_folds and folds_fn is None:
         folds_fn = mr_svm_folds
+    if args.pca:
+        fn = functools.partial(fn, pca=args.pca)
+        folds_fn = functools.partial(folds_fn, pca=args.pca) if folds_fn is not None else None
     hook = folds_fn if args.group_folds else None
     baseline_tables(args.tables, fn, dataset_fn, args.verbose, folds_fn=hook, objects_fn=hook)
 

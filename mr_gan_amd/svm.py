@@ -64,9 +64,9 @@ def _finite_matrix(X, name, d=None):
     return X32
 
 
-class _DeviceSVM:
-    """what RBFSVM and RBFSVMGroup share: the hyper-parameters and their checks, the library call on the current stream and
-    the per-stage device-event timer"""
+class _DeviceSVM(E.DeviceCalls):
+    """what RBFSVM and RBFSVMGroup share: the hyper-parameters and their checks; the library call on the current stream and
+    the per-stage device-event timer are engine.DeviceCalls'"""
 
     def __init__(self, C, gamma, tol, max_iter, device):
         if not (isinstance(gamma, str) and gamma == 'auto') and not (np.isreal(gamma) and np.isfinite(gamma) and gamma > 0):
@@ -78,30 +78,6 @@ class _DeviceSVM:
         self.C, self.gamma, self.tol, self.max_iter, self.device = float(C), gamma, float(tol), int(max_iter), torch.device(device)
         self.times_ = {}                 # seconds of the last fit / predict per stage, filled only while time_stages is set
         self.time_stages = False
-
-    # ---- device plumbing ----
-    def _call(self, name, *args):
-        lib = E.load_library()
-        with torch.cuda.device(self.device):
-            rc = getattr(lib, name)(*args, torch.cuda.current_stream(self.device).cuda_stream)
-        if rc != 0:
-            raise E.MrganError("%s failed (%d): %s" % (name, rc, lib.mrgan_last_error().decode()))
-
-    def _timed(self, key, fn):
-        if not self.time_stages:
-            return fn()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(torch.cuda.current_stream(self.device))
-        out = fn()
-        b.record(torch.cuda.current_stream(self.device))
-        b.synchronize()
-        self.times_[key] = self.times_.get(key, 0.0) + a.elapsed_time(b) * 1e-3
-        return out
-
-    def _require_gpu(self):
-        E.load_library()
-        if not torch.cuda.is_available():
-            raise RuntimeError("RBFSVM runs on the GPU only (mrgan_svm_*); no HIP device is visible and there is no CPU fallback")
 
 
 class _SingleSVM(_DeviceSVM):
